@@ -10,17 +10,31 @@ HBM before the timed region starts.  Batches rotate through several HBM copies
 so the 256 MiB Infinity Cache cannot hold the working set.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5|c4|c6]
-                    [--also c2,c5,c4]
+                    [--dump-outputs DIR] [--full [--also c2,c5,c4] [--repeats R]]
 
-The headline (`value`, `roofline`, `cpu_baseline` at the top level) is the
+The headline (`value`, `ms_per_step` at the top level) is the
 61-state codon configuration C3 (BASELINE.json configs[2]: the largest
 single-GPU configuration and the one the >= 100x target is stated on): 10 000
 sites per GPU, weak scaling -- at N > 1 the global batch has N x 10 000 sites
-(one seed) and rank r uploads dist.shard_range(...) of it.  The other
-configurations ride in the same JSON line under "workloads" (each with its own
-value / ms_per_step / roofline / cpu_baseline): C2 and C5 the same way, and C4
+(one seed) and rank r uploads dist.shard_range(...) of it.
+
+A plain run sets up, warms up, times exactly K steps (one window), writes the
+outputs of the last timed step if --dump-outputs is given, and prints the line.
+Everything else is measured only with --full: the median of R timed windows
+(default 9), the per-kernel event times and the roofline (`kernels_us`,
+`roofline`), the interpreter kernel and the warm code-object cache, the CPU
+baseline (`cpu_baseline`), the paths either side of the hot path (`next_rows`),
+and the other configurations under "workloads" (each with its own value /
+ms_per_step / roofline / cpu_baseline): C2 and C5 the same way as C3, and C4
 as STRONG scaling: the one 1 000 000-site codon batch (seed 3), rank r uploads
 shard_range(1 000 000, r, N) -- at N = 1 the whole million on one GPU.
+
+--dump-outputs DIR writes what a caller of the timed path receives after its
+last timed step (rank 0's block of sites), as float64 arrays: DIR/log_likelihoods.npy
+and DIR/status.npy per site, DIR/totals.npy = (sum of log-likelihoods, zero-probability
+sites, sites) over the whole batch.  The inputs depend only on the arguments (seeded
+synthetic data), so two builds can be compared output for output.  Above 64 MB a
+fixed, seeded sample of the sites is written, with DIR/site_index.npy naming them.
 
 N > 1 is launched by `python -m torch.distributed.run --nproc-per-node N ...`
 (one rank per GPU; RANK / LOCAL_RANK / WORLD_SIZE from the environment).  The
@@ -48,6 +62,7 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 F64_MFMA_DATASHEET_TFLOPS = 78.6    # MI355X datasheet dense FP64 matrix
 ROOFLINE_LAUNCHES = 32         # event-timed launches per kernel after the timed region
 SPINUP_SECONDS = 0.3        # untimed load before the warm-up steps (clock ramp of an idle box)
+DUMP_LIMIT_BYTES = 64 * 2 ** 20     # --dump-outputs: at most this much in all
 
 
 def f64_mfma_peak():
@@ -131,11 +146,23 @@ def cpu_baseline(cfg, gpu_ll, budget_s):
         Q, node_q = ta.rate_matrices(n, cfg['Q_default'])
         oidx = [ta.node_to_index[v] for v in cfg['leaves']]
         mf = max(2, min(m, int(3.0 * out['value'] * (40 if n > 20 else 8))))
+        # at most mf sites and, like the Python loop, about budget_s seconds: chunks of ~1 s
+        # (the C port's speed relative to the Python one differs from host to host, 0.2x-2x)
         t0 = time.perf_counter()
-        llc, _ = oracle_c.batch_loglik_faithful(ta.indices, ta.indptr, Q, node_q,
-                                                ta.branch_lengths(), oidx,
-                                                dense[:mf], cfg['root_distn'])
-        out['c_port_faithful_sites_per_s'] = mf / (time.perf_counter() - t0)
+        parts, done_c, chunk = [], 0, 2
+        while done_c < mf:
+            k = min(chunk, mf - done_c)
+            parts.append(oracle_c.batch_loglik_faithful(ta.indices, ta.indptr, Q, node_q,
+                                                        ta.branch_lengths(), oidx,
+                                                        dense[done_c:done_c + k],
+                                                        cfg['root_distn'])[0])
+            done_c += k
+            el = time.perf_counter() - t0
+            if el > budget_s:
+                break
+            chunk = max(1, int(done_c / el))
+        out['c_port_faithful_sites_per_s'] = done_c / (time.perf_counter() - t0)
+        llc, mf = np.concatenate(parts), done_c
         t0 = time.perf_counter()
         lla, _ = oracle_c.batch_loglik(ta.indices, ta.indptr, esd, oidx, dense,
                                        cfg['root_distn'])
@@ -195,9 +222,28 @@ def shard_config(name, rank, world, sites):
     return cfg, total
 
 
+def dump_outputs(path, ll, status, totals):
+    """--dump-outputs: the per-site log-likelihoods and status codes and the batch totals
+    of the last timed step, as float64 .npy files under `path`.  A block of sites too large
+    for DUMP_LIMIT_BYTES is written as a fixed, seeded sample (site_index.npy)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    cap = (DUMP_LIMIT_BYTES - 2 ** 16) // (3 * 8)      # ll, status, index: 8 bytes each
+    if ll.shape[0] > cap:
+        idx = np.sort(np.random.default_rng(0).choice(ll.shape[0], cap, replace=False))
+        arrays['site_index'] = idx.astype(np.float64)
+        ll, status = ll[idx], status[idx]
+    arrays['log_likelihoods'] = np.asarray(ll, dtype=np.float64)
+    arrays['status'] = np.asarray(status, dtype=np.float64)
+    arrays['totals'] = np.asarray(totals, dtype=np.float64)
+    for key, a in arrays.items():
+        np.save(os.path.join(path, key + '.npy'), a)
+
+
 def run_workload(name, ctx, ctl, rank, world, reduce_kind, steps, warmup, args,
-                 cpu_seconds, interpreter=True):
-    """Run one workload; every rank takes part, rank 0 gets the result dict."""
+                 cpu_seconds, interpreter=True, full=True, dump_dir=None):
+    """Run one workload; every rank takes part, rank 0 gets the result dict.  full=False:
+    only the timed window (no events inside it) and what the headline line needs."""
     from raoteh_amd import synth, device, _lib
     wl = WORKLOADS[name]
     cfg, total_sites = shard_config(name, rank, world, args.sites if name == args.workload
@@ -278,17 +324,18 @@ def run_workload(name, ctx, ctl, rank, world, reduce_kind, steps, warmup, args,
     for j in range(warmup):
         step(j)
     ctx.sync()
-    ll0, st0 = model.fetch_log_likelihoods(batch0)
-    # inside the timed region: HIP events stamped with each kernel's own begin / end
+    ll0 = model.fetch_log_likelihoods(batch0)[0] if full else None
+    # --full, inside the timed region: HIP events stamped with each kernel's own begin / end
     # (hipExtLaunchKernelGGL, on the library's stream) on every 8th launch of each kernel
-    # (timing every launch would cost ~20 us per step)
-    ctx.set_timing(0 if os.environ.get('RAOTEH_BENCH_NO_EVENTS') else 8)
+    # (timing every launch would cost ~20 us per step); a plain run times the steps alone
+    ctx.set_timing(8 if full and not os.environ.get('RAOTEH_BENCH_NO_EVENTS') else 0)
     ctx.reset_timing()
 
     # The timed window -- EXACTLY `steps` steps between barrier + sync on both sides, the
-    # maximum over the ranks -- is run `repeats` times back to back; the line reports the
-    # MEDIAN window (ms_per_step, value) with the fastest and slowest next to it: a single
-    # window of 20 steps is 4 ms of GPU time, and one hiccup of a shared box moves it by 5 %.
+    # maximum over the ranks -- is run `repeats` times back to back (once in a plain run,
+    # 9 times by default with --full); the line reports the MEDIAN window (ms_per_step,
+    # value) with the fastest and slowest next to it: a single window of 20 steps is 4 ms
+    # of GPU time, and one hiccup of a shared box moves it by 5 %.
     windows = []
     enqueue = []
     for rep in range(max(1, args.repeats)):
@@ -320,6 +367,56 @@ def run_workload(name, ctx, ctl, rank, world, reduce_kind, steps, warmup, args,
     else:
         assert totals[2] == total_sites, (totals, total_sites)
     assert np.isfinite(totals[0]) and totals[1] == 0, totals
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, *model.fetch_log_likelihoods(last), totals)
+
+    # the headline fields: all that a plain run reports
+    jit_compile_s = batch0.jit_compile_seconds
+    out = {
+        'value': total_sites * steps / elapsed if wl['scaling'] == 'strong'
+                 else nsites * world * steps / elapsed,
+        'unit': 'sites/s',
+        'steps': steps,
+        'warmup': warmup,
+        'ms_per_step': elapsed / steps * 1e3,
+        'ms_per_step_min': min(windows) / steps * 1e3,
+        'ms_per_step_max': max(windows) / steps * 1e3,
+        'timed_windows': len(windows),
+        'host_enqueue_us_per_step': (t_enq - t0) / steps * 1e6,
+        'scaling': wl['scaling'],
+        'dtype': 'f64',
+        'config': {'workload': '%s: %s' % (
+                       name, wl['desc'] if encoding == 'dense' else
+                       wl['desc'].replace('dense f64 leaf likelihood vectors',
+                                          'uint8 leaf states (compact encoding)')),
+                   'encoding': encoding,
+                   'sites_per_gpu': nsites, 'sites_total': total_sites if wl['scaling'] == 'strong'
+                   else nsites * world,
+                   'states': n, 'leaves': nleaves,
+                   'edges': nedges, 'batches_rotated': len(batches),
+                   'reduce': reduce_kind,
+                   # hiprtc compile of the tree-specialised kernel: once per distinct
+                   # (tree, observed nodes) and context, in rt_sites_create, OUTSIDE the
+                   # timed region; `interpreter_kernel` is what the same batch runs at
+                   # until / without it (an MCMC over topologies lives there)
+                   'spinup_s': SPINUP_SECONDS,
+                   'jit_compile_s': jit_compile_s,
+                   # cold: hiprtc on the background thread (rt_sites_create itself returned
+                   # after upload_and_pack_s); warm: the same kernel for a fresh context, from
+                   # the persistent code-object cache (--full)
+                   'jit_cold_s': jit_compile_s,
+                   'jit_warm_s': None,
+                   'jit_wait_s': jit_wait_s,
+                   'upload_and_pack_s': upload_s,
+                   'interpreter_kernel': None},
+        'total_log_likelihood': float(totals[0]),
+    }
+    if not full:
+        for b in batches:
+            b.close()
+        model.close()
+        return out if rank == 0 else None
+
     sampled = {}
     for key, kid in (('expm', _lib.RT_K_EXPM), ('prune', _lib.RT_K_PRUNE),
                      ('reduce', _lib.RT_K_REDUCE), ('combine', _lib.RT_K_COMBINE)):
@@ -368,7 +465,6 @@ def run_workload(name, ctx, ctl, rank, world, reduce_kind, steps, warmup, args,
         finally:
             ctx.set_option('jit', None)
 
-    jit_compile_s = batch0.jit_compile_seconds
     for b in batches[1:]:
         b.close()
     # what a SECOND process pays for the same kernel: a fresh context (empty in-memory cache)
@@ -443,55 +539,17 @@ def run_workload(name, ctx, ctl, rank, world, reduce_kind, steps, warmup, args,
     if interp is not None:
         interp['frac'] = peak_for(interp['avg_kernel_us'] * 1e-6)
 
-    out = {
-        'value': total_sites * steps / elapsed if wl['scaling'] == 'strong'
-                 else nsites * world * steps / elapsed,
-        'unit': 'sites/s',
-        'steps': steps,
-        'warmup': warmup,
-        'ms_per_step': elapsed / steps * 1e3,
-        'ms_per_step_min': min(windows) / steps * 1e3,
-        'ms_per_step_max': max(windows) / steps * 1e3,
-        'timed_windows': len(windows),
-        'host_enqueue_us_per_step': (t_enq - t0) / steps * 1e6,
-        'scaling': wl['scaling'],
-        'dtype': 'f64',
-        'config': {'workload': '%s: %s' % (
-                       name, wl['desc'] if encoding == 'dense' else
-                       wl['desc'].replace('dense f64 leaf likelihood vectors',
-                                          'uint8 leaf states (compact encoding)')),
-                   'encoding': encoding,
-                   'sites_per_gpu': nsites, 'sites_total': total_sites if wl['scaling'] == 'strong'
-                   else nsites * world,
-                   'states': n, 'leaves': nleaves,
-                   'edges': nedges, 'batches_rotated': len(batches),
-                   'reduce': reduce_kind,
-                   # hiprtc compile of the tree-specialised kernel: once per distinct
-                   # (tree, observed nodes) and context, in rt_sites_create, OUTSIDE the
-                   # timed region; `interpreter_kernel` is what the same batch runs at
-                   # until / without it (an MCMC over topologies lives there)
-                   'spinup_s': SPINUP_SECONDS,
-                   'jit_compile_s': jit_compile_s,
-                   # cold: hiprtc on the background thread (rt_sites_create itself returned
-                   # after upload_and_pack_s); warm: the same kernel for a fresh context, from
-                   # the persistent code-object cache
-                   'jit_cold_s': jit_compile_s,
-                   'jit_warm_s': jit_warm_s,
-                   'jit_wait_s': jit_wait_s,
-                   'upload_and_pack_s': upload_s,
-                   'interpreter_kernel': interp},
-        'roofline': roof,
-        # (expm None: the pruning launch computed the transitions itself -- n <= 4, one launch
-        # per step, kernel name '...,expm>')
-        'kernels_us': {'expm': (expm_ms / expm_cnt * 1e3) if expm_cnt else None,
-                       'prune': first_kernel_s * 1e6,
-                       'reduce': red_ms / max(red_cnt, 1) * 1e3,
-                       'combine': (comb_ms / comb_cnt * 1e3) if comb_cnt else None,
-                       'expm_kernel': expm_name,
-                       'launches_timed': prune_cnt,
-                       'sampled_in_timed_region': sampled},
-        'total_log_likelihood': float(totals[0]),
-    }
+    out['config'].update(jit_warm_s=jit_warm_s, interpreter_kernel=interp)
+    out['roofline'] = roof
+    # (expm None: the pruning launch computed the transitions itself -- n <= 4, one launch
+    # per step, kernel name '...,expm>')
+    out['kernels_us'] = {'expm': (expm_ms / expm_cnt * 1e3) if expm_cnt else None,
+                         'prune': first_kernel_s * 1e6,
+                         'reduce': red_ms / max(red_cnt, 1) * 1e3,
+                         'combine': (comb_ms / comb_cnt * 1e3) if comb_cnt else None,
+                         'expm_kernel': expm_name,
+                         'launches_timed': prune_cnt,
+                         'sampled_in_timed_region': sampled}
     if world == 1 and cpu_seconds > 0 and name != 'c4':
         out['cpu_baseline'] = cpu_baseline(cfg, ll0, cpu_seconds)
         out['speedup_vs_reference_faithful_cpu'] = out['value'] / out['cpu_baseline']['value']
@@ -741,13 +799,15 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--repeats', type=int, default=9,
-                    help='timed windows of --steps steps each; the median one is reported')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='timed windows of --steps steps each; the median one is reported '
+                         '(default: 1, with --full 9)')
     ap.add_argument('--workload', default='c3', choices=sorted(WORKLOADS),
-                    help='the headline workload (top-level value / roofline / cpu_baseline)')
+                    help='the headline workload (top-level value; with --full also roofline / '
+                         'cpu_baseline)')
     ap.add_argument('--also', default=None,
-                    help="comma-separated workloads carried under 'workloads' (default: the "
-                         "other ones of c2, c3, c5, plus c4; '' = none)")
+                    help="--full: comma-separated workloads carried under 'workloads' (default: "
+                         "the other ones of c2, c3, c5, c6, plus c4; '' = none)")
     ap.add_argument('--sites', type=int, default=None,
                     help='sites per GPU of the headline workload (c4: total sites; default: '
                          'the configuration size)')
@@ -758,7 +818,20 @@ def main():
                     help="resident observation encoding of the headline workload: 'dense' f64 "
                          "leaf vectors (8*n bytes per leaf) or 'state' (uint8 per leaf; "
                          "workloads whose leaves are observed states)")
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline: repeated timed windows, '
+                         'per-kernel events and roofline, interpreter kernel, warm code-object '
+                         'cache, CPU baseline, the other workloads and the next rows')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step of the headline workload '
+                         'as DIR/<name>.npy (float64)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit('--steps must be >= 1 and --warmup >= 0')
+    if args.repeats is None:
+        args.repeats = 9 if args.full else 1
+    if args.also and not args.full:
+        sys.exit('--also %s: the other workloads are measured with --full' % args.also)
 
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -776,7 +849,9 @@ def main():
     # a one-GPU box (RCCL refuses two ranks on one device: the host-socket reduce then runs)
     ctx = device.Context(0 if os.environ.get('RAOTEH_BENCH_ONE_DEVICE') else local_rank)
 
-    if args.also is None:
+    if not args.full:
+        also = []
+    elif args.also is None:
         also = [w for w in ('c2', 'c5', 'c6', 'c4') if w != args.workload]
         if args.workload != 'c3':
             also.insert(0, 'c3')
@@ -804,9 +879,9 @@ def main():
         os.dup2(saved_stdout, 1)
         os.close(saved_stdout)
 
-    cpu_s = 0.0 if args.no_cpu_baseline else args.cpu_seconds
+    cpu_s = 0.0 if (args.no_cpu_baseline or not args.full) else args.cpu_seconds
     head = run_workload(args.workload, ctx, ctl, rank, world, reduce_kind, args.steps,
-                        args.warmup, args, cpu_s)
+                        args.warmup, args, cpu_s, full=args.full, dump_dir=args.dump_outputs)
     extra = {}
     for w in also:
         # the carried workloads use their own short fixed step counts (c4: a step is
@@ -817,7 +892,8 @@ def main():
                                 min(cpu_s, 8.0))
     if rank != 0:
         return
-    next_rows = measure_next_rows(ctx) if (world == 1 and also and not args.no_cpu_baseline) else None
+    next_rows = measure_next_rows(ctx) if (args.full and world == 1 and also and
+                                           not args.no_cpu_baseline) else None
 
     out = {
         'metric': 'site log-likelihoods/sec (batched tree pruning)',
@@ -837,14 +913,15 @@ def main():
         'dtype': 'f64',
         'data': 'synthetic',
         'config': head['config'],
-        'roofline': head['roofline'],
-        'kernels_us': head['kernels_us'],
         'total_log_likelihood': head['total_log_likelihood'],
-        'cpu_baseline': head['cpu_baseline'],
     }
-    if head.get('speedup_vs_reference_faithful_cpu') is not None:
-        out['speedup_vs_reference_faithful_cpu'] = head['speedup_vs_reference_faithful_cpu']
-    out['workloads'] = extra
+    if args.full:
+        out['roofline'] = head['roofline']
+        out['kernels_us'] = head['kernels_us']
+        out['cpu_baseline'] = head['cpu_baseline']
+        if head.get('speedup_vs_reference_faithful_cpu') is not None:
+            out['speedup_vs_reference_faithful_cpu'] = head['speedup_vs_reference_faithful_cpu']
+        out['workloads'] = extra
     if next_rows is not None:
         out['next_rows'] = next_rows
     print(json.dumps(out))

@@ -597,18 +597,13 @@ def test_root_halves_source_covers_every_step_once(monkeypatch):
 
 
 def test_pyfelscore_compat_exports_every_name_the_reference_calls():
-    """Container only (the reference tree is not on the GPU box): every ``pyfelscore.<name>``
-    the reference's sampler modules and its p53 example call is exported by the shim."""
+    """Every ``pyfelscore.<name>`` the reference's sampler modules and its p53 example call
+    (tests/golden/pyfelscore_calls.json, tools/gen_golden.py) is exported by the shim."""
     import ast
-    import glob
-    ref = '/root/reference'
-    if not os.path.isdir(ref):
-        pytest.skip('the reference tree is only present in the build container')
-    called = set()
-    for pattern in ('raoteh/sampler/*.py', 'examples/p53/*.py'):
-        for path in glob.glob(os.path.join(ref, pattern)):
-            with open(path, errors='replace') as f:
-                called.update(re.findall(r'pyfelscore\.(\w+)', f.read()))
+    fx = load_golden('pyfelscore_calls')
+    assert fx['patterns'] == ['raoteh/sampler/*.py', 'examples/p53/*.py']
+    called = set(fx['called'])
+    assert called == set(fx['callers']) and all(fx['callers'].values())
     assert {'mcy_get_node_to_pset', 'get_node_to_set', 'tmjp_get_inhomogeneous_mjp',
             'get_lb_transition_matrix', 'mcy_esd_get_node_to_pmap'} <= called
     tree = ast.parse(open(os.path.join(ROOT, 'raoteh_amd', 'pyfelscore_compat.py')).read())

@@ -34,10 +34,12 @@ usage: python tools/gen_golden.py [--out tests/golden]
 from __future__ import annotations
 
 import argparse
+import glob
 import importlib
 import itertools
 import json
 import os
+import re
 import sys
 import time
 import types
@@ -1031,6 +1033,21 @@ def fixture_tmjp_inhomogeneous(mods, ncases=12):
     return dict(cases=cases)
 
 
+def fixture_pyfelscore_calls(mods):
+    """Every ``pyfelscore.<name>`` that the reference's sampler modules and its p53
+    example call, with the files that call it: what raoteh_amd/pyfelscore_compat.py has
+    to export."""
+    patterns = ('raoteh/sampler/*.py', 'examples/p53/*.py')
+    callers = {}
+    for pattern in patterns:
+        for path in sorted(glob.glob(os.path.join(REF, pattern))):
+            with open(path, errors='replace') as f:
+                for name in re.findall(r'pyfelscore\.(\w+)', f.read()):
+                    callers.setdefault(name, set()).add(os.path.relpath(path, REF))
+    return dict(patterns=list(patterns), called=sorted(callers),
+                callers=dict((k, sorted(v)) for k, v in sorted(callers.items())))
+
+
 def fixture_switching(mods, nsites=5):
     """The 122-state "switching" model of examples/p53/liwen.py: MG94 codon process
     (create_mg94, parameters of get_jeff_params_e :273-300) x {reference, default},
@@ -1161,7 +1178,7 @@ def main():
     os.makedirs(args.out, exist_ok=True)
     mods = import_reference()
     meta = dict(generator='tools/gen_golden.py',
-                reference='/root/reference (argriffing/raoteh)',
+                reference='argriffing/raoteh',
                 python=sys.version.split()[0], numpy=np.__version__,
                 scipy=scipy.__version__, networkx=nx.__version__)
     makers = dict(
@@ -1184,6 +1201,7 @@ def main():
         spectral=lambda: fixture_spectral(mods),
         switching=lambda: fixture_switching(mods),
         tmjp_inhomogeneous=lambda: fixture_tmjp_inhomogeneous(mods),
+        pyfelscore_calls=lambda: fixture_pyfelscore_calls(mods),
     )
     only = args.only.split(',') if args.only else list(makers)
     fixtures = dict((name, makers[name]()) for name in only)

@@ -7,7 +7,7 @@ OUT=gpurun_out/sweep_c3.txt
 run() {
   W=$1; shift
   echo "== $W $*" >> $OUT
-  env "$@" python bench.py --workload $W --also '' --steps 30 --warmup 4 --no-cpu-baseline $EXTRA 2>>$OUT | python -c "
+  env "$@" python bench.py --full --workload $W --also '' --steps 30 --warmup 4 --no-cpu-baseline $EXTRA 2>>$OUT | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 r=d['roofline']

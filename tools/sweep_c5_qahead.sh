@@ -5,7 +5,7 @@ OUT=gpurun_out/sweep_c5_qahead.txt
 : > $OUT
 run() {
   echo "== $*" >> $OUT
-  env "$@" python bench.py --workload c5 --also '' --steps 40 --warmup 5 --no-cpu-baseline 2>>$OUT | python -c "
+  env "$@" python bench.py --full --workload c5 --also '' --steps 40 --warmup 5 --no-cpu-baseline 2>>$OUT | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 r=d['roofline']
