@@ -385,6 +385,32 @@ int rt_step(rt_model *model, rt_sites *sites, int recompute_transitions);
  * rt_model_set_rates.  Synchronous.                                                     */
 int rt_expect_step(rt_model *model, rt_sites *sites, int recompute_transitions,
             double *dwell, double *root_posterior, double *trans, int32_t *status);
+/* _mcy_dense.kitchen_sink (_mcy_dense.py:57-230) for every site of a RESIDENT batch: the
+ * posterior node marginals D_v (mc0_esd_get_node_to_distn with the model's root distribution)
+ * and the joint endpoint posteriors J_v[a][b] = D_p[a] P_v[a][b] L_v[b] / (P_v L_v)[a] of every
+ * edge p -> v (mc0_esd_get_joint_endpoint_distn), reduced on the device to sums over state sets.
+ * A set is a state bit mask of two 64-bit words (bit s % 64 of word s / 64, as RT_OBS_MASK).
+ *   node_sets  uint64[n_node_sets][2]; edge_sets uint64[n_edge_sets][2][2] = (A, B)
+ *   node_values[i][v][k] = sum_{s in S_k} D_v[s]                  f64[nsites][nnodes][n_node_sets]
+ *   edge_values[i][v][k] = sum_{a in A_k, b in B_k} J_v[a][b]     f64[nsites][nnodes][n_edge_sets]
+ *                          (keyed by the child's preorder index; the root's slot is 0)
+ *   marginals[i][j] = D_{marginal_nodes[j]}                       f64[nsites][n_marginal_nodes][n]
+ *                          (marginal_nodes preorder indices, distinct; NULL with
+ *                          n_marginal_nodes = nnodes: every node in preorder)
+ *   status[i]: 0, RT_SITE_ZERO_PROB (the site's likelihood is 0: every output of the site is
+ *              0), or 2 (a normalising denominator is zero under a non-zero parent probability)
+ * Any output may be NULL; only the ones given cross PCIe.  Every batch rt_sites_create makes for
+ * 2 <= n <= 128 (dense observations are used as values at every n), models whose transitions came
+ * from any of the rt_model_set_* calls (recompute_transitions != 0 needs rates).  RT_ERR_UNSUPPORTED:
+ * a "rescale" batch, a tree deeper than the fast kernels take, nnodes < 2, more than
+ * RT_MAX_POSTERIOR_SETS sets of a kind, more than 96 GB of scratch.  Synchronous; the batch keeps
+ * its kernel, log-likelihoods, status and totals; sums in a fixed order (bit-identical calls).  */
+#define RT_MAX_POSTERIOR_SETS 8
+int rt_sites_posteriors(rt_model *model, rt_sites *sites, int recompute_transitions,
+            int64_t n_node_sets, const uint64_t *node_sets,
+            int64_t n_edge_sets, const uint64_t *edge_sets,
+            int64_t n_marginal_nodes, const int64_t *marginal_nodes,
+            double *node_values, double *edge_values, double *marginals, int32_t *status);
 /* weights f64[nsites] (copied to the device) or NULL = every site counts once           */
 int rt_sites_set_weights(rt_sites *sites, const double *weights);
 /* loglik f64[nsites] (-inf where status has RT_SITE_ZERO_PROB),

@@ -30,6 +30,7 @@ RT_OBS_DENSE, RT_OBS_STATE, RT_OBS_MASK = 0, 1, 2
 RT_K_EXPM, RT_K_PRUNE, RT_K_REDUCE, RT_K_COMBINE = 0, 1, 2, 3
 RT_SITE_ZERO_PROB = 1
 RT_SITE_NEGATIVE = 4
+RT_MAX_POSTERIOR_SETS = 8
 
 
 class HipLibraryError(ImportError):
@@ -124,6 +125,8 @@ SIGNATURES = {
     'rt_sites_jit_wait': (c_int, [c_void_p]),
     'rt_jit_wait_all': (c_int, []),
     'rt_expect_step': (c_int, [c_void_p, c_void_p, c_int, _p_f64, _p_f64, _p_f64, _p_i32]),
+    'rt_sites_posteriors': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64,
+                                    c_void_p, c_int64, _p_i64, _p_f64, _p_f64, _p_f64, _p_i32]),
     'rt_sites_set_weights': (c_int, [c_void_p, _p_f64]),
     'rt_sites_destroy': (c_int, [c_void_p]),
     'rt_sites_device_bytes': (c_int64, [c_void_p]),

@@ -16,6 +16,7 @@ examples/p53/p53.py:88-100):
   get_log_likelihoods(T, root, nstates, obs_nodes, data, kind, ...)
   get_total_log_likelihood(...)
   get_expected_history_statistics_batch(T, root, nstates, sites, ...)
+  get_posterior_summaries_batch(T, root, nstates, sites, ...)   (kitchen_sink over sites)
 
 Everything numerical runs in hand-written HIP kernels behind the C ABI.
 """
@@ -31,7 +32,7 @@ from .device import TreeModel, get_context
 __all__ = ['custom_expm', 'get_expm_augmented_tree', 'get_likelihood',
            'get_expected_history_statistics', 'get_expected_history_statistics_batch',
            'get_log_likelihoods', 'get_total_log_likelihood',
-           'allowed_states_to_masks']
+           'allowed_states_to_masks', 'get_posterior_summaries_batch']
 
 
 def custom_expm(Q, weight):
@@ -291,3 +292,49 @@ def get_expected_history_statistics_batch(T, root, nstates, sites=None, root_dis
         np.zeros((0, nstates, nstates))
     dwell, trans = _history_statistics_from_weights(ctx, nstates, mats, q_index, ts, Ws)
     return dwell, root_post, trans
+
+
+def get_posterior_summaries_batch(T, root, nstates, sites=None, root_distn=None, Q_default=None,
+                                  node_sets=(), edge_sets=(), marginal_nodes=(),
+                                  obs_nodes=None, data=None, kind='state'):
+    """Per-site sums of the reference's kitchen_sink posteriors (_mcy_dense.py:57-230) over an
+    alignment, on the device (TreeModel.posteriors): ``sites`` is a list of
+    node_to_allowed_states dicts (up to 128 states), or the array form ``obs_nodes`` + ``data``
+    + ``kind`` of get_log_likelihoods.  node_sets: state sets S; edge_sets: pairs (A, B);
+    marginal_nodes: tree nodes whose full marginals are wanted.  Returns a dict:
+      node_values  {node: f64[nsites, len(node_sets)]}   posterior probability of S_k at node
+      edge_values  {(na, nb): f64[nsites, len(edge_sets)]}  of A_k at na and B_k at nb
+      marginals    {node: f64[nsites, nstates]}
+      status       int32[nsites]  (1: the site has likelihood 0, 2: a zero denominator)
+    what examples/p53/liwen-branch-expectation.py:270-315 reads per site."""
+    if root not in T:
+        raise ValueError('the specified root is not in the tree')
+    if sites is not None:
+        obs_nodes = [v for v in TreeArrays(T, root).preorder_nodes
+                     if any(d is not None and v in d for d in sites)]
+        full = set(range(nstates))
+        data = allowed_states_to_masks([dict((v, (d or {}).get(v, full)) for v in obs_nodes)
+                                        for d in sites], obs_nodes, nstates)
+        kind = 'mask'
+    nsites = len(data)
+    if not len(obs_nodes):                   # nothing observed anywhere: the root, unrestricted
+        obs_nodes = [root]
+        data = np.ones((nsites, 1, nstates))
+        kind = 'dense'
+    model, batch = _build(T, root, nstates, obs_nodes, data, kind, root_distn, Q_default, None)
+    try:
+        post = model.posteriors(batch, node_sets=node_sets, edge_sets=edge_sets,
+                                marginal_nodes=list(marginal_nodes) or None)
+        ta = model.tree
+        parent = ta.parent
+        out = dict(status=post.status, node_values={}, edge_values={}, marginals={})
+        for i, v in enumerate(post.nodes):
+            out['node_values'][v] = post.node_values[:, i, :]
+            if i:
+                out['edge_values'][(ta.preorder_nodes[parent[i]], v)] = post.edge_values[:, i, :]
+        for j, v in enumerate(post.marginal_nodes):
+            out['marginals'][v] = post.marginals[:, j, :]
+        return out
+    finally:
+        batch.close()
+        model.close()

@@ -404,6 +404,10 @@ void rt_expect_state_release(rt_model *m);
 // passes.hip: the n <= 8 form of rt_expect_step's passes (W and status on the device)
 int rt_expect_lane_resident(rt_model *m, rt_sites *s, double *d_W, int *d_status);
 void rt_expect_lane_release(rt_model *m);
+// expect_mfma.hip: P^T as A fragments in step order, T[step][m][q][lane][2] (NT row tiles,
+// KP k-step pairs), asynchronous on the context's stream
+int rt_launch_pack_pt(rt_ctx *ctx, int n, int NT, int KP, int nops, const int *d_step_node,
+                      const double *d_P, double *d_PT);
 // a split-M interpreter batch over the resident observations of `src` (api.hip)
 int rt_sites_twin_interpreter(rt_sites *src, rt_sites **out);
 // the context's grow-only device scratch (ctx->d_scratch) holds at least `bytes` afterwards

@@ -976,6 +976,16 @@ int expect_state_get(rt_model *m, expect_state_t **out)
 
 }  // namespace
 
+// the P^T A fragments of pack_pt_kernel for another pass over the same schedule (posterior.hip)
+int rt_launch_pack_pt(rt_ctx *ctx, int n, int NT, int KP, int nops, const int *d_step_node,
+                      const double *d_P, double *d_PT)
+{
+    hipLaunchKernelGGL(pack_pt_kernel, dim3(512), dim3(256), 0, ctx->stream, n, NT, KP, nops, d_step_node,
+                       d_P, d_PT);
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
 void rt_expect_state_release(rt_model *m)
 {
     if (!m || !m->expect_state) return;

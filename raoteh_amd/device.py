@@ -14,6 +14,7 @@ per site (examples/p53/p53.py:88-100).
 from __future__ import annotations
 
 import atexit
+import collections
 import ctypes
 import weakref
 from ctypes import byref, c_char_p, c_double, c_int, c_int32, c_int64, c_void_p
@@ -23,7 +24,8 @@ import numpy as np
 from . import _lib
 from ._tree import TreeArrays
 
-__all__ = ['Context', 'get_context', 'TreeModel', 'SiteBatch', 'device_count']
+__all__ = ['Context', 'get_context', 'TreeModel', 'SiteBatch', 'device_count', 'Posteriors',
+           'states_to_mask']
 
 # At interpreter shutdown objects are finalised in arbitrary order (a model
 # after its context, say); the process is going away, so skip the native
@@ -63,6 +65,31 @@ def _as_uint8_states(data, nstates):
         raise ValueError('observed state outside [0, %d) (255 or -1 = unobserved)'
                          % nstates)
     return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def states_to_mask(states, nstates):
+    """An iterable of state indices -> the two-word bit mask of rt_sites_posteriors (bit s % 64
+    of word s // 64, the RT_OBS_MASK encoding), uint64[2].  ValueError for a state outside
+    0 .. nstates - 1."""
+    words = [0, 0]
+    for s in states:
+        si = int(s)
+        if si != s or not 0 <= si < nstates:
+            raise ValueError('state %r is not in 0..%d' % (s, nstates - 1))
+        words[si >> 6] |= 1 << (si & 63)
+    return np.array(words, dtype=np.uint64)
+
+
+# TreeModel.posteriors: per-site arrays indexed by the preorder `nodes` (node_values
+# [nsites, nnodes, len(node_sets)], edge_values [nsites, nnodes, len(edge_sets)] keyed by the
+# edge's child, 0 at the root), marginals [nsites, len(marginal_nodes), nstates] or None,
+# status int32[nsites] (0 ok, 1 zero likelihood, 2 zero denominator)
+Posteriors = collections.namedtuple(
+    'Posteriors', 'node_values edge_values marginals status nodes marginal_nodes')
+
+
+def _mask_states(mask, nstates):
+    return [s for s in range(nstates) if (int(mask[s >> 6]) >> (s & 63)) & 1]
 
 
 def device_count():
@@ -422,6 +449,31 @@ class SiteBatch(object):
         _lib.check(_lib.lib().rt_sites_set_weights(self._h, _ptr(w, c_double)))
         return self
 
+    def _root_likelihoods(self, nstates):
+        """One-node tree: the root's observation per site as likelihoods f64[nsites, n]
+        (ones where the root is unobserved)."""
+        L = np.ones((self.nsites, nstates))
+        kind, idx, data = getattr(self, '_host_obs', ('dense', [], None))
+        for j, v in enumerate(idx):
+            if v != 0:
+                continue
+            if kind == 'dense':
+                L *= data[:, j, :]
+            elif kind == 'state':
+                col = data[:, j].astype(np.int64)
+                obs = col < nstates
+                onehot = np.zeros((self.nsites, nstates))
+                onehot[np.nonzero(obs)[0], col[obs]] = 1.0
+                onehot[~obs] = 1.0
+                L *= onehot
+            else:
+                words = data[:, j] if data.ndim == 2 else data[:, j, :]
+                words = words.reshape(self.nsites, -1)
+                for s in range(nstates):
+                    bit = (words[:, s >> 6] >> np.uint64(s & 63)) & np.uint64(1)
+                    L[:, s] *= bit.astype(np.float64)
+        return L
+
     def wait_for_kernel(self):
         """Block until the background compile of this batch's tree-specialised kernel (if
         one is pending: rt_set_option 'jit_async') has finished and the batch has switched
@@ -450,6 +502,7 @@ class TreeModel(object):
         self.nstates = int(nstates)
         self._h = c_void_p()
         self._batches = weakref.WeakSet()
+        self._root_w = None             # what set_root_distn sent (the one-node posteriors)
         ta = self.tree
         _lib.check(_lib.lib().rt_model_create(
             self.ctx._h, ta.nnodes, self.nstates, _ptr(ta.indices, c_int64),
@@ -540,6 +593,7 @@ class TreeModel(object):
     def set_root_distn(self, root_distn=None):
         if root_distn is None:
             _lib.check(_lib.lib().rt_model_set_root_distn(self._h, None))
+            self._root_w = None
             return
         w = _f64(root_distn)
         if w.shape != (self.nstates,):
@@ -547,6 +601,7 @@ class TreeModel(object):
                 (self.nstates,), w.shape))
         _lib.check(_lib.lib().rt_model_set_root_distn(self._h,
                                                       _ptr(w, c_double)))
+        self._root_w = w.copy()
 
     def upload_sites(self, obs_nodes, data, kind='dense'):
         """obs_nodes: tree nodes (nx ids) carrying per-site data, in the order
@@ -573,7 +628,10 @@ class TreeModel(object):
         _lib.check(_lib.lib().rt_sites_create(
             self._h, nsites, code, len(idx), _ptr(idx, c_int64),
             data.ctypes.data_as(c_void_p), byref(h)))
-        return SiteBatch(self, h, nsites)
+        batch = SiteBatch(self, h, nsites)
+        if self.tree.nnodes == 1:       # posteriors() answers a one-node tree on the host
+            batch._host_obs = (kind, idx, data.copy())
+        return batch
 
     def prune(self, batch):
         """Asynchronous: upward pass + root reduce + batch sum on the device."""
@@ -602,6 +660,75 @@ class TreeModel(object):
             _ptr(rootp, c_double), _ptr(trans, c_double),
             None if status is None else _ptr(status, c_int32)))
         return (dwell, rootp, trans, status) if return_status else (dwell, rootp, trans)
+
+    def posteriors(self, batch, node_sets=(), edge_sets=(), marginal_nodes=None, marginals=False,
+                   recompute_transitions=False):
+        """rt_sites_posteriors: _mcy_dense.kitchen_sink (_mcy_dense.py:57-230) for every site of
+        the resident batch, reduced on the device.  node_sets: iterables of states S (the posterior
+        probability of S at every node); edge_sets: pairs (A, B) (the joint posterior probability
+        of A at the parent and B at the child, per edge); marginals=True or marginal_nodes (tree
+        nodes): the full posterior marginals of those nodes (all nodes when marginal_nodes is
+        None).  At most RT_MAX_POSTERIOR_SETS (8) sets of each kind.  Returns a Posteriors tuple;
+        its arrays are indexed by `nodes` (the preorder)."""
+        n = self.nstates
+        ta = self.tree
+        nsets = [states_to_mask(S, n) for S in node_sets]
+        esets = []
+        for pair in edge_sets:
+            A, B = pair
+            esets.append(np.concatenate([states_to_mask(A, n), states_to_mask(B, n)]))
+        lim = _lib.RT_MAX_POSTERIOR_SETS
+        if len(nsets) > lim or len(esets) > lim:
+            raise ValueError('at most %d node sets and %d edge sets' % (lim, lim))
+        want_marg = marginals or marginal_nodes is not None
+        if marginal_nodes is None:
+            mnodes = list(ta.preorder_nodes) if want_marg else []
+        else:
+            mnodes = list(marginal_nodes)
+            for v in mnodes:
+                if v not in ta.node_to_index:
+                    raise ValueError('node %r is not in the tree' % (v,))
+        N, S = ta.nnodes, batch.nsites
+        node_values = np.zeros((S, N, len(nsets)))
+        edge_values = np.zeros((S, N, len(esets)))
+        marg = np.zeros((S, len(mnodes), n)) if want_marg else None
+        status = np.zeros(S, dtype=np.int32)
+        nodes = list(ta.preorder_nodes)
+        if N == 1:
+            # one node: the posterior is the normalised root weights times the root's
+            # observation (kitchen_sink's len(T) == 1 case), no edges
+            L = batch._root_likelihoods(n)
+            w = np.ones(n) if self._root_w is None else self._root_w
+            wl = L * w
+            tot = wl.sum(axis=1)
+            ok = tot > 0
+            status[~ok] = _lib.RT_SITE_ZERO_PROB
+            D = np.zeros_like(wl)
+            D[ok] = wl[ok] / tot[ok][:, None]
+            for k, m in enumerate(nsets):
+                node_values[:, 0, k] = D[:, _mask_states(m, n)].sum(axis=1)
+            if want_marg:
+                marg[:, :, :] = D[:, None, :]
+            return Posteriors(node_values, edge_values, marg, status, nodes, mnodes)
+        nmask = np.ascontiguousarray(np.array(nsets, dtype=np.uint64).reshape(-1, 2))
+        emask = np.ascontiguousarray(np.array(esets, dtype=np.uint64).reshape(-1, 2, 2))
+        # (the device writes each node once: a node listed twice is copied here)
+        uniq = list(dict.fromkeys(mnodes))
+        if len(uniq) != len(mnodes):
+            marg = np.zeros((S, len(uniq), n))
+        midx = _i64([ta.node_to_index[v] for v in uniq])
+        _lib.check(_lib.lib().rt_sites_posteriors(
+            self._h, batch._h, 1 if recompute_transitions else 0,
+            len(nsets), nmask.ctypes.data_as(c_void_p) if len(nsets) else None,
+            len(esets), emask.ctypes.data_as(c_void_p) if len(esets) else None,
+            len(uniq), _ptr(midx, c_int64) if len(uniq) else None,
+            _ptr(node_values, c_double) if len(nsets) else None,
+            _ptr(edge_values, c_double) if len(esets) else None,
+            _ptr(marg, c_double) if want_marg and len(mnodes) else None,
+            _ptr(status, c_int32)))
+        if len(uniq) != len(mnodes):
+            marg = marg[:, [uniq.index(v) for v in mnodes]]
+        return Posteriors(node_values, edge_values, marg, status, nodes, mnodes)
 
     def allreduce(self, batch):
         _lib.check(_lib.lib().rt_allreduce_totals(self.ctx._h, batch._h))

@@ -25,6 +25,7 @@ Reference functions exercised:
   _graph_transform.get_chunk_tree_type_b       raoteh/sampler/_graph_transform.py:298-375
   _mc0.get_node_to_distn                       raoteh/sampler/_mc0.py:382-462
   examples/p53/liwen.py:566-636,677-682        the 122-state switching model (fixture_switching)
+  _mc0.get_joint_endpoint_distn                raoteh/sampler/_mc0.py:255-308 (fixture_switching_posteriors)
   _tmjp.get_inhomogeneous_mjp                  raoteh/sampler/_tmjp.py:803-903 (the sparse twin of
                                                pyfelscore.tmjp_get_inhomogeneous_mjp)
 expm per edge is ``scipy.linalg.expm(Q*t)`` exactly as ``_mjp_dense.py:24-25``.
@@ -1048,18 +1049,10 @@ def fixture_pyfelscore_calls(mods):
                 callers=dict((k, sorted(v)) for k, v in sorted(callers.items())))
 
 
-def fixture_switching(mods, nsites=5):
-    """The 122-state "switching" model of examples/p53/liwen.py: MG94 codon process
-    (create_mg94, parameters of get_jeff_params_e :273-300) x {reference, default},
-    built step by step as liwen.py:566-636 builds it (the same reference helpers:
-    create_mg94.create_mg94, _density.rate_matrix_to_numpy_array / dict_to_numpy_array,
-    _util.get_normalized_dict_distn), on the p53 tree re-rooted at the leaf 'Has'
-    (:476-477), leaf sets {c, 61 + c} (:682).  The disease table liwen.py reads is not
-    in the reference tree, so each column gets a seeded benign set of amino acids (the
-    residues seen in the column plus a random half of the others).  Likelihoods and the
-    posterior probability that the ORIGINAL root is in the reference process
-    (:403-415) come from the reference's unaccelerated type-y functions
-    (_mcy.py:396-470,611-682, _mc0.py:89-138,202-252,382-462) with P = scipy expm."""
+def _switching_columns(mods, nsites):
+    """The construction fixture_switching and fixture_switching_posteriors share: the 122-state
+    model of examples/p53/liwen.py on the p53 tree, one compound process per column (see
+    fixture_switching).  Returns (header dict, list of per-column dicts)."""
     sys.path.insert(0, REF + '/examples/p53')
     if not hasattr(nx, 'to_numpy_matrix'):
         nx.to_numpy_matrix = lambda G, **kw: np.asmatrix(nx.to_numpy_array(G, **kw))
@@ -1095,8 +1088,7 @@ def fixture_switching(mods, nsites=5):
     rng = np.random.RandomState(20131205)
     ncompound = 2 * nstates
     compound_states = list(range(ncompound))
-    sites = []
-    t0 = time.time()
+    columns_out = []
     for i in range(nsites):
         column = [c.upper() for c in columns[i]]
         seen = set(state_to_residue[codon_to_state[c]] for c in column)
@@ -1137,11 +1129,44 @@ def fixture_switching(mods, nsites=5):
         for a, b, d in tree.edges(data=True):
             tmp.add_edge(a, b, weight=d['weight'])
         T_aug, dense = augmented(tmp, root, Q_compound_dense)
-        rec = dict(column=column, benign_residues=sorted(benign_residues),
-                   benign_states=sorted(int(s) for s in benign_states),
-                   compound_distn=compound_distn_dense.tolist())
+        columns_out.append(dict(i=i, column=column, benign_residues=benign_residues,
+                                benign_states=benign_states, compound_distn=compound_distn,
+                                compound_distn_dense=compound_distn_dense,
+                                Q_compound_dense=Q_compound_dense, allowed=node_to_allowed_states,
+                                T_aug=T_aug, dense=dense))
+    header = dict(nstates=nstates, ncompound=ncompound, rho=rho, kappa=kappa, omega=omega,
+                  nt=dict(A=A, C=C, G=G, T=T), root=int(root), original_root=int(original_root),
+                  names=names, Q_default_offdiagonal_checksum=float(np.abs(Q_dense).sum()),
+                  primary_distn=[float(primary_distn[s]) for s in states])
+    return header, columns_out
+
+
+def fixture_switching(mods, nsites=5):
+    """The 122-state "switching" model of examples/p53/liwen.py: MG94 codon process
+    (create_mg94, parameters of get_jeff_params_e :273-300) x {reference, default},
+    built step by step as liwen.py:566-636 builds it (the same reference helpers:
+    create_mg94.create_mg94, _density.rate_matrix_to_numpy_array / dict_to_numpy_array,
+    _util.get_normalized_dict_distn), on the p53 tree re-rooted at the leaf 'Has'
+    (:476-477), leaf sets {c, 61 + c} (:682).  The disease table liwen.py reads is not
+    in the reference tree, so each column gets a seeded benign set of amino acids (the
+    residues seen in the column plus a random half of the others).  Likelihoods and the
+    posterior probability that the ORIGINAL root is in the reference process
+    (:403-415) come from the reference's unaccelerated type-y functions
+    (_mcy.py:396-470,611-682, _mc0.py:89-138,202-252,382-462) with P = scipy expm."""
+    _util, _mc0 = mods['_util'], mods['_mc0']
+    t0 = time.time()
+    header, columns = _switching_columns(mods, nsites)
+    nstates, root, original_root = header['nstates'], header['root'], header['original_root']
+    compound_states = list(range(header['ncompound']))
+    sites = []
+    for col in columns:
+        i, T_aug, dense = col['i'], col['T_aug'], col['dense']
+        compound_distn, Q_compound_dense = col['compound_distn'], col['Q_compound_dense']
+        rec = dict(column=col['column'], benign_residues=sorted(col['benign_residues']),
+                   benign_states=sorted(int(s) for s in col['benign_states']),
+                   compound_distn=col['compound_distn_dense'].tolist())
         try:
-            pset, nset, pmap = ref_type_y(mods, T_aug, root, node_to_allowed_states)
+            pset, nset, pmap = ref_type_y(mods, T_aug, root, col['allowed'])
             lik = _mc0.get_likelihood(pmap[root], root_distn=compound_distn)
             node_to_distn = _mc0.get_node_to_distn(T_aug, root, pmap, root_distn=compound_distn)
             d0 = node_to_distn[original_root]
@@ -1161,11 +1186,56 @@ def fixture_switching(mods, nsites=5):
             rec['P_scipy_rows'] = [0, 60, 61, 121]
             rec['P_scipy'] = [dense[nb0][r].tolist() for r in (0, 60, 61, 121)]
         sites.append(rec)
-    return dict(nstates=nstates, ncompound=ncompound, rho=rho, kappa=kappa, omega=omega,
-                nt=dict(A=A, C=C, G=G, T=T), root=int(root), original_root=int(original_root),
-                names=names, Q_default_offdiagonal_checksum=float(np.abs(Q_dense).sum()),
-                primary_distn=[float(primary_distn[s]) for s in states],
-                sites=sites, reference_seconds=time.time() - t0)
+    return dict(header, sites=sites, reference_seconds=time.time() - t0)
+
+
+def fixture_switching_posteriors(mods, nsites=5):
+    """Posterior summaries of the switching model (the columns and compound processes of
+    fixture_switching), what examples/p53/liwen-branch-expectation.py:270-315 and
+    liwen.py:408-416 read: from the reference's unaccelerated _mc0.get_node_to_distn
+    (_mc0.py:382-462) and _mc0.get_joint_endpoint_distn (_mc0.py:255-308) on T_aug, per site
+      p_primary[node]      sum_{s < 61} distn[node][s]
+      switch[child]        J[:61, 61:].sum() of the edge into child
+      switch_back[child]   J[61:, :61].sum()
+      original_root_distn, leaf_distn   the full 122-state marginals of the original root
+                                        and of one leaf (leaf_node)
+    Nodes are tree node ids (strings as JSON keys).  A structural-zero column is marked."""
+    _util, _mc0 = mods['_util'], mods['_mc0']
+    t0 = time.time()
+    header, columns = _switching_columns(mods, nsites)
+    nstates, root, original_root = header['nstates'], header['root'], header['original_root']
+    compound_states = list(range(header['ncompound']))
+    leaf_node = None
+    sites = []
+    for col in columns:
+        T_aug = col['T_aug']
+        if leaf_node is None:           # the first leaf of the tree that is not the root
+            leaf_node = int(min(v for v in T_aug if T_aug.degree(v) == 1 and v != root))
+        rec = dict(benign_states=sorted(int(s) for s in col['benign_states']))
+        try:
+            pset, nset, pmap = ref_type_y(mods, T_aug, root, col['allowed'])
+            _mc0.get_likelihood(pmap[root], root_distn=col['compound_distn'])
+            distn = _mc0.get_node_to_distn(T_aug, root, pmap, root_distn=col['compound_distn'])
+            J_aug = _mc0.get_joint_endpoint_distn(T_aug, root, pmap, distn)
+            rec['p_primary'] = dict((str(int(v)), float(sum(p for s, p in d.items() if s < nstates)))
+                                    for v, d in distn.items())
+            switch, back = {}, {}
+            for na, nb in nx.bfs_edges(T_aug, root):
+                J = J_aug[na][nb]['J']
+                switch[str(int(nb))] = float(sum(d['weight'] for a, b, d in J.edges(data=True)
+                                                 if a < nstates <= b))
+                back[str(int(nb))] = float(sum(d['weight'] for a, b, d in J.edges(data=True)
+                                               if b < nstates <= a))
+            rec.update(structural_zero=False, switch=switch, switch_back=back,
+                       original_root_distn=[float(distn[original_root].get(s, 0.0))
+                                            for s in compound_states],
+                       leaf_distn=[float(distn[leaf_node].get(s, 0.0)) for s in compound_states])
+        except _util.StructuralZeroProb:
+            rec.update(structural_zero=True)
+        sites.append(rec)
+    return dict(nstates=nstates, ncompound=header['ncompound'], root=int(root),
+                original_root=int(original_root), leaf_node=leaf_node, sites=sites,
+                reference_seconds=time.time() - t0)
 
 
 def main():
@@ -1200,6 +1270,7 @@ def main():
         chunk_trees=lambda: fixture_chunk_trees(mods),
         spectral=lambda: fixture_spectral(mods),
         switching=lambda: fixture_switching(mods),
+        switching_posteriors=lambda: fixture_switching_posteriors(mods),
         tmjp_inhomogeneous=lambda: fixture_tmjp_inhomogeneous(mods),
         pyfelscore_calls=lambda: fixture_pyfelscore_calls(mods),
     )
