@@ -321,7 +321,8 @@ int rt_build_schedule(int64_t nnodes, const int64_t *tree_csr_indices,
  * probability" there and, by default, here.  With the option such a batch keeps the
  * interpreter kernels (no tree-specialised kernel); a batch that never comes near the
  * threshold gets the default kernels' numbers bit for bit (powers of two are exact).
- * Likelihood evaluation only (rt_prune / rt_step): expectations stay unscaled.             */
+ * Likelihood evaluation only (rt_prune / rt_step): rt_expect_step and rt_sites_posteriors
+ * return RT_ERR_UNSUPPORTED for such a batch (their passes do not rescale).                 */
 /* "leaf_state_kernels" (1 default / 0): a batch uploaded as observed states at the leaves
  * (RT_OBS_STATE, every leaf observed, 5..128 states) may run a tree-specialised kernel whose
  * leaf steps gather a column of P instead of multiplying P by the one-hot vector -- the same
@@ -345,7 +346,10 @@ int rt_sites_create(rt_model *model, int64_t nsites, int kind, int64_t nobs,
             const int64_t *obs_nodes, const void *data, rt_sites **sites);
 /* A second batch with the same values at different HBM addresses (used by
  * the benchmark to rotate batches so the 256 MiB Infinity Cache cannot hold
- * the working set).                                                         */
+ * the working set): the same observations, pruning kernel, per-site
+ * log-likelihoods, statuses and totals (a pending batch sum is reduced first),
+ * so that both read the same until either is pruned again.  A clone of a batch
+ * that was never pruned is never pruned either.  (Site weights are not copied.) */
 int rt_sites_clone(rt_sites *sites, rt_sites **clone);
 /* Wait for the background compile of this batch's tree-specialised kernel, if one is
  * pending, and switch the batch to it (see "jit_async").                              */
@@ -382,7 +386,8 @@ int rt_step(rt_model *model, rt_sites *sites, int recompute_transitions);
  * raises NumericalZeroProb).  n <= RT_MAX_EXPECT_STATES, batches created by rt_sites_create
  * (n > 4: any observation kind; n <= 4: the fused lane kernel works on allowed sets, so a
  * dense batch counts a state as allowed where its likelihood is not zero), rates set by
- * rt_model_set_rates.  Synchronous.                                                     */
+ * rt_model_set_rates.  RT_ERR_UNSUPPORTED for a "rescale" batch (the passes work on
+ * unscaled f64 messages), at every n.  Synchronous.                                     */
 int rt_expect_step(rt_model *model, rt_sites *sites, int recompute_transitions,
             double *dwell, double *root_posterior, double *trans, int32_t *status);
 /* _mcy_dense.kitchen_sink (_mcy_dense.py:57-230) for every site of a RESIDENT batch: the
@@ -414,10 +419,13 @@ int rt_sites_posteriors(rt_model *model, rt_sites *sites, int recompute_transiti
 /* weights f64[nsites] (copied to the device) or NULL = every site counts once           */
 int rt_sites_set_weights(rt_sites *sites, const double *weights);
 /* loglik f64[nsites] (-inf where status has RT_SITE_ZERO_PROB),
- * status int32[nsites]; either may be NULL.                                 */
+ * status int32[nsites]; either may be NULL.  What the last rt_prune / rt_step
+ * of the batch wrote (or its clone source's); RT_ERR_INVALID for a batch that
+ * no pruning kernel has written yet.                                        */
 int rt_sites_get_logliks(rt_sites *sites, double *loglik, int32_t *status);
 /* totals[0] = sum of log-likelihoods over sites with non-zero likelihood,
- * totals[1] = number of zero-probability sites, totals[2] = number of sites */
+ * totals[1] = number of zero-probability sites, totals[2] = number of sites;
+ * all three are 0 for a batch that was never pruned.                        */
 int rt_sites_get_totals(rt_sites *sites, double totals[3]);
 
 /* ---- 3. multi-GPU: one process per GPU, RCCL over xGMI ------------------- */

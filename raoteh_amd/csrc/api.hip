@@ -1975,6 +1975,19 @@ static int sites_lane_switch(rt_sites *s, const std::string &src)
         if (e != hipSuccess) rc = RT_ERR_NOMEM;
     }
     if (rc == RT_OK) {
+        // what the interpreter kernel's launches left stays readable after the switch (both
+        // kernels index d_loglik and d_status by site; the totals stay where they are)
+        hipError_t e = hipMemcpyAsync(n_ll, s->d_loglik, (size_t)s->nsites * 8, hipMemcpyDeviceToDevice,
+                                      ctx->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(n_st, s->d_status, (size_t)s->nsites * 4, hipMemcpyDeviceToDevice,
+                               ctx->stream);
+        if (e != hipSuccess) {
+            rt_set_error("rt_sites_jit_poll: %s", hipGetErrorString(e));
+            rc = RT_ERR_HIP;
+        }
+    }
+    if (rc == RT_OK) {
         std::swap(s->d_obs, n_obs);
         rc = rt_sites_pack_device(s, s->jit_kind, s->d_raw, s->d_raw_src);
         if (rc == RT_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = RT_ERR_HIP;
@@ -2091,6 +2104,9 @@ extern "C" int rt_sites_clone(rt_sites *src, rt_sites **out)
     // (a lane-family batch changes its resident layout when its kernel arrives: wait for it
     // rather than cloning the image it is about to leave)
     if (src->jit_job && src->layout == RT_LAYOUT_LANE) RT_TRY(rt_sites_jit_poll(src, true));
+    // the clone carries the source's results: its batch sum must be reduced first
+    rt_ctx *ctx = src->model->ctx;
+    if (ctx->pending_reduce == src) RT_TRY(rt_flush_reduce(ctx));
     rt_sites *s = new (std::nothrow) rt_sites();
     if (!s) return RT_ERR_NOMEM;
     s->model = src->model;
@@ -2135,17 +2151,38 @@ extern "C" int rt_sites_clone(rt_sites *src, rt_sites **out)
                        (size_t)s->nblocks * (s->sparse_pairs ? (s->nobs + 1) / 2 : (s->nobs + 3) / 4) * 16 * 4,
                        hipMemcpyDeviceToDevice, src->model->ctx->stream) != hipSuccess)
         rc = RT_ERR_HIP;
-    if (rc == RT_OK && s->obs_bytes > 0) {
+    if (rc == RT_OK) {
         // on the library's stream: a device-to-device hipMemcpy returns before the copy
         // has run and the (non-blocking) stream of the kernels does not wait for the
-        // null stream -- a launch right after the clone would read a half-copied batch
-        hipError_t e = hipMemcpyAsync(s->d_obs, src->d_obs, s->obs_bytes, hipMemcpyDeviceToDevice,
-                                      src->model->ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(src->model->ctx->stream);
+        // null stream -- a launch right after the clone would read a half-copied batch.
+        // The per-site results and the totals come along (the same values: a clone of a
+        // pruned batch reads as its source until either is pruned again)
+        hipError_t e = hipSuccess;
+        if (s->obs_bytes > 0)
+            e = hipMemcpyAsync(s->d_obs, src->d_obs, s->obs_bytes, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e == hipSuccess && src->pruned) {
+            // (sites_alloc zeroed the totals on the null stream, which this stream does not wait for)
+            e = hipDeviceSynchronize();
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(s->d_loglik, src->d_loglik, (size_t)s->nsites * 8, hipMemcpyDeviceToDevice,
+                               ctx->stream);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(s->d_status, src->d_status, (size_t)s->nsites * 4,
+                                   hipMemcpyDeviceToDevice, ctx->stream);
+            // (an all-reduce of the source's totals may still be in flight on the comm stream)
+            if (e == hipSuccess && ctx->comm_stream) e = hipStreamSynchronize(ctx->comm_stream);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(s->d_totals, src->d_totals, 3 * 8, hipMemcpyDeviceToDevice, ctx->stream);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) {
             rt_set_error("rt_sites_clone: %s", hipGetErrorString(e));
             rc = RT_ERR_HIP;
         }
+    }
+    if (rc == RT_OK && src->pruned) {
+        s->pruned = true;
+        memcpy(s->kernel_name, src->kernel_name, sizeof(s->kernel_name));
     }
     if (rc != RT_OK) {
         rt_sites_destroy(s);
@@ -2266,6 +2303,8 @@ extern "C" int rt_step(rt_model *m, rt_sites *s, int recompute_transitions)
 extern "C" int rt_sites_get_logliks(rt_sites *s, double *loglik, int32_t *status)
 {
     RT_REQUIRE(s, "null pointer");
+    RT_REQUIRE(s->pruned, "rt_sites_get_logliks: no pruning kernel has written this batch yet "
+               "(rt_prune / rt_step first)");
     RT_HIP(hipSetDevice(s->model->ctx->device));
     RT_HIP(hipStreamSynchronize(s->model->ctx->stream));
     if (loglik)

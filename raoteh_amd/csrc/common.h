@@ -285,6 +285,9 @@ struct rt_sites {
     rt_sites *expect_twin = nullptr;
     bool obs_borrowed = false;
     bool counted = false;           // this batch is in its model's live_batches
+    // a pruning launch has written d_loglik / d_status (or a clone copied them): before that
+    // they hold nothing and rt_sites_get_logliks refuses
+    bool pruned = false;
     char kernel_name[64] = "";      // the pruning kernel variant of this batch
     double jit_compile_s = 0.0;     // hiprtc time spent for this batch (0: cache hit / none)
 };

@@ -1000,6 +1000,13 @@ extern "C" int rt_expect_step(rt_model *m, rt_sites *s, int recompute_transition
     RT_REQUIRE(s->model == m, "the site batch belongs to another model");
     RT_REQUIRE(m->d_Q && !m->spectral,
                "rt_model_set_rates has not been called (the statistics need the rate matrices)");
+    if (s->rescale) {
+        // neither the lane kernel nor the split-M twin rescales its messages: on a tree whose
+        // likelihood underflows f64 they would return zeros
+        rt_set_error("rt_expect_step: a \"rescale\" batch is not supported (the passes do not "
+                     "rescale their messages)");
+        return RT_ERR_UNSUPPORTED;
+    }
     const int64_t n = m->n, N = m->nnodes;
     const bool lane = n <= 4;                  // resident in the lane layout: the fused lane kernel
     if (n > RT_MAX_EXPECT_STATES || N < 2 || s->d_scratch || m->max_depth > RT_FAST_MAX_DEPTH ||

@@ -2061,6 +2061,7 @@ int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm)
     } else rc = launch_mfma(m, s, &name);
     if (rc != RT_OK) return rc;
     RT_HIP(hipGetLastError());
+    s->pruned = true;
     snprintf(ctx->slots[RT_K_PRUNE].name, sizeof(ctx->slots[RT_K_PRUNE].name), "%s", name);
     if (name != s->kernel_name) snprintf(s->kernel_name, sizeof(s->kernel_name), "%s", name);
     rt_time_end(ctx, RT_K_PRUNE, ev);

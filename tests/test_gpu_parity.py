@@ -20,6 +20,7 @@ import pytest
 from conftest import (expectation_cases, load_golden, tree_from_edges, config_from_golden,
                       switching_cases)
 from oracle import oracle_numpy as orc
+from _resident_cases import _extended_log_likelihoods
 
 pytestmark = pytest.mark.gpu
 
@@ -1245,28 +1246,6 @@ def test_underflow_is_reported_not_hidden(ra):
                                           ra.synth.one_hot(states, n), pi)
     np.testing.assert_array_equal(st, wst)
     assert wst.all() and np.all(np.isneginf(ll))
-
-
-def _extended_log_likelihoods(tree, esd, leaf_idx, states, n, root_w):
-    """Felsenstein pruning in np.longdouble (x87 extended: exponent range 2^-16445) on the
-    device's own transition matrices -- what the f64 recursion would give without underflow."""
-    ld = np.longdouble
-    nsites = states.shape[0]
-    L = [None] * tree.nnodes
-    col = dict((v, k) for k, v in enumerate(leaf_idx))
-    for v in range(tree.nnodes - 1, -1, -1):
-        x = np.ones((nsites, n), dtype=ld)
-        if v in col:
-            s = states[:, col[v]]
-            obs = s != 255
-            x[obs] = 0
-            x[np.nonzero(obs)[0], s[obs]] = 1
-        for c in tree.indices[tree.indptr[v]:tree.indptr[v + 1]]:
-            x = x * (L[c] @ esd[c].astype(ld).T)
-            L[c] = None
-        L[v] = x
-    lik = L[0] @ np.asarray(root_w, dtype=ld)
-    return np.log(lik).astype(np.float64)
 
 
 @pytest.mark.parametrize('n,generic', [(2, False), (4, False), (13, False), (20, False),
