@@ -48,8 +48,14 @@ extern "C" {
                                     (pset / set / pmap / distn / joint): n <= 128 --
                                     examples/p53/liwen.py:599-621 runs _mcy_dense on
                                     2 x 61 = 122 compound states                */
-#define RT_MAX_EXPECT_STATES 64  /* expectation path (rt_mjp_*), Rao-Teh forest /
+#define RT_MAX_EXPECT_STATES 64  /* reference-shaped expectation passes on host
+                                    arrays (rt_mjp_*_expectation_*), Rao-Teh forest /
                                     chains, spectral reconstruction: n <= 64    */
+#define RT_MAX_EXPECT_STEP_STATES 128 /* rt_expect_step on a resident batch and
+                                    rt_mjp_frechet_statistics: n <= 128 (above 64 the
+                                    Frechet derivative is carried as a pair (X, L)
+                                    through the scaling and squaring, no order-2n
+                                    block)                                       */
 #define RT_MAX_EXPM_STATES 128   /* expm: n <= 64 LDS-resident, <= 128 through
                                     L2-resident scratch (the Frechet blocks of the
                                     61-state codon model have order 122)        */
@@ -237,7 +243,9 @@ int rt_mjp_esd_expectation_weights_obs(rt_ctx *ctx, int64_t nnodes, int64_t n,
  *   of the 2n x 2n block [[t Q^T, W], [0, t Q^T]], all edges in one expm launch),
  *   dwell[c] = sum_e t_e M_e[c][c],   trans[c][d] = sum_e t_e Q_e[c][d] M_e[c][d]
  * -- what the reference gets from n + nnz(Q) scipy.linalg.expm_frechet calls per edge
- * and site.  2n <= RT_MAX_EXPM_STATES (n <= 64: the 61-state codon model included).   */
+ * and site.  n <= RT_MAX_EXPECT_STEP_STATES: for n <= 64 the block exponential above (order
+ * 2n <= RT_MAX_EXPM_STATES), for 64 < n <= 128 the pair recurrence (X1, L1)(X2, L2) =
+ * (X1 X2, X1 L2 + L1 X2) with the same degree and squarings rule, taken from |t Q| alone.  */
 int rt_mjp_frechet_statistics(rt_ctx *ctx, int64_t n, int64_t nedges, const double *Q,
             int64_t nq, const int64_t *q_index, const double *t, const double *W,
             double *dwell, double *trans);
@@ -383,8 +391,9 @@ int rt_step(rt_model *model, rt_sites *sites, int recompute_transitions);
  *   trans[c][d]    expected number of c -> d transitions (0 where no rate matrix has c -> d)
  * each site weighted by rt_sites_set_weights (multiplicities of site patterns; default 1).
  * status (optional, int32[nsites]): 2 where a normalising denominator is zero (the reference
- * raises NumericalZeroProb).  n <= RT_MAX_EXPECT_STATES, batches created by rt_sites_create
- * (n > 4: any observation kind; n <= 4: the fused lane kernel works on allowed sets, so a
+ * raises NumericalZeroProb).  n <= RT_MAX_EXPECT_STEP_STATES (every n rt_sites_create takes in
+ * the matrix-pipe layout: the 122-state switching model included), batches created by
+ * rt_sites_create (n > 4: any observation kind; n <= 4: the fused lane kernel works on allowed sets, so a
  * dense batch counts a state as allowed where its likelihood is not zero), rates set by
  * rt_model_set_rates.  RT_ERR_UNSUPPORTED for a "rescale" batch (the passes work on
  * unscaled f64 messages), at every n.  Synchronous.                                     */

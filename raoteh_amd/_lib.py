@@ -31,6 +31,8 @@ RT_K_EXPM, RT_K_PRUNE, RT_K_REDUCE, RT_K_COMBINE = 0, 1, 2, 3
 RT_SITE_ZERO_PROB = 1
 RT_SITE_NEGATIVE = 4
 RT_MAX_POSTERIOR_SETS = 8
+RT_MAX_EXPECT_STATES = 64
+RT_MAX_EXPECT_STEP_STATES = 128
 
 
 class HipLibraryError(ImportError):

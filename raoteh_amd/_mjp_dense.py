@@ -187,6 +187,31 @@ def _history_statistics_from_weights(ctx, nstates, mats, q_index, ts, Ws):
     return ctx.frechet_statistics(np.stack(mats), q_index, ts, Ws)
 
 
+def _expected_history_statistics_resident(T, root, nstates, obs_nodes, data, kind, root_distn,
+                                          Q_default, weights):
+    """The statistics of a batch through a model and a resident batch (rt_expect_step): the
+    route for nstates > 64, where the reference-shaped passes on host arrays and the order-2n
+    Frechet blocks stop.  Same return values as get_expected_history_statistics_batch."""
+    if not len(obs_nodes):                   # nothing observed anywhere: the root, unrestricted
+        obs_nodes = [root]
+        data = np.ones((len(data), 1, nstates))
+        kind = 'dense'
+    model, batch = _build(T, root, nstates, obs_nodes, data, kind, root_distn, Q_default, None)
+    try:
+        if weights is not None:
+            batch.set_weights(weights)
+        dwell, root_post, trans, status = model.expected_history_statistics(
+            batch, return_status=True)
+    finally:
+        batch.close()
+        model.close()
+    if status.any():
+        from ._util import NumericalZeroProb
+        raise NumericalZeroProb('the denominator is zero (site %d)'
+                                % int(np.nonzero(status)[0][0]))
+    return dwell, root_post, trans
+
+
 def get_expected_history_statistics(T, node_to_allowed_states, root, nstates,
                                     root_distn=None, Q_default=None):
     """One site, as the reference (:410-539): returns (dict state -> expected dwell
@@ -197,6 +222,17 @@ def get_expected_history_statistics(T, node_to_allowed_states, root, nstates,
     distributions and the Frechet block exponentials run on the device."""
     if root not in T:
         raise ValueError('the specified root is not in the tree')
+    if nstates > 64:                         # one site of the resident route (two-word masks)
+        dwell, root_post, trans = get_expected_history_statistics_batch(
+            T, root, nstates, sites=[node_to_allowed_states], root_distn=root_distn,
+            Q_default=Q_default)
+        expected_transitions = nx.DiGraph()
+        for Q in _edge_rates(T, root, Q_default)[1]:
+            for c, d in zip(*np.nonzero(Q)):
+                if not expected_transitions.has_edge(int(c), int(d)):
+                    expected_transitions.add_edge(int(c), int(d), weight=float(trans[c, d]))
+        return (dict((c, float(dwell[c])) for c in range(nstates)), root_post,
+                expected_transitions)
     T_aug = get_expm_augmented_tree(T, root, Q_default=Q_default)
     node_to_pmap = _mcy_dense.get_node_to_pmap(
         T_aug, root, nstates, node_to_allowed_states=node_to_allowed_states)
@@ -234,14 +270,27 @@ def get_expected_history_statistics_batch(T, root, nstates, sites=None, root_dis
     per-site multiplicities (site patterns).  Instead of ``sites``, the array form
     of get_log_likelihoods: ``obs_nodes`` + ``data`` [nsites, len(obs_nodes)] of
     states (kind='state', a value >= nstates = unobserved) or allowed-set bit masks
-    (kind='mask')."""
+    (kind='mask').  nstates > 64 (up to 128): through a model and a resident batch
+    (TreeModel.expected_history_statistics), masks of two 64-bit words."""
     if root not in T:
         raise ValueError('the specified root is not in the tree')
+    w = None if weights is None else np.asarray(weights, dtype=np.float64)
+    if nstates > 64:
+        # a model and a resident batch, as get_posterior_summaries_batch: site dicts become
+        # two-word masks
+        if sites is not None:
+            obs_nodes = [v for v in TreeArrays(T, root).preorder_nodes
+                         if any(d is not None and v in d for d in sites)]
+            full = set(range(nstates))
+            data = allowed_states_to_masks([dict((v, (d or {}).get(v, full)) for v in obs_nodes)
+                                            for d in sites], obs_nodes, nstates)
+            kind = 'mask'
+        return _expected_history_statistics_resident(T, root, nstates, obs_nodes, data, kind,
+                                                     root_distn, Q_default, w)
     ctx = get_context()
     T_aug = get_expm_augmented_tree(T, root, Q_default=Q_default)
     ta = TreeArrays(T_aug, root)
     esd = ta.esd_transitions(nstates)
-    w = None if weights is None else np.asarray(weights, dtype=np.float64)
     # upward passes, downward pass and the per-edge site sums of J / P in one call;
     # n*n numbers per edge come back, whatever the number of sites
     if sites is not None:

@@ -402,6 +402,12 @@ int rt_frechet_statistics_device(rt_ctx *ctx, int64_t n, int64_t nedges, const d
                                  const int32_t *dqidx, const double *dt, const double *dW,
                                  double *dB, double *dE, double *dscale, const double *dones,
                                  const int32_t *dident, double *ddwell, double *dtrans);
+// frechet_wide.hip: the same for 64 < n <= 128 by the pair recurrence (no order-2n block);
+// dS: rt_frechet_wide_scratch_doubles(n, nedges) doubles, dinfo (optional) {degree, squarings}
+size_t rt_frechet_wide_scratch_doubles(int64_t n, int64_t nedges);
+int rt_frechet_wide_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double *dQ,
+                           const int32_t *dqidx, const double *dt, const double *dW, double *dS,
+                           double *dscale, int32_t *dinfo, double *ddwell, double *dtrans);
 // ... and what rt_expect_step keeps with a model (rt_model_destroy)
 void rt_expect_state_release(rt_model *m);
 // passes.hip: the n <= 8 form of rt_expect_step's passes (W and status on the device)

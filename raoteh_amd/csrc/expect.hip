@@ -13,6 +13,7 @@
 // scaling and squaring), the Taylor expm kernel (order <= 128: n <= 64, the codon model
 // included) exponentiates all edges in one launch, and a kernel contracts the corner
 // blocks over the edges in a fixed order.  2n + n^2 numbers leave the device.
+// 64 < n <= 128: no block of order 2n; frechet_wide.hip carries the pair (exp(A), L) instead.
 #include "common.h"
 
 namespace {
@@ -109,12 +110,17 @@ extern "C" int rt_mjp_frechet_statistics(rt_ctx *ctx, int64_t n, int64_t nedges,
 {
     RT_REQUIRE(ctx && Q && t && W && dwell && trans, "null pointer");
     RT_REQUIRE(n >= 1 && nedges >= 0 && nq >= 1, "bad sizes");
-    if (2 * n > RT_MAX_EXPM_STATES) {
-        rt_set_error("expected history statistics need the expm kernel at order 2n = %lld; it "
-                     "covers order <= %d", (long long)(2 * n), RT_MAX_EXPM_STATES);
+    if (n > RT_MAX_EXPECT_STEP_STATES) {
+        rt_set_error("expected history statistics: n=%lld > %d", (long long)n,
+                     RT_MAX_EXPECT_STEP_STATES);
         return RT_ERR_UNSUPPORTED;
     }
-    const size_t nn = (size_t)n * n, mm = 4 * nn;
+    // 2n > RT_MAX_EXPM_STATES: no block exponential, the pair kernel of frechet_wide.hip (its
+    // nine matrices per edge take the place of the blocks and their exponentials)
+    const bool wide = 2 * n > RT_MAX_EXPM_STATES;
+    const size_t nn = (size_t)n * n,
+                 mm = wide && nedges ? (rt_frechet_wide_scratch_doubles(n, nedges) / nedges + 1) / 2
+                                     : 4 * nn;
     if (nedges == 0) {
         memset(dwell, 0, n * 8);
         memset(trans, 0, nn * 8);
@@ -134,7 +140,9 @@ extern "C" int rt_mjp_frechet_statistics(rt_ctx *ctx, int64_t n, int64_t nedges,
     unsigned char *base = nullptr;
     RT_HIP(hipMalloc((void **)&base, bytes));
     double *dQ = (double *)base, *dW = dQ + nq * nn, *dt = dW + nedges * nn, *dones = dt + nedges;
-    double *dB = dones + nedges, *dE = dB + nedges * mm, *dscale = dE + nedges * mm;
+    double *dB = dones + nedges;
+    if ((uintptr_t)dB & 15) dB += 1;         // (the pair kernel stages 16 bytes a lane; the slack pays)
+    double *dE = dB + nedges * mm, *dscale = dE + nedges * mm;
     double *ddwell = dscale + nedges, *dtrans = ddwell + n;
     int32_t *dqi = (int32_t *)(dtrans + nn), *dident = dqi + nedges;
     std::vector<double> ones((size_t)nedges, 1.0);
@@ -147,15 +155,19 @@ extern "C" int rt_mjp_frechet_statistics(rt_ctx *ctx, int64_t n, int64_t nedges,
     if (e == hipSuccess) e = hipMemcpyAsync(dones, ones.data(), nedges * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dqi, qi.data(), nedges * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(dident, ident.data(), nedges * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
+    if (e == hipSuccess && wide) {
+        // (dB and dE are adjacent: one region of 2 mm doubles per edge)
+        rc = rt_frechet_wide_device(ctx, n, nedges, dQ, dqi, dt, dW, dB, dscale, nullptr, ddwell, dtrans);
+    }
+    if (e == hipSuccess && !wide) {
         hipLaunchKernelGGL(frechet_assemble_kernel, dim3((unsigned)nedges), dim3(256), 0, st, (int)n,
                            dQ, dqi, dt, dW, dB, dscale);
         e = hipGetLastError();
     }
     // expm of every block (order 2n, "rate matrix" = the block, "branch length" = 1)
-    if (e == hipSuccess)
+    if (e == hipSuccess && !wide)
         rc = rt_launch_expm(ctx, 2 * n, nedges, dB, dident, dones, dE, nullptr, nullptr, 0, nullptr);
-    if (e == hipSuccess && rc == RT_OK) {
+    if (e == hipSuccess && rc == RT_OK && !wide) {
         hipLaunchKernelGGL(frechet_contract_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0,
                            st, (int)n, (int)nedges, dQ, dqi, dt, dE, dscale, ddwell, dtrans);
         e = hipGetLastError();

@@ -1,4 +1,5 @@
-// Expected history statistics on the matrix pipe (8 < n <= 64: the codon and compound models).
+// Expected history statistics on the matrix pipe (4 < n <= 64: the codon and compound models;
+// on a resident batch up to 128 states: the switching model, see expect_wsum_wide_kernel).
 //
 // rt_mjp_esd_expectation_weights_obs needs, per edge e = (p -> v) and summed over the sites,
 //     W_e[a][b] = sum_s w_s u_s[a] L_v,s[b],   u = D_p / M_v,   D_v = (P_v^T u) * L_v,
@@ -526,6 +527,94 @@ expect_wsum_kernel(int nops, const double *__restrict__ Uarr, const double *__re
     }
 }
 
+// The site sums for 5 <= NT <= 8 (65 to 128 states).  All NT x NT tile pairs per wave would be
+// 4 NT^2 accumulator registers a lane (256 at NT = 8) and 128 KB of LDS for the wave reduction.
+// Here wave ma owns ROW tile ma of W and all NT column tiles: 4 NT accumulators a lane, U of its
+// own row tile and L of every column tile per site tile.  Every wave needs the same L, so a site
+// tile's L is staged once per workgroup in LDS (NT x 2 KB, two buffers: one barrier a tile) and
+// not fetched NT times from L2.  Every wave walks all site tiles of the chunk in order: no
+// cross-wave reduction, and the sum order is fixed by construction.  The partials keep the
+// [step][chunk][ma][mb][256] layout of the kernel above (expect_finish_kernel serves both).
+// L of an observed leaf comes from the batch's observation image as above: state s of site t of
+// a tile is obs[tile][k][pair s / 8][lane (s % 4) 16 + t][(s / 4) % 2].
+template <int NT, bool WEIGHTS>
+__global__ void __launch_bounds__(64 * NT)
+expect_wsum_wide_kernel(int nops, const double *__restrict__ Uarr, const double *__restrict__ Larr,
+                        const double *__restrict__ weights, long nsites, long nblocks,
+                        double *__restrict__ partial, const int *__restrict__ leaf_k,
+                        const double *__restrict__ obs, int K, int KP)
+{
+    __shared__ __attribute__((aligned(32))) double Lsm[2][NT * 256];
+    const int lane = threadIdx.x & 63;
+    const int ma = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int step = blockIdx.x, chunk = blockIdx.y;
+    const int nb = (int)nblocks;
+    const int per = (nb + EX_CHUNKS - 1) / EX_CHUNKS;
+    const int t0 = chunk * per, t1 = t0 + per < nb ? t0 + per : nb;
+    const size_t tile_stride = (size_t)NT * 256;
+    const int lo = lane & 15, hi = lane >> 4;
+    const int row_off = (lo >> 2) * 64 + 16 * (lo & 3) + 4 * hi;
+    const int lk = leaf_k[step];                 // (uniform)
+    // this thread's four entries of the staged tile: D-layout positions d .. d + 3 = state
+    // 16 mb + 4 r + x of sites t .. t + 3
+    const int d = 4 * (int)threadIdx.x;
+    const int sstate = 16 * (d >> 8) + 4 * ((d & 255) >> 6) + ((d & 63) >> 4), st = d & 15;
+    const bool sok = (sstate >> 3) < KP;         // beyond the last pair: padding
+    const size_t sobs = (size_t)(sok ? sstate >> 3 : 0) * 128 + (size_t)((sstate & 3) * 16 + st) * 2 +
+                        ((sstate >> 2) & 1);
+    auto fetch_l = [&](int tile) {
+        double4_t v;
+        if (lk < 0) {
+            v = *(const double4_t *)(Larr + ((size_t)step * nblocks + tile) * tile_stride + d);
+        } else {
+            const double *po = obs + ((size_t)tile * K + lk) * KP * 128 + sobs;
+#pragma unroll
+            for (int x = 0; x < 4; ++x) v[x] = sok ? po[2 * x] : 0.0;
+        }
+        return v;
+    };
+    auto fetch_u = [&](int tile, double4_t &w) {
+        const long site = (long)tile * 16 + 4 * hi;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const long sc = site + ks < nsites ? site + ks : nsites - 1;
+            const double wgt = WEIGHTS ? weights[sc] : 1.0;
+            w[ks] = site + ks < nsites ? wgt : 0.0;
+        }
+        return *(const double4_t *)(Uarr + ((size_t)step * nblocks + tile) * tile_stride + ma * 256 +
+                                    row_off);
+    };
+    double4_t acc[NT];
+#pragma unroll
+    for (int mb = 0; mb < NT; ++mb) acc[mb] = (double4_t){0.0, 0.0, 0.0, 0.0};
+    if (t0 < t1) {
+        double4_t ln = fetch_l(t0), wn, un = fetch_u(t0, wn);
+        int p = 0;
+        for (int tile = t0; tile < t1; ++tile) {
+            *(double4_t *)(&Lsm[p][d]) = ln;
+            const double4_t u = un, w = wn;
+            const int nx = tile + 1 < t1 ? tile + 1 : tile;      // (the last tile again: unused)
+            ln = fetch_l(nx);
+            un = fetch_u(nx, wn);
+            __syncthreads();
+            // (two buffers: a wave writes buffer p again two tiles on, behind the next barrier)
+#pragma unroll
+            for (int mb = 0; mb < NT; ++mb) {
+                const double4_t l = *(const double4_t *)(&Lsm[p][mb * 256 + row_off]);
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks)
+                    acc[mb] = __builtin_amdgcn_mfma_f64_16x16x4f64(u[ks] * w[ks], l[ks], acc[mb], 0, 0, 0);
+            }
+            p ^= 1;
+        }
+    }
+    double *out = partial + (((size_t)step * EX_CHUNKS + chunk) * NT + ma) * NT * 256;
+#pragma unroll
+    for (int mb = 0; mb < NT; ++mb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) out[(mb * 4 + r) * 64 + lane] = acc[mb][r];
+}
+
 // chunks summed in order, structural zeros of P masked, reference order [node][a][b]
 __global__ void __launch_bounds__(256)
 expect_finish_kernel(int n, int NT, int nops, const int *__restrict__ step_node,
@@ -550,12 +639,13 @@ expect_finish_kernel(int n, int NT, int nops, const int *__restrict__ step_node,
 // chunks are added in order by expect_root_finish_kernel
 constexpr int EX_ROOT_CHUNKS = 64;
 
-__global__ void __launch_bounds__(64)
+// (64 threads for n <= 64, 128 above: one per state; rootpart [chunk][blockDim.x])
+__global__ void __launch_bounds__(128)
 expect_root_kernel(int n, int NT, int root_step, const double *__restrict__ Darr,
                    const double *__restrict__ weights, long nsites, long nblocks,
                    double *__restrict__ rootpart)
 {
-    const int a = threadIdx.x;                   // state (n <= 64)
+    const int a = threadIdx.x;                   // state
     const long per = (nblocks + EX_ROOT_CHUNKS - 1) / EX_ROOT_CHUNKS;
     const long t0 = blockIdx.x * per, t1 = t0 + per < nblocks ? t0 + per : nblocks;
     double sum = 0.0;
@@ -570,18 +660,19 @@ expect_root_kernel(int n, int NT, int root_step, const double *__restrict__ Darr
             }
         }
     }
-    rootpart[blockIdx.x * 64 + a] = sum;
+    rootpart[blockIdx.x * blockDim.x + a] = sum;
 }
 
 __global__ void __launch_bounds__(256)
-expect_root_finish_kernel(int n, const double *__restrict__ rootpart, double *__restrict__ W)
+expect_root_finish_kernel(int n, int stride, const double *__restrict__ rootpart,
+                          double *__restrict__ W)
 {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= n * n) return;
     const int a = e / n, b = e - a * n;
     double sum = 0.0;
     if (b == 0)
-        for (int c = 0; c < EX_ROOT_CHUNKS; ++c) sum += rootpart[c * 64 + a];
+        for (int c = 0; c < EX_ROOT_CHUNKS; ++c) sum += rootpart[c * stride + a];
     W[e] = sum;
 }
 
@@ -685,34 +776,45 @@ int expect_device_passes(rt_ctx *ctx, rt_model *model, rt_sites *s, const double
     const int regslot = s->down_slots - 1;           // the deepest slot: registers
     const size_t down_lds = (size_t)(1 + regslot) * NT * 256 * 8 + (size_t)nops * 8;
     const char *dv = getenv("RAOTEH_EXPECT_DOWN");
-    if (down_lds <= 120 * 1024 && !(dv && strcmp(dv, "global") == 0)) {
-        auto kern = expect_down_lds_kernel<NT, KS>;
-        RT_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)down_lds));
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(64 * NT), down_lds, st, d_PT, nops,
-                           (const int2 *)s->d_down_meta, d_L, d_M, d_D, d_U, d_root_w, (int)n, d_status,
-                           (long)nsites, nblocks, regslot);
-    } else {
+    // (NT > 4: the global form only -- under its three-waves-per-SIMD register budget the LDS
+    // form spills there, and eight waves a workgroup are two per SIMD already)
+    bool down_in_lds = false;
+    if constexpr (NT <= 4) {
+        if (down_lds <= 120 * 1024 && !(dv && strcmp(dv, "global") == 0)) {
+            auto kern = expect_down_lds_kernel<NT, KS>;
+            RT_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)down_lds));
+            hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(64 * NT), down_lds, st, d_PT, nops,
+                               (const int2 *)s->d_down_meta, d_L, d_M, d_D, d_U, d_root_w, (int)n, d_status,
+                               (long)nsites, nblocks, regslot);
+            down_in_lds = true;
+        }
+    }
+    if (!down_in_lds)
         hipLaunchKernelGGL((expect_down_kernel<NT, KS>), dim3((unsigned)nblocks), dim3(64 * NT), 0, st,
                            d_PT, nops, d_parent_step, d_internal, d_L, d_M, d_D, d_U, d_root_w, (int)n,
                            d_status, (long)nsites, nblocks);
-    }
     const int *d_leaf_k = s->d_down_meta + (size_t)nops * 2;
     const int KPo = (KS + 1) / 2;
-    if (d_w)
-        hipLaunchKernelGGL((expect_wsum_kernel<NT, true>), dim3((unsigned)(nops - 1), EX_CHUNKS),
-                           dim3(64 * NT), 0, st, nops, d_U, d_L, d_w, (long)nsites, nblocks, d_part,
-                           d_leaf_k, (const double *)s->d_obs, (int)s->nobs, KPo);
-    else
-        hipLaunchKernelGGL((expect_wsum_kernel<NT, false>), dim3((unsigned)(nops - 1), EX_CHUNKS),
-                           dim3(64 * NT), 0, st, nops, d_U, d_L, d_w, (long)nsites, nblocks, d_part,
-                           d_leaf_k, (const double *)s->d_obs, (int)s->nobs, KPo);
+#define RT_WSUM(KERN)                                                                             \
+    hipLaunchKernelGGL(KERN, dim3((unsigned)(nops - 1), EX_CHUNKS), dim3(64 * NT), 0, st, nops, d_U, \
+                       d_L, d_w, (long)nsites, nblocks, d_part, d_leaf_k, (const double *)s->d_obs, \
+                       (int)s->nobs, KPo)
+    if constexpr (NT <= 4) {
+        if (d_w) RT_WSUM((expect_wsum_kernel<NT, true>));
+        else RT_WSUM((expect_wsum_kernel<NT, false>));
+    } else {
+        if (d_w) RT_WSUM((expect_wsum_wide_kernel<NT, true>));
+        else RT_WSUM((expect_wsum_wide_kernel<NT, false>));
+    }
+#undef RT_WSUM
     hipLaunchKernelGGL(expect_finish_kernel, dim3((unsigned)(nops - 1)), dim3(256), 0, st, (int)n, NT,
                        nops, d_step_node, esd_dev, d_part, d_W);
-    hipLaunchKernelGGL(expect_root_kernel, dim3(EX_ROOT_CHUNKS), dim3(64), 0, st, (int)n, NT, nops - 1,
-                       d_D, d_w, (long)nsites, nblocks, d_rootpart);
+    const int root_threads = n > 64 ? 128 : 64;    // d_rootpart: EX_ROOT_CHUNKS x 128 doubles
+    hipLaunchKernelGGL(expect_root_kernel, dim3(EX_ROOT_CHUNKS), dim3(root_threads), 0, st, (int)n, NT,
+                       nops - 1, d_D, d_w, (long)nsites, nblocks, d_rootpart);
     hipLaunchKernelGGL(expect_root_finish_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, st,
-                       (int)n, d_rootpart, d_W);
+                       (int)n, root_threads, d_rootpart, d_W);
     RT_HIP(hipGetLastError());
     return RT_OK;
 }
@@ -746,7 +848,7 @@ int run_chunk(rt_ctx *ctx, rt_model *model, int64_t n, int64_t nsites, int64_t n
     const auto t1 = now();
     dev_free mem;
     double *d_rootpart, *d_w = nullptr;
-    RT_TRY(mem.alloc(d_rootpart, (size_t)EX_ROOT_CHUNKS * 64));
+    RT_TRY(mem.alloc(d_rootpart, (size_t)EX_ROOT_CHUNKS * 128));
     if (site_weights) {
         RT_TRY(mem.alloc(d_w, (size_t)nsites));
         RT_HIP(hipMemcpyAsync(d_w, site_weights, (size_t)nsites * 8, hipMemcpyHostToDevice, st));
@@ -951,12 +1053,16 @@ int expect_state_get(rt_model *m, expect_state_t **out)
     const size_t nn = (size_t)n * n, ne = (size_t)(N - 1), mm = 4 * nn;
     if (mfma) RT_HIP(hipMalloc((void **)&st->d_PT, (size_t)nops * NT * KP * 128 * 8));
     RT_HIP(hipMalloc((void **)&st->d_W, (size_t)N * nn * 8));
-    RT_HIP(hipMalloc((void **)&st->d_B, ne * mm * 8));
-    RT_HIP(hipMalloc((void **)&st->d_E, ne * mm * 8));
+    if (n > RT_MAX_EXPECT_STATES) {            // the pair kernel's matrices (frechet_wide.hip)
+        RT_HIP(hipMalloc((void **)&st->d_B, rt_frechet_wide_scratch_doubles(n, N - 1) * 8));
+    } else {
+        RT_HIP(hipMalloc((void **)&st->d_B, ne * mm * 8));
+        RT_HIP(hipMalloc((void **)&st->d_E, ne * mm * 8));
+    }
     RT_HIP(hipMalloc((void **)&st->d_scale, ne * 8));
     RT_HIP(hipMalloc((void **)&st->d_ones, ne * 8));
     RT_HIP(hipMalloc((void **)&st->d_out, (2 * (size_t)n + nn) * 8));
-    RT_HIP(hipMalloc((void **)&st->d_rootpart, (size_t)EX_ROOT_CHUNKS * 64 * 8));
+    RT_HIP(hipMalloc((void **)&st->d_rootpart, (size_t)EX_ROOT_CHUNKS * 128 * 8));
     RT_HIP(hipMalloc((void **)&st->d_step_node, (size_t)nops * 4));
     RT_HIP(hipMalloc((void **)&st->d_parent_step, (size_t)nops * 4));
     RT_HIP(hipMalloc((void **)&st->d_ident, ne * 4));
@@ -1009,10 +1115,10 @@ extern "C" int rt_expect_step(rt_model *m, rt_sites *s, int recompute_transition
     }
     const int64_t n = m->n, N = m->nnodes;
     const bool lane = n <= 4;                  // resident in the lane layout: the fused lane kernel
-    if (n > RT_MAX_EXPECT_STATES || N < 2 || s->d_scratch || m->max_depth > RT_FAST_MAX_DEPTH ||
+    if (n > RT_MAX_EXPECT_STEP_STATES || N < 2 || s->d_scratch || m->max_depth > RT_FAST_MAX_DEPTH ||
         s->layout != (lane ? RT_LAYOUT_LANE : RT_LAYOUT_MFMA)) {
         rt_set_error("rt_expect_step: resident batches of n <= %d states on trees the fast "
-                     "kernels take (n=%lld here)", RT_MAX_EXPECT_STATES, (long long)n);
+                     "kernels take (n=%lld here)", RT_MAX_EXPECT_STEP_STATES, (long long)n);
         return RT_ERR_UNSUPPORTED;
     }
     rt_ctx *ctx = m->ctx;
@@ -1073,7 +1179,23 @@ extern "C" int rt_expect_step(rt_model *m, rt_sites *s, int recompute_transition
     case 13: RT_EX(4, 13); break;
     case 14: RT_EX(4, 14); break;
     case 15: RT_EX(4, 15); break;
-    default: RT_EX(4, 16); break;
+    case 16: RT_EX(4, 16); break;
+    case 17: RT_EX(5, 17); break;
+    case 18: RT_EX(5, 18); break;
+    case 19: RT_EX(5, 19); break;
+    case 20: RT_EX(5, 20); break;
+    case 21: RT_EX(6, 21); break;
+    case 22: RT_EX(6, 22); break;
+    case 23: RT_EX(6, 23); break;
+    case 24: RT_EX(6, 24); break;
+    case 25: RT_EX(7, 25); break;
+    case 26: RT_EX(7, 26); break;
+    case 27: RT_EX(7, 27); break;
+    case 28: RT_EX(7, 28); break;
+    case 29: RT_EX(8, 29); break;
+    case 30: RT_EX(8, 30); break;
+    case 31: RT_EX(8, 31); break;
+    default: RT_EX(8, 32); break;
     }
 #undef RT_EX
     RT_TRY(rc);
@@ -1082,9 +1204,13 @@ extern "C" int rt_expect_step(rt_model *m, rt_sites *s, int recompute_transition
     double *d_dwell = st->d_out, *d_rootp = st->d_out + n, *d_trans = st->d_out + 2 * n;
     RT_HIP(hipMemcpy2DAsync(d_rootp, 8, st->d_W, (size_t)n * 8, 8, (size_t)n, hipMemcpyDeviceToDevice,
                             stream));
-    RT_TRY(rt_frechet_statistics_device(ctx, n, N - 1, m->d_Q, m->d_qidx + 1, m->d_t + 1, st->d_W + nn,
-                                        st->d_B, st->d_E, st->d_scale, st->d_ones, st->d_ident, d_dwell,
-                                        d_trans));
+    if (n > RT_MAX_EXPECT_STATES)              // no order-2n block: the pair kernel (d_B: its scratch)
+        RT_TRY(rt_frechet_wide_device(ctx, n, N - 1, m->d_Q, m->d_qidx + 1, m->d_t + 1, st->d_W + nn,
+                                      st->d_B, st->d_scale, nullptr, d_dwell, d_trans));
+    else
+        RT_TRY(rt_frechet_statistics_device(ctx, n, N - 1, m->d_Q, m->d_qidx + 1, m->d_t + 1, st->d_W + nn,
+                                            st->d_B, st->d_E, st->d_scale, st->d_ones, st->d_ident, d_dwell,
+                                            d_trans));
     std::vector<double> out(2 * (size_t)n + nn);
     RT_HIP(hipMemcpyAsync(out.data(), st->d_out, out.size() * 8, hipMemcpyDeviceToHost, stream));
     if (status)

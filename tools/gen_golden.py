@@ -1238,6 +1238,106 @@ def fixture_switching_posteriors(mods, nsites=5):
                 reference_seconds=time.time() - t0)
 
 
+def _offdiag_triples(M):
+    return [[int(a), int(b), float(M[a, b])] for a, b in zip(*np.nonzero(M)) if a != b]
+
+
+def _rates_digraph(R):
+    G = nx.DiGraph()
+    G.add_nodes_from(range(R.shape[0]))
+    for i, j in zip(*np.nonzero(R)):
+        if i != j:
+            G.add_edge(int(i), int(j), weight=float(R[i, j]))
+    return G
+
+
+def _wide_expectation_case(_mjp, name, n, T, root, mats, edge_q, allowed, w):
+    """One record of expectations_wide.json: the reference's numbers for one site; the rate
+    matrices and the transition counts as (c, d, value) triples of the nonzero rates."""
+    t0 = time.time()
+    graphs = [_rates_digraph(R) for R in mats]
+    for (a, b), k in edge_q.items():
+        if k:
+            T[a][b]['Q'] = graphs[k]
+    distn = dict((i, float(p)) for i, p in enumerate(w) if p)
+    dwell, init, trans = _mjp.get_expected_history_statistics(
+        T, allowed, root, root_distn=distn, Q_default=graphs[0])
+    return dict(name=name, nstates=n, root=int(root), root_distn=[float(p) for p in w],
+                edges=[[int(a), int(b), float(d['weight']), edge_q[(a, b)]]
+                       for a, b, d in T.edges(data=True)],
+                Q_offdiagonal=[_offdiag_triples(R) for R in mats],
+                allowed=set_json(allowed),
+                dwell=[float(dwell.get(s, 0.0)) for s in range(n)],
+                init=[float(init.get(s, 0.0)) for s in range(n)],
+                trans=[[int(sa), int(sb), float(dat['weight'])]
+                       for sa, sb, dat in trans.edges(data=True)],
+                reference_seconds=time.time() - t0)
+
+
+def fixture_expectations_wide(mods):
+    """Expected history statistics above 64 states, from the reference's
+    _mjp.get_expected_history_statistics (raoteh/sampler/_mjp.py:431-595) through the
+    harness of fixture_expectations, one site per case on five-node trees (the reference
+    calls expm_frechet once per state and per nonzero rate on every edge: minutes at 122
+    states):
+     * 'boundary_66': 66 states, random sparse rates drawn as fixture_expectations draws
+       them (nine in ten off-diagonal rates struck, a cycle kept), one edge with its own
+       matrix, allowed-state sets at the leaves, a random root prior;
+     * 'switching_122': the 122-state switching model of _switching_columns (column 0:
+       its compound rate matrix and root prior), leaf sets {c, 61 + c} of the column's
+       first three codons.
+    Rate matrices and transition counts are stored as (c, d, value) triples."""
+    t0 = time.time()
+    _mjp = _reference_mjp(mods)
+    shape = ((0, 1), (0, 2), (2, 3), (2, 4))
+    cases = []
+    # ---- just past the boundary
+    rng = np.random.RandomState(660066)
+    n = 66
+    T = nx.Graph()
+    for a, b in shape:
+        T.add_edge(a, b, weight=float(rng.uniform(0.05, 1.2)))
+
+    def random_rates():
+        R = rng.exponential(size=(n, n))
+        R[rng.uniform(size=(n, n)) < 0.9] = 0.0
+        np.fill_diagonal(R, 0.0)
+        for i in range(n):                   # a cycle keeps every state reachable
+            if R[i, (i + 1) % n] == 0:
+                R[i, (i + 1) % n] = float(rng.uniform(0.2, 1.0))
+        return R
+    mats = [random_rates(), random_rates()]
+    edge_q = dict(((a, b), 0) for a, b in T.edges())
+    edge_q[(2, 3)] = 1
+    allowed = dict((v, set(range(n))) for v in T)
+    for v in (1, 3, 4):
+        allowed[v] = set(int(x) for x in rng.permutation(n)[:int(rng.randint(1, 4))])
+    w = rng.exponential(size=n)
+    w /= w.sum()
+    cases.append(_wide_expectation_case(_mjp, 'boundary_66', n, T, 0, mats, edge_q, allowed, w))
+    # ---- the switching model
+    header, columns = _switching_columns(mods, 1)
+    col = columns[0]
+    nstates, n = header['nstates'], header['ncompound']
+    R = np.array(col['Q_compound_dense'], dtype=float)
+    np.fill_diagonal(R, 0.0)
+    T = nx.Graph()
+    for (a, b), t in zip(shape, (0.08, 0.15, 0.3, 0.6)):
+        T.add_edge(a, b, weight=t)
+    from raoteh_amd import io as rio
+    code = rio.read_genetic_code(os.path.join(os.path.dirname(HERE), 'tests', 'golden', 'p53',
+                                              'universal.code.txt'))
+    codon_to_state = dict((c, s) for s, r, c in code)
+    allowed = dict((v, set(range(n))) for v in T)
+    for v, codon in zip((1, 3, 4), col['column'][:3]):
+        s = codon_to_state[codon]
+        allowed[v] = {s, nstates + s}
+    w = np.asarray(col['compound_distn_dense'], dtype=float)
+    cases.append(_wide_expectation_case(_mjp, 'switching_122', n, T, 0, [R],
+                                        dict(((a, b), 0) for a, b in T.edges()), allowed, w))
+    return dict(cases=cases, reference_seconds=time.time() - t0)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(os.path.dirname(HERE),
@@ -1271,6 +1371,7 @@ def main():
         spectral=lambda: fixture_spectral(mods),
         switching=lambda: fixture_switching(mods),
         switching_posteriors=lambda: fixture_switching_posteriors(mods),
+        expectations_wide=lambda: fixture_expectations_wide(mods),
         tmjp_inhomogeneous=lambda: fixture_tmjp_inhomogeneous(mods),
         pyfelscore_calls=lambda: fixture_pyfelscore_calls(mods),
     )

@@ -1,6 +1,7 @@
 """Diagnostics: seconds per rt_expect_step call (resident batch) for one bench configuration;
 under `rocprofv3 --kernel-trace --stats` for the kernel split.
-    python tools/time_expect_step.py [c3|c5|c2] [calls]"""
+    python tools/time_expect_step.py [c3|c5|c2|c6] [calls]
+(c6: the 122-state switching model, 127 nodes, 847 nonzero rates: the wide kernels.)"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
