@@ -425,6 +425,39 @@ int rt_sites_posteriors(rt_model *model, rt_sites *sites, int recompute_transiti
             int64_t n_edge_sets, const uint64_t *edge_sets,
             int64_t n_marginal_nodes, const int64_t *marginal_nodes,
             double *node_values, double *edge_values, double *marginals, int32_t *status);
+/* The reference's branch-site map, examples/code2x3/extras.get_expected_ntransitions
+ * (extras.py:19-132), for every site of a RESIDENT batch and up to RT_MAX_BRANCH_COEFS coefficient
+ * matrices in one call: per site, per branch, the conditional expectation of a linear statistic
+ * of the history on that branch.  One coefficient matrix E (f64[n][n]) means
+ *   E[c][d], c != d   the weight of one c -> d transition
+ *   E[c][c]           the weight of a unit of time spent in c
+ * so on the edge above node v, with that edge's rate matrix Q_v and length t_v, the direction is
+ * C_v[c][d] = E[c][d] Q_v[c][d] off the diagonal, C_v[c][c] = E[c][c], and with
+ * G_v = L(t_v Q_v, t_v C_v) (the Frechet derivative of the matrix exponential) and J_v, P_v the
+ * joint endpoint posterior and the transition matrix of the edge
+ *   values[i][v][k] = sum_{a,b} J_v[a][b] G_v[a][b] / P_v[a][b]     f64[nsites][nnodes][n_coefs]
+ *                     (keyed by the child's preorder index; the root's slot is 0)
+ *   edge_sums[v][k] = sum_i w_i values[i][v][k]                     f64[nnodes][n_coefs]
+ *                     (w: rt_sites_set_weights, default 1; reduced on the device, fixed order)
+ * With a zero diagonal E is exactly the reference's E (an indicator of the synonymous changes,
+ * say: the expected number of them on every branch).  E = identity gives the branch length;
+ * E = ones off the diagonal and diag(Q) on it gives C = Q and values = t_v d log L_i / d t_v, the
+ * analytic branch-length gradient.  Coefficients may be negative; an all-zero matrix gives zeros;
+ * they must be finite.
+ *   status[i]: as rt_sites_posteriors (a site of zero likelihood: RT_SITE_ZERO_PROB, its values
+ *              are 0 and it adds nothing to edge_sums)
+ * values, edge_sums and status may each be NULL; only what is given crosses PCIe (the per-site
+ * array is large: nsites * nnodes * n_coefs doubles).  Every batch rt_sites_create makes for
+ * 2 <= n <= 128 (dense observations are used as values at every n), per-edge rate matrices, any
+ * tree rt_sites_posteriors takes.  The rates must come from rt_model_set_rates (the derivative
+ * needs Q): RT_ERR_INVALID for a model with spectral rates or with transitions set directly.
+ * RT_ERR_UNSUPPORTED: a "rescale" batch, a tree deeper than the fast kernels take, nnodes < 2,
+ * more than RT_MAX_BRANCH_COEFS matrices, more than 96 GB of scratch.  Synchronous; the batch
+ * keeps its kernel, log-likelihoods, status and totals; two calls return the same bits.      */
+#define RT_MAX_BRANCH_COEFS 8
+int rt_sites_branch_expectations(rt_model *model, rt_sites *sites, int recompute_transitions,
+            int64_t n_coefs, const double *coefs, double *values, double *edge_sums,
+            int32_t *status);
 /* weights f64[nsites] (copied to the device) or NULL = every site counts once           */
 int rt_sites_set_weights(rt_sites *sites, const double *weights);
 /* loglik f64[nsites] (-inf where status has RT_SITE_ZERO_PROB),

@@ -31,6 +31,7 @@ RT_K_EXPM, RT_K_PRUNE, RT_K_REDUCE, RT_K_COMBINE = 0, 1, 2, 3
 RT_SITE_ZERO_PROB = 1
 RT_SITE_NEGATIVE = 4
 RT_MAX_POSTERIOR_SETS = 8
+RT_MAX_BRANCH_COEFS = 8
 RT_MAX_EXPECT_STATES = 64
 RT_MAX_EXPECT_STEP_STATES = 128
 
@@ -129,6 +130,8 @@ SIGNATURES = {
     'rt_expect_step': (c_int, [c_void_p, c_void_p, c_int, _p_f64, _p_f64, _p_f64, _p_i32]),
     'rt_sites_posteriors': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64,
                                     c_void_p, c_int64, _p_i64, _p_f64, _p_f64, _p_f64, _p_i32]),
+    'rt_sites_branch_expectations': (c_int, [c_void_p, c_void_p, c_int, c_int64, _p_f64, _p_f64,
+                                             _p_f64, _p_i32]),
     'rt_sites_set_weights': (c_int, [c_void_p, _p_f64]),
     'rt_sites_destroy': (c_int, [c_void_p]),
     'rt_sites_device_bytes': (c_int64, [c_void_p]),

@@ -18,6 +18,12 @@ examples/p53/p53.py:88-100):
   get_expected_history_statistics_batch(T, root, nstates, sites, ...)
   get_posterior_summaries_batch(T, root, nstates, sites, ...)   (kitchen_sink over sites)
 
+and the branch-site map of the reference's worked example:
+
+  get_expected_ntransitions(T, node_to_allowed_states, root, nstates, root_distn,
+                            Q_default, E)           examples/code2x3/extras.py:19-132
+  get_expected_ntransitions_batch(T, root, nstates, sites, ...)
+
 Everything numerical runs in hand-written HIP kernels behind the C ABI.
 """
 from __future__ import annotations
@@ -32,7 +38,8 @@ from .device import TreeModel, get_context
 __all__ = ['custom_expm', 'get_expm_augmented_tree', 'get_likelihood',
            'get_expected_history_statistics', 'get_expected_history_statistics_batch',
            'get_log_likelihoods', 'get_total_log_likelihood',
-           'allowed_states_to_masks', 'get_posterior_summaries_batch']
+           'allowed_states_to_masks', 'get_posterior_summaries_batch',
+           'get_expected_ntransitions', 'get_expected_ntransitions_batch']
 
 
 def custom_expm(Q, weight):
@@ -387,3 +394,93 @@ def get_posterior_summaries_batch(T, root, nstates, sites=None, root_distn=None,
     finally:
         batch.close()
         model.close()
+
+
+def _reference_coefs(T, root, nstates, Q_default, E):
+    """The reference's E (extras.py:66-68, 109-111: C = E * Q, diagonal included) in the
+    device call's terms, where a diagonal entry weighs time itself: f64[k, n, n]."""
+    if E is None:
+        E = np.ones((nstates, nstates))
+        np.fill_diagonal(E, 0)
+    E = np.array(E, dtype=np.float64)
+    single = E.ndim == 2
+    if single:
+        E = E[None]
+    if E.ndim != 3 or E.shape[1:] != (nstates, nstates):
+        raise ValueError('E must be (%d, %d)' % (nstates, nstates))
+    diag = np.arange(nstates)
+    if E[:, diag, diag].any():
+        mats = _edge_rates(T, root, Q_default)[1]
+        if len(mats) != 1:
+            raise ValueError('a non-zero diagonal of E needs one rate matrix for all edges')
+        E[:, diag, diag] *= np.diag(mats[0])
+    return E, single
+
+
+def get_expected_ntransitions_batch(T, root, nstates, sites=None, root_distn=None,
+                                    Q_default=None, E=None, weights=None, per_site=True,
+                                    obs_nodes=None, data=None, kind='state'):
+    """The reference's get_expected_ntransitions over an alignment in one device call
+    (TreeModel.branch_expectations): ``sites`` a list of node_to_allowed_states dicts, or the
+    array form ``obs_nodes`` + ``data`` + ``kind`` of get_log_likelihoods; E one coefficient
+    matrix or up to eight.  Returns a dict:
+      values     {(na, nb): f64[nsites] (one E) or f64[nsites, len(E)]}   (per_site=True)
+      edge_sums  {(na, nb): float or f64[len(E)]}   the sums over sites, weighted by ``weights``
+      status     int32[nsites]  (1: the site has likelihood 0, 2: a zero denominator)
+    with the edges directed as nx.bfs_edges(T, root) directs them."""
+    if root not in T:
+        raise ValueError('the specified root is not in the tree')
+    coefs, single = _reference_coefs(T, root, nstates, Q_default, E)
+    if sites is not None:
+        obs_nodes = [v for v in TreeArrays(T, root).preorder_nodes
+                     if any(d is not None and v in d for d in sites)]
+        full = set(range(nstates))
+        data = allowed_states_to_masks([dict((v, (d or {}).get(v, full)) for v in obs_nodes)
+                                        for d in sites], obs_nodes, nstates)
+        kind = 'mask'
+    nsites = len(data)
+    if not len(obs_nodes):                   # nothing observed anywhere: the root, unrestricted
+        obs_nodes = [root]
+        data = np.ones((nsites, 1, nstates))
+        kind = 'dense'
+    model, batch = _build(T, root, nstates, obs_nodes, data, kind, root_distn, Q_default, None)
+    try:
+        if weights is not None:
+            batch.set_weights(weights)
+        got = model.branch_expectations(batch, coefs, per_site=per_site)
+        ta = model.tree
+        out = dict(status=got.status, edge_sums={})
+        if per_site:
+            out['values'] = {}
+        for i, v in enumerate(got.nodes):
+            if not i:
+                continue
+            edge = (ta.preorder_nodes[ta.parent[i]], v)
+            out['edge_sums'][edge] = float(got.edge_sums[i, 0]) if single else got.edge_sums[i]
+            if per_site:
+                out['values'][edge] = got.values[:, i, 0] if single else got.values[:, i, :]
+        return out
+    finally:
+        batch.close()
+        model.close()
+
+
+def get_expected_ntransitions(T, node_to_allowed_states, root, nstates,
+                              root_distn=None, Q_default=None, E=None):
+    """One site, as the reference (examples/code2x3/extras.py:19-132): dict edge -> expected
+    number of transitions on that edge conditional on the data, weighted by the coefficients
+    E (default: every transition counts once), edges as nx.bfs_edges(T, root) directs them.
+    One Frechet derivative per edge and the passes run on the device
+    (rt_sites_branch_expectations)."""
+    if E is not None and np.ndim(E) != 2:
+        raise ValueError('E must be (%d, %d)' % (nstates, nstates))
+    out = get_expected_ntransitions_batch(T, root, nstates, sites=[node_to_allowed_states],
+                                          root_distn=root_distn, Q_default=Q_default, E=E)
+    st = int(out['status'][0])
+    if st & 1:
+        from ._util import StructuralZeroProb
+        raise StructuralZeroProb('the site has likelihood zero')
+    if st:
+        from ._util import NumericalZeroProb
+        raise NumericalZeroProb('the denominator is zero')
+    return dict((edge, float(x[0])) for edge, x in out['values'].items())

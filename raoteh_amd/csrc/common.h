@@ -402,12 +402,25 @@ int rt_frechet_statistics_device(rt_ctx *ctx, int64_t n, int64_t nedges, const d
                                  const int32_t *dqidx, const double *dt, const double *dW,
                                  double *dB, double *dE, double *dscale, const double *dones,
                                  const int32_t *dident, double *ddwell, double *dtrans);
+// ... its two halves for a caller that wants the derivatives themselves (branch_expect.hip): the
+// block exponentials without the contraction, then dG[e][a][b] = t_e L(t_e Q_e, C_e)[a][b] for
+// dW[e] = C_e^T
+int rt_frechet_blocks_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double *dQ,
+                             const int32_t *dqidx, const double *dt, const double *dW, double *dB,
+                             double *dE, double *dscale, const double *dones, const int32_t *dident);
+int rt_frechet_extract_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double *dt,
+                              const double *dE, const double *dscale, double *dG);
 // frechet_wide.hip: the same for 64 < n <= 128 by the pair recurrence (no order-2n block);
 // dS: rt_frechet_wide_scratch_doubles(n, nedges) doubles, dinfo (optional) {degree, squarings}
 size_t rt_frechet_wide_scratch_doubles(int64_t n, int64_t nedges);
 int rt_frechet_wide_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double *dQ,
                            const int32_t *dqidx, const double *dt, const double *dW, double *dS,
                            double *dscale, int32_t *dinfo, double *ddwell, double *dtrans);
+int rt_frechet_wide_pairs_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double *dQ,
+                                 const int32_t *dqidx, const double *dt, const double *dW, double *dS,
+                                 double *dscale, int32_t *dinfo);
+int rt_frechet_wide_extract_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double *dt,
+                                   const double *dS, const double *dscale, double *dG);
 // ... and what rt_expect_step keeps with a model (rt_model_destroy)
 void rt_expect_state_release(rt_model *m);
 // passes.hip: the n <= 8 form of rt_expect_step's passes (W and status on the device)

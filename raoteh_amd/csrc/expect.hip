@@ -82,6 +82,21 @@ frechet_contract_kernel(int n, int nedges, const double *__restrict__ Q,
     if (c == d) dwell[c] = dw;
 }
 
+// rt_sites_branch_expectations: the derivative of every edge itself, transposed, unscaled and
+// times the branch length, G[e][a][b] = t_e scale[e] M_e[b][a]  (M_e = L(t Q^T, C^T) = L(t Q, C)^T)
+__global__ void __launch_bounds__(256)
+frechet_extract_kernel(int n, const double *__restrict__ t, const double *__restrict__ E,
+                       const double *__restrict__ scale, double *__restrict__ G)
+{
+    const int e = blockIdx.x;
+    const int nn = n * n, m = 2 * n;
+    const double f = t[e] * scale[e];
+    for (int k = threadIdx.x; k < nn; k += 256) {
+        const int a = k / n, b = k - a * n;
+        G[(long)e * nn + k] = f * E[(long)e * m * m + (long)b * m + (n + a)];
+    }
+}
+
 }  // namespace
 
 // The three launches on device-resident operands, asynchronously on the context's stream:
@@ -94,12 +109,31 @@ int rt_frechet_statistics_device(rt_ctx *ctx, int64_t n, int64_t nedges, const d
 {
     hipStream_t st = ctx->stream;
     const size_t nn = (size_t)n * n;
-    hipLaunchKernelGGL(frechet_assemble_kernel, dim3((unsigned)nedges), dim3(256), 0, st, (int)n, dQ,
-                       dqidx, dt, dW, dB, dscale);
-    RT_HIP(hipGetLastError());
-    RT_TRY(rt_launch_expm(ctx, 2 * n, nedges, dB, dident, dones, dE, nullptr, nullptr, 0, nullptr));
+    RT_TRY(rt_frechet_blocks_device(ctx, n, nedges, dQ, dqidx, dt, dW, dB, dE, dscale, dones, dident));
     hipLaunchKernelGGL(frechet_contract_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st,
                        (int)n, (int)nedges, dQ, dqidx, dt, dE, dscale, ddwell, dtrans);
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+// ... the part before the contraction: dE holds the block exponentials, whose upper right
+// corners are M_e / scale[e]
+int rt_frechet_blocks_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double *dQ,
+                             const int32_t *dqidx, const double *dt, const double *dW, double *dB,
+                             double *dE, double *dscale, const double *dones, const int32_t *dident)
+{
+    hipLaunchKernelGGL(frechet_assemble_kernel, dim3((unsigned)nedges), dim3(256), 0, ctx->stream,
+                       (int)n, dQ, dqidx, dt, dW, dB, dscale);
+    RT_HIP(hipGetLastError());
+    return rt_launch_expm(ctx, 2 * n, nedges, dB, dident, dones, dE, nullptr, nullptr, 0, nullptr);
+}
+
+// ... and the derivatives themselves out of dE: dG [nedges][n][n], row = state at the parent
+int rt_frechet_extract_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double *dt,
+                              const double *dE, const double *dscale, double *dG)
+{
+    hipLaunchKernelGGL(frechet_extract_kernel, dim3((unsigned)nedges), dim3(256), 0, ctx->stream,
+                       (int)n, dt, dE, dscale, dG);
     RT_HIP(hipGetLastError());
     return RT_OK;
 }

@@ -292,6 +292,24 @@ frechet_pair_contract_kernel(int n, int NT, int nedges, const double *__restrict
     if (c == d) dwell[c] = dw;
 }
 
+// rt_sites_branch_expectations: the derivative of every edge itself, transposed, unscaled and
+// times the branch length, G[e][a][b] = t_e scale[e] M_e[b][a]  (M_e = L(t Q^T, C^T) = L(t Q, C)^T)
+__global__ void __launch_bounds__(256)
+frechet_pair_extract_kernel(int n, int NT, const double *__restrict__ t,
+                            const double *__restrict__ scratch, const double *__restrict__ scale,
+                            double *__restrict__ G)
+{
+    const int e = blockIdx.x;
+    const int nn = n * n;
+    const size_t MS = (size_t)256 * NT * NT;
+    const double *L = scratch + ((size_t)e * FM_COUNT + FM_TL) * MS;
+    const double f = t[e] * scale[e];
+    for (int k = threadIdx.x; k < nn; k += 256) {
+        const int a = k / n, b = k - a * n;      // M_e[b][a]: row b, column a of the fragment image
+        G[(size_t)e * nn + k] = f * L[(size_t)(b >> 2) * (64 * NT) + (a >> 4) * 64 + (b & 3) * 16 + (a & 15)];
+    }
+}
+
 }  // namespace
 
 size_t rt_frechet_wide_scratch_doubles(int64_t n, int64_t nedges)
@@ -300,18 +318,17 @@ size_t rt_frechet_wide_scratch_doubles(int64_t n, int64_t nedges)
     return (size_t)nedges * FM_COUNT * 256 * nt * nt;
 }
 
-// 64 < n <= 128: the pair kernel and the contraction on device-resident operands, asynchronously
-// on the context's stream.  dS: rt_frechet_wide_scratch_doubles(n, nedges) doubles; dinfo
-// (optional) int32[nedges][2] = {degree, squarings}.
-int rt_frechet_wide_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double *dQ,
-                           const int32_t *dqidx, const double *dt, const double *dW, double *dS,
-                           double *dscale, int32_t *dinfo, double *ddwell, double *dtrans)
+// 64 < n <= 128: the pair kernel on device-resident operands, asynchronously on the context's
+// stream.  dS: rt_frechet_wide_scratch_doubles(n, nedges) doubles; dinfo (optional)
+// int32[nedges][2] = {degree, squarings}.
+int rt_frechet_wide_pairs_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double *dQ,
+                                 const int32_t *dqidx, const double *dt, const double *dW, double *dS,
+                                 double *dscale, int32_t *dinfo)
 {
     RT_REQUIRE(n > 64 && n <= 128, "the pair kernel serves 64 < n <= 128 (n=%lld)", (long long)n);
     hipStream_t st = ctx->stream;
     const int nt = (int)((n + 15) / 16);
     const size_t lds = (size_t)256 * nt * nt * 8;
-    const size_t nn = (size_t)n * n;
 #define RT_FW(NTV)                                                                              \
     do {                                                                                        \
         RT_HIP(hipFuncSetAttribute((const void *)frechet_pair_kernel<NTV>,                      \
@@ -327,8 +344,29 @@ int rt_frechet_wide_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double 
     }
 #undef RT_FW
     RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+// ... followed by the contraction over the edges
+int rt_frechet_wide_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double *dQ,
+                           const int32_t *dqidx, const double *dt, const double *dW, double *dS,
+                           double *dscale, int32_t *dinfo, double *ddwell, double *dtrans)
+{
+    RT_TRY(rt_frechet_wide_pairs_device(ctx, n, nedges, dQ, dqidx, dt, dW, dS, dscale, dinfo));
+    const int nt = (int)((n + 15) / 16);
+    const size_t nn = (size_t)n * n;
     hipLaunchKernelGGL(frechet_pair_contract_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0,
-                       st, (int)n, nt, (int)nedges, dQ, dqidx, dt, dS, dscale, ddwell, dtrans);
+                       ctx->stream, (int)n, nt, (int)nedges, dQ, dqidx, dt, dS, dscale, ddwell, dtrans);
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+// ... or by the derivatives themselves: dG [nedges][n][n], row = state at the parent
+int rt_frechet_wide_extract_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double *dt,
+                                   const double *dS, const double *dscale, double *dG)
+{
+    hipLaunchKernelGGL(frechet_pair_extract_kernel, dim3((unsigned)nedges), dim3(256), 0, ctx->stream,
+                       (int)n, (int)((n + 15) / 16), dt, dS, dscale, dG);
     RT_HIP(hipGetLastError());
     return RT_OK;
 }

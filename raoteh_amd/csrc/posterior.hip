@@ -23,13 +23,12 @@
 // order), so two calls give the same bits.  Nothing of the batch is written: its own pruning
 // kernel, log-likelihoods, status and totals stay as they were.
 #include "common.h"
+#include "post_common.h"
 
 #include <algorithm>
 #include <vector>
 
 namespace {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 constexpr int PS_MAX = RT_MAX_POSTERIOR_SETS;
 
@@ -225,30 +224,7 @@ post_down_kernel(const double *__restrict__ PfragT, int nops, const int4 *__rest
     if (bad && site_ok) atomicOr(&status[site], 2);
 }
 
-// n <= 4: one lane per site.  The observation of stream position k from the batch's lane-family
-// image (dense pairs, or one byte per leaf: a state or an allowed-set mask; passes.hip
-// sets_from_lane_batch_kernel reads the same layouts).
-template <int N>
-__device__ inline void lane_obs(const void *obs, int compact, int K, int block_sites, long site, int k,
-                                double (&x)[N])
-{
-    const long blk = site / block_sites;
-    const int ln = (int)(site - blk * block_sites);
-    if (compact) {
-        const int KQ = (K + 3) / 4;
-        const unsigned w = ((const unsigned *)obs)[((size_t)blk * KQ + (k >> 2)) * block_sites + ln];
-        const unsigned b = (w >> (8 * (k & 3))) & 255u;
-#pragma unroll
-        for (int s = 0; s < N; ++s)
-            x[s] = compact == 2 ? (double)((b >> s) & 1u) : (b >= (unsigned)N || b == (unsigned)s) ? 1.0 : 0.0;
-    } else {
-        constexpr int hp = ((N + 1) & ~1) / 2;
-        const double *o = (const double *)obs + (((size_t)blk * K + k) * hp * block_sites + ln) * 2;
-#pragma unroll
-        for (int s = 0; s < N; ++s) x[s] = o[(size_t)(s >> 1) * block_sites * 2 + (s & 1)];
-    }
-}
-
+// n <= 4: one lane per site (lane_obs of post_common.h reads the observations);
 // arrays [node][state][site]; nodes in preorder (a parent before its children)
 template <int N>
 __global__ void __launch_bounds__(256)
@@ -379,17 +355,6 @@ int launch_down(rt_ctx *ctx, const double *d_PT, int nops, const int4 *d_steps, 
     return RT_OK;
 }
 
-// byte offsets of the call's pieces in the context's scratch (16-byte aligned)
-struct post_plan {
-    size_t total = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t o = total;
-        total += (bytes + 255) / 256 * 256;
-        return o;
-    }
-};
-
 }  // namespace
 
 extern "C" int rt_sites_posteriors(rt_model *m, rt_sites *s, int recompute_transitions,
@@ -503,14 +468,7 @@ extern "C" int rt_sites_posteriors(rt_model *m, rt_sites *s, int recompute_trans
     RT_HIP(hipMemcpyAsync(d_masks, masks.data(), masks.size() * 8, hipMemcpyHostToDevice, st));
     std::vector<int32_t> table, step_node;       // (alive until the synchronisation below)
     if (lane) {
-        // [parent][stream position][marginal row] per node
-        table.assign((size_t)3 * N, -1);
-        for (int64_t v = 0; v < N; ++v) {
-            table[(size_t)v] = v ? m->parent[(size_t)v] : 0;
-            table[(size_t)2 * N + v] = marg_row[(size_t)v];
-        }
-        for (const rt_op &op : s->ops)           // (the stream is in schedule order)
-            if (op.obs >= 0) table[(size_t)N + op.node] = op.obs;
+        post_lane_table(m, s, marg_row.data(), &table);
         int *d_tab = (int *)(base + o_ptab);
         RT_HIP(hipMemcpyAsync(d_tab, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
         const unsigned grid = (unsigned)((nsites + 255) / 256);
@@ -529,22 +487,10 @@ extern "C" int rt_sites_posteriors(rt_model *m, rt_sites *s, int recompute_trans
         RT_HIP(hipGetLastError());
     } else {
         // the step table of the downward pass
-        std::vector<int> step_of((size_t)N, -1);
-        for (int i = 0; i < nops; ++i) step_of[(size_t)x->ops[(size_t)i].node] = i;
-        RT_REQUIRE(nops == N && x->ops[(size_t)nops - 1].dst < 0, "unexpected schedule");
-        table.assign((size_t)nops * 4, -1);
-        for (int i = 0; i < nops; ++i) {
-            const rt_op &op = x->ops[(size_t)i];
-            table[(size_t)i * 4] = op.node;
-            table[(size_t)i * 4 + 1] = i + 1 < nops ? step_of[(size_t)m->parent[(size_t)op.node]] : 0;
-            table[(size_t)i * 4 + 2] = (op.pop < 0 && op.obs >= 0) ? op.obs : -1;
-            table[(size_t)i * 4 + 3] = marg_row[(size_t)op.node];
-        }
+        RT_TRY(post_step_table(m, x, marg_row.data(), &table, &step_node));
         int4 *d_steps = (int4 *)(base + o_steps);
         double *d_PT = (double *)(base + o_PT);
         int *d_step_node = (int *)(base + o_ptab);
-        step_node.assign((size_t)nops, 0);
-        for (int i = 0; i < nops; ++i) step_node[(size_t)i] = x->ops[(size_t)i].node;
         RT_HIP(hipMemcpyAsync(d_steps, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
         RT_HIP(hipMemcpyAsync(d_step_node, step_node.data(), (size_t)nops * 4, hipMemcpyHostToDevice, st));
         // upward pass: the split-M interpreter kernel with L and M of every step stored (its own

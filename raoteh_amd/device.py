@@ -25,7 +25,7 @@ from . import _lib
 from ._tree import TreeArrays
 
 __all__ = ['Context', 'get_context', 'TreeModel', 'SiteBatch', 'device_count', 'Posteriors',
-           'states_to_mask']
+           'states_to_mask', 'BranchExpectations', 'check_branch_coefs']
 
 # At interpreter shutdown objects are finalised in arbitrary order (a model
 # after its context, say); the process is going away, so skip the native
@@ -86,6 +86,34 @@ def states_to_mask(states, nstates):
 # status int32[nsites] (0 ok, 1 zero likelihood, 2 zero denominator)
 Posteriors = collections.namedtuple(
     'Posteriors', 'node_values edge_values marginals status nodes marginal_nodes')
+
+
+# TreeModel.branch_expectations: values [nsites, nnodes, ncoefs] (or None), edge_sums
+# [nnodes, ncoefs], both keyed by the edge's child in the preorder `nodes` (0 at the root),
+# status int32[nsites] as Posteriors
+BranchExpectations = collections.namedtuple('BranchExpectations', 'values edge_sums status nodes')
+
+
+def check_branch_coefs(coefs, nstates):
+    """One (n, n) coefficient matrix or a sequence of them -> f64[ncoefs, n, n] for
+    rt_sites_branch_expectations.  ValueError for another shape, no matrix or more than
+    RT_MAX_BRANCH_COEFS of them, or a coefficient that is not finite."""
+    try:
+        E = np.array(coefs, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('coefs must be one (%d, %d) array or a sequence of them'
+                         % (nstates, nstates))
+    if E.ndim == 2:
+        E = E[None]
+    if E.ndim != 3 or E.shape[1:] != (nstates, nstates):
+        raise ValueError('coefs must be one (%d, %d) array or a sequence of them, not %s'
+                         % (nstates, nstates, E.shape))
+    if not 1 <= E.shape[0] <= _lib.RT_MAX_BRANCH_COEFS:
+        raise ValueError('between 1 and %d coefficient matrices per call (%d here)'
+                         % (_lib.RT_MAX_BRANCH_COEFS, E.shape[0]))
+    if not np.isfinite(E).all():
+        raise ValueError('the coefficients must be finite')
+    return np.ascontiguousarray(E)
 
 
 def _mask_states(mask, nstates):
@@ -547,6 +575,7 @@ class TreeModel(object):
         _lib.check(_lib.lib().rt_model_set_rates(
             self._h, _ptr(Q, c_double), Q.shape[0],
             None if nq is None else _ptr(nq, c_int64), _ptr(t, c_double)))
+        self._rates = (Q.copy(), t.copy())      # (branch_length_gradient builds its E from Q)
 
     def set_rates_spectral(self, A, lam, B, D=None, t=None):
         """One time-reversible rate matrix given by its spectral decomposition
@@ -567,6 +596,7 @@ class TreeModel(object):
         _lib.check(_lib.lib().rt_model_set_rates_spectral(
             self._h, _ptr(A, c_double), _ptr(lam, c_double), _ptr(B, c_double),
             None if D is None else _ptr(D, c_double), _ptr(t, c_double)))
+        self._rates = None
 
     def recompute_transitions(self):
         _lib.check(_lib.lib().rt_model_recompute_transitions(self._h))
@@ -730,6 +760,62 @@ class TreeModel(object):
         if len(uniq) != len(mnodes):
             marg = marg[:, [uniq.index(v) for v in mnodes]]
         return Posteriors(node_values, edge_values, marg, status, nodes, mnodes)
+
+    def branch_expectations(self, batch, coefs, per_site=True, recompute_transitions=False):
+        """rt_sites_branch_expectations: the reference's branch-site map
+        (examples/code2x3/extras.get_expected_ntransitions) for every site of the resident batch.
+        coefs: one (n, n) array E or up to RT_MAX_BRANCH_COEFS (8) of them; E[c, d] weighs a
+        c -> d transition, E[c, c] a unit of time spent in c.  Returns a BranchExpectations
+        tuple: values[i, v, k] the conditional expectation at site i on the edge above preorder
+        node v (None with per_site=False: the array never leaves the device), edge_sums[v, k]
+        its site-weighted sum (SiteBatch.set_weights), status, nodes.  The rates must have
+        been set with set_rates."""
+        n = self.nstates
+        E = check_branch_coefs(coefs, n)
+        K = E.shape[0]
+        ta = self.tree
+        N, S = ta.nnodes, batch.nsites
+        nodes = list(ta.preorder_nodes)
+        values = np.zeros((S, N, K)) if per_site else None
+        edge_sums = np.zeros((N, K))
+        status = np.zeros(S, dtype=np.int32)
+        if N == 1:
+            # one node, no edges: only the status of the sites is to be had
+            L = batch._root_likelihoods(n)
+            w = np.ones(n) if self._root_w is None else self._root_w
+            status[~((L * w).sum(axis=1) > 0)] = _lib.RT_SITE_ZERO_PROB
+            return BranchExpectations(values, edge_sums, status, nodes)
+        _lib.check(_lib.lib().rt_sites_branch_expectations(
+            self._h, batch._h, 1 if recompute_transitions else 0, K, _ptr(E, c_double),
+            None if values is None else _ptr(values, c_double), _ptr(edge_sums, c_double),
+            _ptr(status, c_int32)))
+        return BranchExpectations(values, edge_sums, status, nodes)
+
+    def branch_length_gradient(self, batch, recompute_transitions=False):
+        """d (sum_i w_i log L_i) / d t_v for every branch, f64[nnodes] in preorder (0 at the
+        root), analytically from one branch_expectations call: with E = ones off the diagonal
+        and diag(Q) on it the direction is Q itself and the edge sum is t_v times the
+        derivative.  For a model with ONE rate matrix: the coefficient matrix of a call is
+        shared by all edges, so with per-edge rate matrices no single E has every edge's
+        diag(Q) on its diagonal -- ValueError then (call branch_expectations once per rate
+        matrix and pick the edges)."""
+        rates = getattr(self, '_rates', None)
+        if rates is None:
+            raise ValueError('set_rates has not been called')
+        Q, t = rates
+        if Q.shape[0] != 1:
+            raise ValueError('branch_length_gradient needs one rate matrix for all edges '
+                             '(%d here): the coefficient matrix is shared by all edges'
+                             % Q.shape[0])
+        E = np.ones((self.nstates, self.nstates))
+        np.fill_diagonal(E, np.diag(Q[0]))
+        sums = self.branch_expectations(batch, E, per_site=False,
+                                        recompute_transitions=recompute_transitions).edge_sums
+        grad = np.zeros(self.tree.nnodes)
+        live = t != 0
+        live[0] = False
+        grad[live] = sums[live, 0] / t[live]
+        return grad
 
     def allreduce(self, batch):
         _lib.check(_lib.lib().rt_allreduce_totals(self.ctx._h, batch._h))
