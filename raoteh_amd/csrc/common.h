@@ -98,6 +98,7 @@ struct rt_ctx {
     size_t expm_attr_lds = 0;      // dynamic-LDS attribute already granted to expm_kernel
     size_t expm_ts_attr_lds[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ... to the Taylor kernels (per NT)
     size_t expm_split_attr_lds = 0;                           // ... to the two-workgroup form
+    size_t expm_w8_attr_lds[3] = {0, 0, 0};    // ... to the eight-wave forms: NT = 3, 4, pair
     size_t expm_wide_attr_lds[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     double *d_expm_scratch = nullptr;   // matrices of the order > 64 Taylor kernel (grow-only)
     void *expect_cache = nullptr;       // expect_mfma.hip: model + packed batch of the last call

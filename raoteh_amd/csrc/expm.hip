@@ -1,5 +1,5 @@
 // P = expm(Q * t) for a batch of small dense rate matrices, f64, one workgroup
-// (4 waves) per matrix, every intermediate resident in LDS or registers.
+// (4 waves; 8 for 33 <= n <= 64) per matrix, every intermediate resident in LDS or registers.
 //
 // Replaces scipy.linalg.expm(Q * weight) at raoteh/sampler/_mjp_dense.py:24-25
 // (one call per edge per site in the reference, _mjp_dense.py:352-358) and
@@ -690,8 +690,8 @@ __device__ __forceinline__ void mm_half(const double *X, const double *Y, double
     double4_t acc[2];
     const double *ap = X + (16 * wave + lr) * LD + lq;
     const double *bp = Y + lq * LD + 32 * h + lr;
-    // operands two k-steps ahead (one wave per SIMD: nobody else hides the LDS latency, and a
-    // k-step is only two MFMAs long); the first ones are requested before the accumulators are
+    // operands two k-steps ahead (this four-wave form has one wave per SIMD: nobody else hides
+    // the LDS latency, and a k-step is only two MFMAs long); the first ones are requested before the accumulators are
     // seeded, and the coefficients of the step arrive in registers (read from LDS here, four
     // dependent-looking reads stood in front of the first MFMA: 1 200-1 500 clocks of a half
     // product's 4 700, fine stamps of RAOTEH_EXPM_TRACE)
@@ -737,7 +737,138 @@ __device__ __forceinline__ void mm_half(const double *X, const double *Y, double
     RT_FINE(5);
 }
 
+// EIGHT WAVES per workgroup (NT = 3, 4: 33 <= n <= 64), two per SIMD.  With one wave per SIMD
+// and two or four MFMAs per k-step nobody hides the LDS latency of the operand reads, and the
+// products above run at 90-117 clocks per MFMA where the fed instruction takes 70-74.  The
+// register file is nearly empty, so a second wave per SIMD fits (<= 256 registers each), and
+// a wave keeps its LEFT operand in registers: the slices of its one row tile, 4 NT doubles per
+// lane, are read from LDS once -- A for A^2 and A^3, A^3 for every Horner step -- instead of
+// at every k-step of every product.  Wave w holds one row tile and NC <= 2 column tiles of
+// it; each accumulator tile sees the same seed and the same k-steps in the same order as in
+// the four-wave kernel, so the results are the same bits.  That rests on the seed, the top
+// block and the k loop of mm8 staying term for term those of mm_blocked and mm_half: change
+// one, change all three (tests/test_expm_two_waves_gpu.py compares the kernels bit for bit).
+//   NT = 4: 4 x 4 tiles, wave w = row tile w / 2, column tiles 2 (w & 1), 2 (w & 1) + 1;
+//           pair form: 4 x 2 tiles, wave w = row tile w / 2, column tile 2 h + (w & 1)
+//   NT = 3: 3 x 3 tiles over eight waves: one tile each, wave 6 two (3 + 2 + 2 + 2 per SIMD)
+template <int NT>
+__device__ __forceinline__ void wave8_tiles(int wave, int &m, int &j0, int &nc)
+{
+    if (NT == 4) { m = wave >> 1; j0 = 2 * (wave & 1); nc = 2; }
+    else if (wave < 6) { m = wave / 3; j0 = wave - 3 * m; nc = 1; }
+    else { m = 2; j0 = wave == 6 ? 0 : 2; nc = wave == 6 ? 2 : 1; }
+}
+
+// this wave's left operand: row tile m of X, one double per lane and k-step (the A layout
+// of v_mfma_f64_16x16x4: lane l holds row 16 m + (l & 15), column 4 kk + (l >> 4))
+template <int NT>
+__device__ __forceinline__ void load_left8(const double *X, int m, double (&a)[4 * NT])
+{
+    constexpr int LD = 16 * NT + 1;
+    const int lane = threadIdx.x & 63;
+    const double *ap = X + (16 * m + (lane & 15)) * LD + (lane >> 4);
+#pragma unroll
+    for (int kk = 0; kk < 4 * NT; ++kk) a[kk] = ap[4 * kk];
+}
+
+// the elements of M at this lane's accumulator positions (tiles (m, j0), (m, j0 + 1))
+template <int NT>
+__device__ __forceinline__ void load_tiles8(const double *M, half_tiles &t, int m, int j0, int nc)
+{
+    constexpr int LD = 16 * NT + 1;
+    const int lane = threadIdx.x & 63;
+    const int lr = lane & 15, lq = lane >> 4;
+#pragma unroll
+    for (int v = 0; v < 2; ++v)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            t.v[v][r] = v < nc ? M[(16 * m + 4 * r + lq) * LD + 16 * (j0 + v) + lr] : 0.0;
+}
+
+// C[tiles of this wave] = X Y (+ c0 I + c1 R1 + c2 R2 when seed), X = the slices in a[].
+// NC = 1, 2: that many column tiles on every wave; 0: nc_wave of them (wave-uniform).
+// top != nullptr: C2 = top0 I + top1 R1 + top2 R2 + top3 (X Y) as well.  C may alias Y.
+template <int NT, int NC>
+__device__ __forceinline__ void mm8(const double (&a)[4 * NT], const double *Y, double *C,
+                                    int m, int j0, int nc_wave, bool seed, double c0, double c1,
+                                    double c2, double nd, const half_tiles *R1,
+                                    const half_tiles *R2, half_tiles *out = nullptr,
+                                    const double *top = nullptr, double *C2 = nullptr,
+                                    bool fine = false)
+{
+    RT_FINE(0);
+    constexpr int LD = 16 * NT + 1, KS = 4 * NT;
+    const int nc = NC ? NC : nc_wave;
+    const int lane = threadIdx.x & 63;
+    const int lr = lane & 15, lq = lane >> 4;
+    const double *bp = Y + lq * LD + 16 * j0 + lr;
+    const int o1 = nc > 1 ? 16 : 0;            // (one tile: the second operand is not used)
+    // operands two k-steps ahead, the first ones requested before the accumulators are seeded
+    double b00 = bp[0], b01 = bp[o1];
+    double b10 = bp[4 * LD], b11 = bp[4 * LD + o1];
+    double4_t acc[2];
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+        acc[v] = (double4_t){0.0, 0.0, 0.0, 0.0};
+        if (seed && v < nc) {
+            const int col = 16 * (j0 + v) + lr;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * m + 4 * r + lq;
+                // (explicit fma: the same contraction in every variant of the kernel)
+                double w = c1 * R1->v[v][r];
+                w = fma(c2, R2->v[v][r], w);
+                if (row == col && (double)row < nd) w += c0;
+                acc[v][r] = w;
+            }
+        }
+    }
+    RT_FINE(1);
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) {
+        const int kn = kk + 2 < KS ? kk + 2 : KS - 1;
+        const double b20 = bp[4 * kn * LD], b21 = bp[4 * kn * LD + o1];
+        __builtin_amdgcn_sched_barrier(0);      // the reads stay ahead of the MFMAs (see mm_half)
+        acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], b00, acc[0], 0, 0, 0);
+        if (NC != 1 && nc > 1)
+            acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], b01, acc[1], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        b00 = b10; b01 = b11;
+        b10 = b20; b11 = b21;
+    }
+    RT_FINE(2);
+    if (out) {
+#pragma unroll
+        for (int v = 0; v < 2; ++v)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) out->v[v][r] = acc[v][r];
+    }
+    __syncthreads();
+    RT_FINE(3);
+#pragma unroll
+    for (int v = 0; v < 2; ++v)
+        if (v < nc) {
+            const int col = 16 * (j0 + v) + lr;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * m + 4 * r + lq;
+                C[row * LD + col] = acc[v][r];
+                if (top) {                     // top = {c0, c1, c2, c3, n}, see mm_blocked
+                    double w = top[1] * R1->v[v][r];
+                    w = fma(top[2], R2->v[v][r], w);
+                    w = fma(top[3], acc[v][r], w);
+                    C2[row * LD + col] = w + ((row == col && (double)row < top[4]) ? top[0] : 0.0);
+                }
+            }
+        }
+    RT_FINE(4);
+    __syncthreads();
+    RT_FINE(5);
+}
+
 // GLOBAL = false: the four matrices in LDS (n <= 64); true: in scratch[blockIdx] (n <= 128)
+// WAVES = 8: the two-waves-per-SIMD products above (LDS-resident, NT = 3, 4); 4: mm_blocked /
+// mm_half (RAOTEH_EXPM_WAVES=4 selects them for NT = 3, 4: the A/B partner)
 // RAOTEH_EXPM_TRACE=1: workgroup 1 of the Taylor kernel stamps the shader clock at its
 // phase boundaries (printed by the launcher): diagnostics
 __device__ int rt_expm_trace_on = 0;
@@ -746,8 +877,8 @@ __device__ unsigned long long rt_expm_trace[8];
     if (trace_on && blockIdx.x == (SPLIT ? 2 : 1) && threadIdx.x == 0)                \
         rt_expm_trace[k] = __builtin_readcyclecounter()
 
-template <int NT, bool GLOBAL, bool SPLIT = false>
-__global__ void __launch_bounds__(TPB)
+template <int NT, bool GLOBAL, bool SPLIT = false, int WAVES = 4>
+__global__ void __launch_bounds__(64 * WAVES)
 expm_taylor_kernel(int n, const double *__restrict__ Q, const int *__restrict__ qidx,
                    const double *__restrict__ tt, double *__restrict__ P,
                    int *__restrict__ info, const int *__restrict__ step_of_node,
@@ -771,6 +902,11 @@ expm_taylor_kernel(int n, const double *__restrict__ Q, const int *__restrict__ 
     double *B3 = B2 + MSZ;                     // T
 
     static_assert(!SPLIT || (NT == 4 && !GLOBAL), "two workgroups per matrix: 49 <= n <= 64");
+    static_assert(WAVES == 4 || (WAVES == 8 && !GLOBAL && (NT == 3 || NT == 4)),
+                  "two waves per SIMD: LDS-resident, 33 <= n <= 64");
+    // threads of the elementwise loops; the load and the norm stay on the first TPB threads
+    // (row groups of TPB / RN: the order of the column sums is part of the result)
+    constexpr int NTH = 64 * WAVES;
     const int b = SPLIT ? (int)(blockIdx.x >> 1) : (int)blockIdx.x;
     const int half = SPLIT ? (int)(blockIdx.x & 1) : 0;      // which columns this workgroup stores
     const int tid = threadIdx.x;
@@ -795,15 +931,15 @@ expm_taylor_kernel(int n, const double *__restrict__ Q, const int *__restrict__ 
     }
     const double t_early = tt[b];
     if (qi < 0) {                              // root slot: zeros (_density.py:171)
-        for (int e = tid; e < nn; e += TPB) Pb[e] = 0.0;
+        for (int e = tid; e < nn; e += NTH) Pb[e] = 0.0;
         if (info && tid == 0) { info[2 * b] = 0; info[2 * b + 1] = 0; }
         if (step >= 0 && frag_kind == 0)
-            for (int e = tid; e < nn; e += TPB) Pfrag[(long)step * nn + e] = 0.0;
+            for (int e = tid; e < nn; e += NTH) Pfrag[(long)step * nn + e] = 0.0;
         if (step >= 0 && frag_kind == 1) {
             const int total = NTn * ((KSn + 1) / 2) * 128;
-            for (int e = tid; e < total; e += TPB) Pfrag[(long)step * total + e] = 0.0;
+            for (int e = tid; e < total; e += NTH) Pfrag[(long)step * total + e] = 0.0;
             if (Pquad)
-                for (int e = tid; e < KSn * KSn * 16; e += TPB)
+                for (int e = tid; e < KSn * KSn * 16; e += NTH)
                     Pquad[(long)step * rt_quad_stride(n) + e] = 0.0;
         }
         return;
@@ -883,7 +1019,7 @@ expm_taylor_kernel(int n, const double *__restrict__ Q, const int *__restrict__ 
     }
     RT_EXPM_STAMP(1);
     if (!(nrm < 1e300)) {                      // inf / NaN in Q * t (block-uniform)
-        for (int e = tid; e < nn; e += TPB) Pb[e] = __builtin_nan("");
+        for (int e = tid; e < nn; e += NTH) Pb[e] = __builtin_nan("");
         if (info && tid == 0) { info[2 * b] = -1; info[2 * b + 1] = 0; }
         return;
     }
@@ -903,62 +1039,109 @@ expm_taylor_kernel(int n, const double *__restrict__ Q, const int *__restrict__ 
     if (info && tid == 0) { info[2 * b] = m; info[2 * b + 1] = s; }
     if (s > 0) {
         const double sc = ldexp(1.0, -s);
-        for (int e = tid; e < MSZ; e += TPB) B0[e] *= sc;
+        for (int e = tid; e < MSZ; e += NTH) B0[e] *= sc;
         __syncthreads();
     }
     const int q = m / 3;
     RT_EXPM_STAMP(2);
-    lane_tiles<NT> ra, ra2;
-    load_tiles<NT>(B0, ra);
-    mm_blocked<NT>(B0, B0, B1, nullptr, nullptr, nullptr, nullptr, nullptr, &ra2);     // A^2
-    // A^3, and with it T = B_(q-1) = c I + c A + c A^2 + c_m A^3 (the degree-m polynomial
-    // is sum_{j<q} A^(3j) B_j plus c_m A^m, and c_m A^m = A^(3(q-1)) (c_m A^3): the top
-    // block carries the A^3 term)
-    __shared__ double tops[5];
-    {
-        const int base = 3 * (q - 1);
-        if (tid == 0) {
-            tops[0] = c_inv_fact[base];
-            tops[1] = c_inv_fact[base + 1];
-            tops[2] = c_inv_fact[base + 2];
-            tops[3] = c_inv_fact[m];
-            tops[4] = (double)n;
+    if constexpr (WAVES == 8) {
+        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        int wm, wj, wn;
+        wave8_tiles<NT>(wave, wm, wj, wn);
+        constexpr int NCF = NT == 4 ? 2 : 0;       // column tiles per wave of a full product
+        const double nd = (double)n;
+        // (m, q block-uniform: the coefficients are scalar loads from constant memory)
+        const double tops8[5] = {c_inv_fact[3 * (q - 1)], c_inv_fact[3 * (q - 1) + 1],
+                                 c_inv_fact[3 * (q - 1) + 2], c_inv_fact[m], nd};
+        double left[4 * NT];
+        half_tiles ra, ra2;
+        load_left8<NT>(B0, wm, left);
+        load_tiles8<NT>(B0, ra, wm, wj, wn);
+        mm8<NT, NCF>(left, B0, B1, wm, wj, wn, false, 0.0, 0.0, 0.0, nd, nullptr, nullptr,
+                     &ra2);                                                 // A^2
+        // A^3 and the top block T = B_(q-1), as below
+        mm8<NT, NCF>(left, B1, B2, wm, wj, wn, false, 0.0, 0.0, 0.0, nd, &ra, &ra2, nullptr,
+                     tops8, B3);
+        RT_EXPM_STAMP(3);
+        RT_EXPM_STAMP(4);
+        if (q >= 2) load_left8<NT>(B2, wm, left);                 // A^3: every Horner step
+        if (SPLIT && s == 0) {
+            if constexpr (SPLIT) {
+                const int hj = 2 * half + (wave & 1);
+                half_tiles ha, ha2;
+                load_tiles8<NT>(B0, ha, wm, hj, 1);
+                load_tiles8<NT>(B1, ha2, wm, hj, 1);
+#pragma unroll
+                for (int u = 3; u >= 0; --u)
+                    if (u <= q - 2)        // T[:, half] = A^3 T[:, half] + B_u
+                        mm8<NT, 1>(left, B3, B3, wm, hj, 1, true, c_inv_fact[3 * u],
+                                   c_inv_fact[3 * u + 1], c_inv_fact[3 * u + 2], nd, &ha, &ha2,
+                                   nullptr, nullptr, nullptr,
+                                   trace_on && blockIdx.x == 2 && u == 0);
+            }
+        } else {
+            for (int jj = q - 2; jj >= 0; --jj)                             // T = A^3 T + B_j
+                mm8<NT, NCF>(left, B3, B3, wm, wj, wn, true, c_inv_fact[3 * jj],
+                             c_inv_fact[3 * jj + 1], c_inv_fact[3 * jj + 2], nd, &ra, &ra2);
         }
-        __syncthreads();
-    }
-    mm_blocked<NT>(B0, B1, B2, nullptr, nullptr, nullptr, &ra, &ra2, nullptr, tops, B3);
-    RT_EXPM_STAMP(3);
-    RT_EXPM_STAMP(4);
-    // the coefficients of every Horner step at once (one barrier, not one per step)
-    __shared__ double cfs_all[5][4];
-    if (tid < 20) cfs_all[tid >> 2][tid & 3] = (tid & 3) == 3 ? (double)n
-                                                             : c_inv_fact[3 * (tid >> 2) + (tid & 3)];
-    __syncthreads();
-    if (SPLIT && s == 0) {
-        if constexpr (SPLIT) {
-            half_tiles ha, ha2;
-            load_half_tiles(B0, ha, half);
-            load_half_tiles(B1, ha2, half);
-            // (the coefficients of all four possible steps in registers: block-uniform loads
-            // from constant memory, long before they are needed)
-            double hc[4][3];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int e = 0; e < 3; ++e) hc[u][e] = c_inv_fact[3 * u + e];
-            const double nd = (double)n;
-#pragma unroll
-            for (int u = 3; u >= 0; --u)
-                if (u <= q - 2)            // T[:, half] = A^3 T[:, half] + B_u
-                    mm_half(B2, B3, B3, hc[u][0], hc[u][1], hc[u][2], nd, ha, ha2, half,
-                            trace_on && blockIdx.x == 2 && u == 0);
+        RT_EXPM_STAMP(5);
+        for (int r = 0; r < s; ++r) {              // T = T T: no constant operand
+            load_left8<NT>(B3, wm, left);
+            mm8<NT, NCF>(left, B3, B3, wm, wj, wn, false, 0.0, 0.0, 0.0, nd, nullptr, nullptr);
         }
     } else {
-        for (int jj = q - 2; jj >= 0; --jj)
-            mm_blocked<NT>(B2, B3, B3, cfs_all[jj], B0, B1, &ra, &ra2);    // T = A^3 T + B_j
+        lane_tiles<NT> ra, ra2;
+        load_tiles<NT>(B0, ra);
+        mm_blocked<NT>(B0, B0, B1, nullptr, nullptr, nullptr, nullptr, nullptr, &ra2);     // A^2
+        // A^3, and with it T = B_(q-1) = c I + c A + c A^2 + c_m A^3 (the degree-m polynomial
+        // is sum_{j<q} A^(3j) B_j plus c_m A^m, and c_m A^m = A^(3(q-1)) (c_m A^3): the top
+        // block carries the A^3 term)
+        __shared__ double tops[5];
+        {
+            const int base = 3 * (q - 1);
+            if (tid == 0) {
+                tops[0] = c_inv_fact[base];
+                tops[1] = c_inv_fact[base + 1];
+                tops[2] = c_inv_fact[base + 2];
+                tops[3] = c_inv_fact[m];
+                tops[4] = (double)n;
+            }
+            __syncthreads();
+        }
+        mm_blocked<NT>(B0, B1, B2, nullptr, nullptr, nullptr, &ra, &ra2, nullptr, tops, B3);
+        RT_EXPM_STAMP(3);
+        RT_EXPM_STAMP(4);
+        // the coefficients of every Horner step at once (one barrier, not one per step)
+        __shared__ double cfs_all[5][4];
+        if (tid < 20) cfs_all[tid >> 2][tid & 3] = (tid & 3) == 3 ? (double)n
+                                                                 : c_inv_fact[3 * (tid >> 2) + (tid & 3)];
+        __syncthreads();
+        if (SPLIT && s == 0) {
+            if constexpr (SPLIT) {
+                half_tiles ha, ha2;
+                load_half_tiles(B0, ha, half);
+                load_half_tiles(B1, ha2, half);
+                // (the coefficients of all four possible steps in registers: block-uniform loads
+                // from constant memory, long before they are needed)
+                double hc[4][3];
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int e = 0; e < 3; ++e) hc[u][e] = c_inv_fact[3 * u + e];
+                const double nd = (double)n;
+#pragma unroll
+                for (int u = 3; u >= 0; --u)
+                    if (u <= q - 2)            // T[:, half] = A^3 T[:, half] + B_u
+                        mm_half(B2, B3, B3, hc[u][0], hc[u][1], hc[u][2], nd, ha, ha2, half,
+                                trace_on && blockIdx.x == 2 && u == 0);
+            }
+        } else {
+            for (int jj = q - 2; jj >= 0; --jj)
+                mm_blocked<NT>(B2, B3, B3, cfs_all[jj], B0, B1, &ra, &ra2);    // T = A^3 T + B_j
+        }
+        RT_EXPM_STAMP(5);
+        for (int r = 0; r < s; ++r) mm_blocked<NT>(B3, B3, B3, nullptr, nullptr, nullptr);
     }
-    RT_EXPM_STAMP(5);
-    for (int r = 0; r < s; ++r) mm_blocked<NT>(B3, B3, B3, nullptr, nullptr, nullptr);
     RT_EXPM_STAMP(6);
 
     const double *Xb = B3;
@@ -967,11 +1150,11 @@ expm_taylor_kernel(int n, const double *__restrict__ Q, const int *__restrict__ 
         // k-pairs (column c of P is k-step c / 4: columns 32 h .. 32 h + 31 = pairs 4 h .. 4 h + 3)
         const int jc = 32 * half + (tid & 31), g = tid >> 5;
         if (jc < n)
-            for (int i = g; i < n; i += TPB / 32) Pb[i * n + jc] = Xb[i * LD + jc];
+            for (int i = g; i < n; i += NTH / 32) Pb[i * n + jc] = Xb[i * LD + jc];
         if (step >= 0 && frag_kind == 1) {
             const int KP = (KSn + 1) / 2;
             const int total = NTn * KP * 128;
-            for (int blk = tid >> 7; blk < NTn * 4; blk += TPB >> 7) {
+            for (int blk = tid >> 7; blk < NTn * 4; blk += NTH >> 7) {
                 const int mm = blk >> 2, qq = 4 * half + (blk & 3);
                 if (qq < KP) {
                     const int e = (mm * KP + qq) * 128 + (tid & 127);
@@ -987,7 +1170,7 @@ expm_taylor_kernel(int n, const double *__restrict__ Q, const int *__restrict__ 
         return;
     }
     if (!GLOBAL) {               // thread = (column, row group) as in the load: no division
-        constexpr int RP = TPB / RN;
+        constexpr int RP = NTH / RN;
         const int jc = tid % RN, g = tid / RN;
         if (g < RP && jc < n)
             for (int i = g; i < n; i += RP) Pb[i * n + jc] = Xb[i * LD + jc];
@@ -998,7 +1181,7 @@ expm_taylor_kernel(int n, const double *__restrict__ Q, const int *__restrict__ 
         }
     }
     if (step >= 0 && frag_kind == 0) {
-        for (int e = tid; e < nn; e += TPB) {
+        for (int e = tid; e < nn; e += NTH) {
             const int i = e / n, j = e - i * n;
             Pfrag[(long)step * nn + e] = Xb[i * LD + j];
         }
@@ -1008,7 +1191,7 @@ expm_taylor_kernel(int n, const double *__restrict__ Q, const int *__restrict__ 
         const int KP = (KSn + 1) / 2;
         const int total = NTn * KP * 128;
         // 128 entries per (row tile, k-pair): the block index is wave-uniform arithmetic
-        for (int blk = tid >> 7; blk < NTn * KP; blk += TPB >> 7) {
+        for (int blk = tid >> 7; blk < NTn * KP; blk += NTH >> 7) {
             const int e = blk * 128 + (tid & 127);
             const int e2 = e & 1;
             const int ln = (e >> 1) & 63;
@@ -1021,7 +1204,7 @@ expm_taylor_kernel(int n, const double *__restrict__ Q, const int *__restrict__ 
         if (Pquad) {
             // Pquad[step][rq][kk][k][i] = P[4 rq + i][4 kk + k] (the padding is zero)
             const int tq = KSn * KSn * 16;
-            for (int e = tid; e < tq; e += TPB) {
+            for (int e = tid; e < tq; e += NTH) {
                 const int i = e & 3, k = (e >> 2) & 3, blk = e >> 4;
                 const int row = 4 * (blk / KSn) + i, col = 4 * (blk % KSn) + k;
                 Pquad[(long)step * rt_quad_stride(n) + e] = Xb[row * LD + col];
@@ -1383,11 +1566,33 @@ int rt_launch_expm(rt_ctx *ctx, int64_t n, int64_t count, const double *d_Q,
                             dim3(TPB), lds_t, (int)n, d_Q, d_qidx, d_t, d_P, d_info,            \
                             d_step_of_node, frag_kind, d_Pfrag, d_Pquad, scratch, red);         \
         } while (0)
+        // 33..64 states: eight waves per workgroup, left operands in registers
+        // (RAOTEH_EXPM_WAVES=4: the four-wave kernel, for A/B runs and
+        // tests/test_expm_two_waves_gpu.py)
+#define RT_TAYLOR8(NTV, SP, SLOT)                                                               \
+        do {                                                                                    \
+            if (lds_t > ctx->expm_w8_attr_lds[SLOT]) {                                          \
+                RT_HIP(hipFuncSetAttribute((const void *)expm_taylor_kernel<NTV, false, SP, 8>, \
+                                           hipFuncAttributeMaxDynamicSharedMemorySize,          \
+                                           (int)lds_t));                                        \
+                ctx->expm_w8_attr_lds[SLOT] = lds_t;                                            \
+            }                                                                                   \
+            RT_LAUNCH_TIMED(ctx, (expm_taylor_kernel<NTV, false, SP, 8>),                       \
+                            dim3((SP ? 2u : 1u) * (unsigned)count + extra), dim3(512), lds_t,   \
+                            (int)n, d_Q, d_qidx, d_t, d_P, d_info, d_step_of_node, frag_kind,   \
+                            d_Pfrag, d_Pquad, scratch, red);                                    \
+        } while (0)
+        const char *wv8 = getenv("RAOTEH_EXPM_WAVES");
+        const bool waves8 = (nt == 3 || nt == 4) && !(wv8 && atoi(wv8) == 4);
         // few 49..64-state matrices (the edges of one tree): two workgroups per matrix, the
         // Horner steps in column halves (RAOTEH_EXPM_SPLIT=0 / 1 overrides)
         bool split2 = nt == 4 && 2 * count + extra <= (int64_t)std::max(2, ctx->num_cus) && !d_Pquad;
         if (const char *v = getenv("RAOTEH_EXPM_SPLIT")) split2 = nt == 4 && !d_Pquad && atoi(v) != 0;
-        if (split2) {
+        if (split2 && waves8) {
+            snprintf(ctx->slots[RT_K_EXPM].name, sizeof(ctx->slots[RT_K_EXPM].name),
+                     "expm_taylor_ps_mfma_split2");
+            RT_TAYLOR8(4, true, 2);
+        } else if (split2) {
             if (lds_t > ctx->expm_split_attr_lds) {
                 RT_HIP(hipFuncSetAttribute((const void *)expm_taylor_kernel<4, false, true>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
@@ -1403,14 +1608,15 @@ int rt_launch_expm(rt_ctx *ctx, int64_t n, int64_t count, const double *d_Q,
         switch (nt) {
         case 1: RT_TAYLOR(1, false); break;
         case 2: RT_TAYLOR(2, false); break;
-        case 3: RT_TAYLOR(3, false); break;
-        case 4: RT_TAYLOR(4, false); break;
+        case 3: if (waves8) RT_TAYLOR8(3, false, 0); else RT_TAYLOR(3, false); break;
+        case 4: if (waves8) RT_TAYLOR8(4, false, 1); else RT_TAYLOR(4, false); break;
         case 5: RT_TAYLOR(5, true); break;
         case 6: RT_TAYLOR(6, true); break;
         case 7: RT_TAYLOR(7, true); break;
         default: RT_TAYLOR(8, true); break;
         }
 #undef RT_TAYLOR
+#undef RT_TAYLOR8
         RT_HIP(hipGetLastError());
         if (getenv("RAOTEH_EXPM_TRACE")) {
             static int armed = 0;
