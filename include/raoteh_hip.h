@@ -49,8 +49,10 @@ extern "C" {
                                     examples/p53/liwen.py:599-621 runs _mcy_dense on
                                     2 x 61 = 122 compound states                */
 #define RT_MAX_EXPECT_STATES 64  /* reference-shaped expectation passes on host
-                                    arrays (rt_mjp_*_expectation_*), Rao-Teh forest /
-                                    chains, spectral reconstruction: n <= 64    */
+                                    arrays (rt_mjp_*_expectation_*), spectral
+                                    reconstruction: n <= 64 (the Rao-Teh forest
+                                    passes and chains of sections 4 and 5 take
+                                    n <= 128)                                    */
 #define RT_MAX_EXPECT_STEP_STATES 128 /* rt_expect_step on a resident batch and
                                     rt_mjp_frechet_statistics: n <= 128 (above 64 the
                                     Frechet derivative is carried as a pair (X, L)
@@ -502,8 +504,11 @@ int rt_allreduce_totals_group(rt_ctx *ctx, rt_sites **sites, int64_t count);
  *       _density.digraph_to_bool_csr returns it) starts at off[k] + k
  *   tree_csr_indices int64[total - ntrees]  tree k's child indices (nnodes_k - 1 local
  *       preorder indices) start at off[k] - k
- *   P f64[n][n]: an entry that is exactly zero is a structural zero; n <= 64
- *   allowed_sets uint64[total]: bit s = state s allowed at the node (in / out).
+ *   P f64[n][n]: an entry that is exactly zero is a structural zero; n <= 128
+ *   allowed_sets (in / out): for n <= 64 uint64[total], bit s = state s allowed at the
+ *       node; for 64 < n <= 128 uint64[total][2], state s = bit s % 64 of word s / 64 (the
+ *       layout of RT_OBS_MASK).  Bits at or above n are ignored on input and, for
+ *       n > 64, zero on output.
  *
  * rt_forest_passes: pyfelscore.mcy_get_node_to_pset then pyfelscore.get_node_to_set
  * with a boolean CSR of P (_mcy.py:139-181; un-accelerated twins _mcy.py:396-470,
@@ -520,7 +525,8 @@ int rt_forest_passes(rt_ctx *ctx, int64_t n, int64_t ntrees,
  * boolean CSR shared by every edge (trans_csr_indptr int64[n + 1], trans_csr_indices the
  * column indices of the nonzero entries of each row, _mcy.py:148-149), state_mask
  * int64[nnodes][n] 0/1 updated in place.  tmp_state_mask int64[n] is the scratch row
- * pyfelscore asks for (may be NULL).  n <= 64.                                        */
+ * pyfelscore asks for (may be NULL).  n <= 128 (the mask stays one int64 per state;
+ * above 64 states the two-word set kernels of rt_forest_passes run underneath).      */
 int rt_mcy_get_node_to_pset(rt_ctx *ctx, int64_t nnodes, int64_t n,
             const int64_t *tree_csr_indices, const int64_t *tree_csr_indptr,
             const int64_t *trans_csr_indices, const int64_t *trans_csr_indptr,
@@ -559,7 +565,9 @@ int rt_forest_resample_states_parents(rt_ctx *ctx, int64_t n, int64_t ntrees,
  * v) under ONE rate matrix, given as the caller computes it for the reference's sampler
  * (_sampler.py:344-357): P = I + Q / omega (f64[n][n]), poisson_rates[s] = omega - q_s,
  * root_distn (f64[n] or NULL = weights of one), node_masks uint64[nchains][nnodes]
- * allowed-state sets of the base nodes.  A history is a run of rows (edge = index of the
+ * allowed-state sets of the base nodes -- for 64 < n <= 128 uint64[nchains][nnodes][2],
+ * state s = bit s % 64 of word s / 64 as in section 4; bits at or above n are ignored;
+ * n <= 128.  A history is a run of rows (edge = index of the
  * edge's lower node, length, state) sorted by (edge, position); rt_chains_create finds a
  * first feasible one by bisecting the edges (_sampler.py:563-648; RT_ERR_ZERO_PROB when
  * some chain has none), rt_chains_sweep runs whole sweeps (_sampler.py:366-390: Poisson

@@ -28,7 +28,45 @@ from ._tree import TreeArrays
 from ._util import StructuralZeroProb
 from .device import get_context
 
-__all__ = ['Forest', 'get_node_to_set_and_pmap', 'resample_states']
+__all__ = ['Forest', 'get_node_to_set_and_pmap', 'resample_states', 'set_words',
+           'states_to_mask', 'mask_to_states', 'full_mask']
+
+MAX_STATES = 128
+
+
+def set_words(nstates):
+    """Words of a state set: one ``uint64`` up to 64 states, two for 65..128 (state s is
+    bit s % 64 of word s // 64, the layout of ``_mjp_dense.allowed_states_to_masks``)."""
+    if nstates > MAX_STATES:
+        raise ValueError('the forest passes hold two states per lane: nstates <= %d'
+                         % MAX_STATES)
+    return 1 if nstates <= 64 else 2
+
+
+def states_to_mask(states, nstates):
+    """Iterable of states -> uint64 scalar (nstates <= 64) or uint64[2]."""
+    words = set_words(nstates)
+    m = 0
+    for s in states:
+        if not 0 <= int(s) < nstates:
+            raise ValueError('state %r outside [0, %d)' % (s, nstates))
+        m |= 1 << int(s)
+    if words == 1:
+        return np.uint64(m)
+    return np.array([(m >> (64 * w)) & (2 ** 64 - 1) for w in range(words)], dtype=np.uint64)
+
+
+def full_mask(nstates):
+    """The set of all states in the layout of ``states_to_mask``."""
+    return states_to_mask(range(nstates), nstates)
+
+
+def mask_to_states(mask, nstates):
+    """uint64 scalar or uint64[words] -> set of states (bits at or above nstates ignored)."""
+    m = 0
+    for w, x in enumerate(np.atleast_1d(mask)):
+        m |= int(x) << (64 * w)
+    return set(s for s in range(nstates) if (m >> s) & 1)
 
 
 def _ptr(a, ctype):
@@ -64,24 +102,20 @@ class Forest(object):
 
     def allowed_masks(self, node_to_allowed_states, nstates):
         """list (one dict per tree, or None) of node -> allowed set; a node that is
-        missing, or a None dict, is unrestricted -> uint64[total] bit masks."""
-        if nstates > 64:
-            raise ValueError('the forest passes hold a state per lane: nstates <= 64')
-        full = (1 << nstates) - 1
-        out = np.empty(self.total, dtype=np.uint64)
+        missing, or a None dict, is unrestricted -> uint64[total] bit masks for
+        nstates <= 64, uint64[total, 2] for 65..128 states (state s = bit s % 64 of word
+        s // 64)."""
+        words = set_words(nstates)
+        full = full_mask(nstates)
+        out = np.empty((self.total, words), dtype=np.uint64)
         for k, nodes in enumerate(self.preorder):
             d = node_to_allowed_states[k] if node_to_allowed_states is not None else None
             lo = int(self.node_offset[k])
             for i, v in enumerate(nodes):
-                m = full
-                if d is not None and v in d:
-                    m = 0
-                    for s in d[v]:
-                        if not 0 <= int(s) < nstates:
-                            raise ValueError('state %r outside [0, %d)' % (s, nstates))
-                        m |= 1 << int(s)
-                out[lo + i] = m
-        return out
+                out[lo + i] = states_to_mask(d[v], nstates) if d is not None and v in d else full
+        return out[:, 0] if words == 1 else out
+
+    masks = allowed_masks
 
     def split(self, flat):
         """Per-node array [total, ...] -> list of {node: row} dicts."""
@@ -112,8 +146,7 @@ def get_node_to_set_and_pmap(forest, P, node_to_allowed_states=None, ctx=None):
         ctx._h, n, forest.ntrees, _ptr(forest.node_offset, c_int64),
         _ptr(forest.indices, c_int64), _ptr(forest.indptr, c_int64), _ptr(P, c_double),
         _ptr(masks, c_uint64), _ptr(L, c_double)))
-    sets = [dict((v, set(s for s in range(n) if (int(m) >> s) & 1)) for v, m in d.items())
-            for d in forest.split(masks)]
+    sets = [dict((v, mask_to_states(m, n)) for v, m in d.items()) for d in forest.split(masks)]
     return sets, forest.split(L)
 
 

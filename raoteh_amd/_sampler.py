@@ -23,7 +23,8 @@ csrc/forest.hip: one wave per chunk tree, lane = state, Philox draws).  The chun
 come out in an order in which every chunk's parent has a smaller index, which is the
 layout that entry point takes; no child lists are built.
 
-    batch = HistoryBatch(T, root, Q, node_masks=masks)      # uint64[nchains, nnodes]
+    batch = HistoryBatch(T, root, Q, node_masks=masks)      # uint64[nchains, nnodes]; above
+                                                            # 64 states [nchains, nnodes, 2]
     for _ in range(nsweeps):
         batch.sweep()
         dwell, trans = batch.dwell_times(), batch.transition_counts()
@@ -41,6 +42,7 @@ import networkx as nx
 import numpy as np
 
 from . import _lib
+from ._forest import full_mask, set_words, states_to_mask
 from ._tree import TreeArrays, check_square_dense
 from ._util import StructuralZeroProb
 from .device import get_context
@@ -184,7 +186,8 @@ class HistoryBatch(object):
     matrix ``Q`` (diagonal = minus the row sums).
 
     node_masks : uint64[nchains, nnodes] allowed-set bit masks by preorder index
-        (``self.tree.preorder_nodes``), or give ``node_to_allowed_states``: one dict
+        (``self.tree.preorder_nodes``) -- uint64[nchains, nnodes, 2] for 65..128 states,
+        state s = bit s % 64 of word s // 64 -- or give ``node_to_allowed_states``: one dict
         {node: set of states} per chain (a missing node is unrestricted), or ONE dict
         together with ``nchains`` for replicate chains of the same data.
     root_distn : f64[nstates] or None (weights of one, _sample_mc0_dense.py:53-56)
@@ -208,8 +211,7 @@ class HistoryBatch(object):
         Q = np.ascontiguousarray(Q, dtype=np.float64)
         check_square_dense(Q)
         n = Q.shape[0]
-        if n > 64:
-            raise ValueError('the forest passes hold a state per lane: nstates <= 64')
+        words = set_words(n)                 # ValueError above 128 states
         self.nstates = n
         self.Q = Q
         self.tree = TreeArrays(T, root)
@@ -222,16 +224,20 @@ class HistoryBatch(object):
         self.omega = float(uniformization_factor) * float(rates.max())
         self.P = np.identity(n) + Q / self.omega            # _sample_mjp_dense.py:107-114
         self.poisson_rates = self.omega - rates              # _sampler.py:356-357
-        full = np.uint64((1 << n) - 1)
+        full = full_mask(n)
         if node_masks is not None:
             masks = np.ascontiguousarray(node_masks, dtype=np.uint64)
-            if masks.ndim != 2 or masks.shape[1] != N:
-                raise ValueError('node_masks must be [nchains, %d]' % N)
+            if words == 1:
+                if masks.ndim != 2 or masks.shape[1] != N:
+                    raise ValueError('node_masks must be [nchains, %d]' % N)
+            elif masks.ndim != 3 or masks.shape[1:] != (N, words):
+                raise ValueError('node_masks must be [nchains, %d, %d]' % (N, words))
         else:
             dicts = node_to_allowed_states
             if dicts is None or isinstance(dicts, dict):
                 dicts = [dicts] * int(nchains or 1)
-            masks = np.full((len(dicts), N), full, dtype=np.uint64)
+            masks = np.empty((len(dicts), N) + full.shape, dtype=np.uint64)
+            masks[:] = full
             cache = {}
             for c, d in enumerate(dicts):
                 if d is None:
@@ -242,14 +248,10 @@ class HistoryBatch(object):
                         raise ValueError('some of the nodes which have been annotated with '
                                          'state restrictions are not even in the tree: '
                                          + str(sorted(bad)))
-                    row = np.full(N, full, dtype=np.uint64)
+                    row = np.empty((N,) + full.shape, dtype=np.uint64)
+                    row[:] = full
                     for v, allowed in d.items():
-                        m = 0
-                        for s in allowed:
-                            if not 0 <= int(s) < n:
-                                raise ValueError('state %r outside [0, %d)' % (s, n))
-                            m |= 1 << int(s)
-                        row[self.tree.node_to_index[v]] = m
+                        row[self.tree.node_to_index[v]] = states_to_mask(allowed, n)
                     cache[id(d)] = row
                 masks[c] = cache[id(d)]
         self.node_masks = masks & full
@@ -275,7 +277,9 @@ class HistoryBatch(object):
         C, N, n = self.nchains, self.tree.nnodes, self.nstates
         offset, cparent, piece, node = chunk_forest(self.parent, C, chain, edge)
         total = int(offset[-1])
-        masks = np.full(total, np.uint64((1 << n) - 1), dtype=np.uint64)
+        full = full_mask(n)
+        masks = np.empty((total,) + full.shape, dtype=np.uint64)
+        masks[:] = full
         glob = offset[:-1, None] + node
         for v in range(N):               # one base node at a time: distinct chunks per chain
             masks[glob[:, v]] &= self.node_masks[:, v]

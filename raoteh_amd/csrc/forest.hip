@@ -25,6 +25,9 @@
 // set test over all states is one ballot; P is kept by rows in ELL form (the
 // uniformized matrix of a codon model has ~10 entries per row), a message entry is a
 // gather from the child's vector in LDS.
+// 65 <= n <= 128 (the *_wide_kernel siblings): still a wave per tree, a lane owns the two
+// states `lane` and `lane + 64`; a set is two words (state s = bit s % 64 of word s / 64),
+// a set test two ballots, the ELL tables and the child's vector are 128 wide.
 #include "common.h"
 
 #include <algorithm>
@@ -36,10 +39,10 @@ constexpr int FOREST_WAVES = 4;            // waves (trees) per workgroup
 
 struct ell_matrix {
     int width = 0;                         // entries per row (padded with col = row, val = 0)
-    int *d_col = nullptr;                  // [width][64]
-    double *d_val = nullptr;               // [width][64]
-    unsigned long long *d_rowbits = nullptr;   // [64] nonzero pattern of row s
-    unsigned long long *d_colbits = nullptr;   // [64] nonzero pattern of column s
+    int *d_col = nullptr;                  // [width][64]; n > 64: [width][128]
+    double *d_val = nullptr;               // [width][64]; n > 64: [width][128]
+    unsigned long long *d_rowbits = nullptr;   // [64] nonzero pattern of row s; n > 64: [128][2]
+    unsigned long long *d_colbits = nullptr;   // [64] nonzero pattern of column s; n > 64: [128][2]
     double *d_dense = nullptr;             // [n][n]
 };
 
@@ -434,6 +437,195 @@ forest_sample_grouped_kernel(int n, long ntrees, const long *__restrict__ off,
     if (active && s == 0) status[tree] = st;
 }
 
+// ---- 65 to 128 states: a lane owns two states ------------------------------------------------
+// Siblings of the three wave-per-tree kernels above.  A set is two words; the set image of a
+// wave in LDS holds two words per node, so the wide form of the boolean passes keeps trees of
+// up to FOREST_CAP_WIDE = 512 nodes there: 4 waves x 512 x 16 B = 32 KB per workgroup, what
+// the one-word kernel takes at 1024 nodes (five workgroups on a CU's 160 KB; at 1024 nodes
+// and 64 KB it would be two).  Larger trees take the coherent global path, as above.
+constexpr int FOREST_CAP_WIDE = 512;
+
+__device__ __forceinline__ unsigned long long word_of_full_set(int n, int j)
+{
+    const int nb = n - 64 * j;
+    return nb >= 64 ? ~0ull : nb <= 0 ? 0ull : (1ull << nb) - 1ull;
+}
+
+__global__ void __launch_bounds__(64 * FOREST_WAVES)
+forest_sets_wide_kernel(int n, long ntrees, const long *__restrict__ off,
+                        const int *__restrict__ parent,
+                        const unsigned long long *__restrict__ rowbits,
+                        const unsigned long long *__restrict__ colbits,
+                        unsigned long long *__restrict__ allowed, int forward)
+{
+    __shared__ unsigned long long lset[FOREST_WAVES][2 * FOREST_CAP_WIDE];
+    const int lane = threadIdx.x & 63;
+    const int w = threadIdx.x >> 6;
+    const long tree = (long)blockIdx.x * FOREST_WAVES + w;
+    if (tree >= ntrees) return;
+    const long lo = off[tree], hi = off[tree + 1];
+    const bool fits = hi - lo <= FOREST_CAP_WIDE;
+    const int s1 = lane + 64;
+    // the lane's states: `lane` (a) and `lane + 64` (b); words 0 and 1 of their row / column
+    const unsigned long long ra0 = lane < n ? rowbits[2 * lane] : 0ull;
+    const unsigned long long ra1 = lane < n ? rowbits[2 * lane + 1] : 0ull;
+    const unsigned long long rb0 = s1 < n ? rowbits[2 * s1] : 0ull;
+    const unsigned long long rb1 = s1 < n ? rowbits[2 * s1 + 1] : 0ull;
+    const unsigned long long ca0 = lane < n ? colbits[2 * lane] : 0ull;
+    const unsigned long long ca1 = lane < n ? colbits[2 * lane + 1] : 0ull;
+    const unsigned long long cb0 = s1 < n ? colbits[2 * s1] : 0ull;
+    const unsigned long long cb1 = s1 < n ? colbits[2 * s1 + 1] : 0ull;
+    // bits at or above n are ignored on input and zero on output
+    const unsigned long long full = word_of_full_set(n, lane & 1);
+    if (fits) {
+        for (long i = lane; i < 2 * (hi - lo); i += 64) lset[w][i] = allowed[2 * lo + i] & full;
+    } else {
+        for (long i = lane; i < 2 * (hi - lo); i += 64)
+            coherent_store(&allowed[2 * lo + i], coherent_load(&allowed[2 * lo + i]) & full);
+    }
+    wave_lds_order();
+    // backward: a state stays at v only if it has a transition into every child's set
+    // (forward: 0 = this pass only, 1 = both, 2 = the forward pass only)
+    for (long v = hi - 1; forward != 2 && v > lo; --v) {
+        const unsigned long long c0 = fits ? lset[w][2 * (v - lo)] : coherent_load(&allowed[2 * v]);
+        const unsigned long long c1 =
+            fits ? lset[w][2 * (v - lo) + 1] : coherent_load(&allowed[2 * v + 1]);
+        const unsigned long long keep0 = __ballot(((ra0 & c0) | (ra1 & c1)) != 0ull);
+        const unsigned long long keep1 = __ballot(((rb0 & c0) | (rb1 & c1)) != 0ull);
+        const long p = lo + parent[v];
+        if (fits) {
+            if (lane < 2) lset[w][2 * (p - lo) + lane] &= lane ? keep1 : keep0;
+            wave_lds_order();
+        } else if (lane < 2) {
+            coherent_store(&allowed[2 * p + lane],
+                           coherent_load(&allowed[2 * p + lane]) & (lane ? keep1 : keep0));
+        }
+    }
+    // forward: a child state stays only if some state of the parent's set reaches it
+    for (long v = lo + 1; forward && v < hi; ++v) {
+        const long p = lo + parent[v];
+        const unsigned long long p0 = fits ? lset[w][2 * (p - lo)] : coherent_load(&allowed[2 * p]);
+        const unsigned long long p1 =
+            fits ? lset[w][2 * (p - lo) + 1] : coherent_load(&allowed[2 * p + 1]);
+        const unsigned long long reach0 = __ballot(((ca0 & p0) | (ca1 & p1)) != 0ull);
+        const unsigned long long reach1 = __ballot(((cb0 & p0) | (cb1 & p1)) != 0ull);
+        if (fits) {
+            if (lane < 2) lset[w][2 * (v - lo) + lane] &= lane ? reach1 : reach0;
+            wave_lds_order();
+        } else if (lane < 2) {
+            coherent_store(&allowed[2 * v + lane],
+                           coherent_load(&allowed[2 * v + lane]) & (lane ? reach1 : reach0));
+        }
+    }
+    if (fits)
+        for (long i = lane; i < 2 * (hi - lo); i += 64) allowed[2 * lo + i] = lset[w][i];
+}
+
+// upward pass: each owned state keeps its own fma chain over k, in the order of the one-word
+// kernel
+__global__ void __launch_bounds__(64 * FOREST_WAVES)
+forest_pmap_wide_kernel(int n, long ntrees, const long *__restrict__ off,
+                        const int *__restrict__ parent, int width, const int *__restrict__ ecol,
+                        const double *__restrict__ eval,
+                        const unsigned long long *__restrict__ allowed, double *__restrict__ L)
+{
+    __shared__ double vec[FOREST_WAVES][128];
+    const int lane = threadIdx.x & 63;
+    const int w = threadIdx.x >> 6;
+    const long tree = (long)blockIdx.x * FOREST_WAVES + w;
+    if (tree >= ntrees) return;
+    const long lo = off[tree], hi = off[tree + 1];
+    const int s1 = lane + 64;
+    const bool live0 = lane < n, live1 = s1 < n;
+    for (long v = lo; v < hi; ++v) {
+        if (live0) L[v * n + lane] = (allowed[2 * v] >> lane) & 1ull ? 1.0 : 0.0;
+        if (live1) L[v * n + s1] = (allowed[2 * v + 1] >> lane) & 1ull ? 1.0 : 0.0;
+    }
+    for (long v = hi - 1; v > lo; --v) {
+        vec[w][lane] = live0 ? L[v * n + lane] : 0.0;
+        vec[w][s1] = live1 ? L[v * n + s1] : 0.0;
+        wave_lds_order();
+        double msg0 = 0.0, msg1 = 0.0;
+        for (int k = 0; k < width; ++k) {
+            msg0 = fma(eval[k * 128 + lane], vec[w][ecol[k * 128 + lane]], msg0);
+            msg1 = fma(eval[k * 128 + s1], vec[w][ecol[k * 128 + s1]], msg1);
+        }
+        const long p = lo + parent[v];
+        if (live0) L[p * n + lane] *= msg0;    // lane-private addresses: ordered per lane
+        if (live1) L[p * n + s1] *= msg1;
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// sampling: cumulative weights in state order 0..n-1.  States 0..63 are summed as the
+// one-word kernel sums them; states 64.. are a second scan whose first element carries the
+// first scan's total.  (A model embedded into n > 64 states with the extra states of weight
+// zero gets the draws of the one-word kernel.)
+__global__ void __launch_bounds__(64 * FOREST_WAVES)
+forest_sample_wide_kernel(int n, long ntrees, const long *__restrict__ off,
+                          const int *__restrict__ parent, const double *__restrict__ P,
+                          const double *__restrict__ root_distn, const double *__restrict__ L,
+                          unsigned long long seed, unsigned long long sweep,
+                          int *__restrict__ states, int *__restrict__ status)
+{
+    __shared__ int lstate[FOREST_WAVES][FOREST_CAP];
+    const int lane = threadIdx.x & 63;
+    const int w = threadIdx.x >> 6;
+    const long tree = (long)blockIdx.x * FOREST_WAVES + w;
+    if (tree >= ntrees) return;
+    const long lo = off[tree], hi = off[tree + 1];
+    const bool fits = hi - lo <= FOREST_CAP;
+    const int s1 = lane + 64;
+    const bool live0 = lane < n, live1 = s1 < n;
+    int st = 0;
+    for (long v = lo; v < hi; ++v) {
+        double prior0 = 0.0, prior1 = 0.0;
+        if (v == lo) {
+            if (live0) prior0 = root_distn ? root_distn[lane] : 1.0;
+            if (live1) prior1 = root_distn ? root_distn[s1] : 1.0;
+        } else {
+            const long p = lo + parent[v];
+            const int ps = fits ? lstate[w][p - lo]
+                                : __hip_atomic_load(&states[p], __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_AGENT);
+            if (live0 && ps >= 0) prior0 = P[(long)ps * n + lane];
+            if (live1 && ps >= 0) prior1 = P[(long)ps * n + s1];
+        }
+        const double wgt0 = live0 ? fmax(prior0 * L[v * n + lane], 0.0) : 0.0;
+        const double wgt1 = live1 ? fmax(prior1 * L[v * n + s1], 0.0) : 0.0;
+        const double cdf0 = wave_inclusive_sum(wgt0, lane);
+        const double low = __shfl(cdf0, 63, 64);
+        const double cdf1 = wave_inclusive_sum(lane == 0 ? low + wgt1 : wgt1, lane);
+        const double total = __shfl(cdf1, 63, 64);
+        int pick = -1;
+        if (total > 0.0 && total < 1e308 * 10.0) {
+            const double target = philox_uniform(seed, sweep, (unsigned long long)v) * total;
+            // first state in state order whose cumulative weight exceeds the target
+            const unsigned long long hit0 = __ballot(wgt0 > 0.0 && cdf0 > target);
+            const unsigned long long hit1 = __ballot(wgt1 > 0.0 && cdf1 > target);
+            if (hit0) pick = __ffsll((long long)hit0) - 1;
+            else if (hit1) pick = 64 + __ffsll((long long)hit1) - 1;
+            else {                                 // rounding at the top: the last positive state
+                const unsigned long long pos0 = __ballot(wgt0 > 0.0);
+                const unsigned long long pos1 = __ballot(wgt1 > 0.0);
+                pick = pos1 ? 127 - __clzll((long long)pos1) : 63 - __clzll((long long)pos0);
+            }
+        } else {
+            if (st == 0) st = v == lo ? 1 : 2;     // the first failure names the cause
+        }
+        if (fits) {
+            if (lane == 0) {
+                lstate[w][v - lo] = pick;
+                states[v] = pick;
+            }
+            wave_lds_order();
+        } else if (lane == 0) {
+            __hip_atomic_store(&states[v], pick, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if (lane == 0) status[tree] = st;
+}
+
 // the three passes, by state count
 unsigned forest_grid_grouped(int64_t ntrees, int G)
 {
@@ -447,7 +639,10 @@ void launch_forest_sets(int n, long ntrees, const long *off, const int *parent,
 {
     const dim3 block(64 * FOREST_WAVES);
     const bool wide = getenv("RAOTEH_FOREST_WAVE_PER_TREE") != nullptr;
-    if (n <= 4 && !wide)
+    if (n > 64)
+        hipLaunchKernelGGL(forest_sets_wide_kernel, dim3(forest_grid_grouped(ntrees, 1)), block, 0,
+                           st, n, ntrees, off, parent, rowbits, colbits, allowed, forward);
+    else if (n <= 4 && !wide)
         hipLaunchKernelGGL(forest_sets_grouped_kernel<4>, dim3(forest_grid_grouped(ntrees, 16)), block,
                            0, st, n, ntrees, off, parent, rowbits, colbits, allowed, forward);
     else if (n <= 8 && !wide)
@@ -467,7 +662,10 @@ void launch_forest_pmap(int n, long ntrees, const long *off, const int *parent, 
 {
     const dim3 block(64 * FOREST_WAVES);
     const bool wide = getenv("RAOTEH_FOREST_WAVE_PER_TREE") != nullptr;
-    if (n <= 4 && !wide)
+    if (n > 64)
+        hipLaunchKernelGGL(forest_pmap_wide_kernel, dim3(forest_grid_grouped(ntrees, 1)), block, 0,
+                           st, n, ntrees, off, parent, width, ecol, eval, allowed, L);
+    else if (n <= 4 && !wide)
         hipLaunchKernelGGL(forest_pmap_grouped_kernel<4>, dim3(forest_grid_grouped(ntrees, 16)), block,
                            0, st, n, ntrees, off, parent, width, ecol, eval, allowed, L);
     else if (n <= 8 && !wide)
@@ -487,7 +685,11 @@ void launch_forest_sample(int n, long ntrees, const long *off, const int *parent
 {
     const dim3 block(64 * FOREST_WAVES);
     const bool wide = getenv("RAOTEH_FOREST_WAVE_PER_TREE") != nullptr;
-    if (n <= 4 && !wide)
+    if (n > 64)
+        hipLaunchKernelGGL(forest_sample_wide_kernel, dim3(forest_grid_grouped(ntrees, 1)), block,
+                           0, st, n, ntrees, off, parent, P, root_distn, L, seed, sweep, states,
+                           status);
+    else if (n <= 4 && !wide)
         hipLaunchKernelGGL(forest_sample_grouped_kernel<4>, dim3(forest_grid_grouped(ntrees, 16)),
                            block, 0, st, n, ntrees, off, parent, P, root_distn, L, seed, sweep, states,
                            status);
@@ -556,41 +758,43 @@ int forest_parents(int64_t ntrees, const int64_t *off, const int64_t *idx, const
 
 int upload_matrix(int64_t n, const double *P, ell_matrix &M)
 {
-    std::vector<unsigned long long> rowbits(64, 0), colbits(64, 0);
+    const int S = n > 64 ? 128 : 64;       // states the tables are padded to
+    const int W = S / 64;                  // words per set
+    std::vector<unsigned long long> rowbits((size_t)S * W, 0), colbits((size_t)S * W, 0);
     int width = 1;
     for (int64_t r = 0; r < n; ++r) {
         int cnt = 0;
         for (int64_t c = 0; c < n; ++c)
             if (P[r * n + c] != 0.0) {
-                rowbits[(size_t)r] |= 1ull << c;
-                colbits[(size_t)c] |= 1ull << r;
+                rowbits[(size_t)(r * W + c / 64)] |= 1ull << (c % 64);
+                colbits[(size_t)(c * W + r / 64)] |= 1ull << (r % 64);
                 ++cnt;
             }
         width = std::max(width, cnt);
     }
-    std::vector<int> col((size_t)width * 64);
-    std::vector<double> val((size_t)width * 64, 0.0);
-    for (int r = 0; r < 64; ++r) {
+    std::vector<int> col((size_t)width * S);
+    std::vector<double> val((size_t)width * S, 0.0);
+    for (int r = 0; r < S; ++r) {
         int k = 0;
         if (r < n)
             for (int64_t c = 0; c < n; ++c)
                 if (P[r * n + c] != 0.0) {
-                    col[(size_t)k * 64 + r] = (int)c;
-                    val[(size_t)k * 64 + r] = P[r * n + c];
+                    col[(size_t)k * S + r] = (int)c;
+                    val[(size_t)k * S + r] = P[r * n + c];
                     ++k;
                 }
-        for (; k < width; ++k) col[(size_t)k * 64 + r] = r < n ? r : 0;
+        for (; k < width; ++k) col[(size_t)k * S + r] = r < n ? r : 0;
     }
     M.width = width;
     RT_HIP(hipMalloc((void **)&M.d_col, col.size() * 4));
     RT_HIP(hipMalloc((void **)&M.d_val, val.size() * 8));
-    RT_HIP(hipMalloc((void **)&M.d_rowbits, 64 * 8));
-    RT_HIP(hipMalloc((void **)&M.d_colbits, 64 * 8));
+    RT_HIP(hipMalloc((void **)&M.d_rowbits, rowbits.size() * 8));
+    RT_HIP(hipMalloc((void **)&M.d_colbits, colbits.size() * 8));
     RT_HIP(hipMalloc((void **)&M.d_dense, (size_t)n * n * 8));
     RT_HIP(hipMemcpy(M.d_col, col.data(), col.size() * 4, hipMemcpyHostToDevice));
     RT_HIP(hipMemcpy(M.d_val, val.data(), val.size() * 8, hipMemcpyHostToDevice));
-    RT_HIP(hipMemcpy(M.d_rowbits, rowbits.data(), 64 * 8, hipMemcpyHostToDevice));
-    RT_HIP(hipMemcpy(M.d_colbits, colbits.data(), 64 * 8, hipMemcpyHostToDevice));
+    RT_HIP(hipMemcpy(M.d_rowbits, rowbits.data(), rowbits.size() * 8, hipMemcpyHostToDevice));
+    RT_HIP(hipMemcpy(M.d_colbits, colbits.data(), colbits.size() * 8, hipMemcpyHostToDevice));
     RT_HIP(hipMemcpy(M.d_dense, P, (size_t)n * n * 8, hipMemcpyHostToDevice));
     return RT_OK;
 }
@@ -617,7 +821,7 @@ int forest_upload(rt_ctx *ctx, int64_t n, int64_t ntrees, const int64_t *off, co
                   const int32_t *given_parent = nullptr)
 {
     RT_REQUIRE(ctx, "null context");
-    RT_REQUIRE(n >= 1 && n <= 64, "the forest passes hold a state per lane: n <= 64");
+    RT_REQUIRE(n >= 1 && n <= 128, "the forest passes hold two states per lane: n <= 128");
     RT_REQUIRE(P, "null transition matrix");
     std::vector<int> parent;
     if (given_parent) {
@@ -639,6 +843,9 @@ int forest_upload(rt_ctx *ctx, int64_t n, int64_t ntrees, const int64_t *off, co
 
 unsigned forest_grid(int64_t ntrees) { return (unsigned)((ntrees + FOREST_WAVES - 1) / FOREST_WAVES); }
 
+// words of a set: one up to 64 states, two above
+int64_t set_words(int64_t n) { return n > 64 ? 2 : 1; }
+
 }  // namespace
 
 extern "C" int rt_forest_passes(rt_ctx *ctx, int64_t n, int64_t ntrees,
@@ -650,9 +857,10 @@ extern "C" int rt_forest_passes(rt_ctx *ctx, int64_t n, int64_t ntrees,
     forest_dev f;
     RT_TRY(forest_upload(ctx, n, ntrees, tree_node_offset, tree_csr_indices, tree_csr_indptr, P, f));
     const int64_t total = tree_node_offset[ntrees];
+    const int64_t set_bytes = total * set_words(n) * 8;
     hipStream_t st = ctx->stream;
-    RT_HIP(hipMalloc((void **)&f.d_allowed, total * 8));
-    RT_HIP(hipMemcpyAsync(f.d_allowed, allowed_sets, total * 8, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMalloc((void **)&f.d_allowed, set_bytes));
+    RT_HIP(hipMemcpyAsync(f.d_allowed, allowed_sets, set_bytes, hipMemcpyHostToDevice, st));
     launch_forest_sets((int)n, (long)ntrees, f.d_off, f.d_parent, f.P.d_rowbits, f.P.d_colbits,
                        (unsigned long long *)f.d_allowed, 1, st);
     RT_HIP(hipGetLastError());
@@ -663,7 +871,7 @@ extern "C" int rt_forest_passes(rt_ctx *ctx, int64_t n, int64_t ntrees,
         RT_HIP(hipGetLastError());
         RT_HIP(hipMemcpyAsync(subtree_probability, f.d_L, total * n * 8, hipMemcpyDeviceToHost, st));
     }
-    RT_HIP(hipMemcpyAsync(allowed_sets, f.d_allowed, total * 8, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipMemcpyAsync(allowed_sets, f.d_allowed, set_bytes, hipMemcpyDeviceToHost, st));
     RT_HIP(hipStreamSynchronize(st));
     return RT_OK;
 }
@@ -678,7 +886,7 @@ static int shared_matrix_mask_pass(rt_ctx *ctx, int mode, int64_t nnodes, int64_
 {
     RT_REQUIRE(ctx, "null context");
     RT_REQUIRE(nnodes >= 1 && n >= 1 && ptr && tptr && state_mask, "bad arguments");
-    RT_REQUIRE(n <= 64, "the forest passes hold a state per lane: n <= 64");
+    RT_REQUIRE(n <= 128, "the forest passes hold two states per lane: n <= 128");
     RT_REQUIRE(tptr[0] == 0 && tptr[n] >= 0 && (tidx || tptr[n] == 0), "bad transition CSR");
     std::vector<double> P((size_t)n * n, 0.0);
     for (int64_t a = 0; a < n; ++a) {
@@ -691,20 +899,22 @@ static int shared_matrix_mask_pass(rt_ctx *ctx, int mode, int64_t nnodes, int64_
     const int64_t off[2] = {0, nnodes};
     forest_dev f;
     RT_TRY(forest_upload(ctx, n, 1, off, idx, ptr, P.data(), f));
-    std::vector<unsigned long long> sets((size_t)nnodes, 0ull);
+    const int64_t W = set_words(n);
+    std::vector<unsigned long long> sets((size_t)(nnodes * W), 0ull);
     for (int64_t v = 0; v < nnodes; ++v)
         for (int64_t a = 0; a < n; ++a)
-            if (state_mask[v * n + a]) sets[(size_t)v] |= 1ull << a;
+            if (state_mask[v * n + a]) sets[(size_t)(v * W + a / 64)] |= 1ull << (a % 64);
     hipStream_t st = ctx->stream;
-    RT_HIP(hipMalloc((void **)&f.d_allowed, nnodes * 8));
-    RT_HIP(hipMemcpyAsync(f.d_allowed, sets.data(), nnodes * 8, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMalloc((void **)&f.d_allowed, nnodes * W * 8));
+    RT_HIP(hipMemcpyAsync(f.d_allowed, sets.data(), nnodes * W * 8, hipMemcpyHostToDevice, st));
     launch_forest_sets((int)n, 1, f.d_off, f.d_parent, f.P.d_rowbits, f.P.d_colbits,
                        (unsigned long long *)f.d_allowed, mode, st);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipMemcpyAsync(sets.data(), f.d_allowed, nnodes * 8, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipMemcpyAsync(sets.data(), f.d_allowed, nnodes * W * 8, hipMemcpyDeviceToHost, st));
     RT_HIP(hipStreamSynchronize(st));
     for (int64_t v = 0; v < nnodes; ++v)
-        for (int64_t a = 0; a < n; ++a) state_mask[v * n + a] = (int64_t)((sets[(size_t)v] >> a) & 1ull);
+        for (int64_t a = 0; a < n; ++a)
+            state_mask[v * n + a] = (int64_t)((sets[(size_t)(v * W + a / 64)] >> (a % 64)) & 1ull);
     return RT_OK;
 }
 
@@ -740,8 +950,9 @@ static int forest_resample_impl(rt_ctx *ctx, int64_t n, int64_t ntrees,
     RT_TRY(forest_upload(ctx, n, ntrees, tree_node_offset, tree_csr_indices, tree_csr_indptr, P, f,
                          tree_parent));
     const int64_t total = tree_node_offset[ntrees];
+    const int64_t set_bytes = total * set_words(n) * 8;
     hipStream_t st = ctx->stream;
-    RT_HIP(hipMalloc((void **)&f.d_allowed, total * 8));
+    RT_HIP(hipMalloc((void **)&f.d_allowed, set_bytes));
     RT_HIP(hipMalloc((void **)&f.d_L, total * n * 8));
     RT_HIP(hipMalloc((void **)&f.d_states, total * 4));
     RT_HIP(hipMalloc((void **)&f.d_status, ntrees * 4));
@@ -749,7 +960,7 @@ static int forest_resample_impl(rt_ctx *ctx, int64_t n, int64_t ntrees,
         RT_HIP(hipMalloc((void **)&f.d_root, n * 8));
         RT_HIP(hipMemcpyAsync(f.d_root, root_distn, n * 8, hipMemcpyHostToDevice, st));
     }
-    RT_HIP(hipMemcpyAsync(f.d_allowed, allowed_sets, total * 8, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemcpyAsync(f.d_allowed, allowed_sets, set_bytes, hipMemcpyHostToDevice, st));
     // one sweep's worth of passes back to back on the stream: sets, pmap, sampling
     launch_forest_sets((int)n, (long)ntrees, f.d_off, f.d_parent, f.P.d_rowbits, f.P.d_colbits,
                        (unsigned long long *)f.d_allowed, 1, st);
@@ -761,7 +972,7 @@ static int forest_resample_impl(rt_ctx *ctx, int64_t n, int64_t ntrees,
     RT_HIP(hipGetLastError());
     RT_HIP(hipMemcpyAsync(states, f.d_states, total * 4, hipMemcpyDeviceToHost, st));
     RT_HIP(hipMemcpyAsync(status, f.d_status, ntrees * 4, hipMemcpyDeviceToHost, st));
-    RT_HIP(hipMemcpyAsync(allowed_sets, f.d_allowed, total * 8, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipMemcpyAsync(allowed_sets, f.d_allowed, set_bytes, hipMemcpyDeviceToHost, st));
     if (subtree_probability)
         RT_HIP(hipMemcpyAsync(subtree_probability, f.d_L, total * n * 8, hipMemcpyDeviceToHost, st));
     RT_HIP(hipStreamSynchronize(st));
@@ -833,7 +1044,7 @@ struct chains_tables {                     // per wave, in dynamic LDS
     int *rows;          // [N] new rows on the edge above node v
     int *first;         // [N] index of the edge's first new row within the chain
     int *node;          // [N] local chunk of base node v
-    unsigned long long *acc;   // [N] allowed sets ANDed over the event-free subtree below v
+    unsigned long long *acc;   // [N][W] allowed sets ANDed over the event-free subtree below v
 };
 
 __device__ __forceinline__ int wave_inclusive_sum_int(int x, int lane)
@@ -899,6 +1110,9 @@ sweep_count_kernel(long nchains, const long *__restrict__ start, const int *__re
     if (lane == 0) newcnt[c] = total;
 }
 
+// W = words per set: 1 up to 64 states, 2 for 65..128 (acc, cmask and the full set carry W
+// words; the per-wave tables take N * (8 W + 16) bytes)
+template <int W>
 __global__ void __launch_bounds__(64 * SWEEP_WAVES)
 sweep_split_kernel(long nchains, int N, int nbits, const int *__restrict__ parent,
                    const long *__restrict__ start, const int *__restrict__ cnt,
@@ -917,12 +1131,17 @@ sweep_split_kernel(long nchains, int N, int nbits, const int *__restrict__ paren
     const int w = threadIdx.x >> 6;
     const long c = (long)blockIdx.x * SWEEP_WAVES + w;
     if (c >= nchains) return;
-    // tables of this wave: acc (8 B) first, then three int arrays
-    unsigned long long *acc = sweep_lds + (size_t)w * N * 3;           // N * 8 B
-    int *rows = (int *)(acc + N);                                       // 3 N ints = N * 12 B
+    // tables of this wave: acc (8 W B) first, then three int arrays
+    unsigned long long *acc = sweep_lds + (size_t)w * N * (W + 2);     // N * 8 W B
+    int *rows = (int *)(acc + (size_t)N * W);                           // 3 N ints = N * 12 B
     int *first = rows + N;
     int *node = first + N;
-    const unsigned long long full = nbits >= 64 ? ~0ull : (1ull << nbits) - 1ull;
+    unsigned long long full[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        const int nb = nbits - 64 * j;
+        full[j] = nb >= 64 ? ~0ull : nb <= 0 ? 0ull : (1ull << nb) - 1ull;
+    }
     const long lo = start[c], out = newstart[c];
     const long ch = out - c * (long)(N - 2);        // chunks of a chain = its rows - (N - 2)
     const int total = (int)(newstart[c + 1] - out);
@@ -967,7 +1186,9 @@ sweep_split_kernel(long nchains, int N, int nbits, const int *__restrict__ paren
     wave_lds_order();
     // chunk of every base node (top-down) and the allowed sets of each event-free subtree
     // (bottom-up): chains of dependent LDS accesses, done by the whole wave in step
-    for (int v = lane; v < N; v += 64) acc[v] = node_masks[c * N + v] & full;
+    for (int v = lane; v < N; v += 64)
+#pragma unroll
+        for (int j = 0; j < W; ++j) acc[v * W + j] = node_masks[(c * N + v) * W + j] & full[j];
     wave_lds_order();
     // the chunk of a base node is the chunk of its nearest ancestor-or-self whose edge carries
     // events (or the root): pointer jumping, ceil(log2 N) rounds of two LDS reads per node (a
@@ -982,7 +1203,9 @@ sweep_split_kernel(long nchains, int N, int nbits, const int *__restrict__ paren
     // allowed sets of the event-free region below each such node, ANDed into it
     for (int v = lane; v < N; v += 64) {
         const int top = node[v];
-        if (top != v) atomicAnd(&acc[top], acc[v]);
+        if (top != v)
+#pragma unroll
+            for (int j = 0; j < W; ++j) atomicAnd(&acc[top * W + j], acc[v * W + j]);
     }
     wave_lds_order();
     {
@@ -1006,7 +1229,8 @@ sweep_split_kernel(long nchains, int N, int nbits, const int *__restrict__ paren
     for (int v = lane; v < N; v += 64) node_chunk[c * N + v] = node[v];
     if (lane == 0) {
         cparent[ch] = -1;
-        cmask[ch] = acc[0];
+#pragma unroll
+        for (int j = 0; j < W; ++j) cmask[ch * W + j] = acc[j];
     }
     // pass 2: chunk of every new row; parents and masks of the chunks the rows open
     // (the rows were written by other lanes of this wave a moment ago, and a neighbouring
@@ -1026,7 +1250,8 @@ sweep_split_kernel(long nchains, int N, int nbits, const int *__restrict__ paren
         row_chunk[out + j] = local;            // local index; global = choff[c] + local
         if (k >= 1) {
             cparent[ch + local] = k == 1 ? up : local - 1;
-            cmask[ch + local] = k == m ? acc[v] : full;
+#pragma unroll
+            for (int j = 0; j < W; ++j) cmask[(ch + local) * W + j] = k == m ? acc[v * W + j] : full[j];
         }
     }
 }
@@ -1079,6 +1304,7 @@ sweep_flag_kernel(long nchains, const int *__restrict__ status, int *__restrict_
     if (c < nchains && status[c] != 0) atomicMax(flag, status[c]);
 }
 
+template <int W>              // states per lane: lane, lane + 64, ...
 __global__ void __launch_bounds__(64 * SWEEP_WAVES)
 sweep_stats_kernel(long nchains, int n, const long *__restrict__ start, const int *__restrict__ cnt,
                    const int *__restrict__ edge, const double *__restrict__ len,
@@ -1091,10 +1317,16 @@ sweep_stats_kernel(long nchains, int n, const long *__restrict__ start, const in
     const long lo = start[c];
     const int m = cnt[c];
     if (dwell) {                 // lane = state: every lane walks the rows in order
-        double sum = 0.0;
+        double sum[W];
+#pragma unroll
+        for (int j = 0; j < W; ++j) sum[j] = 0.0;
         for (int i = 0; i < m; ++i)
-            if (state[lo + i] == lane) sum += len[lo + i];
-        if (lane < n) dwell[c * n + lane] = sum;
+#pragma unroll
+            for (int j = 0; j < W; ++j)
+                if (state[lo + i] == lane + 64 * j) sum[j] += len[lo + i];
+#pragma unroll
+        for (int j = 0; j < W; ++j)
+            if (lane + 64 * j < n) dwell[c * n + lane + 64 * j] = sum[j];
     }
     if (trans) {                 // zeroed by the host; integer adds: order does not matter
         for (int i = 1 + lane; i < m; i += 64)
@@ -1135,6 +1367,7 @@ sweep_restore_kernel(long nchains, int N, const unsigned char *__restrict__ reje
 struct rt_chains {
     rt_ctx *ctx = nullptr;
     int64_t nchains = 0, N = 0, n = 0;
+    int64_t W = 1;                         // words per set: 2 for 65..128 states
     uint64_t seed = 0, nsweeps = 0;
     ell_matrix P;
     int *d_parent = nullptr;               // base tree
@@ -1191,6 +1424,10 @@ int grow(T *&p, int64_t count, int64_t keep, hipStream_t st)
     return RT_OK;
 }
 
+// dynamic LDS of the split kernel: per wave and base node, W words of set and 16 bytes for the
+// three int tables (N * 24 bytes per wave at one word, as ever; N * 32 at two)
+size_t split_lds_bytes(int64_t N, int64_t W) { return (size_t)SWEEP_WAVES * N * (W + 2) * 8; }
+
 unsigned sweep_grid(int64_t nchains) { return (unsigned)((nchains + SWEEP_WAVES - 1) / SWEEP_WAVES); }
 
 // one sweep (per = 0) or one bisection attempt of the start-up (per = pieces per row);
@@ -1243,12 +1480,13 @@ int chains_step(rt_chains *h, int per, int *flag_out)
         const int64_t cap = total_chunks + total_chunks / 4 + 1024;
         RT_TRY(grow(h->d_cparent, cap, 0, st));
         RT_TRY(grow(h->d_cstate, cap, 0, st));
-        RT_TRY(grow(h->d_cmask, cap, 0, st));
+        RT_TRY(grow(h->d_cmask, cap * h->W, 0, st));
         RT_TRY(grow(h->d_L, cap * h->n, 0, st));
         h->cap_chunks = cap;
     }
-    const size_t lds = (size_t)SWEEP_WAVES * N * 24;      // acc (8 B) + three int tables
-    hipLaunchKernelGGL(sweep_split_kernel, grid, block, lds, st, (long)C, (int)N, (int)h->n,
+    const size_t lds = split_lds_bytes(N, h->W);          // acc (8 W B) + three int tables
+    hipLaunchKernelGGL(h->W == 2 ? sweep_split_kernel<2> : sweep_split_kernel<1>, grid, block, lds,
+                       st, (long)C, (int)N, (int)h->n,
                        h->d_parent, h->d_start, h->d_cnt, h->d_edge_a, h->d_len_a, h->d_state_a,
                        h->d_rates, per, (unsigned long long)h->seed, stream_events, h->d_row_k,
                        h->d_node_masks,
@@ -1292,7 +1530,7 @@ extern "C" int rt_chains_create(rt_ctx *ctx, int64_t nnodes, const int32_t *pare
     *out = nullptr;
     RT_REQUIRE(nnodes >= 2 && nnodes <= SWEEP_MAX_NODES, "the base tree needs 2..%d nodes",
                SWEEP_MAX_NODES);
-    RT_REQUIRE(n >= 1 && n <= 64, "the forest passes hold a state per lane: n <= 64");
+    RT_REQUIRE(n >= 1 && n <= 128, "the forest passes hold two states per lane: n <= 128");
     RT_REQUIRE(parent && branch_lengths && P && poisson_rates && node_masks && nchains >= 1,
                "null array or no chains");
     RT_REQUIRE(nchains < (1ll << 23), "at most 2^23 chains per batch");
@@ -1310,9 +1548,10 @@ extern "C" int rt_chains_create(rt_ctx *ctx, int64_t nnodes, const int32_t *pare
     h->nchains = nchains;
     h->N = nnodes;
     h->n = n;
+    h->W = set_words(n);
     h->seed = seed;
     hipStream_t st = ctx->stream;
-    const int64_t C = nchains, N = nnodes, E = N - 1;
+    const int64_t C = nchains, N = nnodes, E = N - 1, W = h->W;
     int rc = upload_matrix(n, P, h->P);
     auto fail = [&](int code) { delete h; return code; };
     if (rc != RT_OK) return fail(rc);
@@ -1320,7 +1559,7 @@ extern "C" int rt_chains_create(rt_ctx *ctx, int64_t nnodes, const int32_t *pare
     RT_CH(hipMalloc((void **)&h->d_parent, N * 4));
     RT_CH(hipMalloc((void **)&h->d_branch, N * 8));
     RT_CH(hipMalloc((void **)&h->d_rates, n * 8));
-    RT_CH(hipMalloc((void **)&h->d_node_masks, C * N * 8));
+    RT_CH(hipMalloc((void **)&h->d_node_masks, C * N * W * 8));
     RT_CH(hipMalloc((void **)&h->d_start, C * sizeof(long)));
     RT_CH(hipMalloc((void **)&h->d_newcnt, (C + 1) * sizeof(long)));
     RT_CH(hipMemsetAsync(h->d_newcnt, 0, (C + 1) * sizeof(long), st));
@@ -1340,7 +1579,7 @@ extern "C" int rt_chains_create(rt_ctx *ctx, int64_t nnodes, const int32_t *pare
     RT_CH(hipMemcpyAsync(h->d_parent, parent, N * 4, hipMemcpyHostToDevice, st));
     RT_CH(hipMemcpyAsync(h->d_branch, branch_lengths, N * 8, hipMemcpyHostToDevice, st));
     RT_CH(hipMemcpyAsync(h->d_rates, poisson_rates, n * 8, hipMemcpyHostToDevice, st));
-    RT_CH(hipMemcpyAsync(h->d_node_masks, node_masks, C * N * 8, hipMemcpyHostToDevice, st));
+    RT_CH(hipMemcpyAsync(h->d_node_masks, node_masks, C * N * W * 8, hipMemcpyHostToDevice, st));
     if (root_distn) {
         RT_CH(hipMalloc((void **)&h->d_root, n * 8));
         RT_CH(hipMemcpyAsync(h->d_root, root_distn, n * 8, hipMemcpyHostToDevice, st));
@@ -1374,10 +1613,13 @@ extern "C" int rt_chains_create(rt_ctx *ctx, int64_t nnodes, const int32_t *pare
     }
 #undef RT_CH
     {
-        const size_t lds = (size_t)SWEEP_WAVES * N * 24;
+        // above 64 KB (N > 682 at one word, N > 512 at two; 128 KB at N = 1024 and two words,
+        // inside the CU's 160 KB) the kernel's dynamic LDS limit is raised explicitly
+        const size_t lds = split_lds_bytes(N, W);
         if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)sweep_split_kernel,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipError_t e = hipFuncSetAttribute(
+                W == 2 ? (const void *)sweep_split_kernel<2> : (const void *)sweep_split_kernel<1>,
+                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) {
                 rt_set_error("cannot reserve %zu bytes of LDS for the split kernel", lds);
                 return fail(RT_ERR_HIP);
@@ -1457,7 +1699,7 @@ extern "C" int rt_chains_get_statistics(rt_chains *h, double *dwell, int64_t *tr
         RT_HIP(hipMemsetAsync(d_trans, 0, C * n * n * 8, st));
     }
     if (dwell || transitions) {
-        hipLaunchKernelGGL(sweep_stats_kernel, dim3(sweep_grid(C)), dim3(64 * SWEEP_WAVES), 0, st,
+        hipLaunchKernelGGL(n > 64 ? sweep_stats_kernel<2> : sweep_stats_kernel<1>, dim3(sweep_grid(C)), dim3(64 * SWEEP_WAVES), 0, st,
                            (long)C, (int)n, h->d_start, h->d_cnt, h->d_edge_a, h->d_len_a,
                            h->d_state_a, d_dwell, d_trans);
         RT_HIP(hipGetLastError());

@@ -15,7 +15,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from raoteh_amd import _sampler, device, synth          # noqa: E402
+from raoteh_amd import _forest, _sampler, device, synth          # noqa: E402
 
 
 def main():
@@ -26,13 +26,17 @@ def main():
     T, root, n = cfg['T'], cfg['root'], cfg['nstates']
     ctx = device.get_context(0)
     index = _sampler.TreeArrays(T, root).node_to_index
-    masks = np.full((nchains, len(index)), (1 << n) - 1, dtype=np.uint64)
+    # one uint64 per set up to 64 states, two above (the package's layout)
+    full = _forest.full_mask(n)
+    masks = np.empty((nchains, len(index)) + full.shape, dtype=np.uint64)
+    masks[:] = full
     cols = [index[v] for v in cfg['leaves']]
     if cfg['obs_kind'] == 'state':
-        masks[:, cols] = np.uint64(1) << cfg['leaf_states'].astype(np.uint64)
+        table = np.array([_forest.states_to_mask([x], n) for x in range(n)], dtype=np.uint64)
     else:
-        table = np.array([sum(1 << x for x in ss) for ss in cfg['leaf_allowed']], dtype=np.uint64)
-        masks[:, cols] = table[cfg['leaf_states']]
+        table = np.array([_forest.states_to_mask(ss, n) for ss in cfg['leaf_allowed']],
+                         dtype=np.uint64)
+    masks[:, cols] = table[cfg['leaf_states']]
     where = sys.argv[4] if len(sys.argv) > 4 else 'device'
     t0 = time.perf_counter()
     if where == 'device':
