@@ -472,6 +472,51 @@ int rt_sites_get_logliks(rt_sites *sites, double *loglik, int32_t *status);
  * all three are 0 for a batch that was never pruned.                        */
 int rt_sites_get_totals(rt_sites *sites, double totals[3]);
 
+/* ---- 2b. K rate sets against one resident batch in a single step ----------
+ *
+ * A finite-difference gradient, a line search, a multi-start or a site-class mixture evaluates
+ * the same tree and alignment under K parameter vectors.  The rate sets are a SECOND state of
+ * the model, independent of the one rt_model_set_rates owns: their own rate matrices, branch
+ * lengths and K transition tables in every layout the pruning kernels read.  Nothing below
+ * changes the model's own transitions or a batch's own kernel, log-likelihoods, status or totals.
+ *
+ * rt_model_set_rate_sets: Q f64[K][nq][n][n], node_q int64[nnodes] shared by all sets (NULL: every
+ *   edge uses matrix 0 of its set), t f64[K][nnodes].  Argument checks as rt_model_set_rates, and
+ *   1 <= K <= RT_MAX_RATE_SETS.  The exponentials of all K (nnodes - 1) edges are computed in ONE
+ *   launch; set k's matrices are bit for bit those of rt_model_set_rates(Q[k], nq, node_q, t[k]).
+ *   Buffers are allocated on first use and grow with K.
+ * rt_step_multi: (recompute_transitions != 0: those exponentials again from the resident rate
+ *   sets,) then the batch is pruned once per set and K batch sums are reduced.  Asynchronous on the
+ *   context's stream; a pending deferred reduction of the context is flushed first and nothing is
+ *   deferred by this call.  Every batch rt_sites_create makes.  RT_ERR_INVALID without rate sets.
+ * rt_sites_get_multi_logliks: loglik f64[K][nsites], status int32[K][nsites] of the last
+ *   rt_step_multi (either may be NULL); set k's slice has the bits a separate rt_model_set_rates +
+ *   rt_step with set k leaves in rt_sites_get_logliks.
+ * rt_sites_get_multi_totals: totals f64[K][3], totals[k] with the meaning and the bits of
+ *   rt_sites_get_totals after a separate step with set k; weighted_sums f64[K] (or NULL),
+ *   weighted_sums[k] = sum_i w_i loglik[k][i] over the sites of non-zero likelihood, w from
+ *   rt_sites_set_weights at the time of the step (default 1), reduced on the device in a fixed
+ *   order (what a pattern-compressed alignment needs).
+ * rt_sites_multi_mixture: per site log sum_k c_k exp(loglik[k][i]) with the maximum taken out;
+ *   sets with c_k = 0 or zero likelihood are skipped, a site where none remains gets -inf and
+ *   RT_SITE_ZERO_PROB.  totals as rt_sites_get_totals, with the site weights applied to
+ *   totals[0].  class_weights f64[K] finite, >= 0, not all zero.  loglik, status and totals may
+ *   each be NULL.  Synchronous; two calls return the same bits.
+ * The getters and the mixture synchronise; they return RT_ERR_INVALID before any rt_step_multi
+ * of the batch and after the number of rate sets changed (until the next rt_step_multi).
+ * rt_sites_multi_kernel_name: the batch's kernel plus ",loop" (one launch per set) or ",multi"
+ *   (one launch for all sets); "" before the first rt_step_multi.  RAOTEH_MULTI=loop forces the
+ *   loop form.                                                                            */
+#define RT_MAX_RATE_SETS 64
+int rt_model_set_rate_sets(rt_model *model, int64_t K, const double *Q, int64_t nq,
+            const int64_t *node_q, const double *t);
+int rt_step_multi(rt_model *model, rt_sites *sites, int recompute_transitions);
+int rt_sites_get_multi_logliks(rt_sites *sites, double *loglik, int32_t *status);
+int rt_sites_get_multi_totals(rt_sites *sites, double *totals, double *weighted_sums);
+int rt_sites_multi_mixture(rt_sites *sites, const double *class_weights, double *loglik,
+            int32_t *status, double totals[3]);
+const char *rt_sites_multi_kernel_name(const rt_sites *sites);
+
 /* ---- 3. multi-GPU: one process per GPU, RCCL over xGMI ------------------- */
 
 /* rank 0 calls rt_comm_unique_id and ships the 128 bytes to the other ranks

@@ -34,6 +34,7 @@ RT_MAX_POSTERIOR_SETS = 8
 RT_MAX_BRANCH_COEFS = 8
 RT_MAX_EXPECT_STATES = 64
 RT_MAX_EXPECT_STEP_STATES = 128
+RT_MAX_RATE_SETS = 64
 
 
 class HipLibraryError(ImportError):
@@ -139,6 +140,12 @@ SIGNATURES = {
     'rt_step': (c_int, [c_void_p, c_void_p, c_int]),
     'rt_sites_get_logliks': (c_int, [c_void_p, _p_f64, _p_i32]),
     'rt_sites_get_totals': (c_int, [c_void_p, _p_f64]),
+    'rt_model_set_rate_sets': (c_int, [c_void_p, c_int64, _p_f64, c_int64, _p_i64, _p_f64]),
+    'rt_step_multi': (c_int, [c_void_p, c_void_p, c_int]),
+    'rt_sites_get_multi_logliks': (c_int, [c_void_p, _p_f64, _p_i32]),
+    'rt_sites_get_multi_totals': (c_int, [c_void_p, _p_f64, _p_f64]),
+    'rt_sites_multi_mixture': (c_int, [c_void_p, _p_f64, _p_f64, _p_i32, _p_f64]),
+    'rt_sites_multi_kernel_name': (c_char_p, [c_void_p]),
     'rt_comm_available': (c_int, []),
     'rt_comm_unique_id': (c_int, [POINTER(c_ubyte)]),
     'rt_comm_init': (c_int, [c_void_p, c_int, c_int, POINTER(c_ubyte)]),

@@ -394,6 +394,14 @@ static int64_t pfrag_doubles(const rt_model *m)
     return nops * nt * kp * 128;
 }
 
+static void rate_sets_release(rt_model *m)
+{
+    rt_rate_sets &r = m->multi;
+    hipFree(r.d_Q); hipFree(r.d_qidx); hipFree(r.d_t); hipFree(r.d_info); hipFree(r.d_step_of_node);
+    hipFree(r.d_P); hipFree(r.d_Pfrag); hipFree(r.d_Pquad); hipFree(r.d_Pcol);
+    r = rt_rate_sets();
+}
+
 extern "C" int rt_model_destroy(rt_model *m)
 {
     if (!m) return RT_OK;
@@ -412,6 +420,7 @@ extern "C" int rt_model_destroy(rt_model *m)
     hipFree(m->d_Pfrag); hipFree(m->d_Pquad); hipFree(m->d_Pcol); hipFree(m->d_root); hipFree(m->d_Q); hipFree(m->d_spec); hipFree(m->d_qidx);
     hipFree(m->d_t); hipFree(m->d_info); hipFree(m->d_step_of_node);
     hipFree(m->d_qidx_step); hipFree(m->d_t_step);
+    rate_sets_release(m);
     delete m;
     return RT_OK;
 }
@@ -663,6 +672,146 @@ extern "C" int rt_expm_spectral(rt_ctx *ctx, int64_t n, int64_t count, const dou
     return RT_OK;
 }
 
+// ---- K rate sets (rt_model_set_rate_sets) ----------------------------------------------------
+
+// schedule steps between two sets' step-ordered tables (n <= 4: each set keeps the zero record
+// the lane kernels fetch ahead of the last step)
+static int64_t rate_sets_steps(const rt_model *m)
+{
+    return (int64_t)m->ops.size() + (m->n <= 4 ? 1 : 0);
+}
+
+// tables for K sets of nq rate matrices each (grow-only; what they held is gone when they grow)
+static int rate_sets_reserve(rt_model *m, int64_t K, int64_t nq)
+{
+    rt_rate_sets &r = m->multi;
+    const int64_t n = m->n, N = m->nnodes, nn = n * n, nops = (int64_t)m->ops.size();
+    if (K * nq > r.q_capacity) {
+        RT_HIP(hipStreamSynchronize(m->ctx->stream));
+        hipFree(r.d_Q);
+        r.d_Q = nullptr;
+        r.q_capacity = 0;
+        RT_HIP(hipMalloc((void **)&r.d_Q, (size_t)(K * nq * nn) * 8));
+        r.q_capacity = K * nq;
+    }
+    if (K <= r.capacity) return RT_OK;
+    RT_HIP(hipStreamSynchronize(m->ctx->stream));
+    double *keep_Q = r.d_Q;
+    const int64_t keep_cap = r.q_capacity;
+    r.d_Q = nullptr;
+    const uint64_t epoch = r.epoch;
+    rate_sets_release(m);
+    r.d_Q = keep_Q;
+    r.q_capacity = keep_cap;
+    r.epoch = epoch + 1;               // whatever a batch holds came from tables that are gone
+    r.P_stride = N * nn;
+    r.frag_stride = pfrag_doubles(m);
+    r.quad_stride = m->d_Pquad ? nops * (int64_t)rt_quad_stride((int)n) : 0;
+    r.pcol_stride = nops * n * 16 * ((n + 15) / 16);
+    hipError_t e = hipMalloc((void **)&r.d_qidx, (size_t)(K * N) * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&r.d_t, (size_t)(K * N) * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&r.d_info, (size_t)(K * N) * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&r.d_step_of_node, (size_t)(K * N) * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&r.d_P, (size_t)(K * r.P_stride) * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&r.d_Pfrag, (size_t)(K * r.frag_stride) * 8);
+    if (e == hipSuccess) e = hipMemset(r.d_Pfrag, 0, (size_t)(K * r.frag_stride) * 8);
+    if (e == hipSuccess && r.quad_stride) {
+        e = hipMalloc((void **)&r.d_Pquad, (size_t)(K * r.quad_stride) * 8);
+        if (e == hipSuccess) e = hipMemset(r.d_Pquad, 0, (size_t)(K * r.quad_stride) * 8);
+    }
+    if (e == hipSuccess) e = hipMemset(r.d_info, 0, (size_t)(K * N) * 8);
+    // step of every node, set k's entries offset by k sets of steps: the expm epilogue's
+    // step-ordered stores of set k land in set k's tables
+    std::vector<int32_t> son((size_t)(K * N));
+    const int64_t steps = rate_sets_steps(m);
+    for (int64_t k = 0; k < K; ++k)
+        for (size_t j = 0; j < m->ops.size(); ++j)
+            son[(size_t)(k * N + m->ops[j].node)] = (int32_t)(k * steps + (int64_t)j);
+    if (e == hipSuccess)
+        e = hipMemcpy(r.d_step_of_node, son.data(), son.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();     // (the memsets are asynchronous)
+    if (e != hipSuccess) {
+        rt_set_error("rt_model_set_rate_sets: %s", hipGetErrorString(e));
+        rate_sets_release(m);
+        m->multi.epoch = epoch + 1;
+        return e == hipErrorOutOfMemory ? RT_ERR_NOMEM : RT_ERR_HIP;
+    }
+    r.capacity = K;
+    return RT_OK;
+}
+
+// the leaf-column tables of the sets, where the model keeps one for its own transitions (a
+// batch of observed states at the leaves exists); fresh: the tables hold new matrices
+static int rate_sets_pack_pcol(rt_model *m, bool fresh)
+{
+    rt_rate_sets &r = m->multi;
+    if (!m->d_Pcol || m->n <= 4 || r.K <= 0) return RT_OK;
+    if (r.pcol_capacity < r.capacity) {
+        RT_HIP(hipStreamSynchronize(m->ctx->stream));
+        hipFree(r.d_Pcol);
+        r.d_Pcol = nullptr;
+        r.pcol_capacity = 0;
+        RT_HIP(hipMalloc((void **)&r.d_Pcol, (size_t)(r.capacity * r.pcol_stride) * 8));
+        r.pcol_capacity = r.capacity;
+        fresh = true;
+    }
+    if (!fresh) return RT_OK;
+    return rt_pack_pcol_sets(m, r.K, r.d_P, r.P_stride, r.d_Pcol, r.pcol_stride);
+}
+
+// the exponentials of all K (nnodes - 1) edges in one launch; the kernel variant goes by the
+// per-set count, so that a set's matrices are those of rt_model_set_rates bit for bit
+static int rate_sets_run_expm(rt_model *m)
+{
+    rt_rate_sets &r = m->multi;
+    RT_TRY(rt_launch_expm(m->ctx, m->n, r.K * m->nnodes, r.d_Q, r.d_qidx, r.d_t, r.d_P, r.d_info,
+                          r.d_step_of_node, m->n <= 4 ? 0 : 1, r.d_Pfrag, nullptr, r.d_Pquad,
+                          m->nnodes));
+    return rate_sets_pack_pcol(m, true);
+}
+
+extern "C" int rt_model_set_rate_sets(rt_model *m, int64_t K, const double *Q, int64_t nq,
+                                      const int64_t *node_q, const double *t)
+{
+    RT_REQUIRE(m && Q && t, "null pointer");
+    RT_REQUIRE(K >= 1 && K <= RT_MAX_RATE_SETS, "K=%lld rate sets: 1..%d", (long long)K,
+               RT_MAX_RATE_SETS);
+    RT_REQUIRE(nq >= 1, "nq must be >= 1");
+    if (m->n > RT_MAX_EXPM_STATES) {
+        rt_set_error("expm: n=%lld > %d", (long long)m->n, RT_MAX_EXPM_STATES);
+        return RT_ERR_UNSUPPORTED;
+    }
+    RT_HIP(hipSetDevice(m->ctx->device));
+    const int64_t N = m->nnodes;
+    const size_t nn = (size_t)m->n * m->n;
+    std::vector<int32_t> qi((size_t)(K * N));
+    std::vector<double> tt((size_t)(K * N));
+    for (int64_t k = 0; k < K; ++k) {
+        qi[(size_t)(k * N)] = -1;
+        tt[(size_t)(k * N)] = 0.0;
+        for (int64_t v = 1; v < N; ++v) {
+            const int64_t q = node_q ? node_q[v] : 0;
+            RT_REQUIRE(q >= 0 && q < nq, "node_q[%lld]=%lld out of range", (long long)v, (long long)q);
+            RT_REQUIRE(std::isfinite(t[k * N + v]),
+                       "branch length of node %lld in rate set %lld is not finite", (long long)v,
+                       (long long)k);
+            qi[(size_t)(k * N + v)] = (int32_t)(k * nq + q);
+            tt[(size_t)(k * N + v)] = t[k * N + v];
+        }
+    }
+    RT_TRY(rate_sets_reserve(m, K, nq));
+    rt_rate_sets &r = m->multi;
+    // pageable sources: synchronous copies (as rt_model_set_rates)
+    RT_HIP(hipStreamSynchronize(m->ctx->stream));
+    RT_HIP(hipMemcpy(r.d_Q, Q, (size_t)(K * nq) * nn * 8, hipMemcpyHostToDevice));
+    RT_HIP(hipMemcpy(r.d_qidx, qi.data(), qi.size() * 4, hipMemcpyHostToDevice));
+    RT_HIP(hipMemcpy(r.d_t, tt.data(), tt.size() * 8, hipMemcpyHostToDevice));
+    if (K != r.K) r.epoch += 1;
+    r.K = K;
+    r.nq = nq;
+    return rate_sets_run_expm(m);
+}
+
 extern "C" int rt_model_recompute_transitions(rt_model *m)
 {
     RT_REQUIRE(m, "null model");
@@ -837,6 +986,9 @@ extern "C" int rt_sites_destroy(rt_sites *s)
     hipFree(s->d_partial); hipFree(s->d_partial_alt); hipFree(s->d_scratch); hipFree(s->d_half);
     hipFree(s->d_half_count);
     hipFree(s->d_leafw);
+    hipFree(s->d_mloglik); hipFree(s->d_mstatus); hipFree(s->d_mpartial); hipFree(s->d_mtotals);
+    hipFree(s->d_mhalf); hipFree(s->d_mhalf_count);
+    if (s->multi_state == 2 && s->multi_fn) rt_jit_ref(s->model->ctx, s->multi_fn, -1);
     if (s->totals_slot >= 0) {
         // keep the free list sorted (descending) so that batches created one after
         // the other keep getting neighbouring slots
@@ -1088,11 +1240,12 @@ static int sites_alloc(rt_sites *s, bool generic)
 // (the probe batches of verify_jit_kernel).
 // the split-M generator in use: pipelined unless RAOTEH_JIT_SPLIT=serial (A/B runs)
 static std::string split_source(const std::vector<rt_op> &ops, int n, int K, int T, int D, int LA,
-                                bool halves = false)
+                                bool halves = false, bool multi = false)
 {
     const char *v = getenv("RAOTEH_JIT_SPLIT");
-    if (v && strcmp(v, "serial") == 0 && !halves) return rt_jit_mfma_split_source(ops, n, K, T, D, LA);
-    return rt_jit_mfma_split_pipelined_source(ops, n, K, T, D, LA, halves);
+    if (v && strcmp(v, "serial") == 0 && !halves && !multi)
+        return rt_jit_mfma_split_source(ops, n, K, T, D, LA);
+    return rt_jit_mfma_split_pipelined_source(ops, n, K, T, D, LA, halves, 0, multi);
 }
 
 // Root halves (jit.hip) for a split-M batch of `ntiles` tiles at one tile per workgroup:
@@ -1576,6 +1729,8 @@ extern "C" int rt_jit_source(int64_t nnodes, const int64_t *idx, const int64_t *
         if (node_obs[(size_t)op.node] >= 0) op.obs = k++;
     const int LA = getenv("RAOTEH_JIT_LOOKAHEAD") ? std::max(1, atoi(getenv("RAOTEH_JIT_LOOKAHEAD"))) : 2;
     const int T = getenv("RAOTEH_JIT_TILES") ? std::min(5, std::max(1, atoi(getenv("RAOTEH_JIT_TILES")))) : 2;
+    // RAOTEH_JIT_SOURCE_MULTI=1: the split-M family's form for all rate sets in one launch
+    const bool multi = getenv("RAOTEH_JIT_SOURCE_MULTI") && atoi(getenv("RAOTEH_JIT_SOURCE_MULTI")) != 0;
     const std::string src = n <= 4
         ? rt_jit_lane_source(m.ops, (int)n, (int)nobs, (int)prefetch, LA, 64, 4,
                              getenv("RAOTEH_JIT_SOURCE_STATES") != nullptr,
@@ -1588,20 +1743,22 @@ extern "C" int rt_jit_source(int64_t nnodes, const int64_t *idx, const int64_t *
                         ? rt_jit_mfma_split_pipelined_source(
                               m.ops, (int)n, (int)nobs, T, 2, 1,
                               getenv("RAOTEH_JIT_HALVES") && atoi(getenv("RAOTEH_JIT_HALVES")),
-                              strcmp(getenv("RAOTEH_JIT_SOURCE_SPARSE"), "pipe2") == 0 ? 2 : 1)
+                              strcmp(getenv("RAOTEH_JIT_SOURCE_SPARSE"), "pipe2") == 0 ? 2 : 1, multi)
                   : getenv("RAOTEH_JIT_SOURCE_SPARSE")
                         ? rt_jit_mfma_split_source(m.ops, (int)n, (int)nobs, std::min(T, 2), 2, 1, 1)
                   : split_source(m.ops, (int)n, (int)nobs,
                                  getenv("RAOTEH_JIT_HALVES") && atoi(getenv("RAOTEH_JIT_HALVES"))
                                      ? T : std::min(T, 3), (int)prefetch, 1,
-                                 getenv("RAOTEH_JIT_HALVES") && atoi(getenv("RAOTEH_JIT_HALVES")));
+                                 getenv("RAOTEH_JIT_HALVES") && atoi(getenv("RAOTEH_JIT_HALVES")), multi);
     RT_REQUIRE((int64_t)src.size() + 1 <= capacity, "buffer too small: %lld bytes needed",
                (long long)src.size() + 1);
     memcpy(buf, src.c_str(), src.size() + 1);
     return RT_OK;
 }
 
-static int verify_jit_kernel(rt_sites *s, int kind);
+static void sites_multi_poll(rt_sites *s, bool wait);
+static int verify_jit_kernel(rt_sites *s, int kind, void *multi_fn = nullptr,
+                             void *multi_combine = nullptr);
 
 static int sites_create_impl(rt_model *m, int64_t nsites, int kind, int64_t nobs,
                              const int64_t *obs_nodes, const void *data,
@@ -1806,7 +1963,10 @@ extern "C" int rt_sites_create(rt_model *m, int64_t nsites, int kind, int64_t no
 // transition matrices, root weights and observations on the batch's own tree) next to the
 // interpreter kernel, and is used only if all log-likelihoods and statuses agree bit for
 // bit -- which is what correct code guarantees (same arithmetic order).  ~1 ms per compile.
-static int verify_jit_kernel(rt_sites *s, int kind)
+// multi_fn: the kernel under test is the batch kernel's multi form (one launch for all rate
+// sets, rt_step_multi): the probe batch gets the batch's own (verified) kernel, the probe model
+// two random rate sets, and one launch must leave the bits of the loop form.
+static int verify_jit_kernel(rt_sites *s, int kind, void *multi_fn, void *multi_combine)
 {
     rt_model *m = s->model;
     const int64_t n = m->n, N = m->nnodes, K = s->nobs;
@@ -1899,6 +2059,55 @@ static int verify_jit_kernel(rt_sites *s, int kind)
     // no event timing for the probe launches (they are not the caller's)
     const bool timing = m->ctx->timing;
     m->ctx->timing = false;
+    if (multi_fn) {
+        std::vector<double> Q((size_t)2 * n * n), tt((size_t)2 * N), la((size_t)2 * np),
+            lb((size_t)2 * np), ta(6), tb(6);
+        std::vector<int32_t> sa((size_t)2 * np), sb((size_t)2 * np);
+        for (int k = 0; k < 2; ++k)
+            for (int64_t a = 0; a < n; ++a) {
+                double row = 0.0;
+                for (int64_t b = 0; b < n; ++b)
+                    if (a != b) row += Q[(size_t)((k * n + a) * n + b)] = (0.1 + next()) / (double)n;
+                Q[(size_t)((k * n + a) * n + a)] = -row;
+            }
+        for (double &v : tt) v = 0.05 + 0.4 * next();
+        if (rc == RT_OK) rc = rt_model_set_rate_sets(tm, 2, Q.data(), 1, nullptr, tt.data());
+        if (rc == RT_OK) {
+            sj->multi_state = -1;                     // the loop form
+            sj->multi_for = sj->jit_fn;
+            rc = rt_step_multi(tm, sj, 0);
+        }
+        if (rc == RT_OK) rc = rt_sites_get_multi_logliks(sj, la.data(), sa.data());
+        if (rc == RT_OK) rc = rt_sites_get_multi_totals(sj, ta.data(), nullptr);
+        if (rc == RT_OK) {
+            sj->multi_state = 2;                      // the kernel under test (not owned)
+            sj->multi_fn = multi_fn;
+            sj->multi_combine = multi_combine;
+            sj->multi_for = sj->jit_fn;
+            rc = rt_step_multi(tm, sj, 0);
+            if (rc == RT_OK && !strstr(sj->multi_kernel_name, ",multi")) {
+                rt_set_error("probe batch did not run the multi form");
+                rc = RT_ERR_UNSUPPORTED;
+            }
+        }
+        if (rc == RT_OK) rc = rt_sites_get_multi_logliks(sj, lb.data(), sb.data());
+        if (rc == RT_OK) rc = rt_sites_get_multi_totals(sj, tb.data(), nullptr);
+        if (sj) {
+            sj->multi_fn = sj->multi_combine = nullptr;
+            sj->multi_state = -1;
+        }
+        m->ctx->timing = timing;
+        if (rc == RT_OK &&
+            (memcmp(la.data(), lb.data(), la.size() * 8) != 0 || sa != sb ||
+             memcmp(ta.data(), tb.data(), 6 * 8) != 0)) {
+            rt_set_error("multi-form kernel rejected: its probe results differ from the loop form");
+            rc = RT_ERR_UNSUPPORTED;
+        }
+        rt_sites_destroy(si);
+        rt_sites_destroy(sj);
+        rt_model_destroy(tm);
+        return rc;
+    }
     if (rc == RT_OK) rc = rt_prune(tm, si);
     if (rc == RT_OK) rc = rt_prune(tm, sj);
     m->ctx->timing = timing;
@@ -2093,7 +2302,13 @@ int rt_sites_jit_poll(rt_sites *s, bool wait)
 extern "C" int rt_sites_jit_wait(rt_sites *s)
 {
     RT_REQUIRE(s, "null pointer");
-    return rt_sites_jit_poll(s, true);
+    RT_TRY(rt_sites_jit_poll(s, true));
+    // ... and the multi form of its kernel, if a multi step has asked for one
+    if (s->multi_state == 1) {
+        RT_HIP(hipSetDevice(s->model->ctx->device));
+        sites_multi_poll(s, true);
+    }
+    return RT_OK;
 }
 
 extern "C" int rt_sites_clone(rt_sites *src, rt_sites **out)
@@ -2324,6 +2539,313 @@ extern "C" int rt_sites_get_totals(rt_sites *s, double totals[3])
         RT_HIP(hipStreamSynchronize(s->model->ctx->comm_stream));
     RT_HIP(hipMemcpy(totals, s->d_totals, 3 * 8, hipMemcpyDeviceToHost));
     return RT_OK;
+}
+
+// ---- rt_step_multi --------------------------------------------------------------------------
+
+// per-set result buffers of a batch for K sets in its current resident layout
+static int sites_multi_reserve(rt_sites *s, int64_t K)
+{
+    const int64_t padded = s->nblocks * (s->layout == RT_LAYOUT_LANE ? s->block_sites : 16);
+    if (K <= s->multi_capacity && padded == s->multi_padded && s->npartials == s->multi_npartials)
+        return RT_OK;
+    hipStream_t st = s->model->ctx->stream;
+    const int64_t cap = std::max(K, s->multi_capacity);
+    RT_HIP(hipStreamSynchronize(st));
+    hipFree(s->d_mloglik); hipFree(s->d_mstatus); hipFree(s->d_mpartial); hipFree(s->d_mtotals);
+    s->d_mloglik = s->d_mpartial = s->d_mtotals = nullptr;
+    s->d_mstatus = nullptr;
+    s->multi_capacity = 0;
+    s->multi_K = 0;
+    s->multi_last_valid = false;
+    const size_t tot = (size_t)rt_multi_totals_doubles(cap, s->nsites) * 8;
+    hipError_t e = hipMalloc((void **)&s->d_mloglik, (size_t)(cap * padded) * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_mstatus, (size_t)(cap * padded) * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_mpartial, (size_t)(cap * s->npartials) * 16);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_mtotals, tot);
+    // entries no kernel writes (padding of the last workgroup) must read as zero
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_mpartial, 0, (size_t)(cap * s->npartials) * 16, st);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_mtotals, 0, tot, st);
+    if (e != hipSuccess) {
+        rt_set_error("rt_step_multi: %s", hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? RT_ERR_NOMEM : RT_ERR_HIP;
+    }
+    s->multi_capacity = cap;
+    s->multi_padded = padded;
+    s->multi_npartials = s->npartials;
+    return RT_OK;
+}
+
+// One launch for all sets: which batches have such a form (the split-M family at 33..64 states
+// running a kernel of the pipelined generator) ...
+static bool multi_form_possible(const rt_sites *s)
+{
+    const rt_model *m = s->model;
+    if (!s->jit_fn || s->jit_fn2 || s->layout != RT_LAYOUT_MFMA || m->n <= 32 || m->n > 64) return false;
+    if (s->jit_sparse && !s->jit_pipe) return false;            // the serial generator's leaf states
+    const char *sv = getenv("RAOTEH_JIT_SPLIT");
+    if (sv && strcmp(sv, "serial") == 0 && !s->jit_halves && !s->jit_sparse) return false;
+    const char *mv = getenv("RAOTEH_MULTI");
+    if (mv && strcmp(mv, "loop") == 0) return false;
+    return true;
+}
+
+// ... the kernel is in the context's cache: take it, with its combine kernel, and verify it on a
+// probe batch against the loop form unless somebody has
+static void sites_multi_take(rt_sites *s)
+{
+    rt_ctx *ctx = s->model->ctx;
+    void *fn = nullptr, *comb = nullptr;
+    s->multi_state = -1;
+    if (rt_jit_get(ctx, s->multi_src, &fn, true, nullptr) != RT_OK) return;
+    int rc = RT_OK;
+    if (s->jit_halves && !s->jit_fold) rc = rt_jit_companion(ctx, fn, "rt_jit_combine", &comb);
+    if (rc == RT_OK && !rt_jit_verified(ctx, fn) && !getenv("RAOTEH_JIT_NO_VERIFY")) {
+        rc = verify_jit_kernel(s, s->jit_kind, fn, comb);
+        rt_jit_set_verified(ctx, fn, rc == RT_OK);
+    }
+    if (rc != RT_OK) {
+        rt_jit_ref(ctx, fn, -1);
+        return;
+    }
+    s->multi_fn = fn;
+    s->multi_combine = comb;
+    s->multi_state = 2;
+}
+
+// ... and where the batch stands: asked for at the first multi step that meets the batch (in
+// the background unless the kernel is cached or the "jit" option forces kernels), taken when
+// the job is done.  Any failure leaves the batch on the loop form.
+static void sites_multi_poll(rt_sites *s, bool wait)
+{
+    rt_ctx *ctx = s->model->ctx;
+    if (s->multi_for != s->jit_fn) {                 // the batch changed its kernel
+        if (s->multi_state == 2 && s->multi_fn) rt_jit_ref(ctx, s->multi_fn, -1);
+        s->multi_fn = s->multi_combine = nullptr;
+        s->multi_job.reset();
+        s->multi_state = 0;
+        s->multi_for = s->jit_fn;
+    }
+    if (s->multi_state == 0) {
+        if (!multi_form_possible(s)) return;
+        s->multi_src = rt_jit_mfma_split_pipelined_source(
+            s->ops, (int)s->model->n, (int)s->nobs, s->jit_tiles, s->jit_prefetch, s->jit_lookahead,
+            s->jit_halves, s->jit_sparse ? (s->sparse_pairs ? 2 : 1) : 0, true);
+        const int known = s->multi_src.empty() ? -1 : rt_jit_cached(ctx, s->multi_src);
+        if (known < 0) {
+            s->multi_state = -1;
+            return;
+        }
+        int want = opt_jit(ctx);
+        if (const char *v = getenv("RAOTEH_JIT")) want = atoi(v);
+        if (known > 0 || want > 0 || !opt_jit_async(ctx)) {
+            sites_multi_take(s);
+            return;
+        }
+        if (jit_jobs_full()) return;                 // asked for again at the next multi step
+        s->multi_job = rt_jit_start(ctx, std::vector<std::string>(1, s->multi_src), true);
+        s->multi_state = 1;
+    }
+    if (s->multi_state == 1) {
+        if (!rt_jit_job_done(s->multi_job.get(), wait)) return;
+        std::shared_ptr<rt_jit_job> job;
+        job.swap(s->multi_job);
+        int rc = RT_OK, chosen = -1;
+        double seconds = 0.0;
+        std::string err;
+        rt_jit_job_result(job.get(), &rc, &chosen, &seconds, &err);
+        if (rc != RT_OK || chosen != 0) {
+            rt_set_error("background compile of the multi form: %s", err.c_str());
+            s->multi_state = -1;
+            return;
+        }
+        sites_multi_take(s);
+    }
+}
+
+// K copies of the root-halves buffer (and of the arrival counters) for the one-launch form
+static int sites_multi_reserve_halves(rt_sites *s, int64_t K)
+{
+    if (!s->jit_halves) return RT_OK;
+    const int64_t n = s->model->n;
+    const int64_t hs = (s->nblocks + 8) * 2 * ((n + 15) / 16) * 4 * 64, cs = s->nblocks + 8;
+    if (K <= s->multi_half_capacity && hs == s->multi_half_stride) return RT_OK;
+    hipStream_t st = s->model->ctx->stream;
+    RT_HIP(hipStreamSynchronize(st));
+    hipFree(s->d_mhalf);
+    hipFree(s->d_mhalf_count);
+    s->d_mhalf = nullptr;
+    s->d_mhalf_count = nullptr;
+    s->multi_half_capacity = 0;
+    hipError_t e = hipMalloc((void **)&s->d_mhalf, (size_t)(K * hs) * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_mhalf_count, (size_t)(K * cs) * 4);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_mhalf_count, 0, (size_t)(K * cs) * 4, st);
+    if (e != hipSuccess) {
+        rt_set_error("rt_step_multi: %s", hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? RT_ERR_NOMEM : RT_ERR_HIP;
+    }
+    s->multi_half_capacity = K;
+    s->multi_half_stride = hs;
+    s->multi_count_stride = cs;
+    return RT_OK;
+}
+
+extern "C" int rt_step_multi(rt_model *m, rt_sites *s, int recompute_transitions)
+{
+    RT_REQUIRE(m && s, "null pointer");
+    RT_REQUIRE(s->model == m, "the site batch belongs to another model");
+    RT_REQUIRE(m->multi.K > 0, "rt_model_set_rate_sets has not been called");
+    rt_ctx *ctx = m->ctx;
+    rt_rate_sets &r = m->multi;
+    RT_HIP(hipSetDevice(ctx->device));
+    if (s->jit_job) RT_TRY(rt_sites_jit_poll(s, false));
+    // nothing of this call is deferred, and what was is reduced now
+    RT_TRY(rt_flush_reduce(ctx));
+    if (recompute_transitions) RT_TRY(rate_sets_run_expm(m));
+    else RT_TRY(rate_sets_pack_pcol(m, false));      // (a leaf-state batch created since)
+    const int64_t K = r.K;
+    RT_TRY(sites_multi_reserve(s, K));
+    // the interpreter kernel and a specialised one leave their per-wave partial sums in
+    // different places: what the other one wrote must read as zero
+    if (s->multi_last_valid && s->multi_last_fn != s->jit_fn)
+        RT_HIP(hipMemsetAsync(s->d_mpartial, 0, (size_t)(s->multi_capacity * s->multi_npartials) * 16,
+                              ctx->stream));
+    s->multi_K = 0;
+    // one launch for all sets where the batch has that form of its kernel (split-M family)
+    if (s->multi_state >= 0 || s->multi_for != s->jit_fn) sites_multi_poll(s, false);
+    const bool one_launch = s->multi_state == 2 && s->multi_fn && s->multi_for == s->jit_fn &&
+                            (!s->jit_sparse || r.d_Pcol);
+    if (one_launch) {
+        RT_TRY(sites_multi_reserve_halves(s, K));
+        rt_multi_launch a;
+        a.K = K;
+        a.Pfrag = r.d_Pfrag;
+        a.Pcol = r.d_Pcol;
+        a.loglik = s->d_mloglik;
+        a.status = s->d_mstatus;
+        a.partial = s->d_mpartial;
+        a.half = s->d_mhalf;
+        a.counters = s->d_mhalf_count;
+        a.s_table = (long)r.frag_stride;
+        a.s_site = (long)s->multi_padded;
+        a.s_partial = (long)s->multi_npartials * 2;
+        a.s_half = (long)s->multi_half_stride;
+        a.s_count = (long)s->multi_count_stride;
+        a.s_pcol = (long)r.pcol_stride;
+        // (the name rt_launch_prune gives the batch's kernel)
+        snprintf(s->multi_kernel_name, sizeof(s->multi_kernel_name), "prune_tree_jit_mfma<%d,T%d%s>,multi",
+                 (int)m->n, s->jit_tiles,
+                 s->jit_sparse && s->jit_halves ? ",halves,leaf-states"
+                 : s->jit_sparse ? (s->jit_pipe ? ",pipelined,leaf-states" : ",leaf-states")
+                 : s->jit_halves ? ",halves" : "");
+        hipEvent_t ev = nullptr;
+        rt_time_begin(ctx, RT_K_PRUNE, s->multi_kernel_name, &ev);
+        RT_TRY(rt_launch_prune_jit_multi(m, s, a));
+        rt_time_end(ctx, RT_K_PRUNE, ev);
+    }
+    // loop form: one launch per set of whatever kernel the batch runs, on that set's tables and
+    // output slices (RAOTEH_MULTI=loop asks for exactly this)
+    for (int64_t k = 0; k < K && !one_launch; ++k) {
+        rt_prune_view v;
+        v.P = r.d_P + k * r.P_stride;
+        v.Pfrag = r.d_Pfrag + k * r.frag_stride;
+        v.Pquad = r.d_Pquad ? r.d_Pquad + k * r.quad_stride : nullptr;
+        v.Pcol = r.d_Pcol ? r.d_Pcol + k * r.pcol_stride : nullptr;
+        v.loglik = s->d_mloglik + k * s->multi_padded;
+        v.status = s->d_mstatus + k * s->multi_padded;
+        v.partial = s->d_mpartial + k * s->multi_npartials * 2;
+        RT_TRY(rt_launch_prune(m, s, false, false, &v));
+    }
+    s->multi_last_fn = s->jit_fn;
+    s->multi_last_valid = true;
+    RT_TRY(rt_multi_reduce_launch(ctx, K, s->d_mpartial, s->multi_npartials, s->d_mloglik, s->d_mstatus,
+                                  s->multi_padded, s->nsites, s->d_weights, s->d_mtotals,
+                                  s->d_mtotals + 3 * K));
+    if (!one_launch)
+        snprintf(s->multi_kernel_name, sizeof(s->multi_kernel_name), "%s,loop", s->kernel_name);
+    s->multi_K = K;
+    s->multi_epoch = r.epoch;
+    return RT_OK;
+}
+
+static int sites_multi_ready(const rt_sites *s, const char *who)
+{
+    RT_REQUIRE(s->multi_K > 0, "%s: no rt_step_multi has written this batch yet", who);
+    RT_REQUIRE(s->multi_epoch == s->model->multi.epoch && s->multi_K == s->model->multi.K,
+               "%s: the number of rate sets changed since the batch's last rt_step_multi", who);
+    return RT_OK;
+}
+
+extern "C" int rt_sites_get_multi_logliks(rt_sites *s, double *loglik, int32_t *status)
+{
+    RT_REQUIRE(s, "null pointer");
+    RT_TRY(sites_multi_ready(s, "rt_sites_get_multi_logliks"));
+    RT_HIP(hipSetDevice(s->model->ctx->device));
+    RT_HIP(hipStreamSynchronize(s->model->ctx->stream));
+    if (loglik)
+        RT_HIP(hipMemcpy2D(loglik, (size_t)s->nsites * 8, s->d_mloglik, (size_t)s->multi_padded * 8,
+                           (size_t)s->nsites * 8, (size_t)s->multi_K, hipMemcpyDeviceToHost));
+    if (status)
+        RT_HIP(hipMemcpy2D(status, (size_t)s->nsites * 4, s->d_mstatus, (size_t)s->multi_padded * 4,
+                           (size_t)s->nsites * 4, (size_t)s->multi_K, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" int rt_sites_get_multi_totals(rt_sites *s, double *totals, double *weighted_sums)
+{
+    RT_REQUIRE(s && totals, "null pointer");
+    RT_TRY(sites_multi_ready(s, "rt_sites_get_multi_totals"));
+    RT_HIP(hipSetDevice(s->model->ctx->device));
+    RT_HIP(hipStreamSynchronize(s->model->ctx->stream));
+    // totals [K][3] and the weighted sums [K] are neighbours: one copy
+    std::vector<double> h((size_t)s->multi_K * 4);
+    RT_HIP(hipMemcpy(h.data(), s->d_mtotals, h.size() * 8, hipMemcpyDeviceToHost));
+    memcpy(totals, h.data(), (size_t)s->multi_K * 3 * 8);
+    if (weighted_sums) memcpy(weighted_sums, h.data() + 3 * s->multi_K, (size_t)s->multi_K * 8);
+    return RT_OK;
+}
+
+extern "C" int rt_sites_multi_mixture(rt_sites *s, const double *class_weights, double *loglik,
+                                      int32_t *status, double totals[3])
+{
+    RT_REQUIRE(s && class_weights, "null pointer");
+    RT_TRY(sites_multi_ready(s, "rt_sites_multi_mixture"));
+    const int64_t K = s->multi_K;
+    std::vector<double> logc((size_t)K);
+    bool any = false;
+    for (int64_t k = 0; k < K; ++k) {
+        const double c = class_weights[k];
+        RT_REQUIRE(std::isfinite(c) && c >= 0.0, "class_weights[%lld] is not finite and >= 0",
+                   (long long)k);
+        any = any || c > 0.0;
+        logc[(size_t)k] = c > 0.0 ? std::log(c) : -HUGE_VAL;
+    }
+    RT_REQUIRE(any, "class_weights are all zero");
+    rt_ctx *ctx = s->model->ctx;
+    RT_HIP(hipSetDevice(ctx->device));
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t nparts = (size_t)((s->nsites + 255) / 256);
+    const size_t o_c = 0, o_ll = o_c + up((size_t)K * 8), o_st = o_ll + up((size_t)s->nsites * 8),
+                 o_part = o_st + up((size_t)s->nsites * 4), o_tot = o_part + up(nparts * 16),
+                 total = o_tot + up(3 * 8);
+    RT_TRY(rt_scratch_reserve(ctx, total));
+    unsigned char *base = ctx->d_scratch;
+    double *d_c = (double *)(base + o_c), *d_ll = (double *)(base + o_ll),
+           *d_part = (double *)(base + o_part), *d_tot = (double *)(base + o_tot);
+    int32_t *d_st = (int32_t *)(base + o_st);
+    RT_HIP(hipMemcpyAsync(d_c, logc.data(), (size_t)K * 8, hipMemcpyHostToDevice, ctx->stream));
+    RT_TRY(rt_multi_mixture_launch(ctx, K, d_c, s->d_mloglik, s->d_mstatus, s->multi_padded, s->nsites,
+                                   s->d_weights, d_ll, d_st, d_part, d_tot));
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    if (loglik) RT_HIP(hipMemcpy(loglik, d_ll, (size_t)s->nsites * 8, hipMemcpyDeviceToHost));
+    if (status) RT_HIP(hipMemcpy(status, d_st, (size_t)s->nsites * 4, hipMemcpyDeviceToHost));
+    if (totals) RT_HIP(hipMemcpy(totals, d_tot, 3 * 8, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" const char *rt_sites_multi_kernel_name(const rt_sites *s)
+{
+    return s ? s->multi_kernel_name : "";
 }
 
 // Debug / test hook: copy the post-order schedule out (rt_op as int32[4]).

@@ -127,6 +127,26 @@ struct rt_op {
     int32_t dst;       // parent's accumulator slot | (first child ? 256 : 0); -1 root
 };
 
+// rt_model_set_rate_sets: K rate sets next to the state rt_model_set_rates owns.  Every table a
+// pruning kernel reads exists K times, set k at k * (its per-set stride): one expm launch over
+// K * nnodes matrices fills them all (the rate-matrix index and the step index of an edge are
+// offset by its set, so the epilogue's step-ordered stores land in the set's own tables).
+struct rt_rate_sets {
+    int64_t K = 0;                  // sets resident (0: rt_model_set_rate_sets not called yet)
+    int64_t capacity = 0;           // sets the tables are allocated for (grow-only)
+    int64_t nq = 0, q_capacity = 0; // rate matrices per set / K * nq the buffer holds
+    uint64_t epoch = 0;             // bumped whenever K changes: results of another K are stale
+    double *d_Q = nullptr;          // [K][nq][n][n]
+    int32_t *d_qidx = nullptr;      // [K][nnodes], set k's entries + k * nq (root: -1)
+    double *d_t = nullptr;          // [K][nnodes]
+    int32_t *d_info = nullptr;      // [K][nnodes][2]
+    int32_t *d_step_of_node = nullptr;  // [K][nnodes], set k's entries + k * steps per set
+    double *d_P = nullptr;          // [K][nnodes][n][n]
+    double *d_Pfrag = nullptr, *d_Pquad = nullptr, *d_Pcol = nullptr;
+    int64_t pcol_capacity = 0;
+    int64_t P_stride = 0, frag_stride = 0, quad_stride = 0, pcol_stride = 0;   // doubles per set
+};
+
 struct rt_model {
     rt_ctx *ctx = nullptr;
     int64_t nnodes = 0;
@@ -173,6 +193,7 @@ struct rt_model {
     int live_batches = 0;           // site batches created from this model and not yet destroyed
     void *expect_state = nullptr;   // expect_mfma.hip: device buffers of rt_expect_step (lazy)
     void *expect_lane_state = nullptr;  // passes.hip: its n <= 8 form (plan, pattern bits)
+    rt_rate_sets multi;             // rt_model_set_rate_sets (buffers allocated on first use)
 };
 
 // Device layouts of a site batch:
@@ -290,6 +311,30 @@ struct rt_sites {
     // they hold nothing and rt_sites_get_logliks refuses
     bool pruned = false;
     char kernel_name[64] = "";      // the pruning kernel variant of this batch
+    // rt_step_multi: per-set results [K][...] next to the batch's own (allocated on first use,
+    // again when K grows or the batch changes its resident layout)
+    int64_t multi_capacity = 0;     // sets the buffers hold
+    int64_t multi_padded = 0, multi_npartials = 0;   // per-set strides they were allocated with
+    int64_t multi_K = 0;            // sets of the last rt_step_multi (0: none yet)
+    uint64_t multi_epoch = 0;       // the model's rate-set epoch at that step
+    void *multi_last_fn = nullptr;  // kernel that last wrote d_mpartial (another one: zero them)
+    bool multi_last_valid = false;
+    double *d_mloglik = nullptr;    // [K][multi_padded]
+    int32_t *d_mstatus = nullptr;   // [K][multi_padded]
+    double *d_mpartial = nullptr;   // [K][multi_npartials][2]
+    double *d_mtotals = nullptr;    // [K][3], then [K] weighted sums
+    char multi_kernel_name[80] = "";
+    // one launch for all sets (split-M family, 33..64 states): the batch's own kernel form
+    // generated with the multi prologue (jit.hip), a cache entry of its own.  multi_state:
+    // 0 not asked for yet, 1 compiling in the background, 2 verified and in use, -1 none
+    // (rejected or failed: the loop form runs); multi_for: the batch kernel it belongs to
+    int multi_state = 0;
+    void *multi_fn = nullptr, *multi_combine = nullptr, *multi_for = nullptr;
+    std::shared_ptr<rt_jit_job> multi_job;
+    std::string multi_src;
+    double *d_mhalf = nullptr;      // [K][multi_half_stride] root halves per set
+    int *d_mhalf_count = nullptr;   // [K][multi_count_stride] arrival counters per set
+    int64_t multi_half_stride = 0, multi_count_stride = 0, multi_half_capacity = 0;
     double jit_compile_s = 0.0;     // hiprtc time spent for this batch (0: cache hit / none)
 };
 
@@ -314,11 +359,14 @@ int rt_expm_wide_launch(rt_ctx *ctx, int nt, bool split2, size_t grid, int64_t n
                         const int *d_qidx, const double *d_t, double *d_P, int *d_info,
                         const int *d_step_of_node, int frag_kind, double *d_Pfrag,
                         const rt_reduce_args &red);
+// variant_count > 0: the kernel variant (one or two workgroups per matrix) is chosen as for
+// that many matrices, whatever `count` is (K rate sets in one launch: each set's matrices are
+// those of a launch over the set alone, bit for bit)
 int rt_launch_expm(rt_ctx *ctx, int64_t n, int64_t count, const double *d_Q,
                    const int32_t *d_qidx, const double *d_t, double *d_P,
                    int32_t *d_info, const int32_t *d_step_of_node, int frag_kind,
                    double *d_Pfrag, const rt_reduce_args *fused_reduce = nullptr,
-                   double *d_Pquad = nullptr);
+                   double *d_Pquad = nullptr, int64_t variant_count = 0);
 // spectral.hip: P_e = A diag(exp(lam t_e)) B per edge, outputs as rt_launch_expm's
 int rt_launch_spectral(rt_ctx *ctx, int64_t n, int64_t count, const double *d_A,
                        const double *d_lam, const double *d_B, const double *d_D,
@@ -343,9 +391,34 @@ int rt_flush_reduce(rt_ctx *ctx);
 int rt_launch_pfrag(rt_model *m);
 int rt_model_pack_pcol(rt_model *m);            // (no-op without d_Pcol)
 int rt_model_need_pcol(rt_model *m);            // allocate + fill from the current d_P
+// the leaf-column tables of `sets` rate sets, set k from d_P + k * P_stride to d_Pcol + k * pcol_stride
+int rt_pack_pcol_sets(rt_model *m, int64_t sets, const double *d_P, int64_t P_stride, double *d_Pcol,
+                      int64_t pcol_stride);
+// The tables a pruning launch reads and the per-site outputs it writes, when they are not the
+// model's and the batch's own (rt_step_multi: one rate set's tables, that set's output slices).
+// The observations, the root weights, the programs and the scratch of the batch stay its own.
+struct rt_prune_view {
+    const double *P = nullptr, *Pfrag = nullptr, *Pquad = nullptr, *Pcol = nullptr;
+    double *loglik = nullptr;
+    int32_t *status = nullptr;
+    double *partial = nullptr;
+};
+// multi.hip: K fixed-order reductions (the arithmetic of rt_flush_reduce's kernel per set) and
+// the weighted sums, asynchronous on the context's stream; the per-site mixture over the sets
+int64_t rt_multi_totals_doubles(int64_t K, int64_t nsites);   // doubles behind d_totals
+int rt_multi_reduce_launch(rt_ctx *ctx, int64_t K, const double *d_partial, int64_t npartials,
+                           const double *d_loglik, const int32_t *d_status, int64_t padded,
+                           int64_t nsites, const double *d_weights, double *d_totals,
+                           double *d_wsums);
+int rt_multi_mixture_launch(rt_ctx *ctx, int64_t K, const double *d_logc, const double *d_loglik,
+                            const int32_t *d_status, int64_t padded, int64_t nsites,
+                            const double *d_weights, double *d_out, int32_t *d_out_status,
+                            double *d_partial, double *d_totals);
 // fuse_expm: the pruning launch computes the transitions from the resident rates itself
 // (batches with jit_fused only) and carries the pending reduction
-int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce = false, bool fuse_expm = false);
+// view: the launch reads / writes these instead (no reduction follows, nothing is deferred)
+int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce = false, bool fuse_expm = false,
+                    const struct rt_prune_view *view = nullptr);
 // what such a launch is handed besides the pruning arguments
 struct rt_fuse_args {
     rt_reduce_args red;     // partial == nullptr: nothing carried
@@ -362,7 +435,7 @@ std::string rt_jit_mfma_split_source(const std::vector<rt_op> &ops, int n, int K
 bool rt_jit_fold_enabled();
 std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, int n, int K, int T,
                                                int D, int LA, bool halves = false,
-                                               int sparse = 0);
+                                               int sparse = 0, bool multi = false);
 // steps of the two root programs the halves form would run (0, 0: the root has < 2 children)
 void rt_jit_root_halves(const std::vector<rt_op> &ops, int *stepsA, int *stepsB);
 // the cut itself: A = the subtrees of all children of the root but the last, B = the last
@@ -392,7 +465,21 @@ int rt_jit_verified(const rt_ctx *ctx, void *fn);
 void rt_jit_set_verified(const rt_ctx *ctx, void *fn, bool ok);
 void rt_jit_release(const rt_ctx *ctx);
 int rt_jit_read_global(const rt_ctx *ctx, void *fn, const char *name, void *dst, size_t bytes);
-int rt_launch_prune_jit(rt_model *m, rt_sites *s, const rt_fuse_args *fuse = nullptr);
+int rt_launch_prune_jit(rt_model *m, rt_sites *s, const rt_fuse_args *fuse = nullptr,
+                        const struct rt_prune_view *view = nullptr);
+// one launch for all K rate sets of a split-M batch whose multi-form kernel is s->multi_fn:
+// set k reads Pfrag + k s_table (Pcol + k s_pcol) and writes loglik / status + k s_site,
+// partial + k s_partial (half + k s_half, counters + k s_count)
+struct rt_multi_launch {
+    int64_t K = 0;
+    const double *Pfrag = nullptr, *Pcol = nullptr;
+    double *loglik = nullptr;
+    int32_t *status = nullptr;
+    double *partial = nullptr, *half = nullptr;
+    int *counters = nullptr;
+    long s_table = 0, s_site = 0, s_partial = 0, s_half = 0, s_count = 0, s_pcol = 0;
+};
+int rt_launch_prune_jit_multi(rt_model *m, rt_sites *s, const rt_multi_launch &a);
 // a batch that runs the interpreter kernels only (no tree-specialised kernel is compiled)
 int rt_sites_create_interpreter(rt_model *m, int64_t nsites, int kind, int64_t nobs,
                                 const int64_t *obs_nodes, const void *data, rt_sites **out);

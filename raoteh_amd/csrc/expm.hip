@@ -1452,8 +1452,11 @@ expm_small_taylor_kernel(int count, const double *__restrict__ Q, const int *__r
 int rt_launch_expm(rt_ctx *ctx, int64_t n, int64_t count, const double *d_Q,
                    const int32_t *d_qidx, const double *d_t, double *d_P,
                    int32_t *d_info, const int32_t *d_step_of_node, int frag_kind,
-                   double *d_Pfrag, const rt_reduce_args *fused_reduce, double *d_Pquad)
+                   double *d_Pfrag, const rt_reduce_args *fused_reduce, double *d_Pquad,
+                   int64_t variant_count)
 {
+    // what the choice between one and two workgroups per matrix goes by
+    const int64_t vcount = variant_count > 0 ? variant_count : count;
     // one extra workgroup when the launch carries the pending reduction of a batch
     const rt_reduce_args red = fused_reduce ? *fused_reduce : rt_reduce_args();
     const unsigned extra = red.partial ? 1u : 0u;
@@ -1535,7 +1538,7 @@ int rt_launch_expm(rt_ctx *ctx, int64_t n, int64_t count, const double *d_Q,
         // RAOTEH_EXPM_WIDE=0: the global-scratch form.  Few matrices: two workgroups each
         const char *wv = getenv("RAOTEH_EXPM_WIDE");
         if (global && !(wv && atoi(wv) == 0) && !d_Pquad) {
-            bool split2 = 2 * count + extra <= (int64_t)std::max(2, ctx->num_cus);
+            bool split2 = 2 * vcount + extra <= (int64_t)std::max(2, ctx->num_cus);
             if (const char *v = getenv("RAOTEH_EXPM_SPLIT")) split2 = atoi(v) != 0;
             const size_t wgs = (size_t)count * (split2 ? 2 : 1);
             const size_t need = wgs * ((nt + 1) / 2) * 4 * nt * 256 * 8;   // A, A^2 in D layout per workgroup
@@ -1586,7 +1589,7 @@ int rt_launch_expm(rt_ctx *ctx, int64_t n, int64_t count, const double *d_Q,
         const bool waves8 = (nt == 3 || nt == 4) && !(wv8 && atoi(wv8) == 4);
         // few 49..64-state matrices (the edges of one tree): two workgroups per matrix, the
         // Horner steps in column halves (RAOTEH_EXPM_SPLIT=0 / 1 overrides)
-        bool split2 = nt == 4 && 2 * count + extra <= (int64_t)std::max(2, ctx->num_cus) && !d_Pquad;
+        bool split2 = nt == 4 && 2 * vcount + extra <= (int64_t)std::max(2, ctx->num_cus) && !d_Pquad;
         if (const char *v = getenv("RAOTEH_EXPM_SPLIT")) split2 = nt == 4 && !d_Pquad && atoi(v) != 0;
         if (split2 && waves8) {
             snprintf(ctx->slots[RT_K_EXPM].name, sizeof(ctx->slots[RT_K_EXPM].name),

@@ -1667,8 +1667,16 @@ bool rt_jit_fold_enabled()
     return v && atoi(v) != 0;
 }
 
+// multi (rt_step_multi, one launch for all rate sets): the kernels take the rate set from
+// blockIdx.y and add that set's strides to the table and output pointers in their prologue
+// (wave-uniform scalar adds); without it the text is what it was.  The strides follow the
+// family's arguments, the same six for every form (doubles / ints; unused ones are ignored).
+static const char *MULTI_PARAMS =
+    ",\n             long ms_table, long ms_site, long ms_partial, long ms_half, long ms_count,"
+    " long ms_pcol";
+
 std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, int n, int K, int T,
-                                               int D, int LA, bool halves, int sparse)
+                                               int D, int LA, bool halves, int sparse, bool multi)
 {
     (void)LA;
     const bool fold = halves && !sparse && rt_jit_fold_enabled();
@@ -1777,7 +1785,19 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
       << (halves ? ", double *__restrict__ halfbuf" : "")
       << (fold ? ", int *__restrict__ counters" : "")
       << (sparse ? ", const unsigned *__restrict__ leafw, const double *__restrict__ Pesd" : "")
+      << (multi ? MULTI_PARAMS : "")
       << ")\n{\n";
+    if (multi) {
+        o << "    // ---- rate set of this workgroup: its tables and its output slices\n"
+             "    const long rset = (long)blockIdx.y;\n"
+             "    Pfrag += rset * ms_table;\n"
+             "    loglik += rset * ms_site;\n"
+             "    status += rset * ms_site;\n"
+             "    partial += rset * ms_partial;\n";
+        if (halves) o << "    halfbuf += rset * ms_half;\n";
+        if (fold) o << "    counters += rset * ms_count;\n";
+        if (sparse) o << "    Pesd += rset * ms_pcol;\n";
+    }
     // two OBJECTS, not one array of two: step i reads xb<i & 1> while x of step i + 1 is
     // written to the other one, and only for distinct objects does the compiler know that
     // an LDS read may be hoisted above an earlier LDS write (with one array every read of
@@ -2234,7 +2254,14 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
              "rt_jit_combine(const double *__restrict__ halfbuf, const rt_d2 *__restrict__ obs,\n"
              "               const double *__restrict__ root_w, double *__restrict__ loglik,\n"
              "               int *__restrict__ status, double *__restrict__ partial,\n"
-             "               long nsites, long nblocks)\n{\n";
+             "               long nsites, long nblocks"
+          << (multi ? MULTI_PARAMS : "") << ")\n{\n";
+        if (multi)
+            o << "    const long rset = (long)blockIdx.y;\n"
+                 "    halfbuf += rset * ms_half;\n"
+                 "    loglik += rset * ms_site;\n"
+                 "    status += rset * ms_site;\n"
+                 "    partial += rset * ms_partial;\n";
         o << "    __shared__ double red[1][" << NT << "][16];\n";
         o << "    const int lane = threadIdx.x & 63;\n";
         o << "    const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);\n";
@@ -2688,16 +2715,29 @@ void rt_jit_release(const rt_ctx *ctx)
     }
 }
 
-int rt_launch_prune_jit(rt_model *m, rt_sites *s, const rt_fuse_args *fuse)
+int rt_launch_prune_jit(rt_model *m, rt_sites *s, const rt_fuse_args *fuse, const rt_prune_view *view)
 {
+    // the model's tables and the batch's outputs unless the caller brought others
+    rt_prune_view v;
+    if (view) {
+        v = *view;
+    } else {
+        v.P = m->d_P;
+        v.Pfrag = m->d_Pfrag;
+        v.Pquad = m->d_Pquad;
+        v.Pcol = m->d_Pcol;
+        v.loglik = s->d_loglik;
+        v.status = s->d_status;
+        v.partial = s->d_partial;
+    }
     if (s->jit_fused && s->layout == RT_LAYOUT_LANE) {
         // lane kernel with the fused prologue: the same kernel runs a plain pruning launch
         // (fq == nullptr: it copies the resident P table) and a whole step
         static const rt_fuse_args none;
         const rt_fuse_args &f = fuse ? *fuse : none;
-        const double *Pord = m->d_Pfrag, *obs = s->d_obs, *root_w = m->d_root;
-        double *loglik = s->d_loglik, *partial = s->d_partial;
-        int *status = s->d_status;
+        const double *Pord = v.Pfrag, *obs = s->d_obs, *root_w = m->d_root;
+        double *loglik = v.loglik, *partial = v.partial;
+        int *status = v.status;
         long nsites = (long)s->nsites, nblocks = (long)s->nblocks;
         const double *fq = f.expm ? m->d_Q : nullptr, *ftt = m->d_t_step;
         const int *fqidx = m->d_qidx_step;
@@ -2720,19 +2760,19 @@ int rt_launch_prune_jit(rt_model *m, rt_sites *s, const rt_fuse_args *fuse)
                                          m->ctx->stream, args, nullptr));
         return RT_OK;
     }
-    const double *Pord = s->jit_quad ? m->d_Pquad : m->d_Pfrag;
+    const double *Pord = s->jit_quad ? v.Pquad : v.Pfrag;
     const double *obs = s->d_obs;
     const double *root_w = m->d_root;
-    double *loglik = s->d_loglik;
-    int *status = s->d_status;
-    double *partial = s->d_partial;
+    double *loglik = v.loglik;
+    int *status = v.status;
+    double *partial = v.partial;
     long nsites = (long)s->nsites;
     long nblocks = (long)s->nblocks;
     long tile0 = 0, stride1 = 1;     // declared by the one-wave MFMA family only
     // the column-gathering split-M kernels declare the leaf-state words and the transition
     // matrices in the reference's order in those two places
     const unsigned *leafw = s->d_leafw;
-    const double *Pesd = (s->jit_sparse && !(m->n <= 32 && s->mfma_solo) && m->d_Pcol) ? m->d_Pcol : m->d_P;
+    const double *Pesd = (s->jit_sparse && !(m->n <= 32 && s->mfma_solo) && m->d_Pcol) ? v.Pcol : v.P;
     void *args_dense[] = {&Pord, &obs, &root_w, &loglik, &status, &partial, &nsites, &nblocks, &tile0,
                           &stride1};
     void *args_sparse[] = {&Pord, &obs, &root_w, &loglik, &status, &partial, &nsites, &nblocks, &leafw,
@@ -2835,5 +2875,57 @@ int rt_launch_prune_jit(rt_model *m, rt_sites *s, const rt_fuse_args *fuse)
     else
         RT_HIP(hipModuleLaunchKernel((hipFunction_t)s->jit_fn, groups, 1, 1, 64 * wg, 1, 1, 0,
                                      m->ctx->stream, args, nullptr));
+    return RT_OK;
+}
+
+// The split-M family's multi form (rt_jit_mfma_split_pipelined_source, multi): the launches of
+// rt_launch_prune_jit for that family with the rate sets along y; x runs fastest, so one set's
+// workgroups are dispatched together and its tables stay in L2.
+int rt_launch_prune_jit_multi(rt_model *m, rt_sites *s, const rt_multi_launch &a)
+{
+    const double *Pord = a.Pfrag, *obs = s->d_obs, *root_w = m->d_root;
+    double *loglik = a.loglik, *partial = a.partial;
+    int *status = a.status;
+    long nsites = (long)s->nsites, nblocks = (long)s->nblocks;
+    const unsigned *leafw = s->d_leafw;
+    const double *Pesd = a.Pcol;
+    double *half = a.half;
+    const double *chalf = a.half;
+    int *counters = a.counters;
+    long st = a.s_table, ss = a.s_site, sp = a.s_partial, sh = a.s_half, sc = a.s_count, spc = a.s_pcol;
+    std::vector<void *> args = {&Pord, &obs, &root_w, &loglik, &status, &partial, &nsites, &nblocks};
+    if (s->jit_halves) args.push_back(&half);
+    if (s->jit_halves && s->jit_fold) args.push_back(&counters);
+    if (s->jit_sparse) {
+        args.push_back(&leafw);
+        args.push_back(&Pesd);
+    }
+    void *strides[] = {&st, &ss, &sp, &sh, &sc, &spc};
+    args.insert(args.end(), strides, strides + 6);
+    std::vector<void *> cargs = {&chalf, &obs, &root_w, &loglik, &status, &partial, &nsites, &nblocks};
+    cargs.insert(cargs.end(), strides, strides + 6);
+    const unsigned tpb = 64u * (unsigned)s->jit_waves;
+    const unsigned K = (unsigned)a.K;
+    const unsigned groups = (unsigned)((s->nblocks + s->jit_tiles - 1) / s->jit_tiles) *
+                            (s->jit_halves ? 2u : 1u);
+    if (m->ctx->ev_start)
+        RT_HIP(hipExtModuleLaunchKernel((hipFunction_t)s->multi_fn, groups * tpb, K, 1, tpb, 1, 1, 0,
+                                        m->ctx->stream, args.data(), nullptr, m->ctx->ev_start,
+                                        m->ctx->ev_stop, 0));
+    else
+        RT_HIP(hipModuleLaunchKernel((hipFunction_t)s->multi_fn, groups, K, 1, tpb, 1, 1, 0,
+                                     m->ctx->stream, args.data(), nullptr));
+    if (s->jit_halves && !s->jit_fold) {
+        hipEvent_t ca = nullptr, cb = nullptr;
+        if (m->ctx->ev_start) rt_time_extra_begin(m->ctx, RT_K_COMBINE, "rt_jit_combine,multi", &ca, &cb);
+        const unsigned tiles = (unsigned)s->nblocks;
+        if (ca)
+            RT_HIP(hipExtModuleLaunchKernel((hipFunction_t)s->multi_combine, tiles * tpb, K, 1, tpb, 1, 1,
+                                            0, m->ctx->stream, cargs.data(), nullptr, ca, cb, 0));
+        else
+            RT_HIP(hipModuleLaunchKernel((hipFunction_t)s->multi_combine, tiles, K, 1, tpb, 1, 1, 0,
+                                         m->ctx->stream, cargs.data(), nullptr));
+        rt_time_extra_end(m->ctx, RT_K_COMBINE, ca, cb);
+    }
     return RT_OK;
 }

@@ -1544,10 +1544,13 @@ static int nt_of(int64_t n) { return (int)((n + 15) / 16); }
 // step of the 61-state model).
 __global__ void __launch_bounds__(256)
 pack_pcol_kernel(const double *__restrict__ P, const rt_op *__restrict__ ops, int nops, int n,
-                 int NT, double *__restrict__ out)
+                 int NT, double *__restrict__ out, long P_set_stride = 0, long out_set_stride = 0)
 {
     __shared__ double tile[128][33];
     const int i = blockIdx.x;
+    // (rate sets, rt_model_set_rate_sets: one table per blockIdx.y)
+    P += blockIdx.y * P_set_stride;
+    out += blockIdx.y * out_set_stride;
     const rt_op op = ops[i];
     if (op.pop >= 0 || op.dst < 0) return;      // only the leaves' records are ever read
     const int RN = 16 * NT;
@@ -1583,7 +1586,18 @@ int rt_model_pack_pcol(rt_model *m)
     if (!m->d_Pcol || m->n <= 4) return RT_OK;
     hipLaunchKernelGGL(pack_pcol_kernel, dim3((unsigned)m->ops.size()), dim3(256), 0, m->ctx->stream,
                        m->d_P, m->d_ops, (int)m->ops.size(), (int)m->n, (int)((m->n + 15) / 16),
-                       m->d_Pcol);
+                       m->d_Pcol, 0l, 0l);
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+int rt_pack_pcol_sets(rt_model *m, int64_t sets, const double *d_P, int64_t P_stride, double *d_Pcol,
+                      int64_t pcol_stride)
+{
+    if (!d_Pcol || m->n <= 4 || sets <= 0) return RT_OK;
+    hipLaunchKernelGGL(pack_pcol_kernel, dim3((unsigned)m->ops.size(), (unsigned)sets), dim3(256), 0,
+                       m->ctx->stream, d_P, m->d_ops, (int)m->ops.size(), (int)m->n,
+                       (int)((m->n + 15) / 16), d_Pcol, (long)P_stride, (long)pcol_stride);
     RT_HIP(hipGetLastError());
     return RT_OK;
 }
@@ -1699,7 +1713,7 @@ int rt_sites_pack(rt_sites *s, int kind, const int64_t *src_of_k, const void *da
 }
 
 template <int N, int R, bool RESC = false>
-static int launch_lane_reg(rt_model *m, rt_sites *s, bool *plds_out)
+static int launch_lane_reg(rt_model *m, rt_sites *s, const rt_prune_view &v, bool *plds_out)
 {
     // the deepest accumulator never leaves the register cache
     const int depth = std::max(1, m->max_depth - 1);
@@ -1716,17 +1730,17 @@ static int launch_lane_reg(rt_model *m, rt_sites *s, bool *plds_out)
         RT_HIP(hipFuncSetAttribute((const void *)kern,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         RT_LAUNCH_TIMED(m->ctx, kern, dim3((unsigned)((s->nblocks + 3) / 4)), dim3(256), lds,
-                           m->d_Pfrag, (const int4_t *)s->d_lane_ops, nops,
-                           s->d_obs, (int)s->nobs, m->d_root, depth_arg, s->d_loglik,
-                           s->d_status, s->d_partial, (long)s->nsites, (long)s->nblocks);
+                           v.Pfrag, (const int4_t *)s->d_lane_ops, nops,
+                           s->d_obs, (int)s->nobs, m->d_root, depth_arg, v.loglik,
+                           v.status, v.partial, (long)s->nsites, (long)s->nblocks);
     } else {
         auto kern = prune_lane_kernel<N, R, false, RESC>;
         RT_HIP(hipFuncSetAttribute((const void *)kern,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, stack));
         RT_LAUNCH_TIMED(m->ctx, kern, dim3((unsigned)s->nblocks), dim3(64), stack,
-                           m->d_Pfrag, (const int4_t *)s->d_lane_ops, nops,
-                           s->d_obs, (int)s->nobs, m->d_root, depth, s->d_loglik,
-                           s->d_status, s->d_partial, (long)s->nsites, (long)s->nblocks);
+                           v.Pfrag, (const int4_t *)s->d_lane_ops, nops,
+                           s->d_obs, (int)s->nobs, m->d_root, depth, v.loglik,
+                           v.status, v.partial, (long)s->nsites, (long)s->nblocks);
     }
     return RT_OK;
 }
@@ -1739,7 +1753,7 @@ static int lane_dma_lds(int n, int R, int B, int wpb, int nrec, int slots)
 }
 
 template <int N, int R, int B, int WPB>
-static int launch_lane_dma(rt_model *m, rt_sites *s)
+static int launch_lane_dma(rt_model *m, rt_sites *s, const rt_prune_view &v)
 {
     const int depth = s->lane_stack_slots;
     const int nrec = (int)s->ops.size();          // P records = schedule steps
@@ -1756,14 +1770,14 @@ static int launch_lane_dma(rt_model *m, rt_sites *s)
     RT_HIP(hipFuncSetAttribute((const void *)kern,
                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     RT_LAUNCH_TIMED(m->ctx, kern, dim3((unsigned)((nwaves + WPB - 1) / WPB)), dim3(64 * WPB), lds,
-                       m->d_Pfrag, (const int4_t *)s->d_lane_ops, nops, nrec,
-                       s->d_obs, (int)s->nobs, m->d_root, depth, s->d_loglik, s->d_status,
-                       s->d_partial, (long)s->nsites, nwaves);
+                       v.Pfrag, (const int4_t *)s->d_lane_ops, nops, nrec,
+                       s->d_obs, (int)s->nobs, m->d_root, depth, v.loglik, v.status,
+                       v.partial, (long)s->nsites, nwaves);
     return RT_OK;
 }
 
 template <int N>
-static int launch_lane(rt_model *m, rt_sites *s, const char **name)
+static int launch_lane(rt_model *m, rt_sites *s, const rt_prune_view &v, const char **name)
 {
     int R = s->lane_ring;
     int B = 1, W = 4;
@@ -1786,9 +1800,9 @@ static int launch_lane(rt_model *m, rt_sites *s, const char **name)
     }
     if (s->lane_dma) {
 #define RT_DMA_CASE(r) \
-        rc = B == 2 ? (W == 2 ? launch_lane_dma<N, r, 2, 2>(m, s)               \
-                              : launch_lane_dma<N, r, 2, 4>(m, s))              \
-                    : launch_lane_dma<N, r, 1, 4>(m, s)
+        rc = B == 2 ? (W == 2 ? launch_lane_dma<N, r, 2, 2>(m, s, v)               \
+                              : launch_lane_dma<N, r, 2, 4>(m, s, v))              \
+                    : launch_lane_dma<N, r, 1, 4>(m, s, v)
         switch (R) {
         case 2: RT_DMA_CASE(2); break;
         case 4: RT_DMA_CASE(4); break;
@@ -1797,13 +1811,13 @@ static int launch_lane(rt_model *m, rt_sites *s, const char **name)
 #undef RT_DMA_CASE
     } else if (s->rescale) {
         R = 8;
-        rc = launch_lane_reg<N, 8, true>(m, s, &plds);
+        rc = launch_lane_reg<N, 8, true>(m, s, v, &plds);
     } else {
         switch (R) {
-        case 4: rc = launch_lane_reg<N, 4>(m, s, &plds); break;
-        case 6: rc = launch_lane_reg<N, 6>(m, s, &plds); break;
-        case 12: rc = launch_lane_reg<N, 12>(m, s, &plds); break;
-        default: rc = launch_lane_reg<N, 8>(m, s, &plds); break;
+        case 4: rc = launch_lane_reg<N, 4>(m, s, v, &plds); break;
+        case 6: rc = launch_lane_reg<N, 6>(m, s, v, &plds); break;
+        case 12: rc = launch_lane_reg<N, 12>(m, s, v, &plds); break;
+        default: rc = launch_lane_reg<N, 8>(m, s, v, &plds); break;
         }
     }
     if (s->lane_dma)
@@ -1816,7 +1830,7 @@ static int launch_lane(rt_model *m, rt_sites *s, const char **name)
 }
 
 template <int NT, int KS>
-static int launch_mfma_inst(rt_model *m, rt_sites *s)
+static int launch_mfma_inst(rt_model *m, rt_sites *s, const rt_prune_view &v)
 {
     const int lds_slots = std::max(1, s->lane_stack_slots);
     if (s->mfma_solo) {
@@ -1826,10 +1840,10 @@ static int launch_mfma_inst(rt_model *m, rt_sites *s)
             auto kern = prune_mfma_solo_kernel<NT, KS>;
             RT_HIP(hipFuncSetAttribute((const void *)kern,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            RT_LAUNCH_TIMED(m->ctx, kern, dim3(grid), dim3(256), lds, m->d_Pfrag,
+            RT_LAUNCH_TIMED(m->ctx, kern, dim3(grid), dim3(256), lds, v.Pfrag,
                                (const int4_t *)s->d_lane_ops, (int)s->ops.size(), s->d_obs,
-                               (int)s->nobs, m->d_root, (int)m->n, lds_slots, s->d_loglik,
-                               s->d_status, s->d_partial, (long)s->nsites, (long)s->nblocks,
+                               (int)s->nobs, m->d_root, (int)m->n, lds_slots, v.loglik,
+                               v.status, v.partial, (long)s->nsites, (long)s->nblocks,
                                (int)s->rescale);
             return RT_OK;
         }
@@ -1849,7 +1863,7 @@ static int launch_mfma_inst(rt_model *m, rt_sites *s)
     RT_HIP(hipFuncSetAttribute((const void *)kern,
                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     const unsigned *ilw = isp ? s->d_leafw : nullptr;
-    const double *ipc = isp ? m->d_Pcol : nullptr;
+    const double *ipc = isp ? v.Pcol : nullptr;
     const int ism = isp ? (s->sparse_pairs ? 2 : 1) : 0;
     rt_interp_halves hv;
     if (s->interp_halves && !s->d_Lout) {
@@ -1861,9 +1875,9 @@ static int launch_mfma_inst(rt_model *m, rt_sites *s)
         hv.kobs1 = s->half_kobs1;
         hv.halfbuf = s->d_half;
         RT_LAUNCH_TIMED(m->ctx, kern, dim3(2 * grid), dim3(WAVES * 64), lds,
-                           m->d_Pfrag, (const int4_t *)s->d_lane_ops_a, hv.nops0,
+                           v.Pfrag, (const int4_t *)s->d_lane_ops_a, hv.nops0,
                            s->d_obs, (int)s->nobs, m->d_root, (int)m->n, lds_slots,
-                           s->d_loglik, s->d_status, s->d_partial, (long)s->nsites,
+                           v.loglik, v.status, v.partial, (long)s->nsites,
                            (long)s->nblocks, s->d_Lout, s->d_Mout, hv, 0, ilw, ipc, ism);
         hipEvent_t ca = nullptr, cb = nullptr;
         rt_time_extra_begin(m->ctx, RT_K_COMBINE, "prune_mfma_combine", &ca, &cb);
@@ -1872,27 +1886,27 @@ static int launch_mfma_inst(rt_model *m, rt_sites *s)
         if (ca)
             hipExtLaunchKernelGGL(ckern, dim3(grid), dim3(WAVES * 64), 0, m->ctx->stream, ca, cb, 0,
                                   chalf, (const double *)s->d_obs, (int)s->nobs, (KS + 1) / 2,
-                                  s->half_kroot, (const double *)m->d_root, (int)m->n, s->d_loglik,
-                                  s->d_status, s->d_partial, (long)s->nsites, (long)s->nblocks);
+                                  s->half_kroot, (const double *)m->d_root, (int)m->n, v.loglik,
+                                  v.status, v.partial, (long)s->nsites, (long)s->nblocks);
         else
             hipLaunchKernelGGL(ckern, dim3(grid), dim3(WAVES * 64), 0, m->ctx->stream,
                                chalf, (const double *)s->d_obs, (int)s->nobs, (KS + 1) / 2,
-                               s->half_kroot, (const double *)m->d_root, (int)m->n, s->d_loglik,
-                               s->d_status, s->d_partial, (long)s->nsites, (long)s->nblocks);
+                               s->half_kroot, (const double *)m->d_root, (int)m->n, v.loglik,
+                               v.status, v.partial, (long)s->nsites, (long)s->nblocks);
         rt_time_extra_end(m->ctx, RT_K_COMBINE, ca, cb);
         return RT_OK;
     }
     RT_LAUNCH_TIMED(m->ctx, kern, dim3(grid), dim3(WAVES * 64), lds,
-                       m->d_Pfrag, (const int4_t *)s->d_lane_ops, (int)s->ops.size(),
+                       v.Pfrag, (const int4_t *)s->d_lane_ops, (int)s->ops.size(),
                        s->d_obs, (int)s->nobs, m->d_root, (int)m->n, lds_slots,
-                       s->d_loglik, s->d_status, s->d_partial, (long)s->nsites,
+                       v.loglik, v.status, v.partial, (long)s->nsites,
                        (long)s->nblocks, s->d_Lout, s->d_Mout, hv,
                        (int)(s->rescale && !s->d_Lout),      // L and M are stored unscaled
                        ilw, ipc, ism);
     return RT_OK;
 }
 
-static int launch_mfma(rt_model *m, rt_sites *s, const char **name)
+static int launch_mfma(rt_model *m, rt_sites *s, const rt_prune_view &v, const char **name)
 {
     const int ks = ks_of(m->n);
     snprintf(s->kernel_name, sizeof(s->kernel_name), "prune_mfma%s<%d,%d%s%s>",
@@ -1903,45 +1917,45 @@ static int launch_mfma(rt_model *m, rt_sites *s, const char **name)
                 !getenv("RAOTEH_INTERP_NO_SPARSE")) ? ",leaf-states" : "");
     *name = s->kernel_name;
     switch (ks) {
-    case 2: return launch_mfma_inst<1, 2>(m, s);
-    case 3: return launch_mfma_inst<1, 3>(m, s);
-    case 4: return launch_mfma_inst<1, 4>(m, s);
-    case 5: return launch_mfma_inst<2, 5>(m, s);
-    case 6: return launch_mfma_inst<2, 6>(m, s);
-    case 7: return launch_mfma_inst<2, 7>(m, s);
-    case 8: return launch_mfma_inst<2, 8>(m, s);
-    case 9: return launch_mfma_inst<3, 9>(m, s);
-    case 10: return launch_mfma_inst<3, 10>(m, s);
-    case 11: return launch_mfma_inst<3, 11>(m, s);
-    case 12: return launch_mfma_inst<3, 12>(m, s);
-    case 13: return launch_mfma_inst<4, 13>(m, s);
-    case 14: return launch_mfma_inst<4, 14>(m, s);
-    case 15: return launch_mfma_inst<4, 15>(m, s);
-    case 16: return launch_mfma_inst<4, 16>(m, s);
+    case 2: return launch_mfma_inst<1, 2>(m, s, v);
+    case 3: return launch_mfma_inst<1, 3>(m, s, v);
+    case 4: return launch_mfma_inst<1, 4>(m, s, v);
+    case 5: return launch_mfma_inst<2, 5>(m, s, v);
+    case 6: return launch_mfma_inst<2, 6>(m, s, v);
+    case 7: return launch_mfma_inst<2, 7>(m, s, v);
+    case 8: return launch_mfma_inst<2, 8>(m, s, v);
+    case 9: return launch_mfma_inst<3, 9>(m, s, v);
+    case 10: return launch_mfma_inst<3, 10>(m, s, v);
+    case 11: return launch_mfma_inst<3, 11>(m, s, v);
+    case 12: return launch_mfma_inst<3, 12>(m, s, v);
+    case 13: return launch_mfma_inst<4, 13>(m, s, v);
+    case 14: return launch_mfma_inst<4, 14>(m, s, v);
+    case 15: return launch_mfma_inst<4, 15>(m, s, v);
+    case 16: return launch_mfma_inst<4, 16>(m, s, v);
     // 64 < n <= 128: one tile of NT = 5..8 waves per workgroup
-    case 17: return launch_mfma_inst<5, 17>(m, s);
-    case 18: return launch_mfma_inst<5, 18>(m, s);
-    case 19: return launch_mfma_inst<5, 19>(m, s);
-    case 20: return launch_mfma_inst<5, 20>(m, s);
-    case 21: return launch_mfma_inst<6, 21>(m, s);
-    case 22: return launch_mfma_inst<6, 22>(m, s);
-    case 23: return launch_mfma_inst<6, 23>(m, s);
-    case 24: return launch_mfma_inst<6, 24>(m, s);
-    case 25: return launch_mfma_inst<7, 25>(m, s);
-    case 26: return launch_mfma_inst<7, 26>(m, s);
-    case 27: return launch_mfma_inst<7, 27>(m, s);
-    case 28: return launch_mfma_inst<7, 28>(m, s);
-    case 29: return launch_mfma_inst<8, 29>(m, s);
-    case 30: return launch_mfma_inst<8, 30>(m, s);
-    case 31: return launch_mfma_inst<8, 31>(m, s);
-    case 32: return launch_mfma_inst<8, 32>(m, s);
+    case 17: return launch_mfma_inst<5, 17>(m, s, v);
+    case 18: return launch_mfma_inst<5, 18>(m, s, v);
+    case 19: return launch_mfma_inst<5, 19>(m, s, v);
+    case 20: return launch_mfma_inst<5, 20>(m, s, v);
+    case 21: return launch_mfma_inst<6, 21>(m, s, v);
+    case 22: return launch_mfma_inst<6, 22>(m, s, v);
+    case 23: return launch_mfma_inst<6, 23>(m, s, v);
+    case 24: return launch_mfma_inst<6, 24>(m, s, v);
+    case 25: return launch_mfma_inst<7, 25>(m, s, v);
+    case 26: return launch_mfma_inst<7, 26>(m, s, v);
+    case 27: return launch_mfma_inst<7, 27>(m, s, v);
+    case 28: return launch_mfma_inst<7, 28>(m, s, v);
+    case 29: return launch_mfma_inst<8, 29>(m, s, v);
+    case 30: return launch_mfma_inst<8, 30>(m, s, v);
+    case 31: return launch_mfma_inst<8, 31>(m, s, v);
+    case 32: return launch_mfma_inst<8, 32>(m, s, v);
     default: break;
     }
     rt_set_error("no MFMA pruning kernel for n=%lld", (long long)m->n);
     return RT_ERR_UNSUPPORTED;
 }
 
-static int launch_generic(rt_model *m, rt_sites *s, const char **name)
+static int launch_generic(rt_model *m, rt_sites *s, const rt_prune_view &v, const char **name)
 {
     const int n = (int)m->n;
     const int np = (n + 1) & ~1;
@@ -1949,9 +1963,9 @@ static int launch_generic(rt_model *m, rt_sites *s, const char **name)
     const unsigned grid = (unsigned)s->nblocks;
 #define RT_GEN(NMAX)                                                               \
     RT_LAUNCH_TIMED(m->ctx, prune_generic_kernel<NMAX>, dim3(grid), dim3(64), 0,    \
-                       m->d_P, s->d_ops, (int)s->ops.size(), s->d_obs,             \
-                       (int)s->nobs, n, np, m->d_root, s->d_loglik, s->d_status,   \
-                       s->d_partial, s->d_scratch, nsp, (long)s->nsites, (int)s->rescale)
+                       v.P, s->d_ops, (int)s->ops.size(), s->d_obs,             \
+                       (int)s->nobs, n, np, m->d_root, v.loglik, v.status,   \
+                       v.partial, s->d_scratch, nsp, (long)s->nsites, (int)s->rescale)
     if (n <= 8) { *name = "prune_generic<8>"; RT_GEN(8); }
     else if (n <= 16) { *name = "prune_generic<16>"; RT_GEN(16); }
     else if (n <= 32) { *name = "prune_generic<32>"; RT_GEN(32); }
@@ -2004,12 +2018,26 @@ int rt_flush_reduce(rt_ctx *ctx)
     return RT_OK;
 }
 
-int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm)
+int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm,
+                    const rt_prune_view *view)
 {
     rt_ctx *ctx = m->ctx;
     const char *name = "";
     hipEvent_t ev = nullptr;
     rt_fuse_args fuse;
+    // the model's tables and the batch's outputs unless the caller brought others
+    rt_prune_view v;
+    if (view) {
+        v = *view;
+        fuse_expm = false;
+    } else {
+        v.P = m->d_P;
+        v.Pfrag = m->d_Pfrag;
+        v.Pquad = m->d_Pquad;
+        v.Pcol = m->d_Pcol;
+        v.loglik = s->d_loglik;
+        v.status = s->d_status;
+    }
     if (fuse_expm && s->jit_fused && s->jit_fn) {
         // one launch: transitions from the resident rates in the kernel's prologue, the pending
         // reduction (of whichever batch) in an extra workgroup.  That reduction reads the
@@ -2028,13 +2056,14 @@ int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm)
     }
     // which family this batch was packed for
     const bool generic = s->d_scratch != nullptr;
-    if (!generic && !fuse_expm) RT_TRY(rt_launch_pfrag(m));
+    if (!generic && !fuse_expm && !view) RT_TRY(rt_launch_pfrag(m));
+    if (!view) v.partial = s->d_partial;        // (after the swap of a fused launch)
     rt_time_begin(ctx, RT_K_PRUNE, "", &ev);
     int rc;
     char *jit_name = s->kernel_name;
-    if (generic) rc = launch_generic(m, s, &name);
+    if (generic) rc = launch_generic(m, s, v, &name);
     else if (s->jit_fn) {
-        rc = rt_launch_prune_jit(m, s, s->jit_fused ? &fuse : nullptr);
+        rc = rt_launch_prune_jit(m, s, s->jit_fused ? &fuse : nullptr, &v);
         if (s->layout == RT_LAYOUT_LANE)
             snprintf(jit_name, sizeof(s->kernel_name), "prune_tree_jit<%d,D%d%s%s>", (int)m->n,
                      s->jit_prefetch, s->compact_states == 1 ? ",states"
@@ -2053,18 +2082,19 @@ int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm)
         name = jit_name;
     } else if (s->layout == RT_LAYOUT_LANE) {
         switch ((int)m->n) {
-        case 1: rc = launch_lane<1>(m, s, &name); break;
-        case 2: rc = launch_lane<2>(m, s, &name); break;
-        case 3: rc = launch_lane<3>(m, s, &name); break;
-        default: rc = launch_lane<4>(m, s, &name); break;
+        case 1: rc = launch_lane<1>(m, s, v, &name); break;
+        case 2: rc = launch_lane<2>(m, s, v, &name); break;
+        case 3: rc = launch_lane<3>(m, s, v, &name); break;
+        default: rc = launch_lane<4>(m, s, v, &name); break;
         }
-    } else rc = launch_mfma(m, s, &name);
+    } else rc = launch_mfma(m, s, v, &name);
     if (rc != RT_OK) return rc;
     RT_HIP(hipGetLastError());
-    s->pruned = true;
+    if (!view) s->pruned = true;
     snprintf(ctx->slots[RT_K_PRUNE].name, sizeof(ctx->slots[RT_K_PRUNE].name), "%s", name);
     if (name != s->kernel_name) snprintf(s->kernel_name, sizeof(s->kernel_name), "%s", name);
     rt_time_end(ctx, RT_K_PRUNE, ev);
+    if (view) return RT_OK;          // (the caller reduces its own partial sums)
 
     ctx->pending_reduce = s;
     // deferred (rt_step): the reduction rides on the next expm launch of this context

@@ -24,7 +24,7 @@ import numpy as np
 from . import _lib
 from ._tree import TreeArrays
 
-__all__ = ['Context', 'get_context', 'TreeModel', 'SiteBatch', 'device_count', 'Posteriors',
+__all__ = ['check_rate_sets', 'Context', 'get_context', 'TreeModel', 'SiteBatch', 'device_count', 'Posteriors',
            'states_to_mask', 'BranchExpectations', 'check_branch_coefs']
 
 # At interpreter shutdown objects are finalised in arbitrary order (a model
@@ -114,6 +114,49 @@ def check_branch_coefs(coefs, nstates):
     if not np.isfinite(E).all():
         raise ValueError('the coefficients must be finite')
     return np.ascontiguousarray(E)
+
+
+def check_rate_sets(Q, t, node_q, nstates, nnodes):
+    """The arguments of TreeModel.set_rate_sets -> (Q f64[K, nq, n, n], t f64[K, nnodes],
+    node_q int64[nnodes] or None).  Q is [K, n, n] or [K, nq, n, n]; t is [K, nnodes], or
+    [nnodes] (broadcast to every set).  ValueError for another shape, no set or more than
+    RT_MAX_RATE_SETS of them, several matrices per set without a node_q, or a node_q that is
+    not one index in [0, nq) per node."""
+    Q = np.asarray(Q, dtype=np.float64)
+    if Q.ndim == 3:
+        Q = Q[:, None]
+    if Q.ndim != 4 or Q.shape[2:] != (nstates, nstates) or Q.shape[1] < 1:
+        raise ValueError('Q must be [K, %d, %d] or [K, nq, %d, %d], not %s'
+                         % (nstates, nstates, nstates, nstates, Q.shape))
+    K, nq = Q.shape[:2]
+    if not 1 <= K <= _lib.RT_MAX_RATE_SETS:
+        raise ValueError('between 1 and %d rate sets per call (%d here)'
+                         % (_lib.RT_MAX_RATE_SETS, K))
+    t = np.asarray(t, dtype=np.float64)
+    if t.shape == (nnodes,):
+        t = np.broadcast_to(t, (K, nnodes))
+    if t.shape != (K, nnodes):
+        raise ValueError('t must be [%d, %d] or [%d], not %s' % (K, nnodes, nnodes, t.shape))
+    if node_q is None:
+        if nq != 1:
+            raise ValueError('%d rate matrices per set need a node_q' % nq)
+    else:
+        node_q = np.ascontiguousarray(node_q, dtype=np.int64)
+        if node_q.shape != (nnodes,):
+            raise ValueError('node_q must have one entry per node')
+        if ((node_q[1:] < 0) | (node_q[1:] >= nq)).any():
+            raise ValueError('node_q out of range')
+    return np.ascontiguousarray(Q), np.ascontiguousarray(t), node_q
+
+
+def check_class_weights(class_weights, nsets):
+    """f64[K] mixture weights: finite, >= 0, not all zero (ValueError otherwise)."""
+    c = np.ascontiguousarray(class_weights, dtype=np.float64)
+    if c.shape != (nsets,):
+        raise ValueError('one class weight per rate set expected (%d), not %s' % (nsets, c.shape))
+    if not np.isfinite(c).all() or (c < 0).any() or not (c > 0).any():
+        raise ValueError('the class weights must be finite, >= 0 and not all zero')
+    return c
 
 
 def _mask_states(mask, nstates):
@@ -465,6 +508,12 @@ class SiteBatch(object):
     def kernel_name(self):
         return (_lib.lib().rt_sites_kernel_name(self._h) or b'').decode()
 
+    @property
+    def multi_kernel_name(self):
+        """The batch's kernel of the last step_multi plus ',loop' (one launch per rate set) or
+        ',multi' (one launch for all sets); '' before the first step_multi."""
+        return (_lib.lib().rt_sites_multi_kernel_name(self._h) or b'').decode()
+
     def set_weights(self, weights=None):
         """Per-site multiplicities for expected_history_statistics (site patterns);
         None = every site counts once."""
@@ -672,6 +721,56 @@ class TreeModel(object):
         per-edge expm from the resident rates (optional) + prune; asynchronous."""
         _lib.check(_lib.lib().rt_step(self._h, batch._h,
                                       1 if recompute_transitions else 0))
+
+    def set_rate_sets(self, Q, t=None, node_q=None):
+        """K rate sets next to the rates set_rates owns (rt_model_set_rate_sets): Q [K, n, n]
+        or [K, nq, n, n] with node_q [nnodes] shared by all sets, t [K, nnodes], or [nnodes] /
+        None (the tree's branch lengths) for every set.  expm(Q t) of every edge of every set
+        in one launch; the model's own transitions do not change."""
+        if t is None:
+            t = self.tree.branch_lengths()
+        Q, t, node_q = check_rate_sets(Q, t, node_q, self.nstates, self.tree.nnodes)
+        _lib.check(_lib.lib().rt_model_set_rate_sets(
+            self._h, Q.shape[0], _ptr(Q, c_double), Q.shape[1],
+            None if node_q is None else _ptr(node_q, c_int64), _ptr(t, c_double)))
+        self._nsets = Q.shape[0]
+
+    def step_multi(self, batch, recompute_transitions=True):
+        """rt_step_multi: (the exponentials of every rate set again +) one pruning of the batch
+        per rate set + K batch sums; asynchronous.  The batch's own results stay."""
+        _lib.check(_lib.lib().rt_step_multi(self._h, batch._h,
+                                            1 if recompute_transitions else 0))
+
+    def fetch_multi_log_likelihoods(self, batch):
+        """(loglik f64[K, nsites], status int32[K, nsites]) of the last step_multi."""
+        K = getattr(self, '_nsets', 0)
+        ll = np.empty((max(K, 1), batch.nsites), dtype=np.float64)
+        st = np.empty((max(K, 1), batch.nsites), dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_get_multi_logliks(
+            batch._h, _ptr(ll, c_double), _ptr(st, c_int32)))
+        return ll, st
+
+    def fetch_multi_totals(self, batch, weighted=False):
+        """totals f64[K, 3] (per set: what fetch_totals gives after a separate step with that
+        set); weighted=True: (totals, weighted_sums f64[K]) with the batch's site weights."""
+        K = getattr(self, '_nsets', 0)
+        tot = np.zeros((max(K, 1), 3), dtype=np.float64)
+        ws = np.zeros(max(K, 1), dtype=np.float64)
+        _lib.check(_lib.lib().rt_sites_get_multi_totals(
+            batch._h, _ptr(tot, c_double), _ptr(ws, c_double) if weighted else None))
+        return (tot, ws) if weighted else tot
+
+    def mixture_log_likelihoods(self, batch, class_weights):
+        """Per site log sum_k c_k exp(loglik[k]) over the rate sets of the last step_multi
+        (site-class models): (loglik f64[nsites], status int32[nsites], totals f64[3])."""
+        c = check_class_weights(class_weights, getattr(self, '_nsets', 0))
+        ll = np.empty(batch.nsites, dtype=np.float64)
+        st = np.empty(batch.nsites, dtype=np.int32)
+        tot = np.zeros(3, dtype=np.float64)
+        _lib.check(_lib.lib().rt_sites_multi_mixture(
+            batch._h, _ptr(c, c_double), _ptr(ll, c_double), _ptr(st, c_int32),
+            _ptr(tot, c_double)))
+        return ll, st, tot
 
     def expected_history_statistics(self, batch, recompute_transitions=True,
                                     return_status=False):
