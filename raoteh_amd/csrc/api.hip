@@ -1240,12 +1240,39 @@ static int sites_alloc(rt_sites *s, bool generic)
 // (the probe batches of verify_jit_kernel).
 // the split-M generator in use: pipelined unless RAOTEH_JIT_SPLIT=serial (A/B runs)
 static std::string split_source(const std::vector<rt_op> &ops, int n, int K, int T, int D, int LA,
-                                bool halves = false, bool multi = false)
+                                bool halves = false, bool multi = false, bool teams = false)
 {
     const char *v = getenv("RAOTEH_JIT_SPLIT");
     if (v && strcmp(v, "serial") == 0 && !halves && !multi)
-        return rt_jit_mfma_split_source(ops, n, K, T, D, LA);
-    return rt_jit_mfma_split_pipelined_source(ops, n, K, T, D, LA, halves, 0, multi);
+        return teams ? std::string() : rt_jit_mfma_split_source(ops, n, K, T, D, LA);
+    return rt_jit_mfma_split_pipelined_source(ops, n, K, T, D, LA, halves, 0, multi, teams);
+}
+
+// Two four-wave teams per workgroup (jit.hip): whenever a dense batch would get the pipelined
+// NT = 4 kernel at three or more tiles per workgroup -- one wave per SIMD -- the same tiles run
+// as two waves per SIMD.  RAOTEH_JIT_TEAMS=0 / 1 overrides.
+static bool want_teams(int n, int T)
+{
+    if (!rt_jit_teams_possible(n, T, 0)) return false;
+    const int forced = rt_jit_teams_env();
+    return forced < 0 ? true : forced != 0;
+}
+
+// the dense split-M candidates of a batch, preferred first: fewer tiles if one spills -- halves
+// at T, halves at one tile, then the whole tree -- and the two-team form ahead of the one-team
+// form of the same tiling
+static std::vector<rt_sites::jit_cand> split_dense_cands(int n, int T, bool halves)
+{
+    std::vector<rt_sites::jit_cand> cands;
+    for (int t = T, h = halves;;) {
+        if (want_teams(n, t)) cands.push_back({t, h != 0, false, false, false, true});
+        cands.push_back({t, h != 0, false});
+        if (h && t > 1) t = 1;
+        else if (h) h = 0;
+        else if (t > 1) --t;
+        else break;
+    }
+    return cands;
 }
 
 // Root halves (jit.hip) for a split-M batch of `ntiles` tiles at one tile per workgroup:
@@ -1288,6 +1315,7 @@ struct jit_override {
     bool no_solo = false;     // n <= 32: the split-M interpreter kernel, not the one-wave one
     bool sparse = false;      // split-M family: leaf steps gather columns of P (leaf states)
     bool pipe = false;        // ... from the pipelined generator (leaves as factors)
+    bool teams = false;       // split-M family: two four-wave teams per workgroup
 };
 
 // At most this many background compiles at a time (RAOTEH_JIT_MAX_JOBS, default 2): a caller
@@ -1355,12 +1383,13 @@ static int sites_jit(rt_sites *s, bool generic, int kind, const jit_override *ov
                                                      s->sparse_pairs ? 2 : 1)
             : split && ov->sparse ? rt_jit_mfma_split_source(s->ops, n, K, ov->T, ov->D, ov->LA,
                                                              s->sparse_pairs ? 2 : 1)
-            : split ? split_source(s->ops, n, K, ov->T, ov->D, ov->LA, ov->halves)
+            : split ? split_source(s->ops, n, K, ov->T, ov->D, ov->LA, ov->halves, false, ov->teams)
                     : rt_jit_mfma_source(s->ops, n, K, ov->T, ov->D, ov->LA, ov->quad,
                                          ov->sparse ? (s->sparse_pairs ? 2 : 1) : 0);
         RT_TRY(rt_jit_get(s->model->ctx, src, &s->jit_fn, mfma));
         s->jit_sparse = mfma && ov->sparse;
         s->jit_pipe = split && ov->sparse && ov->pipe;
+        s->jit_teams = split && !ov->sparse && ov->teams;
         if (split && ov->halves && (!ov->sparse || ov->pipe)) RT_TRY(sites_halves_setup(s));
         s->jit_quad = mfma && !split && ov->quad;
         s->jit_prefetch = ov->D;
@@ -1471,38 +1500,31 @@ static int sites_jit(rt_sites *s, bool generic, int kind, const jit_override *ov
             // fewer tiles if it spills: halves at T, halves at one tile, then the whole tree.
             // Unless the kernel is already in this context's cache, a background job works
             // through that list while the batch runs the interpreter kernel.
-            if (!forced && opt_jit_async(s->model->ctx)) {
-                std::vector<rt_sites::jit_cand> cands;
-                for (int t = T, h = halves;;) {
-                    cands.push_back({t, h != 0, false});
-                    if (h && t > 1) t = 1;
-                    else if (h) h = 0;
-                    else if (t > 1) --t;
-                    else break;
-                }
-                if (sites_jit_start_async(s, cands, [&](const rt_sites::jit_cand &c) {
-                        return split_source(s->ops, (int)s->model->n, (int)s->nobs, c.T, D, LA, c.halves);
-                    }))
-                    return RT_OK;
-            }
-            while (rc == RT_ERR_UNSUPPORTED) {
-                const std::string src =
-                    split_source(s->ops, (int)s->model->n, (int)s->nobs, T, D, LA, halves);
+            const std::vector<rt_sites::jit_cand> cands =
+                split_dense_cands((int)s->model->n, T, halves);
+            auto make = [&](const rt_sites::jit_cand &c) {
+                return split_source(s->ops, (int)s->model->n, (int)s->nobs, c.T, D, LA, c.halves, false,
+                                    c.teams);
+            };
+            if (!forced && opt_jit_async(s->model->ctx) && sites_jit_start_async(s, cands, make))
+                return RT_OK;
+            rt_sites::jit_cand got = cands.back();
+            for (const auto &c : cands) {
+                const std::string src = make(c);
+                if (src.empty()) continue;             // (this form does not exist for this tree)
                 rc = rt_jit_get(s->model->ctx, src, &s->jit_fn, true, &s->jit_compile_s);
+                got = c;
                 if (rc != RT_ERR_UNSUPPORTED) break;
-                if (halves && T > 1) T = 1;
-                else if (halves) halves = false;
-                else if (T > 1) --T;
-                else break;
             }
             if (rc != RT_OK && (!forced || rc == RT_ERR_UNSUPPORTED)) {
                 s->jit_fn = nullptr;           // the interpreter kernel runs
                 return RT_OK;
             }
             if (rc == RT_OK) {
-                s->jit_tiles = T;
+                s->jit_tiles = got.T;
                 s->jit_waves = (int)((s->model->n + 15) / 16);
-                if (halves) rc = sites_halves_setup(s);
+                s->jit_teams = got.teams;
+                if (got.halves) rc = sites_halves_setup(s);
             }
             return rc;
         }
@@ -1749,7 +1771,8 @@ extern "C" int rt_jit_source(int64_t nnodes, const int64_t *idx, const int64_t *
                   : split_source(m.ops, (int)n, (int)nobs,
                                  getenv("RAOTEH_JIT_HALVES") && atoi(getenv("RAOTEH_JIT_HALVES"))
                                      ? T : std::min(T, 3), (int)prefetch, 1,
-                                 getenv("RAOTEH_JIT_HALVES") && atoi(getenv("RAOTEH_JIT_HALVES")), multi);
+                                 getenv("RAOTEH_JIT_HALVES") && atoi(getenv("RAOTEH_JIT_HALVES")), multi,
+                                 rt_jit_teams_env() > 0);
     RT_REQUIRE((int64_t)src.size() + 1 <= capacity, "buffer too small: %lld bytes needed",
                (long long)src.size() + 1);
     memcpy(buf, src.c_str(), src.size() + 1);
@@ -1906,7 +1929,8 @@ static int sites_create_impl(rt_model *m, int64_t nsites, int kind, int64_t nobs
             fprintf(stderr, "[raoteh_amd] probe verification rejected %s\n", s->kernel_name);
             rc = RT_ERR_INVALID;
         }
-        if (vrc != RT_OK) {
+        // back to the interpreter kernel and its layout
+        auto drop_kernel = [&]() {
             rt_jit_ref(m->ctx, s->jit_fn, -1);
             s->jit_fn = nullptr;
             s->block_sites = 64;
@@ -1918,8 +1942,23 @@ static int sites_create_impl(rt_model *m, int64_t nsites, int kind, int64_t nobs
             s->jit_pipe = false;
             s->jit_halves = false;
             s->jit_fold = false;
+            s->jit_teams = false;
             s->jit_combine = nullptr;
             s->jit_fused = false;
+        };
+        if (vrc != RT_OK) {
+            const bool was_teams = s->jit_teams;
+            drop_kernel();
+            // a rejected two-team kernel: the one-team form of the same tiling, not the
+            // interpreter (the rejection is cached, so the policy now passes it over)
+            if (was_teams && rc == RT_OK) {
+                rc = sites_jit(s, generic || s->rescale, kind, ov);
+                if (rc == RT_OK && s->jit_fn && !rt_jit_verified(m->ctx, s->jit_fn)) {
+                    const int vrc2 = verify_jit_kernel(s, kind);
+                    rt_jit_set_verified(m->ctx, s->jit_fn, vrc2 == RT_OK);
+                    if (vrc2 != RT_OK) drop_kernel();
+                }
+            }
         }
     }
     if (rc == RT_OK) rc = sites_alloc(s, generic);
@@ -1968,6 +2007,12 @@ extern "C" int rt_sites_create(rt_model *m, int64_t nsites, int kind, int64_t no
 // two random rate sets, and one launch must leave the bits of the loop form.
 static int verify_jit_kernel(rt_sites *s, int kind, void *multi_fn, void *multi_combine)
 {
+    // (RAOTEH_JIT_REJECT_TEAMS: diagnostics only -- every two-team kernel counts as rejected, so
+    // that the fall-back to the one-team form can be exercised, tests/test_prune_teams_gpu.py)
+    if (s->jit_teams && !multi_fn && getenv("RAOTEH_JIT_REJECT_TEAMS")) {
+        rt_set_error("two-team kernel rejected (RAOTEH_JIT_REJECT_TEAMS)");
+        return RT_ERR_UNSUPPORTED;
+    }
     rt_model *m = s->model;
     const int64_t n = m->n, N = m->nnodes, K = s->nobs;
     const bool mfma = s->layout == RT_LAYOUT_MFMA;
@@ -2046,6 +2091,7 @@ static int verify_jit_kernel(rt_sites *s, int kind, void *multi_fn, void *multi_
     same.fuse = s->jit_fused;
     same.sparse = s->jit_sparse;
     same.pipe = s->jit_pipe;
+    same.teams = s->jit_teams;
     if (rc == RT_OK)
         rc = sites_create_impl(tm, np, pkind, K, obs_nodes.data(), data, &interp, &si);
     if (rc == RT_OK)
@@ -2229,6 +2275,51 @@ static int sites_lane_switch(rt_sites *s, const std::string &src)
     return RT_OK;
 }
 
+// One candidate of a finished background job (MFMA families): take its kernel from the context's
+// cache, set the batch up for it and verify it on a probe batch if nobody has yet.  False: the
+// batch is back on the interpreter kernel (the kernel spilled or was rejected).
+static bool sites_take_candidate(rt_sites *s, const std::string &text, const rt_sites::jit_cand &c)
+{
+    rt_model *m = s->model;
+    void *fn = nullptr;
+    if (rt_jit_get(m->ctx, text, &fn, true, nullptr) != RT_OK) return false;
+    const bool split = m->n > 32 || !s->mfma_solo;
+    s->jit_fn = fn;
+    s->jit_tiles = c.T;
+    s->jit_sparse = c.sparse;
+    s->jit_pipe = split && c.sparse && c.pipe;
+    s->jit_quad = !split && c.quad;
+    s->jit_teams = split && c.teams;
+    if (split) s->jit_waves = (int)((m->n + 15) / 16);
+    int src = RT_OK;
+    if (split && c.halves) src = sites_halves_setup(s);
+    if (src == RT_OK && s->jit_halves && !s->d_half &&
+        hipMalloc((void **)&s->d_half,
+                  (size_t)(s->nblocks + 8) * 2 * ((m->n + 15) / 16) * 4 * 64 * 8) != hipSuccess)
+        src = RT_ERR_NOMEM;
+    if (src == RT_OK && s->jit_halves && !s->d_half_count) {
+        if (hipMalloc((void **)&s->d_half_count, (size_t)(s->nblocks + 8) * 4) != hipSuccess ||
+            hipMemset(s->d_half_count, 0, (size_t)(s->nblocks + 8) * 4) != hipSuccess)
+            src = RT_ERR_NOMEM;
+    }
+    if (src == RT_OK && !rt_jit_verified(m->ctx, fn) && !getenv("RAOTEH_JIT_NO_VERIFY")) {
+        src = verify_jit_kernel(s, s->jit_kind);
+        rt_jit_set_verified(m->ctx, fn, src == RT_OK);
+    }
+    if (src == RT_OK) return true;
+    rt_jit_ref(m->ctx, fn, -1);
+    s->jit_fn = nullptr;
+    s->jit_tiles = 1;
+    s->jit_quad = false;
+    s->jit_sparse = false;
+    s->jit_pipe = false;
+    s->jit_halves = false;
+    s->jit_fold = false;
+    s->jit_teams = false;
+    s->jit_combine = nullptr;
+    return false;
+}
+
 // The background job of this batch is done (or `wait`: join it): take the kernel it left in
 // the context's cache, verify it on a probe batch if nobody has yet, and from the next launch
 // on the batch runs it.  Any failure leaves the batch on the interpreter kernel.
@@ -2255,42 +2346,11 @@ int rt_sites_jit_poll(rt_sites *s, bool wait)
     rt_model *m = s->model;
     RT_HIP(hipSetDevice(m->ctx->device));
     if (s->layout == RT_LAYOUT_LANE) return sites_lane_switch(s, srcs[(size_t)chosen]);
-    void *fn = nullptr;
-    if (rt_jit_get(m->ctx, srcs[(size_t)chosen], &fn, true, nullptr) != RT_OK) return RT_OK;
-    const rt_sites::jit_cand c = cands[(size_t)chosen];
-    const bool split = m->n > 32 || !s->mfma_solo;
-    s->jit_fn = fn;
-    s->jit_tiles = c.T;
-    s->jit_sparse = c.sparse;
-    s->jit_pipe = split && c.sparse && c.pipe;
-    s->jit_quad = !split && c.quad;
-    if (split) s->jit_waves = (int)((m->n + 15) / 16);
-    int src = RT_OK;
-    if (split && c.halves) src = sites_halves_setup(s);
-    if (src == RT_OK && s->jit_halves && !s->d_half &&
-        hipMalloc((void **)&s->d_half,
-                  (size_t)(s->nblocks + 8) * 2 * ((m->n + 15) / 16) * 4 * 64 * 8) != hipSuccess)
-        src = RT_ERR_NOMEM;
-    if (src == RT_OK && s->jit_halves && !s->d_half_count) {
-        if (hipMalloc((void **)&s->d_half_count, (size_t)(s->nblocks + 8) * 4) != hipSuccess ||
-            hipMemset(s->d_half_count, 0, (size_t)(s->nblocks + 8) * 4) != hipSuccess)
-            src = RT_ERR_NOMEM;
-    }
-    if (src == RT_OK && !rt_jit_verified(m->ctx, fn) && !getenv("RAOTEH_JIT_NO_VERIFY")) {
-        src = verify_jit_kernel(s, s->jit_kind);
-        rt_jit_set_verified(m->ctx, fn, src == RT_OK);
-    }
-    if (src != RT_OK) {
-        rt_jit_ref(m->ctx, fn, -1);
-        s->jit_fn = nullptr;
-        s->jit_tiles = 1;
-        s->jit_quad = false;
-        s->jit_sparse = false;
-        s->jit_pipe = false;
-        s->jit_halves = false;
-        s->jit_fold = false;
-        s->jit_combine = nullptr;
-        return RT_OK;
+    // (a two-team kernel the probe rejects: on to the one-team form that follows it in the list)
+    for (;; ++chosen) {
+        const rt_sites::jit_cand &c = cands[(size_t)chosen];
+        if (sites_take_candidate(s, srcs[(size_t)chosen], c)) break;
+        if (!c.teams || chosen + 1 >= (int)cands.size()) return RT_OK;
     }
     // the interpreter kernel and the specialised one leave their per-wave partial sums in
     // different places of d_partial: what the other one wrote must read as zero
@@ -2346,6 +2406,7 @@ extern "C" int rt_sites_clone(rt_sites *src, rt_sites **out)
     s->jit_quad = src->jit_quad;
     s->jit_halves = src->jit_halves;
     s->jit_fold = src->jit_fold;
+    s->jit_teams = src->jit_teams;
     s->jit_combine = src->jit_combine;
     s->jit_fused = src->jit_fused;
     s->compact_states = src->compact_states;
@@ -2630,7 +2691,7 @@ static void sites_multi_poll(rt_sites *s, bool wait)
         if (!multi_form_possible(s)) return;
         s->multi_src = rt_jit_mfma_split_pipelined_source(
             s->ops, (int)s->model->n, (int)s->nobs, s->jit_tiles, s->jit_prefetch, s->jit_lookahead,
-            s->jit_halves, s->jit_sparse ? (s->sparse_pairs ? 2 : 1) : 0, true);
+            s->jit_halves, s->jit_sparse ? (s->sparse_pairs ? 2 : 1) : 0, true, s->jit_teams);
         const int known = s->multi_src.empty() ? -1 : rt_jit_cached(ctx, s->multi_src);
         if (known < 0) {
             s->multi_state = -1;
@@ -2737,7 +2798,8 @@ extern "C" int rt_step_multi(rt_model *m, rt_sites *s, int recompute_transitions
                  (int)m->n, s->jit_tiles,
                  s->jit_sparse && s->jit_halves ? ",halves,leaf-states"
                  : s->jit_sparse ? (s->jit_pipe ? ",pipelined,leaf-states" : ",leaf-states")
-                 : s->jit_halves ? ",halves" : "");
+                 : s->jit_halves ? (s->jit_teams ? ",halves,teams" : ",halves")
+                 : s->jit_teams ? ",teams" : "");
         hipEvent_t ev = nullptr;
         rt_time_begin(ctx, RT_K_PRUNE, s->multi_kernel_name, &ev);
         RT_TRY(rt_launch_prune_jit_multi(m, s, a));

@@ -256,6 +256,7 @@ struct rt_sites {
     // folded form: the second workgroup of a pair to arrive finishes the pair's tiles (no
     // combine launch); d_half_count: one arrival counter per pair, zero between launches
     bool jit_fold = false;
+    bool jit_teams = false;         // ... two four-wave teams per workgroup (jit.hip)
     int *d_half_count = nullptr;
     // the same cut for the split-M INTERPRETER kernel (prune.hip rt_interp_halves), used while
     // the batch has no tree-specialised kernel: the two root programs, the P record and the
@@ -280,7 +281,8 @@ struct rt_sites {
     // background compile of the tree-specialised kernel (MFMA family): the batch runs the
     // interpreter kernel until the job is done and rt_sites_jit_poll swaps the kernel in
     std::shared_ptr<rt_jit_job> jit_job;
-    struct jit_cand { int T; bool halves; bool quad; bool sparse = false; bool pipe = false; };
+    struct jit_cand { int T; bool halves; bool quad; bool sparse = false; bool pipe = false;
+                      bool teams = false; };
     std::vector<jit_cand> jit_cands;        // what each candidate source of the job was built with
     std::vector<std::string> jit_srcs;
     int jit_kind = 0;                       // observation kind of the batch (probe batches)
@@ -435,7 +437,12 @@ std::string rt_jit_mfma_split_source(const std::vector<rt_op> &ops, int n, int K
 bool rt_jit_fold_enabled();
 std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, int n, int K, int T,
                                                int D, int LA, bool halves = false,
-                                               int sparse = 0, bool multi = false);
+                                               int sparse = 0, bool multi = false,
+                                               bool teams = false);
+// the two-team form of that generator (eight waves per workgroup) exists for these parameters
+bool rt_jit_teams_possible(int n, int T, int sparse);
+// RAOTEH_JIT_TEAMS: -1 not set (the policy decides), 0 / 1 forced
+int rt_jit_teams_env();
 // steps of the two root programs the halves form would run (0, 0: the root has < 2 children)
 void rt_jit_root_halves(const std::vector<rt_op> &ops, int *stepsA, int *stepsB);
 // the cut itself: A = the subtrees of all children of the root but the last, B = the last

@@ -1667,6 +1667,17 @@ bool rt_jit_fold_enabled()
     return v && atoi(v) != 0;
 }
 
+bool rt_jit_teams_possible(int n, int T, int sparse)
+{
+    return (n + 15) / 16 == 4 && T >= 3 && T <= 5 && !sparse && !rt_jit_fold_enabled();
+}
+
+int rt_jit_teams_env()
+{
+    const char *v = getenv("RAOTEH_JIT_TEAMS");
+    return v && v[0] ? (atoi(v) != 0) : -1;
+}
+
 // multi (rt_step_multi, one launch for all rate sets): the kernels take the rate set from
 // blockIdx.y and add that set's strides to the table and output pointers in their prologue
 // (wave-uniform scalar adds); without it the text is what it was.  The strides follow the
@@ -1676,13 +1687,26 @@ static const char *MULTI_PARAMS =
     " long ms_pcol";
 
 std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, int n, int K, int T,
-                                               int D, int LA, bool halves, int sparse, bool multi)
+                                               int D, int LA, bool halves, int sparse, bool multi,
+                                               bool teams)
 {
     (void)LA;
     const bool fold = halves && !sparse && rt_jit_fold_enabled();
+    // teams: two four-wave teams per workgroup, chains 0 .. TA-1 on waves 0-3 and the rest on
+    // waves 4-7, so that every SIMD holds two waves that alternate on the matrix pipe while the
+    // dealing of the tiles stays that of one workgroup per CU.  Each team runs the per-chain
+    // emission of the one-team form restricted to its chains (a chain's instruction sequence is
+    // what it was: same bits); the workgroup's barriers are shared, so both bodies must execute
+    // the same number of them.  NT = 4 and T = 3, 4, 5 only: (2,1), (2,2), (3,2).
+    if (teams && !rt_jit_teams_possible(n, T, sparse)) return std::string();
+    const int TA = teams ? (T + 1) / 2 : T;      // chains of team 0
+    int TLO = 0, THI = T;                        // the chains the emission below is restricted to
     // x of a step is published one step early, so its leaf vector must be in registers a
     // step earlier than in the serial kernel: at least two leaves ahead
-    D = std::max(D, 2);
+    // (teams: the SIMD's other wave covers the latency, one leaf ahead is enough -- the vector
+    // of step i + 1 is requested at the top of step i's shadow and read at its end -- and the
+    // three-chain body then fits the 256 registers of a wave that shares its SIMD)
+    D = teams ? std::max(D - 1, 1) : std::max(D, 2);
     const int NT = (n + 15) / 16;
     const int KS = (n + 3) / 4;
     const int KP = (KS + 1) / 2;
@@ -1701,7 +1725,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
     // step in the shadow, and 16 more live registers in a kernel that already keeps 250
     // values in AGPRs; at T = 1 and T = 2 the register budget no longer holds (scratch: the
     // kernel is rejected and the interpreter runs).
-    const bool lastk = (n % 4 == 1) && KS >= 4 && !sparse && getenv("RAOTEH_JIT_LASTK") &&
+    const bool lastk = (n % 4 == 1) && KS >= 4 && !sparse && !teams && getenv("RAOTEH_JIT_LASTK") &&
                        atoi(getenv("RAOTEH_JIT_LASTK")) != 0;
     const int KSM = lastk ? KS - 1 : KS;      // k-steps on the matrix pipe
     int nslots = 1;
@@ -1759,24 +1783,37 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
       << "): " << nrec_all
       << " steps (" << nlate << " serial), " << n << " states, " << K << " observed nodes, " << T
       << " tiles per workgroup of " << NT << " waves, " << nslots << " accumulator slots, prefetch "
-      << D << " leaves\n";
+      << D << " leaves"
+      << (teams ? ", two teams of four waves" : "") << "\n";
     o << "typedef double rt_d2 __attribute__((ext_vector_type(2)));\n";
     o << "typedef double rt_d4 __attribute__((ext_vector_type(4)));\n";
     const char *trace_env = getenv("RAOTEH_JIT_TRACE");
     const bool trace = trace_env != nullptr;
     const long trace_wg = trace ? atol(trace_env) : 0;
-    if (trace) o << "__device__ unsigned long long rt_trace[" << NT * (nrec_max + 1) * 3 << "];\n";
+    // [wave][step][t0 step start, t1 behind the barrier, t2 last MFMA issued]; teams: the waves
+    // of team 1 follow team 0's, and a fourth stamp stands in front of the barrier (t1 - t3 is
+    // the wait for the other team).  Row nrec_max, places 1 and 2: the constant 100 MHz clock at
+    // the start and the end of the kernel, so that the core clock can be read off.
+    const int TW = teams ? 4 : 3;
+    const std::string trace_row = std::string("(") + (teams ? "(team * 4 + m)" : "m") + " * " +
+                                  std::to_string(nrec_max + 1) + " + ";
+    if (trace) o << "__device__ unsigned long long rt_trace[" << (teams ? 2 : 1) * NT * (nrec_max + 1) * TW << "];\n";
     auto stamp = [&](int i, int which) {
+        if (!trace || which >= TW) return;
+        o << "    if (blockIdx.x == " << trace_wg << " && lane == 0) rt_trace[" << trace_row << i << ") * " << TW
+          << " + " << which << "] = __builtin_readcyclecounter();\n";
+    };
+    auto stamp_real = [&](int which) {
         if (!trace) return;
-        o << "    if (blockIdx.x == " << trace_wg << " && lane == 0) rt_trace[(m * " << (nrec_max + 1)
-          << " + " << i << ") * 3 + " << which << "] = __builtin_readcyclecounter();\n";
+        o << "    if (blockIdx.x == " << trace_wg << " && lane == 0) rt_trace[" << trace_row << nrec_max << ") * "
+          << TW << " + " << which << "] = __builtin_amdgcn_s_memrealtime();\n";
     };
     // NT <= 4 waves: one wave per SIMD and workgroup, three / two / one workgroups per CU at
     // T = 1 / 2 / more tiles.  NT = 5..8 (64 < n <= 128): two waves on some or all SIMDs and
     // the A fragments of two steps alone are up to 128 registers: one workgroup per CU
-    o << "extern \"C\" __global__ void __launch_bounds__(" << 64 * NT
+    o << "extern \"C\" __global__ void __launch_bounds__(" << 64 * NT * (teams ? 2 : 1)
       << ") __attribute__((amdgpu_waves_per_eu("
-      << (NT > 4 ? "2, 2" : T == 1 ? "3, 3" : T == 2 ? "2, 2" : "1, 1")
+      << (NT > 4 || teams ? "2, 2" : T == 1 ? "3, 3" : T == 2 ? "2, 2" : "1, 1")
       << ")))\n"
          "rt_jit_prune(const double *__restrict__ Pfrag, const rt_d2 *__restrict__ obs,\n"
          "             const double *__restrict__ root_w, double *__restrict__ loglik,\n"
@@ -1810,20 +1847,35 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
     o << "    __shared__ double xb2[" << T << "][" << XT << "];\n";
     o << "    __shared__ double red[" << T << "][" << NT << "][16];\n";
     o << "    const int lane = threadIdx.x & 63;\n";
-    o << "    const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // row tile of this wave\n";
+    if (teams) {
+        o << "    const int m = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) & 3);   // row tile of this wave\n";
+        o << "    const int team = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8);   // 0: chains 0 .. "
+          << TA - 1 << ", 1: the rest\n";
+    } else {
+        o << "    const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // row tile of this wave\n";
+    }
     if (halves) {
         o << "    const long tbase = (long)(blockIdx.x >> 1) * " << T << ";\n";
         o << "    const int half = (int)(blockIdx.x & 1);      // which root program\n";
     } else {
         o << "    const long tbase = (long)blockIdx.x * " << T << ";\n";
     }
+    stamp_real(1);
     o << "    typedef const __attribute__((address_space(1))) rt_d2 *rt_glb2;\n";
-    o << "    rt_glb2 ag = (rt_glb2)Pfrag + (m * " << KP * 64 << " + lane);   // [step][m][k-pair][lane][2]\n";
+    // (teams: the table and leaf pointers stay wave-uniform -- scalar registers -- and the lane
+    // is the vector offset of each load: two vector registers less per chain in a body that
+    // has none to spare)
+    const std::string lane_off = teams ? "" : " + lane";
+    auto at_lane = [&](const std::string &base, long off) {
+        return teams ? "(" + base + " + " + std::to_string(off) + ")[lane]"
+                     : base + "[" + std::to_string(off) + "]";
+    };
+    o << "    rt_glb2 ag = (rt_glb2)Pfrag + (m * " << KP * 64 << lane_off << ");   // [step][m][k-pair][lane][2]\n";
     o << "    const bool pair1 = 2 * m + 1 < " << KP << ";\n";
     for (int t = 0; t < T; ++t) {
         o << "    const long tile" << t << " = tbase + " << t << ";\n";
         o << "    rt_glb2 g" << t << " = (rt_glb2)obs + (size_t)(tile" << t << " < nblocks ? tile" << t
-          << " : nblocks - 1) * " << (long)K * KP * 64 << " + (2 * m * 64 + lane);\n";
+          << " : nblocks - 1) * " << (long)K * KP * 64 << " + (2 * m * 64" << lane_off << ");\n";
     }
     for (int r = 0; r < 4; ++r)
         o << "    const bool rowok" << r << " = 16 * m + " << 4 * r << " + (lane >> 4) < " << n << ";\n";
@@ -1844,7 +1896,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
         for (int r = 0; r < 4; ++r)
             os << "    const double w" << r << " = rowok" << r << " ? root_w[16 * m + " << 4 * r
                << " + (lane >> 4)] : 0.0;\n";
-        for (int t = 0; t < T; ++t) {
+        for (int t = TLO; t < THI; ++t) {
             os << "    {\n    double sacc = 0.0;\n";
             for (int r = 0; r < 4; ++r) {
                 os << "    negative" << t << " |= rowok" << r << " && (" << xp << "_" << t << "_" << r
@@ -1856,7 +1908,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
                   "    if (lane < 16) red[" << t << "][m][lane] = sacc;\n    }\n";
         }
         os << "    __syncthreads();\n";
-        for (int t = 0; t < T; ++t) {
+        for (int t = TLO; t < THI; ++t) {
             os << "    if (m == 0 && lane < 16) {\n        double tot = 0.0;\n";
             for (int mm = 0; mm < NT; ++mm)
                 os << "        tot += red[" << t << "][" << mm << "][lane];\n";
@@ -1864,13 +1916,16 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
         }
     };
     // lanes 0..15 of wave 0 own the 16 sites of a tile
+    bool epi_teams = teams;
     auto emit_site_epilogue = [&](std::ostream &os) {
         for (int t = 0; t < T; ++t) {
+            // (teams: wave 0 of the team that ran chain t)
+            const std::string own = epi_teams ? (t < TA ? "team == 0 && " : "team == 1 && ") : "";
             os << "    {\n"
                   "    const long site = tile" << t << " * 16 + (lane & 15);\n"
                   "    const bool ok = lik" << t << " > 0.0;\n"
                   "    double sum = 0.0, nzero = 0.0;\n"
-                  "    if (m == 0 && lane < 16 && tile" << t << " < nblocks && site < nsites) {\n"
+                  "    if (" << own << "m == 0 && lane < 16 && tile" << t << " < nblocks && site < nsites) {\n"
                   "        loglik[site] = ok ? log(lik" << t << ") : -__builtin_inf();\n"
                   "        status[site] = (ok ? " << RT_SITE_OK << " : " << RT_SITE_ZERO_PROB
                << ") | (negative" << t << " ? " << RT_SITE_NEGATIVE << " : 0);\n"
@@ -1881,7 +1936,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
                   "        sum += __shfl_xor(sum, off, 64);\n"
                   "        nzero += __shfl_xor(nzero, off, 64);\n"
                   "    }\n"
-                  "    if (m == 0 && lane == 0 && tile" << t << " < nblocks) {\n"
+                  "    if (" << own << "m == 0 && lane == 0 && tile" << t << " < nblocks) {\n"
                   "        partial[tile" << t << " * 2] = sum;\n"
                   "        partial[tile" << t << " * 2 + 1] = nzero;\n"
                   "    }\n"
@@ -1910,22 +1965,24 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
     std::vector<int> obs_rank((size_t)std::max(K, 1), -1);
     for (size_t k = 0; k < obs_order.size(); ++k) obs_rank[(size_t)obs_order[k]] = (int)k;
     auto emit_obs_load = [&](std::ostream &os, int pos) {       // pos = stream position (op.obs)
-        for (int t = 0; t < T; ++t) {
-            os << "    const rt_d2 o" << pos << "_" << t << "_0 = __builtin_nontemporal_load(&g" << t
-               << "[" << (long)pos * KP * 64 << "]);\n";
-            os << "    const rt_d2 o" << pos << "_" << t << "_1 = pair1 ? __builtin_nontemporal_load(&g"
-               << t << "[" << ((long)pos * KP + 1) * 64 << "]) : zero2;\n";
+        for (int t = TLO; t < THI; ++t) {
+            const std::string gt = "g" + std::to_string(t);
+            os << "    const rt_d2 o" << pos << "_" << t << "_0 = __builtin_nontemporal_load(&"
+               << at_lane(gt, (long)pos * KP * 64) << ");\n";
+            os << "    const rt_d2 o" << pos << "_" << t << "_1 = pair1 ? __builtin_nontemporal_load(&"
+               << at_lane(gt, ((long)pos * KP + 1) * 64) << ") : zero2;\n";
         }
     };
-    auto emit_a_load = [&](std::ostream &os, int k) {           // k = issue index
+    // k = issue index; k-pairs q0 .. q1 - 1 (all by default)
+    auto emit_a_load = [&](std::ostream &os, int k, int q0 = 0, int q1 = -1) {
         const int rec = rec_of_node[(size_t)st[(size_t)k].op.node];
-        for (int q = 0; q < KP; ++q) {
+        for (int q = q0; q < (q1 < 0 ? KP : q1); ++q) {
             const long at = ((long)rec * NT * KP + q) * 64;
             if ((KS & 1) && q == KP - 1)
                 os << "    const rt_d2 A" << k << "_" << q << " = "
-                   << half_pair_load("ag[" + std::to_string(at) + "]", false) << ";\n";
+                   << half_pair_load(at_lane("ag", at), false) << ";\n";
             else
-                os << "    const rt_d2 A" << k << "_" << q << " = ag[" << at << "];\n";
+                os << "    const rt_d2 A" << k << "_" << q << " = " << at_lane("ag", at) << ";\n";
         }
     };
     // (lastk) this lane's four entries of column n - 1 of P, from the A fragment of issue step k
@@ -1948,7 +2005,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
         const int shf = sparse == 2 ? 16 * (lf.obs & 1) : 8 * (lf.obs & 3);
         if (!word_seen[(size_t)w]) {
             word_seen[(size_t)w] = 1;
-            for (int t = 0; t < T; ++t)
+            for (int t = TLO; t < THI; ++t)
                 os << "    const unsigned lw" << prog << "_" << w << "_" << t << " = leafw[((size_t)(tile" << t
                    << " < nblocks ? tile" << t << " : nblocks - 1) * " << KW << " + " << w
                    << ") * 16 + (lane & 15)];\n";
@@ -1958,7 +2015,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
         // row-lanes of a site then read one 64-byte sector together, where the row-major P costs
         // a sector per lane -- the gathers, not the products, bounded the first version.
         const int rec = rec_of_node[(size_t)lf.node];
-        for (int t = 0; t < T; ++t) {
+        for (int t = TLO; t < THI; ++t) {
             os << "    const int st" << lf.node << "_" << t << " = (int)((lw" << prog << "_" << w << "_" << t
                << " >> " << shf << ") & 255u);\n";
             os << "    const rt_d4 pf" << lf.node << "_" << t << " = pcm[(" << (long)rec * n << " + st" << lf.node
@@ -1991,7 +2048,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
     auto emit_x = [&](std::ostream &os, int k) {
         const rt_op &op = st[(size_t)k].op;
         const std::vector<leaf_ref> &tr = trail_of(op);
-        for (int t = 0; t < T; ++t)
+        for (int t = TLO; t < THI; ++t)
             for (int r = 0; r < 4; ++r) {
                 std::ostringstream obs_r;
                 if (op.obs >= 0)
@@ -2017,7 +2074,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
     };
     auto emit_publish = [&](std::ostream &os, int k) {          // x(k) -> xb<k % 3>
         emit_x(os, k);
-        for (int t = 0; t < T; ++t)
+        for (int t = TLO; t < THI; ++t)
             for (int r = 0; r < 4; ++r)
                 os << "    xb" << (k % 3) << "[" << t << "][(4 * m + " << r << ") * 64 + lane] = x" << k
                    << "_" << t << "_" << r << ";\n";
@@ -2027,7 +2084,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
         const int d = op.dst & 255;
         const bool first = (op.dst >> 8) != 0;
         if (lastk)
-            for (int t = 0; t < T; ++t) {
+            for (int t = TLO; t < THI; ++t) {
                 os << "    const double xl" << k << "_" << t << " = xb" << k % 3 << "[" << t << "]["
                    << (KS - 1) * 64 << " + (lane & 15)];\n";
                 for (int r = 0; r < 4; ++r)
@@ -2035,7 +2092,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
                        << "_" << t << ", c" << k << "_" << t << "[" << r << "]);\n";
             }
         const std::vector<leaf_ref> &ld = lead_of(op);
-        for (int t = 0; t < T; ++t)
+        for (int t = TLO; t < THI; ++t)
             for (int r = 0; r < 4; ++r) {
                 os << "    a" << d << "_" << t << "_" << r << " = ";
                 // (the leaves folded since the previous matrix sibling, then this result: the
@@ -2052,6 +2109,16 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
                 os << (any ? " * " : "") << "c" << k << "_" << t << "[" << r << "];\n";
             }
     };
+    size_t barriers0 = 0;
+    for (int team = 0; team < (teams ? 2 : 1); ++team) {
+    // (teams: a wave-uniform branch over the two straight-line bodies)
+    if (teams) {
+        TLO = team == 0 ? 0 : TA;
+        THI = team == 0 ? TA : T;
+        o << (team == 0 ? "    if (team == 0) {\n" : "    } else {\n");
+    }
+    const int TT = THI - TLO;
+    const size_t body_begin = (size_t)o.tellp();
     // ---- prologue -----------------------------------------------------------------------
     for (int k = 0; k < GA; ++k) emit_gathers_of(o, k);
     for (int k = 0; k < std::min(D, (int)obs_order.size()); ++k) emit_obs_load(o, obs_order[(size_t)k]);
@@ -2068,8 +2135,8 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
     std::string dep = "lane";
     for (int i = 0; i < nrec; ++i) {
         const rt_op &op = st[(size_t)i].op;
-        o << "    asm volatile(\"\" : \"+v\"(ag)";
-        for (int t = 0; t < T; ++t) o << ", \"+v\"(g" << t << ")";
+        o << "    asm volatile(\"\" : \"+" << (teams ? "s" : "v") << "\"(ag)";
+        for (int t = TLO; t < THI; ++t) o << ", \"+" << (teams ? "s" : "v") << "\"(g" << t << ")";
         o << " : \"v\"(" << dep << "));\n";
         o << "    __builtin_amdgcn_sched_barrier(0);\n";
         o << "    // ---- step " << i << ": node " << op.node << (st[(size_t)i].late ? " (serial)" : "")
@@ -2081,7 +2148,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
             if (halves) {
                 // this program's share of the root's accumulator (own rows) -> halfbuf
                 // (the buffer is padded to whole groups of T tiles: no bounds check)
-                for (int t = 0; t < T; ++t) {
+                for (int t = TLO; t < THI; ++t) {
                     o << "    {\n    double *hb = halfbuf + ((size_t)tile" << t << " * 2 + " << prog
                       << ") * " << XT << " + (4 * m) * 64 + lane;\n";
                     for (int r = 0; r < 4; ++r) {
@@ -2112,7 +2179,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
             emit_root_reduce(o, "x" + std::to_string(i));
             continue;
         }
-        dep = "c" + std::to_string(i) + "_0[0]";
+        dep = "c" + std::to_string(i) + "_" + std::to_string(TLO) + "[0]";
         const bool have_next = i + 1 < nrec;
         const bool next_root = have_next && st[(size_t)(i + 1)].op.dst < 0;
         const bool next_late = have_next && st[(size_t)(i + 1)].late;
@@ -2123,15 +2190,22 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
         // the pipe up, which is what the first version of this kernel did: 84 cycles per
         // MFMA instead of 67)
         std::ostringstream sh;
+        // (teams: the A look-ahead is half a step shallower, so that the three-chain body fits the
+        // 256 registers of a wave that shares its SIMD: the second half of this step's k-pairs
+        // is asked for here, behind the first MFMAs and long before its k-steps, and the first
+        // half of the next step's at the end of the shadow, when the first half of this step's
+        // is dead; the SIMD's other wave covers the shorter lead)
+        if (teams && i > 0) emit_a_load(sh, i, KP / 2, KP);
         // (the fetches first: a leaf vector is declared before anything that may name it)
         if (op.obs >= 0) {
             const int rank = obs_rank[(size_t)op.obs];
             if (rank + D < (int)obs_order.size()) emit_obs_load(sh, obs_order[(size_t)(rank + D)]);
         }
-        if (i + 1 < nrec && st[(size_t)(i + 1)].op.dst >= 0) emit_a_load(sh, i + 1);
+        if (!teams && i + 1 < nrec && st[(size_t)(i + 1)].op.dst >= 0) emit_a_load(sh, i + 1);
         emit_gathers_of(sh, i + GA);
         if (fold_pending) { emit_fold(sh, i - 1); fold_pending = false; }
         if (have_next && !next_root && !next_late) emit_publish(sh, i + 1);
+        if (teams && i + 1 < nrec && st[(size_t)(i + 1)].op.dst >= 0) emit_a_load(sh, i + 1, 0, KP / 2);
         // (behind everything else: the fragment it reads was requested at the top of this shadow)
         if (i + 1 < nrec && st[(size_t)(i + 1)].op.dst >= 0) emit_pcol(sh, i + 1);
         std::vector<std::string> shadow;
@@ -2144,24 +2218,25 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
                 pos = nl + 1;
             }
         }
-        for (int t = 0; t < T; ++t) o << "    rt_d4 c" << i << "_" << t << " = {0.0, 0.0, 0.0, 0.0};\n";
+        for (int t = TLO; t < THI; ++t) o << "    rt_d4 c" << i << "_" << t << " = {0.0, 0.0, 0.0, 0.0};\n";
         // MFMAs, MFMA results and LDS writes keep their order across these barriers; LDS
         // reads, global reads and scalar instructions may move (0x100 | 0x20 | 0x4)
-        const int nmfma = KSM * T;
-        const int lead = std::min(2 * T, nmfma);          // MFMAs before the first shadow slice
-        const int slots = std::max(1, nmfma - lead - 2 * T);   // ... none behind the last 2 T
+        const int nmfma = KSM * TT;
+        const int lead = std::min(2 * TT, nmfma);          // MFMAs before the first shadow slice
+        const int slots = std::max(1, nmfma - lead - 2 * TT);   // ... none behind the last 2 T
         size_t next_sh = 0;
         int issued = 0;
         const bool early_barrier = have_next && !next_root && !next_late && KS >= 4;
         for (int kk = 0; kk < KSM; ++kk)
-            for (int t = 0; t < T; ++t) {
-                if (early_barrier && issued == nmfma - T) {
+            for (int t = TLO; t < THI; ++t) {
+                if (early_barrier && issued == nmfma - TT) {
                     // the shadow is empty: x of step i + 1 is on its way to LDS
                     while (next_sh < shadow.size()) o << shadow[next_sh++];
+                    stamp(i + 1, 3);
                     o << "    __syncthreads();      // x of step " << i + 1 << " is in LDS\n";
                     stamp(i + 1, 1);
                     for (int k2 = 0; k2 < 2; ++k2)
-                        for (int t2 = 0; t2 < T; ++t2)
+                        for (int t2 = TLO; t2 < THI; ++t2)
                             o << "    const double bp" << i + 1 << "_" << t2 << "_" << k2 << " = xb"
                               << (i + 1) % 3 << "[" << t2 << "][" << k2 * 64 << " + lane];\n";
                     o << "    __builtin_amdgcn_sched_barrier(0x124);\n";
@@ -2177,7 +2252,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
                     // spread what is left evenly over the MFMAs that are left
                     const int left = std::max(1, slots - (issued - lead));
                     size_t take = (shadow.size() - next_sh + (size_t)left - 1) / (size_t)left;
-                    if (issued >= nmfma - 2 * T) take = shadow.size() - next_sh;
+                    if (issued >= nmfma - 2 * TT) take = shadow.size() - next_sh;
                     o << "    __builtin_amdgcn_sched_barrier(0x124);\n";
                     for (size_t q = 0; q < take && next_sh < shadow.size(); ++q) o << shadow[next_sh++];
                     o << "    __builtin_amdgcn_sched_barrier(0x124);\n";
@@ -2193,12 +2268,28 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
             fold_pending = true;
         }
         if (have_next && !next_root && !early_barrier) {
+            stamp(i + 1, 3);
             o << "    __syncthreads();      // x of step " << i + 1 << " is in LDS\n";
             stamp(i + 1, 1);
         }
         prefetched = early_barrier;
     }
     stamp(nrec, 0);
+    stamp_real(2);
+    if (teams) {
+        // the workgroup's barriers are shared by the two bodies
+        const std::string text = o.str().substr(body_begin);
+        size_t nb = 0;
+        for (size_t at = text.find("__syncthreads()"); at != std::string::npos;
+             at = text.find("__syncthreads()", at + 1))
+            ++nb;
+        if (team == 0) barriers0 = nb;
+        else if (nb != barriers0) return std::string();
+        if (team == 1) o << "    }\n";
+    }
+    }   // teams
+    TLO = 0;
+    THI = T;
     }   // programs
     if (halves) {
         if (fold) {
@@ -2249,6 +2340,9 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
         // ---- second kernel of the module: root step + site epilogue from the two halves,
         // one tile per workgroup whatever T is
         T = 1;
+        TLO = 0;
+        THI = 1;
+        epi_teams = false;
         const rt_op &root = ops.back();
         o << "extern \"C\" __global__ void __launch_bounds__(" << 64 * NT << ")\n"
              "rt_jit_combine(const double *__restrict__ halfbuf, const rt_d2 *__restrict__ obs,\n"
@@ -2840,7 +2934,9 @@ int rt_launch_prune_jit(rt_model *m, rt_sites *s, const rt_fuse_args *fuse, cons
             return RT_OK;
         }
         void *cargs[] = {&chalf, &obs, &root_w, &loglik, &status, &partial, &nsites, &nblocks};
-        const unsigned tpb = 64u * (unsigned)s->jit_waves;
+        // (teams: eight waves per pruning workgroup; the combine kernel keeps its four)
+        const unsigned ctpb = 64u * (unsigned)s->jit_waves;
+        const unsigned tpb = ctpb * (s->jit_teams ? 2u : 1u);
         const unsigned tiles = (unsigned)s->nblocks;
         const unsigned groups = (unsigned)((s->nblocks + s->jit_tiles - 1) / s->jit_tiles);
         if (m->ctx->ev_start) {
@@ -2849,13 +2945,13 @@ int rt_launch_prune_jit(rt_model *m, rt_sites *s, const rt_fuse_args *fuse, cons
             RT_HIP(hipExtModuleLaunchKernel((hipFunction_t)s->jit_fn, 2u * groups * tpb, 1, 1, tpb, 1, 1,
                                             0, m->ctx->stream, hargs, nullptr, m->ctx->ev_start,
                                             m->ctx->ev_stop, 0));
-            RT_HIP(hipExtModuleLaunchKernel((hipFunction_t)s->jit_combine, tiles * tpb, 1, 1, tpb, 1, 1,
+            RT_HIP(hipExtModuleLaunchKernel((hipFunction_t)s->jit_combine, tiles * ctpb, 1, 1, ctpb, 1, 1,
                                             0, m->ctx->stream, cargs, nullptr, ca, cb, 0));
             rt_time_extra_end(m->ctx, RT_K_COMBINE, ca, cb);
         } else {
             RT_HIP(hipModuleLaunchKernel((hipFunction_t)s->jit_fn, 2u * groups, 1, 1, tpb, 1, 1, 0,
                                          m->ctx->stream, hargs, nullptr));
-            RT_HIP(hipModuleLaunchKernel((hipFunction_t)s->jit_combine, tiles, 1, 1, tpb, 1, 1, 0,
+            RT_HIP(hipModuleLaunchKernel((hipFunction_t)s->jit_combine, tiles, 1, 1, ctpb, 1, 1, 0,
                                          m->ctx->stream, cargs, nullptr));
         }
         return RT_OK;
@@ -2863,7 +2959,8 @@ int rt_launch_prune_jit(rt_model *m, rt_sites *s, const rt_fuse_args *fuse, cons
     // lane family: jit_waves waves of one site block each per workgroup; MFMA family,
     // n <= 32: one wave of jit_tiles site tiles per workgroup; n > 32: jit_waves = NT
     // waves share jit_tiles tiles
-    const int wg = (s->layout == RT_LAYOUT_LANE || !s->mfma_solo) ? s->jit_waves : 1;
+    const int wg = ((s->layout == RT_LAYOUT_LANE || !s->mfma_solo) ? s->jit_waves : 1) *
+                   (s->jit_teams ? 2 : 1);
     const long per = s->layout == RT_LAYOUT_LANE ? wg : s->jit_tiles;
     // global size in work-items; the events (null unless this launch is sampled) get
     // the kernel's own begin / end
@@ -2904,7 +3001,8 @@ int rt_launch_prune_jit_multi(rt_model *m, rt_sites *s, const rt_multi_launch &a
     args.insert(args.end(), strides, strides + 6);
     std::vector<void *> cargs = {&chalf, &obs, &root_w, &loglik, &status, &partial, &nsites, &nblocks};
     cargs.insert(cargs.end(), strides, strides + 6);
-    const unsigned tpb = 64u * (unsigned)s->jit_waves;
+    const unsigned ctpb = 64u * (unsigned)s->jit_waves;
+    const unsigned tpb = ctpb * (s->jit_teams ? 2u : 1u);
     const unsigned K = (unsigned)a.K;
     const unsigned groups = (unsigned)((s->nblocks + s->jit_tiles - 1) / s->jit_tiles) *
                             (s->jit_halves ? 2u : 1u);
@@ -2920,10 +3018,10 @@ int rt_launch_prune_jit_multi(rt_model *m, rt_sites *s, const rt_multi_launch &a
         if (m->ctx->ev_start) rt_time_extra_begin(m->ctx, RT_K_COMBINE, "rt_jit_combine,multi", &ca, &cb);
         const unsigned tiles = (unsigned)s->nblocks;
         if (ca)
-            RT_HIP(hipExtModuleLaunchKernel((hipFunction_t)s->multi_combine, tiles * tpb, K, 1, tpb, 1, 1,
+            RT_HIP(hipExtModuleLaunchKernel((hipFunction_t)s->multi_combine, tiles * ctpb, K, 1, ctpb, 1, 1,
                                             0, m->ctx->stream, cargs.data(), nullptr, ca, cb, 0));
         else
-            RT_HIP(hipModuleLaunchKernel((hipFunction_t)s->multi_combine, tiles, K, 1, tpb, 1, 1, 0,
+            RT_HIP(hipModuleLaunchKernel((hipFunction_t)s->multi_combine, tiles, K, 1, ctpb, 1, 1, 0,
                                          m->ctx->stream, cargs.data(), nullptr));
         rt_time_extra_end(m->ctx, RT_K_COMBINE, ca, cb);
     }

@@ -2078,7 +2078,8 @@ int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm,
                      s->jit_quad ? "4x4" : "", (int)m->n, s->jit_tiles,
                      s->jit_sparse && s->jit_halves ? ",halves,leaf-states"
                      : s->jit_sparse ? (s->jit_pipe ? ",pipelined,leaf-states" : ",leaf-states")
-                     : s->jit_halves ? ",halves" : "");
+                     : s->jit_halves ? (s->jit_teams ? ",halves,teams" : ",halves")
+                     : s->jit_teams ? ",teams" : "");
         name = jit_name;
     } else if (s->layout == RT_LAYOUT_LANE) {
         switch ((int)m->n) {
