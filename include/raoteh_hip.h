@@ -460,6 +460,46 @@ int rt_sites_posteriors(rt_model *model, rt_sites *sites, int recompute_transiti
 int rt_sites_branch_expectations(rt_model *model, rt_sites *sites, int recompute_transitions,
             int64_t n_coefs, const double *coefs, double *values, double *edge_sums,
             int32_t *status);
+/* _sample_mcy_dense.resample_states (_sample_mcy_dense.py:23-69, through
+ * _sample_mc0_dense.resample_states, _sample_mc0_dense.py:20-98) for every site of a RESIDENT
+ * batch: ndraws joint draws of a state for every node from the posterior given the observations.
+ *   states[d][i][v]  uint8[ndraws][nsites][nnodes], v the preorder index; 255 = no state (the code
+ *                    an RT_OBS_STATE upload reads as "unobserved": a draw can be uploaded back)
+ * With L_v the subtree likelihood of node v including its own observation (dense observations are
+ * used as values, as in rt_sites_posteriors), the weights of the root are
+ *   w[s] = root_w[s] * L_root[s]       (root_w: rt_model_set_root_distn, ones if unset)
+ * and those of a node v whose parent drew state a
+ *   w[b] = P_v[a][b] * L_v[b];
+ * a negative product counts as 0.  With total = sum_s w[s] and
+ *   u = philox_uniform(seed, first_draw + d, i * nnodes + v)
+ * (Philox4x32-10: counter words {index low, index high, draw low, draw high}, key {seed low, seed
+ * high}; u = (((c0 << 21) ^ (c1 >> 11)) mod 2^53) * 2^-53 of the output words c0, c1 -- the
+ * generator of rt_forest_resample_states with the draw number as its sweep) the pick is the first
+ * state in index order with w > 0 whose cumulative weight exceeds u * total; if rounding leaves
+ * none, the last state with w > 0.  (The kernels accumulate in chunks of four states: the
+ * cumulative weights agree with a sequential sum to rounding.)  So a draw depends on (seed,
+ * first_draw + d, site, node) and the numbers alone: not on ndraws, not on the batch's pruning
+ * kernel, and draws [f, f + k) of one call equal draws [0, k) of a call with first_draw = f.
+ *   status[i] (optional), OR-ed over the draws: RT_SITE_ZERO_PROB when the root's total is not
+ *              positive and finite (every node of every draw of the site is 255); 2 when a
+ *              non-root node has no state of positive weight (that node and its descendants are
+ *              255; impossible with a consistent L)
+ * Every batch rt_sites_create makes for 2 <= n <= 128 (all observation kinds), transitions from
+ * any of the rt_model_set_* calls (recompute_transitions != 0 needs rates).  RT_ERR_INVALID:
+ * ndraws < 1, states NULL, a batch of another model, no transitions yet.  RT_ERR_UNSUPPORTED: what
+ * rt_sites_posteriors refuses (a "rescale" batch, a generic-kernel batch, a tree deeper than the
+ * fast kernels take, nnodes < 2), more than 96 GB of scratch, and for n > 4 a tree of more than
+ * RT_MAX_SAMPLE_NODES nodes (the sampled states of one wave's sites live in LDS, 16 bytes per node
+ * and draw of a block).  Synchronous; only states and status cross PCIe; the batch keeps its
+ * kernel, log-likelihoods, status and totals.                                                  */
+#define RT_MAX_SAMPLE_NODES 8192
+int rt_sites_sample_states(rt_model *model, rt_sites *sites, int recompute_transitions,
+            uint64_t seed, uint64_t first_draw, int64_t ndraws,
+            uint8_t *states /* [ndraws][nsites][nnodes], preorder index */,
+            int32_t *status /* [nsites] or NULL */);
+/* draws that share one read of L in rt_sites_sample_states for a tree of nnodes nodes (n > 4):
+ * 16 at most, fewer as the tree grows, 1 from 1025 nodes on; 0 beyond RT_MAX_SAMPLE_NODES       */
+int rt_sample_states_draw_block(int64_t nnodes);
 /* weights f64[nsites] (copied to the device) or NULL = every site counts once           */
 int rt_sites_set_weights(rt_sites *sites, const double *weights);
 /* loglik f64[nsites] (-inf where status has RT_SITE_ZERO_PROB),

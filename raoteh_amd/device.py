@@ -25,7 +25,7 @@ from . import _lib
 from ._tree import TreeArrays
 
 __all__ = ['check_rate_sets', 'Context', 'get_context', 'TreeModel', 'SiteBatch', 'device_count', 'Posteriors',
-           'states_to_mask', 'BranchExpectations', 'check_branch_coefs']
+           'states_to_mask', 'BranchExpectations', 'check_branch_coefs', 'SampledStates']
 
 # At interpreter shutdown objects are finalised in arbitrary order (a model
 # after its context, say); the process is going away, so skip the native
@@ -92,6 +92,12 @@ Posteriors = collections.namedtuple(
 # [nnodes, ncoefs], both keyed by the edge's child in the preorder `nodes` (0 at the root),
 # status int32[nsites] as Posteriors
 BranchExpectations = collections.namedtuple('BranchExpectations', 'values edge_sums status nodes')
+
+
+# TreeModel.sample_states: states uint8[ndraws, nsites, nnodes] indexed by the preorder `nodes`
+# (255 = no state), status int32[nsites] (0 ok, 1 zero likelihood: the site's draws are all 255,
+# 2 a node without a state of positive weight)
+SampledStates = collections.namedtuple('SampledStates', 'states status nodes')
 
 
 def check_branch_coefs(coefs, nstates):
@@ -859,6 +865,45 @@ class TreeModel(object):
         if len(uniq) != len(mnodes):
             marg = marg[:, [uniq.index(v) for v in mnodes]]
         return Posteriors(node_values, edge_values, marg, status, nodes, mnodes)
+
+    def sample_states(self, batch, ndraws=1, seed=0, first_draw=0, recompute_transitions=False):
+        """rt_sites_sample_states: _sample_mcy_dense.resample_states
+        (_sample_mcy_dense.py:23-69) for every site of the resident batch, `ndraws` joint draws of
+        a state for every node from the posterior.  The uniform of draw d, site i, preorder node
+        v is _philox.philox_uniform(seed, first_draw + d, i * nnodes + v): draws [f, f + k) of one
+        call are draws [0, k) of a call with first_draw = f.  Returns a SampledStates tuple."""
+        ndraws, seed, first_draw = int(ndraws), int(seed), int(first_draw)
+        if ndraws < 1:
+            raise ValueError('ndraws must be at least 1')
+        if not (0 <= seed < 1 << 64 and 0 <= first_draw and first_draw + ndraws <= 1 << 64):
+            raise ValueError('seed and draw numbers are unsigned 64-bit integers')
+        n = self.nstates
+        ta = self.tree
+        N, S = ta.nnodes, batch.nsites
+        nodes = list(ta.preorder_nodes)
+        states = np.full((ndraws, S, N), 255, dtype=np.uint8)
+        status = np.zeros(S, dtype=np.int32)
+        if N == 1:
+            # one node: the root weights times the root's observation, on the host with the
+            # device's uniform and rule (the first state whose cumulative weight exceeds u * total)
+            from ._philox import philox_uniform
+            L = batch._root_likelihoods(n)
+            w = (L * (np.ones(n) if self._root_w is None else self._root_w)).clip(min=0)
+            cdf = np.cumsum(w, axis=1)
+            total = cdf[:, -1]
+            ok = (total > 0) & np.isfinite(total)
+            status[~ok] = _lib.RT_SITE_ZERO_PROB
+            d = np.arange(first_draw, first_draw + ndraws, dtype=np.uint64)
+            u = philox_uniform(seed, d[:, None], np.arange(S, dtype=np.uint64)[None, :])
+            for i in np.nonzero(ok)[0]:
+                pos = np.nonzero(w[i] > 0)[0]
+                k = np.searchsorted(cdf[i, pos], u[:, i] * total[i], side='right')
+                states[:, i, 0] = pos[np.minimum(k, len(pos) - 1)]
+            return SampledStates(states, status, nodes)
+        _lib.check(_lib.lib().rt_sites_sample_states(
+            self._h, batch._h, 1 if recompute_transitions else 0, seed, first_draw, ndraws,
+            _ptr(states, ctypes.c_ubyte), _ptr(status, c_int32)))
+        return SampledStates(states, status, nodes)
 
     def branch_expectations(self, batch, coefs, per_site=True, recompute_transitions=False):
         """rt_sites_branch_expectations: the reference's branch-site map
