@@ -500,6 +500,63 @@ int rt_sites_sample_states(rt_model *model, rt_sites *sites, int recompute_trans
 /* draws that share one read of L in rt_sites_sample_states for a tree of nnodes nodes (n > 4):
  * 16 at most, fewer as the tree grows, 1 from 1025 nodes on; 0 beyond RT_MAX_SAMPLE_NODES       */
 int rt_sample_states_draw_block(int64_t nnodes);
+/* Stochastic mappings (Nielsen 2002; the uniformization sampler of Hobolth & Stone 2009) of every
+ * branch for every site of a RESIDENT batch: ndraws independent, exact draws of a substitution
+ * history given the observations, each reduced on the device to the linear statistics of
+ * rt_sites_branch_expectations.  coefs f64[n_coefs][n][n], 1..RT_MAX_BRANCH_COEFS matrices E with
+ * the meaning they have there (E[c][d], c != d: the weight of one c -> d change; E[c][c]: the
+ * weight of a unit of time in c).  Arrays are keyed by the child's preorder index v of the edge,
+ * the root's slot is 0:
+ *   states[d][i][v]     uint8   the node states of draw d: exactly those of rt_sites_sample_states
+ *                               for the same (seed, first_draw, ndraws), bit for bit
+ *   values[d][i][v][c]  f64     the statistic c of the sampled path on the edge above v
+ *   counts[d][i][v][2]  int32   {uniformized events k, real changes} of that path
+ *   means[i][v][c]      f64     (sum_d values[d][i][v][c]) / ndraws, summed on the device in draw
+ *                               order: the same bits whether or not values is asked for
+ *   status[i]           int32   OR-ed over the draws: RT_SITE_ZERO_PROB and 2 as
+ *                               rt_sites_sample_states; 4: an edge whose event-count weights have
+ *                               no positive finite total
+ * Each output may be NULL; only those given cross PCIe.  The rule, per draw d, site i and edge
+ * above v with rate matrix Q_v and length t_v, the parent having drawn state a and v state b:
+ *   constants  mu = max_c(-Q_v[c][c]), R = I + Q_v / mu (R = I if mu = 0), lam = mu t_v (a lam
+ *              that is not positive counts as 0), K_v = ceil(lam + 10 sqrt(lam) + 20),
+ *              pois[0] = exp(-lam) (1 if lam = 0), pois[k] = pois[k-1] * lam / k.
+ *   uniforms   ub(j) = philox_uniform(seed, first_draw + d, 2^63 + (i * nnodes + v) * 2048 + j)
+ *              (the generator of rt_sites_sample_states; its node-state draws use indices below
+ *              2^63, so nsites * nnodes < 2^52 is required).
+ *   1. k among 0..K_v with weights pois[k] * (R^k)[a][b] and ub(0), by the pick rule of
+ *      rt_sites_sample_states: the first index with a positive weight whose cumulative weight
+ *      exceeds u * total, the last positive one if rounding leaves none.  lam = 0 gives k = 0.
+ *   2. x_0 = a, x_k = b and for i = 1 .. k-1 in turn x_i among the states c with weights
+ *      R[x_{i-1}][c] * (R^{k-i})[c][b] and ub(i), by the same rule (x_i = b if no weight is
+ *      positive, which only underflow can cause).
+ *   3. e_l = -log1p(-ub(1024 + l)), l = 0..k; the time spent in x_l is dt_l = t_v e_l / sum(e)
+ *      (normalised exponentials are the spacings of k sorted uniforms; if every e_l is 0 the
+ *      whole length is spent in x_0).
+ *   4. values[c] = sum_l E_c[x_l][x_l] dt_l + sum_{i : x_i != x_{i-1}} E_c[x_{i-1}][x_i],
+ *      counts = {k, the number of i with x_i != x_{i-1}}.
+ * (The kernels sum weights in chunks of four and scale the dwell sum once by t_v / sum(e): sums
+ * agree with sequential ones to rounding.)  A node without a state (255) has values and counts 0
+ * on the edge above it and on those below; so has an edge of status 4.  A draw depends on (seed,
+ * first_draw + d, site, node) and the numbers alone: draws [f, f + k) of one call equal a call
+ * with first_draw = f.  The mean over the draws converges to rt_sites_branch_expectations.
+ * Batches and trees: those of rt_sites_sample_states (2..128 states, every observation kind,
+ * per-edge rate matrices).  The rates must come from rt_model_set_rates: RT_ERR_INVALID for
+ * spectral rates or transitions set directly, as for ndraws < 1, no coefficient matrix, a batch
+ * of another model.  RT_ERR_UNSUPPORTED: what rt_sites_sample_states refuses, more than
+ * RT_MAX_BRANCH_COEFS matrices, more than 96 GB of scratch, an edge with K_v >
+ * RT_MAX_MAPPING_EVENTS (checked before anything is launched).  The per-draw outputs pass through
+ * the device in chunks: scratch grows with ndraws by the node states only.  Synchronous; the
+ * batch keeps its kernel, log-likelihoods, status and totals.                                  */
+#define RT_MAX_MAPPING_EVENTS 512
+int rt_sites_sample_mappings(rt_model *model, rt_sites *sites, int recompute_transitions,
+            uint64_t seed, uint64_t first_draw, int64_t ndraws,
+            int64_t n_coefs, const double *coefs /* f64[n_coefs][n][n] */,
+            uint8_t *states  /* [ndraws][nsites][nnodes] or NULL */,
+            double *values   /* [ndraws][nsites][nnodes][n_coefs] or NULL */,
+            int32_t *counts  /* [ndraws][nsites][nnodes][2] or NULL */,
+            double *means    /* [nsites][nnodes][n_coefs] or NULL */,
+            int32_t *status  /* [nsites] or NULL */);
 /* weights f64[nsites] (copied to the device) or NULL = every site counts once           */
 int rt_sites_set_weights(rt_sites *sites, const double *weights);
 /* loglik f64[nsites] (-inf where status has RT_SITE_ZERO_PROB),

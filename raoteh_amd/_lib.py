@@ -33,6 +33,7 @@ RT_SITE_NEGATIVE = 4
 RT_MAX_POSTERIOR_SETS = 8
 RT_MAX_BRANCH_COEFS = 8
 RT_MAX_SAMPLE_NODES = 8192
+RT_MAX_MAPPING_EVENTS = 512
 RT_MAX_EXPECT_STATES = 64
 RT_MAX_EXPECT_STEP_STATES = 128
 RT_MAX_RATE_SETS = 64
@@ -137,6 +138,9 @@ SIGNATURES = {
     'rt_sites_sample_states': (c_int, [c_void_p, c_void_p, c_int, ctypes.c_uint64,
                                        ctypes.c_uint64, c_int64, POINTER(c_ubyte), _p_i32]),
     'rt_sample_states_draw_block': (c_int, [c_int64]),
+    'rt_sites_sample_mappings': (c_int, [c_void_p, c_void_p, c_int, ctypes.c_uint64,
+                                         ctypes.c_uint64, c_int64, c_int64, _p_f64,
+                                         POINTER(c_ubyte), _p_f64, _p_i32, _p_f64, _p_i32]),
     'rt_sites_set_weights': (c_int, [c_void_p, _p_f64]),
     'rt_sites_destroy': (c_int, [c_void_p]),
     'rt_sites_device_bytes': (c_int64, [c_void_p]),

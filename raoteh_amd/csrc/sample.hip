@@ -303,60 +303,59 @@ extern "C" int rt_sample_states_draw_block(int64_t nnodes)
     return (int)std::min<int64_t>(SAMPLE_MAX_DB, std::max<int64_t>(1, db));
 }
 
-extern "C" int rt_sites_sample_states(rt_model *m, rt_sites *s, int recompute_transitions,
-                                      uint64_t seed, uint64_t first_draw, int64_t ndraws,
-                                      uint8_t *states, int32_t *status)
+// the checks and the scratch plan of the draws: offsets in `w` from the base the caller hands to
+// rt_sample_states_enqueue
+int rt_sample_states_plan(const char *who, rt_model *m, rt_sites *s, int64_t ndraws, rt_sample_work *w)
 {
-    RT_REQUIRE(m && s, "null pointer");
-    RT_REQUIRE(s->model == m, "the site batch belongs to another model");
-    RT_REQUIRE(ndraws >= 1, "ndraws must be at least 1");
-    RT_REQUIRE(states, "states is null");
     const int64_t n = m->n, N = m->nnodes, nsites = s->nsites;
     const bool lane = s->layout == RT_LAYOUT_LANE;
     if (s->rescale || N < 2 || n < 2 || n > RT_MAX_STATES || s->d_scratch ||
         m->max_depth > RT_FAST_MAX_DEPTH || lane != (n <= 4)) {
-        rt_set_error("rt_sites_sample_states: batches of 2..%d states without \"rescale\" on trees "
+        rt_set_error("%s: batches of 2..%d states without \"rescale\" on trees "
                      "of at least two nodes that the fast kernels take (n=%lld, nnodes=%lld, depth "
-                     "%d%s)", RT_MAX_STATES, (long long)n, (long long)N, m->max_depth,
+                     "%d%s)", who, RT_MAX_STATES, (long long)n, (long long)N, m->max_depth,
                      s->rescale ? ", rescale" : "");
         return RT_ERR_UNSUPPORTED;
     }
     if (!lane && N > RT_MAX_SAMPLE_NODES) {
-        rt_set_error("rt_sites_sample_states: trees of at most %d nodes (the sampled states of a "
-                     "wave live in LDS; %lld nodes here)", RT_MAX_SAMPLE_NODES, (long long)N);
+        rt_set_error("%s: trees of at most %d nodes (the sampled states of a "
+                     "wave live in LDS; %lld nodes here)", who, RT_MAX_SAMPLE_NODES, (long long)N);
         return RT_ERR_UNSUPPORTED;
     }
-    rt_ctx *ctx = m->ctx;
-    RT_HIP(hipSetDevice(ctx->device));
     const int NT = (int)((n + 15) / 16);
     const int nops = (int)s->ops.size();
     const size_t arr = lane ? (size_t)N * n * nsites * 8 : (size_t)nops * s->nblocks * NT * 256 * 8;
     post_plan plan;
-    const size_t o_L = plan.take(arr), o_M = plan.take(lane ? 8 : arr);
-    const size_t o_states = plan.take((size_t)ndraws * nsites * N);
-    const size_t o_status = plan.take((size_t)nsites * 4);
-    const size_t o_steps = plan.take((size_t)std::max<int64_t>(nops, N) * 16);
-    const size_t o_ptab = plan.take((size_t)3 * N * 4);
-    if ((double)plan.total > 96e9) {
-        rt_set_error("rt_sites_sample_states: this call needs %.0f GB of scratch; split the batch "
-                     "or the draws", (double)plan.total / 1e9);
-        return RT_ERR_UNSUPPORTED;
-    }
-    if (recompute_transitions) RT_TRY(rt_model_recompute_transitions(m));
-    RT_REQUIRE(m->have_P, "the model has no transition matrices yet");
+    w->o_L = plan.take(arr);
+    w->o_M = plan.take(lane ? 8 : arr);
+    w->o_states = plan.take((size_t)ndraws * nsites * N);
+    w->o_status = plan.take((size_t)nsites * 4);
+    w->o_steps = plan.take((size_t)std::max<int64_t>(nops, N) * 16);
+    w->o_ptab = plan.take((size_t)3 * N * 4);
+    w->bytes = plan.total;
+    return RT_OK;
+}
+
+// the upward pass and the draws on the context's stream: states [ndraws][nsites][nnodes] at
+// base + w->o_states, status (OR-ed over the draws) at base + w->o_status.  A batch of the
+// matrix-pipe layout has its interpreter twin (s->expect_twin) by now.
+int rt_sample_states_enqueue(rt_model *m, rt_sites *s, uint64_t seed, uint64_t first_draw,
+                             int64_t ndraws, unsigned char *base, rt_sample_work *w)
+{
+    const int64_t n = m->n, N = m->nnodes, nsites = s->nsites;
+    const bool lane = s->layout == RT_LAYOUT_LANE;
+    rt_ctx *ctx = m->ctx;
+    const int NT = (int)((n + 15) / 16);
+    const int nops = (int)s->ops.size();
     hipStream_t st = ctx->stream;
-    rt_sites *x = nullptr;
-    if (!lane) {
-        if (!s->expect_twin) RT_TRY(rt_sites_twin_interpreter(s, &s->expect_twin));
-        x = s->expect_twin;
-    }
-    RT_TRY(rt_scratch_reserve(ctx, plan.total));
-    unsigned char *base = ctx->d_scratch;
+    rt_sites *x = lane ? nullptr : s->expect_twin;
+    const size_t o_L = w->o_L, o_M = w->o_M, o_states = w->o_states, o_status = w->o_status;
+    const size_t o_steps = w->o_steps, o_ptab = w->o_ptab;
+    std::vector<int32_t> &table = w->table, &step_node = w->step_node;
     double *d_L = (double *)(base + o_L), *d_M = (double *)(base + o_M);
     unsigned char *d_states = base + o_states;
     int *d_status = (int *)(base + o_status);
     RT_HIP(hipMemsetAsync(d_status, 0, (size_t)nsites * 4, st));
-    std::vector<int32_t> table, step_node;       // (alive until the synchronisation below)
     std::vector<int> none((size_t)N, -1);
     if (lane) {
         post_lane_table(m, s, none.data(), &table);
@@ -424,6 +423,37 @@ extern "C" int rt_sites_sample_states(rt_model *m, rt_sites *s, int recompute_tr
 #undef RT_SAMPLE_DOWN
         RT_HIP(hipGetLastError());
     }
+    return RT_OK;
+}
+
+extern "C" int rt_sites_sample_states(rt_model *m, rt_sites *s, int recompute_transitions,
+                                      uint64_t seed, uint64_t first_draw, int64_t ndraws,
+                                      uint8_t *states, int32_t *status)
+{
+    RT_REQUIRE(m && s, "null pointer");
+    RT_REQUIRE(s->model == m, "the site batch belongs to another model");
+    RT_REQUIRE(ndraws >= 1, "ndraws must be at least 1");
+    RT_REQUIRE(states, "states is null");
+    const int64_t N = m->nnodes, nsites = s->nsites;
+    rt_sample_work work;                         // (its host buffers: alive until the synchronisation)
+    RT_TRY(rt_sample_states_plan("rt_sites_sample_states", m, s, ndraws, &work));
+    if ((double)work.bytes > 96e9) {
+        rt_set_error("rt_sites_sample_states: this call needs %.0f GB of scratch; split the batch "
+                     "or the draws", (double)work.bytes / 1e9);
+        return RT_ERR_UNSUPPORTED;
+    }
+    rt_ctx *ctx = m->ctx;
+    RT_HIP(hipSetDevice(ctx->device));
+    if (recompute_transitions) RT_TRY(rt_model_recompute_transitions(m));
+    RT_REQUIRE(m->have_P, "the model has no transition matrices yet");
+    hipStream_t st = ctx->stream;
+    if (s->layout != RT_LAYOUT_LANE && !s->expect_twin)
+        RT_TRY(rt_sites_twin_interpreter(s, &s->expect_twin));
+    RT_TRY(rt_scratch_reserve(ctx, work.bytes));
+    unsigned char *base = ctx->d_scratch;
+    RT_TRY(rt_sample_states_enqueue(m, s, seed, first_draw, ndraws, base, &work));
+    unsigned char *d_states = base + work.o_states;
+    int *d_status = (int *)(base + work.o_status);
     // only the draws and the status cross PCIe
     RT_HIP(hipMemcpyAsync(states, d_states, (size_t)ndraws * nsites * N, hipMemcpyDeviceToHost, st));
     if (status) RT_HIP(hipMemcpyAsync(status, d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));

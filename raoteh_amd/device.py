@@ -25,7 +25,7 @@ from . import _lib
 from ._tree import TreeArrays
 
 __all__ = ['check_rate_sets', 'Context', 'get_context', 'TreeModel', 'SiteBatch', 'device_count', 'Posteriors',
-           'states_to_mask', 'BranchExpectations', 'check_branch_coefs', 'SampledStates']
+           'states_to_mask', 'BranchExpectations', 'check_branch_coefs', 'SampledStates', 'SampledMappings']
 
 # At interpreter shutdown objects are finalised in arbitrary order (a model
 # after its context, say); the process is going away, so skip the native
@@ -98,6 +98,15 @@ BranchExpectations = collections.namedtuple('BranchExpectations', 'values edge_s
 # (255 = no state), status int32[nsites] (0 ok, 1 zero likelihood: the site's draws are all 255,
 # 2 a node without a state of positive weight)
 SampledStates = collections.namedtuple('SampledStates', 'states status nodes')
+
+
+# TreeModel.sample_mappings: states as SampledStates; values f64[ndraws, nsites, nnodes, ncoefs]
+# and counts int32[ndraws, nsites, nnodes, 2] = (uniformized events, real changes) of the sampled
+# path on the edge above each preorder node (None with per_draw=False), means
+# f64[nsites, nnodes, ncoefs] over the draws; status as SampledStates, 4: an edge whose
+# event-count weights have no positive total
+SampledMappings = collections.namedtuple('SampledMappings',
+                                         'states values counts means status nodes')
 
 
 def check_branch_coefs(coefs, nstates):
@@ -904,6 +913,44 @@ class TreeModel(object):
             self._h, batch._h, 1 if recompute_transitions else 0, seed, first_draw, ndraws,
             _ptr(states, ctypes.c_ubyte), _ptr(status, c_int32)))
         return SampledStates(states, status, nodes)
+
+    def sample_mappings(self, batch, coefs, ndraws=1, seed=0, first_draw=0, per_draw=True,
+                        recompute_transitions=False):
+        """rt_sites_sample_mappings: `ndraws` stochastic mappings of every site of the resident
+        batch: the node states of sample_states(batch, ndraws, seed, first_draw), then on every
+        branch an endpoint-conditioned path by uniformization with that edge's Q and t, reduced
+        to the statistics of branch_expectations: coefs is one (n, n) array E or up to 8 of them,
+        E[c, d] the weight of a c -> d change, E[c, c] of a unit of time in c.  Returns a
+        SampledMappings tuple; with per_draw=False values and counts are None (they never leave
+        the device) and only the means over the draws come back.  The means converge to
+        branch_expectations(batch, coefs).values.  The rates must have been set with set_rates."""
+        ndraws, seed, first_draw = int(ndraws), int(seed), int(first_draw)
+        if ndraws < 1:
+            raise ValueError('ndraws must be at least 1')
+        if not (0 <= seed < 1 << 64 and 0 <= first_draw and first_draw + ndraws <= 1 << 64):
+            raise ValueError('seed and draw numbers are unsigned 64-bit integers')
+        n = self.nstates
+        E = check_branch_coefs(coefs, n)
+        K = E.shape[0]
+        ta = self.tree
+        N, S = ta.nnodes, batch.nsites
+        nodes = list(ta.preorder_nodes)
+        values = np.zeros((ndraws, S, N, K)) if per_draw else None
+        counts = np.zeros((ndraws, S, N, 2), dtype=np.int32) if per_draw else None
+        means = np.zeros((S, N, K))
+        if N == 1:
+            # one node, no edges: the states as sample_states draws them, nothing else
+            got = self.sample_states(batch, ndraws=ndraws, seed=seed, first_draw=first_draw)
+            return SampledMappings(got.states, values, counts, means, got.status, nodes)
+        states = np.full((ndraws, S, N), 255, dtype=np.uint8)
+        status = np.zeros(S, dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_sample_mappings(
+            self._h, batch._h, 1 if recompute_transitions else 0, seed, first_draw, ndraws, K,
+            _ptr(E, c_double), _ptr(states, ctypes.c_ubyte),
+            None if values is None else _ptr(values, c_double),
+            None if counts is None else _ptr(counts, c_int32), _ptr(means, c_double),
+            _ptr(status, c_int32)))
+        return SampledMappings(states, values, counts, means, status, nodes)
 
     def branch_expectations(self, batch, coefs, per_site=True, recompute_transitions=False):
         """rt_sites_branch_expectations: the reference's branch-site map
