@@ -18,7 +18,8 @@
 //      per step and k one more n x n by n x 16 matrix-pipe product from the u already staged in
 //      LDS, reduced over the states in a fixed order.  D is formed at internal nodes only (a
 //      leaf's D has no reader).
-//      n <= 4: be_lane_kernel, one lane per site (post_lane_kernel's twin);
+//      n <= 4: be_lane_kernel, one lane per site (the upward pass, the root and u are
+//      post_lane_kernel's: post_common.h);
 //   3. edge_sums_kernel: the site-weighted sums per (node, k) in a fixed order.
 //
 // Nothing of the batch is written: its own pruning kernel, log-likelihoods, status and totals
@@ -68,13 +69,11 @@ be_down_kernel(const double *__restrict__ PfragT, const double *__restrict__ Gfr
     const long blk = blockIdx.x;
     const long site = blk * 16 + (lane & 15);
     const bool site_ok = site < nsites;
-    const size_t tile_stride = (size_t)NT * 256;
-    auto at = [&](int step) { return ((size_t)step * nblocks + blk) * tile_stride + (m * 4) * 64 + lane; };
     bool bad = false;
     // root: D = w L / sum_states(w L); its slot of the output is 0
     {
         const int i = nops - 1;
-        const size_t o = at(i);
+        const size_t o = down_at<NT>(i, nblocks, blk, m, lane);
         double wl[4], s = 0.0;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -83,13 +82,9 @@ be_down_kernel(const double *__restrict__ PfragT, const double *__restrict__ Gfr
             wl[r] = w * Larr[o + r * 64];
             s += wl[r];
         }
-        s += __shfl_xor(s, 16, 64);
-        s += __shfl_xor(s, 32, 64);
-        if (lane < 16) red[m][lane] = s;
+        down_part(red, m, lane, s);
         __syncthreads();
-        double tot = 0.0;
-#pragma unroll
-        for (int mm = 0; mm < NT; ++mm) tot += red[mm][lane & 15];
+        const double tot = down_total<NT>(red, lane & 15);
         const bool zero = !(tot > 0.0);
 #pragma unroll
         for (int r = 0; r < 4; ++r) Darr[o + r * 64] = zero ? 0.0 : wl[r] / tot;
@@ -100,84 +95,34 @@ be_down_kernel(const double *__restrict__ PfragT, const double *__restrict__ Gfr
     }
     const size_t frag = ((size_t)m * KP * 64 + lane) * 2;
     constexpr size_t ASTRIDE = (size_t)NT * KP * 128;
-    // observation pairs holding this wave's own rows 4m..4m+3: q = 2m, 2m+1 (prune.hip)
     const double *og = obs + (size_t)blk * K * (KP * 128) + lane * 2;
     for (int i = nops - 2; i >= 0; --i) {
         const int4 st = steps[i];
-        const size_t o = at(i), po = at(st.y);
+        const size_t o = down_at<NT>(i, nblocks, blk, m, lane);
         double L[4], u[4];
-        if (st.z >= 0) {                         // an observed leaf: L is its observation
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int q = 2 * m + h;
-                double2 v = {0.0, 0.0};
-                if (q < KP) v = *(const double2 *)(og + ((size_t)st.z * KP + q) * 128);
-                L[2 * h] = v.x;
-                L[2 * h + 1] = v.y;
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) L[r] = Larr[o + r * 64];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const double dp = Darr[po + r * 64];
-            const double den = Marr[o + r * 64];
-            u[r] = 0.0;
-            if (dp != 0.0) {
-                if (den > 0.0) u[r] = dp / den;
-                else bad = true;
-            }
-        }
-        __syncthreads();                         // every wave is done with the previous operands
-#pragma unroll
-        for (int r = 0; r < 4; ++r) xb[(4 * m + r) * 64 + lane] = u[r];
-        __syncthreads();
+        down_L<KP>(st.z, og, Larr, o, m, L);
+        down_u(Darr, down_at<NT>(st.y, nblocks, blk, m, lane), Marr, o, u, bad);
+        down_stage(xb, m, lane, u);
         double a[2 * KP];
         if (st.w) {                              // D_v = (P^T u) * L for the children's steps
-            const double *ag = PfragT + (size_t)i * ASTRIDE + frag;
-#pragma unroll
-            for (int q = 0; q < KP; ++q) {
-                const double2 v = *(const double2 *)(ag + q * 128);
-                a[2 * q] = v.x;
-                a[2 * q + 1] = v.y;
-            }
-            double4_t acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk)
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], xb[kk * 64 + lane], acc, 0, 0, 0);
+            down_frag<KP>(PfragT + (size_t)i * ASTRIDE + frag, a);
+            const double4_t acc = down_product<KS>(a, xb, lane);
 #pragma unroll
             for (int r = 0; r < 4; ++r) Darr[o + r * 64] = acc[r] * L[r];
         }
         // per coefficient matrix: sum_b L[b] (G_k^T u)[b], one fragment table live at a time
         for (int k = 0; k < nk; ++k) {
-            const double *gg = GfragT + ((size_t)k * nops + i) * ASTRIDE + frag;
-#pragma unroll
-            for (int q = 0; q < KP; ++q) {
-                const double2 v = *(const double2 *)(gg + q * 128);
-                a[2 * q] = v.x;
-                a[2 * q + 1] = v.y;
-            }
-            double4_t y = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk)
-                y = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], xb[kk * 64 + lane], y, 0, 0, 0);
+            down_frag<KP>(GfragT + ((size_t)k * nops + i) * ASTRIDE + frag, a);
+            const double4_t y = down_product<KS>(a, xb, lane);
             double v = 0.0;
 #pragma unroll
             for (int r = 0; r < 4; ++r) v += y[r] * L[r];
-            // own rows, the four lane groups, then (below) the waves in order
-            v += __shfl_xor(v, 16, 64);
-            v += __shfl_xor(v, 32, 64);
-            if (lane < 16) sums[k][m][lane] = v;
+            down_part(sums[k], m, lane, v);      // (then, below, the waves in order)
         }
         __syncthreads();
         if (m == 0 && lane < 16 && site_ok)
-            for (int k = 0; k < nk; ++k) {
-                double t = 0.0;
-#pragma unroll
-                for (int mm = 0; mm < NT; ++mm) t += sums[k][mm][lane];
-                out[((size_t)site * nnodes + st.x) * nk + k] = t;
-            }
+            for (int k = 0; k < nk; ++k)
+                out[((size_t)site * nnodes + st.x) * nk + k] = down_total<NT>(sums[k], lane);
     }
     if (bad && site_ok) atomicOr(&status[site], 2);
 }
@@ -195,44 +140,11 @@ be_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const doub
     const long site = (long)blockIdx.x * 256 + threadIdx.x;
     if (site >= nsites) return;
     auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
-    // up: L_v = observation, times the messages of the children (descending preorder index)
-    for (int v = 0; v < nnodes; ++v) {
-        double x[N];
-        const int k = node_k[v];
-        if (k >= 0) lane_obs<N>(obs, compact, K, block_sites, site, k, x);
-        else
-#pragma unroll
-            for (int s = 0; s < N; ++s) x[s] = 1.0;
-#pragma unroll
-        for (int s = 0; s < N; ++s) Larr[idx(v, s)] = x[s];
-    }
-    for (int v = nnodes - 1; v >= 1; --v) {
-        double x[N];
-#pragma unroll
-        for (int s = 0; s < N; ++s) x[s] = Larr[idx(v, s)];
-        const double *Pv = P + (size_t)v * N * N;
-        const int p = parent[v];
-#pragma unroll
-        for (int a = 0; a < N; ++a) {
-            double t = 0.0;
-#pragma unroll
-            for (int b = 0; b < N; ++b) t += Pv[a * N + b] * x[b];
-            Marr[idx(v, a)] = t;
-            Larr[idx(p, a)] *= t;
-        }
-    }
+    lane_up<N, true>(nnodes, nsites, site, P, parent, node_k, obs, compact, K, block_sites, Larr, Marr);
     // down: the root, then every node after its parent
     {
-        double wl[N], tot = 0.0;
-#pragma unroll
-        for (int s = 0; s < N; ++s) {
-            wl[s] = (root_w ? root_w[s] : 1.0) * Larr[idx(0, s)];
-            tot += wl[s];
-        }
-        const bool zero = !(tot > 0.0);
-#pragma unroll
-        for (int s = 0; s < N; ++s) Darr[idx(0, s)] = zero ? 0.0 : wl[s] / tot;
-        if (zero) status[site] |= RT_SITE_ZERO_PROB;
+        double d[N];
+        if (lane_root<N>(nsites, site, root_w, Larr, Darr, d)) status[site] |= RT_SITE_ZERO_PROB;
         for (int k = 0; k < nk; ++k) out[(size_t)site * nnodes * nk + k] = 0.0;
     }
     bool bad = false;
@@ -240,16 +152,7 @@ be_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const doub
         const int p = parent[v];
         const double *Pv = P + (size_t)v * N * N;
         double u[N], L[N];
-#pragma unroll
-        for (int a = 0; a < N; ++a) {
-            const double dp = Darr[idx(p, a)];
-            const double den = Marr[idx(v, a)];
-            u[a] = 0.0;
-            if (dp != 0.0) {
-                if (den > 0.0) u[a] = dp / den;
-                else bad = true;
-            }
-        }
+        lane_u<N>(nsites, site, p, v, Darr, Marr, u, bad);
 #pragma unroll
         for (int b = 0; b < N; ++b) {
             L[b] = Larr[idx(v, b)];
@@ -303,27 +206,14 @@ edge_sums_kernel(int nnodes, int nk, long nsites, const double *__restrict__ val
     if (tid < nk) sums[(size_t)v * nk + tid] = part[tid][0];
 }
 
-template <int NT, int KS>
-int launch_down(rt_ctx *ctx, const double *d_PT, const double *d_GT, int nk, int nops,
-                const int4 *d_steps, const double *d_L, const double *d_M, double *d_D,
-                const rt_sites *x, const double *d_root, int n, int nnodes, double *d_out, int *d_status)
-{
-    hipLaunchKernelGGL((be_down_kernel<NT, KS>), dim3((unsigned)x->nblocks), dim3(64 * NT), 0, ctx->stream,
-                       d_PT, d_GT, nk, nops, d_steps, d_L, d_M, d_D, (const double *)x->d_obs,
-                       (int)x->nobs, d_root, n, nnodes, d_out, d_status, (long)x->nsites,
-                       (long)x->nblocks);
-    RT_HIP(hipGetLastError());
-    return RT_OK;
-}
-
 }  // namespace
 
 extern "C" int rt_sites_branch_expectations(rt_model *m, rt_sites *s, int recompute_transitions,
                                             int64_t n_coefs, const double *coefs, double *values,
                                             double *edge_sums, int32_t *status)
 {
-    RT_REQUIRE(m && s, "null pointer");
-    RT_REQUIRE(s->model == m, "the site batch belongs to another model");
+    post_pass p;                                 // (alive until the synchronisation below)
+    RT_TRY(post_open(&p, "rt_sites_branch_expectations", m, s));
     RT_REQUIRE(n_coefs >= 1 && coefs, "at least one coefficient matrix is needed");
     RT_REQUIRE(m->d_Q && !m->spectral,
                "rt_sites_branch_expectations: rt_model_set_rates has not been called (the "
@@ -334,37 +224,21 @@ extern "C" int rt_sites_branch_expectations(rt_model *m, rt_sites *s, int recomp
                      RT_MAX_BRANCH_COEFS, (long long)n_coefs);
         return RT_ERR_UNSUPPORTED;
     }
-    const int64_t n = m->n, N = m->nnodes, nsites = s->nsites;
-    const bool lane = s->layout == RT_LAYOUT_LANE;
-    if (s->rescale || N < 2 || n < 2 || n > RT_MAX_STATES || s->d_scratch ||
-        m->max_depth > RT_FAST_MAX_DEPTH || lane != (n <= 4)) {
-        rt_set_error("rt_sites_branch_expectations: batches of 2..%d states without \"rescale\" on "
-                     "trees of at least two nodes that the fast kernels take (n=%lld, nnodes=%lld, "
-                     "depth %d%s)", RT_MAX_STATES, (long long)n, (long long)N, m->max_depth,
-                     s->rescale ? ", rescale" : "");
-        return RT_ERR_UNSUPPORTED;
-    }
+    const int64_t n = p.n, N = p.N, nsites = p.nsites;
+    RT_TRY(post_layout(&p, true));
     const size_t nn = (size_t)n * n, ne = (size_t)(N - 1);
     const int nk = (int)n_coefs;
     for (size_t j = 0; j < (size_t)nk * nn; ++j)
         RT_REQUIRE(std::isfinite(coefs[j]), "coefficient %lld of matrix %lld is not finite",
                    (long long)(j % nn), (long long)(j / nn));
-    rt_ctx *ctx = m->ctx;
-    RT_HIP(hipSetDevice(ctx->device));
-    const int NT = (int)((n + 15) / 16), KS = (int)((n + 3) / 4), KP = (KS + 1) / 2;
-    const int nops = (int)s->ops.size();
+    rt_ctx *ctx = p.ctx;
     const bool wide = 2 * n > RT_MAX_EXPM_STATES;
-    // scratch: L, M, D of every node and site, the values, the derivative route's buffers, the
-    // derivative tables and their fragments
-    const size_t arr = lane ? (size_t)N * n * nsites * 8 : (size_t)nops * s->nblocks * NT * 256 * 8;
-    const size_t tab = (size_t)nops * NT * KP * 128 * 8;
-    post_plan plan;
-    const size_t o_L = plan.take(arr), o_M = plan.take(arr), o_D = plan.take(arr);
+    // scratch: L, M, D of every node and site (post_layout), the values, the derivative route's
+    // buffers, the derivative tables and their fragments
+    const size_t tab = (size_t)p.nops * p.NT * p.KP * 128 * 8;
+    post_plan &plan = p.plan;
     const size_t o_val = plan.take((size_t)nsites * N * nk * 8);
     const size_t o_sum = plan.take((size_t)N * nk * 8);
-    const size_t o_status = plan.take((size_t)nsites * 4);
-    const size_t o_steps = plan.take((size_t)std::max<int64_t>(nops, N) * 16);
-    const size_t o_ptab = plan.take((size_t)3 * N * 4);
     const size_t o_E = plan.take((size_t)nk * nn * 8);
     const size_t o_G = plan.take((size_t)nk * N * nn * 8);
     const size_t o_W = plan.take(ne * nn * 8);
@@ -372,33 +246,18 @@ extern "C" int rt_sites_branch_expectations(rt_model *m, rt_sites *s, int recomp
                             : plan.take(ne * 4 * nn * 8);
     const size_t o_X = wide ? plan.take(8) : plan.take(ne * 4 * nn * 8);
     const size_t o_scale = plan.take(ne * 8), o_ones = plan.take(ne * 8), o_ident = plan.take(ne * 4);
-    const size_t o_PT = lane ? plan.take(8) : plan.take(tab);
-    const size_t o_GT = lane ? plan.take(8) : plan.take((size_t)nk * tab);
-    if ((double)plan.total > 96e9) {
-        rt_set_error("rt_sites_branch_expectations: this batch needs %.0f GB of scratch; split the "
-                     "batch", (double)plan.total / 1e9);
-        return RT_ERR_UNSUPPORTED;
-    }
-    if (recompute_transitions) RT_TRY(rt_model_recompute_transitions(m));
-    RT_REQUIRE(m->have_P, "the model has no transition matrices yet");
-    hipStream_t st = ctx->stream;
-    rt_sites *x = nullptr;
-    if (!lane) {
-        if (!s->expect_twin) RT_TRY(rt_sites_twin_interpreter(s, &s->expect_twin));
-        x = s->expect_twin;
-    }
-    RT_TRY(rt_scratch_reserve(ctx, plan.total));
-    unsigned char *base = ctx->d_scratch;
-    double *d_L = (double *)(base + o_L), *d_M = (double *)(base + o_M), *d_D = (double *)(base + o_D);
+    const size_t o_GT = p.lane ? plan.take(8) : plan.take((size_t)nk * tab);
+    RT_TRY(post_begin(&p, recompute_transitions));
+    hipStream_t st = p.st;
+    unsigned char *base = p.base;
     double *d_val = (double *)(base + o_val), *d_sum = (double *)(base + o_sum);
     double *d_E = (double *)(base + o_E), *d_G = (double *)(base + o_G), *d_W = (double *)(base + o_W);
     double *d_B = (double *)(base + o_B), *d_X = (double *)(base + o_X);
     double *d_scale = (double *)(base + o_scale), *d_ones = (double *)(base + o_ones);
-    int *d_ident = (int *)(base + o_ident), *d_status = (int *)(base + o_status);
-    RT_HIP(hipMemsetAsync(d_status, 0, (size_t)nsites * 4, st));
+    int *d_ident = (int *)(base + o_ident), *d_status = p.d_status;
     // (host buffers of the asynchronous copies: alive until the synchronisation below)
     std::vector<double> ones(ne, 1.0);
-    std::vector<int32_t> ident(ne), table, step_node, internal((size_t)N, 0);
+    std::vector<int32_t> ident(ne), internal((size_t)N, 0);
     for (size_t e = 0; e < ne; ++e) ident[e] = (int32_t)e;
     for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
     RT_HIP(hipMemcpyAsync(d_E, coefs, (size_t)nk * nn * 8, hipMemcpyHostToDevice, st));
@@ -423,59 +282,34 @@ extern "C" int rt_sites_branch_expectations(rt_model *m, rt_sites *s, int recomp
             RT_TRY(rt_frechet_extract_device(ctx, n, N - 1, m->d_t + 1, d_X, d_scale, Gk + nn));
         }
     }
-    if (lane) {
-        post_lane_table(m, s, internal.data(), &table);
-        int *d_tab = (int *)(base + o_ptab);
-        RT_HIP(hipMemcpyAsync(d_tab, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
-        const unsigned grid = (unsigned)((nsites + 255) / 256);
-#define RT_BE_LANE(NV)                                                                              \
-        hipLaunchKernelGGL((be_lane_kernel<NV>), dim3(grid), dim3(256), 0, st, (int)N, (long)nsites,     \
-                           (const double *)m->d_P, (const double *)d_G, nk, d_tab, d_tab + N,           \
-                           (const void *)s->d_obs, s->compact_states, (int)s->nobs, s->block_sites,     \
-                           (const double *)m->d_root, d_L, d_M, d_D, d_val, d_status)
-        switch ((int)n) {
-        case 2: RT_BE_LANE(2); break;
-        case 3: RT_BE_LANE(3); break;
-        default: RT_BE_LANE(4); break;
-        }
-#undef RT_BE_LANE
-        RT_HIP(hipGetLastError());
+    RT_TRY(post_up(&p, internal.data(), true));
+    if (p.lane) {
+        const int *d_tab = p.d_ptab;
+        RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
+            hipLaunchKernelGGL((be_lane_kernel<decltype(nv)::value>), dim3((unsigned)((nsites + 255) / 256)),
+                               dim3(256), 0, st, (int)N, (long)nsites, (const double *)m->d_P,
+                               (const double *)d_G, nk, d_tab, d_tab + N, (const void *)s->d_obs,
+                               s->compact_states, (int)s->nobs, s->block_sites,
+                               (const double *)m->d_root, p.d_L, p.d_M, p.d_D, d_val, d_status);
+            return RT_OK;
+        }));
     } else {
-        RT_TRY(post_step_table(m, x, internal.data(), &table, &step_node));
-        int4 *d_steps = (int4 *)(base + o_steps);
-        double *d_PT = (double *)(base + o_PT), *d_GT = (double *)(base + o_GT);
-        int *d_step_node = (int *)(base + o_ptab);
-        RT_HIP(hipMemcpyAsync(d_steps, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
-        RT_HIP(hipMemcpyAsync(d_step_node, step_node.data(), (size_t)nops * 4, hipMemcpyHostToDevice, st));
-        // upward pass: the split-M interpreter kernel with L and M of every step stored (its own
-        // log-likelihoods and totals are the twin's, not the batch's)
-        x->d_Lout = d_L;
-        x->d_Mout = d_M;
-        const int rc = rt_launch_prune(m, x, false);
-        x->d_Lout = x->d_Mout = nullptr;
-        RT_TRY(rc);
-        RT_TRY(rt_launch_pack_pt(ctx, (int)n, NT, KP, nops, d_step_node, m->d_P, d_PT));
+        const rt_sites *x = p.x;
+        double *d_GT = (double *)(base + o_GT);
         for (int k = 0; k < nk; ++k)
-            RT_TRY(rt_launch_pack_pt(ctx, (int)n, NT, KP, nops, d_step_node, d_G + (size_t)k * N * nn,
+            RT_TRY(rt_launch_pack_pt(ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab, d_G + (size_t)k * N * nn,
                                      d_GT + (size_t)k * (tab / 8)));
-        int lrc = RT_ERR_UNSUPPORTED;
-#define RT_BD(NTV, KSV)                                                                               \
-        case KSV: lrc = launch_down<NTV, KSV>(ctx, d_PT, d_GT, nk, nops, d_steps, d_L, d_M, d_D, x,   \
-                                              m->d_root, (int)n, (int)N, d_val, d_status); break
-        switch (KS) {
-        RT_BD(1, 2); RT_BD(1, 3); RT_BD(1, 4);
-        RT_BD(2, 5); RT_BD(2, 6); RT_BD(2, 7); RT_BD(2, 8);
-        RT_BD(3, 9); RT_BD(3, 10); RT_BD(3, 11); RT_BD(3, 12);
-        RT_BD(4, 13); RT_BD(4, 14); RT_BD(4, 15); RT_BD(4, 16);
-        RT_BD(5, 17); RT_BD(5, 18); RT_BD(5, 19); RT_BD(5, 20);
-        RT_BD(6, 21); RT_BD(6, 22); RT_BD(6, 23); RT_BD(6, 24);
-        RT_BD(7, 25); RT_BD(7, 26); RT_BD(7, 27); RT_BD(7, 28);
-        RT_BD(8, 29); RT_BD(8, 30); RT_BD(8, 31); RT_BD(8, 32);
-        default: break;
-        }
-#undef RT_BD
-        RT_TRY(lrc);
+        RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
+            constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
+            hipLaunchKernelGGL((be_down_kernel<NT, KS>), dim3((unsigned)x->nblocks), dim3(64 * NT), 0, st,
+                               (const double *)p.d_PT, (const double *)d_GT, nk, p.nops,
+                               (const int4 *)p.d_steps, (const double *)p.d_L, (const double *)p.d_M,
+                               p.d_D, (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
+                               (int)n, (int)N, d_val, d_status, (long)x->nsites, (long)x->nblocks);
+            return RT_OK;
+        }));
     }
+    RT_HIP(hipGetLastError());
     // 3. the weighted site sums, whether or not the per-site array is returned
     if (edge_sums) {
         hipLaunchKernelGGL(edge_sums_kernel, dim3((unsigned)N), dim3(256), 0, st, (int)N, nk, (long)nsites,

@@ -37,9 +37,9 @@ void rt_set_error(const char *fmt, ...);
         }                                                                     \
     } while (0)
 
-#define RT_TRY(call)                                                          \
+#define RT_TRY(...)                                                           \
     do {                                                                      \
-        int rc_ = (call);                                                     \
+        int rc_ = (__VA_ARGS__);                                              \
         if (rc_ != RT_OK) return rc_;                                         \
     } while (0)
 
@@ -529,20 +529,6 @@ int rt_launch_pack_pt(rt_ctx *ctx, int n, int NT, int KP, int nops, const int *d
 int rt_sites_twin_interpreter(rt_sites *src, rt_sites **out);
 // the context's grow-only device scratch (ctx->d_scratch) holds at least `bytes` afterwards
 int rt_scratch_reserve(rt_ctx *ctx, size_t bytes);
-// sample.hip: the device part of rt_sites_sample_states for a caller that goes on with the draws
-// on the device (mapping.hip).  rt_sample_states_plan makes the checks of that call (errors name
-// `who`) and lays its scratch out from offset 0; rt_sample_states_enqueue runs the upward pass and
-// the draws on the context's stream and leaves states [ndraws][nsites][nnodes] at base + o_states
-// and the status at base + o_status.  The host buffers in `w` feed asynchronous copies: `w` lives
-// until the stream is synchronised.
-struct rt_sample_work {
-    size_t bytes = 0;
-    size_t o_L = 0, o_M = 0, o_states = 0, o_status = 0, o_steps = 0, o_ptab = 0;
-    std::vector<int32_t> table, step_node;
-};
-int rt_sample_states_plan(const char *who, rt_model *m, rt_sites *s, int64_t ndraws, rt_sample_work *w);
-int rt_sample_states_enqueue(rt_model *m, rt_sites *s, uint64_t seed, uint64_t first_draw,
-                             int64_t ndraws, unsigned char *base, rt_sample_work *w);
 // expectation path on the matrix pipe (expect_mfma.hip); RT_ERR_UNSUPPORTED = not this case
 int rt_expectation_weights_mfma(rt_ctx *ctx, int64_t nnodes, int64_t n, int64_t nsites,
                                 const int64_t *idx, const int64_t *ptr, const double *esd,

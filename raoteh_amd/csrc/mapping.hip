@@ -453,8 +453,8 @@ extern "C" int rt_sites_sample_mappings(rt_model *m, rt_sites *s, int recompute_
                                         int32_t *status)
 {
     static const char who[] = "rt_sites_sample_mappings";
-    RT_REQUIRE(m && s, "null pointer");
-    RT_REQUIRE(s->model == m, "the site batch belongs to another model");
+    post_pass p;                                 // (host buffers: alive until the synchronisation)
+    RT_TRY(post_open(&p, who, m, s));
     RT_REQUIRE(ndraws >= 1, "ndraws must be at least 1");
     RT_REQUIRE(n_coefs >= 1 && coefs, "at least one coefficient matrix is needed");
     RT_REQUIRE(m->d_Q && !m->spectral,
@@ -466,20 +466,19 @@ extern "C" int rt_sites_sample_mappings(rt_model *m, rt_sites *s, int recompute_
                      (long long)n_coefs);
         return RT_ERR_UNSUPPORTED;
     }
-    const int64_t n = m->n, N = m->nnodes, nsites = s->nsites;
-    rt_sample_work work;                         // (host buffers: alive until the synchronisation)
-    RT_TRY(rt_sample_states_plan(who, m, s, ndraws, &work));
+    const int64_t n = p.n, N = p.N, nsites = p.nsites;
+    size_t o_states = 0;
+    RT_TRY(rt_sample_states_plan(&p, ndraws, &o_states));
     RT_REQUIRE((double)nsites * (double)N < 4503599627370496.0,
                "nsites * nnodes must be below 2^52 (the counters of the branch uniforms)");
-    const bool lane = s->layout == RT_LAYOUT_LANE;
+    const bool lane = p.lane;
     const size_t nn = (size_t)n * n;
     const int nk = (int)n_coefs;
     for (size_t j = 0; j < (size_t)nk * nn; ++j)
         RT_REQUIRE(std::isfinite(coefs[j]), "coefficient %lld of matrix %lld is not finite",
                    (long long)(j % nn), (long long)(j / nn));
-    rt_ctx *ctx = m->ctx;
-    RT_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
+    RT_HIP(hipSetDevice(p.ctx->device));
+    hipStream_t st = p.st;
     // the uniformization rate of every rate matrix in use and the event bound of every edge,
     // before anything is launched
     RT_REQUIRE((int64_t)m->h_qidx.size() == N && (int64_t)m->h_t.size() == N, "the model has no rates");
@@ -533,8 +532,7 @@ extern "C" int rt_sites_sample_mappings(rt_model *m, rt_sites *s, int recompute_
     CH = std::max<int64_t>(1, std::min<int64_t>(CH, (((int64_t)1 << 31) - 1) / per_draw_wgs));
     RT_REQUIRE((int64_t)((size_t)nsites * N * nk + 255) / 256 < (int64_t)1 << 31,
                "too many sites for one call");
-    post_plan plan;
-    plan.total = work.bytes;
+    post_plan &plan = p.plan;
     const size_t o_mu = plan.take((size_t)nq * 8), o_powoff = plan.take((size_t)nq * 8);
     const size_t o_Kq = plan.take((size_t)nq * 4), o_eK = plan.take((size_t)N * 4);
     const size_t o_parent = plan.take((size_t)N * 4);
@@ -544,16 +542,8 @@ extern "C" int rt_sites_sample_mappings(rt_model *m, rt_sites *s, int recompute_
     const size_t o_val = plan.take((size_t)CH * cells * 8);
     const size_t o_cnt = plan.take(counts ? (size_t)CH * nsites * N * 8 : 8);
     const size_t o_means = plan.take(cells * 8);
-    if ((double)plan.total > 96e9) {
-        rt_set_error("%s: this call needs %.0f GB of scratch; split the batch or the draws", who,
-                     (double)plan.total / 1e9);
-        return RT_ERR_UNSUPPORTED;
-    }
-    if (recompute_transitions) RT_TRY(rt_model_recompute_transitions(m));
-    RT_REQUIRE(m->have_P, "the model has no transition matrices yet");
-    if (!lane && !s->expect_twin) RT_TRY(rt_sites_twin_interpreter(s, &s->expect_twin));
-    RT_TRY(rt_scratch_reserve(ctx, plan.total));
-    unsigned char *base = ctx->d_scratch;
+    RT_TRY(post_begin(&p, recompute_transitions, true));
+    unsigned char *base = p.base;
     double *d_mu = (double *)(base + o_mu), *d_R = (double *)(base + o_R), *d_T = (double *)(base + o_T);
     double *d_pois = (double *)(base + o_pois), *d_E = (double *)(base + o_E);
     double *d_val = (double *)(base + o_val), *d_means = (double *)(base + o_means);
@@ -580,43 +570,33 @@ extern "C" int rt_sites_sample_mappings(rt_model *m, rt_sites *s, int recompute_
         RT_HIP(hipGetLastError());
     }
     // 2. the node states: rt_sites_sample_states' own draws, left in scratch
-    RT_TRY(rt_sample_states_enqueue(m, s, seed, first_draw, ndraws, base, &work));
-    const unsigned char *d_states = base + work.o_states;
-    int *d_status = (int *)(base + work.o_status);
+    unsigned char *d_states = base + o_states;
+    RT_TRY(rt_sample_states_enqueue(&p, seed, first_draw, ndraws, d_states));
+    int *d_status = p.d_status;
     // 3. the paths, chunk by chunk
     map_tables tb;
     tb.parent = d_parent; tb.qidx = m->d_qidx; tb.eK = d_eK; tb.t = m->d_t; tb.powoff = d_powoff;
     tb.R = d_R; tb.T = d_T; tb.pois = d_pois; tb.E = d_E; tb.KS = KS; tb.nk = nk;
-    const int NT = (int)((n + 15) / 16);
     for (int64_t d0 = 0; d0 < ndraws; d0 += CH) {
         const int64_t nd = std::min<int64_t>(CH, ndraws - d0);
         if (lane) {
             const unsigned grid = (unsigned)((nsites * nd + 255) / 256);
-#define RT_MAP_LANE(NV)                                                                             \
-            hipLaunchKernelGGL((map_lane_kernel<NV>), dim3(grid), dim3(256), 0, st, tb, (int)N,         \
-                               (long)nsites, (long)nd, (unsigned long long)seed,                        \
-                               (unsigned long long)first_draw, (long)d0, d_states, d_val, d_cnt, d_status)
-            switch ((int)n) {
-            case 2: RT_MAP_LANE(2); break;
-            case 3: RT_MAP_LANE(3); break;
-            default: RT_MAP_LANE(4); break;
-            }
-#undef RT_MAP_LANE
+            RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
+                hipLaunchKernelGGL((map_lane_kernel<decltype(nv)::value>), dim3(grid), dim3(256), 0, st, tb,
+                                   (int)N, (long)nsites, (long)nd, (unsigned long long)seed,
+                                   (unsigned long long)first_draw, (long)d0,
+                                   (const unsigned char *)d_states, d_val, d_cnt, d_status);
+                return RT_OK;
+            }));
         } else {
             const unsigned grid = (unsigned)(tiles * nd);
-#define RT_MAP_PATH(NTV)                                                                            \
-            case NTV:                                                                               \
-                hipLaunchKernelGGL((map_path_kernel<NTV>), dim3(grid), dim3(64), 0, st, tb, (int)n,     \
-                                   (int)N, (long)nsites, (long)tiles, (unsigned long long)seed,         \
-                                   (unsigned long long)first_draw, (long)d0, d_states, d_val, d_cnt,    \
-                                   d_status);                                                       \
-                break
-            switch (NT) {
-            RT_MAP_PATH(1); RT_MAP_PATH(2); RT_MAP_PATH(3); RT_MAP_PATH(4);
-            RT_MAP_PATH(5); RT_MAP_PATH(6); RT_MAP_PATH(7); RT_MAP_PATH(8);
-            default: return RT_ERR_UNSUPPORTED;
-            }
-#undef RT_MAP_PATH
+            RT_TRY(post_dispatch<1, 8>(p.NT, [&](auto nt) {
+                hipLaunchKernelGGL((map_path_kernel<decltype(nt)::value>), dim3(grid), dim3(64), 0, st, tb,
+                                   (int)n, (int)N, (long)nsites, (long)tiles, (unsigned long long)seed,
+                                   (unsigned long long)first_draw, (long)d0,
+                                   (const unsigned char *)d_states, d_val, d_cnt, d_status);
+                return RT_OK;
+            }));
         }
         RT_HIP(hipGetLastError());
         hipLaunchKernelGGL(map_means_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st,

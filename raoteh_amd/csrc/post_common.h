@@ -1,12 +1,13 @@
-// What the downward passes over a RESIDENT batch share (posterior.hip, branch_expect.hip): the
-// scratch plan, the step tables of the two layouts and the lane family's observation read.
+// What the reads of a RESIDENT batch share (posterior.hip, branch_expect.hip, sample.hip,
+// mapping.hip).  Host: post_pass, one description of such a call -- its checks, the common
+// pieces of its scratch, the upward pass with L (and M) of every step stored -- and the dispatch
+// over the kernels' template arguments.  Device: the steps the downward kernels have in common.
 #pragma once
 
 #include "common.h"
 
-namespace {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
+#include <algorithm>
+#include <type_traits>
 
 // byte offsets of the call's pieces in the context's scratch (256-byte aligned)
 struct post_plan {
@@ -18,6 +19,41 @@ struct post_plan {
         return o;
     }
 };
+
+// One read of a resident batch.  post_open .. post_layout make the checks every such call makes
+// and take the common pieces from `plan`; the caller takes its own from the same plan, then
+// post_begin reserves the scratch and post_up leaves L (and M) of every node in it.  `table` and
+// `step_node` feed asynchronous copies: the pass lives until the stream is synchronised.
+struct post_pass {
+    const char *who = nullptr;                  // the entry point, for the messages
+    rt_model *m = nullptr;
+    rt_sites *s = nullptr, *x = nullptr;        // x: the split-M interpreter twin (n > 4)
+    rt_ctx *ctx = nullptr;
+    hipStream_t st = nullptr;
+    int64_t n = 0, N = 0, nsites = 0;
+    bool lane = false, with_D = false;
+    int NT = 0, KS = 0, KP = 0, nops = 0;       // row tiles, k-steps, k-step pairs; schedule steps
+    post_plan plan;
+    size_t o_L = 0, o_M = 0, o_D = 0, o_status = 0, o_steps = 0, o_ptab = 0, o_PT = 0;
+    unsigned char *base = nullptr;
+    double *d_L = nullptr, *d_M = nullptr, *d_D = nullptr, *d_PT = nullptr;
+    int *d_status = nullptr, *d_ptab = nullptr; // ptab: the lane table, or step -> node
+    int4 *d_steps = nullptr;
+    std::vector<int32_t> table, step_node;
+};
+
+// sample.hip: the device part of rt_sites_sample_states for a caller that goes on with the draws
+// on the device (mapping.hip).  rt_sample_states_plan is post_layout, the checks of the draws and
+// their piece of the scratch (*o_states: [ndraws][nsites][nnodes]); after post_begin,
+// rt_sample_states_enqueue runs the upward pass and the draws on the context's stream and leaves
+// the states at d_states and the status (OR-ed over the draws) at p->d_status.
+int rt_sample_states_plan(post_pass *p, int64_t ndraws, size_t *o_states);
+int rt_sample_states_enqueue(post_pass *p, uint64_t seed, uint64_t first_draw, int64_t ndraws,
+                             unsigned char *d_states);
+
+namespace {
+
+typedef double double4_t __attribute__((ext_vector_type(4)));
 
 // n > 4: steps[i] = {node, step of the parent, stream position of an observed leaf or -1,
 // w_of_node[node]} in the schedule order of the split-M twin `x` (the root is the last step), and
@@ -57,6 +93,119 @@ inline void post_lane_table(const rt_model *m, const rt_sites *s, const int *w_o
         if (op.obs >= 0) (*table)[(size_t)N + op.node] = op.obs;
 }
 
+// the handles and the sizes every later check and layout goes by
+inline int post_open(post_pass *p, const char *who, rt_model *m, rt_sites *s)
+{
+    RT_REQUIRE(m && s, "null pointer");
+    RT_REQUIRE(s->model == m, "the site batch belongs to another model");
+    p->who = who; p->m = m; p->s = s; p->ctx = m->ctx; p->st = m->ctx->stream;
+    p->n = m->n; p->N = m->nnodes; p->nsites = s->nsites; p->nops = (int)s->ops.size();
+    p->lane = s->layout == RT_LAYOUT_LANE;
+    p->NT = (int)((p->n + 15) / 16); p->KS = (int)((p->n + 3) / 4); p->KP = (p->KS + 1) / 2;
+    return RT_OK;
+}
+
+// the batches these passes take, and the common pieces of the scratch.  with_D: M, D and the P^T
+// fragments (8 bytes in the lane layout) as well; else L alone -- and a buffer for M where the
+// upward kernel's store variant writes it unconditionally (n > 4).
+inline int post_layout(post_pass *p, bool with_D)
+{
+    const rt_model *m = p->m;
+    const rt_sites *s = p->s;
+    const int64_t n = p->n, N = p->N;
+    if (s->rescale || N < 2 || n < 2 || n > RT_MAX_STATES || s->d_scratch ||
+        m->max_depth > RT_FAST_MAX_DEPTH || p->lane != (n <= 4)) {
+        rt_set_error("%s: batches of 2..%d states without \"rescale\" on trees of at least two "
+                     "nodes that the fast kernels take (n=%lld, nnodes=%lld, depth %d%s)", p->who,
+                     RT_MAX_STATES, (long long)n, (long long)N, m->max_depth,
+                     s->rescale ? ", rescale" : "");
+        return RT_ERR_UNSUPPORTED;
+    }
+    // L, M, D of every node and site
+    const size_t arr = p->lane ? (size_t)N * n * p->nsites * 8
+                               : (size_t)p->nops * s->nblocks * p->NT * 256 * 8;
+    p->with_D = with_D;
+    p->o_L = p->plan.take(arr);
+    p->o_M = p->plan.take(with_D || !p->lane ? arr : 8);
+    if (with_D) p->o_D = p->plan.take(arr);
+    p->o_status = p->plan.take((size_t)p->nsites * 4);
+    p->o_steps = p->plan.take((size_t)std::max<int64_t>(p->nops, N) * 16);
+    p->o_ptab = p->plan.take((size_t)3 * N * 4);
+    if (with_D) p->o_PT = p->plan.take(p->lane ? 8 : (size_t)p->nops * p->NT * p->KP * 128 * 8);
+    return RT_OK;
+}
+
+// once the caller has taken its pieces: the cap, the transition matrices, the twin, the scratch
+// (status cleared).  `draws`: the call's scratch grows with a number of draws too.
+inline int post_begin(post_pass *p, int recompute_transitions, bool draws = false)
+{
+    if ((double)p->plan.total > 96e9) {
+        rt_set_error("%s: this %s needs %.0f GB of scratch; split the batch%s", p->who,
+                     draws ? "call" : "batch", (double)p->plan.total / 1e9,
+                     draws ? " or the draws" : "");
+        return RT_ERR_UNSUPPORTED;
+    }
+    RT_HIP(hipSetDevice(p->ctx->device));
+    if (recompute_transitions) RT_TRY(rt_model_recompute_transitions(p->m));
+    RT_REQUIRE(p->m->have_P, "the model has no transition matrices yet");
+    if (!p->lane) {
+        if (!p->s->expect_twin) RT_TRY(rt_sites_twin_interpreter(p->s, &p->s->expect_twin));
+        p->x = p->s->expect_twin;
+    }
+    RT_TRY(rt_scratch_reserve(p->ctx, p->plan.total));
+    unsigned char *base = p->base = p->ctx->d_scratch;
+    p->d_L = (double *)(base + p->o_L);
+    p->d_M = (double *)(base + p->o_M);
+    p->d_D = p->with_D ? (double *)(base + p->o_D) : nullptr;
+    p->d_PT = p->with_D ? (double *)(base + p->o_PT) : nullptr;
+    p->d_status = (int *)(base + p->o_status);
+    p->d_steps = (int4 *)(base + p->o_steps);
+    p->d_ptab = (int *)(base + p->o_ptab);
+    RT_HIP(hipMemsetAsync(p->d_status, 0, (size_t)p->nsites * 4, p->st));
+    return RT_OK;
+}
+
+// the table of the downward pass with `w_of_node` as its last column and, for n > 4, the upward
+// pass: the split-M interpreter kernel with L and M of every step stored (its own log-likelihoods
+// and totals are the twin's, not the batch's), then with pack_pt the model's P^T as A fragments.
+// (n <= 4: the lane kernels make the upward pass themselves, lane_up.)
+inline int post_up(post_pass *p, const int *w_of_node, bool pack_pt)
+{
+    if (p->lane) {
+        post_lane_table(p->m, p->s, w_of_node, &p->table);
+        RT_HIP(hipMemcpyAsync(p->d_ptab, p->table.data(), p->table.size() * 4, hipMemcpyHostToDevice,
+                              p->st));
+        return RT_OK;
+    }
+    rt_sites *x = p->x;
+    RT_TRY(post_step_table(p->m, x, w_of_node, &p->table, &p->step_node));
+    RT_HIP(hipMemcpyAsync(p->d_steps, p->table.data(), p->table.size() * 4, hipMemcpyHostToDevice,
+                          p->st));
+    if (pack_pt)
+        RT_HIP(hipMemcpyAsync(p->d_ptab, p->step_node.data(), (size_t)p->nops * 4,
+                              hipMemcpyHostToDevice, p->st));
+    x->d_Lout = p->d_L;
+    x->d_Mout = p->d_M;
+    const int rc = rt_launch_prune(p->m, x, false);
+    x->d_Lout = x->d_Mout = nullptr;
+    RT_TRY(rc);
+    if (pack_pt)
+        RT_TRY(rt_launch_pack_pt(p->ctx, (int)p->n, p->NT, p->KP, p->nops, p->d_ptab, p->m->d_P,
+                                 p->d_PT));
+    return RT_OK;
+}
+
+// f(std::integral_constant<int, V>) for the V in LO .. HI that equals v: the one table of the
+// kernels' template arguments.  The lane kernels take the states (2 .. 4), the wave-per-tile
+// kernels the row tiles NT (1 .. 8), the downward kernels the k-steps KS (2 .. 32) with
+// NT = ceil(KS / 4).
+template <int LO, int HI, class F>
+inline int post_dispatch(int v, F &&f)
+{
+    if constexpr (LO > HI) return RT_ERR_UNSUPPORTED;
+    else return v == LO ? f(std::integral_constant<int, LO>()) : post_dispatch<LO + 1, HI>(v, f);
+}
+
 // n <= 4: one lane per site.  The observation of stream position k from the batch's lane-family
 // image (dense pairs, or one byte per leaf: a state or an allowed-set mask; passes.hip
 // sets_from_lane_batch_kernel reads the same layouts).
@@ -79,6 +228,183 @@ __device__ inline void lane_obs(const void *obs, int compact, int K, int block_s
 #pragma unroll
         for (int s = 0; s < N; ++s) x[s] = o[(size_t)(s >> 1) * block_sites * 2 + (s & 1)];
     }
+}
+
+// ---- n <= 4: one lane per site; arrays [node][state][site], nodes in preorder (a parent before
+// its children) ----
+
+// up: L_v = observation, times the messages M_v = P_v L_v of the children (descending preorder
+// index); M stored too where the downward pass divides by it
+template <int N, bool STORE_M>
+__device__ __forceinline__ void lane_up(int nnodes, long nsites, long site, const double *P,
+                               const int *parent, const int *node_k,
+                               const void *obs, int compact, int K, int block_sites,
+                               double *Larr, double *Marr)
+{
+    auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
+    for (int v = 0; v < nnodes; ++v) {
+        double x[N];
+        const int k = node_k[v];
+        if (k >= 0) lane_obs<N>(obs, compact, K, block_sites, site, k, x);
+        else
+#pragma unroll
+            for (int s = 0; s < N; ++s) x[s] = 1.0;
+#pragma unroll
+        for (int s = 0; s < N; ++s) Larr[idx(v, s)] = x[s];
+    }
+    for (int v = nnodes - 1; v >= 1; --v) {
+        double x[N];
+#pragma unroll
+        for (int s = 0; s < N; ++s) x[s] = Larr[idx(v, s)];
+        const double *Pv = P + (size_t)v * N * N;
+        const int p = parent[v];
+#pragma unroll
+        for (int a = 0; a < N; ++a) {
+            double t = 0.0;
+#pragma unroll
+            for (int b = 0; b < N; ++b) t += Pv[a * N + b] * x[b];
+            if (STORE_M) Marr[idx(v, a)] = t;
+            Larr[idx(p, a)] *= t;
+        }
+    }
+}
+
+// the root: D = w L / sum_states(w L), stored and in d; true where the sum is not positive (D = 0)
+template <int N>
+__device__ __forceinline__ bool lane_root(long nsites, long site, const double *root_w,
+                                 const double *Larr, double *Darr,
+                                 double (&d)[N])
+{
+    double wl[N], tot = 0.0;
+#pragma unroll
+    for (int s = 0; s < N; ++s) {
+        wl[s] = (root_w ? root_w[s] : 1.0) * Larr[(size_t)s * nsites + site];
+        tot += wl[s];
+    }
+    const bool zero = !(tot > 0.0);
+#pragma unroll
+    for (int s = 0; s < N; ++s) {
+        d[s] = zero ? 0.0 : wl[s] / tot;
+        Darr[(size_t)s * nsites + site] = d[s];
+    }
+    return zero;
+}
+
+// u = D_p / M_v of node v below p; bad is set where a live parent state meets a denominator <= 0
+template <int N>
+__device__ __forceinline__ void lane_u(long nsites, long site, int p, int v, const double *Darr,
+                                       const double *Marr, double (&u)[N], bool &bad)
+{
+#pragma unroll
+    for (int a = 0; a < N; ++a) {
+        const double dp = Darr[((size_t)p * N + a) * nsites + site];
+        const double den = Marr[((size_t)v * N + a) * nsites + site];
+        u[a] = 0.0;
+        if (dp != 0.0) {
+            if (den > 0.0) u[a] = dp / den;
+            else bad = true;
+        }
+    }
+}
+
+// ---- n > 4: one workgroup of NT row-tile waves per 16-site tile; wave m, lane l holds rows
+// 16 m + 4 r + (l >> 4), r = 0 .. 3, of site l & 15; L, M, D [step][tile][NT][4][64] ----
+
+// element r of this lane's rows at step `step`: down_at(..) + r * 64
+template <int NT>
+__device__ __forceinline__ size_t down_at(int step, long nblocks, long blk, int m, int lane)
+{
+    return ((size_t)step * nblocks + blk) * ((size_t)NT * 256) + (m * 4) * 64 + lane;
+}
+
+// v over the states: own rows are in v; the four lane groups by xor shuffles into part[m], then
+// (after a barrier) down_total adds the waves in order -- a fixed order, the same bits every call
+__device__ __forceinline__ void down_part(double (*part)[16], int m, int lane, double v)
+{
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    if (lane < 16) part[m][lane] = v;
+}
+
+template <int NT>
+__device__ __forceinline__ double down_total(const double (*part)[16], int j)
+{
+    double t = 0.0;
+#pragma unroll
+    for (int mm = 0; mm < NT; ++mm) t += part[mm][j];
+    return t;
+}
+
+// own rows of L at a step: what the upward pass stored (at o), or for an observed leaf (stream
+// position k >= 0) its observation: the pairs q = 2m, 2m + 1 of og hold rows 4m .. 4m + 3
+// (prune.hip)
+template <int KP>
+__device__ __forceinline__ void down_L(int k, const double *og, const double *Larr,
+                              size_t o, int m, double (&L)[4])
+{
+    if (k >= 0) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int q = 2 * m + h;
+            double2 v = {0.0, 0.0};
+            if (q < KP) v = *(const double2 *)(og + ((size_t)k * KP + q) * 128);
+            L[2 * h] = v.x;
+            L[2 * h + 1] = v.y;
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) L[r] = Larr[o + r * 64];
+    }
+}
+
+// u = D_p / M_v on own rows (parent's D at po, M at o); bad is set where a live parent state
+// meets a denominator <= 0
+__device__ __forceinline__ void down_u(const double *Darr, size_t po, const double *Marr, size_t o,
+                                       double (&u)[4], bool &bad)
+{
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const double dp = Darr[po + r * 64];
+        const double den = Marr[o + r * 64];
+        u[r] = 0.0;
+        if (dp != 0.0) {
+            if (den > 0.0) u[r] = dp / den;
+            else bad = true;
+        }
+    }
+}
+
+// own rows of u into xb, the B operands of every wave's products, between two barriers (the
+// first: every wave is done with the previous operands)
+__device__ __forceinline__ void down_stage(double *xb, int m, int lane, const double (&u)[4])
+{
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) xb[(4 * m + r) * 64 + lane] = u[r];
+    __syncthreads();
+}
+
+// this wave's A fragments of step `step` of a rt_launch_pack_pt table
+template <int KP>
+__device__ __forceinline__ void down_frag(const double *ag, double (&a)[2 * KP])
+{
+#pragma unroll
+    for (int q = 0; q < KP; ++q) {
+        const double2 v = *(const double2 *)(ag + q * 128);
+        a[2 * q] = v.x;
+        a[2 * q + 1] = v.y;
+    }
+}
+
+// own rows of A x for the staged x
+template <int KS>
+__device__ __forceinline__ double4_t down_product(const double (&a)[2 * ((KS + 1) / 2)], const double *xb, int lane)
+{
+    double4_t acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], xb[kk * 64 + lane], acc, 0, 0, 0);
+    return acc;
 }
 
 }  // namespace

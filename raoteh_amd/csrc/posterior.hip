@@ -21,7 +21,9 @@
 //
 // Every sum is taken in a fixed order (the four lane groups by xor shuffles, then the waves in
 // order), so two calls give the same bits.  Nothing of the batch is written: its own pruning
-// kernel, log-likelihoods, status and totals stay as they were.
+// kernel, log-likelihoods, status and totals stay as they were.  The checks, the scratch, the
+// upward pass and the steps of the two kernels that rt_sites_branch_expectations and the sampling
+// calls make as well are post_common.h's.
 #include "common.h"
 #include "post_common.h"
 
@@ -59,42 +61,27 @@ post_down_kernel(const double *__restrict__ PfragT, int nops, const int4 *__rest
     const long blk = blockIdx.x;
     const long site = blk * 16 + (lane & 15);
     const bool site_ok = site < nsites;
-    const size_t tile_stride = (size_t)NT * 256;
-    auto at = [&](int step) { return ((size_t)step * nblocks + blk) * tile_stride + (m * 4) * 64 + lane; };
     const unsigned long long *nmask = masks, *amask = masks + 2 * PS_MAX, *bmask = masks + 4 * PS_MAX;
     bool bad = false;
-    // the sums of one node over the state layout: own rows, the four lane groups, then the waves
-    auto wave_part = [&](int slot, double v) {
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
-        if (lane < 16) sums[slot][m][lane] = v;
-    };
-    // node sets of D (own rows d), into sums[0 .. nns)
+    // node sets of D (own rows d), into sums[0 .. nns): own rows, the four lane groups, then
+    // (write_sums) the waves
     auto node_parts = [&](const double (&d)[4]) {
         for (int k = 0; k < nns; ++k) {
             double v = 0.0;
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (in_set(nmask + 2 * k, 16 * m + 4 * r + (lane >> 4))) v += d[r];
-            wave_part(k, v);
+            down_part(sums[k], m, lane, v);
         }
     };
     // after a barrier: wave 0 adds the waves' parts in order and writes the site's row
     auto write_sums = [&](int v, bool edges) {
         if (m == 0 && lane < 16 && site_ok) {
-            for (int k = 0; k < nns; ++k) {
-                double t = 0.0;
-#pragma unroll
-                for (int mm = 0; mm < NT; ++mm) t += sums[k][mm][lane];
-                node_out[((size_t)site * nnodes + v) * nns + k] = t;
-            }
-            for (int k = 0; k < nes; ++k) {
-                double t = 0.0;
-                if (edges)
-#pragma unroll
-                    for (int mm = 0; mm < NT; ++mm) t += sums[PS_MAX + k][mm][lane];
-                edge_out[((size_t)site * nnodes + v) * nes + k] = t;
-            }
+            for (int k = 0; k < nns; ++k)
+                node_out[((size_t)site * nnodes + v) * nns + k] = down_total<NT>(sums[k], lane);
+            for (int k = 0; k < nes; ++k)
+                edge_out[((size_t)site * nnodes + v) * nes + k] =
+                    edges ? down_total<NT>(sums[PS_MAX + k], lane) : 0.0;
         }
     };
     auto write_marg = [&](int j, const double (&d)[4]) {
@@ -108,9 +95,8 @@ post_down_kernel(const double *__restrict__ PfragT, int nops, const int4 *__rest
     };
     // root: D = w L / sum_states(w L)  (_mc0_dense.py:400-489 with the prior weights)
     {
-        const int i = nops - 1;
-        const int4 st = steps[i];
-        const size_t o = at(i);
+        const int4 st = steps[nops - 1];
+        const size_t o = down_at<NT>(nops - 1, nblocks, blk, m, lane);
         double wl[4], s = 0.0;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -119,13 +105,9 @@ post_down_kernel(const double *__restrict__ PfragT, int nops, const int4 *__rest
             wl[r] = w * Larr[o + r * 64];
             s += wl[r];
         }
-        s += __shfl_xor(s, 16, 64);
-        s += __shfl_xor(s, 32, 64);
-        if (lane < 16) red[m][lane] = s;
+        down_part(red, m, lane, s);
         __syncthreads();
-        double tot = 0.0;
-#pragma unroll
-        for (int mm = 0; mm < NT; ++mm) tot += red[mm][lane & 15];
+        const double tot = down_total<NT>(red, lane & 15);
         const bool zero = !(tot > 0.0);
         double d[4];
 #pragma unroll
@@ -141,51 +123,17 @@ post_down_kernel(const double *__restrict__ PfragT, int nops, const int4 *__rest
     }
     const double *ag = PfragT + ((size_t)m * KP * 64 + lane) * 2;
     constexpr size_t ASTRIDE = (size_t)NT * KP * 128;
-    // observation pairs holding this wave's own rows 4m..4m+3: q = 2m, 2m+1 (prune.hip)
     const double *og = obs + (size_t)blk * K * (KP * 128) + lane * 2;
     for (int i = nops - 2; i >= 0; --i) {
         const int4 st = steps[i];
-        const size_t o = at(i), po = at(st.y);
-        double a[2 * KP];
-#pragma unroll
-        for (int q = 0; q < KP; ++q) {
-            const double2 v = *(const double2 *)(ag + (size_t)i * ASTRIDE + q * 128);
-            a[2 * q] = v.x;
-            a[2 * q + 1] = v.y;
-        }
-        double L[4], u[4];
-        if (st.z >= 0) {                         // an observed leaf: L is its observation
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int q = 2 * m + h;
-                double2 v = {0.0, 0.0};
-                if (q < KP) v = *(const double2 *)(og + ((size_t)st.z * KP + q) * 128);
-                L[2 * h] = v.x;
-                L[2 * h + 1] = v.y;
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) L[r] = Larr[o + r * 64];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const double dp = Darr[po + r * 64];
-            const double den = Marr[o + r * 64];
-            u[r] = 0.0;
-            if (dp != 0.0) {
-                if (den > 0.0) u[r] = dp / den;
-                else bad = true;
-            }
-        }
+        const size_t o = down_at<NT>(i, nblocks, blk, m, lane);
+        double a[2 * KP], L[4], u[4];
+        down_frag<KP>(ag + (size_t)i * ASTRIDE, a);
+        down_L<KP>(st.z, og, Larr, o, m, L);
+        down_u(Darr, down_at<NT>(st.y, nblocks, blk, m, lane), Marr, o, u, bad);
         // D_v = (P^T u) * L
-        __syncthreads();                         // every wave is done with the previous operands
-#pragma unroll
-        for (int r = 0; r < 4; ++r) xb[(4 * m + r) * 64 + lane] = u[r];
-        __syncthreads();
-        double4_t acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int kk = 0; kk < KS; ++kk)
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], xb[kk * 64 + lane], acc, 0, 0, 0);
+        down_stage(xb, m, lane, u);
+        const double4_t acc = down_product<KS>(a, xb, lane);
         double d[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -207,15 +155,12 @@ post_down_kernel(const double *__restrict__ PfragT, int nops, const int4 *__rest
                 for (int r = 0; r < 4; ++r)
                     xb[(4 * m + r) * 64 + lane] = in_set(am, 16 * m + 4 * r + (lane >> 4)) ? u[r] : 0.0;
                 __syncthreads();
-                double4_t y = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int kk = 0; kk < KS; ++kk)
-                    y = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], xb[kk * 64 + lane], y, 0, 0, 0);
+                const double4_t y = down_product<KS>(a, xb, lane);
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (in_set(bm, 16 * m + 4 * r + (lane >> 4))) v += y[r] * L[r];
             }
-            wave_part(PS_MAX + k, v);
+            down_part(sums[PS_MAX + k], m, lane, v);
         }
         __syncthreads();
         write_sums(st.x, true);
@@ -224,7 +169,7 @@ post_down_kernel(const double *__restrict__ PfragT, int nops, const int4 *__rest
     if (bad && site_ok) atomicOr(&status[site], 2);
 }
 
-// n <= 4: one lane per site (lane_obs of post_common.h reads the observations);
+// n <= 4: one lane per site (the upward pass, the root and u: post_common.h);
 // arrays [node][state][site]; nodes in preorder (a parent before its children)
 template <int N>
 __global__ void __launch_bounds__(256)
@@ -240,32 +185,7 @@ post_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const in
     if (site >= nsites) return;
     const unsigned long long *nmask = masks, *amask = masks + 2 * PS_MAX, *bmask = masks + 4 * PS_MAX;
     auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
-    // up: L_v = observation, times the messages of the children (descending preorder index)
-    for (int v = 0; v < nnodes; ++v) {
-        double x[N];
-        const int k = node_k[v];
-        if (k >= 0) lane_obs<N>(obs, compact, K, block_sites, site, k, x);
-        else
-#pragma unroll
-            for (int s = 0; s < N; ++s) x[s] = 1.0;
-#pragma unroll
-        for (int s = 0; s < N; ++s) Larr[idx(v, s)] = x[s];
-    }
-    for (int v = nnodes - 1; v >= 1; --v) {
-        double x[N];
-#pragma unroll
-        for (int s = 0; s < N; ++s) x[s] = Larr[idx(v, s)];
-        const double *Pv = P + (size_t)v * N * N;
-        const int p = parent[v];
-#pragma unroll
-        for (int a = 0; a < N; ++a) {
-            double t = 0.0;
-#pragma unroll
-            for (int b = 0; b < N; ++b) t += Pv[a * N + b] * x[b];
-            Marr[idx(v, a)] = t;
-            Larr[idx(p, a)] *= t;
-        }
-    }
+    lane_up<N, true>(nnodes, nsites, site, P, parent, node_k, obs, compact, K, block_sites, Larr, Marr);
     auto sums = [&](int v, const double (&d)[N], const double (&u)[N], const double (&L)[N], const double *Pv) {
         for (int k = 0; k < nns; ++k) {
             double t = 0.0;
@@ -296,37 +216,16 @@ post_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const in
     };
     // down: the root, then every node after its parent
     {
-        double wl[N], L[N], d[N], tot = 0.0;
-#pragma unroll
-        for (int s = 0; s < N; ++s) {
-            L[s] = Larr[idx(0, s)];
-            wl[s] = (root_w ? root_w[s] : 1.0) * L[s];
-            tot += wl[s];
-        }
-        const bool zero = !(tot > 0.0);
-#pragma unroll
-        for (int s = 0; s < N; ++s) {
-            d[s] = zero ? 0.0 : wl[s] / tot;
-            Darr[idx(0, s)] = d[s];
-        }
-        if (zero) status[site] |= RT_SITE_ZERO_PROB;
-        sums(0, d, d, L, nullptr);
+        double d[N];
+        if (lane_root<N>(nsites, site, root_w, Larr, Darr, d)) status[site] |= RT_SITE_ZERO_PROB;
+        sums(0, d, d, d, nullptr);               // (no edge: u and L are not read)
     }
     bool bad = false;
     for (int v = 1; v < nnodes; ++v) {
         const int p = parent[v];
         const double *Pv = P + (size_t)v * N * N;
         double u[N], L[N], d[N];
-#pragma unroll
-        for (int a = 0; a < N; ++a) {
-            const double dp = Darr[idx(p, a)];
-            const double den = Marr[idx(v, a)];
-            u[a] = 0.0;
-            if (dp != 0.0) {
-                if (den > 0.0) u[a] = dp / den;
-                else bad = true;
-            }
-        }
+        lane_u<N>(nsites, site, p, v, Darr, Marr, u, bad);
 #pragma unroll
         for (int b = 0; b < N; ++b) {
             L[b] = Larr[idx(v, b)];
@@ -341,20 +240,6 @@ post_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const in
     if (bad) status[site] |= 2;
 }
 
-template <int NT, int KS>
-int launch_down(rt_ctx *ctx, const double *d_PT, int nops, const int4 *d_steps, const double *d_L,
-                const double *d_M, double *d_D, const rt_sites *x, const double *d_root, int n,
-                const unsigned long long *d_masks, int nns, int nes, unsigned a_full, int nnodes,
-                int nmarg, double *d_node, double *d_edge, double *d_marg, int *d_status)
-{
-    hipLaunchKernelGGL((post_down_kernel<NT, KS>), dim3((unsigned)x->nblocks), dim3(64 * NT), 0, ctx->stream,
-                       d_PT, nops, d_steps, d_L, d_M, d_D, (const double *)x->d_obs, (int)x->nobs, d_root,
-                       n, d_masks, nns, nes, a_full, nnodes, nmarg, d_node, d_edge, d_marg, d_status,
-                       (long)x->nsites, (long)x->nblocks);
-    RT_HIP(hipGetLastError());
-    return RT_OK;
-}
-
 }  // namespace
 
 extern "C" int rt_sites_posteriors(rt_model *m, rt_sites *s, int recompute_transitions,
@@ -363,27 +248,19 @@ extern "C" int rt_sites_posteriors(rt_model *m, rt_sites *s, int recompute_trans
                                    const int64_t *marginal_nodes, double *node_values,
                                    double *edge_values, double *marginals, int32_t *status)
 {
-    RT_REQUIRE(m && s, "null pointer");
-    RT_REQUIRE(s->model == m, "the site batch belongs to another model");
+    post_pass p;                                 // (alive until the synchronisation below)
+    RT_TRY(post_open(&p, "rt_sites_posteriors", m, s));
     RT_REQUIRE(n_node_sets >= 0 && n_edge_sets >= 0 && n_marginal_nodes >= 0, "negative count");
     RT_REQUIRE(!n_node_sets || node_sets, "node_sets is null");
     RT_REQUIRE(!n_edge_sets || edge_sets, "edge_sets is null");
-    const int64_t n = m->n, N = m->nnodes, nsites = s->nsites;
+    const int64_t n = p.n, N = p.N, nsites = p.nsites;
     if (n_node_sets > RT_MAX_POSTERIOR_SETS || n_edge_sets > RT_MAX_POSTERIOR_SETS) {
         rt_set_error("rt_sites_posteriors: at most %d node sets and %d edge sets (%lld, %lld here)",
                      RT_MAX_POSTERIOR_SETS, RT_MAX_POSTERIOR_SETS, (long long)n_node_sets,
                      (long long)n_edge_sets);
         return RT_ERR_UNSUPPORTED;
     }
-    const bool lane = s->layout == RT_LAYOUT_LANE;
-    if (s->rescale || N < 2 || n < 2 || n > RT_MAX_STATES || s->d_scratch ||
-        m->max_depth > RT_FAST_MAX_DEPTH || lane != (n <= 4)) {
-        rt_set_error("rt_sites_posteriors: batches of 2..%d states without \"rescale\" on trees of "
-                     "at least two nodes that the fast kernels take (n=%lld, nnodes=%lld, depth %d%s)",
-                     RT_MAX_STATES, (long long)n, (long long)N, m->max_depth,
-                     s->rescale ? ", rescale" : "");
-        return RT_ERR_UNSUPPORTED;
-    }
+    RT_TRY(post_layout(&p, true));
     // the sets: no state beyond n
     const int words = 2;
     std::vector<unsigned long long> masks((size_t)3 * RT_MAX_POSTERIOR_SETS * words, 0ull);
@@ -428,98 +305,44 @@ extern "C" int rt_sites_posteriors(rt_model *m, rt_sites *s, int recompute_trans
         }
     }
     const int nns = node_values ? (int)n_node_sets : 0, nes = edge_values ? (int)n_edge_sets : 0;
-    rt_ctx *ctx = m->ctx;
-    RT_HIP(hipSetDevice(ctx->device));
-    const int NT = (int)((n + 15) / 16), KS = (int)((n + 3) / 4), KP = (KS + 1) / 2;
-    const int nops = (int)s->ops.size();
-    // scratch: L, M, D of every node and site, the outputs, the step table, the masks
-    const size_t arr = lane ? (size_t)N * n * nsites * 8 : (size_t)nops * s->nblocks * NT * 256 * 8;
-    post_plan plan;
-    const size_t o_L = plan.take(arr), o_M = plan.take(arr), o_D = plan.take(arr);
-    const size_t o_node = plan.take((size_t)nsites * N * std::max(nns, 1) * 8);
-    const size_t o_edge = plan.take((size_t)nsites * N * std::max(nes, 1) * 8);
-    const size_t o_marg = plan.take((size_t)nsites * std::max<int64_t>(nmarg, 1) * n * 8);
-    const size_t o_status = plan.take((size_t)nsites * 4);
-    const size_t o_masks = plan.take(masks.size() * 8);
-    const size_t o_steps = plan.take((size_t)std::max<int64_t>(nops, N) * 16);
-    const size_t o_PT = lane ? plan.take(8) : plan.take((size_t)nops * NT * KP * 128 * 8);
-    const size_t o_ptab = plan.take((size_t)3 * N * 4);
-    if ((double)plan.total > 96e9) {
-        rt_set_error("rt_sites_posteriors: this batch needs %.0f GB of scratch; split the batch",
-                     (double)plan.total / 1e9);
-        return RT_ERR_UNSUPPORTED;
-    }
-    if (recompute_transitions) RT_TRY(rt_model_recompute_transitions(m));
-    RT_REQUIRE(m->have_P, "the model has no transition matrices yet");
-    hipStream_t st = ctx->stream;
-    rt_sites *x = nullptr;
-    if (!lane) {
-        if (!s->expect_twin) RT_TRY(rt_sites_twin_interpreter(s, &s->expect_twin));
-        x = s->expect_twin;
-    }
-    RT_TRY(rt_scratch_reserve(ctx, plan.total));
-    unsigned char *base = ctx->d_scratch;
-    double *d_L = (double *)(base + o_L), *d_M = (double *)(base + o_M), *d_D = (double *)(base + o_D);
-    double *d_node = (double *)(base + o_node), *d_edge = (double *)(base + o_edge);
-    double *d_marg = (double *)(base + o_marg);
-    int *d_status = (int *)(base + o_status);
-    unsigned long long *d_masks = (unsigned long long *)(base + o_masks);
-    RT_HIP(hipMemsetAsync(d_status, 0, (size_t)nsites * 4, st));
+    // scratch: L, M, D of every node and site (post_layout), the outputs, the masks
+    const size_t o_node = p.plan.take((size_t)nsites * N * std::max(nns, 1) * 8);
+    const size_t o_edge = p.plan.take((size_t)nsites * N * std::max(nes, 1) * 8);
+    const size_t o_marg = p.plan.take((size_t)nsites * std::max<int64_t>(nmarg, 1) * n * 8);
+    const size_t o_masks = p.plan.take(masks.size() * 8);
+    RT_TRY(post_begin(&p, recompute_transitions));
+    hipStream_t st = p.st;
+    double *d_node = (double *)(p.base + o_node), *d_edge = (double *)(p.base + o_edge);
+    double *d_marg = (double *)(p.base + o_marg);
+    int *d_status = p.d_status;
+    unsigned long long *d_masks = (unsigned long long *)(p.base + o_masks);
     RT_HIP(hipMemcpyAsync(d_masks, masks.data(), masks.size() * 8, hipMemcpyHostToDevice, st));
-    std::vector<int32_t> table, step_node;       // (alive until the synchronisation below)
-    if (lane) {
-        post_lane_table(m, s, marg_row.data(), &table);
-        int *d_tab = (int *)(base + o_ptab);
-        RT_HIP(hipMemcpyAsync(d_tab, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
-        const unsigned grid = (unsigned)((nsites + 255) / 256);
-#define RT_POST_LANE(NV)                                                                            \
-        hipLaunchKernelGGL((post_lane_kernel<NV>), dim3(grid), dim3(256), 0, st, (int)N, (long)nsites,   \
-                           (const double *)m->d_P, d_tab, d_tab + N, (const void *)s->d_obs,            \
-                           s->compact_states, (int)s->nobs, s->block_sites, (const double *)m->d_root,  \
-                           (const unsigned long long *)d_masks, nns, nes, d_tab + 2 * N, (int)nmarg,    \
-                           d_L, d_M, d_D, d_node, d_edge, d_marg, d_status)
-        switch ((int)n) {
-        case 2: RT_POST_LANE(2); break;
-        case 3: RT_POST_LANE(3); break;
-        default: RT_POST_LANE(4); break;
-        }
-#undef RT_POST_LANE
-        RT_HIP(hipGetLastError());
+    RT_TRY(post_up(&p, marg_row.data(), true));
+    if (p.lane) {
+        const int *d_tab = p.d_ptab;
+        RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
+            hipLaunchKernelGGL((post_lane_kernel<decltype(nv)::value>), dim3((unsigned)((nsites + 255) / 256)),
+                               dim3(256), 0, st, (int)N, (long)nsites, (const double *)m->d_P, d_tab,
+                               d_tab + N, (const void *)s->d_obs, s->compact_states, (int)s->nobs,
+                               s->block_sites, (const double *)m->d_root,
+                               (const unsigned long long *)d_masks, nns, nes, d_tab + 2 * N, (int)nmarg,
+                               p.d_L, p.d_M, p.d_D, d_node, d_edge, d_marg, d_status);
+            return RT_OK;
+        }));
     } else {
-        // the step table of the downward pass
-        RT_TRY(post_step_table(m, x, marg_row.data(), &table, &step_node));
-        int4 *d_steps = (int4 *)(base + o_steps);
-        double *d_PT = (double *)(base + o_PT);
-        int *d_step_node = (int *)(base + o_ptab);
-        RT_HIP(hipMemcpyAsync(d_steps, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
-        RT_HIP(hipMemcpyAsync(d_step_node, step_node.data(), (size_t)nops * 4, hipMemcpyHostToDevice, st));
-        // upward pass: the split-M interpreter kernel with L and M of every step stored (its own
-        // log-likelihoods and totals are the twin's, not the batch's)
-        x->d_Lout = d_L;
-        x->d_Mout = d_M;
-        const int rc = rt_launch_prune(m, x, false);
-        x->d_Lout = x->d_Mout = nullptr;
-        RT_TRY(rc);
-        RT_TRY(rt_launch_pack_pt(ctx, (int)n, NT, KP, nops, d_step_node, m->d_P, d_PT));
-        int lrc = RT_ERR_UNSUPPORTED;
-#define RT_PD(NTV, KSV)                                                                               \
-        case KSV: lrc = launch_down<NTV, KSV>(ctx, d_PT, nops, d_steps, d_L, d_M, d_D, x, m->d_root,  \
-                                              (int)n, d_masks, nns, nes, a_full, (int)N, (int)nmarg,   \
-                                              d_node, d_edge, d_marg, d_status); break
-        switch (KS) {
-        RT_PD(1, 2); RT_PD(1, 3); RT_PD(1, 4);
-        RT_PD(2, 5); RT_PD(2, 6); RT_PD(2, 7); RT_PD(2, 8);
-        RT_PD(3, 9); RT_PD(3, 10); RT_PD(3, 11); RT_PD(3, 12);
-        RT_PD(4, 13); RT_PD(4, 14); RT_PD(4, 15); RT_PD(4, 16);
-        RT_PD(5, 17); RT_PD(5, 18); RT_PD(5, 19); RT_PD(5, 20);
-        RT_PD(6, 21); RT_PD(6, 22); RT_PD(6, 23); RT_PD(6, 24);
-        RT_PD(7, 25); RT_PD(7, 26); RT_PD(7, 27); RT_PD(7, 28);
-        RT_PD(8, 29); RT_PD(8, 30); RT_PD(8, 31); RT_PD(8, 32);
-        default: break;
-        }
-#undef RT_PD
-        RT_TRY(lrc);
+        const rt_sites *x = p.x;
+        RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
+            constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
+            hipLaunchKernelGGL((post_down_kernel<NT, KS>), dim3((unsigned)x->nblocks), dim3(64 * NT), 0, st,
+                               (const double *)p.d_PT, p.nops, (const int4 *)p.d_steps,
+                               (const double *)p.d_L, (const double *)p.d_M, p.d_D,
+                               (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root, (int)n,
+                               (const unsigned long long *)d_masks, nns, nes, a_full, (int)N, (int)nmarg,
+                               d_node, d_edge, d_marg, d_status, (long)x->nsites, (long)x->nblocks);
+            return RT_OK;
+        }));
     }
+    RT_HIP(hipGetLastError());
     // only what was asked for crosses PCIe
     if (node_values && n_node_sets)
         RT_HIP(hipMemcpyAsync(node_values, d_node, (size_t)nsites * N * nns * 8, hipMemcpyDeviceToHost, st));

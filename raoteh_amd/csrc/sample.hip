@@ -7,9 +7,9 @@
 // parent, child ~ P_v[parent's state] * L_v.  Unlike rt_forest_resample_states (forest.hip: one P
 // shared by every edge of every tree) each edge has its own P_v, the model's.
 //
-//   n > 4   the split-M interpreter pruning kernel with L of every step stored (the upward pass of
-//           posterior.hip; its store variant writes M unconditionally, so it is handed a buffer for
-//           M as well), then sample_down_kernel: one wave per (16-site tile, block of DB draws)
+//   n > 4   the split-M interpreter pruning kernel with L of every step stored (post_up of
+//           post_common.h, the upward pass of every read of a resident batch; its store variant
+//           writes M unconditionally, so it is handed a buffer for M as well), then sample_down_kernel: one wave per (16-site tile, block of DB draws)
 //           walks the steps in reverse.  A lane holds the rows of L the upward pass stored for it
 //           (16 m + 4 r + (lane >> 4) of site lane & 15), so L_v is one coalesced load per draw
 //           BLOCK; per draw the lane gathers its entries of the P row its site's parent state
@@ -188,8 +188,8 @@ sample_down_kernel(const double *__restrict__ P, int nops, const int4 *__restric
     if (flags && g == 0 && site_ok) atomicOr(&status[site], flags);
 }
 
-// n <= 4, upward: one lane per site, L in [node][state][site]; nodes in preorder (the upward part
-// of post_lane_kernel, posterior.hip)
+// n <= 4, upward: one lane per site, L in [node][state][site]; nodes in preorder (lane_up of
+// post_common.h: the upward part of post_lane_kernel without M)
 template <int N>
 __global__ void __launch_bounds__(256)
 sample_lane_up_kernel(int nnodes, long nsites, const double *__restrict__ P,
@@ -199,31 +199,7 @@ sample_lane_up_kernel(int nnodes, long nsites, const double *__restrict__ P,
 {
     const long site = (long)blockIdx.x * 256 + threadIdx.x;
     if (site >= nsites) return;
-    auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
-    for (int v = 0; v < nnodes; ++v) {
-        double x[N];
-        const int k = node_k[v];
-        if (k >= 0) lane_obs<N>(obs, compact, K, block_sites, site, k, x);
-        else
-#pragma unroll
-            for (int s = 0; s < N; ++s) x[s] = 1.0;
-#pragma unroll
-        for (int s = 0; s < N; ++s) Larr[idx(v, s)] = x[s];
-    }
-    for (int v = nnodes - 1; v >= 1; --v) {
-        double x[N];
-#pragma unroll
-        for (int s = 0; s < N; ++s) x[s] = Larr[idx(v, s)];
-        const double *Pv = P + (size_t)v * N * N;
-        const int p = parent[v];
-#pragma unroll
-        for (int a = 0; a < N; ++a) {
-            double t = 0.0;
-#pragma unroll
-            for (int b = 0; b < N; ++b) t += Pv[a * N + b] * x[b];
-            Larr[idx(p, a)] *= t;
-        }
-    }
+    lane_up<N, false>(nnodes, nsites, site, P, parent, node_k, obs, compact, K, block_sites, Larr, nullptr);
 }
 
 // n <= 4, downward: one thread per (site, draw); the thread reads the parent's state back from
@@ -303,99 +279,51 @@ extern "C" int rt_sample_states_draw_block(int64_t nnodes)
     return (int)std::min<int64_t>(SAMPLE_MAX_DB, std::max<int64_t>(1, db));
 }
 
-// the checks and the scratch plan of the draws: offsets in `w` from the base the caller hands to
-// rt_sample_states_enqueue
-int rt_sample_states_plan(const char *who, rt_model *m, rt_sites *s, int64_t ndraws, rt_sample_work *w)
+// the checks and the scratch of the draws (post_common.h)
+int rt_sample_states_plan(post_pass *p, int64_t ndraws, size_t *o_states)
 {
-    const int64_t n = m->n, N = m->nnodes, nsites = s->nsites;
-    const bool lane = s->layout == RT_LAYOUT_LANE;
-    if (s->rescale || N < 2 || n < 2 || n > RT_MAX_STATES || s->d_scratch ||
-        m->max_depth > RT_FAST_MAX_DEPTH || lane != (n <= 4)) {
-        rt_set_error("%s: batches of 2..%d states without \"rescale\" on trees "
-                     "of at least two nodes that the fast kernels take (n=%lld, nnodes=%lld, depth "
-                     "%d%s)", who, RT_MAX_STATES, (long long)n, (long long)N, m->max_depth,
-                     s->rescale ? ", rescale" : "");
-        return RT_ERR_UNSUPPORTED;
-    }
-    if (!lane && N > RT_MAX_SAMPLE_NODES) {
+    RT_TRY(post_layout(p, false));
+    if (!p->lane && p->N > RT_MAX_SAMPLE_NODES) {
         rt_set_error("%s: trees of at most %d nodes (the sampled states of a "
-                     "wave live in LDS; %lld nodes here)", who, RT_MAX_SAMPLE_NODES, (long long)N);
+                     "wave live in LDS; %lld nodes here)", p->who, RT_MAX_SAMPLE_NODES, (long long)p->N);
         return RT_ERR_UNSUPPORTED;
     }
-    const int NT = (int)((n + 15) / 16);
-    const int nops = (int)s->ops.size();
-    const size_t arr = lane ? (size_t)N * n * nsites * 8 : (size_t)nops * s->nblocks * NT * 256 * 8;
-    post_plan plan;
-    w->o_L = plan.take(arr);
-    w->o_M = plan.take(lane ? 8 : arr);
-    w->o_states = plan.take((size_t)ndraws * nsites * N);
-    w->o_status = plan.take((size_t)nsites * 4);
-    w->o_steps = plan.take((size_t)std::max<int64_t>(nops, N) * 16);
-    w->o_ptab = plan.take((size_t)3 * N * 4);
-    w->bytes = plan.total;
+    *o_states = p->plan.take((size_t)ndraws * p->nsites * p->N);
     return RT_OK;
 }
 
-// the upward pass and the draws on the context's stream: states [ndraws][nsites][nnodes] at
-// base + w->o_states, status (OR-ed over the draws) at base + w->o_status.  A batch of the
-// matrix-pipe layout has its interpreter twin (s->expect_twin) by now.
-int rt_sample_states_enqueue(rt_model *m, rt_sites *s, uint64_t seed, uint64_t first_draw,
-                             int64_t ndraws, unsigned char *base, rt_sample_work *w)
+// the upward pass and the draws on the context's stream, after post_begin: states
+// [ndraws][nsites][nnodes] at d_states, status (OR-ed over the draws) at p->d_status
+int rt_sample_states_enqueue(post_pass *p, uint64_t seed, uint64_t first_draw, int64_t ndraws,
+                             unsigned char *d_states)
 {
-    const int64_t n = m->n, N = m->nnodes, nsites = s->nsites;
-    const bool lane = s->layout == RT_LAYOUT_LANE;
-    rt_ctx *ctx = m->ctx;
-    const int NT = (int)((n + 15) / 16);
-    const int nops = (int)s->ops.size();
-    hipStream_t st = ctx->stream;
-    rt_sites *x = lane ? nullptr : s->expect_twin;
-    const size_t o_L = w->o_L, o_M = w->o_M, o_states = w->o_states, o_status = w->o_status;
-    const size_t o_steps = w->o_steps, o_ptab = w->o_ptab;
-    std::vector<int32_t> &table = w->table, &step_node = w->step_node;
-    double *d_L = (double *)(base + o_L), *d_M = (double *)(base + o_M);
-    unsigned char *d_states = base + o_states;
-    int *d_status = (int *)(base + o_status);
-    RT_HIP(hipMemsetAsync(d_status, 0, (size_t)nsites * 4, st));
-    std::vector<int> none((size_t)N, -1);
-    if (lane) {
-        post_lane_table(m, s, none.data(), &table);
-        int *d_tab = (int *)(base + o_ptab);
-        RT_HIP(hipMemcpyAsync(d_tab, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
+    const rt_model *m = p->m;
+    const rt_sites *s = p->s, *x = p->x;
+    const int64_t n = p->n, N = p->N, nsites = p->nsites;
+    hipStream_t st = p->st;
+    const double *d_L = p->d_L;
+    int *d_status = p->d_status;
+    // the table of the downward pass: the parent NODE in its last column
+    RT_TRY(post_up(p, m->parent.data(), false));
+    if (p->lane) {
+        const int *d_tab = p->d_ptab;
         const unsigned grid_up = (unsigned)((nsites + 255) / 256);
         const int64_t threads = nsites * ndraws;
         RT_REQUIRE((threads + 255) / 256 < (int64_t)1 << 31, "too many draws for one call");
         const unsigned grid_down = (unsigned)((threads + 255) / 256);
-#define RT_SAMPLE_LANE(NV)                                                                          \
-        do {                                                                                        \
-            hipLaunchKernelGGL((sample_lane_up_kernel<NV>), dim3(grid_up), dim3(256), 0, st, (int)N,    \
-                               (long)nsites, (const double *)m->d_P, d_tab, d_tab + N,               \
-                               (const void *)s->d_obs, s->compact_states, (int)s->nobs,              \
-                               s->block_sites, d_L);                                                 \
-            hipLaunchKernelGGL((sample_lane_down_kernel<NV>), dim3(grid_down), dim3(256), 0, st,        \
-                               (int)N, (long)nsites, (const double *)m->d_P, d_tab,                  \
-                               (const double *)d_L, (const double *)m->d_root,                       \
-                               (unsigned long long)seed, (unsigned long long)first_draw,             \
-                               (long)ndraws, d_states, d_status);                                    \
-        } while (0)
-        switch ((int)n) {
-        case 2: RT_SAMPLE_LANE(2); break;
-        case 3: RT_SAMPLE_LANE(3); break;
-        default: RT_SAMPLE_LANE(4); break;
-        }
-#undef RT_SAMPLE_LANE
-        RT_HIP(hipGetLastError());
+        RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
+            constexpr int NV = decltype(nv)::value;
+            hipLaunchKernelGGL((sample_lane_up_kernel<NV>), dim3(grid_up), dim3(256), 0, st, (int)N,
+                               (long)nsites, (const double *)m->d_P, d_tab, d_tab + N,
+                               (const void *)s->d_obs, s->compact_states, (int)s->nobs,
+                               s->block_sites, p->d_L);
+            hipLaunchKernelGGL((sample_lane_down_kernel<NV>), dim3(grid_down), dim3(256), 0, st,
+                               (int)N, (long)nsites, (const double *)m->d_P, d_tab, d_L,
+                               (const double *)m->d_root, (unsigned long long)seed,
+                               (unsigned long long)first_draw, (long)ndraws, d_states, d_status);
+            return RT_OK;
+        }));
     } else {
-        // the step table of the downward pass: the parent NODE in its last column
-        RT_TRY(post_step_table(m, x, m->parent.data(), &table, &step_node));
-        int4 *d_steps = (int4 *)(base + o_steps);
-        RT_HIP(hipMemcpyAsync(d_steps, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));
-        // upward pass: the split-M interpreter kernel with L (and M) of every step stored (its own
-        // log-likelihoods and totals are the twin's, not the batch's)
-        x->d_Lout = d_L;
-        x->d_Mout = d_M;
-        const int rc = rt_launch_prune(m, x, false);
-        x->d_Lout = x->d_Mout = nullptr;
-        RT_TRY(rc);
         // (a call of fewer draws than the tree's block keeps its table, and so its LDS, that small:
         // which draws share a block has no bearing on a draw)
         const int DB = (int)std::min<int64_t>(rt_sample_states_draw_block(N), ndraws);
@@ -403,26 +331,20 @@ int rt_sample_states_enqueue(rt_model *m, rt_sites *s, uint64_t seed, uint64_t f
         const int64_t dblocks = (ndraws + DB - 1) / DB;
         RT_REQUIRE(dblocks * x->nblocks < (int64_t)1 << 31, "too many draws for one call");
         const unsigned grid = (unsigned)(dblocks * x->nblocks);
-#define RT_SAMPLE_DOWN(NTV)                                                                         \
-        case NTV: {                                                                                 \
-            auto kern = sample_down_kernel<NTV>;                                                    \
-            if (lds > 64 * 1024)                                                                    \
-                RT_HIP(hipFuncSetAttribute((const void *)kern,                                      \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(64), lds, st, (const double *)m->d_P, nops,   \
-                               (const int4 *)d_steps, (const double *)d_L, (const double *)x->d_obs, \
-                               (int)x->nobs, (const double *)m->d_root, (int)n, (int)N, DB,          \
-                               (unsigned long long)seed, (unsigned long long)first_draw,             \
-                               (long)ndraws, d_states, d_status, (long)nsites, (long)x->nblocks);    \
-        } break
-        switch (NT) {
-        RT_SAMPLE_DOWN(1); RT_SAMPLE_DOWN(2); RT_SAMPLE_DOWN(3); RT_SAMPLE_DOWN(4);
-        RT_SAMPLE_DOWN(5); RT_SAMPLE_DOWN(6); RT_SAMPLE_DOWN(7); RT_SAMPLE_DOWN(8);
-        default: return RT_ERR_UNSUPPORTED;
-        }
-#undef RT_SAMPLE_DOWN
-        RT_HIP(hipGetLastError());
+        RT_TRY(post_dispatch<1, 8>(p->NT, [&](auto nt) {
+            auto kern = sample_down_kernel<decltype(nt)::value>;
+            if (lds > 64 * 1024)
+                RT_HIP(hipFuncSetAttribute((const void *)kern,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(64), lds, st, (const double *)m->d_P, p->nops,
+                               (const int4 *)p->d_steps, d_L, (const double *)x->d_obs, (int)x->nobs,
+                               (const double *)m->d_root, (int)n, (int)N, DB, (unsigned long long)seed,
+                               (unsigned long long)first_draw, (long)ndraws, d_states, d_status,
+                               (long)nsites, (long)x->nblocks);
+            return RT_OK;
+        }));
     }
+    RT_HIP(hipGetLastError());
     return RT_OK;
 }
 
@@ -430,33 +352,19 @@ extern "C" int rt_sites_sample_states(rt_model *m, rt_sites *s, int recompute_tr
                                       uint64_t seed, uint64_t first_draw, int64_t ndraws,
                                       uint8_t *states, int32_t *status)
 {
-    RT_REQUIRE(m && s, "null pointer");
-    RT_REQUIRE(s->model == m, "the site batch belongs to another model");
+    post_pass p;                                 // (alive until the synchronisation below)
+    RT_TRY(post_open(&p, "rt_sites_sample_states", m, s));
     RT_REQUIRE(ndraws >= 1, "ndraws must be at least 1");
     RT_REQUIRE(states, "states is null");
-    const int64_t N = m->nnodes, nsites = s->nsites;
-    rt_sample_work work;                         // (its host buffers: alive until the synchronisation)
-    RT_TRY(rt_sample_states_plan("rt_sites_sample_states", m, s, ndraws, &work));
-    if ((double)work.bytes > 96e9) {
-        rt_set_error("rt_sites_sample_states: this call needs %.0f GB of scratch; split the batch "
-                     "or the draws", (double)work.bytes / 1e9);
-        return RT_ERR_UNSUPPORTED;
-    }
-    rt_ctx *ctx = m->ctx;
-    RT_HIP(hipSetDevice(ctx->device));
-    if (recompute_transitions) RT_TRY(rt_model_recompute_transitions(m));
-    RT_REQUIRE(m->have_P, "the model has no transition matrices yet");
-    hipStream_t st = ctx->stream;
-    if (s->layout != RT_LAYOUT_LANE && !s->expect_twin)
-        RT_TRY(rt_sites_twin_interpreter(s, &s->expect_twin));
-    RT_TRY(rt_scratch_reserve(ctx, work.bytes));
-    unsigned char *base = ctx->d_scratch;
-    RT_TRY(rt_sample_states_enqueue(m, s, seed, first_draw, ndraws, base, &work));
-    unsigned char *d_states = base + work.o_states;
-    int *d_status = (int *)(base + work.o_status);
+    size_t o_states = 0;
+    RT_TRY(rt_sample_states_plan(&p, ndraws, &o_states));
+    RT_TRY(post_begin(&p, recompute_transitions, true));
+    unsigned char *d_states = p.base + o_states;
+    RT_TRY(rt_sample_states_enqueue(&p, seed, first_draw, ndraws, d_states));
     // only the draws and the status cross PCIe
-    RT_HIP(hipMemcpyAsync(states, d_states, (size_t)ndraws * nsites * N, hipMemcpyDeviceToHost, st));
-    if (status) RT_HIP(hipMemcpyAsync(status, d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
-    RT_HIP(hipStreamSynchronize(st));
+    const size_t nsites = (size_t)p.nsites;
+    RT_HIP(hipMemcpyAsync(states, d_states, (size_t)ndraws * nsites * p.N, hipMemcpyDeviceToHost, p.st));
+    if (status) RT_HIP(hipMemcpyAsync(status, p.d_status, nsites * 4, hipMemcpyDeviceToHost, p.st));
+    RT_HIP(hipStreamSynchronize(p.st));
     return RT_OK;
 }

@@ -131,6 +131,17 @@ def check_branch_coefs(coefs, nstates):
     return np.ascontiguousarray(E)
 
 
+def check_draws(ndraws, seed, first_draw):
+    """The draw arguments of sample_states / sample_mappings as ints; ValueError unless there is
+    at least one draw and the seed and every draw number fit an unsigned 64-bit integer."""
+    ndraws, seed, first_draw = int(ndraws), int(seed), int(first_draw)
+    if ndraws < 1:
+        raise ValueError('ndraws must be at least 1')
+    if not (0 <= seed < 1 << 64 and 0 <= first_draw and first_draw + ndraws <= 1 << 64):
+        raise ValueError('seed and draw numbers are unsigned 64-bit integers')
+    return ndraws, seed, first_draw
+
+
 def check_rate_sets(Q, t, node_q, nstates, nnodes):
     """The arguments of TreeModel.set_rate_sets -> (Q f64[K, nq, n, n], t f64[K, nnodes],
     node_q int64[nnodes] or None).  Q is [K, n, n] or [K, nq, n, n]; t is [K, nnodes], or
@@ -806,6 +817,12 @@ class TreeModel(object):
             None if status is None else _ptr(status, c_int32)))
         return (dwell, rootp, trans, status) if return_status else (dwell, rootp, trans)
 
+    def _root_weights(self, batch):
+        """One-node trees are answered on the host: the root's observation times the root
+        weights, f64[nsites, n]."""
+        n = self.nstates
+        return batch._root_likelihoods(n) * (np.ones(n) if self._root_w is None else self._root_w)
+
     def posteriors(self, batch, node_sets=(), edge_sets=(), marginal_nodes=None, marginals=False,
                    recompute_transitions=False):
         """rt_sites_posteriors: _mcy_dense.kitchen_sink (_mcy_dense.py:57-230) for every site of
@@ -842,9 +859,7 @@ class TreeModel(object):
         if N == 1:
             # one node: the posterior is the normalised root weights times the root's
             # observation (kitchen_sink's len(T) == 1 case), no edges
-            L = batch._root_likelihoods(n)
-            w = np.ones(n) if self._root_w is None else self._root_w
-            wl = L * w
+            wl = self._root_weights(batch)
             tot = wl.sum(axis=1)
             ok = tot > 0
             status[~ok] = _lib.RT_SITE_ZERO_PROB
@@ -881,11 +896,7 @@ class TreeModel(object):
         a state for every node from the posterior.  The uniform of draw d, site i, preorder node
         v is _philox.philox_uniform(seed, first_draw + d, i * nnodes + v): draws [f, f + k) of one
         call are draws [0, k) of a call with first_draw = f.  Returns a SampledStates tuple."""
-        ndraws, seed, first_draw = int(ndraws), int(seed), int(first_draw)
-        if ndraws < 1:
-            raise ValueError('ndraws must be at least 1')
-        if not (0 <= seed < 1 << 64 and 0 <= first_draw and first_draw + ndraws <= 1 << 64):
-            raise ValueError('seed and draw numbers are unsigned 64-bit integers')
+        ndraws, seed, first_draw = check_draws(ndraws, seed, first_draw)
         n = self.nstates
         ta = self.tree
         N, S = ta.nnodes, batch.nsites
@@ -896,8 +907,7 @@ class TreeModel(object):
             # one node: the root weights times the root's observation, on the host with the
             # device's uniform and rule (the first state whose cumulative weight exceeds u * total)
             from ._philox import philox_uniform
-            L = batch._root_likelihoods(n)
-            w = (L * (np.ones(n) if self._root_w is None else self._root_w)).clip(min=0)
+            w = self._root_weights(batch).clip(min=0)
             cdf = np.cumsum(w, axis=1)
             total = cdf[:, -1]
             ok = (total > 0) & np.isfinite(total)
@@ -924,11 +934,7 @@ class TreeModel(object):
         SampledMappings tuple; with per_draw=False values and counts are None (they never leave
         the device) and only the means over the draws come back.  The means converge to
         branch_expectations(batch, coefs).values.  The rates must have been set with set_rates."""
-        ndraws, seed, first_draw = int(ndraws), int(seed), int(first_draw)
-        if ndraws < 1:
-            raise ValueError('ndraws must be at least 1')
-        if not (0 <= seed < 1 << 64 and 0 <= first_draw and first_draw + ndraws <= 1 << 64):
-            raise ValueError('seed and draw numbers are unsigned 64-bit integers')
+        ndraws, seed, first_draw = check_draws(ndraws, seed, first_draw)
         n = self.nstates
         E = check_branch_coefs(coefs, n)
         K = E.shape[0]
@@ -972,9 +978,7 @@ class TreeModel(object):
         status = np.zeros(S, dtype=np.int32)
         if N == 1:
             # one node, no edges: only the status of the sites is to be had
-            L = batch._root_likelihoods(n)
-            w = np.ones(n) if self._root_w is None else self._root_w
-            status[~((L * w).sum(axis=1) > 0)] = _lib.RT_SITE_ZERO_PROB
+            status[~(self._root_weights(batch).sum(axis=1) > 0)] = _lib.RT_SITE_ZERO_PROB
             return BranchExpectations(values, edge_sums, status, nodes)
         _lib.check(_lib.lib().rt_sites_branch_expectations(
             self._h, batch._h, 1 if recompute_transitions else 0, K, _ptr(E, c_double),
