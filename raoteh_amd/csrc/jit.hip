@@ -96,6 +96,57 @@ void emit_matvec(std::ostringstream &o, int n, int rec, const std::string &x,
     }
 }
 
+// accumulator slots a schedule names (rt_op::pop, low byte of rt_op::dst)
+int slot_count(const std::vector<rt_op> &ops)
+{
+    int nslots = 1;
+    for (const rt_op &op : ops) {
+        if (op.pop >= 0) nslots = std::max(nslots, op.pop + 1);
+        if (op.dst >= 0) nslots = std::max(nslots, (op.dst & 255) + 1);
+    }
+    return nslots;
+}
+
+// RAOTEH_JIT_TRACE=<workgroup>: diagnostics -- the waves of that workgroup stamp clocks into
+// the module's rt_trace (each MFMA generator says where)
+struct trace_opt {
+    bool on;
+    long wg;
+};
+
+trace_opt trace_from_env()
+{
+    const char *v = getenv("RAOTEH_JIT_TRACE");
+    return {v != nullptr, v ? atol(v) : 0};
+}
+
+// MFMA families, end of the kernel: log-likelihood, status and the tile's partial sums for
+// tile t (finish_site / wave_sum of prune.hip).  Lanes 0..15 of the wave that `guard` names
+// ("" or a condition ending in " && ") hold lik<t> of the tile's 16 sites.
+void emit_tile_epilogue(std::ostream &os, const std::string &guard, int t)
+{
+    os << "    {\n"
+          "    const long site = tile" << t << " * 16 + (lane & 15);\n"
+          "    const bool ok = lik" << t << " > 0.0;\n"
+          "    double sum = 0.0, nzero = 0.0;\n"
+          "    if (" << guard << "lane < 16 && tile" << t << " < nblocks && site < nsites) {\n"
+          "        loglik[site] = ok ? log(lik" << t << ") : -__builtin_inf();\n"
+          "        status[site] = (ok ? " << RT_SITE_OK << " : " << RT_SITE_ZERO_PROB
+       << ") | (negative" << t << " ? " << RT_SITE_NEGATIVE << " : 0);\n"
+          "        sum = ok ? log(lik" << t << ") : 0.0;\n"
+          "        nzero = ok ? 0.0 : 1.0;\n"
+          "    }\n"
+          "    for (int off = 32; off > 0; off >>= 1) {\n"
+          "        sum += __shfl_xor(sum, off, 64);\n"
+          "        nzero += __shfl_xor(nzero, off, 64);\n"
+          "    }\n"
+          "    if (" << guard << "lane == 0 && tile" << t << " < nblocks) {\n"
+          "        partial[tile" << t << " * 2] = sum;\n"
+          "        partial[tile" << t << " * 2 + 1] = nzero;\n"
+          "    }\n"
+          "    }\n";
+}
+
 }  // namespace
 
 // A pair load (rt_d2) of which only .x is used -- the last k-pair when the number of
@@ -135,11 +186,7 @@ std::string rt_jit_lane_source(const std::vector<rt_op> &ops, int n, int K, int 
     const int np = (n + 1) & ~1;
     const int hp = np / 2;
     const int nrec = (int)ops.size();
-    int nslots = 1;
-    for (const rt_op &op : ops) {
-        if (op.pop >= 0) nslots = std::max(nslots, op.pop + 1);
-        if (op.dst >= 0) nslots = std::max(nslots, (op.dst & 255) + 1);
-    }
+    const int nslots = slot_count(ops);
     std::ostringstream o;
     o << "// generated by raoteh_amd/csrc/jit.hip: " << nrec << " steps, " << n << " states, "
       << K << " observed nodes, prefetch distance " << D << " leaves / " << LA
@@ -232,8 +279,6 @@ std::string rt_jit_lane_source(const std::vector<rt_op> &ops, int n, int K, int 
     for (int s = 0; s < nslots; ++s)
         for (int j = 0; j < n; ++j) o << "    double a" << s << "_" << j << " = 1.0;\n";
 
-    // timing experiment only (RAOTEH_JIT_NOLOAD): every leaf re-reads slot 0
-    const bool noload = getenv("RAOTEH_JIT_NOLOAD") != nullptr;
     // the leaf vectors are read exactly once: non-temporal loads keep them from
     // displacing L2 / Infinity-Cache lines (C2: 36.5 -> 33 us); RAOTEH_JIT_NT=0 for A/B runs
     const bool nt = !(getenv("RAOTEH_JIT_NT") && atoi(getenv("RAOTEH_JIT_NT")) == 0);
@@ -246,7 +291,7 @@ std::string rt_jit_lane_source(const std::vector<rt_op> &ops, int n, int K, int 
             return;
         }
         for (int h = 0; h < hp; ++h) {
-            const long at = ((long)(noload ? 0 : k) * hp + h) * S;
+            const long at = ((long)k * hp + h) * S;
             if ((n & 1) && h == hp - 1)
                 o << "    const rt_d2 o" << k << "_" << h << " = "
                   << half_pair_load("g[" + std::to_string(at) + "]", nt) << ";\n";
@@ -490,261 +535,7 @@ std::string rt_jit_lane_source(const std::vector<rt_op> &ops, int n, int K, int 
 // quad-block table (rt_model::d_Pquad), each lane fetching element (lane >> 4, lane & 3)
 // of a 16-double block.  (The instruction's A-broadcast controls cbsz / abid have no
 // effect on the f64 form -- probed -- so the block is fetched replicated.)
-// ---------------------------------------------------------------------------
-// 4x4x4-block form, two tile groups in turn ("ping-pong", T even)
-// ---------------------------------------------------------------------------
-// One wave, one step: chain (T * KS^2 block MFMAs), then fold the result into the parent's
-// accumulator, prepare the next operands (accumulator x observation), park the next blocks
-// of P -- 450 to 900 cycles of the 2 500 a step took at T = 4 with the matrix pipe idle
-// (step stamps, tools/trace_c5.py).  Two waves per SIMD (T = 2) did not hide it: both run
-// the same program from the same start and stay in phase -- both in their chains (sharing
-// the pipe), then both outside (pipe idle): 2 C + E per pair of steps, the same as one
-// wave with twice the tiles (measured: 68 us either way; 60 us with the observations
-// served from L2, so the HBM stream is not what holds it).  Here the wave's T tiles are
-// two groups, and the program itself is out of phase: while group A's chain of step i
-// runs, the statements of group B's fold (step i - 1) and operand preparation (step i)
-// are issued one or two behind each block of MFMAs; under group B's chain, group A's
-// fold of step i, the park of the next blocks of P and group A's operands of step i + 1.
-// Any step order works (the other group's chain always stands between a group's chain
-// and its next one).  Same k order and fold order per tile as rt_jit_mfma_source:
-// bit-identical results.
-// RESULT: correct (the probe verification and the tests pass with it) and the tail between
-// chains is gone (80 cycles), but a chain of 2-MFMA blocks with a statement behind each
-// runs at 20-24 cycles per MFMA instead of 17.5, and a step takes the same 2 200 cycles.
-// Kept behind RAOTEH_JIT_PINGPONG=1 as the record of the experiment.
-static std::string rt_jit_mfma_quad_pp_source(const std::vector<rt_op> &ops, int n, int K, int T,
-                                              int D)
-{
-    const int KS = (n + 3) / 4;
-    const int KP = (KS + 1) / 2;
-    const int TG = T / 2;
-    const int NB = KS * KS;
-    const int nrec = (int)ops.size();
-    int nslots = 1;
-    for (const rt_op &op : ops) {
-        if (op.pop >= 0) nslots = std::max(nslots, op.pop + 1);
-        if (op.dst >= 0) nslots = std::max(nslots, (op.dst & 255) + 1);
-    }
-    const int QS = ((KS * KS * 16 + 127) / 128) * 128;    // rt_quad_stride(n)
-    const int QL = QS / 128;
-    const char *qa_env = getenv("RAOTEH_JIT_QAHEAD");
-    const int QA = std::max(1, qa_env ? atoi(qa_env) : 4);
-    const char *pd_env = getenv("RAOTEH_JIT_PARKDELAY");
-    const int PD = pd_env ? std::max(0, atoi(pd_env)) : 1;
-    std::ostringstream o;
-    o << "// generated by raoteh_amd/csrc/jit.hip (MFMA family, 4x4x4 blocks, two tile groups in "
-         "turn): " << nrec << " steps, " << n << " states, " << K << " observed nodes, " << T
-      << " tiles per wave, prefetch " << D << " leaves\n";
-    o << "typedef double rt_d2 __attribute__((ext_vector_type(2)));\n";
-    const char *trace_env = getenv("RAOTEH_JIT_TRACE");
-    const bool trace = trace_env != nullptr;
-    const long trace_wg = trace ? atol(trace_env) : 0;
-    if (trace) o << "__device__ unsigned long long rt_trace[" << (nrec + 1) * 3 << "];\n";
-    auto stamp = [&](int i, int which) {
-        if (!trace) return;
-        o << "    if (blockIdx.x == " << trace_wg << " && lane == 0) rt_trace[" << i * 3 + which
-          << "] = __builtin_readcyclecounter();\n";
-    };
-    o << "extern \"C\" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu("
-      << (T <= 2 ? "2, 2" : "1, 1") << ")))\n"
-         "rt_jit_prune(const double *__restrict__ Pfrag, const rt_d2 *__restrict__ obs,\n"
-         "             const double *__restrict__ root_w, double *__restrict__ loglik,\n"
-         "             int *__restrict__ status, double *__restrict__ partial,\n"
-         "             long nsites, long nblocks, long first_tile, long stride)\n{\n"
-         "    if (blockIdx.x % stride) return;      // a sparse launch: every stride-th workgroup works\n";
-    o << "    const int lane = threadIdx.x;\n";
-    if (trace)      // the constant 100 MHz clock next to the shader clock: the core frequency
-        o << "    if (blockIdx.x == " << trace_wg << " && lane == 0) rt_trace[" << nrec * 3 + 1
-          << "] = __builtin_amdgcn_s_memrealtime();\n";
-    o << "    const long tbase = first_tile + (long)(blockIdx.x / stride) * " << T << ";\n";
-    o << "    typedef const __attribute__((address_space(1))) rt_d2 *rt_glb2;\n";
-    o << "    __shared__ __attribute__((aligned(16))) double qa0[" << QS << "];\n";
-    o << "    __shared__ __attribute__((aligned(16))) double qa1[" << QS << "];\n";
-    o << "    rt_glb2 ag = (rt_glb2)Pfrag + lane;          // [step][QS doubles]\n";
-    o << "    const int alane = (lane >> 4) * 4 + (lane & 3);\n";
-    for (int t = 0; t < T; ++t) {
-        o << "    const long tile" << t << " = tbase + " << t << ";\n";
-        o << "    rt_glb2 g" << t << " = (rt_glb2)obs + (size_t)(tile" << t << " < nblocks ? tile" << t
-          << " : nblocks - 1) * " << (long)K * KP * 64 << " + lane;\n";
-    }
-    for (int j = 0; j < KS; ++j)
-        o << "    const bool rowok" << j << " = " << 4 * j << " + (lane >> 4) < " << n << ";\n";
-    for (int t = 0; t < T; ++t) {
-        o << "    double lik" << t << " = 0.0;\n    bool negative" << t << " = false;\n";
-        for (int sl = 0; sl < nslots; ++sl)
-            for (int j = 0; j < KS; ++j)
-                o << "    double a" << sl << "_" << t << "_" << j << " = 1.0;\n";
-        for (int j = 0; j < KS; ++j)
-            o << "    double x" << t << "_" << j << " = 0.0, c" << t << "_" << j << " = 0.0;\n";
-    }
-    auto emit_obs_load = [&](int k) {
-        for (int t = 0; t < T; ++t)
-            for (int q = 0; q < KP; ++q) {
-                const std::string at = "g" + std::to_string(t) + "[" +
-                                       std::to_string(((long)k * KP + q) * 64) + "]";
-                if ((KS & 1) && q == KP - 1)
-                    o << "    const rt_d2 o" << k << "_" << t << "_" << q << " = "
-                      << half_pair_load(at, true) << ";\n";
-                else
-                    o << "    const rt_d2 o" << k << "_" << t << "_" << q
-                      << " = __builtin_nontemporal_load(&" << at << ");\n";
-            }
-    };
-    auto emit_a_load = [&](int i) {
-        for (int j = 0; j < QL; ++j)
-            o << "    const rt_d2 V" << i << "_" << j << " = ag[" << ((long)i * QS / 2 + j * 64)
-              << "];\n";
-    };
-    typedef std::vector<std::string> stmts;
-    auto park = [&](int i, stmts &out) {           // blocks of step i: registers -> qa<i & 1>
-        for (int j = 0; j < QL; ++j)
-            out.push_back("((rt_d2 *)qa" + std::to_string(i & 1) + ")[" + std::to_string(j * 64) +
-                          " + lane] = V" + std::to_string(i) + "_" + std::to_string(j) + ";");
-    };
-    auto operands = [&](int g, int i, stmts &out) {   // x of group g for step i
-        const rt_op &op = ops[(size_t)i];
-        for (int t = g * TG; t < (g + 1) * TG; ++t)
-            for (int j = 0; j < KS; ++j) {
-                std::ostringstream e;
-                e << "x" << t << "_" << j << " = ";
-                std::ostringstream obs_j;
-                if (op.obs >= 0)
-                    obs_j << "o" << op.obs << "_" << t << "_" << (j >> 1) << ((j & 1) ? ".y" : ".x");
-                if (op.pop >= 0) {
-                    e << "a" << op.pop << "_" << t << "_" << j;
-                    if (op.obs >= 0) e << " * " << obs_j.str();
-                } else if (op.obs >= 0) {
-                    e << obs_j.str();
-                } else {
-                    e << "1.0";
-                }
-                e << ";";
-                out.push_back(e.str());
-            }
-    };
-    auto fold = [&](int g, int i, stmts &out) {       // result of group g's chain of step i
-        const rt_op &op = ops[(size_t)i];
-        const int d = op.dst & 255;
-        const bool first = (op.dst >> 8) != 0;
-        for (int t = g * TG; t < (g + 1) * TG; ++t)
-            for (int j = 0; j < KS; ++j)
-                out.push_back("a" + std::to_string(d) + "_" + std::to_string(t) + "_" +
-                              std::to_string(j) + (first ? " = c" : " *= c") + std::to_string(t) +
-                              "_" + std::to_string(j) + ";");
-    };
-    // chain of group g for step i; the statements of `shadow` are spread behind its blocks
-    auto chain = [&](int g, int i, const stmts &shadow) {
-        auto q_read = [&](int b) {
-            const int kk = b / KS, rq = b % KS;
-            o << "    const double Q" << i << "_" << g << "_" << rq << "_" << kk << " = qa" << (i & 1)
-              << "[" << (rq * KS + kk) * 16 << " + alane];\n";
-        };
-        for (int b = 0; b < std::min(QA, NB); ++b) q_read(b);
-        o << "    __builtin_amdgcn_sched_barrier(0);\n";
-        size_t done = 0;
-        for (int b = 0; b < NB; ++b) {
-            const int kk = b / KS, rq = b % KS;
-            if (b + QA < NB) q_read(b + QA);
-            for (int t = g * TG; t < (g + 1) * TG; ++t) {
-                o << "    c" << t << "_" << rq << " = __builtin_amdgcn_mfma_f64_4x4x4f64(Q" << i << "_"
-                  << g << "_" << rq << "_" << kk << ", x" << t << "_" << kk << ", ";
-                if (kk == 0) o << "0.0";
-                else o << "c" << t << "_" << rq;
-                o << ", 0, 0, 0);\n";
-            }
-            const size_t upto = shadow.size() * (size_t)(b + 1) / (size_t)NB;
-            for (; done < upto; ++done) o << "    " << shadow[done] << "\n";
-            o << "    __builtin_amdgcn_sched_barrier(0);\n";
-        }
-    };
-    for (int k = 0; k < std::min(D, K); ++k) emit_obs_load(k);
-    for (int i = 0; i < std::min(1 + PD, nrec); ++i)
-        if (ops[(size_t)i].dst >= 0) emit_a_load(i);
-    {
-        stmts pre;
-        if (nrec > 0 && ops[0].dst >= 0) park(0, pre);
-        operands(0, 0, pre);
-        for (const std::string &st : pre) o << "    " << st << "\n";
-    }
-    stmts pending;                                 // group B's fold of the previous step
-    for (int i = 0; i < nrec; ++i) {
-        const rt_op &op = ops[(size_t)i];
-        o << "    // step " << i << ": node " << op.node << "\n";
-        if (!getenv("RAOTEH_JIT_NO_PINS")) {
-            o << "    asm volatile(\"\" : \"+v\"(ag)";
-            for (int t = 0; t < T; ++t) o << ", \"+v\"(g" << t << ")";
-            o << " : \"v\"(x0_0));\n";
-        }
-        o << "    __builtin_amdgcn_sched_barrier(0);\n";
-        stamp(i, 0);
-        if (i + 1 + PD < nrec && ops[(size_t)(i + 1 + PD)].dst >= 0) emit_a_load(i + 1 + PD);
-        if (op.obs >= 0 && op.obs + D < K) emit_obs_load(op.obs + D);
-        if (op.dst < 0) {
-            // root reduction (_mc0_dense.py:184-209): flush what is pending, then all tiles
-            stmts rest = pending;
-            pending.clear();
-            operands(1, i, rest);
-            for (const std::string &st : rest) o << "    " << st << "\n";
-            for (int j = 0; j < KS; ++j)
-                o << "    const double w" << j << " = rowok" << j << " ? root_w[" << 4 * j
-                  << " + (lane >> 4)] : 0.0;\n";
-            for (int t = 0; t < T; ++t) {
-                o << "    {\n    double sacc = 0.0;\n";
-                for (int j = 0; j < KS; ++j) {
-                    o << "    negative" << t << " |= rowok" << j << " && (x" << t << "_" << j
-                      << " < 0.0);\n";
-                    o << "    sacc += w" << j << " * fmax(x" << t << "_" << j << ", 0.0);\n";
-                }
-                o << "    sacc += __shfl_xor(sacc, 16, 64);\n"
-                     "    sacc += __shfl_xor(sacc, 32, 64);\n"
-                     "    lik" << t << " = sacc;\n    }\n";
-            }
-            continue;
-        }
-        stmts under_a = pending;
-        pending.clear();
-        operands(1, i, under_a);
-        chain(0, i, under_a);
-        stamp(i, 1);
-        stmts under_b;
-        fold(0, i, under_b);
-        if (i + 1 < nrec && ops[(size_t)(i + 1)].dst >= 0) park(i + 1, under_b);
-        if (i + 1 < nrec) operands(0, i + 1, under_b);
-        chain(1, i, under_b);
-        stamp(i, 2);
-        fold(1, i, pending);
-    }
-    for (const std::string &st : pending) o << "    " << st << "\n";
-    stamp(nrec, 0);
-    if (trace)
-        o << "    if (blockIdx.x == " << trace_wg << " && lane == 0) rt_trace[" << nrec * 3 + 2
-          << "] = __builtin_amdgcn_s_memrealtime();\n";
-    for (int t = 0; t < T; ++t) {
-        o << "    {\n"
-             "    const long site = tile" << t << " * 16 + (lane & 15);\n"
-             "    const bool ok = lik" << t << " > 0.0;\n"
-             "    double sum = 0.0, nzero = 0.0;\n"
-             "    if (lane < 16 && tile" << t << " < nblocks && site < nsites) {\n"
-             "        loglik[site] = ok ? log(lik" << t << ") : -__builtin_inf();\n"
-             "        status[site] = (ok ? " << RT_SITE_OK << " : " << RT_SITE_ZERO_PROB
-          << ") | (negative" << t << " ? " << RT_SITE_NEGATIVE << " : 0);\n"
-             "        sum = ok ? log(lik" << t << ") : 0.0;\n"
-             "        nzero = ok ? 0.0 : 1.0;\n"
-             "    }\n"
-             "    for (int off = 32; off > 0; off >>= 1) {\n"
-             "        sum += __shfl_xor(sum, off, 64);\n"
-             "        nzero += __shfl_xor(nzero, off, 64);\n"
-             "    }\n"
-             "    if (lane == 0 && tile" << t << " < nblocks) {\n"
-             "        partial[tile" << t << " * 2] = sum;\n"
-             "        partial[tile" << t << " * 2 + 1] = nzero;\n"
-             "    }\n"
-             "    }\n";
-    }
-    o << "}\n";
-    return o.str();
-}
-
+//
 // sparse (quad form only; 1: one observed state per leaf, 2: allowed sets of one or two states;
 // the batch's `sparse_ok`): a leaf's message is a column of its transition matrix or the sum of
 // two, and the 4 x 4 blocks of that matrix are parked in this wave's LDS buffer anyway -- a leaf
@@ -755,23 +546,11 @@ std::string rt_jit_mfma_source(const std::vector<rt_op> &ops, int n, int K, int 
                                bool quad, int sparse)
 {
     if (sparse && !quad) return std::string();
-    // RAOTEH_JIT_PINGPONG=1: two tile groups in turn (T even).  Not the default: measured
-    // no faster (C5, T = 4: 69.8 us against 67.4; T = 2 on 2 048 tiles: 44.8 against 40.4)
-    {
-        const char *pp_env = getenv("RAOTEH_JIT_PINGPONG");
-        if (quad && T >= 2 && T % 2 == 0 && pp_env && atoi(pp_env) != 0 &&
-            !getenv("RAOTEH_JIT_FAKE_LEAFMAJOR") && !getenv("RAOTEH_JIT_FAKE_ONETILE"))
-            return rt_jit_mfma_quad_pp_source(ops, n, K, T, D);
-    }
     const int NT = (n + 15) / 16;
     const int KS = (n + 3) / 4;
     const int KP = (KS + 1) / 2;
     const int nrec = (int)ops.size();
-    int nslots = 1;
-    for (const rt_op &op : ops) {
-        if (op.pop >= 0) nslots = std::max(nslots, op.pop + 1);
-        if (op.dst >= 0) nslots = std::max(nslots, (op.dst & 255) + 1);
-    }
+    const int nslots = slot_count(ops);
     std::ostringstream o;
     o << "// generated by raoteh_amd/csrc/jit.hip (MFMA family" << (quad ? ", 4x4x4 blocks" : "")
       << (sparse == 2 ? ", leaf state pairs" : sparse ? ", leaf states" : "")
@@ -783,13 +562,11 @@ std::string rt_jit_mfma_source(const std::vector<rt_op> &ops, int n, int K, int 
     // RAOTEH_JIT_TRACE=<workgroup>: diagnostics (tools/trace_c5.py) -- that wave stamps the
     // shader clock at the start of every step, before its first MFMA and after its last
     // MFMA has been issued: rt_trace[step][3]
-    const char *trace_env = getenv("RAOTEH_JIT_TRACE");
-    const bool trace = trace_env != nullptr;
-    const long trace_wg = trace ? atol(trace_env) : 0;
-    if (trace) o << "__device__ unsigned long long rt_trace[" << (nrec + 1) * 3 << "];\n";
+    const trace_opt trace = trace_from_env();
+    if (trace.on) o << "__device__ unsigned long long rt_trace[" << (nrec + 1) * 3 << "];\n";
     auto stamp = [&](int i, int which) {
-        if (!trace) return;
-        o << "    if (blockIdx.x == " << trace_wg << " && lane == 0) rt_trace[" << i * 3 + which
+        if (!trace.on) return;
+        o << "    if (blockIdx.x == " << trace.wg << " && lane == 0) rt_trace[" << i * 3 + which
           << "] = __builtin_readcyclecounter();\n";
     };
     // up to two tiles per wave: two waves per SIMD (256 VGPRs); more tiles: one wave
@@ -805,8 +582,8 @@ std::string rt_jit_mfma_source(const std::vector<rt_op> &ops, int n, int K, int 
       << ")\n{\n"
          "    if (blockIdx.x % stride) return;      // a sparse launch: every stride-th workgroup works\n";
     o << "    const int lane = threadIdx.x;\n";
-    if (trace)      // the constant 100 MHz clock next to the shader clock: the core frequency
-        o << "    if (blockIdx.x == " << trace_wg << " && lane == 0) rt_trace[" << nrec * 3 + 1
+    if (trace.on)      // the constant 100 MHz clock next to the shader clock: the core frequency
+        o << "    if (blockIdx.x == " << trace.wg << " && lane == 0) rt_trace[" << nrec * 3 + 1
           << "] = __builtin_amdgcn_s_memrealtime();\n";
     o << "    const long tbase = first_tile + (long)(blockIdx.x / stride) * " << T << ";\n";
     o << "    typedef const __attribute__((address_space(1))) rt_d2 *rt_glb2;\n";
@@ -829,15 +606,8 @@ std::string rt_jit_mfma_source(const std::vector<rt_op> &ops, int n, int K, int 
     for (int t = 0; t < T; ++t) {
         o << "    const long tile" << t << " = tbase + " << t << ";\n";
         // tiles past the end re-read the last one; their results are dropped
-        // RAOTEH_JIT_FAKE_LEAFMAJOR: timing experiment only (wrong results): address the
-        // observations as if they were stored [leaf][tile] instead of [tile][leaf]
-        // RAOTEH_JIT_FAKE_ONETILE: timing experiment only (wrong results): every wave reads
-        // the observations of tiles 0..T-1 (L2-resident) -- the kernel without its HBM stream
-        o << "    rt_glb2 g" << t << " = (rt_glb2)obs + (size_t)("
-          << (getenv("RAOTEH_JIT_FAKE_ONETILE") ? std::to_string(t) + " + 0 * tile" + std::to_string(t)
-              : "tile" + std::to_string(t) + " < nblocks ? tile" + std::to_string(t) + " : nblocks - 1")
-          << ") * " << (getenv("RAOTEH_JIT_FAKE_LEAFMAJOR") ? (long)KP * 64 : (long)K * KP * 64)
-          << " + lane;\n";
+        o << "    rt_glb2 g" << t << " = (rt_glb2)obs + (size_t)(tile" << t << " < nblocks ? tile" << t
+          << " : nblocks - 1) * " << (long)K * KP * 64 << " + lane;\n";
     }
     // the root weights are loaded where the root step uses them, not here: KS doubles
     // that stay live through the whole walk are the first values the register allocator
@@ -861,19 +631,15 @@ std::string rt_jit_mfma_source(const std::vector<rt_op> &ops, int n, int K, int 
     auto emit_obs_load = [&](int k) {
         for (int t = 0; t < T; ++t)
             for (int q = 0; q < KP; ++q)
-                if (getenv("RAOTEH_JIT_FAKE_LEAFMAJOR"))
-                    o << "    const rt_d2 o" << k << "_" << t << "_" << q
-                      << " = __builtin_nontemporal_load(&g" << t << "[" << (long)k * KP * 64
-                      << " * nblocks + " << q * 64 << "]);\n";
-                else if ((KS & 1) && q == KP - 1)
+                if ((KS & 1) && q == KP - 1)
                     o << "    const rt_d2 o" << k << "_" << t << "_" << q << " = "
                       << half_pair_load("g" + std::to_string(t) + "[" +
                                         std::to_string(((long)k * KP + q) * 64) + "]", true)
                       << ";\n";
                 else
-                o << "    const rt_d2 o" << k << "_" << t << "_" << q
-                  << " = __builtin_nontemporal_load(&g" << t << "[" << ((long)k * KP + q) * 64
-                  << "]);\n";     // read once: keep L2 for the A fragments
+                    o << "    const rt_d2 o" << k << "_" << t << "_" << q
+                      << " = __builtin_nontemporal_load(&g" << t << "[" << ((long)k * KP + q) * 64
+                      << "]);\n";     // read once: keep L2 for the A fragments
     };
     auto emit_a_load = [&](int i) {
         if (quad) {
@@ -1039,7 +805,7 @@ std::string rt_jit_mfma_source(const std::vector<rt_op> &ops, int n, int K, int 
             };
             for (int b = 0; b < std::min(QA, NB); ++b) emit_q_read(b);
             if (QA > 0) o << "    __builtin_amdgcn_sched_barrier(0);\n";
-            if (trace) {
+            if (trace.on) {
                 // the stamp after the operands: x of every tile is in registers here
                 o << "    asm volatile(\"\" :: \"v\"(x" << T - 1 << "_" << KS - 1 << "));\n";
                 stamp(i, 1);
@@ -1086,32 +852,11 @@ std::string rt_jit_mfma_source(const std::vector<rt_op> &ops, int n, int K, int 
     }
 
     stamp(nrec, 0);
-    if (trace)
-        o << "    if (blockIdx.x == " << trace_wg << " && lane == 0) rt_trace[" << nrec * 3 + 2
+    if (trace.on)
+        o << "    if (blockIdx.x == " << trace.wg << " && lane == 0) rt_trace[" << nrec * 3 + 2
           << "] = __builtin_amdgcn_s_memrealtime();\n";
     // lanes 0..15 own the 16 sites of a tile (finish_site / wave_sum of prune.hip)
-    for (int t = 0; t < T; ++t) {
-        o << "    {\n"
-             "    const long site = tile" << t << " * 16 + (lane & 15);\n"
-             "    const bool ok = lik" << t << " > 0.0;\n"
-             "    double sum = 0.0, nzero = 0.0;\n"
-             "    if (lane < 16 && tile" << t << " < nblocks && site < nsites) {\n"
-             "        loglik[site] = ok ? log(lik" << t << ") : -__builtin_inf();\n"
-             "        status[site] = (ok ? " << RT_SITE_OK << " : " << RT_SITE_ZERO_PROB
-          << ") | (negative" << t << " ? " << RT_SITE_NEGATIVE << " : 0);\n"
-             "        sum = ok ? log(lik" << t << ") : 0.0;\n"
-             "        nzero = ok ? 0.0 : 1.0;\n"
-             "    }\n"
-             "    for (int off = 32; off > 0; off >>= 1) {\n"
-             "        sum += __shfl_xor(sum, off, 64);\n"
-             "        nzero += __shfl_xor(nzero, off, 64);\n"
-             "    }\n"
-             "    if (lane == 0 && tile" << t << " < nblocks) {\n"
-             "        partial[tile" << t << " * 2] = sum;\n"
-             "        partial[tile" << t << " * 2 + 1] = nzero;\n"
-             "    }\n"
-             "    }\n";
-    }
+    for (int t = 0; t < T; ++t) emit_tile_epilogue(o, "", t);
     o << "}\n";
     return o.str();
 }
@@ -1148,11 +893,7 @@ std::string rt_jit_mfma_split_source(const std::vector<rt_op> &ops, int n, int K
     const int KP = (KS + 1) / 2;
     const int nrec = (int)ops.size();
     const int XT = NT * 4 * 64;               // doubles of one tile's x image
-    int nslots = 1;
-    for (const rt_op &op : ops) {
-        if (op.pop >= 0) nslots = std::max(nslots, op.pop + 1);
-        if (op.dst >= 0) nslots = std::max(nslots, (op.dst & 255) + 1);
-    }
+    const int nslots = slot_count(ops);
     std::ostringstream o;
     o << "// generated by raoteh_amd/csrc/jit.hip (split-M MFMA family"
       << (sparse == 2 ? ", leaf state pairs" : sparse ? ", leaf states" : "")
@@ -1164,14 +905,12 @@ std::string rt_jit_mfma_split_source(const std::vector<rt_op> &ops, int n, int K
     // RAOTEH_JIT_TRACE=<workgroup>: diagnostics (tools/trace_c3.py) -- the waves of that
     // workgroup stamp the shader clock at the start of every step, after its barrier and
     // after its last MFMA has been issued: rt_trace[wave][step][3]
-    const char *trace_env = getenv("RAOTEH_JIT_TRACE");
-    const bool trace = trace_env != nullptr;
-    const long trace_wg = trace ? atol(trace_env) : 0;
-    if (trace)
+    const trace_opt trace = trace_from_env();
+    if (trace.on)
         o << "__device__ unsigned long long rt_trace[" << NT * (nrec + 1) * 3 << "];\n";
     auto stamp = [&](int i, int which) {
-        if (!trace) return;
-        o << "    if (blockIdx.x == " << trace_wg << " && lane == 0) rt_trace[(m * " << (nrec + 1)
+        if (!trace.on) return;
+        o << "    if (blockIdx.x == " << trace.wg << " && lane == 0) rt_trace[(m * " << (nrec + 1)
           << " + " << i << ") * 3 + " << which << "] = __builtin_readcyclecounter();\n";
     };
     o << "extern \"C\" __global__ void __launch_bounds__(" << 64 * NT
@@ -1387,28 +1126,7 @@ std::string rt_jit_mfma_split_source(const std::vector<rt_op> &ops, int n, int K
     stamp(nrec, 0);
 
     // lanes 0..15 of wave 0 own the 16 sites of a tile
-    for (int t = 0; t < T; ++t) {
-        o << "    {\n"
-             "    const long site = tile" << t << " * 16 + (lane & 15);\n"
-             "    const bool ok = lik" << t << " > 0.0;\n"
-             "    double sum = 0.0, nzero = 0.0;\n"
-             "    if (m == 0 && lane < 16 && tile" << t << " < nblocks && site < nsites) {\n"
-             "        loglik[site] = ok ? log(lik" << t << ") : -__builtin_inf();\n"
-             "        status[site] = (ok ? " << RT_SITE_OK << " : " << RT_SITE_ZERO_PROB
-          << ") | (negative" << t << " ? " << RT_SITE_NEGATIVE << " : 0);\n"
-             "        sum = ok ? log(lik" << t << ") : 0.0;\n"
-             "        nzero = ok ? 0.0 : 1.0;\n"
-             "    }\n"
-             "    for (int off = 32; off > 0; off >>= 1) {\n"
-             "        sum += __shfl_xor(sum, off, 64);\n"
-             "        nzero += __shfl_xor(nzero, off, 64);\n"
-             "    }\n"
-             "    if (m == 0 && lane == 0 && tile" << t << " < nblocks) {\n"
-             "        partial[tile" << t << " * 2] = sum;\n"
-             "        partial[tile" << t << " * 2 + 1] = nzero;\n"
-             "    }\n"
-             "    }\n";
-    }
+    for (int t = 0; t < T; ++t) emit_tile_epilogue(o, "m == 0 && ", t);
     o << "}\n";
     return o.str();
 }
@@ -1711,23 +1429,6 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
     const int KS = (n + 3) / 4;
     const int KP = (KS + 1) / 2;
     const int XT = NT * 4 * 64;               // doubles of one tile's x image
-    // n = 4 KS - 3: the last k-step holds ONE real state (the codon model: state 60 of 61), an
-    // MFMA of which three quarters multiply zeros.  Then the chain stops one k-step early and
-    // the last state's term is added on the vector ALU when the result is folded:
-    // c[r] = fma(P[16 m + 4 r + (lane >> 4)][n - 1], x[n - 1][lane & 15], c[r]) -- the matrix
-    // pipe adds the k-steps of a chain in order, each as fused multiply-adds in k order, and
-    // the three padded terms are exact zeros, so this is the chain's last MFMA bit for bit
-    // (the probe verification agrees: bit-identical at T = 5).  The four P values of a lane sit
-    // in its wave's A fragment of that k-step at lanes 4 r + (lane >> 4).
-    // MEASURED, AND NOT THE DEFAULT (RAOTEH_JIT_LASTK=1 turns it on): config 3, root halves,
-    // T = 5: 176.3 us against 173.1 with the MFMA -- the 16th MFMA of a chain costs 70 pipe
-    // cycles, its replacement 8 cross-lane reads per step + 5 LDS reads and 20 v_fma_f64 per
-    // step in the shadow, and 16 more live registers in a kernel that already keeps 250
-    // values in AGPRs; at T = 1 and T = 2 the register budget no longer holds (scratch: the
-    // kernel is rejected and the interpreter runs).
-    const bool lastk = (n % 4 == 1) && KS >= 4 && !sparse && !teams && getenv("RAOTEH_JIT_LASTK") &&
-                       atoi(getenv("RAOTEH_JIT_LASTK")) != 0;
-    const int KSM = lastk ? KS - 1 : KS;      // k-steps on the matrix pipe
     int nslots = 1;
     std::vector<std::vector<pipe_step>> programs;
     // (sparse: leaves as factors, see sparse_reduce; one plan per program -- the root's step
@@ -1787,9 +1488,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
       << (teams ? ", two teams of four waves" : "") << "\n";
     o << "typedef double rt_d2 __attribute__((ext_vector_type(2)));\n";
     o << "typedef double rt_d4 __attribute__((ext_vector_type(4)));\n";
-    const char *trace_env = getenv("RAOTEH_JIT_TRACE");
-    const bool trace = trace_env != nullptr;
-    const long trace_wg = trace ? atol(trace_env) : 0;
+    const trace_opt trace = trace_from_env();
     // [wave][step][t0 step start, t1 behind the barrier, t2 last MFMA issued]; teams: the waves
     // of team 1 follow team 0's, and a fourth stamp stands in front of the barrier (t1 - t3 is
     // the wait for the other team).  Row nrec_max, places 1 and 2: the constant 100 MHz clock at
@@ -1797,15 +1496,15 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
     const int TW = teams ? 4 : 3;
     const std::string trace_row = std::string("(") + (teams ? "(team * 4 + m)" : "m") + " * " +
                                   std::to_string(nrec_max + 1) + " + ";
-    if (trace) o << "__device__ unsigned long long rt_trace[" << (teams ? 2 : 1) * NT * (nrec_max + 1) * TW << "];\n";
+    if (trace.on) o << "__device__ unsigned long long rt_trace[" << (teams ? 2 : 1) * NT * (nrec_max + 1) * TW << "];\n";
     auto stamp = [&](int i, int which) {
-        if (!trace || which >= TW) return;
-        o << "    if (blockIdx.x == " << trace_wg << " && lane == 0) rt_trace[" << trace_row << i << ") * " << TW
+        if (!trace.on || which >= TW) return;
+        o << "    if (blockIdx.x == " << trace.wg << " && lane == 0) rt_trace[" << trace_row << i << ") * " << TW
           << " + " << which << "] = __builtin_readcyclecounter();\n";
     };
     auto stamp_real = [&](int which) {
-        if (!trace) return;
-        o << "    if (blockIdx.x == " << trace_wg << " && lane == 0) rt_trace[" << trace_row << nrec_max << ") * "
+        if (!trace.on) return;
+        o << "    if (blockIdx.x == " << trace.wg << " && lane == 0) rt_trace[" << trace_row << nrec_max << ") * "
           << TW << " + " << which << "] = __builtin_amdgcn_s_memrealtime();\n";
     };
     // NT <= 4 waves: one wave per SIMD and workgroup, three / two / one workgroups per CU at
@@ -1921,26 +1620,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
         for (int t = 0; t < T; ++t) {
             // (teams: wave 0 of the team that ran chain t)
             const std::string own = epi_teams ? (t < TA ? "team == 0 && " : "team == 1 && ") : "";
-            os << "    {\n"
-                  "    const long site = tile" << t << " * 16 + (lane & 15);\n"
-                  "    const bool ok = lik" << t << " > 0.0;\n"
-                  "    double sum = 0.0, nzero = 0.0;\n"
-                  "    if (" << own << "m == 0 && lane < 16 && tile" << t << " < nblocks && site < nsites) {\n"
-                  "        loglik[site] = ok ? log(lik" << t << ") : -__builtin_inf();\n"
-                  "        status[site] = (ok ? " << RT_SITE_OK << " : " << RT_SITE_ZERO_PROB
-               << ") | (negative" << t << " ? " << RT_SITE_NEGATIVE << " : 0);\n"
-                  "        sum = ok ? log(lik" << t << ") : 0.0;\n"
-                  "        nzero = ok ? 0.0 : 1.0;\n"
-                  "    }\n"
-                  "    for (int off = 32; off > 0; off >>= 1) {\n"
-                  "        sum += __shfl_xor(sum, off, 64);\n"
-                  "        nzero += __shfl_xor(nzero, off, 64);\n"
-                  "    }\n"
-                  "    if (" << own << "m == 0 && lane == 0 && tile" << t << " < nblocks) {\n"
-                  "        partial[tile" << t << " * 2] = sum;\n"
-                  "        partial[tile" << t << " * 2 + 1] = nzero;\n"
-                  "    }\n"
-                  "    }\n";
+            emit_tile_epilogue(os, own + "m == 0 && ", t);
         }
     };
     // the P record of a step is addressed by the step's position in the ORIGINAL schedule
@@ -1984,13 +1664,6 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
             else
                 os << "    const rt_d2 A" << k << "_" << q << " = " << at_lane("ag", at) << ";\n";
         }
-    };
-    // (lastk) this lane's four entries of column n - 1 of P, from the A fragment of issue step k
-    auto emit_pcol = [&](std::ostream &os, int k) {
-        if (!lastk) return;
-        for (int r = 0; r < 4; ++r)
-            os << "    const double pc" << k << "_" << r << " = __shfl(A" << k << "_" << ((KS - 1) >> 1)
-               << (((KS - 1) & 1) ? ".y" : ".x") << ", " << 4 * r << " + (lane >> 4), 64);\n";
     };
     // (sparse) the state words of the leaves, four leaves a word, loaded where first needed in
     // this program; then this lane's four entries of column `state` of the leaf's P (zero in the
@@ -2083,14 +1756,6 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
         const rt_op &op = st[(size_t)k].op;
         const int d = op.dst & 255;
         const bool first = (op.dst >> 8) != 0;
-        if (lastk)
-            for (int t = TLO; t < THI; ++t) {
-                os << "    const double xl" << k << "_" << t << " = xb" << k % 3 << "[" << t << "]["
-                   << (KS - 1) * 64 << " + (lane & 15)];\n";
-                for (int r = 0; r < 4; ++r)
-                    os << "    c" << k << "_" << t << "[" << r << "] = fma(pc" << k << "_" << r << ", xl" << k
-                       << "_" << t << ", c" << k << "_" << t << "[" << r << "]);\n";
-            }
         const std::vector<leaf_ref> &ld = lead_of(op);
         for (int t = TLO; t < THI; ++t)
             for (int r = 0; r < 4; ++r) {
@@ -2122,7 +1787,7 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
     // ---- prologue -----------------------------------------------------------------------
     for (int k = 0; k < GA; ++k) emit_gathers_of(o, k);
     for (int k = 0; k < std::min(D, (int)obs_order.size()); ++k) emit_obs_load(o, obs_order[(size_t)k]);
-    if (nrec > 0 && st[0].op.dst >= 0) { emit_a_load(o, 0); emit_pcol(o, 0); }
+    if (nrec > 0 && st[0].op.dst >= 0) emit_a_load(o, 0);
     o << "    {\n";
     if (st[0].op.dst >= 0) {
         emit_publish(o, 0);
@@ -2206,8 +1871,6 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
         if (fold_pending) { emit_fold(sh, i - 1); fold_pending = false; }
         if (have_next && !next_root && !next_late) emit_publish(sh, i + 1);
         if (teams && i + 1 < nrec && st[(size_t)(i + 1)].op.dst >= 0) emit_a_load(sh, i + 1, 0, KP / 2);
-        // (behind everything else: the fragment it reads was requested at the top of this shadow)
-        if (i + 1 < nrec && st[(size_t)(i + 1)].op.dst >= 0) emit_pcol(sh, i + 1);
         std::vector<std::string> shadow;
         {
             const std::string all = sh.str();
@@ -2221,13 +1884,13 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
         for (int t = TLO; t < THI; ++t) o << "    rt_d4 c" << i << "_" << t << " = {0.0, 0.0, 0.0, 0.0};\n";
         // MFMAs, MFMA results and LDS writes keep their order across these barriers; LDS
         // reads, global reads and scalar instructions may move (0x100 | 0x20 | 0x4)
-        const int nmfma = KSM * TT;
+        const int nmfma = KS * TT;
         const int lead = std::min(2 * TT, nmfma);          // MFMAs before the first shadow slice
         const int slots = std::max(1, nmfma - lead - 2 * TT);   // ... none behind the last 2 T
         size_t next_sh = 0;
         int issued = 0;
         const bool early_barrier = have_next && !next_root && !next_late && KS >= 4;
-        for (int kk = 0; kk < KSM; ++kk)
+        for (int kk = 0; kk < KS; ++kk)
             for (int t = TLO; t < THI; ++t) {
                 if (early_barrier && issued == nmfma - TT) {
                     // the shadow is empty: x of step i + 1 is on its way to LDS
@@ -2876,38 +2539,6 @@ int rt_launch_prune_jit(rt_model *m, rt_sites *s, const rt_fuse_args *fuse, cons
                                 &tile0, &stride1, &leafw, &Pesd};
     const bool solo_family = m->n <= 32 && s->mfma_solo;
     void **args = s->jit_sparse ? (solo_family ? args_solo_sparse : args_sparse) : args_dense;
-    if (s->jit_fn2) {
-        // main kernel: jit_split_tiles tiles, jit_tiles per wave (one wave per SIMD); the rest
-        // one tile per wave on the side stream, at the same time.  The timing events, when
-        // this launch is sampled, stand around both.
-        rt_ctx *ctx = m->ctx;
-        if (!ctx->stream2) {
-            RT_HIP(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-            RT_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-            RT_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-        }
-        if (ctx->ev_start) RT_HIP(hipEventRecord(ctx->ev_start, ctx->stream));
-        RT_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-        RT_HIP(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-        const unsigned main_groups = (unsigned)(s->jit_split_tiles / s->jit_tiles);
-        RT_HIP(hipModuleLaunchKernel((hipFunction_t)s->jit_fn, main_groups, 1, 1, 64, 1, 1, 0,
-                                     ctx->stream, args, nullptr));
-        // the few tail waves as every stride-th workgroup of a launch as wide as the main one:
-        // launched dense, the dispatcher put all of them on the first free slots it found -- a
-        // handful of CUs -- and those SIMDs carried six tiles (87 us instead of 67)
-        long tail0 = (long)s->jit_split_tiles;
-        const long tail_waves = (s->nblocks - s->jit_split_tiles + s->jit_tiles2 - 1) / s->jit_tiles2;
-        long stride = std::max<long>(1, (long)main_groups / tail_waves);
-        if (const char *v = getenv("RAOTEH_JIT_TAIL_STRIDE")) stride = std::max(1, atoi(v));
-        void *args2[] = {&Pord, &obs, &root_w, &loglik, &status, &partial, &nsites, &nblocks, &tail0,
-                         &stride};
-        RT_HIP(hipModuleLaunchKernel((hipFunction_t)s->jit_fn2, (unsigned)(tail_waves * stride), 1, 1,
-                                     64, 1, 1, 0, ctx->stream2, args2, nullptr));
-        RT_HIP(hipEventRecord(ctx->ev_join, ctx->stream2));
-        RT_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-        if (ctx->ev_stop) RT_HIP(hipEventRecord(ctx->ev_stop, ctx->stream));
-        return RT_OK;
-    }
     if (s->jit_halves) {
         // split-M family, root halves: 2 workgroups per tile, then the combine kernel (one
         // per tile); in a sampled launch each kernel gets its own begin / end stamps (the

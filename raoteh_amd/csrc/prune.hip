@@ -2070,10 +2070,6 @@ int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm,
                                       : s->compact_states == 2 ? ",masks" : "",
                      fuse_expm ? ",expm" : "");
         else
-            if (s->jit_fn2)
-                snprintf(jit_name, sizeof(s->kernel_name), "prune_tree_jit_mfma%s<%d,T%d+T%d>",
-                         s->jit_quad ? "4x4" : "", (int)m->n, s->jit_tiles, s->jit_tiles2);
-            else
             snprintf(jit_name, sizeof(s->kernel_name), "prune_tree_jit_mfma%s<%d,T%d%s>",
                      s->jit_quad ? "4x4" : "", (int)m->n, s->jit_tiles,
                      s->jit_sparse && s->jit_halves ? ",halves,leaf-states"

@@ -784,3 +784,18 @@ def test_library_kernels_have_no_scratch_beyond_the_known_few(tmp_path):
                 hot += 1
                 assert scratch == 0, (name, scratch)
     assert seen > 300 and hot >= 40, (seen, hot)
+
+
+def test_every_environment_knob_of_the_library_is_listed_in_the_readme():
+    """A knob nobody can find is dead code waiting to happen: every RAOTEH_* name the library
+    reads with getenv (raoteh_amd/csrc) stands in README.md's knob lists."""
+    csrc = os.path.join(ROOT, 'raoteh_amd', 'csrc')
+    read = set()
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith(('.hip', '.h', '.inc')):
+            with open(os.path.join(csrc, fn)) as f:
+                read.update(re.findall(r'getenv\(\s*"(RAOTEH_[A-Z0-9_]+)"', f.read()))
+    assert len(read) > 50, sorted(read)              # the scan found the sources
+    with open(os.path.join(ROOT, 'README.md')) as f:
+        listed = set(re.findall(r'RAOTEH_[A-Z0-9_]+', f.read()))
+    assert not read - listed, sorted(read - listed)

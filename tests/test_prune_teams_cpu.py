@@ -14,8 +14,7 @@ from raoteh_amd import _lib
 
 KNOBS = ('RAOTEH_JIT_TILES', 'RAOTEH_JIT_QUAD', 'RAOTEH_JIT_HALVES', 'RAOTEH_JIT_FOLD',
          'RAOTEH_JIT_SOURCE_SPARSE', 'RAOTEH_JIT_SOURCE_STATES', 'RAOTEH_JIT_SOURCE_MULTI',
-         'RAOTEH_JIT_SPLIT', 'RAOTEH_JIT_TEAMS', 'RAOTEH_JIT_TRACE', 'RAOTEH_JIT_LASTK',
-         'RAOTEH_JIT_GATHER_AHEAD')
+         'RAOTEH_JIT_SPLIT', 'RAOTEH_JIT_TEAMS', 'RAOTEH_JIT_TRACE', 'RAOTEH_JIT_GATHER_AHEAD')
 READELF = '/opt/rocm/lib/llvm/bin/llvm-readelf'
 
 # (label, environment, has a combine kernel)
