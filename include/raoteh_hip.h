@@ -460,6 +460,48 @@ int rt_sites_posteriors(rt_model *model, rt_sites *sites, int recompute_transiti
 int rt_sites_branch_expectations(rt_model *model, rt_sites *sites, int recompute_transitions,
             int64_t n_coefs, const double *coefs, double *values, double *edge_sums,
             int32_t *status);
+/* Per-branch likelihood profiles of a RESIDENT batch: what a line search, Brent or Newton per
+ * branch, a test for a zero-length branch or a likelihood-ratio interval of one branch asks of the
+ * likelihood, for every branch at once and without one rt_model_set_rates + rt_step per branch and
+ * trial length.  lengths f64[nnodes][npoints], rows in preorder (row 0, the root's, is ignored):
+ * 1..RT_MAX_PROFILE_POINTS trial lengths per branch, finite and >= 0.
+ *   values[i][v][g] = log L_i(t_v -> lengths[v][g]) - log L_i       f64[nsites][nnodes][npoints]
+ *                     the change of site i's log-likelihood when the branch above preorder node v
+ *                     alone takes the length lengths[v][g], every other branch staying at its
+ *                     resident length; the root's row is 0; -inf where the site has likelihood 0
+ *                     at that length
+ *   sums[v][g]      = sum_i w_i values[i][v][g]                     f64[nnodes][npoints]
+ *                     (w: rt_sites_set_weights, default 1; reduced on the device, fixed order;
+ *                     a site of weight 0 adds nothing, even where its value is -inf)
+ *   status[i]       : as rt_sites_branch_expectations (a site of zero likelihood:
+ *                     RT_SITE_ZERO_PROB, its values are 0 and it adds nothing to sums; 2: a live
+ *                     parent state over a non-positive denominator)
+ * One upward and one downward pass serve all branches and lengths: with J_v the joint endpoint
+ * posterior and P_v the resident transition matrix of the edge, L_i(tau) / L_i =
+ * sum_{a,b} J_v[a][b] expm(tau Q_v)[a][b] / P_v[a][b]; the (nnodes - 1) npoints exponentials are
+ * one launch.  The identity is exact while the resident t_v > 0 (where J_v / P_v has lost a state
+ * pair because P_v[a][b] = 0, Q_v cannot reach b from a at any length).  CAVEAT: at a resident
+ * t_v = 0, P_v is the identity and that argument fails -- the row of such an edge is NaN in values
+ * (at every site but those of zero likelihood, which stay 0) and in sums; give the edge a
+ * positive length to profile it.
+ * values, sums and status may each be NULL; only what is given crosses PCIe.  Every batch
+ * rt_sites_posteriors takes; rates from rt_model_set_rates (per-edge rate matrices included) or
+ * from rt_model_set_rates_spectral (n <= 64).  RT_ERR_INVALID: no rates (transitions set
+ * directly: on a model that never had rates, or after them with recompute_transitions == 0 --
+ * the resident rates would no longer describe P_v), npoints outside 1..RT_MAX_PROFILE_POINTS, a
+ * negative or non-finite length, lengths NULL, a batch of another model.  RT_ERR_SINGULAR: an
+ * exponential failed (tau Q_v not finite: a huge length); nothing returned is usable then.
+ * RT_ERR_UNSUPPORTED: a "rescale" batch, a batch of the generic
+ * kernel, a tree deeper than the fast kernels take, nnodes < 2, more than 96 GB of scratch.
+ * Synchronous; the model keeps its transitions and the batch its kernel, log-likelihoods, status
+ * and totals; two calls return the same bits.                                                  */
+#define RT_MAX_PROFILE_POINTS 64
+int rt_sites_branch_profiles(rt_model *model, rt_sites *sites, int recompute_transitions,
+            int64_t npoints, const double *lengths, double *values, double *sums,
+            int32_t *status);
+/* The branch lengths of the last rt_model_set_rates / rt_model_set_rates_spectral, f64[nnodes] in
+ * preorder (0 at the root).  RT_ERR_INVALID before either call.                               */
+int rt_model_get_branch_lengths(rt_model *model, double *t);
 /* _sample_mcy_dense.resample_states (_sample_mcy_dense.py:23-69, through
  * _sample_mc0_dense.resample_states, _sample_mc0_dense.py:20-98) for every site of a RESIDENT
  * batch: ndraws joint draws of a state for every node from the posterior given the observations.

@@ -539,6 +539,7 @@ static int model_run_expm(rt_model *m)
                                   m->n <= 4 ? 0 : 1, m->d_Pfrag, carry ? &red : nullptr,
                                   m->d_Pquad));
         m->have_P = true;
+        m->rates_current = true;
         m->frag_dirty = false;
         return rt_model_pack_pcol(m);
     }
@@ -546,6 +547,7 @@ static int model_run_expm(rt_model *m)
                           m->d_info, m->d_step_of_node, m->n <= 4 ? 0 : 1, m->d_Pfrag,
                           carry ? &red : nullptr, m->d_Pquad));
     m->have_P = true;
+    m->rates_current = true;
     m->frag_dirty = false;
     return rt_model_pack_pcol(m);
 }
@@ -825,6 +827,7 @@ extern "C" int rt_model_set_transitions(rt_model *m, const double *esd)
     RT_HIP(hipMemcpy(m->d_P, esd, (size_t)m->nnodes * m->n * m->n * 8,
                      hipMemcpyHostToDevice));
     m->have_P = true;
+    m->rates_current = false;
     m->frag_dirty = true;
     return rt_launch_pfrag(m);
 }

@@ -1,0 +1,395 @@
+// Per-branch likelihood profiles of a RESIDENT batch (rt_sites_branch_profiles): for every site i,
+// every edge p -> v and every length tau of a grid of that edge,
+//     log L_i(t_v -> tau) - log L_i,        every other branch at its resident length.
+//
+// The downward pass of posterior.hip / branch_expect.hip holds u = D_p / (P_v L_v) and L_v at
+// every step.  The site's likelihood is linear in the edge's transition matrix, and with
+// J[a][b] = u[a] P_v[a][b] L_v[b] the joint endpoint posterior,
+//     L_i(t_v -> tau) / L_i = sum_{a,b} J[a][b] P_v(tau)[a][b] / P_v[a][b]
+//                           = sum_b L_v[b] (P_v(tau)^T u)[b],      P_v(tau) = expm(tau Q_v):
+// the contraction of be_down_kernel with P_v(tau)^T in the place of G_k^T.  (Exact while the
+// resident t_v > 0: where (P_v L_v)[a] = 0, Q_v reaches no state of supp(L_v) from a at any
+// length.  At t_v = 0, P_v = I and u has lost the states the other lengths would reach: such an
+// edge's row is NaN.)  Here:
+//
+//   1. P_v(tau) of every edge and grid point in ONE launch of the model's own exponential
+//      (rt_launch_expm, or rt_launch_spectral for spectral rates) over tiled qidx / tau arrays,
+//      laid out [point][node][n][n] like the model's transition matrices;
+//   2. n > 4: rt_launch_pack_pt per grid point, the upward pass with L and M of every step stored,
+//      then bp_down_kernel: be_down_kernel with a run-time loop over the grid points; per step u
+//      is staged once, per point one n x n by n x 16 matrix-pipe product reduced over the states
+//      in a fixed order and stored (coalesced over the sites); the logs by all lanes at the end.
+//      n <= 4: bp_lane_kernel, one lane per site;
+//   3. profile_sums_kernel: the site-weighted sums per (node, point) in a fixed order; then, if
+//      the per-site array is asked for, its transpose to [site][node][point].
+//
+// Nothing of the batch or the model is written; two calls give the same bits.
+#include "common.h"
+#include "post_common.h"
+
+#include <algorithm>
+#include <cmath>
+#include <limits>
+#include <vector>
+
+namespace {
+
+constexpr int BP_CHUNK = 8;      // grid points between two barriers of bp_down_kernel
+
+// the stored value: 0 at a site of zero likelihood, NaN on an edge of resident length 0, else the
+// log of the ratio (-inf where it is not positive)
+__device__ __forceinline__ double bp_value(double ratio, bool zero, double tv)
+{
+    if (zero) return 0.0;
+    if (tv == 0.0) return __builtin_nan("");
+    return ratio > 0.0 ? log(ratio) : -__builtin_inf();
+}
+
+// steps[i] = {node, step of the parent, stream position of an observed leaf or -1, 1 if the node
+// has children}; the root is the last step.  GfragT: [point][step] A fragments of P(tau)^T;
+// tlen: the resident lengths [node]; out [node][point][site].
+template <int NT, int KS>
+__global__ void __launch_bounds__(64 * NT)
+bp_down_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT, int np, int nops,
+               const int4 *__restrict__ steps, const double *__restrict__ Larr,
+               const double *__restrict__ Marr, double *__restrict__ Darr,
+               const double *__restrict__ obs, int K, const double *__restrict__ root_w,
+               const double *__restrict__ tlen, int n, double *__restrict__ out,
+               int *__restrict__ status, long nsites, long nblocks)
+{
+    constexpr int KP = (KS + 1) / 2;
+    __shared__ double xb[NT * 4 * 64];
+    __shared__ double red[NT][16];
+    __shared__ double sums[2][BP_CHUNK][NT][16];
+    const int lane = threadIdx.x & 63;
+    const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long blk = blockIdx.x;
+    const long site = blk * 16 + (lane & 15);
+    const bool site_ok = site < nsites;
+    const bool writer = m == 0 && lane < 16 && site_ok;
+    bool bad = false, zero;
+    // root: D = w L / sum_states(w L); its row of the output is 0
+    {
+        const int i = nops - 1;
+        const size_t o = down_at<NT>(i, nblocks, blk, m, lane);
+        double wl[4], s = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * m + 4 * r + (lane >> 4);
+            const double w = row < n ? (root_w ? root_w[row] : 1.0) : 0.0;
+            wl[r] = w * Larr[o + r * 64];
+            s += wl[r];
+        }
+        down_part(red, m, lane, s);
+        __syncthreads();
+        const double tot = down_total<NT>(red, lane & 15);
+        zero = !(tot > 0.0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Darr[o + r * 64] = zero ? 0.0 : wl[r] / tot;
+        if (writer) {
+            if (zero) atomicOr(&status[site], RT_SITE_ZERO_PROB);
+            double *row = out + (size_t)steps[i].x * np * nsites + site;
+            for (int g = 0; g < np; ++g) row[(size_t)g * nsites] = 0.0;
+        }
+    }
+    const size_t frag = ((size_t)m * KP * 64 + lane) * 2;
+    constexpr size_t ASTRIDE = (size_t)NT * KP * 128;
+    const double *og = obs + (size_t)blk * K * (KP * 128) + lane * 2;
+    int par = 0;                                 // the half of `sums` the next chunk writes
+    for (int i = nops - 2; i >= 0; --i) {
+        const int4 st = steps[i];
+        const size_t o = down_at<NT>(i, nblocks, blk, m, lane);
+        double L[4], u[4];
+        down_L<KP>(st.z, og, Larr, o, m, L);
+        down_u(Darr, down_at<NT>(st.y, nblocks, blk, m, lane), Marr, o, u, bad);
+        down_stage(xb, m, lane, u);
+        double a[2 * KP];
+        if (st.w) {                              // D_v = (P^T u) * L for the children's steps
+            down_frag<KP>(PfragT + (size_t)i * ASTRIDE + frag, a);
+            const double4_t acc = down_product<KS>(a, xb, lane);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Darr[o + r * 64] = acc[r] * L[r];
+        }
+        double *row = out + (size_t)st.x * np * nsites + site;
+        // per grid point: sum_b L[b] (P(tau)^T u)[b], one fragment table live at a time.  A chunk
+        // of points goes into one half of `sums`; after the barrier wave 0 adds the waves in
+        // order and stores the ratio while the next chunk fills the other half (the barrier after
+        // that chunk is behind these reads: one barrier per chunk).  The logs wait for the end
+        // of the kernel, where nothing of the pass is live in registers
+        for (int g0 = 0; g0 < np; g0 += BP_CHUNK) {
+            const int cnt = min(BP_CHUNK, np - g0);
+            for (int j = 0; j < cnt; ++j) {
+                down_frag<KP>(GfragT + ((size_t)(g0 + j) * nops + i) * ASTRIDE + frag, a);
+                const double4_t y = down_product<KS>(a, xb, lane);
+                double v = 0.0;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v += y[r] * L[r];
+                down_part(sums[par][j], m, lane, v);
+            }
+            __syncthreads();
+            if (writer)
+                for (int j = 0; j < cnt; ++j)
+                    row[(size_t)(g0 + j) * nsites] = down_total<NT>(sums[par][j], lane);
+            par ^= 1;
+        }
+    }
+    if (bad && site_ok) atomicOr(&status[site], 2);
+    // the tile's ratios -> values, by all waves: lane group q of the workgroup takes the rows
+    // (node, point) q, q + 4 NT, ... of its site (the barrier: wave 0's stores are visible)
+    __syncthreads();
+    if (site_ok) {
+        const long rows = (long)(nops - 1) * np;
+        for (long k = 4 * m + (lane >> 4); k < rows; k += 4 * NT) {
+            const int node = steps[k / np].x;
+            double *x = out + ((size_t)node * np + k % np) * nsites + site;
+            *x = bp_value(*x, zero, tlen[node]);
+        }
+    }
+}
+
+// n <= 4: one lane per site; arrays [node][state][site], nodes in preorder; G [point][node][N][N]
+// (the same address in every lane: the scalar path)
+template <int N>
+__global__ void __launch_bounds__(256)
+bp_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const double *__restrict__ G,
+               int np, const int *__restrict__ parent, const int *__restrict__ node_k,
+               const void *__restrict__ obs, int compact, int K, int block_sites,
+               const double *__restrict__ root_w, const double *__restrict__ tlen,
+               double *__restrict__ Larr, double *__restrict__ Marr, double *__restrict__ Darr,
+               double *__restrict__ out, int *__restrict__ status)
+{
+    const long site = (long)blockIdx.x * 256 + threadIdx.x;
+    if (site >= nsites) return;
+    auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
+    lane_up<N, true>(nnodes, nsites, site, P, parent, node_k, obs, compact, K, block_sites, Larr, Marr);
+    // down: the root, then every node after its parent
+    bool zero;
+    {
+        double d[N];
+        zero = lane_root<N>(nsites, site, root_w, Larr, Darr, d);
+        if (zero) status[site] |= RT_SITE_ZERO_PROB;
+        for (int g = 0; g < np; ++g) out[(size_t)g * nsites + site] = 0.0;
+    }
+    bool bad = false;
+    for (int v = 1; v < nnodes; ++v) {
+        const int p = parent[v];
+        const double *Pv = P + (size_t)v * N * N;
+        double u[N], L[N];
+        lane_u<N>(nsites, site, p, v, Darr, Marr, u, bad);
+#pragma unroll
+        for (int b = 0; b < N; ++b) {
+            L[b] = Larr[idx(v, b)];
+            double y = 0.0;
+#pragma unroll
+            for (int a = 0; a < N; ++a) y += Pv[a * N + b] * u[a];
+            Darr[idx(v, b)] = y * L[b];
+        }
+        const double tv = tlen[v];
+        for (int g = 0; g < np; ++g) {
+            const double *Gv = G + ((size_t)g * nnodes + v) * N * N;
+            double t = 0.0;
+#pragma unroll
+            for (int b = 0; b < N; ++b) {
+                double y = 0.0;
+#pragma unroll
+                for (int a = 0; a < N; ++a) y += Gv[a * N + b] * u[a];
+                t += y * L[b];
+            }
+            out[((size_t)v * np + g) * nsites + site] = bp_value(t, zero, tv);
+        }
+    }
+    if (bad) status[site] |= 2;
+}
+
+// one workgroup per (node, point), the order of edge_sums_kernel: thread j adds sites j, j + 256,
+// ... in order, then the 256 partial sums by halves (fixed rounding).  Sites of zero likelihood
+// and of weight 0 are skipped; the row of an edge of resident length 0 is NaN.
+__global__ void __launch_bounds__(256)
+profile_sums_kernel(int np, long nsites, const double *__restrict__ values,
+                    const double *__restrict__ weights, const int *__restrict__ status,
+                    const double *__restrict__ tlen, double *__restrict__ sums)
+{
+    __shared__ double part[256];
+    const int row = blockIdx.x, v = row / np, tid = threadIdx.x;
+    const double *x = values + (size_t)row * nsites;
+    double acc = 0.0;
+    for (long i = tid; i < nsites; i += 256)
+    {
+        const double w = weights ? weights[i] : 1.0;       // (w = 0: not -inf * 0 = NaN)
+        if (w != 0.0 && !(status[i] & RT_SITE_ZERO_PROB)) acc += w * x[i];
+    }
+    part[tid] = acc;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) part[tid] += part[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) sums[row] = (v > 0 && tlen[v] == 0.0) ? __builtin_nan("") : part[0];
+}
+
+// [row][site] -> [site][row] for the caller's per-site array, 32 x 32 tiles through LDS
+__global__ void __launch_bounds__(256)
+profile_transpose_kernel(long nrows, long nsites, const double *__restrict__ in,
+                         double *__restrict__ outT)
+{
+    __shared__ double tile[32][33];
+    const long s0 = (long)blockIdx.x * 32, r0 = (long)blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int k = ty; k < 32; k += 8)
+        if (r0 + k < nrows && s0 + tx < nsites) tile[k][tx] = in[(size_t)(r0 + k) * nsites + s0 + tx];
+    __syncthreads();
+    for (int k = ty; k < 32; k += 8)
+        if (s0 + k < nsites && r0 + tx < nrows) outT[(size_t)(s0 + k) * nrows + r0 + tx] = tile[tx][k];
+}
+
+// the model keeps the branch lengths of the last rt_model_set_rates / _spectral on the host
+inline bool model_has_rates(const rt_model *m)
+{
+    return (m->d_Q || m->spectral) && (int64_t)m->h_t.size() == m->nnodes &&
+           (int64_t)m->h_qidx.size() == m->nnodes;
+}
+
+}  // namespace
+
+extern "C" int rt_model_get_branch_lengths(rt_model *m, double *t)
+{
+    RT_REQUIRE(m && t, "null pointer");
+    RT_REQUIRE(model_has_rates(m),
+               "rt_model_get_branch_lengths: no rates have been set (rt_model_set_rates or "
+               "rt_model_set_rates_spectral)");
+    std::copy(m->h_t.begin(), m->h_t.end(), t);
+    return RT_OK;
+}
+
+extern "C" int rt_sites_branch_profiles(rt_model *m, rt_sites *s, int recompute_transitions,
+                                        int64_t npoints, const double *lengths, double *values,
+                                        double *sums, int32_t *status)
+{
+    post_pass p;                                 // (alive until the synchronisation below)
+    RT_TRY(post_open(&p, "rt_sites_branch_profiles", m, s));
+    RT_REQUIRE(model_has_rates(m),
+               "rt_sites_branch_profiles: no rates have been set (rt_model_set_rates or "
+               "rt_model_set_rates_spectral; a model with transitions set directly has no rate "
+               "matrix to exponentiate at another length)");
+    RT_REQUIRE(m->rates_current || recompute_transitions,
+               "rt_sites_branch_profiles: the transitions were set directly after the rates "
+               "(rt_model_set_transitions): the resident rates and lengths no longer describe them; "
+               "set the rates again or pass recompute_transitions");
+    RT_REQUIRE(lengths, "rt_sites_branch_profiles: lengths is NULL");
+    RT_REQUIRE(npoints >= 1 && npoints <= RT_MAX_PROFILE_POINTS,
+               "rt_sites_branch_profiles: 1..%d grid points per branch (%lld here)",
+               RT_MAX_PROFILE_POINTS, (long long)npoints);
+    const int64_t n = p.n, N = p.N, nsites = p.nsites;
+    const int np = (int)npoints;
+    for (int64_t v = 1; v < N; ++v)
+        for (int g = 0; g < np; ++g) {
+            const double x = lengths[v * np + g];
+            RT_REQUIRE(std::isfinite(x) && x >= 0.0,
+                       "rt_sites_branch_profiles: length %d of node %lld is negative or not finite",
+                       g, (long long)v);
+        }
+    RT_TRY(post_layout(&p, true));
+    if (m->spectral ? n > 64 : n > RT_MAX_EXPM_STATES) {
+        rt_set_error("rt_sites_branch_profiles: n=%lld is beyond what the model's exponential takes",
+                     (long long)n);
+        return RT_ERR_UNSUPPORTED;
+    }
+    rt_ctx *ctx = p.ctx;
+    const size_t nn = (size_t)n * n, rows = (size_t)N * np, cnt = (size_t)np * N;
+    // scratch: L, M, D of every node and site (post_layout), the result, the grid matrices, their
+    // fragments and the tiled arguments of the exponential
+    const size_t tab = (size_t)p.nops * p.NT * p.KP * 128 * 8;
+    post_plan &plan = p.plan;
+    const size_t o_val = plan.take(rows * nsites * 8);
+    const size_t o_valT = plan.take(values ? rows * nsites * 8 : 8);
+    const size_t o_sum = plan.take(rows * 8);
+    const size_t o_G = plan.take(cnt * nn * 8);
+    const size_t o_tau = plan.take(cnt * 8), o_qidx = plan.take(cnt * 4);
+    const size_t o_info = plan.take(cnt * 8);
+    const size_t o_GT = p.lane ? plan.take(8) : plan.take((size_t)np * tab);
+    RT_TRY(post_begin(&p, recompute_transitions));
+    hipStream_t st = p.st;
+    unsigned char *base = p.base;
+    double *d_val = (double *)(base + o_val), *d_valT = (double *)(base + o_valT);
+    double *d_sum = (double *)(base + o_sum), *d_G = (double *)(base + o_G);
+    double *d_tau = (double *)(base + o_tau);
+    int32_t *d_qidx = (int32_t *)(base + o_qidx);
+    int32_t *d_info = (int32_t *)(base + o_info);
+    int *d_status = p.d_status;
+    // (host buffers of the asynchronous copies: alive until the synchronisation below)
+    std::vector<double> tau(cnt, 0.0);
+    std::vector<int32_t> qidx(cnt), internal((size_t)N, 0), info(2 * cnt, 0);
+    for (int g = 0; g < np; ++g)
+        for (int64_t v = 0; v < N; ++v) {
+            qidx[(size_t)g * N + v] = m->h_qidx[(size_t)v];      // (the root's: -1, a zero matrix)
+            if (v) tau[(size_t)g * N + v] = lengths[v * np + g];
+        }
+    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
+    RT_HIP(hipMemcpyAsync(d_tau, tau.data(), cnt * 8, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemcpyAsync(d_qidx, qidx.data(), cnt * 4, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemsetAsync(d_info, 0, cnt * 8, st));
+    // 1. the grid matrices: one launch of the route the model's own transitions take
+    if (m->spectral)
+        RT_TRY(rt_launch_spectral(ctx, n, (int64_t)cnt, m->d_spec, m->d_spec + 2 * nn, m->d_spec + nn,
+                                  m->spectral_has_D ? m->d_spec + 2 * nn + n : nullptr, d_qidx, d_tau,
+                                  d_G, d_info, nullptr, 0, nullptr));
+    else
+        RT_TRY(rt_launch_expm(ctx, n, (int64_t)cnt, m->d_Q, d_qidx, d_tau, d_G, d_info, nullptr, 0,
+                              nullptr));
+    RT_HIP(hipMemcpyAsync(info.data(), d_info, cnt * 8, hipMemcpyDeviceToHost, st));
+    RT_TRY(post_up(&p, internal.data(), true));
+    if (p.lane) {
+        const int *d_tab = p.d_ptab;
+        RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
+            hipLaunchKernelGGL((bp_lane_kernel<decltype(nv)::value>), dim3((unsigned)((nsites + 255) / 256)),
+                               dim3(256), 0, st, (int)N, (long)nsites, (const double *)m->d_P,
+                               (const double *)d_G, np, d_tab, d_tab + N, (const void *)s->d_obs,
+                               s->compact_states, (int)s->nobs, s->block_sites,
+                               (const double *)m->d_root, (const double *)m->d_t, p.d_L, p.d_M, p.d_D,
+                               d_val, d_status);
+            return RT_OK;
+        }));
+    } else {
+        const rt_sites *x = p.x;
+        double *d_GT = (double *)(base + o_GT);
+        for (int g = 0; g < np; ++g)
+            RT_TRY(rt_launch_pack_pt(ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab, d_G + (size_t)g * N * nn,
+                                     d_GT + (size_t)g * (tab / 8)));
+        RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
+            constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
+            hipLaunchKernelGGL((bp_down_kernel<NT, KS>), dim3((unsigned)x->nblocks), dim3(64 * NT), 0, st,
+                               (const double *)p.d_PT, (const double *)d_GT, np, p.nops,
+                               (const int4 *)p.d_steps, (const double *)p.d_L, (const double *)p.d_M,
+                               p.d_D, (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
+                               (const double *)m->d_t, (int)n, d_val, d_status, (long)x->nsites,
+                               (long)x->nblocks);
+            return RT_OK;
+        }));
+    }
+    RT_HIP(hipGetLastError());
+    // 3. the weighted site sums; only what was asked for crosses PCIe
+    if (sums) {
+        hipLaunchKernelGGL(profile_sums_kernel, dim3((unsigned)rows), dim3(256), 0, st, np, (long)nsites,
+                           (const double *)d_val, (const double *)s->d_weights, (const int *)d_status,
+                           (const double *)m->d_t, d_sum);
+        RT_HIP(hipGetLastError());
+        RT_HIP(hipMemcpyAsync(sums, d_sum, rows * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (values) {
+        hipLaunchKernelGGL(profile_transpose_kernel,
+                           dim3((unsigned)((nsites + 31) / 32), (unsigned)((rows + 31) / 32)), dim3(256),
+                           0, st, (long)rows, (long)nsites, (const double *)d_val, d_valT);
+        RT_HIP(hipGetLastError());
+        RT_HIP(hipMemcpyAsync(values, d_valT, rows * nsites * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (status) RT_HIP(hipMemcpyAsync(status, d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipStreamSynchronize(st));
+    // an exponential the kernel gave up on (tau Q not finite): its row holds nothing usable
+    for (size_t j = 0; j < cnt; ++j)
+        if (info[2 * j] < 0) {
+            rt_set_error("rt_sites_branch_profiles: expm failed for node %lld at length %g (a "
+                         "non-finite entry or norm of tau Q)", (long long)(j % (size_t)N), tau[j]);
+            return RT_ERR_SINGULAR;
+        }
+    return RT_OK;
+}

@@ -187,6 +187,9 @@ struct rt_model {
     int32_t *d_qidx_step = nullptr;
     double *d_t_step = nullptr;
     bool have_P = false;
+    // the transition matrices are those of the resident rates (rt_model_set_rates / _spectral,
+    // a recompute); rt_model_set_transitions clears it: the rates no longer describe P
+    bool rates_current = false;
     bool frag_dirty = true;
     int live_batches = 0;           // site batches created from this model and not yet destroyed
     void *expect_state = nullptr;   // expect_mfma.hip: device buffers of rt_expect_step (lazy)

@@ -2047,6 +2047,7 @@ int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm,
         if (!rt_take_pending_reduce(ctx, &fuse.red) && ctx->pending_reduce) RT_TRY(rt_flush_reduce(ctx));
         std::swap(s->d_partial, s->d_partial_alt);
         m->have_P = true;
+        m->rates_current = true;
         m->frag_dirty = false;        // workgroup 0 leaves the step-ordered table behind
     } else {
         fuse_expm = false;

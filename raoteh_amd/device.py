@@ -131,6 +131,93 @@ def check_branch_coefs(coefs, nstates):
     return np.ascontiguousarray(E)
 
 
+# TreeModel.branch_profiles: lengths and sums [nnodes, G], values [nsites, nnodes, G] (or None),
+# all keyed by the edge's child in the preorder `nodes` (the root's row: lengths 0, values 0);
+# values[i, v, g] = log L_i(t_v -> lengths[v, g]) - log L_i, NaN in the row of an edge whose
+# resident length is 0; status as Posteriors
+BranchProfiles = collections.namedtuple('BranchProfiles', 'nodes lengths sums values status')
+
+
+def check_profile_lengths(lengths, nnodes, factors=None, resident=None, tree=None):
+    """The grid of TreeModel.branch_profiles -> f64[nnodes, G], C-contiguous, for
+    rt_sites_branch_profiles.  Exactly one of `lengths` and `factors`:
+    lengths  an absolute [nnodes, G] array in preorder (row 0, the root's, is ignored and comes
+             back as zeros), or a dict edge -> sequence of G lengths, an edge being the preorder
+             index of its child, or with `tree` (a TreeArrays) a pair of tree nodes in either
+             direction; edges the dict leaves out stay at their `resident` length;
+    factors  a 1-D sequence of G multipliers of every branch's `resident` length f64[nnodes].
+    ValueError for both or neither, another shape, G outside 1..RT_MAX_PROFILE_POINTS, or a
+    length that is negative or not finite."""
+    if (lengths is None) == (factors is None):
+        raise ValueError('exactly one of lengths and factors must be given')
+    if resident is not None:
+        resident = np.asarray(resident, dtype=np.float64)
+        if resident.shape != (nnodes,):
+            raise ValueError('the resident lengths must have one entry per node')
+    if factors is not None:
+        if resident is None:
+            raise ValueError('factors multiply the resident branch lengths, which are not known')
+        try:
+            f = np.array(factors, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('factors must be a 1-D sequence of numbers')
+        if f.ndim != 1:
+            raise ValueError('factors must be 1-D, not %s' % (f.shape,))
+        grid = resident[:, None] * f[None, :]
+    elif isinstance(lengths, dict):
+        rows = {}
+        for edge, seq in lengths.items():
+            if isinstance(edge, tuple):
+                if tree is None or len(edge) != 2:
+                    raise ValueError('an edge given as a pair of nodes needs the tree')
+                try:
+                    a, b = (tree.node_to_index[x] for x in edge)
+                except KeyError:
+                    raise ValueError('%r is not an edge of the tree' % (edge,))
+                if tree.parent[b] == a:
+                    v = b
+                elif tree.parent[a] == b:
+                    v = a
+                else:
+                    raise ValueError('%r is not an edge of the tree' % (edge,))
+            else:
+                v = int(edge)
+                if v != edge or not 1 <= v < nnodes:
+                    raise ValueError('edge %r: the preorder index of a non-root node' % (edge,))
+            try:
+                row = np.array(seq, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError('the lengths of edge %r must be a sequence of numbers' % (edge,))
+            if row.ndim != 1 or v in rows:
+                raise ValueError('edge %r: one 1-D sequence of lengths per edge' % (edge,))
+            rows[v] = row
+        sizes = set(len(r) for r in rows.values())
+        if len(sizes) != 1:
+            raise ValueError('every edge needs the same number of lengths (at least one edge)')
+        if len(rows) < nnodes - 1 and resident is None:
+            raise ValueError('edges left out stay at their resident length, which is not known')
+        grid = np.zeros((nnodes, sizes.pop()))
+        if resident is not None:
+            grid[:] = resident[:, None]
+        for v, row in rows.items():
+            grid[v] = row
+    else:
+        try:
+            grid = np.array(lengths, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('lengths must be a [%d, G] array or a dict edge -> sequence' % nnodes)
+        if grid.ndim != 2 or grid.shape[0] != nnodes:
+            raise ValueError('lengths must be [%d, G], not %s' % (nnodes, grid.shape))
+    if not 1 <= grid.shape[1] <= _lib.RT_MAX_PROFILE_POINTS:
+        raise ValueError('between 1 and %d lengths per branch (%d here)'
+                         % (_lib.RT_MAX_PROFILE_POINTS, grid.shape[1]))
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    grid[0] = 0.0
+    if not (np.isfinite(grid).all() and (grid >= 0).all()):
+        raise ValueError('the lengths must be finite and not negative')
+    return grid
+
+
 def check_draws(ndraws, seed, first_draw):
     """The draw arguments of sample_states / sample_mappings as ints; ValueError unless there is
     at least one draw and the seed and every draw number fit an unsigned 64-bit integer."""
@@ -985,6 +1072,41 @@ class TreeModel(object):
             None if values is None else _ptr(values, c_double), _ptr(edge_sums, c_double),
             _ptr(status, c_int32)))
         return BranchExpectations(values, edge_sums, status, nodes)
+
+    def branch_lengths(self):
+        """The branch lengths of the last set_rates / set_rates_spectral as the device holds
+        them (rt_model_get_branch_lengths), f64[nnodes] in preorder, 0 at the root."""
+        t = np.zeros(self.tree.nnodes)
+        _lib.check(_lib.lib().rt_model_get_branch_lengths(self._h, _ptr(t, c_double)))
+        return t
+
+    def branch_profiles(self, batch, lengths=None, factors=None, per_site=False,
+                        recompute_transitions=False):
+        """rt_sites_branch_profiles: for every branch v and every trial length of its grid, the
+        change of the log-likelihood when that branch alone takes that length -- one upward and
+        one downward pass for all of them instead of one set_rates + step per branch and length.
+        Exactly one of `lengths` (absolute, [nnodes, G] in preorder or a dict edge -> sequence)
+        and `factors` (G multipliers of every branch's resident length): check_profile_lengths.
+        Returns a BranchProfiles tuple: nodes, lengths [nnodes, G] as evaluated, sums[v, g] the
+        site-weighted sum (SiteBatch.set_weights) of values[i, v, g] = log L_i(t_v ->
+        lengths[v, g]) - log L_i (None unless per_site: the array never leaves the device),
+        status.  The root's row is 0; the row of a branch whose resident length is 0 is NaN.
+        The rates come from set_rates (per-edge rate matrices included) or set_rates_spectral."""
+        ta = self.tree
+        N, S = ta.nnodes, batch.nsites
+        resident = None
+        if factors is not None or isinstance(lengths, dict):
+            resident = self.branch_lengths()
+        grid = check_profile_lengths(lengths, N, factors=factors, resident=resident, tree=ta)
+        G = grid.shape[1]
+        values = np.zeros((S, N, G)) if per_site else None
+        sums = np.zeros((N, G))
+        status = np.zeros(S, dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_branch_profiles(
+            self._h, batch._h, 1 if recompute_transitions else 0, G, _ptr(grid, c_double),
+            None if values is None else _ptr(values, c_double), _ptr(sums, c_double),
+            _ptr(status, c_int32)))
+        return BranchProfiles(list(ta.preorder_nodes), grid, sums, values, status)
 
     def branch_length_gradient(self, batch, recompute_transitions=False):
         """d (sum_i w_i log L_i) / d t_v for every branch, f64[nnodes] in preorder (0 at the
