@@ -11,6 +11,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/raoteh_hip.h"
@@ -42,6 +43,49 @@ void rt_set_error(const char *fmt, ...);
         int rc_ = (__VA_ARGS__);                                              \
         if (rc_ != RT_OK) return rc_;                                         \
     } while (0)
+
+// ---- what the host side of the calls shares ----------------------------------
+
+// device allocations freed when the guard goes, but those released to a longer-lived owner
+struct dev_free {
+    std::vector<void *> ptrs;
+    ~dev_free() { for (void *p : ptrs) hipFree(p); }
+    template <class T> int alloc(T *&p, size_t count)
+    {
+        p = nullptr;
+        RT_HIP(hipMalloc((void **)&p, (count ? count : 1) * sizeof(T)));
+        ptrs.push_back(p);
+        return RT_OK;
+    }
+    template <class T> T *release(T *p)
+    {
+        for (void *&q : ptrs) if (q == p) q = nullptr;
+        return p;
+    }
+};
+
+// A call's pieces of the context's grow-only device scratch: byte offsets, 256-byte aligned,
+// bumped out of one plan; rt_scratch_reserve(ctx, plan.total) then makes ctx->d_scratch hold them
+// all (valid until the next reserve)
+struct post_plan {
+    size_t total = 0;
+    size_t take(size_t bytes)
+    {
+        const size_t o = total;
+        total += (bytes + 255) / 256 * 256;
+        return o;
+    }
+};
+// f(std::integral_constant<int, V>) for the V in LO .. HI that equals v, RT_ERR_UNSUPPORTED for
+// any other v: the one table of the kernels' template arguments.  The lane kernels take the
+// states, the wave-per-tile kernels the row tiles NT (1 .. 8), the downward kernels the k-steps
+// KS (2 .. 32) with NT = ceil(KS / 4).
+template <int LO, int HI, class F>
+inline int post_dispatch(int v, F &&f)
+{
+    if constexpr (LO > HI) return RT_ERR_UNSUPPORTED;
+    else return v == LO ? f(std::integral_constant<int, LO>()) : post_dispatch<LO + 1, HI>(v, f);
+}
 
 struct rt_jit_job;      // a background compile (jit.hip)
 
@@ -513,8 +557,13 @@ int rt_frechet_wide_extract_device(rt_ctx *ctx, int64_t n, int64_t nedges, const
                                    const double *dS, const double *dscale, double *dG);
 // ... and what rt_expect_step keeps with a model (rt_model_destroy)
 void rt_expect_state_release(rt_model *m);
-// passes.hip: the n <= 8 form of rt_expect_step's passes (W and status on the device)
-int rt_expect_lane_resident(rt_model *m, rt_sites *s, double *d_W, int *d_status);
+// passes.hip: the lane form (n <= 4) of rt_expect_step's passes.  rt_expect_lane_take: its pieces
+// of the call's scratch; then W and the status (cleared by the caller) on the device,
+// asynchronous on the context's stream
+struct rt_expect_lane_scratch { size_t o_L = 0, o_part = 0; };
+rt_expect_lane_scratch rt_expect_lane_take(const rt_model *m, const rt_sites *s, post_plan *plan);
+int rt_expect_lane_resident(rt_model *m, rt_sites *s, unsigned char *scratch,
+                            const rt_expect_lane_scratch &at, double *d_W, int *d_status);
 void rt_expect_lane_release(rt_model *m);
 // expect_mfma.hip: P^T as A fragments in step order, T[step][m][q][lane][2] (NT row tiles,
 // KP k-step pairs), asynchronous on the context's stream
@@ -522,7 +571,8 @@ int rt_launch_pack_pt(rt_ctx *ctx, int n, int NT, int KP, int nops, const int *d
                       const double *d_P, double *d_PT);
 // a split-M interpreter batch over the resident observations of `src` (api.hip)
 int rt_sites_twin_interpreter(rt_sites *src, rt_sites **out);
-// the context's grow-only device scratch (ctx->d_scratch) holds at least `bytes` afterwards
+// passes.hip: the context's grow-only device scratch (ctx->d_scratch) holds at least `bytes`
+// afterwards
 int rt_scratch_reserve(rt_ctx *ctx, size_t bytes);
 // expectation path on the matrix pipe (expect_mfma.hip); RT_ERR_UNSUPPORTED = not this case
 int rt_expectation_weights_mfma(rt_ctx *ctx, int64_t nnodes, int64_t n, int64_t nsites,

@@ -24,7 +24,7 @@
 // Everything is summed in a fixed order.  The boolean passes are not run: with the upward pass
 // carrying exact zeros they change no number here (an infeasible site has likelihood 0 and
 // contributes nothing, as before).
-#include "common.h"
+#include "post_common.h"
 
 #include <algorithm>
 #include <chrono>
@@ -676,18 +676,6 @@ expect_root_finish_kernel(int n, int stride, const double *__restrict__ rootpart
     W[e] = sum;
 }
 
-struct dev_free {
-    std::vector<void *> ptrs;
-    ~dev_free() { for (void *p : ptrs) hipFree(p); }
-    template <class T> int alloc(T *&p, size_t count)
-    {
-        p = nullptr;
-        RT_HIP(hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T)));
-        ptrs.push_back(p);
-        return RT_OK;
-    }
-};
-
 // An EM loop calls with the same tree and the same observations again and again, only the
 // transition matrices change: the model (schedule, device tree) and the packed batch of the
 // last call stay with the context (one entry; 2.5 of a call's 6 ms at 10 000 codon sites were
@@ -720,44 +708,96 @@ uint64_t fnv1a(const void *p, size_t bytes, uint64_t h = 1469598103934665603ull)
     return h;
 }
 
+// The schedule of the downward pass from a model's ops: step -> node, the step of its parent (0
+// for the root, the last step), whether the node has children.  (post_common.h post_step_table
+// makes the same walk over a twin's ops for the other reads of a resident batch; their downward
+// kernels take one int4 per step with the leaf's observation and a caller's column in it, the
+// kernels here three plain arrays: two consumers, two tables.)
+struct expect_schedule {
+    std::vector<int> step_node, parent_step;
+    std::vector<unsigned char> internal;
+};
+
+int expect_schedule_build(const rt_model *m, expect_schedule *t)
+{
+    const int nops = (int)m->ops.size();
+    RT_REQUIRE(nops == m->nnodes && m->ops[(size_t)nops - 1].dst < 0, "unexpected schedule");
+    std::vector<int> step_of((size_t)nops, -1);
+    t->step_node.assign((size_t)nops, 0);
+    t->parent_step.assign((size_t)nops, 0);
+    t->internal.assign((size_t)nops, 0);
+    for (int i = 0; i < nops; ++i) {
+        t->step_node[(size_t)i] = m->ops[(size_t)i].node;
+        step_of[(size_t)m->ops[(size_t)i].node] = i;
+        t->internal[(size_t)i] = m->ops[(size_t)i].pop >= 0;
+    }
+    for (int i = 0; i + 1 < nops; ++i)
+        t->parent_step[(size_t)i] = step_of[(size_t)m->parent[(size_t)t->step_node[(size_t)i]]];
+    return RT_OK;
+}
+
+// What one pass works on besides the model and its batch (device pointers): the tables of the
+// schedule, the site weights (null: ones), W, and the pass's pieces of the context's scratch
+struct expect_pass {
+    const double *d_PT = nullptr;
+    const int *d_step_node = nullptr, *d_parent_step = nullptr;
+    const unsigned char *d_internal = nullptr;
+    const double *d_w = nullptr;
+    double *d_W = nullptr;
+    // [step][tile][NT][4][64] each, the chunk partials of the site sums, the root's
+    double *d_L = nullptr, *d_M = nullptr, *d_D = nullptr, *d_U = nullptr, *d_part = nullptr;
+    double *d_rootpart = nullptr;
+    int *d_status = nullptr;                   // cleared by the caller
+};
+
+// ... those pieces in a plan (2.6 GB at 10 000 sites of the codon model: they live in the
+// context's grow-only scratch, a hipMalloc / hipFree pair per call costs more than the kernels)
+struct expect_pieces {
+    size_t o_L = 0, o_M = 0, o_D = 0, o_U = 0, o_part = 0, o_rootpart = 0, o_status = 0;
+    void take(post_plan *plan, int nops, int64_t nblocks, int NT, int64_t nsites)
+    {
+        const size_t arr = (size_t)nops * nblocks * NT * 256 * 8;
+        o_L = plan->take(arr); o_M = plan->take(arr); o_D = plan->take(arr); o_U = plan->take(arr);
+        o_part = plan->take((size_t)nops * EX_CHUNKS * NT * NT * 256 * 8);
+        o_rootpart = plan->take((size_t)EX_ROOT_CHUNKS * 128 * 8);
+        o_status = plan->take((size_t)nsites * 4);
+    }
+    void bind(unsigned char *base, expect_pass *a) const
+    {
+        a->d_L = (double *)(base + o_L); a->d_M = (double *)(base + o_M);
+        a->d_D = (double *)(base + o_D); a->d_U = (double *)(base + o_U);
+        a->d_part = (double *)(base + o_part); a->d_rootpart = (double *)(base + o_rootpart);
+        a->d_status = (int *)(base + o_status);
+    }
+};
+
 // Everything of one pass that happens on the device, asynchronously on the context's stream:
 // upward pass of the split-M interpreter kernel with L and M of every step stored, downward
 // pass, per-edge site sums, W in the reference's [node][a][b] order (slot 0, column 0: the
 // weighted sum of the root posteriors).  `s`: a split-M interpreter batch (MFMA layout, one
-// row tile per wave, no tree-specialised kernel); d_w device weights or null.
-template <int NT, int KS>
-int expect_device_passes(rt_ctx *ctx, rt_model *model, rt_sites *s, const double *d_PT,
-                         const int *d_step_node, const int *d_parent_step,
-                         const unsigned char *d_internal, const double *esd_dev,
-                         const double *d_root_w, const double *d_w, double *d_W, int *d_status,
-                         double *d_rootpart, bool trace)
+// row tile per wave, no tree-specialised kernel).
+template <int KS>
+int expect_device_passes(rt_ctx *ctx, rt_model *model, rt_sites *s, const expect_pass &a, bool trace)
 {
+    constexpr int NT = (KS + 3) / 4;
     hipStream_t st = ctx->stream;
     RT_REQUIRE(s->layout == RT_LAYOUT_MFMA && !s->mfma_solo && !s->jit_fn,
                "unexpected batch layout for the matrix-pipe expectation path");
     const int64_t n = model->n, nsites = s->nsites;
     const int nops = (int)s->ops.size();
     const long nblocks = (long)s->nblocks;
-    const size_t arr = (size_t)nops * nblocks * NT * 256;
-    // the four per-step arrays and the chunk partials live in the context's grow-only scratch
-    // (2.6 GB at 10 000 sites of the codon model: a hipMalloc / hipFree pair per call costs more
-    // than the kernels)
-    const size_t npart = (size_t)nops * EX_CHUNKS * NT * NT * 256;
-    RT_TRY(rt_scratch_reserve(ctx, (4 * arr + npart) * 8));
-    double *d_L = (double *)ctx->d_scratch;
-    double *d_M = d_L + arr, *d_D = d_M + arr, *d_U = d_D + arr, *d_part = d_U + arr;
     // M of the root step is never written by the upward pass (no product there)
-    s->d_Lout = d_L;
-    s->d_Mout = d_M;
+    s->d_Lout = a.d_L;
+    s->d_Mout = a.d_M;
     const int rc = rt_launch_prune(model, s, false);
     s->d_Lout = s->d_Mout = nullptr;
     RT_TRY(rc);
     if (trace) hipStreamSynchronize(st);
-    RT_HIP(hipMemsetAsync(d_status, 0, (size_t)nsites * 4, st));
     // the LDS form of the downward pass when the slots of the tree fit (RAOTEH_EXPECT_DOWN=global:
     // the first form, D through HBM)
     if (!s->d_down_meta) {
-        // [nops] {parent slot, own slot} then [nops] the stream position of an observed leaf (-1)
+        // [nops] {parent slot, own slot} then [nops] the stream position of an observed leaf (-1);
+        // the batch gets the table, with its slot count, when the table is complete
         std::vector<int32_t> meta((size_t)nops * 3);
         int nslots = 0;
         for (int i = 0; i < nops; ++i) {
@@ -768,14 +808,18 @@ int expect_device_passes(rt_ctx *ctx, rt_model *model, rt_sites *s, const double
             if (op.dst >= 0) nslots = std::max(nslots, (op.dst & 255) + 1);
             if (op.pop >= 0) nslots = std::max(nslots, op.pop + 1);
         }
-        RT_HIP(hipMalloc((void **)&s->d_down_meta, meta.size() * 4));
-        RT_HIP(hipMemcpyAsync(s->d_down_meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, st));
+        dev_free mem;
+        int32_t *d_meta;
+        RT_TRY(mem.alloc(d_meta, meta.size()));
+        RT_HIP(hipMemcpyAsync(d_meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, st));
         RT_HIP(hipStreamSynchronize(st));            // (meta is a local)
+        s->d_down_meta = mem.release(d_meta);
         s->down_slots = std::max(nslots, 1);
     }
     const int regslot = s->down_slots - 1;           // the deepest slot: registers
     const size_t down_lds = (size_t)(1 + regslot) * NT * 256 * 8 + (size_t)nops * 8;
     const char *dv = getenv("RAOTEH_EXPECT_DOWN");
+    const double *d_root_w = model->d_root;
     // (NT > 4: the global form only -- under its three-waves-per-SIMD register budget the LDS
     // form spills there, and eight waves a workgroup are two per SIMD already)
     bool down_in_lds = false;
@@ -784,51 +828,47 @@ int expect_device_passes(rt_ctx *ctx, rt_model *model, rt_sites *s, const double
             auto kern = expect_down_lds_kernel<NT, KS>;
             RT_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)down_lds));
-            hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(64 * NT), down_lds, st, d_PT, nops,
-                               (const int2 *)s->d_down_meta, d_L, d_M, d_D, d_U, d_root_w, (int)n, d_status,
-                               (long)nsites, nblocks, regslot);
+            hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(64 * NT), down_lds, st, a.d_PT, nops,
+                               (const int2 *)s->d_down_meta, a.d_L, a.d_M, a.d_D, a.d_U, d_root_w, (int)n,
+                               a.d_status, (long)nsites, nblocks, regslot);
             down_in_lds = true;
         }
     }
     if (!down_in_lds)
         hipLaunchKernelGGL((expect_down_kernel<NT, KS>), dim3((unsigned)nblocks), dim3(64 * NT), 0, st,
-                           d_PT, nops, d_parent_step, d_internal, d_L, d_M, d_D, d_U, d_root_w, (int)n,
-                           d_status, (long)nsites, nblocks);
+                           a.d_PT, nops, a.d_parent_step, a.d_internal, a.d_L, a.d_M, a.d_D, a.d_U,
+                           d_root_w, (int)n, a.d_status, (long)nsites, nblocks);
     const int *d_leaf_k = s->d_down_meta + (size_t)nops * 2;
-    const int KPo = (KS + 1) / 2;
-#define RT_WSUM(KERN)                                                                             \
-    hipLaunchKernelGGL(KERN, dim3((unsigned)(nops - 1), EX_CHUNKS), dim3(64 * NT), 0, st, nops, d_U, \
-                       d_L, d_w, (long)nsites, nblocks, d_part, d_leaf_k, (const double *)s->d_obs, \
-                       (int)s->nobs, KPo)
+    auto wsum = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)(nops - 1), EX_CHUNKS), dim3(64 * NT), 0, st, nops,
+                           a.d_U, a.d_L, a.d_w, (long)nsites, nblocks, a.d_part, d_leaf_k,
+                           (const double *)s->d_obs, (int)s->nobs, (KS + 1) / 2);
+    };
     if constexpr (NT <= 4) {
-        if (d_w) RT_WSUM((expect_wsum_kernel<NT, true>));
-        else RT_WSUM((expect_wsum_kernel<NT, false>));
+        if (a.d_w) wsum(expect_wsum_kernel<NT, true>);
+        else wsum(expect_wsum_kernel<NT, false>);
     } else {
-        if (d_w) RT_WSUM((expect_wsum_wide_kernel<NT, true>));
-        else RT_WSUM((expect_wsum_wide_kernel<NT, false>));
+        if (a.d_w) wsum(expect_wsum_wide_kernel<NT, true>);
+        else wsum(expect_wsum_wide_kernel<NT, false>);
     }
-#undef RT_WSUM
     hipLaunchKernelGGL(expect_finish_kernel, dim3((unsigned)(nops - 1)), dim3(256), 0, st, (int)n, NT,
-                       nops, d_step_node, esd_dev, d_part, d_W);
+                       nops, a.d_step_node, (const double *)model->d_P, a.d_part, a.d_W);
     const int root_threads = n > 64 ? 128 : 64;    // d_rootpart: EX_ROOT_CHUNKS x 128 doubles
     hipLaunchKernelGGL(expect_root_kernel, dim3(EX_ROOT_CHUNKS), dim3(root_threads), 0, st, (int)n, NT,
-                       nops - 1, d_D, d_w, (long)nsites, nblocks, d_rootpart);
+                       nops - 1, a.d_D, a.d_w, (long)nsites, nblocks, a.d_rootpart);
     hipLaunchKernelGGL(expect_root_finish_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, st,
-                       (int)n, root_threads, d_rootpart, d_W);
+                       (int)n, root_threads, a.d_rootpart, a.d_W);
     RT_HIP(hipGetLastError());
     return RT_OK;
 }
 
-template <int NT, int KS>
-int run_chunk(rt_ctx *ctx, rt_model *model, int64_t n, int64_t nsites, int64_t nobs,
-              const int64_t *obs_nodes, int kind, const void *data, const double *esd_dev,
-              const double *d_root_w, const double *site_weights, const std::vector<int> &step_node,
-              const std::vector<int> &parent_step, const std::vector<unsigned char> &internal,
-              double *d_W, int *d_status, double *d_PT, const int *d_step_node,
-              const int *d_parent_step, const unsigned char *d_internal, rt_sites *cached_sites,
-              rt_sites **keep_sites)
+// One pass of the reference-shaped entry over `nsites` sites from `data`: the packed batch
+// (`cached_sites`, or made here and handed to *keep_sites or destroyed), the weights, the passes.
+// `a`: the tables and W; a->d_status is where the pass left the status, until the next reserve.
+int run_chunk(rt_ctx *ctx, rt_model *model, int64_t nsites, int64_t nobs, const int64_t *obs_nodes,
+              int kind, const void *data, const double *site_weights, expect_pass *a,
+              rt_sites *cached_sites, rt_sites **keep_sites)
 {
-    (void)step_node; (void)parent_step; (void)internal;
     hipStream_t st = ctx->stream;
     // RAOTEH_EXPECT_TRACE=1: host wall clock of the stages (each ends with a stream sync)
     const bool trace = getenv("RAOTEH_EXPECT_TRACE") != nullptr;
@@ -846,15 +886,23 @@ int run_chunk(rt_ctx *ctx, rt_model *model, int64_t n, int64_t nsites, int64_t n
     }
     if (trace) hipStreamSynchronize(st);
     const auto t1 = now();
+    const int NT = (int)((model->n + 15) / 16), KS = (int)((model->n + 3) / 4);
+    post_plan plan;
+    expect_pieces pieces;
+    pieces.take(&plan, (int)s->ops.size(), s->nblocks, NT, nsites);
+    RT_TRY(rt_scratch_reserve(ctx, plan.total));
+    pieces.bind(ctx->d_scratch, a);
+    RT_HIP(hipMemsetAsync(a->d_status, 0, (size_t)nsites * 4, st));
     dev_free mem;
-    double *d_rootpart, *d_w = nullptr;
-    RT_TRY(mem.alloc(d_rootpart, (size_t)EX_ROOT_CHUNKS * 128));
+    double *d_w = nullptr;
     if (site_weights) {
         RT_TRY(mem.alloc(d_w, (size_t)nsites));
         RT_HIP(hipMemcpyAsync(d_w, site_weights, (size_t)nsites * 8, hipMemcpyHostToDevice, st));
     }
-    RT_TRY((expect_device_passes<NT, KS>(ctx, model, s, d_PT, d_step_node, d_parent_step, d_internal,
-                                         esd_dev, d_root_w, d_w, d_W, d_status, d_rootpart, trace)));
+    a->d_w = d_w;
+    RT_TRY(post_dispatch<3, 16>(KS, [&](auto ks) {
+        return expect_device_passes<decltype(ks)::value>(ctx, model, s, *a, trace);
+    }));
     const auto t2 = now();
     RT_HIP(hipStreamSynchronize(st));
     if (trace)
@@ -872,6 +920,7 @@ int rt_expectation_weights_mfma(rt_ctx *ctx, int64_t nnodes, int64_t n, int64_t 
                                 int kind, const void *data, const double *site_weights,
                                 double *edge_weights, int32_t *status)
 {
+    // (9 .. 64 states: 3 .. 16 k-steps, the table of run_chunk)
     if (n <= 8 || n > 64 || nnodes < 2 || getenv("RAOTEH_EXPECT_LEGACY")) return RT_ERR_UNSUPPORTED;
     const auto call_start = std::chrono::steady_clock::now();
     const size_t item = kind == RT_OBS_STATE ? 1 : 8;
@@ -909,39 +958,28 @@ int rt_expectation_weights_mfma(rt_ctx *ctx, int64_t nnodes, int64_t n, int64_t 
         root_distn = ones.data();
     }
     RT_TRY(rt_model_set_root_distn(model, root_distn));
-    // the schedule: step -> node, its parent's step, whether it has children
+    expect_schedule sched;
+    RT_TRY(expect_schedule_build(model, &sched));
     const int nops = (int)model->ops.size();
-    std::vector<int> parent((size_t)nnodes, -1), step_of((size_t)nnodes, -1);
-    for (int64_t v = 0; v < nnodes; ++v)
-        for (int64_t e = ptr[v]; e < ptr[v + 1]; ++e) parent[(size_t)idx[e]] = (int)v;
-    std::vector<int> step_node((size_t)nops), parent_step((size_t)nops, 0);
-    std::vector<unsigned char> internal((size_t)nops, 0);
-    for (int i = 0; i < nops; ++i) {
-        step_node[(size_t)i] = model->ops[(size_t)i].node;
-        step_of[(size_t)model->ops[(size_t)i].node] = i;
-        internal[(size_t)i] = model->ops[(size_t)i].pop >= 0;
-    }
-    RT_REQUIRE(nops == nnodes && model->ops[(size_t)nops - 1].dst < 0, "unexpected schedule");
-    for (int i = 0; i + 1 < nops; ++i) parent_step[(size_t)i] = step_of[(size_t)parent[(size_t)step_node[(size_t)i]]];
-    const int NT = (int)((n + 15) / 16), KS = (int)((n + 3) / 4), KP = (KS + 1) / 2;
+    const int NT = (int)((n + 15) / 16), KP = ((int)((n + 3) / 4) + 1) / 2;
     hipStream_t st = ctx->stream;
     dev_free mem;
     double *d_W, *d_PT;
-    int *d_status, *d_step_node, *d_parent_step;
+    int *d_step_node, *d_parent_step;
     unsigned char *d_internal;
     const int64_t CS = 32768;                 // sites per pass: 4 arrays of nops x tiles x 8 KB
     RT_TRY(mem.alloc(d_W, (size_t)nnodes * n * n));
     RT_TRY(mem.alloc(d_PT, (size_t)nops * NT * KP * 128));
-    RT_TRY(mem.alloc(d_status, (size_t)std::min<int64_t>(nsites, CS)));
     RT_TRY(mem.alloc(d_step_node, (size_t)nops));
     RT_TRY(mem.alloc(d_parent_step, (size_t)nops));
     RT_TRY(mem.alloc(d_internal, (size_t)nops));
-    RT_HIP(hipMemcpyAsync(d_step_node, step_node.data(), (size_t)nops * 4, hipMemcpyHostToDevice, st));
-    RT_HIP(hipMemcpyAsync(d_parent_step, parent_step.data(), (size_t)nops * 4, hipMemcpyHostToDevice, st));
-    RT_HIP(hipMemcpyAsync(d_internal, internal.data(), (size_t)nops, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(pack_pt_kernel, dim3(512), dim3(256), 0, st, (int)n, NT, KP, nops, d_step_node,
-                       model->d_P, d_PT);
-    RT_HIP(hipGetLastError());
+    RT_HIP(hipMemcpyAsync(d_step_node, sched.step_node.data(), (size_t)nops * 4, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemcpyAsync(d_parent_step, sched.parent_step.data(), (size_t)nops * 4, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemcpyAsync(d_internal, sched.internal.data(), (size_t)nops, hipMemcpyHostToDevice, st));
+    RT_TRY(rt_launch_pack_pt(ctx, (int)n, NT, KP, nops, d_step_node, model->d_P, d_PT));
+    expect_pass pass;
+    pass.d_PT = d_PT; pass.d_step_node = d_step_node; pass.d_parent_step = d_parent_step;
+    pass.d_internal = d_internal; pass.d_W = d_W;
     const size_t wcount = (size_t)nnodes * n * n;
     std::vector<double> acc(wcount, 0.0), part(wcount);
     // the packed batch is kept when the whole call is one pass (its observations hashed)
@@ -964,28 +1002,8 @@ int rt_expectation_weights_mfma(rt_ctx *ctx, int64_t nnodes, int64_t n, int64_t 
         rt_sites *cached = one_pass ? cache->sites : nullptr;
         rt_sites *made = nullptr;
         rt_sites **keep = one_pass && !cached ? &made : nullptr;
-        int rc = RT_ERR_UNSUPPORTED;
-#define RT_EX(NTV, KSV)                                                                           \
-        rc = run_chunk<NTV, KSV>(ctx, model, n, cnt, nobs, obs_nodes, kind, chunk_data, model->d_P, \
-                                 model->d_root, chunk_w, step_node, parent_step, internal, d_W,     \
-                                 d_status, d_PT, d_step_node, d_parent_step, d_internal, cached, keep)
-        switch (KS) {
-        case 3: RT_EX(1, 3); break;
-        case 4: RT_EX(1, 4); break;
-        case 5: RT_EX(2, 5); break;
-        case 6: RT_EX(2, 6); break;
-        case 7: RT_EX(2, 7); break;
-        case 8: RT_EX(2, 8); break;
-        case 9: RT_EX(3, 9); break;
-        case 10: RT_EX(3, 10); break;
-        case 11: RT_EX(3, 11); break;
-        case 12: RT_EX(3, 12); break;
-        case 13: RT_EX(4, 13); break;
-        case 14: RT_EX(4, 14); break;
-        case 15: RT_EX(4, 15); break;
-        default: RT_EX(4, 16); break;
-        }
-#undef RT_EX
+        const int rc = run_chunk(ctx, model, cnt, nobs, obs_nodes, kind, chunk_data, chunk_w, &pass,
+                                 cached, keep);
         if (made) {
             cache->sites = made;
             cache->data_key = data_key;
@@ -994,7 +1012,7 @@ int rt_expectation_weights_mfma(rt_ctx *ctx, int64_t nnodes, int64_t n, int64_t 
         RT_TRY(rc);
         RT_HIP(hipMemcpy(part.data(), d_W, wcount * 8, hipMemcpyDeviceToHost));
         for (size_t e = 0; e < wcount; ++e) acc[e] += part[e];
-        if (status) RT_HIP(hipMemcpy(status + lo, d_status, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+        if (status) RT_HIP(hipMemcpy(status + lo, pass.d_status, (size_t)cnt * 4, hipMemcpyDeviceToHost));
     }
     memcpy(edge_weights, acc.data(), wcount * 8);
     if (getenv("RAOTEH_EXPECT_TRACE"))
@@ -1015,15 +1033,14 @@ namespace {
 struct expect_state_t {
     int nops = 0;
     double *d_PT = nullptr, *d_W = nullptr, *d_B = nullptr, *d_E = nullptr, *d_scale = nullptr;
-    double *d_ones = nullptr, *d_out = nullptr, *d_rootpart = nullptr;
-    int *d_step_node = nullptr, *d_parent_step = nullptr, *d_ident = nullptr, *d_status = nullptr;
-    int64_t status_cap = 0;
+    double *d_ones = nullptr, *d_out = nullptr;
+    int *d_step_node = nullptr, *d_parent_step = nullptr, *d_ident = nullptr;
     unsigned char *d_internal = nullptr;
     ~expect_state_t()
     {
         hipFree(d_PT); hipFree(d_W); hipFree(d_B); hipFree(d_E); hipFree(d_scale); hipFree(d_ones);
-        hipFree(d_out); hipFree(d_rootpart); hipFree(d_step_node); hipFree(d_parent_step);
-        hipFree(d_ident); hipFree(d_status); hipFree(d_internal);
+        hipFree(d_out); hipFree(d_step_node); hipFree(d_parent_step); hipFree(d_ident);
+        hipFree(d_internal);
     }
 };
 
@@ -1034,18 +1051,10 @@ int expect_state_get(rt_model *m, expect_state_t **out)
         return RT_OK;
     }
     const int64_t n = m->n, N = m->nnodes;
+    expect_schedule sched;
+    RT_TRY(expect_schedule_build(m, &sched));
     const int nops = (int)m->ops.size();
-    RT_REQUIRE(nops == N && m->ops[(size_t)nops - 1].dst < 0, "unexpected schedule");
     const bool mfma = n > 4;                   // (n <= 4: the fused lane kernel of passes.hip)
-    std::vector<int> step_node((size_t)nops), parent_step((size_t)nops, 0), step_of((size_t)N, -1);
-    std::vector<unsigned char> internal((size_t)nops, 0);
-    for (int i = 0; i < nops; ++i) {
-        step_node[(size_t)i] = m->ops[(size_t)i].node;
-        step_of[(size_t)m->ops[(size_t)i].node] = i;
-        internal[(size_t)i] = m->ops[(size_t)i].pop >= 0;
-    }
-    for (int i = 0; i + 1 < nops; ++i)
-        parent_step[(size_t)i] = step_of[(size_t)m->parent[(size_t)step_node[(size_t)i]]];
     std::unique_ptr<expect_state_t> st(new (std::nothrow) expect_state_t());
     if (!st) return RT_ERR_NOMEM;
     st->nops = nops;
@@ -1062,7 +1071,6 @@ int expect_state_get(rt_model *m, expect_state_t **out)
     RT_HIP(hipMalloc((void **)&st->d_scale, ne * 8));
     RT_HIP(hipMalloc((void **)&st->d_ones, ne * 8));
     RT_HIP(hipMalloc((void **)&st->d_out, (2 * (size_t)n + nn) * 8));
-    RT_HIP(hipMalloc((void **)&st->d_rootpart, (size_t)EX_ROOT_CHUNKS * 128 * 8));
     RT_HIP(hipMalloc((void **)&st->d_step_node, (size_t)nops * 4));
     RT_HIP(hipMalloc((void **)&st->d_parent_step, (size_t)nops * 4));
     RT_HIP(hipMalloc((void **)&st->d_ident, ne * 4));
@@ -1072,9 +1080,9 @@ int expect_state_get(rt_model *m, expect_state_t **out)
     for (size_t e = 0; e < ne; ++e) ident[e] = (int)e;
     RT_HIP(hipMemcpy(st->d_ones, ones.data(), ne * 8, hipMemcpyHostToDevice));
     RT_HIP(hipMemcpy(st->d_ident, ident.data(), ne * 4, hipMemcpyHostToDevice));
-    RT_HIP(hipMemcpy(st->d_step_node, step_node.data(), (size_t)nops * 4, hipMemcpyHostToDevice));
-    RT_HIP(hipMemcpy(st->d_parent_step, parent_step.data(), (size_t)nops * 4, hipMemcpyHostToDevice));
-    RT_HIP(hipMemcpy(st->d_internal, internal.data(), (size_t)nops, hipMemcpyHostToDevice));
+    RT_HIP(hipMemcpy(st->d_step_node, sched.step_node.data(), (size_t)nops * 4, hipMemcpyHostToDevice));
+    RT_HIP(hipMemcpy(st->d_parent_step, sched.parent_step.data(), (size_t)nops * 4, hipMemcpyHostToDevice));
+    RT_HIP(hipMemcpy(st->d_internal, sched.internal.data(), (size_t)nops, hipMemcpyHostToDevice));
     m->expect_state = st.release();
     *out = (expect_state_t *)m->expect_state;
     return RT_OK;
@@ -1102,8 +1110,9 @@ void rt_expect_state_release(rt_model *m)
 extern "C" int rt_expect_step(rt_model *m, rt_sites *s, int recompute_transitions, double *dwell,
                               double *root_posterior, double *trans, int32_t *status)
 {
-    RT_REQUIRE(m && s && dwell && root_posterior && trans, "null pointer");
-    RT_REQUIRE(s->model == m, "the site batch belongs to another model");
+    RT_REQUIRE(dwell && root_posterior && trans, "null pointer");
+    post_pass p;
+    RT_TRY(post_open(&p, "rt_expect_step", m, s));
     RT_REQUIRE(m->d_Q && !m->spectral,
                "rt_model_set_rates has not been called (the statistics need the rate matrices)");
     if (s->rescale) {
@@ -1113,92 +1122,44 @@ extern "C" int rt_expect_step(rt_model *m, rt_sites *s, int recompute_transition
                      "rescale their messages)");
         return RT_ERR_UNSUPPORTED;
     }
-    const int64_t n = m->n, N = m->nnodes;
-    const bool lane = n <= 4;                  // resident in the lane layout: the fused lane kernel
+    const int64_t n = p.n, N = p.N;
+    // n <= 4: resident in the lane layout, the fused lane kernel; above: 5 .. 128 states, the
+    // 2 .. 32 k-steps of the table below
     if (n > RT_MAX_EXPECT_STEP_STATES || N < 2 || s->d_scratch || m->max_depth > RT_FAST_MAX_DEPTH ||
-        s->layout != (lane ? RT_LAYOUT_LANE : RT_LAYOUT_MFMA)) {
+        p.lane != (n <= 4)) {
         rt_set_error("rt_expect_step: resident batches of n <= %d states on trees the fast "
                      "kernels take (n=%lld here)", RT_MAX_EXPECT_STEP_STATES, (long long)n);
         return RT_ERR_UNSUPPORTED;
     }
-    rt_ctx *ctx = m->ctx;
-    RT_HIP(hipSetDevice(ctx->device));
-    const int NT = (int)((n + 15) / 16), KS = (int)((n + 3) / 4), KP = (KS + 1) / 2;
-    // the four per-step arrays of the passes: nodes x tiles x 8 KB x NT each (n <= 8: one
-    // array of nodes x states x sites doubles)
-    const double scratch_gb = lane ? (double)N * (double)n * (double)s->nsites * 8.0 / 1e9
-                                   : 4.0 * (double)N * (double)((s->nsites + 15) / 16) * NT * 2048.0 / 1e9;
-    if (scratch_gb > 96.0) {
-        rt_set_error("rt_expect_step: the passes of this batch need %.0f GB of scratch; split the "
-                     "batch", scratch_gb);
-        return RT_ERR_UNSUPPORTED;
+    // the scratch of the call: the lane kernel's L and partial sums, or the four per-step arrays of
+    // the passes (nodes x tiles x 8 KB x NT each) and their partials; the status words
+    rt_expect_lane_scratch lane_at;
+    expect_pieces pieces;
+    if (p.lane) {
+        lane_at = rt_expect_lane_take(m, s, &p.plan);
+        p.o_status = p.plan.take((size_t)p.nsites * 4);
+    } else {
+        pieces.take(&p.plan, p.nops, s->nblocks, p.NT, p.nsites);
+        p.o_status = pieces.o_status;
     }
+    RT_TRY(post_begin(&p, recompute_transitions));
     expect_state_t *st = nullptr;
     RT_TRY(expect_state_get(m, &st));
-    const int64_t status_need = (s->nsites + 63) / 64 * 64;
-    if (st->status_cap < status_need) {
-        hipFree(st->d_status);
-        st->d_status = nullptr;
-        st->status_cap = 0;
-        RT_HIP(hipMalloc((void **)&st->d_status, (size_t)status_need * 4));
-        st->status_cap = status_need;
-    }
-    if (recompute_transitions) RT_TRY(rt_model_recompute_transitions(m));
-    RT_REQUIRE(m->have_P, "the model has no transition matrices yet");
-    hipStream_t stream = ctx->stream;
-    int rc = RT_ERR_UNSUPPORTED;
-    rt_sites *x = nullptr;
-    if (lane) {
-        RT_HIP(hipMemsetAsync(st->d_status, 0, (size_t)status_need * 4, stream));
-        RT_TRY(rt_expect_lane_resident(m, s, st->d_W, st->d_status));
-        rc = RT_OK;
+    rt_ctx *ctx = p.ctx;
+    hipStream_t stream = p.st;
+    if (p.lane) {
+        RT_TRY(rt_expect_lane_resident(m, s, p.base, lane_at, st->d_W, p.d_status));
     } else {
-        if (!s->expect_twin) RT_TRY(rt_sites_twin_interpreter(s, &s->expect_twin));
-        x = s->expect_twin;
-        hipLaunchKernelGGL(pack_pt_kernel, dim3(512), dim3(256), 0, stream, (int)n, NT, KP, st->nops,
-                           st->d_step_node, m->d_P, st->d_PT);
-        RT_HIP(hipGetLastError());
+        RT_REQUIRE(p.x->nblocks == s->nblocks && (int)p.x->ops.size() == p.nops, "unexpected twin");
+        RT_TRY(rt_launch_pack_pt(ctx, (int)n, p.NT, p.KP, st->nops, st->d_step_node, m->d_P, st->d_PT));
+        expect_pass a;
+        a.d_PT = st->d_PT; a.d_step_node = st->d_step_node; a.d_parent_step = st->d_parent_step;
+        a.d_internal = st->d_internal; a.d_w = s->d_weights; a.d_W = st->d_W;
+        pieces.bind(p.base, &a);
+        RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
+            return expect_device_passes<decltype(ks)::value>(ctx, m, p.x, a, false);
+        }));
     }
-#define RT_EX(NTV, KSV)                                                                            \
-    rc = expect_device_passes<NTV, KSV>(ctx, m, x, st->d_PT, st->d_step_node, st->d_parent_step,   \
-                                        st->d_internal, m->d_P, m->d_root, s->d_weights, st->d_W,  \
-                                        st->d_status, st->d_rootpart, false)
-    if (!lane)
-    switch (KS) {
-    case 2: RT_EX(1, 2); break;
-    case 3: RT_EX(1, 3); break;
-    case 4: RT_EX(1, 4); break;
-    case 5: RT_EX(2, 5); break;
-    case 6: RT_EX(2, 6); break;
-    case 7: RT_EX(2, 7); break;
-    case 8: RT_EX(2, 8); break;
-    case 9: RT_EX(3, 9); break;
-    case 10: RT_EX(3, 10); break;
-    case 11: RT_EX(3, 11); break;
-    case 12: RT_EX(3, 12); break;
-    case 13: RT_EX(4, 13); break;
-    case 14: RT_EX(4, 14); break;
-    case 15: RT_EX(4, 15); break;
-    case 16: RT_EX(4, 16); break;
-    case 17: RT_EX(5, 17); break;
-    case 18: RT_EX(5, 18); break;
-    case 19: RT_EX(5, 19); break;
-    case 20: RT_EX(5, 20); break;
-    case 21: RT_EX(6, 21); break;
-    case 22: RT_EX(6, 22); break;
-    case 23: RT_EX(6, 23); break;
-    case 24: RT_EX(6, 24); break;
-    case 25: RT_EX(7, 25); break;
-    case 26: RT_EX(7, 26); break;
-    case 27: RT_EX(7, 27); break;
-    case 28: RT_EX(7, 28); break;
-    case 29: RT_EX(8, 29); break;
-    case 30: RT_EX(8, 30); break;
-    case 31: RT_EX(8, 31); break;
-    default: RT_EX(8, 32); break;
-    }
-#undef RT_EX
-    RT_TRY(rc);
     // slot 0, column 0 of W: the weighted sum of the root posteriors; edges 1 .. N - 1 follow
     const size_t nn = (size_t)n * n;
     double *d_dwell = st->d_out, *d_rootp = st->d_out + n, *d_trans = st->d_out + 2 * n;
@@ -1214,7 +1175,7 @@ extern "C" int rt_expect_step(rt_model *m, rt_sites *s, int recompute_transition
     std::vector<double> out(2 * (size_t)n + nn);
     RT_HIP(hipMemcpyAsync(out.data(), st->d_out, out.size() * 8, hipMemcpyDeviceToHost, stream));
     if (status)
-        RT_HIP(hipMemcpyAsync(status, st->d_status, (size_t)s->nsites * 4, hipMemcpyDeviceToHost, stream));
+        RT_HIP(hipMemcpyAsync(status, p.d_status, (size_t)s->nsites * 4, hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
     memcpy(dwell, out.data(), (size_t)n * 8);
     memcpy(root_posterior, out.data() + n, (size_t)n * 8);
@@ -1228,4 +1189,3 @@ void rt_expect_cache_release(rt_ctx *ctx)
     delete (expect_cache_t *)ctx->expect_cache;
     ctx->expect_cache = nullptr;
 }
-

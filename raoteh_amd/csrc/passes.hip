@@ -124,31 +124,6 @@ pmap_kernel(int nnodes, int n, long nsites, const long *__restrict__ idx,
     }
 }
 
-// bump allocation out of the context's grow-only scratch (valid until the next call)
-struct scratch_plan {
-    size_t total = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t off = total;
-        total += (bytes + 255) & ~(size_t)255;
-        return off;
-    }
-};
-
-int scratch_reserve(rt_ctx *ctx, size_t bytes)
-{
-    if (bytes <= ctx->scratch_bytes) return RT_OK;
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    hipFree(ctx->d_scratch);
-    ctx->d_scratch = nullptr;
-    ctx->scratch_bytes = 0;
-    const size_t want = std::max(bytes + bytes / 2, (size_t)1 << 20);
-    RT_HIP(hipMalloc((void **)&ctx->d_scratch, want));
-    ctx->scratch_bytes = want;
-    return RT_OK;
-}
-
-
 // the tree of a reference-format call, in the context's scratch (nothing to free: a
 // hipMalloc / hipFree pair per array was most of the 0.8-3.5 ms of a single-site call)
 struct dev_tree {
@@ -179,10 +154,10 @@ int upload_tree(rt_ctx *ctx, dev_tree &d, int64_t nnodes, int64_t n,
                 const int64_t *idx, const int64_t *ptr, const double *esd, size_t extra = 0)
 {
     const size_t ni = (size_t)(nnodes > 1 ? nnodes - 1 : 1);
-    scratch_plan plan;
+    post_plan plan;
     const size_t o_idx = plan.take(ni * 8), o_ptr = plan.take((size_t)(nnodes + 1) * 8);
     const size_t o_esd = plan.take((size_t)nnodes * n * n * 8), o_rest = plan.take(extra);
-    RT_TRY(scratch_reserve(ctx, plan.total));
+    RT_TRY(rt_scratch_reserve(ctx, plan.total));
     d.idx = (long *)(ctx->d_scratch + o_idx);
     d.ptr = (long *)(ctx->d_scratch + o_ptr);
     d.esd = (double *)(ctx->d_scratch + o_esd);
@@ -233,7 +208,18 @@ int mask_pass(rt_ctx *ctx, bool forward, int64_t nnodes, int64_t n, int64_t nsit
 
 }  // namespace
 
-int rt_scratch_reserve(rt_ctx *ctx, size_t bytes) { return scratch_reserve(ctx, bytes); }
+int rt_scratch_reserve(rt_ctx *ctx, size_t bytes)
+{
+    if (bytes <= ctx->scratch_bytes) return RT_OK;
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    hipFree(ctx->d_scratch);
+    ctx->d_scratch = nullptr;
+    ctx->scratch_bytes = 0;
+    const size_t want = std::max(bytes + bytes / 2, (size_t)1 << 20);
+    RT_HIP(hipMalloc((void **)&ctx->d_scratch, want));
+    ctx->scratch_bytes = want;
+    return RT_OK;
+}
 
 // The pass sequence of _mcy_dense.py:261-291 / _mcz.py:128-163 in ONE call: the tree,
 // the transition matrices and the masks go to the device once, the three kernels
@@ -251,12 +237,12 @@ extern "C" int rt_mcy_esd_passes(rt_ctx *ctx, int64_t nnodes, int64_t n, int64_t
     RT_HIP(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)nsites * nnodes * n * 8;
     const size_t ni = (size_t)(nnodes > 1 ? nnodes - 1 : 1);
-    scratch_plan plan;
+    post_plan plan;
     const size_t o_idx = plan.take(ni * 8), o_ptr = plan.take((size_t)(nnodes + 1) * 8);
     const size_t o_esd = plan.take((size_t)nnodes * n * n * 8);
     const size_t o_mask = plan.take(bytes), o_out = plan.take(bytes);
     const size_t o_obs = obs_likelihood ? plan.take(bytes) : 0;
-    RT_TRY(scratch_reserve(ctx, plan.total));
+    RT_TRY(rt_scratch_reserve(ctx, plan.total));
     unsigned char *base = ctx->d_scratch;
     long *d_idx = (long *)(base + o_idx), *d_ptr = (long *)(base + o_ptr);
     double *d_esd = (double *)(base + o_esd), *d_out = (double *)(base + o_out);
@@ -1196,6 +1182,59 @@ expect_lane_lds_kernel(int nnodes, long nsites, long S, int nslots, const int4 *
 #undef RT_STAMP
 }
 
+// LDS of the fused lane kernel.  Per wave: slots + state sets; per workgroup: topology (+ P when
+// it fits).  As many waves per workgroup (<= 8) as make the most waves resident on a CU's 160 KB.
+struct lane_lds {
+    bool fits = false, p_in_lds = false;
+    int waves_per_group = 1;
+    size_t shared = 0, wave_bytes = 0;       // lds_bytes() of w waves: shared + w * wave_bytes
+    size_t lds_bytes() const { return shared + waves_per_group * wave_bytes; }
+};
+constexpr size_t LANE_LDS_CAP = 160 * 1024;
+
+lane_lds lane_lds_size(int nslots, int64_t nnodes, int64_t n)
+{
+    lane_lds r;
+    r.wave_bytes = (size_t)nslots * n * 512 + (((size_t)nnodes * 64 + 15) & ~(size_t)15);
+    const size_t topo = (((size_t)nnodes * (16 + 4 + 2 * n)) + 15) & ~(size_t)15;
+    const size_t pbytes = ((size_t)nnodes * n * n + 1) / 2 * 2 * 8;
+    if (topo + r.wave_bytes > LANE_LDS_CAP) return r;
+    r.fits = true;
+    r.p_in_lds = topo + pbytes + r.wave_bytes <= LANE_LDS_CAP && pbytes <= 64 * 1024;
+    r.shared = topo + (r.p_in_lds ? pbytes : 0);
+    int best_resident = 0;
+    for (int w = 1; w <= 8; ++w) {
+        const size_t bytes = r.shared + w * r.wave_bytes;
+        if (bytes > LANE_LDS_CAP) break;
+        const int resident = (int)(LANE_LDS_CAP / bytes) * w;
+        if (resident > best_resident) { best_resident = resident; r.waves_per_group = w; }
+    }
+    return r;
+}
+
+// the fused lane kernel for n states over G waves of sites
+int launch_expect_lane_lds(hipStream_t st, int64_t n, const lane_lds &lds, int G, int nnodes,
+                           long nsites, long S, int nslots, const int4 *ops, const int *parent,
+                           const double *esd, const unsigned char *rowbits,
+                           const unsigned char *colbits, const double *root_distn,
+                           const double *weights, const unsigned char *sets, double *Lb, double *part,
+                           int *status, unsigned long long *trace)
+{
+    const int wpg = lds.waves_per_group;
+    const size_t lds_bytes = lds.lds_bytes();
+    return post_dispatch<1, 8>((int)n, [&](auto nv) {
+        constexpr int N = decltype(nv)::value;
+        auto kern = lds.p_in_lds ? expect_lane_lds_kernel<N, true> : expect_lane_lds_kernel<N, false>;
+        if (lds_bytes > 64 * 1024)
+            RT_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds_bytes));
+        hipLaunchKernelGGL(kern, dim3((unsigned)((G + wpg - 1) / wpg)), dim3(64 * wpg), lds_bytes, st,
+                           nnodes, nsites, S, nslots, ops, parent, esd, rowbits, colbits, root_distn,
+                           weights, sets, Lb, part, status, trace);
+        return RT_OK;
+    });
+}
+
 int expectation_weights_lane(rt_ctx *ctx, int64_t nnodes, int64_t n, int64_t nsites,
         const int64_t *idx, const int64_t *ptr, const double *esd, const double *root_distn,
         const int64_t *state_mask, int64_t nobs, const std::vector<int> &obs_idx, int kind,
@@ -1220,38 +1259,19 @@ int expectation_weights_lane(rt_ctx *ctx, int64_t nnodes, int64_t n, int64_t nsi
     // the LDS-resident kernel when its working set fits the default 64 KB of a workgroup
     // (RAOTEH_EXPECT_GLOBAL=1: the global-memory kernel, for A/B runs)
     lane_plan lp;
-    size_t lds_bytes = 0;
+    lane_lds lds;
     bool use_lds = !getenv("RAOTEH_EXPECT_GLOBAL") && build_lane_plan(nnodes, idx, ptr, parent, lp);
-    bool p_in_lds = false;
-    int waves_per_group = 1;
     if (use_lds) {
-        // per wave: slots + state sets; per workgroup: topology (+ P when it fits).  As many
-        // waves per workgroup (<= 8) as make the most waves resident on a CU's 160 KB --
-        // RAOTEH_EXPECT_WAVES overrides
-        const size_t wave_bytes = (size_t)lp.nslots * n * 512 + (((size_t)nnodes * 64 + 15) & ~(size_t)15);
-        const size_t topo = (((size_t)nnodes * (16 + 4 + 2 * n)) + 15) & ~(size_t)15;
-        const size_t pbytes = ((size_t)nnodes * nn + 1) / 2 * 2 * 8;
-        const size_t cap = 160 * 1024;
-        if (topo + wave_bytes > cap) use_lds = false;
-        else {
-            p_in_lds = topo + pbytes + wave_bytes <= cap && pbytes <= 64 * 1024;
-            const size_t shared = topo + (p_in_lds ? pbytes : 0);
-            int best = 1, best_resident = 0;
-            for (int w = 1; w <= 8; ++w) {
-                const size_t bytes = shared + w * wave_bytes;
-                if (bytes > cap) break;
-                const int resident = (int)(cap / bytes) * w;
-                if (resident > best_resident) { best_resident = resident; best = w; }
-            }
-            if (const char *v = getenv("RAOTEH_EXPECT_WAVES")) {
-                const int w = atoi(v);
-                if (w >= 1 && w <= 8 && shared + w * wave_bytes <= cap) best = w;
-            }
-            waves_per_group = best;
-            lds_bytes = shared + best * wave_bytes;
+        lds = lane_lds_size(lp.nslots, nnodes, n);
+        use_lds = lds.fits;
+        // RAOTEH_EXPECT_WAVES overrides the waves per workgroup
+        if (const char *v = use_lds ? getenv("RAOTEH_EXPECT_WAVES") : nullptr) {
+            const int w = atoi(v);
+            if (w >= 1 && w <= 8 && lds.shared + w * lds.wave_bytes <= LANE_LDS_CAP)
+                lds.waves_per_group = w;
         }
     }
-    scratch_plan plan;
+    post_plan plan;
     const size_t o_ops = plan.take((size_t)nnodes * 16), o_trace = plan.take(64);
     const size_t o_idx = plan.take(ni * 8), o_ptr = plan.take((size_t)(nnodes + 1) * 8);
     const size_t o_esd = plan.take(wcount * 8), o_par = plan.take((size_t)nnodes * 4);
@@ -1266,7 +1286,7 @@ int expectation_weights_lane(rt_ctx *ctx, int64_t nnodes, int64_t n, int64_t nsi
     const size_t data_bytes = state_mask ? 0 : (size_t)nsites * nobs * (kind == RT_OBS_STATE ? 1 : 8);
     const size_t o_data = plan.take(std::max<size_t>(std::max(data_bytes, mask_bytes), 8));
     const size_t o_obsn = plan.take(std::max<size_t>((size_t)nobs * 4, 8));
-    RT_TRY(scratch_reserve(ctx, plan.total));
+    RT_TRY(rt_scratch_reserve(ctx, plan.total));
     unsigned char *base = ctx->d_scratch;
     long *d_idx = (long *)(base + o_idx), *d_ptr = (long *)(base + o_ptr);
     double *d_esd = (double *)(base + o_esd);
@@ -1308,41 +1328,17 @@ int expectation_weights_lane(rt_ctx *ctx, int64_t nnodes, int64_t n, int64_t nsi
             hipLaunchKernelGGL(sets_apply_obs_kernel, dim3(2048), dim3(256), 0, st, (int)n,
                                (long)nsites, S, (int)nobs, d_obsn, kind, d_data, d_sets);
     }
-#define RT_EXPECT_LDS_ONE(NV, PL)                                                            \
-    do {                                                                                      \
-        if (lds_bytes > 64 * 1024)                                                            \
-            RT_HIP(hipFuncSetAttribute((const void *)expect_lane_lds_kernel<NV, PL>,          \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize,            \
-                                       (int)lds_bytes));                                      \
-        hipLaunchKernelGGL((expect_lane_lds_kernel<NV, PL>),                                  \
-                           dim3((unsigned)((G + waves_per_group - 1) / waves_per_group)),     \
-                           dim3(64 * waves_per_group), lds_bytes, st, (int)nnodes,            \
-                           (long)nsites, S, lp.nslots, d_ops, d_par, d_esd, d_rb, d_cb, d_root, \
-                           d_w, d_sets, d_L, d_part, d_st, d_trace);                          \
-    } while (0)
-#define RT_EXPECT_LDS(NV)                                                                    \
-    do {                                                                                      \
-        if (p_in_lds) RT_EXPECT_LDS_ONE(NV, true);                                            \
-        else RT_EXPECT_LDS_ONE(NV, false);                                                    \
-    } while (0)
-#define RT_EXPECT_LANE(NV)                                                                   \
-    if (use_lds) RT_EXPECT_LDS(NV);                                                          \
-    else hipLaunchKernelGGL(expect_lane_kernel<NV>, dim3((unsigned)G), dim3(64), 0, st, (int)nnodes, \
-                       (long)nsites, S, d_par, d_idx, d_ptr, d_esd, d_rb, d_cb, d_root, d_w,   \
-                       d_sets, d_M, d_L, d_D, d_part, d_st)
-    switch ((int)n) {
-    case 1: RT_EXPECT_LANE(1); break;
-    case 2: RT_EXPECT_LANE(2); break;
-    case 3: RT_EXPECT_LANE(3); break;
-    case 4: RT_EXPECT_LANE(4); break;
-    case 5: RT_EXPECT_LANE(5); break;
-    case 6: RT_EXPECT_LANE(6); break;
-    case 7: RT_EXPECT_LANE(7); break;
-    default: RT_EXPECT_LANE(8); break;
-    }
-#undef RT_EXPECT_LANE
-#undef RT_EXPECT_LDS
-#undef RT_EXPECT_LDS_ONE
+    if (use_lds)
+        RT_TRY(launch_expect_lane_lds(st, n, lds, G, (int)nnodes, (long)nsites, S, lp.nslots, d_ops,
+                                      d_par, d_esd, d_rb, d_cb, d_root, d_w, d_sets, d_L, d_part, d_st,
+                                      d_trace));
+    else
+        RT_TRY(post_dispatch<1, 8>((int)n, [&](auto nv) {
+            hipLaunchKernelGGL(expect_lane_kernel<decltype(nv)::value>, dim3((unsigned)G), dim3(64), 0,
+                               st, (int)nnodes, (long)nsites, S, d_par, d_idx, d_ptr, d_esd, d_rb, d_cb,
+                               d_root, d_w, d_sets, d_M, d_L, d_D, d_part, d_st);
+            return RT_OK;
+        }));
     hipLaunchKernelGGL(sum_parts_wide_kernel, dim3((unsigned)((wcount + 3) / 4)), dim3(256), 0,
                        st, G, (long)wcount, d_part, d_out);
     RT_HIP(hipGetLastError());
@@ -1354,13 +1350,13 @@ int expectation_weights_lane(rt_ctx *ctx, int64_t nnodes, int64_t n, int64_t nsi
         RT_HIP(hipMemcpy(t, d_trace, sizeof t, hipMemcpyDeviceToHost));
         fprintf(stderr, "[raoteh_amd] expect trace (clocks): fill %llu, sets %llu, up %llu, root %llu, "
                 "down %llu; %d slots, %d waves per workgroup, %zu B of LDS\n", t[1] - t[0],
-                t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4], lp.nslots, waves_per_group,
-                lds_bytes);
+                t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4], lp.nslots, lds.waves_per_group,
+                lds.lds_bytes());
     }
     return RT_OK;
 }
 
-// ---- n <= 8 on a RESIDENT batch (rt_expect_step) -------------------------------------------
+// ---- n <= 4 on a RESIDENT batch (rt_expect_step) -------------------------------------------
 // The same fused lane-per-site kernel, with everything it needs already on the device: the
 // transition matrices of the model (their zero patterns are read off by a kernel), the
 // allowed sets of the batch (built once per batch from its resident layout), the stack
@@ -1368,11 +1364,9 @@ int expectation_weights_lane(rt_ctx *ctx, int64_t nnodes, int64_t n, int64_t nsi
 
 struct expect_lane_state_t {
     lane_plan lp;
-    bool p_in_lds = false;
-    int waves_per_group = 1;
-    size_t lds_bytes = 0;
+    lane_lds lds;
     int4 *d_ops = nullptr;
-    int *d_par = nullptr, *d_node_of_k = nullptr;
+    int *d_par = nullptr;
     unsigned char *d_rb = nullptr, *d_cb = nullptr;
     ~expect_lane_state_t()
     {
@@ -1436,16 +1430,27 @@ void rt_expect_lane_release(rt_model *m)
     m->expect_lane_state = nullptr;
 }
 
+// the kernel's L of every node and its per-wave partial sums
+rt_expect_lane_scratch rt_expect_lane_take(const rt_model *m, const rt_sites *s, post_plan *plan)
+{
+    const size_t S = (size_t)((s->nsites + 63) / 64 * 64), cells = (size_t)m->nnodes * m->n;
+    rt_expect_lane_scratch at;
+    at.o_L = plan->take(cells * S * 8);
+    at.o_part = plan->take(S / 64 * cells * m->n * 8);
+    return at;
+}
+
 // W f64[nnodes][n][n] (device; slot 0, column 0: the weighted root posterior sums) and the
 // per-site status for a resident lane-family batch; asynchronous on the context's stream
-int rt_expect_lane_resident(rt_model *m, rt_sites *s, double *d_W, int *d_status)
+int rt_expect_lane_resident(rt_model *m, rt_sites *s, unsigned char *scratch,
+                            const rt_expect_lane_scratch &at, double *d_W, int *d_status)
 {
     rt_ctx *ctx = m->ctx;
     const int64_t n = m->n, nnodes = m->nnodes, nsites = s->nsites;
     RT_REQUIRE(n <= 8 && s->layout == RT_LAYOUT_LANE && !s->d_scratch,
                "not a resident lane-family batch");
     hipStream_t st = ctx->stream;
-    const size_t nn = (size_t)n * n, wcount = (size_t)nnodes * nn;
+    const size_t wcount = (size_t)nnodes * n * n;
     expect_lane_state_t *ls = (expect_lane_state_t *)m->expect_lane_state;
     if (!ls) {
         std::unique_ptr<expect_lane_state_t> fresh(new (std::nothrow) expect_lane_state_t());
@@ -1454,25 +1459,11 @@ int rt_expect_lane_resident(rt_model *m, rt_sites *s, double *d_W, int *d_status
             rt_set_error("rt_expect_step: no LDS stack program for this tree");
             return RT_ERR_UNSUPPORTED;
         }
-        const size_t wave_bytes = (size_t)fresh->lp.nslots * n * 512 + (((size_t)nnodes * 64 + 15) & ~(size_t)15);
-        const size_t topo = (((size_t)nnodes * (16 + 4 + 2 * n)) + 15) & ~(size_t)15;
-        const size_t pbytes = ((size_t)nnodes * nn + 1) / 2 * 2 * 8;
-        const size_t cap = 160 * 1024;
-        if (topo + wave_bytes > cap) {
+        fresh->lds = lane_lds_size(fresh->lp.nslots, nnodes, n);
+        if (!fresh->lds.fits) {
             rt_set_error("rt_expect_step: the tree does not fit the LDS of the fused kernel");
             return RT_ERR_UNSUPPORTED;
         }
-        fresh->p_in_lds = topo + pbytes + wave_bytes <= cap && pbytes <= 64 * 1024;
-        const size_t shared = topo + (fresh->p_in_lds ? pbytes : 0);
-        int best = 1, best_resident = 0;
-        for (int w = 1; w <= 8; ++w) {
-            const size_t bytes = shared + w * wave_bytes;
-            if (bytes > cap) break;
-            const int resident = (int)(cap / bytes) * w;
-            if (resident > best_resident) { best_resident = resident; best = w; }
-        }
-        fresh->waves_per_group = best;
-        fresh->lds_bytes = shared + best * wave_bytes;
         RT_HIP(hipMalloc((void **)&fresh->d_ops, (size_t)nnodes * 16));
         RT_HIP(hipMalloc((void **)&fresh->d_par, (size_t)nnodes * 4));
         RT_HIP(hipMalloc((void **)&fresh->d_rb, (size_t)nnodes * n));
@@ -1486,64 +1477,34 @@ int rt_expect_lane_resident(rt_model *m, rt_sites *s, double *d_W, int *d_status
     }
     const long S = (long)((nsites + 63) / 64 * 64);
     const int G = (int)(S / 64);
-    // the allowed sets of the batch, once
+    // the allowed sets of the batch, once: the batch gets them when they are complete
     if (!s->d_sets) {
         const int K = (int)s->nobs;
         std::vector<int> node_of_k((size_t)std::max(K, 1), 0);
         for (const rt_op &op : s->ops)
             if (op.obs >= 0) node_of_k[(size_t)op.obs] = op.node;
-        int *d_nk = nullptr;
-        RT_HIP(hipMalloc((void **)&s->d_sets, (size_t)nnodes * S));
-        RT_HIP(hipMalloc((void **)&d_nk, node_of_k.size() * 4));
+        dev_free mem;
+        unsigned char *d_sets;
+        int *d_nk;
+        RT_TRY(mem.alloc(d_sets, (size_t)nnodes * S));
+        RT_TRY(mem.alloc(d_nk, node_of_k.size()));
         RT_HIP(hipMemcpyAsync(d_nk, node_of_k.data(), node_of_k.size() * 4, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(sets_fill_kernel, dim3(2048), dim3(256), 0, st, (long)nnodes * S, (int)n,
-                           s->d_sets);
+                           d_sets);
         if (K > 0)
             hipLaunchKernelGGL(sets_from_lane_batch_kernel, dim3(2048), dim3(256), 0, st, (int)n,
                                (long)nsites, S, K, s->block_sites, s->compact_states,
-                               (const void *)s->d_obs, d_nk, s->d_sets);
+                               (const void *)s->d_obs, d_nk, d_sets);
         RT_HIP(hipGetLastError());
         RT_HIP(hipStreamSynchronize(st));
-        hipFree(d_nk);
+        s->d_sets = mem.release(d_sets);
     }
-    const size_t arr = (size_t)nnodes * n * S * 8;
-    scratch_plan plan;
-    const size_t o_L = plan.take(arr), o_part = plan.take((size_t)G * wcount * 8);
-    RT_TRY(scratch_reserve(ctx, plan.total));
-    double *d_L = (double *)(ctx->d_scratch + o_L), *d_part = (double *)(ctx->d_scratch + o_part);
+    double *d_L = (double *)(scratch + at.o_L), *d_part = (double *)(scratch + at.o_part);
     hipLaunchKernelGGL(pattern_bits_kernel, dim3((unsigned)nnodes), dim3(64), 0, st, (int)n, m->d_P,
                        ls->d_rb, ls->d_cb);
-    const size_t lds_bytes = ls->lds_bytes;
-    const int wpg = ls->waves_per_group;
-#define RT_EXPECT_RES_ONE(NV, PL)                                                            \
-    do {                                                                                      \
-        if (lds_bytes > 64 * 1024)                                                            \
-            RT_HIP(hipFuncSetAttribute((const void *)expect_lane_lds_kernel<NV, PL>,          \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize,            \
-                                       (int)lds_bytes));                                      \
-        hipLaunchKernelGGL((expect_lane_lds_kernel<NV, PL>), dim3((unsigned)((G + wpg - 1) / wpg)), \
-                           dim3(64 * wpg), lds_bytes, st, (int)nnodes, (long)nsites, S,       \
-                           ls->lp.nslots, ls->d_ops, ls->d_par, m->d_P, ls->d_rb, ls->d_cb,   \
-                           m->d_root, s->d_weights, s->d_sets, d_L, d_part, d_status,         \
-                           (unsigned long long *)nullptr);                                    \
-    } while (0)
-#define RT_EXPECT_RES(NV)                                                                    \
-    do {                                                                                      \
-        if (ls->p_in_lds) RT_EXPECT_RES_ONE(NV, true);                                        \
-        else RT_EXPECT_RES_ONE(NV, false);                                                    \
-    } while (0)
-    switch ((int)n) {
-    case 1: RT_EXPECT_RES(1); break;
-    case 2: RT_EXPECT_RES(2); break;
-    case 3: RT_EXPECT_RES(3); break;
-    case 4: RT_EXPECT_RES(4); break;
-    case 5: RT_EXPECT_RES(5); break;
-    case 6: RT_EXPECT_RES(6); break;
-    case 7: RT_EXPECT_RES(7); break;
-    default: RT_EXPECT_RES(8); break;
-    }
-#undef RT_EXPECT_RES
-#undef RT_EXPECT_RES_ONE
+    RT_TRY(launch_expect_lane_lds(st, n, ls->lds, G, (int)nnodes, (long)nsites, S, ls->lp.nslots,
+                                  ls->d_ops, ls->d_par, m->d_P, ls->d_rb, ls->d_cb, m->d_root,
+                                  s->d_weights, s->d_sets, d_L, d_part, d_status, nullptr));
     hipLaunchKernelGGL(sum_parts_wide_kernel, dim3((unsigned)((wcount + 3) / 4)), dim3(256), 0, st, G,
                        (long)wcount, d_part, d_W);
     RT_HIP(hipGetLastError());
@@ -1604,7 +1565,7 @@ int expectation_weights_impl(rt_ctx *ctx, int64_t nnodes, int64_t n, int64_t nsi
     const int G = (int)std::min<int64_t>(nsites, 64);
     const size_t bytes = (size_t)nsites * nnodes * n * 8;
     const size_t ni = (size_t)(nnodes > 1 ? nnodes - 1 : 1);
-    scratch_plan plan;
+    post_plan plan;
     const size_t o_idx = plan.take(ni * 8), o_ptr = plan.take((size_t)(nnodes + 1) * 8);
     const size_t o_esd = plan.take(wcount * 8), o_par = plan.take((size_t)nnodes * 4);
     const size_t o_mask = plan.take(bytes), o_pmap = plan.take(bytes), o_distn = plan.take(bytes);
@@ -1614,7 +1575,7 @@ int expectation_weights_impl(rt_ctx *ctx, int64_t nnodes, int64_t n, int64_t nsi
     const size_t data_bytes = state_mask ? 0 : (size_t)nsites * nobs * (kind == RT_OBS_STATE ? 1 : 8);
     const size_t o_data = plan.take(std::max<size_t>(data_bytes, 8));
     const size_t o_obsn = plan.take(std::max<size_t>((size_t)nobs * 4, 8));
-    RT_TRY(scratch_reserve(ctx, plan.total));
+    RT_TRY(rt_scratch_reserve(ctx, plan.total));
     unsigned char *base = ctx->d_scratch;
     long *d_idx = (long *)(base + o_idx), *d_ptr = (long *)(base + o_ptr);
     double *d_esd = (double *)(base + o_esd);

@@ -1,24 +1,13 @@
 // What the reads of a RESIDENT batch share (posterior.hip, branch_expect.hip, sample.hip,
 // mapping.hip).  Host: post_pass, one description of such a call -- its checks, the common
-// pieces of its scratch, the upward pass with L (and M) of every step stored -- and the dispatch
-// over the kernels' template arguments.  Device: the steps the downward kernels have in common.
+// pieces of its scratch, the upward pass with L (and M) of every step stored (the plan of the
+// scratch and the dispatch over the kernels' template arguments: common.h).  Device: the steps the
+// downward kernels have in common.
 #pragma once
 
 #include "common.h"
 
 #include <algorithm>
-#include <type_traits>
-
-// byte offsets of the call's pieces in the context's scratch (256-byte aligned)
-struct post_plan {
-    size_t total = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t o = total;
-        total += (bytes + 255) / 256 * 256;
-        return o;
-    }
-};
 
 // One read of a resident batch.  post_open .. post_layout make the checks every such call makes
 // and take the common pieces from `plan`; the caller takes its own from the same plan, then
@@ -193,17 +182,6 @@ inline int post_up(post_pass *p, const int *w_of_node, bool pack_pt)
         RT_TRY(rt_launch_pack_pt(p->ctx, (int)p->n, p->NT, p->KP, p->nops, p->d_ptab, p->m->d_P,
                                  p->d_PT));
     return RT_OK;
-}
-
-// f(std::integral_constant<int, V>) for the V in LO .. HI that equals v: the one table of the
-// kernels' template arguments.  The lane kernels take the states (2 .. 4), the wave-per-tile
-// kernels the row tiles NT (1 .. 8), the downward kernels the k-steps KS (2 .. 32) with
-// NT = ceil(KS / 4).
-template <int LO, int HI, class F>
-inline int post_dispatch(int v, F &&f)
-{
-    if constexpr (LO > HI) return RT_ERR_UNSUPPORTED;
-    else return v == LO ? f(std::integral_constant<int, LO>()) : post_dispatch<LO + 1, HI>(v, f);
 }
 
 // n <= 4: one lane per site.  The observation of stream position k from the batch's lane-family
