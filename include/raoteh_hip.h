@@ -656,6 +656,75 @@ int rt_sites_multi_mixture(rt_sites *sites, const double *class_weights, double 
             int32_t *status, double totals[3]);
 const char *rt_sites_multi_kernel_name(const rt_sites *sites);
 
+/* ---- 2c. partitioned likelihood: each site under its own rate set, one pruning launch ------
+ *
+ * Codon positions, genes, rate categories fixed per column, or one compound process per
+ * alignment column (examples/p53/liwen.py:599-650): site i is evaluated under rate set
+ * site_set[i] of rt_model_set_rate_sets (section 2b: the K transition tables of one exponential
+ * launch).  Neither K sub-batches with K x (rt_model_set_rates + rt_step) nor rt_step_multi on
+ * everything (K times the arithmetic) is needed.
+ *
+ * rt_partition_plan: the resident order of such a batch, host only (no context).  A granule is
+ *   `granule` consecutive resident sites that share one copy of the tables in the kernel that
+ *   runs: 16 in the matrix-pipe layout (n > 4), the workgroup's span of sites in the lane layout.
+ *   The sites are sorted by set (stable counting sort: a set's sites keep the caller's order),
+ *   every set's run is padded up to a multiple of the granule by repeating the run's last real
+ *   site (valid data, no spurious zero-probability status); an empty set has an empty run.
+ *   site_set int32[nsites]; *padded receives the number of slots; with every array NULL that is
+ *   all.  Otherwise `capacity` >= *padded slots (nsites + nsets * (granule - 1) always holds
+ *   them) and each array given is filled: order int64[padded] (source site of every slot),
+ *   slot_of_site int64[nsites] (the slot holding site i itself), is_pad uint8[padded],
+ *   granule_set int32[padded / granule], run_begin int64[nsets + 1] (set k's run is the slots
+ *   [run_begin[k], run_begin[k + 1])).  RT_ERR_INVALID: a set index outside 0..nsets-1, sizes
+ *   below 1, a capacity too small.
+ * rt_sites_create_partitioned: rt_sites_create (same nsites, kind, nobs, obs_nodes, data: all
+ *   three observation kinds; the host data is site-major, so the permutation is a row gather
+ *   before the packing) plus site_set int32[nsites] and nsets.  The batch is resident in the
+ *   planner's order and runs the interpreter kernels only (no tree-specialised kernel is
+ *   compiled): in the lane family the register-ring form, above 4 states the one-wave and the
+ *   split-M forms a "jit" = 0 batch runs -- leaf states and root halves included -- with the
+ *   tables of granule g taken from set granule_set[g] (one scalar load and add per wave; tiles
+ *   of different sets share workgroups).  RT_ERR_UNSUPPORTED with a message: the "rescale" or
+ *   "force_generic" option set, a tree the fast kernels do not take, nsets outside
+ *   1..RT_MAX_RATE_SETS.  RT_ERR_INVALID: a set index outside 0..nsets-1, and what
+ *   rt_sites_create refuses.
+ * rt_step_partitioned: (recompute_transitions != 0: the K (nnodes - 1) exponentials again from
+ *   the resident rate sets, as rt_step_multi,) ONE pruning launch, then per set a fixed-order
+ *   two-stage sum over the resident results with the pads masked, the batch totals and the
+ *   gather into caller order.  Asynchronous on the context's stream; a pending deferred reduction
+ *   of the context is flushed first and nothing is deferred.  RT_ERR_INVALID: an ordinary batch;
+ *   fewer rate sets resident in the model than the batch's nsets (none at all included; sets
+ *   beyond nsets are simply not used).
+ * On a partitioned batch
+ *   rt_sites_get_logliks   returns caller order, never a pad;
+ *   rt_sites_set_weights   takes caller order (f64[nsites]);
+ *   rt_sites_get_totals    gives the totals over the real sites;
+ *   rt_sites_get_partition_totals: totals f64[nsets][3], totals[k] with the meaning of
+ *     rt_sites_get_totals over set k's sites ({0, 0, 0} for an empty set); weighted_sums
+ *     f64[nsets] (or NULL), weighted_sums[k] = sum_i w_i loglik[i] over set k's sites of non-zero
+ *     likelihood, w from rt_sites_set_weights at the time of the step (default 1).  Two steps
+ *     give the same bits (the shape of the sums depends on the plan alone);
+ *   rt_sites_kernel_name   ends in ",partitioned" after a step.
+ *   The getters synchronise; they return RT_ERR_INVALID before the first rt_step_partitioned
+ *   (rt_sites_get_totals: zeros) and after the model's number of rate sets changed, until the
+ *   next rt_step_partitioned (the epoch of section 2b).
+ * Everything else refuses a partitioned batch with RT_ERR_UNSUPPORTED and leaves it untouched:
+ *   rt_prune, rt_step, rt_step_multi, rt_sites_clone, rt_expect_step, rt_sites_posteriors,
+ *   rt_sites_branch_expectations, rt_sites_branch_profiles, rt_sites_sample_states,
+ *   rt_sites_sample_mappings, rt_allreduce_totals, rt_allreduce_totals_group.
+ *                                                               */
+int rt_partition_plan(const int32_t *site_set, int64_t nsites, int64_t nsets, int64_t granule,
+            int64_t capacity, int64_t *order, int64_t *slot_of_site, uint8_t *is_pad,
+            int32_t *granule_set, int64_t *run_begin, int64_t *padded);
+int rt_sites_create_partitioned(rt_model *model, int64_t nsites, int kind, int64_t nobs,
+            const int64_t *obs_nodes, const void *data, const int32_t *site_set, int64_t nsets,
+            rt_sites **sites);
+int rt_step_partitioned(rt_model *model, rt_sites *sites, int recompute_transitions);
+int rt_sites_get_partition_totals(rt_sites *sites, double *totals, double *weighted_sums);
+/* what the batch was laid out with: any pointer may be NULL; an ordinary batch gives zeros */
+int rt_sites_partition_info(const rt_sites *sites, int64_t *nsets, int64_t *granule,
+            int64_t *padded);
+
 /* ---- 3. multi-GPU: one process per GPU, RCCL over xGMI ------------------- */
 
 /* rank 0 calls rt_comm_unique_id and ships the 128 bytes to the other ranks

@@ -158,6 +158,13 @@ SIGNATURES = {
     'rt_sites_get_multi_totals': (c_int, [c_void_p, _p_f64, _p_f64]),
     'rt_sites_multi_mixture': (c_int, [c_void_p, _p_f64, _p_f64, _p_i32, _p_f64]),
     'rt_sites_multi_kernel_name': (c_char_p, [c_void_p]),
+    'rt_partition_plan': (c_int, [_p_i32, c_int64, c_int64, c_int64, c_int64, _p_i64, _p_i64,
+                                  POINTER(c_ubyte), _p_i32, _p_i64, _p_i64]),
+    'rt_sites_create_partitioned': (c_int, [c_void_p, c_int64, c_int, c_int64, _p_i64, c_void_p,
+                                            _p_i32, c_int64, POINTER(c_void_p)]),
+    'rt_step_partitioned': (c_int, [c_void_p, c_void_p, c_int]),
+    'rt_sites_get_partition_totals': (c_int, [c_void_p, _p_f64, _p_f64]),
+    'rt_sites_partition_info': (c_int, [c_void_p, _p_i64, _p_i64, _p_i64]),
     'rt_comm_available': (c_int, []),
     'rt_comm_unique_id': (c_int, [POINTER(c_ubyte)]),
     'rt_comm_init': (c_int, [c_void_p, c_int, c_int, POINTER(c_ubyte)]),

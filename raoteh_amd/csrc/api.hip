@@ -2,6 +2,7 @@
 // site batches, and the host-pointer reference-shaped entry points.
 // See include/raoteh_hip.h for the contract of every function.
 #include "common.h"
+#include "partition_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -964,6 +965,16 @@ static int opt_jit_block_sites(const rt_ctx *c)
     return c->opt_jit_block_sites != RT_OPT_UNSET ? c->opt_jit_block_sites : g_jit_block_sites.load();
 }
 
+static void partition_release(rt_sites *s)
+{
+    rt_partition *p = s->part;
+    if (!p) return;
+    hipFree(p->d_order); hipFree(p->d_slot_of_site); hipFree(p->d_is_pad); hipFree(p->d_granule_set);
+    hipFree(p->d_run_begin); hipFree(p->d_loglik); hipFree(p->d_status); hipFree(p->d_totals);
+    delete p;
+    s->part = nullptr;
+}
+
 extern "C" int rt_sites_destroy(rt_sites *s)
 {
     if (!s) return RT_OK;
@@ -974,6 +985,7 @@ extern "C" int rt_sites_destroy(rt_sites *s)
     // an all-reduce of this batch's totals may still be in flight on the comm stream
     rt_jit_ref(s->model->ctx, s->jit_fn, -1);
     if (s->expect_twin) rt_sites_destroy(s->expect_twin);
+    partition_release(s);
     hipFree(s->d_weights);
     hipFree(s->d_sets);
     hipFree(s->d_raw);
@@ -1089,6 +1101,23 @@ static int program_stack_slots(const std::vector<int32_t> &prog, int64_t slot_by
 }
 
 static bool want_root_halves(const rt_sites *s, int64_t ntiles);
+
+// what does not take a partitioned batch (include/raoteh_hip.h, section 2c)
+static int partition_refuse(const rt_sites *s, const char *who)
+{
+    if (!s->part) return RT_OK;
+    rt_set_error("%s: a partitioned batch is evaluated by rt_step_partitioned only", who);
+    return RT_ERR_UNSUPPORTED;
+}
+// the results a getter is about to read belong to the model's current rate sets
+static int partition_ready(const rt_sites *s, const char *who)
+{
+    const rt_partition *p = s->part;
+    RT_REQUIRE(p->stepped, "%s: no rt_step_partitioned has written this batch yet", who);
+    RT_REQUIRE(p->epoch == s->model->multi.epoch && p->model_K == s->model->multi.K,
+               "%s: the number of rate sets changed since the batch's last rt_step_partitioned", who);
+    return RT_OK;
+}
 
 // sizes of the resident layout (blocks, bytes, partial sums) -> *padded = sites incl. padding
 static void sites_layout_sizes(rt_sites *s, int64_t *padded_out)
@@ -1315,6 +1344,7 @@ struct jit_override {
     bool sparse = false;      // split-M family: leaf steps gather columns of P (leaf states)
     bool pipe = false;        // ... from the pipelined generator (leaves as factors)
     bool teams = false;       // split-M family: two four-wave teams per workgroup
+    bool reg_lane = false;    // lane family: the register-ring kernel, never the LDS-DMA one
 };
 
 // At most this many background compiles at a time (RAOTEH_JIT_MAX_JOBS, default 2): a caller
@@ -1738,6 +1768,14 @@ static void sites_multi_poll(rt_sites *s, bool wait);
 static int verify_jit_kernel(rt_sites *s, int kind, void *multi_fn = nullptr,
                              void *multi_combine = nullptr);
 
+// a tree the fast kernels do not take: more accumulator slots than their LDS stack has
+static bool sites_need_generic(const rt_model *m)
+{
+    const int64_t nt_waves = std::max<int64_t>(4, (m->n + 15) / 16);
+    return m->max_depth > RT_FAST_MAX_DEPTH ||
+           (m->n > 64 && nt_waves * m->max_depth * 2048 + 20 * 1024 > 160 * 1024);
+}
+
 static int sites_create_impl(rt_model *m, int64_t nsites, int kind, int64_t nobs,
                              const int64_t *obs_nodes, const void *data,
                              const jit_override *ov, rt_sites **out)
@@ -1780,9 +1818,7 @@ static int sites_create_impl(rt_model *m, int64_t nsites, int kind, int64_t nobs
     }
     // the split-M kernels keep NT * 2 KB of LDS per accumulator slot: above 64 states a tree
     // that needs more slots than the CU's 160 KB hold runs the generic kernel
-    const int64_t nt_waves = std::max<int64_t>(4, (m->n + 15) / 16);
-    const bool generic = opt_force_generic(m->ctx) || m->max_depth > RT_FAST_MAX_DEPTH ||
-                         (m->n > 64 && nt_waves * m->max_depth * 2048 + 20 * 1024 > 160 * 1024);
+    const bool generic = opt_force_generic(m->ctx) || sites_need_generic(m);
     s->layout = (generic || m->n <= 4) ? RT_LAYOUT_LANE : RT_LAYOUT_MFMA;
     // rescaling lives in the interpreter kernels: no tree-specialised kernel for such a batch,
     // and the lane family's VGPR-ring variant (the LDS-DMA variant fuses cherries)
@@ -1800,7 +1836,7 @@ static int sites_create_impl(rt_model *m, int64_t nsites, int kind, int64_t nobs
     s->mfma_solo = s->layout == RT_LAYOUT_MFMA && m->n <= 32 && !getenv("RAOTEH_MFMA_NO_SOLO");
     if (ov && ov->no_solo) s->mfma_solo = false;
     if (const char *v = getenv("RAOTEH_LANE_VARIANT")) s->lane_dma = strcmp(v, "dma") == 0;
-    if (s->rescale) s->lane_dma = false;
+    if (s->rescale || (ov && ov->reg_lane)) s->lane_dma = false;
     if (const char *r = getenv("RAOTEH_LANE_RING")) s->lane_ring = atoi(r);
     else s->lane_ring = s->lane_dma ? 0 : 8;      // 0: rt_launch_prune picks what fits
     // observed STATES, all at leaves, none unobserved, split-M family: the kernel's leaf steps
@@ -2304,6 +2340,7 @@ extern "C" int rt_sites_clone(rt_sites *src, rt_sites **out)
 {
     RT_REQUIRE(src && out, "null pointer");
     *out = nullptr;
+    RT_TRY(partition_refuse(src, "rt_sites_clone"));
     RT_HIP(hipSetDevice(src->model->ctx->device));
     // (a lane-family batch changes its resident layout when its kernel arrives: wait for it
     // rather than cloning the image it is about to leave)
@@ -2437,14 +2474,18 @@ extern "C" int rt_sites_set_weights(rt_sites *s, const double *weights)
         s->d_weights = nullptr;
         return RT_OK;
     }
-    if (!s->d_weights) RT_HIP(hipMalloc((void **)&s->d_weights, (size_t)s->nsites * 8));
-    RT_HIP(hipMemcpy(s->d_weights, weights, (size_t)s->nsites * 8, hipMemcpyHostToDevice));
+    // (a partitioned batch: caller order, one weight per real site; the reductions look them up
+    // through the plan's order)
+    const size_t nw = (size_t)(s->part ? s->part->nsites : s->nsites);
+    if (!s->d_weights) RT_HIP(hipMalloc((void **)&s->d_weights, nw * 8));
+    RT_HIP(hipMemcpy(s->d_weights, weights, nw * 8, hipMemcpyHostToDevice));
     return RT_OK;
 }
 
 extern "C" int64_t rt_sites_device_bytes(const rt_sites *s)
 {
-    return s ? s->obs_bytes : 0;
+    // (a partitioned batch: the plan's arrays, the caller-order results and the per-set sums too)
+    return s ? s->obs_bytes + (s->part ? s->part->device_bytes : 0) : 0;
 }
 
 extern "C" double rt_sites_jit_compile_seconds(const rt_sites *s)
@@ -2470,6 +2511,7 @@ extern "C" const char *rt_sites_kernel_name(const rt_sites *s)
 extern "C" int rt_prune(rt_model *m, rt_sites *s)
 {
     RT_REQUIRE(m && s, "null pointer");
+    RT_TRY(partition_refuse(s, "rt_prune"));
     RT_REQUIRE(s->model == m, "the site batch belongs to another model");
     RT_REQUIRE(m->have_P, "the model has no transition matrices yet");
     RT_HIP(hipSetDevice(m->ctx->device));
@@ -2484,6 +2526,7 @@ extern "C" int rt_prune(rt_model *m, rt_sites *s)
 extern "C" int rt_step(rt_model *m, rt_sites *s, int recompute_transitions)
 {
     RT_REQUIRE(m && s, "null pointer");
+    RT_TRY(partition_refuse(s, "rt_step"));
     RT_REQUIRE(s->model == m, "the site batch belongs to another model");
     RT_REQUIRE(!recompute_transitions || m->d_Q || m->spectral,
                "rt_model_set_rates has not been called");
@@ -2504,6 +2547,16 @@ extern "C" int rt_step(rt_model *m, rt_sites *s, int recompute_transitions)
 extern "C" int rt_sites_get_logliks(rt_sites *s, double *loglik, int32_t *status)
 {
     RT_REQUIRE(s, "null pointer");
+    if (s->part) {
+        // caller order, gathered on the device by the step: never a pad
+        RT_TRY(partition_ready(s, "rt_sites_get_logliks"));
+        const rt_partition *p = s->part;
+        RT_HIP(hipSetDevice(s->model->ctx->device));
+        RT_HIP(hipStreamSynchronize(s->model->ctx->stream));
+        if (loglik) RT_HIP(hipMemcpy(loglik, p->d_loglik, p->nsites * 8, hipMemcpyDeviceToHost));
+        if (status) RT_HIP(hipMemcpy(status, p->d_status, p->nsites * 4, hipMemcpyDeviceToHost));
+        return RT_OK;
+    }
     RT_REQUIRE(s->pruned, "rt_sites_get_logliks: no pruning kernel has written this batch yet "
                "(rt_prune / rt_step first)");
     RT_HIP(hipSetDevice(s->model->ctx->device));
@@ -2518,6 +2571,7 @@ extern "C" int rt_sites_get_logliks(rt_sites *s, double *loglik, int32_t *status
 extern "C" int rt_sites_get_totals(rt_sites *s, double totals[3])
 {
     RT_REQUIRE(s && totals, "null pointer");
+    if (s->part && s->part->stepped) RT_TRY(partition_ready(s, "rt_sites_get_totals"));
     RT_HIP(hipSetDevice(s->model->ctx->device));
     RT_TRY(rt_flush_reduce(s->model->ctx));
     RT_HIP(hipStreamSynchronize(s->model->ctx->stream));
@@ -2679,6 +2733,7 @@ static int sites_multi_reserve_halves(rt_sites *s, int64_t K)
 extern "C" int rt_step_multi(rt_model *m, rt_sites *s, int recompute_transitions)
 {
     RT_REQUIRE(m && s, "null pointer");
+    RT_TRY(partition_refuse(s, "rt_step_multi"));
     RT_REQUIRE(s->model == m, "the site batch belongs to another model");
     RT_REQUIRE(m->multi.K > 0, "rt_model_set_rate_sets has not been called");
     rt_ctx *ctx = m->ctx;
@@ -2833,6 +2888,169 @@ extern "C" int rt_sites_multi_mixture(rt_sites *s, const double *class_weights, 
 extern "C" const char *rt_sites_multi_kernel_name(const rt_sites *s)
 {
     return s ? s->multi_kernel_name : "";
+}
+
+// ---- partitioned likelihood (section 2c of the header) ----------------------------------------
+
+extern "C" int rt_sites_create_partitioned(rt_model *m, int64_t nsites, int kind, int64_t nobs,
+                                           const int64_t *obs_nodes, const void *data,
+                                           const int32_t *site_set, int64_t nsets, rt_sites **out)
+{
+    RT_REQUIRE(m && out && site_set, "null pointer");
+    *out = nullptr;
+    RT_REQUIRE(nsites >= 1, "nsites must be >= 1");
+    RT_REQUIRE(kind == RT_OBS_DENSE || kind == RT_OBS_STATE || kind == RT_OBS_MASK,
+               "unknown observation kind %d", kind);
+    RT_REQUIRE(nobs >= 0 && nobs <= m->nnodes, "bad nobs");
+    RT_REQUIRE(nobs == 0 || (obs_nodes && data), "null observation arrays");
+    const char *why = nullptr;
+    if (nsets < 1 || nsets > RT_MAX_RATE_SETS) why = "the number of sets is outside 1..64";
+    else if (opt_rescale(m->ctx)) why = "the \"rescale\" option is set (its kernels have no per-granule lookup)";
+    else if (opt_force_generic(m->ctx)) why = "the \"force_generic\" option is set (the generic kernel has no per-granule lookup)";
+    else if (sites_need_generic(m)) why = "the tree is one the fast kernels do not take";
+    if (why) {
+        rt_set_error("rt_sites_create_partitioned: %s (nsets=%lld)", why, (long long)nsets);
+        return RT_ERR_UNSUPPORTED;
+    }
+    // the granule of the kernel that will run, then the resident order
+    const int64_t n = m->n;
+    const int64_t G = n <= 4 ? rt_lane_reg_granule(m) : 16;
+    rt_partition_layout plan;
+    int64_t bad = -1;
+    if (rt_partition_plan_build(site_set, nsites, nsets, G, &plan, &bad) != 0) {
+        rt_set_error("rt_sites_create_partitioned: site_set[%lld]=%d is outside 0..%lld",
+                     (long long)bad, bad >= 0 ? (int)site_set[bad] : 0, (long long)nsets - 1);
+        return RT_ERR_INVALID;
+    }
+    // site-major host data: the permutation is a gather of rows
+    const size_t row = kind == RT_OBS_DENSE ? (size_t)nobs * (size_t)n * 8
+                     : kind == RT_OBS_STATE ? (size_t)nobs
+                                            : (size_t)nobs * 8 * (size_t)((n + 63) / 64);
+    std::vector<unsigned char> rows;
+    try {
+        rows.resize((size_t)plan.padded * row + 8);
+    } catch (const std::bad_alloc &) {
+        rt_set_error("rt_sites_create_partitioned: out of host memory");
+        return RT_ERR_NOMEM;
+    }
+    for (int64_t slot = 0; slot < plan.padded && row; ++slot)
+        memcpy(rows.data() + (size_t)slot * row,
+               (const unsigned char *)data + (size_t)plan.order[(size_t)slot] * row, row);
+    jit_override interp;
+    interp.mode = 1;              // interpreter kernels only
+    interp.sparse = true;         // ... their leaf-state form where the data allows it
+    interp.reg_lane = true;
+    rt_sites *s = nullptr;
+    RT_TRY(sites_create_impl(m, plan.padded, kind, nobs, obs_nodes, rows.data(), &interp, &s));
+    rt_partition *p = new (std::nothrow) rt_partition();
+    if (!p) {
+        rt_sites_destroy(s);
+        rt_set_error("rt_sites_create_partitioned: out of host memory");
+        return RT_ERR_NOMEM;
+    }
+    s->part = p;
+    p->nsites = nsites;
+    p->nsets = nsets;
+    p->G = G;
+    p->padded = plan.padded;
+    int64_t longest = 0;
+    for (int64_t k = 0; k < nsets; ++k)
+        longest = std::max(longest, plan.run_begin[(size_t)k + 1] - plan.run_begin[(size_t)k]);
+    p->nblocks = rt_partition_stage1_blocks(longest);
+    // one entry per granule the grid covers (the lane layout rounds its blocks up to an even
+    // number: a block past the plan reads set 0's table and writes nothing)
+    const int64_t block = s->layout == RT_LAYOUT_LANE ? 64 : 16;
+    std::vector<int32_t> gset(plan.granule_set);
+    gset.resize((size_t)std::max<int64_t>((int64_t)gset.size(), (s->nblocks * block + G - 1) / G), 0);
+    const size_t tot = (size_t)rt_partition_totals_doubles(nsets, p->nblocks) * 8;
+    hipError_t e = hipMalloc((void **)&p->d_order, (size_t)plan.padded * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&p->d_slot_of_site, (size_t)nsites * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&p->d_is_pad, (size_t)plan.padded);
+    if (e == hipSuccess) e = hipMalloc((void **)&p->d_granule_set, gset.size() * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&p->d_run_begin, (size_t)(nsets + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&p->d_loglik, (size_t)nsites * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&p->d_status, (size_t)nsites * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&p->d_totals, tot);
+    if (e == hipSuccess) e = hipMemset(p->d_totals, 0, tot);
+    if (e == hipSuccess) e = hipMemcpy(p->d_order, plan.order.data(), (size_t)plan.padded * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->d_slot_of_site, plan.slot_of_site.data(), (size_t)nsites * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->d_is_pad, plan.is_pad.data(), (size_t)plan.padded, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->d_granule_set, gset.data(), gset.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->d_run_begin, plan.run_begin.data(), (size_t)(nsets + 1) * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        rt_set_error("rt_sites_create_partitioned: %s", hipGetErrorString(e));
+        rt_sites_destroy(s);
+        return e == hipErrorOutOfMemory ? RT_ERR_NOMEM : RT_ERR_HIP;
+    }
+    p->device_bytes = (int64_t)((size_t)plan.padded * 9 + (size_t)nsites * 20 + gset.size() * 4 +
+                                (size_t)(nsets + 1) * 8 + tot);
+    *out = s;
+    return RT_OK;
+}
+
+extern "C" int rt_step_partitioned(rt_model *m, rt_sites *s, int recompute_transitions)
+{
+    RT_REQUIRE(m && s, "null pointer");
+    RT_REQUIRE(s->model == m, "the site batch belongs to another model");
+    RT_REQUIRE(s->part, "rt_step_partitioned: an ordinary batch (rt_sites_create_partitioned makes "
+               "the batches this call takes)");
+    rt_partition *p = s->part;
+    rt_rate_sets &r = m->multi;
+    RT_REQUIRE(r.K >= p->nsets, "rt_step_partitioned: the batch uses %lld rate sets, the model holds "
+               "%lld (rt_model_set_rate_sets)", (long long)p->nsets, (long long)r.K);
+    rt_ctx *ctx = m->ctx;
+    RT_HIP(hipSetDevice(ctx->device));
+    // nothing of this call is deferred, and what was is reduced now
+    RT_TRY(rt_flush_reduce(ctx));
+    if (recompute_transitions) RT_TRY(rate_sets_run_expm(m));
+    else RT_TRY(rate_sets_pack_pcol(m, false));      // (a leaf-state batch created since)
+    p->stepped = false;
+    // ONE pruning launch: set 0's tables, every granule its own set's further on
+    rt_prune_view v;
+    v.P = r.d_P;
+    v.Pfrag = r.d_Pfrag;
+    v.Pquad = r.d_Pquad;
+    v.Pcol = r.d_Pcol;
+    v.loglik = s->d_loglik;
+    v.status = s->d_status;
+    v.partial = s->d_partial;
+    v.granule_set = p->d_granule_set;
+    v.frag_stride = r.frag_stride;
+    v.pcol_stride = r.pcol_stride;
+    RT_TRY(rt_launch_prune(m, s, false, false, &v));
+    RT_TRY(rt_partition_reduce_launch(ctx, p, s->d_loglik, s->d_status, s->d_weights, s->d_totals));
+    p->stepped = true;
+    p->epoch = r.epoch;
+    p->model_K = r.K;
+    return RT_OK;
+}
+
+extern "C" int rt_sites_get_partition_totals(rt_sites *s, double *totals, double *weighted_sums)
+{
+    RT_REQUIRE(s && totals, "null pointer");
+    RT_REQUIRE(s->part, "rt_sites_get_partition_totals: an ordinary batch");
+    RT_TRY(partition_ready(s, "rt_sites_get_partition_totals"));
+    const rt_partition *p = s->part;
+    RT_HIP(hipSetDevice(s->model->ctx->device));
+    RT_HIP(hipStreamSynchronize(s->model->ctx->stream));
+    // totals [nsets][3] and the weighted sums [nsets] are neighbours: one copy
+    std::vector<double> h((size_t)p->nsets * 4);
+    RT_HIP(hipMemcpy(h.data(), p->d_totals, h.size() * 8, hipMemcpyDeviceToHost));
+    memcpy(totals, h.data(), (size_t)p->nsets * 3 * 8);
+    if (weighted_sums) memcpy(weighted_sums, h.data() + 3 * p->nsets, (size_t)p->nsets * 8);
+    return RT_OK;
+}
+
+extern "C" int rt_sites_partition_info(const rt_sites *s, int64_t *nsets, int64_t *granule,
+                                       int64_t *padded)
+{
+    RT_REQUIRE(s, "null pointer");
+    const rt_partition *p = s->part;
+    if (nsets) *nsets = p ? p->nsets : 0;
+    if (granule) *granule = p ? p->G : 0;
+    if (padded) *padded = p ? p->padded : 0;
+    return RT_OK;
 }
 
 // Debug / test hook: copy the post-order schedule out (rt_op as int32[4]).

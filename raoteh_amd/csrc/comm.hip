@@ -129,6 +129,13 @@ extern "C" int rt_comm_destroy(rt_ctx *ctx)
 extern "C" int rt_allreduce_totals_group(rt_ctx *ctx, rt_sites **sites, int64_t count)
 {
     RT_REQUIRE(ctx && sites && count >= 1, "bad arguments");
+    for (int64_t k = 0; k < count; ++k) {
+        if (sites[k] && sites[k]->part) {
+            rt_set_error("rt_allreduce_totals: batch %lld is a partitioned batch (evaluated by "
+                         "rt_step_partitioned only; not sharded)", (long long)k);
+            return RT_ERR_UNSUPPORTED;
+        }
+    }
     RT_REQUIRE(ctx->comm, "rt_comm_init has not been called");
     for (int64_t k = 0; k < count; ++k) {
         RT_REQUIRE(sites[k] && sites[k]->model->ctx == ctx, "batch %lld: wrong context",

@@ -248,6 +248,28 @@ struct rt_model {
 //                  f64 in v_mfma_f64_16x16x4 B-operand order
 enum { RT_LAYOUT_LANE = 0, RT_LAYOUT_MFMA = 1 };
 
+// rt_sites_create_partitioned: site i under rate set site_set[i].  The batch is resident in the
+// planner's order (partition_plan.h): s->nsites counts its SLOTS (pads included), every granule of
+// G slots belongs to one set, and the pruning launch looks the set up per granule.  The caller's
+// order exists in the gathered copies and in the per-set reductions only.
+struct rt_partition {
+    int64_t nsites = 0;             // the caller's sites
+    int64_t nsets = 0, G = 0, padded = 0;
+    int64_t *d_order = nullptr;         // [padded] source site of every slot
+    int64_t *d_slot_of_site = nullptr;  // [nsites]
+    uint8_t *d_is_pad = nullptr;        // [padded]
+    int32_t *d_granule_set = nullptr;   // [granules the kernel's grid covers]
+    int64_t *d_run_begin = nullptr;     // [nsets + 1]
+    double *d_loglik = nullptr;         // [nsites] caller order (gathered after every step)
+    int32_t *d_status = nullptr;
+    int nblocks = 1;                    // stage-1 workgroups per set (from the plan alone)
+    double *d_totals = nullptr;         // [nsets][3], [nsets] weighted sums, [nsets][nblocks][4]
+    bool stepped = false;               // an rt_step_partitioned has written the results
+    uint64_t epoch = 0;                 // the model's rate-set epoch and K at that step
+    int64_t model_K = 0;
+    int64_t device_bytes = 0;           // of the arrays above (rt_sites_device_bytes adds them)
+};
+
 struct rt_sites {
     rt_model *model = nullptr;
     int64_t nsites = 0;
@@ -377,6 +399,7 @@ struct rt_sites {
     int *d_mhalf_count = nullptr;   // [K][multi_count_stride] arrival counters per set
     int64_t multi_half_stride = 0, multi_count_stride = 0, multi_half_capacity = 0;
     double jit_compile_s = 0.0;     // hiprtc time spent for this batch (0: cache hit / none)
+    rt_partition *part = nullptr;   // a partitioned batch (rt_sites_create_partitioned), owned
 };
 
 // ---- internal entry points ---------------------------------------------------------
@@ -443,7 +466,22 @@ struct rt_prune_view {
     double *loglik = nullptr;
     int32_t *status = nullptr;
     double *partial = nullptr;
+    // a partitioned batch (rt_step_partitioned): the tables above are set 0's, granule g of the
+    // batch reads those of set granule_set[g], the per-set strides (doubles) further on
+    const int32_t *granule_set = nullptr;
+    int64_t frag_stride = 0, pcol_stride = 0;
 };
+// prune.hip: sites per granule of the lane family's VGPR-ring kernel on this model's tree (the
+// workgroup's span: 256 with the transition table staged in LDS, else 64)
+int64_t rt_lane_reg_granule(const rt_model *m);
+// partition.hip: what follows the pruning launch of a partitioned batch, asynchronous on the
+// context's stream -- per set a fixed-order two-stage sum over the slot-ordered results (pads
+// masked), the batch totals, and the results gathered into caller order
+int rt_partition_stage1_blocks(int64_t longest_run);
+int64_t rt_partition_totals_doubles(int64_t nsets, int nblocks);
+int rt_partition_reduce_launch(rt_ctx *ctx, const rt_partition *part, const double *d_loglik,
+                               const int32_t *d_status, const double *d_weights,
+                               double *d_batch_totals);
 // multi.hip: K fixed-order reductions (the arithmetic of rt_flush_reduce's kernel per set) and
 // the weighted sums, asynchronous on the context's stream; the per-site mixture over the sets
 int64_t rt_multi_totals_doubles(int64_t K, int64_t nsites);   // doubles behind d_totals

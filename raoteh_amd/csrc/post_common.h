@@ -86,6 +86,10 @@ inline void post_lane_table(const rt_model *m, const rt_sites *s, const int *w_o
 inline int post_open(post_pass *p, const char *who, rt_model *m, rt_sites *s)
 {
     RT_REQUIRE(m && s, "null pointer");
+    if (s->part) {
+        rt_set_error("%s: a partitioned batch is evaluated by rt_step_partitioned only", who);
+        return RT_ERR_UNSUPPORTED;
+    }
     RT_REQUIRE(s->model == m, "the site batch belongs to another model");
     p->who = who; p->m = m; p->s = s; p->ctx = m->ctx; p->st = m->ctx->stream;
     p->n = m->n; p->N = m->nnodes; p->nsites = s->nsites; p->nops = (int)s->ops.size();

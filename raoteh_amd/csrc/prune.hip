@@ -399,6 +399,12 @@ struct LaneCtx {
 // cache cannot hold P for a 64-leaf tree (16 KB + schedule), and an L2 round
 // trip per step is what the wave then waits for.  PLDS = false: one wave per
 // workgroup, P through the scalar cache (trees whose P table does not fit LDS).
+//
+// prune_lane_part_kernel (a partitioned batch, rt_step_partitioned): the workgroup's span of
+// sites -- 256 with PLDS, 64 without -- is one granule of the batch, and its table is the one of
+// the granule's rate set: gset[workgroup] * gstride doubles further on, added once (a scalar
+// load and a scalar add) before the table is staged or the first record is fetched.  The body is
+// one text for both kernels (RT_PART), so that the plain kernel compiles exactly as it did.
 template <int N, int R, bool PLDS, bool RESC = false>
 __global__ void __launch_bounds__(PLDS ? 256 : 64)
 prune_lane_kernel(const double *__restrict__ Pord,   // [nops][N][N]
@@ -407,85 +413,20 @@ prune_lane_kernel(const double *__restrict__ Pord,   // [nops][N][N]
                   const double *__restrict__ root_w, int depth_arg,
                   double *__restrict__ loglik, int *__restrict__ status,
                   double *__restrict__ partial, long nsites, long nblocks)
-{
-    constexpr int NP = (N + 1) & ~1;
-    constexpr int HP = NP / 2;                // 16-byte pairs per site
-    // timing experiment only (RAOTEH_LANE_NOLOAD): skip the HBM stream
-    const bool noload = depth_arg < 0;
-    const int depth = noload ? -depth_arg : depth_arg;
-    constexpr int WPB = PLDS ? 4 : 1;         // waves per workgroup
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+#define RT_PART 0
+#include "prune_lane_body.inc"
+#undef RT_PART
 
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long gw = (long)blockIdx.x * WPB + wave;    // site block of this wave
-
-    LaneCtx<N, PLDS, 1, RESC> C;
-    unsigned char *stack_base = smem;
-    if (PLDS) {
-        double *pl = (double *)smem;
-        for (int e = threadIdx.x; e < (nops + 1) * N * N; e += 256) pl[e] = Pord[e];
-        stack_base = smem + (((size_t)(nops + 1) * N * N * 8 + 15) & ~(size_t)15);
-        __syncthreads();
-        if (gw >= nblocks) return;            // wave-uniform, after the only barrier
-        C.P_l = pl;
-    } else {
-        C.P_l = nullptr;
-    }
-    const double2 *g = (const double2 *)obs + (size_t)gw * K * HP * 64 + lane;
-    C.ops_c = (const RT_CONST_AS int4_t *)ops;
-    C.P_c = (const RT_CONST_AS double *)Pord;
-    C.w_c = (const RT_CONST_AS double *)root_w;
-    C.stack[0] = stack_base + (size_t)wave * depth * N * 512 + lane * 8;
-    C.nops = nops;
-    C.nrec = nops;
-    C.init();
-
-    // prologue: R slots in flight
-    double2 ring[R][HP];
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-#pragma unroll
-        for (int h = 0; h < HP; ++h) ring[j][h] = make_double2(1.0, 1.0);
-        if (j < K && !noload) {
-#pragma unroll
-            for (int h = 0; h < HP; ++h) ring[j][h] = g[((size_t)j * HP + h) * 64];
-        }
-    }
-
-    C.load_current();
-    C.run_plain();
-    for (int k0 = 0; k0 < K; k0 += R) {
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-            const int k = k0 + j;
-            if (k < K) {              // wave-uniform; the current step consumes slot k
-                double o[1][N];
-#pragma unroll
-                for (int q = 0; q < N; ++q)
-                    o[0][q] = (q & 1) ? ring[j][q >> 1].y : ring[j][q >> 1].x;
-                C.template step<true>(o);
-                if (k + R < K && !noload) {
-#pragma unroll
-                    for (int h = 0; h < HP; ++h)
-                        ring[j][h] = g[((size_t)(k + R) * HP + h) * 64];
-                }
-                C.run_plain();
-            }
-        }
-    }
-
-    const long site = gw * 64 + lane;
-    double sum, nzero;
-    finish_site(C.lik[0], C.negative[0], site < nsites, loglik, status, site, sum, nzero,
-                C.escale[0]);
-    sum = wave_sum(sum);
-    nzero = wave_sum(nzero);
-    if (lane == 0) {
-        partial[gw * 2] = sum;
-        partial[gw * 2 + 1] = nzero;
-    }
-}
+template <int N, int R, bool PLDS, bool RESC = false>
+__global__ void __launch_bounds__(PLDS ? 256 : 64)
+prune_lane_part_kernel(const double *__restrict__ Pord, const int4_t *__restrict__ ops, int nops,
+                       const double *__restrict__ obs, int K, const double *__restrict__ root_w,
+                       int depth_arg, double *__restrict__ loglik, int *__restrict__ status,
+                       double *__restrict__ partial, long nsites, long nblocks,
+                       const int *__restrict__ gset, long gstride)
+#define RT_PART 1
+#include "prune_lane_body.inc"
+#undef RT_PART
 
 // ---------------------------------------------------------------------------
 // n <= 4, variant B: the same walk (LaneCtx) with the leaf vectors landing in an
@@ -659,6 +600,12 @@ struct rt_interp_halves {
 // waves; 4 < NT <= 8, i.e. 64 < n <= 128 states: one tile of NT waves)
 __host__ __device__ constexpr int rt_split_waves(int NT) { return NT == 3 ? 3 : (NT < 4 ? 4 : NT); }
 
+//
+// prune_mfma_part_kernel (a partitioned batch): every 16-site tile is one granule, and its
+// tables are those of the tile's rate set, gset[tile] * (gs_frag, gs_pcol) doubles further on.  The tiles of a workgroup
+// may belong to different sets: each wave looks up ITS tile's set (wave-uniform: a scalar load
+// and scalar adds, once, before the first fragment load); the exchange buffer and the root's
+// reduction buffer are per tile, and the workgroup barriers only keep the tiles in step.
 template <int NT, int KS, bool STORE, bool SPARSE = false>
 __global__ void __launch_bounds__(rt_split_waves(NT) * 64)
 prune_mfma_kernel(const double *__restrict__ Pfrag,  // [nops][NT][KP][64][2]
@@ -670,287 +617,24 @@ prune_mfma_kernel(const double *__restrict__ Pfrag,  // [nops][NT][KP][64][2]
                   double *__restrict__ Lout, double *__restrict__ Mout, rt_interp_halves hv,
                   int rescale, const unsigned *__restrict__ leafw, const double *__restrict__ Pcol,
                   int sparse_mode)
-{
-    // (a compile-time switch: as a run-time one the leaf path cost the dense instance 35 %)
-    const int sparse = SPARSE ? sparse_mode : 0;
-    // sparse (1: one observed state per leaf, 2: allowed sets of one or two; batches whose
-    // `sparse_ok` holds): a leaf step is a gathered column of P (or two, added) from the model's
-    // leaf-column table instead of an x exchange and KS MFMAs -- what the tree-specialised
-    // kernels do (jit.hip), for the trees that have none: more than 600 steps, or not compiled yet.
-    // Lout / Mout (optional): own rows of L_v and of the message M_v = P_v L_v of every step,
-    // [step][tile][m][r][lane] -- what the downward pass and the site sums of the expectation
-    // path read back (csrc/expect_mfma.hip)
-    constexpr int WAVES = rt_split_waves(NT);
-    constexpr int TILES = WAVES / NT;
-    constexpr int KP = (KS + 1) / 2;           // k-step pairs
-    constexpr int XB = NT * 4 * 64;            // doubles of one x exchange buffer
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+#define RT_PART 0
+#include "prune_mfma_body.inc"
+#undef RT_PART
 
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int tile = wave / NT;
-    const int m = wave - tile * NT;
-    const bool halves = !STORE && hv.halfbuf != nullptr;
-    const int half = halves ? (int)(blockIdx.x & 1) : 0;
-    const long bidx = halves ? (long)(blockIdx.x >> 1) : (long)blockIdx.x;
-    const long gt = bidx * TILES + tile;                   // global site tile
-    const bool live = gt < nblocks16;
-    const long blk = live ? gt : nblocks16 - 1;           // keep barriers uniform
-    if (halves) {
-        nops = half ? hv.nops1 : hv.nops0;
-        if (half) prog = hv.prog1;
-    }
-    const int rec0 = half ? hv.rec1 : 0;                   // P record of this program's step 0
-    const int kobs0 = half ? hv.kobs1 : 0;                 // stream position of its first leaf
-
-    double *xb = (double *)smem + tile * XB;               // [TILES][XB], single buffer
-    double *red = (double *)smem + TILES * XB;             // [TILES][NT][16]
-    // this wave's rows of the spilled accumulators: [slot][4][64], + lane
-    unsigned char *stack = (unsigned char *)(red + TILES * NT * 16) +
-                           (size_t)wave * lds_slots * 2048 + lane * 8;
-
-    const RT_CONST_AS int4_t *prog_c = (const RT_CONST_AS int4_t *)prog;
-    // A fragments of this wave: [op][m][q][lane][2]
-    constexpr size_t ASTRIDE = (size_t)NT * KP * 128;
-    const double *ag = Pfrag + (size_t)rec0 * ASTRIDE + ((size_t)m * KP * 64 + lane) * 2;
-    // observation pairs holding this wave's own rows 4m..4m+3: q = 2m, 2m+1
-    const double *og = obs + (size_t)blk * K * (KP * 128) + lane * 2;
-
-    double an[2 * KP];            // A fragments of the NEXT step
-    double on[4];                 // own rows of the next observation in the stream
-#pragma unroll
-    for (int j = 0; j < 4; ++j) on[j] = 1.0;
-
-    int4_t op = prog_c[0];
-    int knext = kobs0;            // stream position `on` holds / will hold
-#pragma unroll
-    for (int q = 0; q < KP; ++q) {
-        const double2 v = *(const double2 *)(ag + q * 128);
-        an[2 * q] = v.x;
-        an[2 * q + 1] = v.y;
-    }
-    if (!SPARSE && knext < K) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int q = 2 * m + h;
-            double2 v = {0.0, 0.0};
-            if (q < KP) v = *(const double2 *)(og + ((size_t)knext * KP + q) * 128);
-            on[2 * h] = v.x;
-            on[2 * h + 1] = v.y;
-        }
-    }
-
-    double lik = 0.0;
-    bool negative = false;
-    double cur[4] = {1.0, 1.0, 1.0, 1.0};      // register-cached top accumulator
-    int escale = 0;               // rescaling: exponent tally of this lane's site (lane & 15)
-
-    // ---- sparse leaves: the state words (two in flight) and the gathered column of the NEXT
-    // leaf step, requested when the step before it starts its products
-    const int per_word = sparse == 2 ? 2 : 4;
-    const int KW = (K + per_word - 1) / per_word;
-    const unsigned *lwp = SPARSE ? leafw + (size_t)blk * KW * 16 + (lane & 15) : nullptr;
-    const double4_t *pcm = (const double4_t *)Pcol + (4 * m + (lane >> 4));
-    int lwidx = SPARSE ? kobs0 / per_word : 0;
-    unsigned lwcur = 0, lwnext = 0;
-    if constexpr (SPARSE) {
-        lwcur = lwp[(size_t)lwidx * 16];
-        lwnext = lwp[(size_t)(lwidx + 1 < KW ? lwidx + 1 : lwidx) * 16];
-    }
-    double4_t pcn = {0.0, 0.0, 0.0, 0.0}, pcq = {0.0, 0.0, 0.0, 0.0};
-    bool pair_on = false;
-    // the column(s) of the leaf whose step is program index `step`, stream position kpos
-    auto gather = [&](int step, int kpos) {
-        const int wq = kpos / per_word;
-        if (wq != lwidx) {                       // (uniform) the next word becomes the current one
-            lwcur = lwnext;
-            lwidx = wq;
-            lwnext = lwp[(size_t)(wq + 1 < KW ? wq + 1 : wq) * 16];
-        }
-        const int sh = sparse == 2 ? 16 * (kpos & 1) : 8 * (kpos & 3);
-        const int sa = (int)((lwcur >> sh) & 255u);
-        pcn = pcm[((size_t)(rec0 + step) * n + sa) * (4 * NT)];
-        if (sparse == 2) {
-            const int sb = (int)((lwcur >> (sh + 8)) & 255u);
-            pair_on = sb != 255;
-            pcq = pcm[((size_t)(rec0 + step) * n + (sb != 255 ? sb : sa)) * (4 * NT)];
-        }
-    };
-    auto is_sleaf = [&](int f) { return SPARSE && !(f & LOP_INTERNAL) && (f & LOP_OBS); };
-    if constexpr (SPARSE) {
-        if (is_sleaf(op.x)) gather(0, kobs0);
-    }
-
-    for (int i = 0; i < nops; ++i) {
-        const int flags = op.x;
-        const bool sleaf = SPARSE && is_sleaf(flags);      // (uniform)
-        // own rows of L_v = (accumulator of v) * (observation at v)
-        double x[4];
-        if (flags & LOP_INTERNAL) {
-            if (flags & LOP_X_CUR) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) x[r] = cur[r];
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) x[r] = *(const double *)(stack + op.y + r * 512);
-            }
-            if (flags & LOP_OBS) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) x[r] *= on[r];
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) x[r] = (flags & LOP_OBS) ? on[r] : 1.0;
-        }
-        if (flags & LOP_OBS) knext += 1;
-        // (L of an observed leaf is its observation vector, which is resident already: the site
-        // sums read it from there, expect_mfma.hip -- a quarter of this pass's stores)
-        if (STORE && live && ((flags & LOP_INTERNAL) || !(flags & LOP_OBS))) {
-            double *lo = Lout + ((size_t)i * nblocks16 + gt) * (NT * 256) + (m * 4) * 64 + lane;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) lo[r * 64] = x[r];
-        }
-        if (flags & LOP_ROOT) {
-            if (halves) {
-                // this program's share of the root's accumulator (the root's own observation
-                // is the combine kernel's: the half programs' root step carries none)
-                if (live) {
-                    double *hb = hv.halfbuf + ((size_t)gt * 2 + half) * (NT * 256) + (m * 4) * 64 + lane;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) hb[r * 64] = x[r];
-                }
-                return;
-            }
-            double s = 0.0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 16 * m + 4 * r + (lane >> 4);
-                const double w = row < n ? root_w[row] : 0.0;
-                negative |= (row < n) && (x[r] < 0.0);
-                s += w * fmax(x[r], 0.0);
-            }
-            s += __shfl_xor(s, 16, 64);
-            s += __shfl_xor(s, 32, 64);
-            if (lane < 16) red[(tile * NT + m) * 16 + lane] = s;
-            __syncthreads();
-            if (m == 0 && lane < 16) {
-                double tot = 0.0;
-#pragma unroll
-                for (int mm = 0; mm < NT; ++mm) tot += red[(tile * NT + mm) * 16 + lane];
-                lik = tot;
-            }
-            break;
-        }
-        double a[2 * KP];
-        double4_t acc = {0.0, 0.0, 0.0, 0.0};
-        if (SPARSE && sleaf) {
-            // the message of this leaf: its column(s), requested one step ago (one rounding for
-            // two columns, as the chain of the matrix pipe adds two non-zero terms)
-            acc = pcn;
-            if (sparse == 2 && pair_on) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[r] = pcn[r] + pcq[r];
-            }
-        } else {
-            __syncthreads();      // every wave is done reading the previous step's x
-#pragma unroll
-            for (int r = 0; r < 4; ++r) xb[((4 * m + r) * 64) + lane] = x[r];
-#pragma unroll
-            for (int j = 0; j < 2 * KP; ++j) a[j] = an[j];
-            __syncthreads();      // x of every wave of the tile is in LDS
-        }
-
-        // start everything the next step needs
-        const int inext = (i + 1 < nops) ? i + 1 : i;
-        const int4_t opn = prog_c[inext];
-        if (SPARSE && is_sleaf(opn.x)) {
-            if constexpr (SPARSE) {
-                if (inext != i) gather(inext, knext);
-            }
-        } else if (!(opn.x & LOP_ROOT)) {
-#pragma unroll
-            for (int q = 0; q < KP; ++q) {
-                const double2 v = *(const double2 *)(ag + (size_t)inext * ASTRIDE + q * 128);
-                an[2 * q] = v.x;
-                an[2 * q + 1] = v.y;
-            }
-        }
-        if (!SPARSE && (flags & LOP_OBS) && knext < K) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int q = 2 * m + h;
-                double2 v = {0.0, 0.0};
-                if (q < KP) v = *(const double2 *)(og + ((size_t)knext * KP + q) * 128);
-                on[2 * h] = v.x;
-                on[2 * h + 1] = v.y;
-            }
-        }
-
-        if (!sleaf) {
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk) {
-                const double b = xb[kk * 64 + lane];
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], b, acc, 0, 0, 0);
-            }
-        }
-        if (rescale && !sleaf) {
-            // every wave of the tile sees all of x as its B operands: the site's largest
-            // entry, the same number in every lane of the site and in every wave
-            double xmax = 0.0;
-#pragma unroll
-            for (int kk = 0; kk < KS; ++kk) xmax = fmax(xmax, xb[kk * 64 + lane]);
-            xmax = fmax(xmax, __shfl_xor(xmax, 16, 64));
-            xmax = fmax(xmax, __shfl_xor(xmax, 32, 64));
-            const int e = rescale_exponent(xmax);
-            if (e != 0) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[r] = ldexp(acc[r], -e);
-                escale += e;
-            }
-        }
-        if (STORE && live) {
-            double *mo = Mout + ((size_t)i * nblocks16 + gt) * (NT * 256) + (m * 4) * 64 + lane;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) mo[r * 64] = acc[r];
-        }
-
-        if (flags & LOP_FIRST) {
-            if (flags & LOP_SPILL) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) *(double *)(stack + op.w + r * 512) = cur[r];
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) cur[r] = acc[r];
-        } else if (flags & LOP_DST_CUR) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) cur[r] *= acc[r];
-        } else if (flags & LOP_FAST) {     // un-spill: the parent's step is next
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                cur[r] = *(const double *)(stack + op.z + r * 512) * acc[r];
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                double *d = (double *)(stack + op.z + r * 512);
-                *d = *d * acc[r];
-            }
-        }
-        op = opn;
-    }
-
-    // lanes 0..15 of wave m == 0 own the 16 sites of the tile
-    const long site = blk * 16 + (lane & 15);
-    const bool valid = live && m == 0 && lane < 16 && site < nsites;
-    double sum, nzero;
-    finish_site(lik, negative, valid, loglik, status, site, sum, nzero, escale);
-    sum = wave_sum(sum);
-    nzero = wave_sum(nzero);
-    if (lane == 0) {
-        const long gwv = (long)blockIdx.x * WAVES + wave;
-        partial[gwv * 2] = sum;
-        partial[gwv * 2 + 1] = nzero;
-    }
-}
+// (instantiated with STORE = false only: the expectation path has no partitioned form)
+template <int NT, int KS, bool STORE, bool SPARSE>
+__global__ void __launch_bounds__(rt_split_waves(NT) * 64)
+prune_mfma_part_kernel(const double *__restrict__ Pfrag, const int4_t *__restrict__ prog, int nops,
+                       const double *__restrict__ obs, int K, const double *__restrict__ root_w,
+                       int n, int lds_slots, double *__restrict__ loglik, int *__restrict__ status,
+                       double *__restrict__ partial, long nsites, long nblocks16,
+                       double *__restrict__ Lout, double *__restrict__ Mout, rt_interp_halves hv,
+                       int rescale, const unsigned *__restrict__ leafw,
+                       const double *__restrict__ Pcol, int sparse_mode,
+                       const int *__restrict__ gset, long gs_frag, long gs_pcol)
+#define RT_PART 1
+#include "prune_mfma_body.inc"
+#undef RT_PART
 
 // Second kernel of a root-halves interpreter launch: the root's accumulator is the product of
 // the two shares (in child order: the interpreter's own product bit for bit), times the root's
@@ -1033,6 +717,10 @@ prune_mfma_combine_kernel(const double *__restrict__ halfbuf, const double *__re
 // the launch.  Stack: [slot][NT*4][lane] doubles per wave in LDS, top cached in
 // registers (same LOP_* program as the other kernels).
 
+//
+// prune_mfma_solo_part_kernel (a partitioned batch): the wave's tile is one granule; its A
+// fragments are those of the tile's rate set, gset[tile] * gs_frag doubles further on (the four
+// waves of a workgroup are independent, so four sets in one workgroup is nothing special here).
 template <int NT, int KS>
 __global__ void __launch_bounds__(256)
 prune_mfma_solo_kernel(const double *__restrict__ Pfrag,  // [nops][NT][KP][64][2]
@@ -1041,177 +729,21 @@ prune_mfma_solo_kernel(const double *__restrict__ Pfrag,  // [nops][NT][KP][64][
                        const double *__restrict__ root_w, int n, int lds_slots,
                        double *__restrict__ loglik, int *__restrict__ status,
                        double *__restrict__ partial, long nsites, long nblocks16, int rescale)
-{
-    constexpr int MW = NT * 4;                 // message doubles per lane
-    constexpr int KP = (KS + 1) / 2;           // k-step pairs
-    constexpr int NA = NT * 2 * KP;            // A-fragment doubles per lane and step
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+#define RT_PART 0
+#include "prune_mfma_solo_body.inc"
+#undef RT_PART
 
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long gw = (long)blockIdx.x * 4 + wave;           // site tile of this wave
-    if (gw >= nblocks16) {                                  // wave-uniform; no barriers
-        if (lane == 0) { partial[gw * 2] = 0.0; partial[gw * 2 + 1] = 0.0; }
-        return;
-    }
-    unsigned char *stack = smem + (size_t)wave * lds_slots * (MW * 512) + lane * 8;
-    const RT_CONST_AS int4_t *prog_c = (const RT_CONST_AS int4_t *)prog;
-    const double *ag = Pfrag + lane * 2;                    // [op][m][q][lane][2]
-    constexpr size_t ASTRIDE = (size_t)NT * KP * 128;
-    const double *og = obs + (size_t)gw * K * (KP * 128) + lane * 2;
-
-    double an[NA];                // A fragments of the NEXT step
-    double on[2 * KP];            // next observation of the stream (B-operand order)
-#pragma unroll
-    for (int j = 0; j < 2 * KP; ++j) on[j] = 1.0;
-    int4_t op = prog_c[0];
-    int knext = 0;
-#pragma unroll
-    for (int q = 0; q < NT * KP; ++q) {
-        const double2 v = *(const double2 *)(ag + q * 128);
-        an[2 * q] = v.x;
-        an[2 * q + 1] = v.y;
-    }
-    if (K > 0) {
-#pragma unroll
-        for (int q = 0; q < KP; ++q) {
-            const double2 v = *(const double2 *)(og + (size_t)q * 128);
-            on[2 * q] = v.x;
-            on[2 * q + 1] = v.y;
-        }
-    }
-
-    double lik = 0.0;
-    bool negative = false;
-    int escale = 0;               // rescaling: exponent tally of this lane's site
-    double cur[MW];
-#pragma unroll
-    for (int j = 0; j < MW; ++j) cur[j] = 1.0;
-
-    for (int i = 0; i < nops; ++i) {
-        const int flags = op.x;
-        double x[MW];
-        if (flags & LOP_INTERNAL) {
-            if (flags & LOP_X_CUR) {
-#pragma unroll
-                for (int j = 0; j < MW; ++j) x[j] = cur[j];
-            } else {
-#pragma unroll
-                for (int j = 0; j < MW; ++j) x[j] = *(const double *)(stack + op.y + j * 512);
-            }
-            if (flags & LOP_OBS) {
-#pragma unroll
-                for (int j = 0; j < KS; ++j) x[j] *= on[j];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < MW; ++j)
-                x[j] = (flags & LOP_OBS) ? (j < 2 * KP ? on[j] : 0.0) : 1.0;
-        }
-        if (flags & LOP_OBS) knext += 1;
-        if (flags & LOP_ROOT) {
-            double sacc = 0.0;
-#pragma unroll
-            for (int j = 0; j < KS; ++j) {
-                const int row = 4 * j + (lane >> 4);
-                const double w = row < n ? root_w[row] : 0.0;
-                negative |= (row < n) && (x[j] < 0.0);
-                sacc += w * fmax(x[j], 0.0);
-            }
-            sacc += __shfl_xor(sacc, 16, 64);
-            sacc += __shfl_xor(sacc, 32, 64);
-            lik = sacc;
-            break;
-        }
-        double a[NA];
-#pragma unroll
-        for (int j = 0; j < NA; ++j) a[j] = an[j];
-
-        // start everything the next step needs
-        const int inext = (i + 1 < nops) ? i + 1 : i;
-        const int4_t opn = prog_c[inext];
-        if (!(opn.x & LOP_ROOT)) {
-#pragma unroll
-            for (int q = 0; q < NT * KP; ++q) {
-                const double2 v = *(const double2 *)(ag + (size_t)inext * ASTRIDE + q * 128);
-                an[2 * q] = v.x;
-                an[2 * q + 1] = v.y;
-            }
-        }
-        if ((flags & LOP_OBS) && knext < K) {
-#pragma unroll
-            for (int q = 0; q < KP; ++q) {
-                const double2 v = *(const double2 *)(og + ((size_t)knext * KP + q) * 128);
-                on[2 * q] = v.x;
-                on[2 * q + 1] = v.y;
-            }
-        }
-
-        double4_t acc[NT];
-#pragma unroll
-        for (int m = 0; m < NT; ++m) acc[m] = (double4_t){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int kk = 0; kk < KS; ++kk) {
-#pragma unroll
-            for (int m = 0; m < NT; ++m)
-                acc[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m * 2 * KP + kk], x[kk],
-                                                              acc[m], 0, 0, 0);
-        }
-        double t[MW];
-#pragma unroll
-        for (int m = 0; m < NT; ++m)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) t[m * 4 + r] = acc[m][r];
-        if (rescale) {
-            double xmax = 0.0;
-#pragma unroll
-            for (int j = 0; j < KS; ++j) xmax = fmax(xmax, x[j]);
-            xmax = fmax(xmax, __shfl_xor(xmax, 16, 64));
-            xmax = fmax(xmax, __shfl_xor(xmax, 32, 64));
-            const int e = rescale_exponent(xmax);
-            if (e != 0) {
-#pragma unroll
-                for (int j = 0; j < MW; ++j) t[j] = ldexp(t[j], -e);
-                escale += e;
-            }
-        }
-
-        if (flags & LOP_FIRST) {
-            if (flags & LOP_SPILL) {
-#pragma unroll
-                for (int j = 0; j < MW; ++j) *(double *)(stack + op.w + j * 512) = cur[j];
-            }
-#pragma unroll
-            for (int j = 0; j < MW; ++j) cur[j] = t[j];
-        } else if (flags & LOP_DST_CUR) {
-#pragma unroll
-            for (int j = 0; j < MW; ++j) cur[j] *= t[j];
-        } else if (flags & LOP_FAST) {     // un-spill: the parent's step is next
-#pragma unroll
-            for (int j = 0; j < MW; ++j)
-                cur[j] = *(const double *)(stack + op.z + j * 512) * t[j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < MW; ++j) {
-                double *d = (double *)(stack + op.z + j * 512);
-                *d = *d * t[j];
-            }
-        }
-        op = opn;
-    }
-
-    // lanes 0..15 own the 16 sites of the tile
-    const long site = gw * 16 + (lane & 15);
-    const bool valid = lane < 16 && site < nsites;
-    double sum, nzero;
-    finish_site(lik, negative, valid, loglik, status, site, sum, nzero, escale);
-    sum = wave_sum(sum);
-    nzero = wave_sum(nzero);
-    if (lane == 0) {
-        partial[gw * 2] = sum;
-        partial[gw * 2 + 1] = nzero;
-    }
-}
+template <int NT, int KS>
+__global__ void __launch_bounds__(256)
+prune_mfma_solo_part_kernel(const double *__restrict__ Pfrag, const int4_t *__restrict__ prog,
+                            int nops, const double *__restrict__ obs, int K,
+                            const double *__restrict__ root_w, int n, int lds_slots,
+                            double *__restrict__ loglik, int *__restrict__ status,
+                            double *__restrict__ partial, long nsites, long nblocks16, int rescale,
+                            const int *__restrict__ gset, long gs_frag)
+#define RT_PART 1
+#include "prune_mfma_solo_body.inc"
+#undef RT_PART
 
 // ---------------------------------------------------------------------------
 // generic fallback: lane per site, accumulator stack in global scratch
@@ -1712,6 +1244,18 @@ int rt_sites_pack(rt_sites *s, int kind, const int64_t *src_of_k, const void *da
     return RT_OK;
 }
 
+// P table of the VGPR-ring lane kernel in LDS when two 4-wave workgroups still fit on a CU
+static bool lane_reg_plds(const rt_model *m)
+{
+    const int n = (int)m->n;
+    const int depth = std::max(1, m->max_depth - 1);
+    const int stack = depth * n * 512;                        // per wave
+    const int ptab = (((int)m->ops.size() + 1) * n * n * 8 + 15) & ~15;
+    return ptab + 4 * stack <= 80 * 1024 && !getenv("RAOTEH_LANE_NO_PLDS");
+}
+
+int64_t rt_lane_reg_granule(const rt_model *m) { return lane_reg_plds(m) ? 256 : 64; }
+
 template <int N, int R, bool RESC = false>
 static int launch_lane_reg(rt_model *m, rt_sites *s, const rt_prune_view &v, bool *plds_out)
 {
@@ -1720,10 +1264,24 @@ static int launch_lane_reg(rt_model *m, rt_sites *s, const rt_prune_view &v, boo
     const int nops = (int)s->ops.size();
     const int stack = depth * N * 512;                        // per wave
     const int ptab = ((nops + 1) * N * N * 8 + 15) & ~15;
-    // P table in LDS when two 4-wave workgroups still fit on a CU
-    const bool plds = ptab + 4 * stack <= 80 * 1024 && !getenv("RAOTEH_LANE_NO_PLDS");
+    // (a partitioned batch was laid out for one of the two forms: its granule says which)
+    const bool plds = v.granule_set ? s->part->G == 256 : lane_reg_plds(m);
     *plds_out = plds;
     const int depth_arg = getenv("RAOTEH_LANE_NOLOAD") ? -depth : depth;
+    if constexpr (R == 8 && !RESC) {
+        if (v.granule_set) {
+            const int lds = plds ? ptab + 4 * stack : stack;
+            auto kern = plds ? prune_lane_part_kernel<N, 8, true> : prune_lane_part_kernel<N, 8, false>;
+            RT_HIP(hipFuncSetAttribute((const void *)kern,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            RT_LAUNCH_TIMED(m->ctx, kern, dim3((unsigned)(plds ? (s->nblocks + 3) / 4 : s->nblocks)),
+                            dim3(plds ? 256 : 64), lds, v.Pfrag, (const int4_t *)s->d_lane_ops, nops,
+                            s->d_obs, (int)s->nobs, m->d_root, depth, v.loglik, v.status, v.partial,
+                            (long)s->nsites, (long)s->nblocks, (const int *)v.granule_set,
+                            (long)v.frag_stride);
+            return RT_OK;
+        }
+    }
     if (plds) {
         const int lds = ptab + 4 * stack;
         auto kern = prune_lane_kernel<N, R, true, RESC>;
@@ -1812,6 +1370,9 @@ static int launch_lane(rt_model *m, rt_sites *s, const rt_prune_view &v, const c
     } else if (s->rescale) {
         R = 8;
         rc = launch_lane_reg<N, 8, true>(m, s, v, &plds);
+    } else if (v.granule_set) {
+        R = 8;
+        rc = launch_lane_reg<N, 8>(m, s, v, &plds);
     } else {
         switch (R) {
         case 4: rc = launch_lane_reg<N, 4>(m, s, v, &plds); break;
@@ -1838,6 +1399,17 @@ static int launch_mfma_inst(rt_model *m, rt_sites *s, const rt_prune_view &v)
             const int lds = 4 * lds_slots * (NT * 4 * 512);
             const unsigned grid = (unsigned)((s->nblocks + 3) / 4);
             auto kern = prune_mfma_solo_kernel<NT, KS>;
+            if (v.granule_set) {
+                auto pkern = prune_mfma_solo_part_kernel<NT, KS>;
+                RT_HIP(hipFuncSetAttribute((const void *)pkern,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+                RT_LAUNCH_TIMED(m->ctx, pkern, dim3(grid), dim3(256), lds, v.Pfrag,
+                                (const int4_t *)s->d_lane_ops, (int)s->ops.size(), s->d_obs,
+                                (int)s->nobs, m->d_root, (int)m->n, lds_slots, v.loglik, v.status,
+                                v.partial, (long)s->nsites, (long)s->nblocks, 0,
+                                (const int *)v.granule_set, (long)v.frag_stride);
+                return RT_OK;
+            }
             RT_HIP(hipFuncSetAttribute((const void *)kern,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds));
             RT_LAUNCH_TIMED(m->ctx, kern, dim3(grid), dim3(256), lds, v.Pfrag,
@@ -1866,6 +1438,16 @@ static int launch_mfma_inst(rt_model *m, rt_sites *s, const rt_prune_view &v)
     const double *ipc = isp ? v.Pcol : nullptr;
     const int ism = isp ? (s->sparse_pairs ? 2 : 1) : 0;
     rt_interp_halves hv;
+    // a partitioned batch: the same forms with the per-tile set lookup (the combine kernel of the
+    // halves form reads no transition table: it is the batch's ordinary one)
+    auto pkern = isp ? prune_mfma_part_kernel<NT, KS, false, (NT > 2)>
+                     : prune_mfma_part_kernel<NT, KS, false, false>;
+    const bool part = v.granule_set != nullptr;
+    if (part) {
+        RT_REQUIRE(!s->d_Lout && !s->rescale, "a partitioned batch runs the plain interpreter forms");
+        RT_HIP(hipFuncSetAttribute((const void *)pkern,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    }
     if (s->interp_halves && !s->d_Lout) {
         // the two root programs as even / odd workgroups, then the combine kernel
         hv.prog1 = (const int4_t *)s->d_lane_ops_b;
@@ -1874,6 +1456,14 @@ static int launch_mfma_inst(rt_model *m, rt_sites *s, const rt_prune_view &v)
         hv.rec1 = s->half_rec1;
         hv.kobs1 = s->half_kobs1;
         hv.halfbuf = s->d_half;
+        if (part)
+            RT_LAUNCH_TIMED(m->ctx, pkern, dim3(2 * grid), dim3(WAVES * 64), lds, v.Pfrag,
+                            (const int4_t *)s->d_lane_ops_a, hv.nops0, s->d_obs, (int)s->nobs,
+                            m->d_root, (int)m->n, lds_slots, v.loglik, v.status, v.partial,
+                            (long)s->nsites, (long)s->nblocks, (double *)nullptr, (double *)nullptr, hv, 0,
+                            ilw, ipc, ism,
+                            (const int *)v.granule_set, (long)v.frag_stride, (long)v.pcol_stride);
+        else
         RT_LAUNCH_TIMED(m->ctx, kern, dim3(2 * grid), dim3(WAVES * 64), lds,
                            v.Pfrag, (const int4_t *)s->d_lane_ops_a, hv.nops0,
                            s->d_obs, (int)s->nobs, m->d_root, (int)m->n, lds_slots,
@@ -1894,6 +1484,15 @@ static int launch_mfma_inst(rt_model *m, rt_sites *s, const rt_prune_view &v)
                                s->half_kroot, (const double *)m->d_root, (int)m->n, v.loglik,
                                v.status, v.partial, (long)s->nsites, (long)s->nblocks);
         rt_time_extra_end(m->ctx, RT_K_COMBINE, ca, cb);
+        return RT_OK;
+    }
+    if (part) {
+        RT_LAUNCH_TIMED(m->ctx, pkern, dim3(grid), dim3(WAVES * 64), lds, v.Pfrag,
+                        (const int4_t *)s->d_lane_ops, (int)s->ops.size(), s->d_obs, (int)s->nobs,
+                        m->d_root, (int)m->n, lds_slots, v.loglik, v.status, v.partial,
+                        (long)s->nsites, (long)s->nblocks, (double *)nullptr, (double *)nullptr, hv, 0,
+                            ilw, ipc, ism,
+                        (const int *)v.granule_set, (long)v.frag_stride, (long)v.pcol_stride);
         return RT_OK;
     }
     RT_LAUNCH_TIMED(m->ctx, kern, dim3(grid), dim3(WAVES * 64), lds,
@@ -2062,6 +1661,8 @@ int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm,
     rt_time_begin(ctx, RT_K_PRUNE, "", &ev);
     int rc;
     char *jit_name = s->kernel_name;
+    RT_REQUIRE(!v.granule_set || (!generic && !s->jit_fn && !s->lane_dma),
+               "a partitioned batch runs the interpreter kernels with the per-granule lookup only");
     if (generic) rc = launch_generic(m, s, v, &name);
     else if (s->jit_fn) {
         rc = rt_launch_prune_jit(m, s, s->jit_fused ? &fuse : nullptr, &v);
@@ -2088,6 +1689,13 @@ int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm,
     } else rc = launch_mfma(m, s, v, &name);
     if (rc != RT_OK) return rc;
     RT_HIP(hipGetLastError());
+    if (v.granule_set) {
+        // (the interpreter launchers leave the name in the batch's own buffer)
+        if (name != s->kernel_name) snprintf(s->kernel_name, sizeof(s->kernel_name), "%s", name);
+        const size_t len = strlen(s->kernel_name);
+        snprintf(s->kernel_name + len, sizeof(s->kernel_name) - len, ",partitioned");
+        name = s->kernel_name;
+    }
     if (!view) s->pruned = true;
     snprintf(ctx->slots[RT_K_PRUNE].name, sizeof(ctx->slots[RT_K_PRUNE].name), "%s", name);
     if (name != s->kernel_name) snprintf(s->kernel_name, sizeof(s->kernel_name), "%s", name);

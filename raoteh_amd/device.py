@@ -24,7 +24,7 @@ import numpy as np
 from . import _lib
 from ._tree import TreeArrays
 
-__all__ = ['check_rate_sets', 'Context', 'get_context', 'TreeModel', 'SiteBatch', 'device_count', 'Posteriors',
+__all__ = ['check_rate_sets', 'check_site_sets', 'Context', 'get_context', 'TreeModel', 'SiteBatch', 'device_count', 'Posteriors',
            'states_to_mask', 'BranchExpectations', 'check_branch_coefs', 'SampledStates', 'SampledMappings']
 
 # At interpreter shutdown objects are finalised in arbitrary order (a model
@@ -260,6 +260,27 @@ def check_rate_sets(Q, t, node_q, nstates, nnodes):
         if ((node_q[1:] < 0) | (node_q[1:] >= nq)).any():
             raise ValueError('node_q out of range')
     return np.ascontiguousarray(Q), np.ascontiguousarray(t), node_q
+
+
+def check_site_sets(site_sets, nsites, nsets=None):
+    """The site_sets argument of TreeModel.upload_sites -> (int32[nsites], nsets).  One rate-set
+    index per site, integers in [0, nsets); nsets None: one more than the largest index.
+    ValueError for another shape, non-integers, an index out of range, or nsets outside
+    1..RT_MAX_RATE_SETS."""
+    a = np.asarray(site_sets)
+    if a.shape != (nsites,):
+        raise ValueError('site_sets must have one entry per site (%d), not %s' % (nsites, a.shape))
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError('site_sets must be integers, not %s' % a.dtype)
+    if nsites < 1:
+        raise ValueError('a partitioned batch needs at least one site')
+    if nsets is None:
+        nsets = int(a.max()) + 1
+    if int(nsets) != nsets or not 1 <= nsets <= _lib.RT_MAX_RATE_SETS:
+        raise ValueError('between 1 and %d rate sets (%r here)' % (_lib.RT_MAX_RATE_SETS, nsets))
+    if (a < 0).any() or (a >= nsets).any():
+        raise ValueError('site_sets must lie in [0, %d)' % nsets)
+    return np.ascontiguousarray(a, dtype=np.int32), int(nsets)
 
 
 def check_class_weights(class_weights, nsets):
@@ -593,10 +614,14 @@ def get_context(device=0):
 
 
 class SiteBatch(object):
-    def __init__(self, model, handle, nsites):
+    def __init__(self, model, handle, nsites, site_sets=None, nsets=0):
         self.model = model
         self._h = handle
         self.nsites = nsites
+        # a partitioned batch (upload_sites(..., site_sets=...)): the rate set of every site,
+        # int32[nsites], and the number of sets; None / 0 for an ordinary batch
+        self.site_sets = site_sets
+        self.nsets = nsets
         # the C object refers to its model: when both die in one garbage-collection cycle
         # (a traceback kept them alive) the model may be finalised first, so the model closes
         # its batches before it goes
@@ -795,11 +820,14 @@ class TreeModel(object):
                                                       _ptr(w, c_double)))
         self._root_w = w.copy()
 
-    def upload_sites(self, obs_nodes, data, kind='dense'):
+    def upload_sites(self, obs_nodes, data, kind='dense', site_sets=None, nsets=None):
         """obs_nodes: tree nodes (nx ids) carrying per-site data, in the order
         of the data's second axis.  data: dense f64[nsites,nobs,n] | state
         uint8[nsites,nobs] (255 = unobserved) | mask uint64[nsites,nobs] (nstates
-        <= 64) or uint64[nsites,nobs,ceil(nstates/64)] (bit s % 64 of word s // 64)."""
+        <= 64) or uint64[nsites,nobs,ceil(nstates/64)] (bit s % 64 of word s // 64).
+        site_sets (int[nsites], with nsets or one more than its maximum): a PARTITIONED batch
+        (rt_sites_create_partitioned) -- site i is evaluated under rate set site_sets[i] of
+        set_rate_sets by step_partitioned, and by nothing else."""
         code = _KINDS[kind]
         idx = _i64([self.tree.node_to_index[v] for v in obs_nodes])
         if kind == 'dense':
@@ -817,6 +845,12 @@ class TreeModel(object):
             raise ValueError('observation array has the wrong shape')
         nsites = data.shape[0]
         h = c_void_p()
+        if site_sets is not None:
+            sets, nsets = check_site_sets(site_sets, nsites, nsets)
+            _lib.check(_lib.lib().rt_sites_create_partitioned(
+                self._h, nsites, code, len(idx), _ptr(idx, c_int64),
+                data.ctypes.data_as(c_void_p), _ptr(sets, c_int32), nsets, byref(h)))
+            return SiteBatch(self, h, nsites, sets, nsets)
         _lib.check(_lib.lib().rt_sites_create(
             self._h, nsites, code, len(idx), _ptr(idx, c_int64),
             data.ctypes.data_as(c_void_p), byref(h)))
@@ -870,6 +904,25 @@ class TreeModel(object):
         tot = np.zeros((max(K, 1), 3), dtype=np.float64)
         ws = np.zeros(max(K, 1), dtype=np.float64)
         _lib.check(_lib.lib().rt_sites_get_multi_totals(
+            batch._h, _ptr(tot, c_double), _ptr(ws, c_double) if weighted else None))
+        return (tot, ws) if weighted else tot
+
+    def step_partitioned(self, batch, recompute_transitions=True):
+        """rt_step_partitioned on a batch uploaded with site_sets: (the exponentials of every
+        rate set again +) ONE pruning launch in which every site reads the tables of its own
+        set + the per-set sums; asynchronous.  fetch_log_likelihoods / fetch_totals /
+        fetch_partition_totals read the results (caller order, real sites only)."""
+        _lib.check(_lib.lib().rt_step_partitioned(self._h, batch._h,
+                                                  1 if recompute_transitions else 0))
+
+    def fetch_partition_totals(self, batch, weighted=False):
+        """totals f64[nsets, 3] of the last step_partitioned (per set: what fetch_totals means,
+        over that set's sites; zeros for an empty set); weighted=True: (totals, weighted_sums
+        f64[nsets]) with the batch's site weights (caller order)."""
+        K = max(int(getattr(batch, 'nsets', 0) or 0), 1)
+        tot = np.zeros((K, 3), dtype=np.float64)
+        ws = np.zeros(K, dtype=np.float64)
+        _lib.check(_lib.lib().rt_sites_get_partition_totals(
             batch._h, _ptr(tot, c_double), _ptr(ws, c_double) if weighted else None))
         return (tot, ws) if weighted else tot
 
