@@ -708,6 +708,38 @@ const char *rt_sites_multi_kernel_name(const rt_sites *sites);
  *   The getters synchronise; they return RT_ERR_INVALID before the first rt_step_partitioned
  *   (rt_sites_get_totals: zeros) and after the model's number of rate sets changed, until the
  *   next rt_step_partitioned (the epoch of section 2b).
+ * rt_sites_branch_expectations_partitioned: rt_sites_branch_expectations (above) for a
+ *   partitioned batch, with one change: on the edge above node v, site i uses Q, t, P and the
+ *   derivative G of its own set k = site_set[i] of rt_model_set_rate_sets, Q[k][node_q[v]] and
+ *   t[k][v].  The per-branch map of expected changes when the columns do not share one rate set
+ *   (the per-column compound process above), and with C = Q[k] the analytic gradient in the
+ *   branch lengths of every set, t[k][v] d log L_i / d t[k][v], for a tree shared by partitions.
+ *     coefs           f64[n_coefs][n][n] shared by all sets (coefs_per_set == 0), or
+ *                     f64[nsets][n_coefs][n][n], set k's matrices at [k] (coefs_per_set != 0: the
+ *                     gradient needs diag(Q[k]) on the diagonal); 1 <= n_coefs <=
+ *                     RT_MAX_BRANCH_COEFS, every entry finite
+ *     values          f64[nsites][nnodes][n_coefs] in CALLER order, real sites only, never a
+ *                     pad; the root's slot is 0; a site of zero likelihood under its set: zeros
+ *     edge_sums       f64[nnodes][n_coefs]: the sum over all real sites, weighted by
+ *                     rt_sites_set_weights (caller order); the per-set rows added in set order
+ *     set_edge_sums   f64[nsets][nnodes][n_coefs]: the same over set k's sites; zeros for an
+ *                     empty set
+ *     status          int32[nsites] in caller order, as rt_sites_branch_expectations:
+ *                     RT_SITE_ZERO_PROB, or 2 (a zero denominator)
+ *   Each output may be NULL; only what is given crosses PCIe.  The sums are reduced on the device
+ *   per (set, node, matrix) over the set's run in two stages whose shape depends on the plan
+ *   alone, with the pad slots skipped (a pad repeats a real site: weighting it out would not do).
+ *   recompute_transitions != 0: the K (nnodes - 1) exponentials again from the resident rate
+ *   sets, as rt_step_partitioned; no earlier rt_step_partitioned is needed.  The derivatives of
+ *   all K (nnodes - 1) edges come from one launch of the derivative route per coefficient matrix;
+ *   every edge's derivative and every site's arithmetic are those of rt_sites_branch_expectations
+ *   under that site's set, bit for bit (per-set scratch grows with K; no chunking over the sets:
+ *   a call whose scratch passes 96 GB is refused).  Synchronous; two calls return the same bits.
+ *   The batch's log-likelihoods, status, totals, per-set totals and kernel name, the model's own
+ *   transitions and its rate sets keep what they had.  RT_ERR_INVALID: an ordinary batch; fewer
+ *   rate sets resident in the model than the batch's nsets; a batch of another model; n_coefs < 1
+ *   or coefs NULL; a coefficient that is not finite.  RT_ERR_UNSUPPORTED: more than
+ *   RT_MAX_BRANCH_COEFS matrices; more than 96 GB of scratch.
  * Everything else refuses a partitioned batch with RT_ERR_UNSUPPORTED and leaves it untouched:
  *   rt_prune, rt_step, rt_step_multi, rt_sites_clone, rt_expect_step, rt_sites_posteriors,
  *   rt_sites_branch_expectations, rt_sites_branch_profiles, rt_sites_sample_states,
@@ -721,6 +753,9 @@ int rt_sites_create_partitioned(rt_model *model, int64_t nsites, int kind, int64
             rt_sites **sites);
 int rt_step_partitioned(rt_model *model, rt_sites *sites, int recompute_transitions);
 int rt_sites_get_partition_totals(rt_sites *sites, double *totals, double *weighted_sums);
+int rt_sites_branch_expectations_partitioned(rt_model *model, rt_sites *sites,
+            int recompute_transitions, int64_t n_coefs, int coefs_per_set, const double *coefs,
+            double *values, double *edge_sums, double *set_edge_sums, int32_t *status);
 /* what the batch was laid out with: any pointer may be NULL; an ordinary batch gives zeros */
 int rt_sites_partition_info(const rt_sites *sites, int64_t *nsets, int64_t *granule,
             int64_t *padded);

@@ -770,6 +770,12 @@ static int rate_sets_run_expm(rt_model *m)
     return rate_sets_pack_pcol(m, true);
 }
 
+int rt_rate_sets_recompute(rt_model *m)
+{
+    RT_REQUIRE(m->multi.K > 0, "rt_model_set_rate_sets has not been called");
+    return rate_sets_run_expm(m);
+}
+
 extern "C" int rt_model_set_rate_sets(rt_model *m, int64_t K, const double *Q, int64_t nq,
                                       const int64_t *node_q, const double *t)
 {

@@ -24,6 +24,9 @@
 //
 // Nothing of the batch is written: its own pruning kernel, log-likelihoods, status and totals
 // stay as they were; two calls give the same bits.
+//
+// rt_sites_branch_expectations_partitioned (at the end): the same read of a partitioned batch,
+// every site under its own rate set -- the kernels' PART forms and the part_* kernels.
 #include "common.h"
 #include "post_common.h"
 
@@ -35,13 +38,17 @@ namespace {
 
 constexpr int BC_MAX = RT_MAX_BRANCH_COEFS;
 
-// W[e][r][c] = C_e[c][r]: C_e = E * Q_e off the diagonal, E on it (edge e is node e + 1)
+// W[e][r][c] = C_e[c][r]: C_e = E * Q_e off the diagonal, E on it (edge e is node e + 1).
+// PART (the edges of all rate sets, set after set, per_set each): E of the edge's set, e_stride
+// doubles per set further on (0: one E for all sets)
+template <bool PART>
 __global__ void __launch_bounds__(256)
 direction_kernel(int n, const double *__restrict__ Q, const int *__restrict__ qidx,
-                 const double *__restrict__ E, double *__restrict__ W)
+                 const double *__restrict__ E, double *__restrict__ W, int per_set, long e_stride)
 {
     const int e = blockIdx.x;
     const int nn = n * n;
+    if constexpr (PART) E += (long)(e / per_set) * e_stride;
     const double *Qe = Q + (size_t)qidx[e] * nn;
     for (int k = threadIdx.x; k < nn; k += 256) {
         const int r = k / n, c = k - r * n;
@@ -52,13 +59,17 @@ direction_kernel(int n, const double *__restrict__ Q, const int *__restrict__ qi
 
 // steps[i] = {node, step of the parent, stream position of an observed leaf or -1, 1 if the node
 // has children}; the root is the last step.  GfragT: [k][step] A fragments of G_k^T.
-template <int NT, int KS>
+// PART (a partitioned batch: sites are its slots, the output is in slot order): the workgroup's
+// tile is one granule; the tables of its rate set are gset[tile] * (gs_pt, gs_gt) doubles further
+// on -- wave-uniform, a scalar load and two scalar adds before the first fragment load.
+template <int NT, int KS, bool PART = false>
 __global__ void __launch_bounds__(64 * NT)
 be_down_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT, int nk, int nops,
                const int4 *__restrict__ steps, const double *__restrict__ Larr,
                const double *__restrict__ Marr, double *__restrict__ Darr,
                const double *__restrict__ obs, int K, const double *__restrict__ root_w, int n,
-               int nnodes, double *__restrict__ out, int *__restrict__ status, long nsites, long nblocks)
+               int nnodes, double *__restrict__ out, int *__restrict__ status, long nsites, long nblocks,
+               const int *__restrict__ gset, long gs_pt, long gs_gt)
 {
     constexpr int KP = (KS + 1) / 2;
     __shared__ double xb[NT * 4 * 64];
@@ -67,6 +78,11 @@ be_down_kernel(const double *__restrict__ PfragT, const double *__restrict__ Gfr
     const int lane = threadIdx.x & 63;
     const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long blk = blockIdx.x;
+    if constexpr (PART) {
+        const long gs = __builtin_amdgcn_readfirstlane(gset[blk]);
+        PfragT += gs * gs_pt;
+        GfragT += gs * gs_gt;
+    }
     const long site = blk * 16 + (lane & 15);
     const bool site_ok = site < nsites;
     bool bad = false;
@@ -128,17 +144,26 @@ be_down_kernel(const double *__restrict__ PfragT, const double *__restrict__ Gfr
 }
 
 // n <= 4: one lane per site; arrays [node][state][site], nodes in preorder; G [k][node][N][N]
-template <int N>
+// PART (a partitioned batch: sites are its slots): a wave's 64 slots lie in one granule of
+// `granule` slots (256 or 64); P of its rate set is gset[granule] * gs_p doubles further on, its
+// derivative tables are G [k][set][edge][N][N] (edge = node - 1, gs_g sets) -- wave-uniform, so P
+// and G stay scalar loads.
+template <int N, bool PART = false>
 __global__ void __launch_bounds__(256)
 be_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const double *__restrict__ G,
                int nk, const int *__restrict__ parent, const int *__restrict__ node_k,
                const void *__restrict__ obs, int compact, int K, int block_sites,
                const double *__restrict__ root_w, double *__restrict__ Larr,
                double *__restrict__ Marr, double *__restrict__ Darr, double *__restrict__ out,
-               int *__restrict__ status)
+               int *__restrict__ status, const int *__restrict__ gset, int granule, long gs_p, int gs_g)
 {
     const long site = (long)blockIdx.x * 256 + threadIdx.x;
     if (site >= nsites) return;
+    long gs = 0;
+    if constexpr (PART) {
+        gs = __builtin_amdgcn_readfirstlane(gset[(site & ~63L) / granule]);
+        P += gs * gs_p;
+    }
     auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
     lane_up<N, true>(nnodes, nsites, site, P, parent, node_k, obs, compact, K, block_sites, Larr, Marr);
     // down: the root, then every node after its parent
@@ -162,7 +187,8 @@ be_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const doub
             Darr[idx(v, b)] = y * L[b];
         }
         for (int k = 0; k < nk; ++k) {
-            const double *Gv = G + ((size_t)k * nnodes + v) * N * N;
+            const double *Gv = PART ? G + (((size_t)k * gs_g + gs) * (nnodes - 1) + (v - 1)) * N * N
+                                    : G + ((size_t)k * nnodes + v) * N * N;
             double t = 0.0;
 #pragma unroll
             for (int b = 0; b < N; ++b) {
@@ -204,6 +230,104 @@ edge_sums_kernel(int nnodes, int nk, long nsites, const double *__restrict__ val
         __syncthreads();
     }
     if (tid < nk) sums[(size_t)v * nk + tid] = part[tid][0];
+}
+
+// ---- a partitioned batch (rt_sites_branch_expectations_partitioned) ----
+
+// the edges of the first K rate sets, set after set without the roots' entries: edge e is node
+// e % (N - 1) + 1 of set e / (N - 1); ones / ident: what the block exponential's launch reads
+__global__ void __launch_bounds__(256)
+part_edges_kernel(int K, int N, const int *__restrict__ qidx, const double *__restrict__ t,
+                  int *__restrict__ eq, double *__restrict__ et, double *__restrict__ ones,
+                  int *__restrict__ ident)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= K * (N - 1)) return;
+    const int k = e / (N - 1), v = e - k * (N - 1) + 1;
+    eq[e] = qidx[(size_t)k * N + v];
+    et[e] = t[(size_t)k * N + v];
+    ones[e] = 1.0;
+    ident[e] = e;
+}
+
+// slot order -> caller order: values [site][row] (row = nnodes * nk doubles), status
+__global__ void __launch_bounds__(256)
+part_gather_kernel(const double *__restrict__ val_slot, const int *__restrict__ status_slot,
+                   const long *__restrict__ slot_of_site, long nsites, long row,
+                   double *__restrict__ val, int *__restrict__ status)
+{
+    const long total = nsites * row;
+    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < total; j += (long)gridDim.x * 256) {
+        const long i = j / row, c = j - i * row;
+        const long slot = slot_of_site[i];
+        if (val) val[j] = val_slot[slot * row + c];
+        if (c == 0) status[i] = status_slot[slot];
+    }
+}
+
+// stage 1 of the per-set sums: workgroup (b, k, v) adds a contiguous piece of set k's run for
+// node v, thread t every 256th slot of it, pads skipped, the weights through `order`; then the
+// 256 partial sums by halves.  The shape comes from the plan alone: the same bits every call.
+__global__ void __launch_bounds__(256)
+part_sums_stage1_kernel(int nnodes, int nk, const double *__restrict__ val_slot,
+                        const unsigned char *__restrict__ is_pad, const long *__restrict__ order,
+                        const long *__restrict__ run_begin, const double *__restrict__ weights,
+                        int nblocks, double *__restrict__ part)
+{
+    __shared__ double sh[BC_MAX][256];
+    const int b = blockIdx.x, k = blockIdx.y, v = blockIdx.z, tid = threadIdx.x;
+    const long r0 = run_begin[k], r1 = run_begin[k + 1];
+    const long per = (r1 - r0 + nblocks - 1) / nblocks;
+    const long lo = r0 + (long)b * per, hi = lo + per < r1 ? lo + per : r1;
+    double acc[BC_MAX];
+#pragma unroll
+    for (int c = 0; c < BC_MAX; ++c) acc[c] = 0.0;
+    for (long slot = lo + tid; slot < hi; slot += 256) {
+        if (is_pad[slot]) continue;
+        const double w = weights ? weights[order[slot]] : 1.0;
+        const double *x = val_slot + ((size_t)slot * nnodes + v) * nk;
+#pragma unroll
+        for (int c = 0; c < BC_MAX; ++c)
+            if (c < nk) acc[c] += w * x[c];
+    }
+#pragma unroll
+    for (int c = 0; c < BC_MAX; ++c) sh[c][tid] = acc[c];
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h)
+            for (int c = 0; c < nk; ++c) sh[c][tid] += sh[c][tid + h];
+        __syncthreads();
+    }
+    if (tid < nk) part[(((size_t)k * nblocks + b) * nnodes + v) * nk + tid] = sh[tid][0];
+}
+
+// stage 2: workgroup (k, v) adds set k's stage-1 sums of node v -> set_sums[k][v][.]
+__global__ void __launch_bounds__(256)
+part_sums_stage2_kernel(int nnodes, int nk, const double *__restrict__ part, int nblocks,
+                        double *__restrict__ set_sums)
+{
+    __shared__ double sh[BC_MAX][256];
+    const int k = blockIdx.x, v = blockIdx.y, tid = threadIdx.x;
+    for (int c = 0; c < nk; ++c)
+        sh[c][tid] = tid < nblocks ? part[(((size_t)k * nblocks + tid) * nnodes + v) * nk + c] : 0.0;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h)
+            for (int c = 0; c < nk; ++c) sh[c][tid] += sh[c][tid + h];
+        __syncthreads();
+    }
+    if (tid < nk) set_sums[((size_t)k * nnodes + v) * nk + tid] = sh[tid][0];
+}
+
+// edge_sums[v][c]: the per-set rows added in set order (one thread per entry)
+__global__ void __launch_bounds__(256)
+part_sums_total_kernel(int K, long row, const double *__restrict__ set_sums, double *__restrict__ sums)
+{
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= row) return;
+    double t = 0.0;
+    for (int k = 0; k < K; ++k) t += set_sums[(size_t)k * row + j];
+    sums[j] = t;
 }
 
 }  // namespace
@@ -268,9 +392,9 @@ extern "C" int rt_sites_branch_expectations(rt_model *m, rt_sites *s, int recomp
     for (int k = 0; k < nk; ++k) {
         double *Gk = d_G + (size_t)k * N * nn;
         RT_HIP(hipMemsetAsync(Gk, 0, nn * 8, st));
-        hipLaunchKernelGGL(direction_kernel, dim3((unsigned)ne), dim3(256), 0, st, (int)n,
+        hipLaunchKernelGGL(direction_kernel<false>, dim3((unsigned)ne), dim3(256), 0, st, (int)n,
                            (const double *)m->d_Q, (const int *)(m->d_qidx + 1),
-                           (const double *)(d_E + (size_t)k * nn), d_W);
+                           (const double *)(d_E + (size_t)k * nn), d_W, (int)ne, 0L);
         RT_HIP(hipGetLastError());
         if (wide) {
             RT_TRY(rt_frechet_wide_pairs_device(ctx, n, N - 1, m->d_Q, m->d_qidx + 1, m->d_t + 1, d_W,
@@ -290,7 +414,8 @@ extern "C" int rt_sites_branch_expectations(rt_model *m, rt_sites *s, int recomp
                                dim3(256), 0, st, (int)N, (long)nsites, (const double *)m->d_P,
                                (const double *)d_G, nk, d_tab, d_tab + N, (const void *)s->d_obs,
                                s->compact_states, (int)s->nobs, s->block_sites,
-                               (const double *)m->d_root, p.d_L, p.d_M, p.d_D, d_val, d_status);
+                               (const double *)m->d_root, p.d_L, p.d_M, p.d_D, d_val, d_status,
+                               (const int *)nullptr, 0, 0L, 0);
             return RT_OK;
         }));
     } else {
@@ -305,7 +430,8 @@ extern "C" int rt_sites_branch_expectations(rt_model *m, rt_sites *s, int recomp
                                (const double *)p.d_PT, (const double *)d_GT, nk, p.nops,
                                (const int4 *)p.d_steps, (const double *)p.d_L, (const double *)p.d_M,
                                p.d_D, (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
-                               (int)n, (int)N, d_val, d_status, (long)x->nsites, (long)x->nblocks);
+                               (int)n, (int)N, d_val, d_status, (long)x->nsites, (long)x->nblocks,
+                               (const int *)nullptr, 0L, 0L);
             return RT_OK;
         }));
     }
@@ -321,6 +447,185 @@ extern "C" int rt_sites_branch_expectations(rt_model *m, rt_sites *s, int recomp
     if (values)
         RT_HIP(hipMemcpyAsync(values, d_val, (size_t)nsites * N * nk * 8, hipMemcpyDeviceToHost, st));
     if (status) RT_HIP(hipMemcpyAsync(status, d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+// The same read of a PARTITIONED batch: on the edge above node v, site i uses Q, t, P and the
+// derivative of its own rate set (rt_model_set_rate_sets).  In the order of the data:
+//   1. the edges of the batch's K sets as one list of K (nnodes - 1); per coefficient matrix one
+//      direction launch (E of the edge's set where the coefficients are per set), ONE launch of
+//      the derivative route over the whole list -- the exponential's variant chosen as for one
+//      set's edges, so every derivative has the bits the ordinary call gives under that set -- and
+//      one extract straight into G [coef][set][edge][n][n] (no root slots: an extract writes its
+//      edges contiguously);
+//   2. n > 4: P^T and G^T of every set as A fragments, [set][step] and [set][coef][step], by two
+//      rt_launch_pack_pt launches over step tables that span the sets; the upward pass on the
+//      twin through the batch's granule_set (post_up); be_down_kernel<.., true> per 16-slot tile.
+//      n <= 4: be_lane_kernel<N, true>;
+//   3. per (set, node, coefficient) the fixed-order two-stage sum over the set's run with the
+//      pads skipped, the per-set rows added in set order, and the gather into caller order.
+extern "C" int rt_sites_branch_expectations_partitioned(rt_model *m, rt_sites *s, int recompute_transitions,
+                                                        int64_t n_coefs, int coefs_per_set,
+                                                        const double *coefs, double *values,
+                                                        double *edge_sums, double *set_edge_sums,
+                                                        int32_t *status)
+{
+    static const char who[] = "rt_sites_branch_expectations_partitioned";
+    post_pass p;                                 // (alive until the synchronisation below)
+    RT_TRY(post_open(&p, who, m, s, true));
+    RT_REQUIRE(n_coefs >= 1 && coefs, "at least one coefficient matrix is needed");
+    if (n_coefs > RT_MAX_BRANCH_COEFS) {
+        rt_set_error("%s: at most %d coefficient matrices (%lld here)", who, RT_MAX_BRANCH_COEFS,
+                     (long long)n_coefs);
+        return RT_ERR_UNSUPPORTED;
+    }
+    const rt_partition *pt = s->part;
+    const rt_rate_sets &r = m->multi;
+    const int64_t n = p.n, N = p.N, nslots = p.nsites, nreal = pt->nsites, K = pt->nsets;
+    RT_TRY(post_layout(&p, true));
+    RT_REQUIRE(r.P_stride == N * n * n, "unexpected stride of the sets' transition matrices");
+    const size_t nn = (size_t)n * n, ne1 = (size_t)(N - 1), ne = (size_t)K * ne1;
+    const int nk = (int)n_coefs;
+    const size_t ncoef = (size_t)(coefs_per_set ? K : 1) * nk;
+    for (size_t j = 0; j < ncoef * nn; ++j)
+        RT_REQUIRE(std::isfinite(coefs[j]), "coefficient %lld of matrix %lld is not finite",
+                   (long long)(j % nn), (long long)(j / nn));
+    rt_ctx *ctx = p.ctx;
+    const bool wide = 2 * n > RT_MAX_EXPM_STATES;
+    const int nb = pt->nblocks;
+    const size_t row = (size_t)N * nk;
+    // scratch: L, M, D of every node and slot (post_layout), the values in slot and in caller
+    // order, the sums, the edge list, the derivative route's buffers over all K (nnodes - 1)
+    // edges, the derivative tables, and per set the fragments of P^T and of every G^T
+    const size_t tab = (size_t)p.nops * p.NT * p.KP * 128 * 8;
+    const size_t wide_edge = wide ? rt_frechet_wide_scratch_doubles(n, 1) : 0;
+    post_plan &plan = p.plan;
+    const size_t o_val = plan.take((size_t)nslots * row * 8);
+    const size_t o_valc = plan.take(values ? (size_t)nreal * row * 8 : 8);
+    const size_t o_statc = plan.take((size_t)nreal * 4);
+    const size_t o_setsum = plan.take((size_t)K * row * 8), o_sum = plan.take(row * 8);
+    const size_t o_part = plan.take((size_t)K * nb * row * 8);
+    const size_t o_E = plan.take(ncoef * nn * 8);
+    const size_t o_G = plan.take((size_t)nk * ne * nn * 8);
+    const size_t o_W = plan.take(ne * nn * 8);
+    const size_t o_B = wide ? plan.take(ne * wide_edge * 8) : plan.take(ne * 4 * nn * 8);
+    const size_t o_X = wide ? plan.take(8) : plan.take(ne * 4 * nn * 8);
+    const size_t o_scale = plan.take(ne * 8), o_ones = plan.take(ne * 8), o_ident = plan.take(ne * 4);
+    const size_t o_eq = plan.take(ne * 4), o_et = plan.take(ne * 8);
+    const size_t o_PTs = p.lane ? plan.take(8) : plan.take((size_t)K * tab);
+    const size_t o_GT = p.lane ? plan.take(8) : plan.take((size_t)K * nk * tab);
+    const size_t o_tabP = plan.take((size_t)K * p.nops * 4);
+    const size_t o_tabG = plan.take((size_t)K * nk * p.nops * 4);
+    RT_TRY(post_begin(&p, recompute_transitions));
+    hipStream_t st = p.st;
+    unsigned char *base = p.base;
+    double *d_val = (double *)(base + o_val), *d_valc = (double *)(base + o_valc);
+    double *d_setsum = (double *)(base + o_setsum), *d_sum = (double *)(base + o_sum);
+    double *d_part = (double *)(base + o_part);
+    double *d_E = (double *)(base + o_E), *d_G = (double *)(base + o_G), *d_W = (double *)(base + o_W);
+    double *d_B = (double *)(base + o_B), *d_X = (double *)(base + o_X);
+    double *d_scale = (double *)(base + o_scale), *d_ones = (double *)(base + o_ones);
+    double *d_et = (double *)(base + o_et);
+    int *d_ident = (int *)(base + o_ident), *d_eq = (int *)(base + o_eq), *d_status = p.d_status;
+    int *d_statc = (int *)(base + o_statc), *d_tabP = (int *)(base + o_tabP), *d_tabG = (int *)(base + o_tabG);
+    // (host buffers of the asynchronous copies: alive until the synchronisation below)
+    std::vector<int32_t> internal((size_t)N, 0), tabP, tabG;
+    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
+    RT_HIP(hipMemcpyAsync(d_E, coefs, ncoef * nn * 8, hipMemcpyHostToDevice, st));
+    // 1. the derivative tables
+    hipLaunchKernelGGL(part_edges_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, (int)K,
+                       (int)N, (const int *)r.d_qidx, (const double *)r.d_t, d_eq, d_et, d_ones, d_ident);
+    RT_HIP(hipGetLastError());
+    for (int c = 0; c < nk; ++c) {
+        double *Gc = d_G + (size_t)c * ne * nn;
+        hipLaunchKernelGGL(direction_kernel<true>, dim3((unsigned)ne), dim3(256), 0, st, (int)n,
+                           (const double *)r.d_Q, (const int *)d_eq,
+                           (const double *)(d_E + (size_t)c * nn), d_W, (int)ne1,
+                           (long)(coefs_per_set ? (size_t)nk * nn : 0));
+        RT_HIP(hipGetLastError());
+        if (wide) {
+            RT_TRY(rt_frechet_wide_pairs_device(ctx, n, (int64_t)ne, r.d_Q, d_eq, d_et, d_W, d_B, d_scale,
+                                                nullptr));
+            RT_TRY(rt_frechet_wide_extract_device(ctx, n, (int64_t)ne, d_et, d_B, d_scale, Gc));
+        } else {
+            RT_TRY(rt_frechet_blocks_device(ctx, n, (int64_t)ne, r.d_Q, d_eq, d_et, d_W, d_B, d_X, d_scale,
+                                            d_ones, d_ident, N - 1));
+            RT_TRY(rt_frechet_extract_device(ctx, n, (int64_t)ne, d_et, d_X, d_scale, Gc));
+        }
+    }
+    // 2. the passes
+    RT_TRY(post_up(&p, internal.data(), false));
+    const int *d_gset = pt->d_granule_set;
+    if (p.lane) {
+        const int *d_tab = p.d_ptab;
+        RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
+            hipLaunchKernelGGL((be_lane_kernel<decltype(nv)::value, true>),
+                               dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, st, (int)N,
+                               (long)nslots, (const double *)r.d_P, (const double *)d_G, nk, d_tab,
+                               d_tab + N, (const void *)s->d_obs, s->compact_states, (int)s->nobs,
+                               s->block_sites, (const double *)m->d_root, p.d_L, p.d_M, p.d_D, d_val,
+                               d_status, d_gset, (int)pt->G, (long)r.P_stride, (int)K);
+            return RT_OK;
+        }));
+    } else {
+        const rt_sites *x = p.x;
+        double *d_PTs = (double *)(base + o_PTs), *d_GT = (double *)(base + o_GT);
+        // step -> matrix of the table it is packed from, over the sets: P [set][node], G
+        // [coef][set][edge] (the root's step is never read: any matrix of the set)
+        tabP.resize((size_t)K * p.nops);
+        tabG.resize((size_t)K * nk * p.nops);
+        for (int64_t k = 0; k < K; ++k)
+            for (int i = 0; i < p.nops; ++i) {
+                const int64_t v = p.step_node[(size_t)i];
+                tabP[(size_t)(k * p.nops + i)] = (int32_t)(k * N + v);
+                for (int c = 0; c < nk; ++c)
+                    tabG[(size_t)((k * nk + c) * p.nops + i)] =
+                        (int32_t)((c * K + k) * (int64_t)ne1 + (v ? v - 1 : 0));
+            }
+        RT_HIP(hipMemcpyAsync(d_tabP, tabP.data(), tabP.size() * 4, hipMemcpyHostToDevice, st));
+        RT_HIP(hipMemcpyAsync(d_tabG, tabG.data(), tabG.size() * 4, hipMemcpyHostToDevice, st));
+        RT_TRY(rt_launch_pack_pt(ctx, (int)n, p.NT, p.KP, (int)(K * p.nops), d_tabP, r.d_P, d_PTs));
+        RT_TRY(rt_launch_pack_pt(ctx, (int)n, p.NT, p.KP, (int)(K * nk * p.nops), d_tabG, d_G, d_GT));
+        RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
+            constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
+            hipLaunchKernelGGL((be_down_kernel<NT, KS, true>), dim3((unsigned)x->nblocks), dim3(64 * NT), 0,
+                               st, (const double *)d_PTs, (const double *)d_GT, nk, p.nops,
+                               (const int4 *)p.d_steps, (const double *)p.d_L, (const double *)p.d_M,
+                               p.d_D, (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
+                               (int)n, (int)N, d_val, d_status, (long)x->nsites, (long)x->nblocks, d_gset,
+                               (long)(tab / 8), (long)((size_t)nk * (tab / 8)));
+            return RT_OK;
+        }));
+    }
+    RT_HIP(hipGetLastError());
+    // 3. the sums per set (pads masked, not merely weighted out: a pad repeats a real site), their
+    //    total in set order, and what leaves the device in caller order
+    if (edge_sums || set_edge_sums) {
+        hipLaunchKernelGGL(part_sums_stage1_kernel, dim3((unsigned)nb, (unsigned)K, (unsigned)N), dim3(256),
+                           0, st, (int)N, nk, (const double *)d_val, (const unsigned char *)pt->d_is_pad,
+                           (const long *)pt->d_order, (const long *)pt->d_run_begin,
+                           (const double *)s->d_weights, nb, d_part);
+        hipLaunchKernelGGL(part_sums_stage2_kernel, dim3((unsigned)K, (unsigned)N), dim3(256), 0, st, (int)N,
+                           nk, (const double *)d_part, nb, d_setsum);
+        hipLaunchKernelGGL(part_sums_total_kernel, dim3((unsigned)((row + 255) / 256)), dim3(256), 0, st,
+                           (int)K, (long)row, (const double *)d_setsum, d_sum);
+        RT_HIP(hipGetLastError());
+        if (set_edge_sums)
+            RT_HIP(hipMemcpyAsync(set_edge_sums, d_setsum, (size_t)K * row * 8, hipMemcpyDeviceToHost, st));
+        if (edge_sums) RT_HIP(hipMemcpyAsync(edge_sums, d_sum, row * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (values || status) {
+        const long grow = values ? (long)row : 1;
+        const long blocks = std::min<long>(((long)nreal * grow + 255) / 256, 1 << 16);
+        hipLaunchKernelGGL(part_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, st,
+                           (const double *)d_val, (const int *)d_status,
+                           (const long *)pt->d_slot_of_site, (long)nreal, grow,
+                           values ? d_valc : (double *)nullptr, d_statc);
+        RT_HIP(hipGetLastError());
+        if (values) RT_HIP(hipMemcpyAsync(values, d_valc, (size_t)nreal * row * 8, hipMemcpyDeviceToHost, st));
+        if (status) RT_HIP(hipMemcpyAsync(status, d_statc, (size_t)nreal * 4, hipMemcpyDeviceToHost, st));
+    }
     RT_HIP(hipStreamSynchronize(st));
     return RT_OK;
 }

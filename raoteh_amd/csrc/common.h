@@ -577,9 +577,12 @@ int rt_frechet_statistics_device(rt_ctx *ctx, int64_t n, int64_t nedges, const d
 // ... its two halves for a caller that wants the derivatives themselves (branch_expect.hip): the
 // block exponentials without the contraction, then dG[e][a][b] = t_e L(t_e Q_e, C_e)[a][b] for
 // dW[e] = C_e^T
+// (variant_count > 0: the exponential's kernel variant is chosen as for that many edges, as
+// rt_launch_expm's -- the edges of K rate sets in one launch, each set's as in a launch of its own)
 int rt_frechet_blocks_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double *dQ,
                              const int32_t *dqidx, const double *dt, const double *dW, double *dB,
-                             double *dE, double *dscale, const double *dones, const int32_t *dident);
+                             double *dE, double *dscale, const double *dones, const int32_t *dident,
+                             int64_t variant_count = 0);
 int rt_frechet_extract_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double *dt,
                               const double *dE, const double *dscale, double *dG);
 // frechet_wide.hip: the same for 64 < n <= 128 by the pair recurrence (no order-2n block);
@@ -607,8 +610,12 @@ void rt_expect_lane_release(rt_model *m);
 // KP k-step pairs), asynchronous on the context's stream
 int rt_launch_pack_pt(rt_ctx *ctx, int n, int NT, int KP, int nops, const int *d_step_node,
                       const double *d_P, double *d_PT);
-// a split-M interpreter batch over the resident observations of `src` (api.hip)
+// a split-M interpreter batch over the resident observations of `src` (api.hip); of a
+// partitioned batch: over its slots, launched through a view with the batch's granule_set
 int rt_sites_twin_interpreter(rt_sites *src, rt_sites **out);
+// api.hip: the K (nnodes - 1) exponentials again from the resident rate sets, every table of the
+// sets rewritten (what rt_step_partitioned does with recompute_transitions)
+int rt_rate_sets_recompute(rt_model *m);
 // passes.hip: the context's grow-only device scratch (ctx->d_scratch) holds at least `bytes`
 // afterwards
 int rt_scratch_reserve(rt_ctx *ctx, size_t bytes);

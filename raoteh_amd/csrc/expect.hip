@@ -120,12 +120,14 @@ int rt_frechet_statistics_device(rt_ctx *ctx, int64_t n, int64_t nedges, const d
 // corners are M_e / scale[e]
 int rt_frechet_blocks_device(rt_ctx *ctx, int64_t n, int64_t nedges, const double *dQ,
                              const int32_t *dqidx, const double *dt, const double *dW, double *dB,
-                             double *dE, double *dscale, const double *dones, const int32_t *dident)
+                             double *dE, double *dscale, const double *dones, const int32_t *dident,
+                             int64_t variant_count)
 {
     hipLaunchKernelGGL(frechet_assemble_kernel, dim3((unsigned)nedges), dim3(256), 0, ctx->stream,
                        (int)n, dQ, dqidx, dt, dW, dB, dscale);
     RT_HIP(hipGetLastError());
-    return rt_launch_expm(ctx, 2 * n, nedges, dB, dident, dones, dE, nullptr, nullptr, 0, nullptr);
+    return rt_launch_expm(ctx, 2 * n, nedges, dB, dident, dones, dE, nullptr, nullptr, 0, nullptr,
+                          nullptr, nullptr, variant_count);
 }
 
 // ... and the derivatives themselves out of dE: dG [nedges][n][n], row = state at the parent

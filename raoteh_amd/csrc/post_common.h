@@ -83,14 +83,22 @@ inline void post_lane_table(const rt_model *m, const rt_sites *s, const int *w_o
 }
 
 // the handles and the sizes every later check and layout goes by
-inline int post_open(post_pass *p, const char *who, rt_model *m, rt_sites *s)
+// (partitioned: the call is one of those that take a partitioned batch, and nothing else --
+// nsites counts its slots, the tables are those of the model's rate sets)
+inline int post_open(post_pass *p, const char *who, rt_model *m, rt_sites *s, bool partitioned = false)
 {
     RT_REQUIRE(m && s, "null pointer");
-    if (s->part) {
-        rt_set_error("%s: a partitioned batch is evaluated by rt_step_partitioned only", who);
+    if (s->part && !partitioned) {
+        rt_set_error("%s: a partitioned batch is evaluated by rt_step_partitioned and read by "
+                     "rt_sites_branch_expectations_partitioned only", who);
         return RT_ERR_UNSUPPORTED;
     }
+    RT_REQUIRE(!partitioned || s->part, "%s: an ordinary batch (rt_sites_create_partitioned makes "
+               "the batches this call takes)", who);
     RT_REQUIRE(s->model == m, "the site batch belongs to another model");
+    RT_REQUIRE(!partitioned || m->multi.K >= s->part->nsets, "%s: the batch uses %lld rate sets, the "
+               "model holds %lld (rt_model_set_rate_sets)", who,
+               (long long)(s->part ? s->part->nsets : 0), (long long)m->multi.K);
     p->who = who; p->m = m; p->s = s; p->ctx = m->ctx; p->st = m->ctx->stream;
     p->n = m->n; p->N = m->nnodes; p->nsites = s->nsites; p->nops = (int)s->ops.size();
     p->lane = s->layout == RT_LAYOUT_LANE;
@@ -139,8 +147,12 @@ inline int post_begin(post_pass *p, int recompute_transitions, bool draws = fals
         return RT_ERR_UNSUPPORTED;
     }
     RT_HIP(hipSetDevice(p->ctx->device));
-    if (recompute_transitions) RT_TRY(rt_model_recompute_transitions(p->m));
-    RT_REQUIRE(p->m->have_P, "the model has no transition matrices yet");
+    if (p->s->part) {                            // (the sets' tables exist since set_rate_sets)
+        if (recompute_transitions) RT_TRY(rt_rate_sets_recompute(p->m));
+    } else {
+        if (recompute_transitions) RT_TRY(rt_model_recompute_transitions(p->m));
+        RT_REQUIRE(p->m->have_P, "the model has no transition matrices yet");
+    }
     if (!p->lane) {
         if (!p->s->expect_twin) RT_TRY(rt_sites_twin_interpreter(p->s, &p->s->expect_twin));
         p->x = p->s->expect_twin;
@@ -179,10 +191,28 @@ inline int post_up(post_pass *p, const int *w_of_node, bool pack_pt)
                               hipMemcpyHostToDevice, p->st));
     x->d_Lout = p->d_L;
     x->d_Mout = p->d_M;
-    const int rc = rt_launch_prune(p->m, x, false);
+    int rc;
+    if (p->s->part) {
+        // every tile under the tables of its own set, as rt_step_partitioned launches the batch;
+        // the outputs are the twin's
+        const rt_rate_sets &r = p->m->multi;
+        rt_prune_view v;
+        v.P = r.d_P; v.Pfrag = r.d_Pfrag; v.Pquad = r.d_Pquad; v.Pcol = r.d_Pcol;
+        v.loglik = x->d_loglik; v.status = x->d_status; v.partial = x->d_partial;
+        v.granule_set = p->s->part->d_granule_set;
+        v.frag_stride = r.frag_stride; v.pcol_stride = r.pcol_stride;
+        if (x->nblocks * 16 != p->s->part->padded) {         // (one granule_set entry per tile)
+            rt_set_error("%s: the twin's tiles do not match the batch's plan", p->who);
+            rc = RT_ERR_INVALID;
+        } else {
+            rc = rt_launch_prune(p->m, x, false, false, &v);
+        }
+    } else {
+        rc = rt_launch_prune(p->m, x, false);
+    }
     x->d_Lout = x->d_Mout = nullptr;
     RT_TRY(rc);
-    if (pack_pt)
+    if (pack_pt && !p->s->part)                  // (a partitioned batch: the caller packs per set)
         RT_TRY(rt_launch_pack_pt(p->ctx, (int)p->n, p->NT, p->KP, p->nops, p->d_ptab, p->m->d_P,
                                  p->d_PT));
     return RT_OK;

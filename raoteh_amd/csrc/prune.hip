@@ -621,7 +621,8 @@ prune_mfma_kernel(const double *__restrict__ Pfrag,  // [nops][NT][KP][64][2]
 #include "prune_mfma_body.inc"
 #undef RT_PART
 
-// (instantiated with STORE = false only: the expectation path has no partitioned form)
+// (STORE = true: the upward pass of rt_sites_branch_expectations_partitioned, through the batch's
+// interpreter twin -- dense leaves, no root halves, as the plain kernel's store variant)
 template <int NT, int KS, bool STORE, bool SPARSE>
 __global__ void __launch_bounds__(rt_split_waves(NT) * 64)
 prune_mfma_part_kernel(const double *__restrict__ Pfrag, const int4_t *__restrict__ prog, int nops,
@@ -1440,11 +1441,12 @@ static int launch_mfma_inst(rt_model *m, rt_sites *s, const rt_prune_view &v)
     rt_interp_halves hv;
     // a partitioned batch: the same forms with the per-tile set lookup (the combine kernel of the
     // halves form reads no transition table: it is the batch's ordinary one)
-    auto pkern = isp ? prune_mfma_part_kernel<NT, KS, false, (NT > 2)>
-                     : prune_mfma_part_kernel<NT, KS, false, false>;
+    auto pkern = s->d_Lout ? prune_mfma_part_kernel<NT, KS, true, false>
+                 : isp ? prune_mfma_part_kernel<NT, KS, false, (NT > 2)>
+                       : prune_mfma_part_kernel<NT, KS, false, false>;
     const bool part = v.granule_set != nullptr;
     if (part) {
-        RT_REQUIRE(!s->d_Lout && !s->rescale, "a partitioned batch runs the plain interpreter forms");
+        RT_REQUIRE(!s->rescale, "a partitioned batch runs the plain interpreter forms");
         RT_HIP(hipFuncSetAttribute((const void *)pkern,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     }
@@ -1490,7 +1492,7 @@ static int launch_mfma_inst(rt_model *m, rt_sites *s, const rt_prune_view &v)
         RT_LAUNCH_TIMED(m->ctx, pkern, dim3(grid), dim3(WAVES * 64), lds, v.Pfrag,
                         (const int4_t *)s->d_lane_ops, (int)s->ops.size(), s->d_obs, (int)s->nobs,
                         m->d_root, (int)m->n, lds_slots, v.loglik, v.status, v.partial,
-                        (long)s->nsites, (long)s->nblocks, (double *)nullptr, (double *)nullptr, hv, 0,
+                        (long)s->nsites, (long)s->nblocks, s->d_Lout, s->d_Mout, hv, 0,
                             ilw, ipc, ism,
                         (const int *)v.granule_set, (long)v.frag_stride, (long)v.pcol_stride);
         return RT_OK;

@@ -131,6 +131,53 @@ def check_branch_coefs(coefs, nstates):
     return np.ascontiguousarray(E)
 
 
+# TreeModel.branch_expectations_partitioned: BranchExpectations of a partitioned batch (values in
+# caller order, real sites only) plus set_edge_sums [nsets, nnodes, ncoefs], the weighted sums over
+# each rate set's sites (zeros for an empty set; edge_sums is their sum in set order)
+PartitionedBranchExpectations = collections.namedtuple(
+    'PartitionedBranchExpectations', 'values edge_sums set_edge_sums status nodes')
+
+
+def check_branch_coefs_partitioned(coefs, nstates, nsets):
+    """The coefficients of TreeModel.branch_expectations_partitioned -> (f64[ncoefs, n, n], False)
+    for one (n, n) matrix or a (C, n, n) sequence shared by all rate sets (check_branch_coefs), or
+    (f64[nsets, ncoefs, n, n], True) for an (nsets, C, n, n) array with set k's matrices at [k].
+    ValueError as check_branch_coefs, and for a four-dimensional array whose leading dimension is
+    not nsets."""
+    try:
+        E = np.array(coefs, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('coefs must be (%d, %d), (C, %d, %d) or (nsets, C, %d, %d)'
+                         % ((nstates,) * 6))
+    if E.ndim != 4:
+        return check_branch_coefs(coefs, nstates), False
+    if E.shape[0] != nsets:
+        raise ValueError('per-set coefs must have nsets=%d leading entries, not %d (shape %s)'
+                         % (nsets, E.shape[0], E.shape))
+    if E.shape[2:] != (nstates, nstates):
+        raise ValueError('coefs must be (%d, %d), (C, %d, %d) or (nsets, C, %d, %d), not %s'
+                         % ((nstates,) * 6 + (E.shape,)))
+    if not 1 <= E.shape[1] <= _lib.RT_MAX_BRANCH_COEFS:
+        raise ValueError('between 1 and %d coefficient matrices per call (%d here)'
+                         % (_lib.RT_MAX_BRANCH_COEFS, E.shape[1]))
+    if not np.isfinite(E).all():
+        raise ValueError('the coefficients must be finite')
+    return np.ascontiguousarray(E), True
+
+
+def partition_chain_rule(grad, rates, tau):
+    """The gradient of TreeModel.branch_length_gradient_partitioned, grad[k, v] = d/d t[k][v],
+    under the usual parametrisation t[k][v] = rates[k] * tau[v] -> (d/d tau f64[nnodes],
+    d/d rates f64[nsets]): d/d tau_v = sum_k r_k g[k, v], d/d r_k = sum_v tau_v g[k, v]."""
+    g = np.asarray(grad, dtype=np.float64)
+    r = np.asarray(rates, dtype=np.float64)
+    tau = np.asarray(tau, dtype=np.float64)
+    if g.ndim != 2 or r.shape != (g.shape[0],) or tau.shape != (g.shape[1],):
+        raise ValueError('grad [nsets, nnodes], rates [nsets] and tau [nnodes] expected, not %s, '
+                         '%s and %s' % (g.shape, r.shape, tau.shape))
+    return r @ g, g @ tau
+
+
 # TreeModel.branch_profiles: lengths and sums [nnodes, G], values [nsites, nnodes, G] (or None),
 # all keyed by the edge's child in the preorder `nodes` (the root's row: lengths 0, values 0);
 # values[i, v, g] = log L_i(t_v -> lengths[v, g]) - log L_i, NaN in the row of an edge whose
@@ -827,7 +874,8 @@ class TreeModel(object):
         <= 64) or uint64[nsites,nobs,ceil(nstates/64)] (bit s % 64 of word s // 64).
         site_sets (int[nsites], with nsets or one more than its maximum): a PARTITIONED batch
         (rt_sites_create_partitioned) -- site i is evaluated under rate set site_sets[i] of
-        set_rate_sets by step_partitioned, and by nothing else."""
+        set_rate_sets by step_partitioned and read by branch_expectations_partitioned /
+        branch_length_gradient_partitioned, and by nothing else."""
         code = _KINDS[kind]
         idx = _i64([self.tree.node_to_index[v] for v in obs_nodes])
         if kind == 'dense':
@@ -881,6 +929,8 @@ class TreeModel(object):
             self._h, Q.shape[0], _ptr(Q, c_double), Q.shape[1],
             None if node_q is None else _ptr(node_q, c_int64), _ptr(t, c_double)))
         self._nsets = Q.shape[0]
+        # (branch_length_gradient_partitioned builds each set's E from its Q)
+        self._rate_sets = (Q.copy(), t.copy())
 
     def step_multi(self, batch, recompute_transitions=True):
         """rt_step_multi: (the exponentials of every rate set again +) one pruning of the batch
@@ -1125,6 +1175,73 @@ class TreeModel(object):
             None if values is None else _ptr(values, c_double), _ptr(edge_sums, c_double),
             _ptr(status, c_int32)))
         return BranchExpectations(values, edge_sums, status, nodes)
+
+    def branch_expectations_partitioned(self, batch, coefs, per_site=True,
+                                        recompute_transitions=False):
+        """rt_sites_branch_expectations_partitioned: branch_expectations for a batch uploaded
+        with site_sets -- on every edge site i uses Q, t, P and the derivative of its own rate
+        set of set_rate_sets.  coefs: one (n, n) array, a (C, n, n) sequence shared by all sets,
+        or (nsets, C, n, n) with set k's matrices at [k] (check_branch_coefs_partitioned).
+        Returns a PartitionedBranchExpectations tuple: values[i, v, c] in caller order (None with
+        per_site=False: the array never leaves the device), edge_sums[v, c] the site-weighted
+        sum over the batch, set_edge_sums[k, v, c] the same over set k's sites (zeros for an
+        empty set), status, nodes.  No earlier step_partitioned is needed; what the batch holds
+        (log-likelihoods, totals, per-set totals) stays."""
+        nsets = int(getattr(batch, 'nsets', 0) or 0)
+        if batch.site_sets is None or nsets < 1:
+            raise ValueError('branch_expectations_partitioned takes a batch uploaded with '
+                             'site_sets (an ordinary batch: branch_expectations)')
+        n = self.nstates
+        E, per_set = check_branch_coefs_partitioned(coefs, n, nsets)
+        C = E.shape[1] if per_set else E.shape[0]
+        ta = self.tree
+        N, S = ta.nnodes, batch.nsites
+        values = np.zeros((S, N, C)) if per_site else None
+        edge_sums = np.zeros((N, C))
+        set_sums = np.zeros((nsets, N, C))
+        status = np.zeros(S, dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_branch_expectations_partitioned(
+            self._h, batch._h, 1 if recompute_transitions else 0, C, 1 if per_set else 0,
+            _ptr(E, c_double), None if values is None else _ptr(values, c_double),
+            _ptr(edge_sums, c_double), _ptr(set_sums, c_double), _ptr(status, c_int32)))
+        return PartitionedBranchExpectations(values, edge_sums, set_sums, status,
+                                             list(ta.preorder_nodes))
+
+    def branch_length_gradient_partitioned(self, batch, recompute_transitions=False):
+        """g[k, v] = d (sum over the sites i of set k of w_i log L_i) / d t[k][v], f64[nsets,
+        nnodes] in preorder (0 at the root and where t[k][v] == 0), analytically from one
+        branch_expectations_partitioned call with per-set coefficients: ones off the diagonal
+        and diag(Q[k]) on it, so that set k's direction is Q[k] itself and its edge sum is
+        t[k][v] times the derivative.  For ONE rate matrix per set: the coefficient matrix of
+        a set is shared by all its edges, so with per-edge rate matrices no single E has every
+        edge's diag(Q) on its diagonal -- ValueError then.
+        Chain rule for the usual parametrisation t[k][v] = r_k * tau_v (a tree shared by the
+        partitions, one multiplier each): d/d tau_v = sum_k r_k g[k, v] and d/d r_k =
+        sum_v tau_v g[k, v] (partition_chain_rule)."""
+        rates = getattr(self, '_rate_sets', None)
+        if rates is None:
+            raise ValueError('set_rate_sets has not been called')
+        Q, t = rates
+        nsets = int(getattr(batch, 'nsets', 0) or 0)
+        if Q.shape[1] != 1:
+            raise ValueError('branch_length_gradient_partitioned needs one rate matrix per set '
+                             'for all edges (%d here): the coefficient matrix of a set is '
+                             'shared by all its edges' % Q.shape[1])
+        if Q.shape[0] < nsets:
+            raise ValueError('the batch uses nsets=%d rate sets, set_rate_sets gave %d'
+                             % (nsets, Q.shape[0]))
+        n = self.nstates
+        E = np.ones((max(nsets, 1), 1, n, n))
+        for k in range(nsets):
+            np.fill_diagonal(E[k, 0], np.diag(Q[k, 0]))
+        sums = self.branch_expectations_partitioned(
+            batch, E, per_site=False, recompute_transitions=recompute_transitions).set_edge_sums
+        tk = t[:nsets]
+        grad = np.zeros((nsets, self.tree.nnodes))
+        live = tk != 0
+        live[:, 0] = False
+        grad[live] = sums[:, :, 0][live] / tk[live]
+        return grad
 
     def branch_lengths(self):
         """The branch lengths of the last set_rates / set_rates_spectral as the device holds
