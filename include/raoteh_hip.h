@@ -743,7 +743,8 @@ const char *rt_sites_multi_kernel_name(const rt_sites *sites);
  * Everything else refuses a partitioned batch with RT_ERR_UNSUPPORTED and leaves it untouched:
  *   rt_prune, rt_step, rt_step_multi, rt_sites_clone, rt_expect_step, rt_sites_posteriors,
  *   rt_sites_branch_expectations, rt_sites_branch_profiles, rt_sites_sample_states,
- *   rt_sites_sample_mappings, rt_allreduce_totals, rt_allreduce_totals_group.
+ *   rt_sites_sample_mappings, rt_sites_branch_expectations_mixture, rt_allreduce_totals,
+ *   rt_allreduce_totals_group.
  *                                                               */
 int rt_partition_plan(const int32_t *site_set, int64_t nsites, int64_t nsets, int64_t granule,
             int64_t capacity, int64_t *order, int64_t *slot_of_site, uint8_t *is_pad,
@@ -759,6 +760,58 @@ int rt_sites_branch_expectations_partitioned(rt_model *model, rt_sites *sites,
 /* what the batch was laid out with: any pointer may be NULL; an ordinary batch gives zeros */
 int rt_sites_partition_info(const rt_sites *sites, int64_t *nsets, int64_t *granule,
             int64_t *padded);
+
+/* ---- 2d. site-class mixtures: posterior-weighted branch expectations, gradient ------------
+ *
+ * A site-class mixture (discrete-gamma rate categories, codon omega classes, a +I class) has the
+ * site likelihood L_i = sum_k c_k L_ik over the K rate sets of rt_model_set_rate_sets (section
+ * 2b gives its value).  rt_sites_branch_expectations_mixture gives what an optimiser or an EM
+ * step needs beyond the value, for an ORDINARY resident batch, every site under every set:
+ *     class_weights   f64[K], finite, >= 0, not all zero (the rule of rt_sites_multi_mixture)
+ *     coefs           f64[n_coefs][n][n] shared by all sets (coefs_per_set == 0), or
+ *                     f64[K][n_coefs][n][n], set k's matrices at [k]: layouts and meaning of
+ *                     rt_sites_branch_expectations_partitioned
+ *   L_ik is the site's likelihood under set k; set k is LIVE at site i when c_k > 0 and
+ *   L_ik > 0.  A set that is not live is skipped entirely: nothing of it is multiplied in.  All
+ *   sums over k run in set order.
+ *     loglik          f64[nsites]: log sum_k c_k L_ik; -inf where no set is live
+ *     class_post      f64[nsites][K]: c_k L_ik / sum_j c_j L_ij, the class posteriors (the
+ *                     empirical-Bayes site classification); a site with no live set: zeros
+ *     values          f64[nsites][nnodes][n_coefs]: sum_k class_post[i][k] x_k[i][v][c], x_k
+ *                     exactly what rt_sites_branch_expectations computes for the site with Q, t,
+ *                     P and the derivative G of set k (product and sum rounded separately: a
+ *                     posterior of 1 returns x_k bit for bit); the root's slot is 0; a site
+ *                     with no live set: zeros
+ *     set_edge_sums   f64[K][nnodes][n_coefs]: sum_i w_i class_post[i][k] x_k[i][v][c], w from
+ *                     rt_sites_set_weights (default 1)
+ *     edge_sums       f64[nnodes][n_coefs]: the per-set rows added in set order
+ *     class_sums      f64[K]: sum_i w_i class_post[i][k]
+ *     status          int32[nsites]: RT_SITE_ZERO_PROB where no set is live; else the OR over the
+ *                     LIVE sets of the 2 (a zero denominator) their passes report -- a set under
+ *                     which the site has zero likelihood leaks no bit
+ *   With C = Q_k (coefficients: ones off the diagonal, diag(Q_k) on it) set_edge_sums[k][v] is
+ *   t[k][v] d/d t[k][v] of sum_i w_i loglik[i]; with C = dQ_k/d theta, values is d loglik[i] / d
+ *   theta on each branch; class_sums[k] / c_k is the derivative in c_k.
+ *   Each output may be NULL; only what is given crosses PCIe.  The sums are reduced on the device in
+ *   a fixed order whose shape depends on (nsites, K, nnodes, n_coefs) alone: two calls return the
+ *   same bits.  The per-set sums go over the whole batch in pieces of 4096 sites: with K = 1 and
+ *   one piece edge_sums has the bits of rt_sites_branch_expectations.  Synchronous.
+ *   recompute_transitions != 0: rt_model_set_rate_sets's exponentials again from the resident rate
+ *   sets; no earlier rt_step_multi is needed.  The passes run set after set over one scratch for
+ *   L, M and D; the unweighted x_k of all sets stay in scratch (no chunking over the sets: a call
+ *   whose scratch passes 96 GB is refused).  Nothing resident changes: the batch's kernel,
+ *   log-likelihoods, status and totals, its rt_step_multi results, the model's own transitions
+ *   and the rate sets keep what they had.
+ *   RT_ERR_INVALID: no rate sets; a batch of another model; class_weights NULL or with a negative
+ *   or non-finite entry or all zero; n_coefs < 1 or coefs NULL; a coefficient that is not finite.
+ *   RT_ERR_UNSUPPORTED: a partitioned batch; what rt_sites_branch_expectations refuses ("rescale",
+ *   a generic-kernel batch, deep trees, nnodes < 2); more than RT_MAX_BRANCH_COEFS matrices; more
+ *   than 96 GB of scratch.                                                  */
+int rt_sites_branch_expectations_mixture(rt_model *model, rt_sites *sites,
+            int recompute_transitions, const double *class_weights, int64_t n_coefs,
+            int coefs_per_set, const double *coefs, double *values, double *edge_sums,
+            double *set_edge_sums, double *class_post, double *class_sums, double *loglik,
+            int32_t *status);
 
 /* ---- 3. multi-GPU: one process per GPU, RCCL over xGMI ------------------- */
 

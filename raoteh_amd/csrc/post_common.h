@@ -21,6 +21,8 @@ struct post_pass {
     hipStream_t st = nullptr;
     int64_t n = 0, N = 0, nsites = 0;
     bool lane = false, with_D = false;
+    bool per_set = false;                       // an ordinary batch read under the model's rate sets:
+                                                // the caller runs the upward pass set by set (post_up_set)
     int NT = 0, KS = 0, KP = 0, nops = 0;       // row tiles, k-steps, k-step pairs; schedule steps
     post_plan plan;
     size_t o_L = 0, o_M = 0, o_D = 0, o_status = 0, o_steps = 0, o_ptab = 0, o_PT = 0;
@@ -147,7 +149,7 @@ inline int post_begin(post_pass *p, int recompute_transitions, bool draws = fals
         return RT_ERR_UNSUPPORTED;
     }
     RT_HIP(hipSetDevice(p->ctx->device));
-    if (p->s->part) {                            // (the sets' tables exist since set_rate_sets)
+    if (p->s->part || p->per_set) {              // (the sets' tables exist since set_rate_sets)
         if (recompute_transitions) RT_TRY(rt_rate_sets_recompute(p->m));
     } else {
         if (recompute_transitions) RT_TRY(rt_model_recompute_transitions(p->m));
@@ -170,6 +172,28 @@ inline int post_begin(post_pass *p, int recompute_transitions, bool draws = fals
     return RT_OK;
 }
 
+// n > 4: the upward pass of the twin under the tables of rate set k of the model, L and M of every
+// step stored (the outputs are the twin's).  granule_set (a partitioned batch, k = 0): every tile
+// under the set of its granule instead.
+inline int post_up_set(post_pass *p, int64_t k, const int32_t *granule_set)
+{
+    rt_sites *x = p->x;
+    const rt_rate_sets &r = p->m->multi;
+    rt_prune_view v;
+    v.P = r.d_P + k * r.P_stride;
+    v.Pfrag = r.d_Pfrag + k * r.frag_stride;
+    v.Pquad = r.d_Pquad ? r.d_Pquad + k * r.quad_stride : nullptr;
+    v.Pcol = r.d_Pcol ? r.d_Pcol + k * r.pcol_stride : nullptr;
+    v.loglik = x->d_loglik; v.status = x->d_status; v.partial = x->d_partial;
+    v.granule_set = granule_set;
+    v.frag_stride = r.frag_stride; v.pcol_stride = r.pcol_stride;
+    x->d_Lout = p->d_L;
+    x->d_Mout = p->d_M;
+    const int rc = rt_launch_prune(p->m, x, false, false, &v);
+    x->d_Lout = x->d_Mout = nullptr;
+    return rc;
+}
+
 // the table of the downward pass with `w_of_node` as its last column and, for n > 4, the upward
 // pass: the split-M interpreter kernel with L and M of every step stored (its own log-likelihoods
 // and totals are the twin's, not the batch's), then with pack_pt the model's P^T as A fragments.
@@ -189,30 +213,21 @@ inline int post_up(post_pass *p, const int *w_of_node, bool pack_pt)
     if (pack_pt)
         RT_HIP(hipMemcpyAsync(p->d_ptab, p->step_node.data(), (size_t)p->nops * 4,
                               hipMemcpyHostToDevice, p->st));
-    x->d_Lout = p->d_L;
-    x->d_Mout = p->d_M;
-    int rc;
+    if (p->per_set) return RT_OK;                // (post_up_set per rate set; the caller packs per set)
     if (p->s->part) {
-        // every tile under the tables of its own set, as rt_step_partitioned launches the batch;
-        // the outputs are the twin's
-        const rt_rate_sets &r = p->m->multi;
-        rt_prune_view v;
-        v.P = r.d_P; v.Pfrag = r.d_Pfrag; v.Pquad = r.d_Pquad; v.Pcol = r.d_Pcol;
-        v.loglik = x->d_loglik; v.status = x->d_status; v.partial = x->d_partial;
-        v.granule_set = p->s->part->d_granule_set;
-        v.frag_stride = r.frag_stride; v.pcol_stride = r.pcol_stride;
+        // every tile under the tables of its own set, as rt_step_partitioned launches the batch
         if (x->nblocks * 16 != p->s->part->padded) {         // (one granule_set entry per tile)
             rt_set_error("%s: the twin's tiles do not match the batch's plan", p->who);
-            rc = RT_ERR_INVALID;
-        } else {
-            rc = rt_launch_prune(p->m, x, false, false, &v);
+            return RT_ERR_INVALID;
         }
-    } else {
-        rc = rt_launch_prune(p->m, x, false);
+        return post_up_set(p, 0, p->s->part->d_granule_set);
     }
+    x->d_Lout = p->d_L;
+    x->d_Mout = p->d_M;
+    const int rc = rt_launch_prune(p->m, x, false);
     x->d_Lout = x->d_Mout = nullptr;
     RT_TRY(rc);
-    if (pack_pt && !p->s->part)                  // (a partitioned batch: the caller packs per set)
+    if (pack_pt)
         RT_TRY(rt_launch_pack_pt(p->ctx, (int)p->n, p->NT, p->KP, p->nops, p->d_ptab, p->m->d_P,
                                  p->d_PT));
     return RT_OK;
@@ -281,11 +296,12 @@ __device__ __forceinline__ void lane_up(int nnodes, long nsites, long site, cons
     }
 }
 
-// the root: D = w L / sum_states(w L), stored and in d; true where the sum is not positive (D = 0)
+// the root: D = w L / sum_states(w L), stored and in d; true where the sum is not positive (D = 0);
+// tot (or null): the sum itself, the site's likelihood
 template <int N>
 __device__ __forceinline__ bool lane_root(long nsites, long site, const double *root_w,
                                  const double *Larr, double *Darr,
-                                 double (&d)[N])
+                                 double (&d)[N], double *tot_out = nullptr)
 {
     double wl[N], tot = 0.0;
 #pragma unroll
@@ -294,6 +310,7 @@ __device__ __forceinline__ bool lane_root(long nsites, long site, const double *
         tot += wl[s];
     }
     const bool zero = !(tot > 0.0);
+    if (tot_out) *tot_out = tot;
 #pragma unroll
     for (int s = 0; s < N; ++s) {
         d[s] = zero ? 0.0 : wl[s] / tot;

@@ -165,6 +165,37 @@ def check_branch_coefs_partitioned(coefs, nstates, nsets):
     return np.ascontiguousarray(E), True
 
 
+# TreeModel.branch_expectations_mixture: values [nsites, nnodes, ncoefs] (or None) and edge_sums
+# [nnodes, ncoefs] as BranchExpectations, under the site-class mixture over the K rate sets;
+# set_edge_sums [K, nnodes, ncoefs] the posterior- and site-weighted sums per class (edge_sums is
+# their sum in set order), class_posteriors [nsites, K], class_sums [K] = sum_i w_i posterior,
+# log_likelihoods [nsites] (-inf where no class is live), status int32[nsites]
+MixtureBranchExpectations = collections.namedtuple(
+    'MixtureBranchExpectations',
+    'values edge_sums set_edge_sums class_posteriors class_sums log_likelihoods status')
+
+
+def rate_parameter_coefs(Q, dQ):
+    """The coefficient matrix E for which branch_expectations (and its partitioned and mixture
+    forms) return d log L_i / d theta on each branch, given the rate matrix Q and dQ = dQ / d
+    theta: the direction C = E * Q off the diagonal, E on it, must be dQ, so E[c][d] =
+    dQ[c][d] / Q[c][d] where Q[c][d] != 0 (0 elsewhere) and E[c][c] = dQ[c][c].  ValueError where
+    dQ is non-zero off the diagonal at an entry where Q is zero: no E gives that direction."""
+    Q = np.asarray(Q, dtype=np.float64)
+    dQ = np.asarray(dQ, dtype=np.float64)
+    if Q.ndim != 2 or Q.shape[0] != Q.shape[1] or dQ.shape != Q.shape:
+        raise ValueError('Q and dQ must be square matrices of one shape, not %s and %s'
+                         % (Q.shape, dQ.shape))
+    off = ~np.eye(Q.shape[0], dtype=bool)
+    if ((dQ != 0) & (Q == 0) & off).any():
+        raise ValueError('dQ is non-zero where Q is zero: the direction is not E * Q for any E')
+    E = np.zeros_like(Q)
+    live = off & (Q != 0)
+    E[live] = dQ[live] / Q[live]
+    np.fill_diagonal(E, np.diag(dQ))
+    return E
+
+
 def partition_chain_rule(grad, rates, tau):
     """The gradient of TreeModel.branch_length_gradient_partitioned, grad[k, v] = d/d t[k][v],
     under the usual parametrisation t[k][v] = rates[k] * tau[v] -> (d/d tau f64[nnodes],
@@ -669,6 +700,7 @@ class SiteBatch(object):
         # int32[nsites], and the number of sets; None / 0 for an ordinary batch
         self.site_sets = site_sets
         self.nsets = nsets
+        self._weights = None      # what set_weights gave last (None: every site counts once)
         # the C object refers to its model: when both die in one garbage-collection cycle
         # (a traceback kept them alive) the model may be finalised first, so the model closes
         # its batches before it goes
@@ -704,11 +736,13 @@ class SiteBatch(object):
         None = every site counts once."""
         if weights is None:
             _lib.check(_lib.lib().rt_sites_set_weights(self._h, None))
+            self._weights = None
             return self
         w = _f64(weights)
         if w.shape != (self.nsites,):
             raise ValueError('one weight per site expected')
         _lib.check(_lib.lib().rt_sites_set_weights(self._h, _ptr(w, c_double)))
+        self._weights = w.copy()
         return self
 
     def _root_likelihoods(self, nstates):
@@ -1242,6 +1276,102 @@ class TreeModel(object):
         live[:, 0] = False
         grad[live] = sums[:, :, 0][live] / tk[live]
         return grad
+
+    def branch_expectations_mixture(self, batch, coefs, class_weights, per_site=True,
+                                    recompute_transitions=False):
+        """rt_sites_branch_expectations_mixture: branch_expectations of an ordinary batch under
+        the site-class mixture over the K rate sets of set_rate_sets with the class weights c
+        (check_class_weights): every site under every class, weighted by the class posteriors
+        post[i, k] = c_k L_ik / sum_j c_j L_ij.  coefs: one (n, n) array, a (C, n, n) sequence
+        shared by all classes, or (K, C, n, n) with class k's matrices at [k]
+        (check_branch_coefs_partitioned).  Returns a MixtureBranchExpectations tuple: values[i,
+        v, c] = sum_k post[i, k] x_k[i, v, c] with x_k what branch_expectations gives under set k
+        (None with per_site=False: the array never leaves the device), edge_sums,
+        set_edge_sums[k, v, c] = sum_i w_i post[i, k] x_k[i, v, c], class_posteriors,
+        class_sums[k] = sum_i w_i post[i, k], log_likelihoods[i] = log sum_k c_k L_ik, status.
+        A class with c_k = 0 or L_ik = 0 is skipped at that site.  No earlier step_multi is
+        needed; nothing the batch or the model holds changes."""
+        K = int(getattr(self, '_nsets', 0) or 0)
+        if K < 1:
+            raise ValueError('set_rate_sets has not been called')
+        if batch.site_sets is not None:
+            raise ValueError('branch_expectations_mixture takes an ordinary batch (a batch '
+                             'uploaded with site_sets: branch_expectations_partitioned)')
+        c = check_class_weights(class_weights, K)
+        E, per_set = check_branch_coefs_partitioned(coefs, self.nstates, K)
+        C = E.shape[1] if per_set else E.shape[0]
+        N, S = self.tree.nnodes, batch.nsites
+        values = np.zeros((S, N, C)) if per_site else None
+        edge_sums = np.zeros((N, C))
+        set_sums = np.zeros((K, N, C))
+        post = np.zeros((S, K))
+        class_sums = np.zeros(K)
+        ll = np.zeros(S)
+        status = np.zeros(S, dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_branch_expectations_mixture(
+            self._h, batch._h, 1 if recompute_transitions else 0, _ptr(c, c_double), C,
+            1 if per_set else 0, _ptr(E, c_double),
+            None if values is None else _ptr(values, c_double), _ptr(edge_sums, c_double),
+            _ptr(set_sums, c_double), _ptr(post, c_double), _ptr(class_sums, c_double),
+            _ptr(ll, c_double), _ptr(status, c_int32)))
+        return MixtureBranchExpectations(values, edge_sums, set_sums, post, class_sums, ll, status)
+
+    def class_posteriors(self, batch, class_weights, recompute_transitions=False):
+        """(posteriors f64[nsites, K], log_likelihoods f64[nsites]) of the site-class mixture:
+        post[i, k] = c_k L_ik / sum_j c_j L_ij, the empirical-Bayes classification of the sites
+        (a row of zeros and -inf where no class is live).  This is branch_expectations_mixture
+        with one identity coefficient matrix, the cheapest there is, and its sums left on the
+        device: the call still costs a full expectation pass (K upward and downward passes and
+        the derivative of every edge of every set)."""
+        K = int(getattr(self, '_nsets', 0) or 0)
+        if K < 1:
+            raise ValueError('set_rate_sets has not been called')
+        if batch.site_sets is not None:
+            raise ValueError('class_posteriors takes an ordinary batch')
+        c = check_class_weights(class_weights, K)
+        E = np.ascontiguousarray(np.eye(self.nstates)[None])
+        post = np.zeros((batch.nsites, K))
+        ll = np.zeros(batch.nsites)
+        _lib.check(_lib.lib().rt_sites_branch_expectations_mixture(
+            self._h, batch._h, 1 if recompute_transitions else 0, _ptr(c, c_double), 1, 0,
+            _ptr(E, c_double), None, None, None, _ptr(post, c_double), None, _ptr(ll, c_double),
+            None))
+        return post, ll
+
+    def branch_length_gradient_mixture(self, batch, class_weights, recompute_transitions=False):
+        """The analytic gradient of f = sum_i w_i log sum_k c_k L_ik from ONE
+        branch_expectations_mixture call with per-class coefficients (ones off the diagonal,
+        diag(Q[k]) on it: class k's direction is Q[k] itself) -> (g_t f64[K, nnodes], g_c
+        f64[K], total): g_t[k, v] = d f / d t[k][v] = set_edge_sums[k, v, 0] / t[k][v] (0 at
+        the root), g_c[k] = d f / d c_k = class_sums[k] / c_k (0 where c_k == 0), total = f over
+        the sites with a live class.  ValueError for several rate matrices per set (no single E
+        has every edge's diag(Q)) and for a resident t[k][v] == 0 below the root (the sum is
+        t times the derivative: it says nothing there)."""
+        rates = getattr(self, '_rate_sets', None)
+        if rates is None:
+            raise ValueError('set_rate_sets has not been called')
+        Q, t = rates
+        if Q.shape[1] != 1:
+            raise ValueError('branch_length_gradient_mixture needs one rate matrix per set for '
+                             'all edges (%d here): the coefficient matrix of a set is shared '
+                             'by all its edges' % Q.shape[1])
+        if (t[:, 1:] == 0).any():
+            raise ValueError('a resident branch length t[k][v] is 0: the edge sum is t[k][v] '
+                             'times the derivative and gives no gradient there')
+        K, n = Q.shape[0], self.nstates
+        c = check_class_weights(class_weights, K)
+        E = np.ones((K, 1, n, n))
+        for k in range(K):
+            np.fill_diagonal(E[k, 0], np.diag(Q[k, 0]))
+        res = self.branch_expectations_mixture(batch, E, c, per_site=False,
+                                               recompute_transitions=recompute_transitions)
+        g_t = np.zeros((K, self.tree.nnodes))
+        g_t[:, 1:] = res.set_edge_sums[:, 1:, 0] / t[:, 1:]
+        g_c = np.zeros(K)
+        g_c[c > 0] = res.class_sums[c > 0] / c[c > 0]
+        w = np.ones(batch.nsites) if batch._weights is None else batch._weights
+        live = np.isfinite(res.log_likelihoods)
+        return g_t, g_c, float(np.sum(w[live] * res.log_likelihoods[live]))
 
     def branch_lengths(self):
         """The branch lengths of the last set_rates / set_rates_spectral as the device holds
