@@ -542,6 +542,47 @@ int rt_sites_sample_states(rt_model *model, rt_sites *sites, int recompute_trans
 /* draws that share one read of L in rt_sites_sample_states for a tree of nnodes nodes (n > 4):
  * 16 at most, fewer as the tree grows, 1 from 1025 nodes on; 0 beyond RT_MAX_SAMPLE_NODES       */
 int rt_sample_states_draw_block(int64_t nnodes);
+/* The joint maximum-likelihood reconstruction (Pupko, Pe'er, Shamir & Graur 2000) of every site of
+ * a RESIDENT batch: the single most probable assignment of a state to every node, with its
+ * probability.  The quantities for site i:
+ *   o_v  the observation vector of node v, all ones where unobserved (dense observations are used
+ *        as values);
+ *   w    the root weights (rt_model_set_root_distn), or ones if none was set;
+ *   P_v  the model's transition matrix of edge parent(v) -> v.
+ * The probability of an assignment x of a state to every node is
+ *   J(x) = w[x_root] * prod_v o_v[x_v] * prod_{v != root} P_v[x_parent(v)][x_v];
+ * negative or NaN factors count as 0, as in rt_sites_sample_states.  The recursion:
+ *   L_v(b) = o_v(b) * prod_{c child of v} M_c(b)
+ *   M_c(a) = max_b P_c(a, b) * L_c(b)
+ * The reconstruction, ties ALWAYS to the lowest state index: x_root is the lowest a that maximises
+ * w(a) * L_root(a); then, walking in preorder, x_v is the lowest b that maximises
+ * P_v(x_parent, b) * L_v(b).
+ *   states[i][v]  uint8[nsites][nnodes], v the preorder index
+ *   log_joint[i]  (optional) log J(x*)
+ *   status[i]     (optional) 0; RT_SITE_ZERO_PROB for a site whose maximum is not positive and
+ *                 finite: every state of the site is 255 and log_joint is -inf.  (2: a live parent
+ *                 state without a child state of positive weight, that node and its descendants
+ *                 are 255; impossible with a consistent L.)
+ * Scaling: every node's L_v is multiplied per site by a power of two (the one that brings its
+ * largest entry into [0.5, 1)); the multiplication is exact, so it never changes an arg-max.  The
+ * exponents are summed per site over all nodes and log_joint = log(root maximum) + E ln 2: the
+ * result is what f64 arithmetic with an unbounded exponent would give, with one deviation: entries
+ * more than about 2^1000 below the largest entry of their node's vector (before the scale: the
+ * products of the children's scaled messages) may flush to zero.  Posterior probability of the
+ * reconstruction: exp(log_joint[i] - log-likelihood of site i).
+ * A site's result depends on the site alone: not on the other sites of its tile or batch, not on
+ * the launch shape.  Batches and trees: those of rt_sites_sample_states (2..128 states; dense, state
+ * and mask uploads; observed internal nodes; per-edge P).  RT_ERR_INVALID: states NULL, a batch of
+ * another model, no transitions yet.  RT_ERR_UNSUPPORTED: what rt_sites_sample_states refuses (a
+ * partitioned batch, a "rescale" batch, a generic-kernel batch, a tree deeper than the fast kernels
+ * take, nnodes < 2), more than 96 GB of scratch, and for n > 4 a tree of more than
+ * RT_MAX_SAMPLE_NODES nodes (the states of a tile live in LDS).  Synchronous; only states,
+ * log_joint and status cross PCIe; nothing of the batch is written: it keeps its kernel,
+ * log-likelihoods, status, totals and multi results.                                            */
+int rt_sites_map_states(rt_model *model, rt_sites *sites, int recompute_transitions,
+            uint8_t *states      /* [nsites][nnodes], preorder index */,
+            double  *log_joint   /* [nsites] or NULL */,
+            int32_t *status      /* [nsites] or NULL */);
 /* Stochastic mappings (Nielsen 2002; the uniformization sampler of Hobolth & Stone 2009) of every
  * branch for every site of a RESIDENT batch: ndraws independent, exact draws of a substitution
  * history given the observations, each reduced on the device to the linear statistics of
@@ -743,8 +784,8 @@ const char *rt_sites_multi_kernel_name(const rt_sites *sites);
  * Everything else refuses a partitioned batch with RT_ERR_UNSUPPORTED and leaves it untouched:
  *   rt_prune, rt_step, rt_step_multi, rt_sites_clone, rt_expect_step, rt_sites_posteriors,
  *   rt_sites_branch_expectations, rt_sites_branch_profiles, rt_sites_sample_states,
- *   rt_sites_sample_mappings, rt_sites_branch_expectations_mixture, rt_allreduce_totals,
- *   rt_allreduce_totals_group.
+ *   rt_sites_map_states, rt_sites_sample_mappings, rt_sites_branch_expectations_mixture,
+ *   rt_allreduce_totals, rt_allreduce_totals_group.
  *                                                               */
 int rt_partition_plan(const int32_t *site_set, int64_t nsites, int64_t nsets, int64_t granule,
             int64_t capacity, int64_t *order, int64_t *slot_of_site, uint8_t *is_pad,

@@ -142,6 +142,7 @@ SIGNATURES = {
     'rt_sites_sample_states': (c_int, [c_void_p, c_void_p, c_int, ctypes.c_uint64,
                                        ctypes.c_uint64, c_int64, POINTER(c_ubyte), _p_i32]),
     'rt_sample_states_draw_block': (c_int, [c_int64]),
+    'rt_sites_map_states': (c_int, [c_void_p, c_void_p, c_int, POINTER(c_ubyte), _p_f64, _p_i32]),
     'rt_sites_sample_mappings': (c_int, [c_void_p, c_void_p, c_int, ctypes.c_uint64,
                                          ctypes.c_uint64, c_int64, c_int64, _p_f64,
                                          POINTER(c_ubyte), _p_f64, _p_i32, _p_f64, _p_i32]),

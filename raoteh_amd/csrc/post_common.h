@@ -110,8 +110,9 @@ inline int post_open(post_pass *p, const char *who, rt_model *m, rt_sites *s, bo
 
 // the batches these passes take, and the common pieces of the scratch.  with_D: M, D and the P^T
 // fragments (8 bytes in the lane layout) as well; else L alone -- and a buffer for M where the
-// upward kernel's store variant writes it unconditionally (n > 4).
-inline int post_layout(post_pass *p, bool with_D)
+// upward kernel's store variant writes it unconditionally (n > 4).  with_M = false: a call that
+// makes its upward pass itself and stores no M (map_states.hip) reserves none.
+inline int post_layout(post_pass *p, bool with_D, bool with_M = true)
 {
     const rt_model *m = p->m;
     const rt_sites *s = p->s;
@@ -129,7 +130,7 @@ inline int post_layout(post_pass *p, bool with_D)
                                : (size_t)p->nops * s->nblocks * p->NT * 256 * 8;
     p->with_D = with_D;
     p->o_L = p->plan.take(arr);
-    p->o_M = p->plan.take(with_D || !p->lane ? arr : 8);
+    if (with_M) p->o_M = p->plan.take(with_D || !p->lane ? arr : 8);
     if (with_D) p->o_D = p->plan.take(arr);
     p->o_status = p->plan.take((size_t)p->nsites * 4);
     p->o_steps = p->plan.take((size_t)std::max<int64_t>(p->nops, N) * 16);

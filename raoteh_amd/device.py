@@ -25,7 +25,8 @@ from . import _lib
 from ._tree import TreeArrays
 
 __all__ = ['check_rate_sets', 'check_site_sets', 'Context', 'get_context', 'TreeModel', 'SiteBatch', 'device_count', 'Posteriors',
-           'states_to_mask', 'BranchExpectations', 'check_branch_coefs', 'SampledStates', 'SampledMappings']
+           'states_to_mask', 'BranchExpectations', 'check_branch_coefs', 'SampledStates', 'SampledMappings',
+           'MapStates']
 
 # At interpreter shutdown objects are finalised in arbitrary order (a model
 # after its context, say); the process is going away, so skip the native
@@ -98,6 +99,13 @@ BranchExpectations = collections.namedtuple('BranchExpectations', 'values edge_s
 # (255 = no state), status int32[nsites] (0 ok, 1 zero likelihood: the site's draws are all 255,
 # 2 a node without a state of positive weight)
 SampledStates = collections.namedtuple('SampledStates', 'states status nodes')
+
+
+# TreeModel.map_states: the joint maximum-likelihood reconstruction, states uint8[nsites, nnodes]
+# indexed by the preorder `nodes` (255 = no state), log_joint f64[nsites] the log-probability of
+# the reconstruction with the observations, status int32[nsites] (0 ok, 1 zero likelihood: the
+# site's states are all 255 and log_joint is -inf)
+MapStates = collections.namedtuple('MapStates', 'states log_joint status nodes')
 
 
 # TreeModel.sample_mappings: states as SampledStates; values f64[ndraws, nsites, nnodes, ncoefs]
@@ -1147,6 +1155,37 @@ class TreeModel(object):
             self._h, batch._h, 1 if recompute_transitions else 0, seed, first_draw, ndraws,
             _ptr(states, ctypes.c_ubyte), _ptr(status, c_int32)))
         return SampledStates(states, status, nodes)
+
+    def map_states(self, batch, recompute_transitions=False):
+        """rt_sites_map_states: the joint maximum-likelihood reconstruction (Pupko et al. 2000)
+        of every site of the resident batch: the one assignment x of a state to every node that
+        maximises J(x) = w[x_root] prod_v o_v[x_v] prod_{v != root} P_v[x_parent(v), x_v] (o_v the
+        observation of v, w the root weights), ties always to the lowest state index, and
+        log_joint = log J(x).  It is not the arg-max of the marginals of posteriors(...,
+        marginals=True), which need not even be a possible history.  The posterior probability of
+        the reconstruction of site i is exp(log_joint[i] - log-likelihood of site i), the second
+        from log_likelihoods(batch).  Returns a MapStates tuple."""
+        n = self.nstates
+        ta = self.tree
+        N, S = ta.nnodes, batch.nsites
+        nodes = list(ta.preorder_nodes)
+        states = np.full((S, N), 255, dtype=np.uint8)
+        log_joint = np.full(S, -np.inf)
+        status = np.zeros(S, dtype=np.int32)
+        if N == 1:
+            # one node: the lowest state that maximises the root weights times the observation
+            w = self._root_weights(batch)
+            w = np.where(w > 0, w, 0.0)
+            best = w.max(axis=1)
+            ok = (best > 0) & np.isfinite(best)
+            status[~ok] = _lib.RT_SITE_ZERO_PROB
+            states[ok, 0] = np.argmax(w[ok], axis=1)
+            log_joint[ok] = np.log(best[ok])
+            return MapStates(states, log_joint, status, nodes)
+        _lib.check(_lib.lib().rt_sites_map_states(
+            self._h, batch._h, 1 if recompute_transitions else 0,
+            _ptr(states, ctypes.c_ubyte), _ptr(log_joint, c_double), _ptr(status, c_int32)))
+        return MapStates(states, log_joint, status, nodes)
 
     def sample_mappings(self, batch, coefs, ndraws=1, seed=0, first_draw=0, per_draw=True,
                         recompute_transitions=False):
