@@ -502,6 +502,67 @@ int rt_sites_branch_profiles(rt_model *model, rt_sites *sites, int recompute_tra
 /* The branch lengths of the last rt_model_set_rates / rt_model_set_rates_spectral, f64[nnodes] in
  * preorder (0 at the root).  RT_ERR_INVALID before either call.                               */
 int rt_model_get_branch_lengths(rt_model *model, double *t);
+/* The nearest-neighbour interchanges (NNI) of the model's tree.  Nodes are preorder indices.  A
+ * move is a triple (v, c, s): v a non-root node with at least one child, c a child of v, s a
+ * sibling of v (another child of p = parent(v)).  The move exchanges the subtrees of c and s: the
+ * edges v->c, p->s become v->s, p->c, and every moved subtree keeps its own edge -- the length,
+ * rate matrix and transition matrix of c and of s go with the node below the edge.  The list is
+ * ordered by v ascending, then c in the CSR child order of v, then s in the CSR child order of p:
+ * a pure function of the topology, nmoves = sum_v #children(v) #siblings(v) (0 for a star or a
+ * path).
+ * The definition is ROOTED, because rate matrices need not be reversible.  One case to know:
+ * where p is a root with exactly the two children v and s, the moved tree has the same UNROOTED
+ * topology as before: the edges p->v and p->s are one edge of the unrooted tree, of length
+ * t_v + t_s, and the move only redistributes lengths along it (c now hangs t_c + t_v from v, and
+ * v is t_s from s).  Under a stationary reversible model the moved tree's likelihood is that of
+ * the unmoved tree at those lengths -- the same as before where t_v = 0 -- so a caller with such
+ * a model learns nothing about the topology from those moves and can skip them.
+ * Host only.  moves int32[capacity][3]; moves == NULL asks for the count alone; RT_ERR_INVALID
+ * when capacity < *nmoves (the count is still returned).                                       */
+int rt_model_nni_moves(const rt_model *model, int32_t *moves, int64_t capacity, int64_t *nmoves);
+/* The same list from the tree alone, children CSR in preorder indices as for rt_model_create:
+ * for a caller that has no model (and no device) yet.                                          */
+int rt_tree_nni_moves(int64_t nnodes, const int64_t *tree_csr_indices, const int64_t *tree_csr_indptr,
+            int32_t *moves, int64_t capacity, int64_t *nmoves);
+/* Every NNI neighbour of the tree scored on a RESIDENT batch, without one model build, upload and
+ * rt_step per candidate.  For site i, move mv of rt_model_nni_moves and trial length g of the edge
+ * above v:
+ *   values[i][mv][g] = log L_i(tree after mv, t_v -> lengths[v][g]) - log L_i
+ *                                                                  f64[nsites][nmoves][npoints]
+ *                      -inf where a live site has likelihood 0 on the moved tree
+ *   sums[mv][g]      = sum_i w_i values[i][mv][g]                  f64[nmoves][npoints]
+ *                      (w: rt_sites_set_weights, default 1; reduced on the device, fixed order;
+ *                      a site of weight 0 adds nothing, even where its value is -inf)
+ *   status[i]        : a site of zero likelihood has RT_SITE_ZERO_PROB, its values are 0 and it
+ *                      adds nothing to sums
+ * lengths == NULL: npoints must be 1 and the edge above v keeps its resident matrix (the plain
+ * swap); no exponential runs, so a model whose transitions were set directly is taken too.
+ * Otherwise lengths f64[nnodes][npoints] as for rt_sites_branch_profiles: 1..RT_MAX_PROFILE_POINTS
+ * trial lengths per node, finite and >= 0, shared by all moves about v; the rows of nodes that
+ * have no move (the root's among them) are ignored.  The (nnodes - 1) npoints exponentials are the
+ * one launch of rt_sites_branch_profiles, from rt_model_set_rates (per-edge rate matrices
+ * included) or rt_model_set_rates_spectral (n <= 64).
+ * With L_w, M_w = P_w L_w of the stored upward pass, up_p the message into p from above (the root
+ * weights at the root), W[a] = up_p[a] obs_p[a] prod_{w child of p, not v, s} M_w[a] and
+ * L'_v[b] = obs_v[b] prod_{w child of v, not c} M_w[b] M_s[b]:
+ *   L_i(mv, tau) = sum_b L'_v[b] (P_v(tau)^T (W o M_c))[b].
+ * Nothing is divided: the `up` vectors come from a downward pass of their own, normalised once at
+ * the root by 1 / L_i, so the result is exact where transition matrices or observations have
+ * zeros, and a resident t_v = 0 is nothing special (no NaN rows, unlike rt_sites_branch_profiles).
+ * values, sums and status may each be NULL; only what is given crosses PCIe.  Every batch
+ * rt_sites_posteriors takes.  nmoves == 0: RT_OK, and no output but status is touched.  Where
+ * the result of all moves would not fit the scratch the moves go through the device in chunks.
+ * RT_ERR_INVALID: npoints out of range (or not 1 without lengths), a negative or non-finite
+ * length in a row that counts, lengths on a model without rates (or whose transitions were set
+ * directly after them, with recompute_transitions == 0), a batch of another model.
+ * RT_ERR_SINGULAR: an exponential failed; nothing returned is usable then.  RT_ERR_UNSUPPORTED:
+ * a partitioned batch, a "rescale" batch, a batch of the generic kernel, a tree deeper than the
+ * fast kernels take, nnodes < 2, more than 96 GB of scratch.  Synchronous; the model keeps its
+ * transitions and the batch its kernel, log-likelihoods, status and totals; two calls return the
+ * same bits.                                                                                   */
+int rt_sites_nni_scores(rt_model *model, rt_sites *sites, int recompute_transitions,
+            int64_t npoints, const double *lengths, double *values, double *sums,
+            int32_t *status);
 /* _sample_mcy_dense.resample_states (_sample_mcy_dense.py:23-69, through
  * _sample_mc0_dense.resample_states, _sample_mc0_dense.py:20-98) for every site of a RESIDENT
  * batch: ndraws joint draws of a state for every node from the posterior given the observations.

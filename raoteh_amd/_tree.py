@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ['TreeArrays', 'marshal_tree', 'check_square_dense']
+__all__ = ['TreeArrays', 'marshal_tree', 'check_square_dense', 'nni_apply']
 
 
 def check_square_dense(M):
@@ -122,3 +122,38 @@ class TreeArrays(object):
 
 def marshal_tree(T, root):
     return TreeArrays(T, root)
+
+
+def nni_apply(T, root, v, c, s):
+    """The tree after the nearest-neighbour interchange (v, c, s) of rt_model_nni_moves, on node
+    LABELS of the networkx tree T rooted at `root`: c a child of v, s a sibling of v; the
+    subtrees of c and s change places, and every edge's attributes follow the node below the
+    edge (the data of v-c becomes that of p-c, p = parent(v); that of p-s becomes that of v-s).
+    A new graph of T's class with T's node and graph attributes; s takes the place of c among
+    the children of v and c that of s among the children of p, every other child order stays
+    (so the preorder indices of the untouched nodes before v do, too).  ValueError for a triple
+    that is not a move."""
+    ta = TreeArrays(T, root)
+    idx = ta.node_to_index
+    if v not in idx or c not in idx or s not in idx:
+        raise ValueError('(%r, %r, %r): not nodes of the tree' % (v, c, s))
+    iv, ic, is_ = idx[v], idx[c], idx[s]
+    if iv == 0:
+        raise ValueError('%r is the root: no edge above it to move about' % (v,))
+    ip = int(ta.parent[iv])
+    if ta.parent[ic] != iv:
+        raise ValueError('%r is not a child of %r' % (c, v))
+    if is_ == iv or ta.parent[is_] != ip:
+        raise ValueError('%r is not a sibling of %r' % (s, v))
+    swap = {(iv, ic): is_, (ip, is_): ic}
+    out = T.__class__()
+    out.graph.update(T.graph)
+    out.add_nodes_from((x, dict(T.nodes[x])) for x in ta.preorder_nodes)
+    stack = [0]
+    while stack:
+        a = stack.pop()
+        kids = [swap.get((a, int(b)), int(b)) for b in ta.indices[ta.indptr[a]:ta.indptr[a + 1]]]
+        for b in kids:
+            out.add_edge(ta.preorder_nodes[a], ta.preorder_nodes[b], **dict(ta.edge_data[b]))
+        stack.extend(reversed(kids))
+    return out

@@ -227,34 +227,12 @@ profile_sums_kernel(int np, long nsites, const double *__restrict__ values,
     if (tid == 0) sums[row] = (v > 0 && tlen[v] == 0.0) ? __builtin_nan("") : part[0];
 }
 
-// [row][site] -> [site][row] for the caller's per-site array, 32 x 32 tiles through LDS
-__global__ void __launch_bounds__(256)
-profile_transpose_kernel(long nrows, long nsites, const double *__restrict__ in,
-                         double *__restrict__ outT)
-{
-    __shared__ double tile[32][33];
-    const long s0 = (long)blockIdx.x * 32, r0 = (long)blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int k = ty; k < 32; k += 8)
-        if (r0 + k < nrows && s0 + tx < nsites) tile[k][tx] = in[(size_t)(r0 + k) * nsites + s0 + tx];
-    __syncthreads();
-    for (int k = ty; k < 32; k += 8)
-        if (s0 + k < nsites && r0 + tx < nrows) outT[(size_t)(s0 + k) * nrows + r0 + tx] = tile[tx][k];
-}
-
-// the model keeps the branch lengths of the last rt_model_set_rates / _spectral on the host
-inline bool model_has_rates(const rt_model *m)
-{
-    return (m->d_Q || m->spectral) && (int64_t)m->h_t.size() == m->nnodes &&
-           (int64_t)m->h_qidx.size() == m->nnodes;
-}
-
 }  // namespace
 
 extern "C" int rt_model_get_branch_lengths(rt_model *m, double *t)
 {
     RT_REQUIRE(m && t, "null pointer");
-    RT_REQUIRE(model_has_rates(m),
+    RT_REQUIRE(post_model_has_rates(m),
                "rt_model_get_branch_lengths: no rates have been set (rt_model_set_rates or "
                "rt_model_set_rates_spectral)");
     std::copy(m->h_t.begin(), m->h_t.end(), t);
@@ -267,83 +245,36 @@ extern "C" int rt_sites_branch_profiles(rt_model *m, rt_sites *s, int recompute_
 {
     post_pass p;                                 // (alive until the synchronisation below)
     RT_TRY(post_open(&p, "rt_sites_branch_profiles", m, s));
-    RT_REQUIRE(model_has_rates(m),
-               "rt_sites_branch_profiles: no rates have been set (rt_model_set_rates or "
-               "rt_model_set_rates_spectral; a model with transitions set directly has no rate "
-               "matrix to exponentiate at another length)");
-    RT_REQUIRE(m->rates_current || recompute_transitions,
-               "rt_sites_branch_profiles: the transitions were set directly after the rates "
-               "(rt_model_set_transitions): the resident rates and lengths no longer describe them; "
-               "set the rates again or pass recompute_transitions");
-    RT_REQUIRE(lengths, "rt_sites_branch_profiles: lengths is NULL");
-    RT_REQUIRE(npoints >= 1 && npoints <= RT_MAX_PROFILE_POINTS,
-               "rt_sites_branch_profiles: 1..%d grid points per branch (%lld here)",
-               RT_MAX_PROFILE_POINTS, (long long)npoints);
+    RT_TRY(post_grid_check(&p, recompute_transitions, npoints, lengths));
     const int64_t n = p.n, N = p.N, nsites = p.nsites;
     const int np = (int)npoints;
-    for (int64_t v = 1; v < N; ++v)
-        for (int g = 0; g < np; ++g) {
-            const double x = lengths[v * np + g];
-            RT_REQUIRE(std::isfinite(x) && x >= 0.0,
-                       "rt_sites_branch_profiles: length %d of node %lld is negative or not finite",
-                       g, (long long)v);
-        }
     RT_TRY(post_layout(&p, true));
-    if (m->spectral ? n > 64 : n > RT_MAX_EXPM_STATES) {
-        rt_set_error("rt_sites_branch_profiles: n=%lld is beyond what the model's exponential takes",
-                     (long long)n);
-        return RT_ERR_UNSUPPORTED;
-    }
-    rt_ctx *ctx = p.ctx;
-    const size_t nn = (size_t)n * n, rows = (size_t)N * np, cnt = (size_t)np * N;
+    const size_t rows = (size_t)N * np;
     // scratch: L, M, D of every node and site (post_layout), the result, the grid matrices, their
-    // fragments and the tiled arguments of the exponential
-    const size_t tab = (size_t)p.nops * p.NT * p.KP * 128 * 8;
+    // fragments and the tiled arguments of the exponential (post_grid)
     post_plan &plan = p.plan;
+    post_grid grid;                              // (alive until the synchronisation below)
     const size_t o_val = plan.take(rows * nsites * 8);
     const size_t o_valT = plan.take(values ? rows * nsites * 8 : 8);
     const size_t o_sum = plan.take(rows * 8);
-    const size_t o_G = plan.take(cnt * nn * 8);
-    const size_t o_tau = plan.take(cnt * 8), o_qidx = plan.take(cnt * 4);
-    const size_t o_info = plan.take(cnt * 8);
-    const size_t o_GT = p.lane ? plan.take(8) : plan.take((size_t)np * tab);
+    RT_TRY(post_grid_take(&p, &grid, np));
     RT_TRY(post_begin(&p, recompute_transitions));
     hipStream_t st = p.st;
     unsigned char *base = p.base;
     double *d_val = (double *)(base + o_val), *d_valT = (double *)(base + o_valT);
-    double *d_sum = (double *)(base + o_sum), *d_G = (double *)(base + o_G);
-    double *d_tau = (double *)(base + o_tau);
-    int32_t *d_qidx = (int32_t *)(base + o_qidx);
-    int32_t *d_info = (int32_t *)(base + o_info);
+    double *d_sum = (double *)(base + o_sum);
     int *d_status = p.d_status;
-    // (host buffers of the asynchronous copies: alive until the synchronisation below)
-    std::vector<double> tau(cnt, 0.0);
-    std::vector<int32_t> qidx(cnt), internal((size_t)N, 0), info(2 * cnt, 0);
-    for (int g = 0; g < np; ++g)
-        for (int64_t v = 0; v < N; ++v) {
-            qidx[(size_t)g * N + v] = m->h_qidx[(size_t)v];      // (the root's: -1, a zero matrix)
-            if (v) tau[(size_t)g * N + v] = lengths[v * np + g];
-        }
+    std::vector<int32_t> internal((size_t)N, 0);
     for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
-    RT_HIP(hipMemcpyAsync(d_tau, tau.data(), cnt * 8, hipMemcpyHostToDevice, st));
-    RT_HIP(hipMemcpyAsync(d_qidx, qidx.data(), cnt * 4, hipMemcpyHostToDevice, st));
-    RT_HIP(hipMemsetAsync(d_info, 0, cnt * 8, st));
     // 1. the grid matrices: one launch of the route the model's own transitions take
-    if (m->spectral)
-        RT_TRY(rt_launch_spectral(ctx, n, (int64_t)cnt, m->d_spec, m->d_spec + 2 * nn, m->d_spec + nn,
-                                  m->spectral_has_D ? m->d_spec + 2 * nn + n : nullptr, d_qidx, d_tau,
-                                  d_G, d_info, nullptr, 0, nullptr));
-    else
-        RT_TRY(rt_launch_expm(ctx, n, (int64_t)cnt, m->d_Q, d_qidx, d_tau, d_G, d_info, nullptr, 0,
-                              nullptr));
-    RT_HIP(hipMemcpyAsync(info.data(), d_info, cnt * 8, hipMemcpyDeviceToHost, st));
+    RT_TRY(post_grid_launch(&p, &grid, lengths));
     RT_TRY(post_up(&p, internal.data(), true));
     if (p.lane) {
         const int *d_tab = p.d_ptab;
         RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
             hipLaunchKernelGGL((bp_lane_kernel<decltype(nv)::value>), dim3((unsigned)((nsites + 255) / 256)),
                                dim3(256), 0, st, (int)N, (long)nsites, (const double *)m->d_P,
-                               (const double *)d_G, np, d_tab, d_tab + N, (const void *)s->d_obs,
+                               (const double *)grid.d_G, np, d_tab, d_tab + N, (const void *)s->d_obs,
                                s->compact_states, (int)s->nobs, s->block_sites,
                                (const double *)m->d_root, (const double *)m->d_t, p.d_L, p.d_M, p.d_D,
                                d_val, d_status);
@@ -351,14 +282,11 @@ extern "C" int rt_sites_branch_profiles(rt_model *m, rt_sites *s, int recompute_
         }));
     } else {
         const rt_sites *x = p.x;
-        double *d_GT = (double *)(base + o_GT);
-        for (int g = 0; g < np; ++g)
-            RT_TRY(rt_launch_pack_pt(ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab, d_G + (size_t)g * N * nn,
-                                     d_GT + (size_t)g * (tab / 8)));
+        RT_TRY(post_grid_pack(&p, &grid));
         RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
             constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
             hipLaunchKernelGGL((bp_down_kernel<NT, KS>), dim3((unsigned)x->nblocks), dim3(64 * NT), 0, st,
-                               (const double *)p.d_PT, (const double *)d_GT, np, p.nops,
+                               (const double *)p.d_PT, (const double *)grid.d_GT, np, p.nops,
                                (const int4 *)p.d_steps, (const double *)p.d_L, (const double *)p.d_M,
                                p.d_D, (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
                                (const double *)m->d_t, (int)n, d_val, d_status, (long)x->nsites,
@@ -376,7 +304,7 @@ extern "C" int rt_sites_branch_profiles(rt_model *m, rt_sites *s, int recompute_
         RT_HIP(hipMemcpyAsync(sums, d_sum, rows * 8, hipMemcpyDeviceToHost, st));
     }
     if (values) {
-        hipLaunchKernelGGL(profile_transpose_kernel,
+        hipLaunchKernelGGL(post_transpose_kernel<32>,
                            dim3((unsigned)((nsites + 31) / 32), (unsigned)((rows + 31) / 32)), dim3(256),
                            0, st, (long)rows, (long)nsites, (const double *)d_val, d_valT);
         RT_HIP(hipGetLastError());
@@ -384,12 +312,6 @@ extern "C" int rt_sites_branch_profiles(rt_model *m, rt_sites *s, int recompute_
     }
     if (status) RT_HIP(hipMemcpyAsync(status, d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
     RT_HIP(hipStreamSynchronize(st));
-    // an exponential the kernel gave up on (tau Q not finite): its row holds nothing usable
-    for (size_t j = 0; j < cnt; ++j)
-        if (info[2 * j] < 0) {
-            rt_set_error("rt_sites_branch_profiles: expm failed for node %lld at length %g (a "
-                         "non-finite entry or norm of tau Q)", (long long)(j % (size_t)N), tau[j]);
-            return RT_ERR_SINGULAR;
-        }
+    RT_TRY(post_grid_result(&p, &grid));
     return RT_OK;
 }

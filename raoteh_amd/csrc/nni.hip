@@ -1,0 +1,578 @@
+// Every nearest-neighbour interchange of the model's tree scored on a RESIDENT batch
+// (rt_sites_nni_scores): for every site i, every move (v, c, s) -- the subtrees of a child c of v
+// and of a sibling s of v exchanged, each keeping its own edge -- and every trial length tau of
+// the edge above v,
+//     log L_i(tree after the move, t_v -> tau) - log L_i.
+//
+// With L_v, M_v = P_v L_v of every node from the stored upward pass, up_p the message into
+// p = parent(v) from above (root_w at the root) and
+//     W[a]    = up_p[a] obs_p[a] prod_{w child of p, w not in {v, s}} M_w[a]
+//     L'_v[b] = obs_v[b] prod_{w child of v, w != c} M_w[b] M_s[b]
+// the moved tree's likelihood is  sum_b L'_v[b] (P_v(tau)^T (W o M_c))[b].  Nothing is divided:
+// the posterior D_p is 0 wherever M_v or M_s is, yet after the move such a state of p may be live,
+// so the `up` vectors come from a downward pass of their own,
+//     up_v[b] = sum_a P_v[a][b] up_p[a] obs_p[a] prod_{w child of p, w != v} M_w[a],
+// normalised once at the root by 1 / L_i: everything after it is the ratio itself, exact where
+// transition matrices or observations have zeros and at a resident t_v = 0.  Here:
+//
+//   1. lengths given: P_v(tau) of every edge and grid point in ONE launch of the model's own
+//      exponential (post_grid, what rt_sites_branch_profiles runs); else the resident P_v;
+//   2. n > 4: the upward pass with L and M of every step stored, then nni_kernel, one workgroup of
+//      NT row-tile waves per 16-site tile: the `up` pass down the schedule, then per node v with
+//      moves and per move the staged W o M_c, per grid point one n x n by n x 16 matrix-pipe
+//      product dotted with L'_v and reduced over the states in a fixed order; the logs by all
+//      lanes at the end.  n <= 4: nni_lane_kernel, one lane per site;
+//   3. nni_sums_kernel: the site-weighted sums per (move, point) in a fixed order; then, if the
+//      per-site array is asked for, its transpose to [site][move][point].
+//
+// Steps 2 and 3 run per chunk of moves where the result of all moves would not fit the scratch.
+// Nothing of the batch or the model is written; two calls give the same bits.
+#include "common.h"
+#include "post_common.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <vector>
+
+namespace {
+
+constexpr int NNI_CHUNK = 8;                     // grid points between two barriers of nni_kernel
+constexpr size_t NNI_CHUNK_BYTES = (size_t)4 << 30;      // result bytes of one chunk of moves
+constexpr double NNI_SCRATCH_CAP = 96e9;         // (post_begin's)
+
+// the stored value: 0 at a site of zero likelihood, else the log of the ratio (-inf where it is
+// not positive)
+__device__ __forceinline__ double nni_value(double ratio, bool zero)
+{
+    if (zero) return 0.0;
+    return ratio > 0.0 ? log(ratio) : -__builtin_inf();
+}
+
+// The move tables, over slots j = 0 .. cnt - 1 (n > 4: schedule steps; n <= 4: preorder nodes):
+//   obs[j]          stream position of the slot's node, a leaf or an observed INTERNAL node (the
+//                   shared step table has the leaves' only), or -1
+//   cptr[j], cidx   the slots of its children in the CSR child order
+//   first[j]        the index of its first move: moves go by node ascending, then by child of the
+//                   node, then by sibling
+struct nni_tab {
+    const int *obs, *cptr, *first, *cidx;
+    __host__ __device__ nni_tab(const int *t, int cnt)
+        : obs(t), cptr(t + cnt), first(t + 2 * cnt + 1), cidx(t + 3 * cnt + 1) {}
+};
+
+// n > 4.  steps[i] = {node, step of the parent, stream position of an observed leaf or -1, 1 if
+// the node has children}; the root is the last step.  PfragT: [step] A fragments of the resident
+// P^T; GfragT: [point][step] those of P(tau)^T (PfragT itself for the plain swap, np = 1);
+// Uarr: the `up` vectors, laid out as L and M; out [move - mv0][point][site] for the moves
+// mv0 .. mv1 - 1.  The first chunk (mv0 == 0) makes the `up` pass, later ones find it in Uarr.
+// (NT = 7: four waves per SIMD asked for, as bp_down_kernel has them -- left alone KS = 28 takes
+// 130 VGPRs.  NT = 8 takes 130 .. 136 and runs three: held to 128 it spills to scratch.)
+template <int NT, int KS>
+__global__ void __launch_bounds__(64 * NT, NT == 7 ? 4 : 1)
+nni_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT, int np, int nops,
+           const int4 *__restrict__ steps, const int *__restrict__ tabp,
+           const double *__restrict__ Larr, const double *__restrict__ Marr,
+           double *__restrict__ Uarr, const double *__restrict__ obs, int K,
+           const double *__restrict__ root_w, int n, int mv0, int mv1, double *__restrict__ out,
+           int *__restrict__ status, long nsites, long nblocks)
+{
+    constexpr int KP = (KS + 1) / 2;
+    __shared__ double xb[NT * 4 * 64];
+    __shared__ double red[NT][16];
+    __shared__ double sums[2][NNI_CHUNK][NT][16];
+    const nni_tab tab(tabp, nops);
+    const int lane = threadIdx.x & 63;
+    const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long blk = blockIdx.x;
+    const long site = blk * 16 + (lane & 15);
+    const bool site_ok = site < nsites;
+    const bool writer = m == 0 && lane < 16 && site_ok;
+    bool live[4];                                // own rows that are states
+#pragma unroll
+    for (int r = 0; r < 4; ++r) live[r] = 16 * m + 4 * r + (lane >> 4) < n;
+    const size_t frag = ((size_t)m * KP * 64 + lane) * 2;
+    constexpr size_t ASTRIDE = (size_t)NT * KP * 128;
+    const double *og = obs + (size_t)blk * K * (KP * 128) + lane * 2;
+    // root: the site's likelihood sum_states(w L); up = w / it
+    bool zero;
+    {
+        const int i = nops - 1;
+        const size_t o = down_at<NT>(i, nblocks, blk, m, lane);
+        double w[4], s = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            w[r] = live[r] ? (root_w ? root_w[16 * m + 4 * r + (lane >> 4)] : 1.0) : 0.0;
+            s += w[r] * Larr[o + r * 64];
+        }
+        down_part(red, m, lane, s);
+        __syncthreads();
+        const double tot = down_total<NT>(red, lane & 15);
+        zero = !(tot > 0.0);
+        if (mv0 == 0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Uarr[o + r * 64] = zero ? 0.0 : w[r] / tot;
+        }
+        if (writer && zero) atomicOr(&status[site], RT_SITE_ZERO_PROB);
+    }
+    double a[2 * KP];
+    // 1. the `up` vectors of the nodes with children, a parent before its children
+    if (mv0 == 0)
+        for (int i = nops - 2; i >= 0; --i) {
+            const int4 st = steps[i];
+            if (!st.w) continue;
+            const size_t o = down_at<NT>(i, nblocks, blk, m, lane);
+            const size_t po = down_at<NT>(st.y, nblocks, blk, m, lane);
+            double x[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) x[r] = Uarr[po + r * 64];
+            const int kp = tab.obs[st.y];
+            if (kp >= 0) {
+                double ob[4];
+                down_L<KP>(kp, og, Larr, po, m, ob);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) x[r] *= ob[r];
+            }
+            for (int e = tab.cptr[st.y]; e < tab.cptr[st.y + 1]; ++e) {
+                const int w = tab.cidx[e];
+                if (w == i) continue;
+                const size_t wo = down_at<NT>(w, nblocks, blk, m, lane);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) x[r] *= Marr[wo + r * 64];
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) x[r] = live[r] ? x[r] : 0.0;     // (rows past the states)
+            down_stage(xb, m, lane, x);
+            down_frag<KP>(PfragT + (size_t)i * ASTRIDE + frag, a);
+            const double4_t acc = down_product<KS>(a, xb, lane);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Uarr[o + r * 64] = acc[r];
+        }
+    // 2. the moves about every node v with children and siblings
+    int par = 0;                                 // the half of `sums` the next chunk writes
+    for (int i = nops - 2; i >= 0; --i) {
+        const int4 st = steps[i];
+        if (!st.w) continue;
+        const int pi = st.y;
+        const int c0 = tab.cptr[i], c1 = tab.cptr[i + 1], s0 = tab.cptr[pi], s1 = tab.cptr[pi + 1];
+        int k = tab.first[i];
+        if (s1 - s0 < 2 || k >= mv1 || k + (c1 - c0) * (s1 - s0 - 1) <= mv0) continue;
+        const size_t po = down_at<NT>(pi, nblocks, blk, m, lane);
+        const int kp = tab.obs[pi], kv = tab.obs[i];
+        for (int ec = c0; ec < c1; ++ec)
+            for (int es = s0; es < s1; ++es) {
+                const int c = tab.cidx[ec], s = tab.cidx[es];
+                if (s == i) continue;
+                const int mv = k++;
+                if (mv < mv0 || mv >= mv1) continue;
+                // x = W o M_c on own rows, staged; then lp = L'_v (x is dead by then: the
+                // products below hold lp, one fragment table and the accumulator, as
+                // bp_down_kernel's -- up_p and the observations are read again per move)
+                {
+                    double x[4];
+                    const size_t co = down_at<NT>(c, nblocks, blk, m, lane);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) x[r] = Uarr[po + r * 64] * Marr[co + r * 64];
+                    if (kp >= 0) {
+                        double ob[4];
+                        down_L<KP>(kp, og, Larr, po, m, ob);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) x[r] *= ob[r];
+                    }
+                    for (int e = s0; e < s1; ++e) {
+                        const int w = tab.cidx[e];
+                        if (w == i || w == s) continue;
+                        const size_t wo = down_at<NT>(w, nblocks, blk, m, lane);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) x[r] *= Marr[wo + r * 64];
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) x[r] = live[r] ? x[r] : 0.0;   // (rows past the states)
+                    down_stage(xb, m, lane, x);
+                }
+                double lp[4];
+                {
+                    const size_t so = down_at<NT>(s, nblocks, blk, m, lane);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) lp[r] = Marr[so + r * 64];
+                    if (kv >= 0) {
+                        double ob[4];
+                        down_L<KP>(kv, og, Larr, so, m, ob);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) lp[r] *= ob[r];
+                    }
+                    for (int e = c0; e < c1; ++e) {
+                        const int w = tab.cidx[e];
+                        if (w == c) continue;
+                        const size_t wo = down_at<NT>(w, nblocks, blk, m, lane);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) lp[r] *= Marr[wo + r * 64];
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) lp[r] = live[r] ? lp[r] : 0.0;
+                }
+                double *row = out + (size_t)(mv - mv0) * np * nsites + site;
+                // per grid point: sum_b L'_v[b] (P(tau)^T x)[b], one fragment table live at a
+                // time.  A chunk of points goes into one half of `sums`; after the barrier wave 0
+                // adds the waves in order and stores the ratio while the next chunk fills the
+                // other half (the barrier after that chunk is behind these reads)
+                for (int g0 = 0; g0 < np; g0 += NNI_CHUNK) {
+                    const int cnt = min(NNI_CHUNK, np - g0);
+                    for (int j = 0; j < cnt; ++j) {
+                        down_frag<KP>(GfragT + ((size_t)(g0 + j) * nops + i) * ASTRIDE + frag, a);
+                        const double4_t y = down_product<KS>(a, xb, lane);
+                        double v = 0.0;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v += y[r] * lp[r];
+                        down_part(sums[par][j], m, lane, v);
+                    }
+                    __syncthreads();
+                    if (writer)
+                        for (int j = 0; j < cnt; ++j)
+                            row[(size_t)(g0 + j) * nsites] = down_total<NT>(sums[par][j], lane);
+                    par ^= 1;
+                }
+            }
+    }
+    // the tile's ratios -> values, by all waves: lane group q of the workgroup takes the rows
+    // (move, point) q, q + 4 NT, ... of its site (the barrier: wave 0's stores are visible)
+    __syncthreads();
+    if (site_ok) {
+        const long rows = (long)(mv1 - mv0) * np;
+        for (long r = 4 * m + (lane >> 4); r < rows; r += 4 * NT) {
+            double *x = out + (size_t)r * nsites + site;
+            *x = nni_value(*x, zero);
+        }
+    }
+}
+
+// n <= 4: one lane per site; arrays [node][state][site], nodes in preorder; G [point][node][N][N]
+// or null for the resident P (the same address in every lane: the scalar path)
+template <int N>
+__global__ void __launch_bounds__(256)
+nni_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const double *__restrict__ G,
+                int np, const int *__restrict__ parent, const int *__restrict__ node_k,
+                const int *__restrict__ tabp, const void *__restrict__ obs, int compact, int K,
+                int block_sites, const double *__restrict__ root_w, double *__restrict__ Larr,
+                double *__restrict__ Marr, double *__restrict__ Uarr, int mv0, int mv1,
+                double *__restrict__ out, int *__restrict__ status)
+{
+    const long site = (long)blockIdx.x * 256 + threadIdx.x;
+    if (site >= nsites) return;
+    const nni_tab tab(tabp, nnodes);
+    auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
+    auto node_obs = [&](int v, double (&x)[N]) {
+        const int k = node_k[v];
+        if (k >= 0) lane_obs<N>(obs, compact, K, block_sites, site, k, x);
+        else
+#pragma unroll
+            for (int s = 0; s < N; ++s) x[s] = 1.0;
+    };
+    if (mv0 == 0)
+        lane_up<N, true>(nnodes, nsites, site, P, parent, node_k, obs, compact, K, block_sites, Larr,
+                         Marr);
+    double tot = 0.0;
+#pragma unroll
+    for (int s = 0; s < N; ++s) tot += (root_w ? root_w[s] : 1.0) * Larr[idx(0, s)];
+    const bool zero = !(tot > 0.0);
+    if (zero) status[site] |= RT_SITE_ZERO_PROB;
+    if (mv0 == 0) {
+        // the `up` vectors: the root, then every node with children after its parent
+#pragma unroll
+        for (int s = 0; s < N; ++s) Uarr[idx(0, s)] = zero ? 0.0 : (root_w ? root_w[s] : 1.0) / tot;
+        for (int v = 1; v < nnodes; ++v) {
+            if (tab.cptr[v + 1] == tab.cptr[v]) continue;
+            const int p = parent[v];
+            double x[N];
+            node_obs(p, x);
+#pragma unroll
+            for (int s = 0; s < N; ++s) x[s] *= Uarr[idx(p, s)];
+            for (int e = tab.cptr[p]; e < tab.cptr[p + 1]; ++e) {
+                const int w = tab.cidx[e];
+                if (w == v) continue;
+#pragma unroll
+                for (int s = 0; s < N; ++s) x[s] *= Marr[idx(w, s)];
+            }
+            const double *Pv = P + (size_t)v * N * N;
+#pragma unroll
+            for (int b = 0; b < N; ++b) {
+                double y = 0.0;
+#pragma unroll
+                for (int a = 0; a < N; ++a) y += Pv[a * N + b] * x[a];
+                Uarr[idx(v, b)] = y;
+            }
+        }
+    }
+    for (int v = 1; v < nnodes; ++v) {
+        const int p = parent[v];
+        const int c0 = tab.cptr[v], c1 = tab.cptr[v + 1], s0 = tab.cptr[p], s1 = tab.cptr[p + 1];
+        int k = tab.first[v];
+        if (c1 == c0 || s1 - s0 < 2 || k >= mv1 || k + (c1 - c0) * (s1 - s0 - 1) <= mv0) continue;
+        double base[N], lv[N];
+        node_obs(p, base);
+        node_obs(v, lv);
+#pragma unroll
+        for (int s = 0; s < N; ++s) base[s] *= Uarr[idx(p, s)];
+        for (int ec = c0; ec < c1; ++ec)
+            for (int es = s0; es < s1; ++es) {
+                const int c = tab.cidx[ec], sb = tab.cidx[es];
+                if (sb == v) continue;
+                const int mv = k++;
+                if (mv < mv0 || mv >= mv1) continue;
+                double x[N], lp[N];
+#pragma unroll
+                for (int s = 0; s < N; ++s) {
+                    x[s] = base[s] * Marr[idx(c, s)];
+                    lp[s] = lv[s] * Marr[idx(sb, s)];
+                }
+                for (int e = s0; e < s1; ++e) {
+                    const int w = tab.cidx[e];
+                    if (w == v || w == sb) continue;
+#pragma unroll
+                    for (int s = 0; s < N; ++s) x[s] *= Marr[idx(w, s)];
+                }
+                for (int e = c0; e < c1; ++e) {
+                    const int w = tab.cidx[e];
+                    if (w == c) continue;
+#pragma unroll
+                    for (int s = 0; s < N; ++s) lp[s] *= Marr[idx(w, s)];
+                }
+                for (int g = 0; g < np; ++g) {
+                    const double *Gv = G ? G + ((size_t)g * nnodes + v) * N * N : P + (size_t)v * N * N;
+                    double t = 0.0;
+#pragma unroll
+                    for (int b = 0; b < N; ++b) {
+                        double y = 0.0;
+#pragma unroll
+                        for (int a = 0; a < N; ++a) y += Gv[a * N + b] * x[a];
+                        t += y * lp[b];
+                    }
+                    out[((size_t)(mv - mv0) * np + g) * nsites + site] = nni_value(t, zero);
+                }
+            }
+    }
+}
+
+// one workgroup per (move, point), the order of profile_sums_kernel: thread j adds sites j,
+// j + 256, ... in order, then the 256 partial sums by halves (fixed rounding).  Sites of zero
+// likelihood and of weight 0 are skipped.
+__global__ void __launch_bounds__(256)
+nni_sums_kernel(long nsites, const double *__restrict__ values, const double *__restrict__ weights,
+                const int *__restrict__ status, double *__restrict__ sums)
+{
+    __shared__ double part[256];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const double *x = values + (size_t)row * nsites;
+    double acc = 0.0;
+    for (long i = tid; i < nsites; i += 256) {
+        const double w = weights ? weights[i] : 1.0;       // (w = 0: not -inf * 0 = NaN)
+        if (w != 0.0 && !(status[i] & RT_SITE_ZERO_PROB)) acc += w * x[i];
+    }
+    part[tid] = acc;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) part[tid] += part[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) sums[row] = part[0];
+}
+
+// the moves in their order: v ascending, then the children c of v, then the siblings s of v, both
+// in CSR order.  first (or null): [nnodes] the index of every node's first move; moves (or null):
+// the triples
+int64_t nni_enumerate(int64_t N, const int64_t *idx, const int64_t *ptr, const int32_t *parent,
+                      int32_t *first, int32_t *moves)
+{
+    int64_t k = 0;
+    for (int64_t v = 0; v < N; ++v) {
+        if (first) first[v] = (int32_t)k;
+        if (!v) continue;
+        const int64_t p = parent[v];
+        for (int64_t ec = ptr[v]; ec < ptr[v + 1]; ++ec)
+            for (int64_t es = ptr[p]; es < ptr[p + 1]; ++es) {
+                if (idx[es] == v) continue;
+                if (moves) {
+                    moves[3 * k] = (int32_t)v;
+                    moves[3 * k + 1] = (int32_t)idx[ec];
+                    moves[3 * k + 2] = (int32_t)idx[es];
+                }
+                ++k;
+            }
+    }
+    return k;
+}
+
+int64_t nni_enumerate(const rt_model *m, int32_t *first, int32_t *moves)
+{
+    return nni_enumerate(m->nnodes, m->indices.data(), m->indptr.data(), m->parent.data(), first, moves);
+}
+
+int nni_moves_out(int64_t cnt, int32_t *moves, int64_t capacity, int64_t *nmoves)
+{
+    *nmoves = cnt;
+    RT_REQUIRE(!moves || capacity >= cnt, "the tree has %lld moves, the array holds %lld",
+               (long long)cnt, (long long)capacity);
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" int rt_model_nni_moves(const rt_model *m, int32_t *moves, int64_t capacity, int64_t *nmoves)
+{
+    RT_REQUIRE(m && nmoves, "null pointer");
+    RT_TRY(nni_moves_out(nni_enumerate(m, nullptr, nullptr), moves, capacity, nmoves));
+    if (moves) nni_enumerate(m, nullptr, moves);
+    return RT_OK;
+}
+
+extern "C" int rt_tree_nni_moves(int64_t nnodes, const int64_t *idx, const int64_t *ptr,
+                                 int32_t *moves, int64_t capacity, int64_t *nmoves)
+{
+    RT_REQUIRE(nnodes >= 1 && ptr && (idx || nnodes == 1) && nmoves, "bad arguments");
+    RT_REQUIRE(ptr[0] == 0 && ptr[nnodes] == nnodes - 1, "tree_csr_indptr does not describe a tree");
+    std::vector<int32_t> parent((size_t)nnodes, -1);
+    for (int64_t v = 0; v < nnodes; ++v) {
+        RT_REQUIRE(ptr[v + 1] >= ptr[v], "tree_csr_indptr not monotone");
+        for (int64_t e = ptr[v]; e < ptr[v + 1]; ++e) {
+            RT_REQUIRE(idx[e] > v && idx[e] < nnodes, "children not in preorder");
+            parent[(size_t)idx[e]] = (int32_t)v;
+        }
+    }
+    RT_TRY(nni_moves_out(nni_enumerate(nnodes, idx, ptr, parent.data(), nullptr, nullptr), moves,
+                         capacity, nmoves));
+    if (moves) nni_enumerate(nnodes, idx, ptr, parent.data(), nullptr, moves);
+    return RT_OK;
+}
+
+extern "C" int rt_sites_nni_scores(rt_model *m, rt_sites *s, int recompute_transitions,
+                                   int64_t npoints, const double *lengths, double *values,
+                                   double *sums, int32_t *status)
+{
+    post_pass p;                                 // (alive until the synchronisation below)
+    RT_TRY(post_open(&p, "rt_sites_nni_scores", m, s));
+    const int64_t n = p.n, N = p.N, nsites = p.nsites;
+    // the moves; the rows of `lengths` that count are those of the nodes with one
+    std::vector<int32_t> first((size_t)N + 1, 0);
+    const int64_t nmoves = nni_enumerate(m, first.data(), nullptr);
+    first[(size_t)N] = (int32_t)nmoves;
+    std::vector<unsigned char> has_move((size_t)N, 0);
+    for (int64_t v = 1; v < N; ++v) has_move[(size_t)v] = first[(size_t)v + 1] > first[(size_t)v];
+    if (lengths)
+        RT_TRY(post_grid_check(&p, recompute_transitions, npoints, lengths, has_move.data()));
+    else
+        RT_REQUIRE(npoints == 1, "rt_sites_nni_scores: without lengths the edge above v keeps its "
+                   "matrix: 1 grid point (%lld here)", (long long)npoints);
+    RT_REQUIRE(nmoves * npoints < (int64_t)1 << 31, "rt_sites_nni_scores: too many moves");
+    const int np = (int)npoints;
+    RT_TRY(post_layout(&p, true));
+    post_plan &plan = p.plan;
+    post_grid grid;                              // (alive until the synchronisation below)
+    if (lengths) RT_TRY(post_grid_take(&p, &grid, np));
+    const int cnt = p.lane ? (int)N : p.nops;    // slots of the move tables
+    const size_t tab_ints = (size_t)4 * cnt;
+    const size_t o_tab = plan.take(tab_ints * 4);
+    const size_t o_sum = plan.take((size_t)std::max<int64_t>(nmoves, 1) * np * 8);
+    // the moves of one chunk: their result (and its transpose) within the chunk size and the cap
+    const size_t per_move = (size_t)np * nsites * 8 * (values ? 2 : 1);
+    size_t chunk_bytes = NNI_CHUNK_BYTES;
+    if (const char *e = getenv("RAOTEH_NNI_CHUNK_BYTES")) {      // (tests: many chunks at small sizes)
+        const long long v = atoll(e);
+        if (v > 0) chunk_bytes = (size_t)v;
+    }
+    const double room = NNI_SCRATCH_CAP - (double)plan.total - 4096.0;
+    if (room < (double)chunk_bytes) chunk_bytes = room > 0.0 ? (size_t)room : 0;
+    int64_t CH = std::max<int64_t>(1, (int64_t)(chunk_bytes / per_move));
+    CH = std::min<int64_t>(CH, std::max<int64_t>(1, ((int64_t)1 << 21) / np));   // (the grids' y)
+    CH = std::min<int64_t>(CH, std::max<int64_t>(nmoves, 1));
+    const size_t chunk_rows = (size_t)CH * np;
+    const size_t o_val = plan.take(chunk_rows * nsites * 8);
+    const size_t o_valT = plan.take(values ? chunk_rows * nsites * 8 : 8);
+    RT_TRY(post_begin(&p, recompute_transitions));
+    hipStream_t st = p.st;
+    unsigned char *base = p.base;
+    double *d_val = (double *)(base + o_val), *d_valT = (double *)(base + o_valT);
+    double *d_sum = (double *)(base + o_sum);
+    int *d_tab = (int *)(base + o_tab);
+    int *d_status = p.d_status;
+    std::vector<int32_t> internal((size_t)N, 0);
+    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
+    if (lengths) RT_TRY(post_grid_launch(&p, &grid, lengths, has_move.data()));
+    RT_TRY(post_up(&p, internal.data(), true));
+    // the move tables, by step (n > 4) or by node
+    std::vector<int32_t> tab(tab_ints, 0), slot_of((size_t)N);
+    {
+        const rt_sites *x = p.lane ? s : p.x;
+        std::vector<int32_t> node_of((size_t)cnt), obs_of((size_t)N, -1);
+        for (int j = 0; j < cnt; ++j) node_of[(size_t)j] = p.lane ? j : x->ops[(size_t)j].node;
+        for (int j = 0; j < cnt; ++j) slot_of[(size_t)node_of[(size_t)j]] = j;
+        for (const rt_op &op : x->ops)
+            if (op.obs >= 0) obs_of[(size_t)op.node] = op.obs;
+        int32_t *t_obs = tab.data(), *t_cptr = t_obs + cnt, *t_first = t_cptr + cnt + 1;
+        int32_t *t_cidx = t_first + cnt;
+        int32_t e = 0;
+        for (int j = 0; j < cnt; ++j) {
+            const int64_t v = node_of[(size_t)j];
+            t_obs[j] = obs_of[(size_t)v];
+            t_first[j] = first[(size_t)v];
+            t_cptr[j] = e;
+            for (int64_t k = m->indptr[(size_t)v]; k < m->indptr[(size_t)v + 1]; ++k)
+                t_cidx[e++] = slot_of[(size_t)m->indices[(size_t)k]];
+        }
+        t_cptr[cnt] = e;
+    }
+    RT_HIP(hipMemcpyAsync(d_tab, tab.data(), tab_ints * 4, hipMemcpyHostToDevice, st));
+    if (!p.lane && lengths) RT_TRY(post_grid_pack(&p, &grid));
+    for (int64_t mv0 = 0; mv0 == 0 || mv0 < nmoves; mv0 += CH) {
+        const int64_t mv1 = std::min(nmoves, mv0 + CH);
+        const size_t rows = (size_t)(mv1 - mv0) * np;
+        if (p.lane) {
+            const int *d_ptab = p.d_ptab;
+            RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
+                hipLaunchKernelGGL((nni_lane_kernel<decltype(nv)::value>),
+                                   dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)N,
+                                   (long)nsites, (const double *)m->d_P,
+                                   (const double *)(lengths ? grid.d_G : nullptr), np, d_ptab, d_ptab + N,
+                                   (const int *)d_tab, (const void *)s->d_obs, s->compact_states,
+                                   (int)s->nobs, s->block_sites, (const double *)m->d_root, p.d_L, p.d_M,
+                                   p.d_D, (int)mv0, (int)mv1, d_val, d_status);
+                return RT_OK;
+            }));
+        } else {
+            const rt_sites *x = p.x;
+            RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
+                constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
+                hipLaunchKernelGGL((nni_kernel<NT, KS>), dim3((unsigned)x->nblocks), dim3(64 * NT), 0, st,
+                                   (const double *)p.d_PT, (const double *)(lengths ? grid.d_GT : p.d_PT),
+                                   np, p.nops, (const int4 *)p.d_steps, (const int *)d_tab,
+                                   (const double *)p.d_L, (const double *)p.d_M, p.d_D,
+                                   (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
+                                   (int)n, (int)mv0, (int)mv1, d_val, d_status, (long)x->nsites,
+                                   (long)x->nblocks);
+                return RT_OK;
+            }));
+        }
+        RT_HIP(hipGetLastError());
+        if (!rows) break;                        // (no moves: the status alone)
+        // 3. the weighted site sums; only what was asked for crosses PCIe
+        if (sums) {
+            hipLaunchKernelGGL(nni_sums_kernel, dim3((unsigned)rows), dim3(256), 0, st, (long)nsites,
+                               (const double *)d_val, (const double *)s->d_weights,
+                               (const int *)d_status, d_sum + (size_t)mv0 * np);
+            RT_HIP(hipGetLastError());
+        }
+        if (values) {
+            hipLaunchKernelGGL(post_transpose_kernel<32>,
+                               dim3((unsigned)((nsites + 31) / 32), (unsigned)((rows + 31) / 32)),
+                               dim3(256), 0, st, (long)rows, (long)nsites, (const double *)d_val, d_valT);
+            RT_HIP(hipGetLastError());
+            // [site][rows of the chunk] into the caller's [site][nmoves][np]
+            RT_HIP(hipMemcpy2DAsync(values + (size_t)mv0 * np, (size_t)nmoves * np * 8, d_valT, rows * 8,
+                                    rows * 8, (size_t)nsites, hipMemcpyDeviceToHost, st));
+        }
+    }
+    if (sums && nmoves)
+        RT_HIP(hipMemcpyAsync(sums, d_sum, (size_t)nmoves * np * 8, hipMemcpyDeviceToHost, st));
+    if (status) RT_HIP(hipMemcpyAsync(status, d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipStreamSynchronize(st));
+    if (lengths) RT_TRY(post_grid_result(&p, &grid));
+    return RT_OK;
+}

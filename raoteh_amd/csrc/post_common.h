@@ -1,13 +1,15 @@
-// What the reads of a RESIDENT batch share (posterior.hip, branch_expect.hip, sample.hip,
-// mapping.hip).  Host: post_pass, one description of such a call -- its checks, the common
-// pieces of its scratch, the upward pass with L (and M) of every step stored (the plan of the
-// scratch and the dispatch over the kernels' template arguments: common.h).  Device: the steps the
-// downward kernels have in common.
+// What the reads of a RESIDENT batch share (posterior.hip, branch_expect.hip, branch_profile.hip,
+// nni.hip, sample.hip, mapping.hip).  Host: post_pass, one description of such a call -- its
+// checks, the common pieces of its scratch, the upward pass with L (and M) of every step stored
+// (the plan of the scratch and the dispatch over the kernels' template arguments: common.h);
+// post_grid, the trial lengths of the edges through the model's own exponential.  Device: the
+// steps the downward kernels have in common.
 #pragma once
 
 #include "common.h"
 
 #include <algorithm>
+#include <cmath>
 
 // One read of a resident batch.  post_open .. post_layout make the checks every such call makes
 // and take the common pieces from `plan`; the caller takes its own from the same plan, then
@@ -234,6 +236,136 @@ inline int post_up(post_pass *p, const int *w_of_node, bool pack_pt)
     return RT_OK;
 }
 
+// ---- trial lengths of the edges (rt_sites_branch_profiles, rt_sites_nni_scores): P_v(tau) of
+// every node and grid point from the model's own exponential, [point][node][n][n] like the model's
+// transition matrices, and for n > 4 their transposes as A fragments [point][step] ----
+
+// the model keeps the branch lengths of the last rt_model_set_rates / _spectral on the host
+inline bool post_model_has_rates(const rt_model *m)
+{
+    return (m->d_Q || m->spectral) && (int64_t)m->h_t.size() == m->nnodes &&
+           (int64_t)m->h_qidx.size() == m->nnodes;
+}
+
+// (the host vectors feed asynchronous copies: alive until the stream is synchronised)
+struct post_grid {
+    int np = 0;
+    size_t cnt = 0;                              // np * nnodes exponentials (the root's: zero matrices)
+    size_t o_G = 0, o_tau = 0, o_qidx = 0, o_info = 0, o_GT = 0;
+    double *d_G = nullptr, *d_GT = nullptr;
+    std::vector<double> tau;
+    std::vector<int32_t> qidx, info;
+};
+
+// what such a call asks of the model and of lengths[nnodes][npoints] (row 0 is ignored; with
+// use_row [nnodes], every row v with use_row[v] == 0 too)
+inline int post_grid_check(const post_pass *p, int recompute_transitions, int64_t npoints,
+                           const double *lengths, const unsigned char *use_row = nullptr)
+{
+    const rt_model *m = p->m;
+    RT_REQUIRE(post_model_has_rates(m),
+               "%s: no rates have been set (rt_model_set_rates or "
+               "rt_model_set_rates_spectral; a model with transitions set directly has no rate "
+               "matrix to exponentiate at another length)", p->who);
+    RT_REQUIRE(m->rates_current || recompute_transitions,
+               "%s: the transitions were set directly after the rates "
+               "(rt_model_set_transitions): the resident rates and lengths no longer describe them; "
+               "set the rates again or pass recompute_transitions", p->who);
+    RT_REQUIRE(lengths, "%s: lengths is NULL", p->who);
+    RT_REQUIRE(npoints >= 1 && npoints <= RT_MAX_PROFILE_POINTS,
+               "%s: 1..%d grid points per branch (%lld here)", p->who,
+               RT_MAX_PROFILE_POINTS, (long long)npoints);
+    for (int64_t v = 1; v < p->N; ++v)
+        for (int64_t g = 0; g < npoints && (!use_row || use_row[v]); ++g) {
+            const double x = lengths[v * npoints + g];
+            RT_REQUIRE(std::isfinite(x) && x >= 0.0,
+                       "%s: length %d of node %lld is negative or not finite", p->who, (int)g,
+                       (long long)v);
+        }
+    return RT_OK;
+}
+
+// after post_layout: the orders the model's exponential takes, the grid's pieces of the scratch
+inline int post_grid_take(post_pass *p, post_grid *g, int np)
+{
+    const rt_model *m = p->m;
+    if (m->spectral ? p->n > 64 : p->n > RT_MAX_EXPM_STATES) {
+        rt_set_error("%s: n=%lld is beyond what the model's exponential takes", p->who,
+                     (long long)p->n);
+        return RT_ERR_UNSUPPORTED;
+    }
+    g->np = np;
+    g->cnt = (size_t)np * p->N;
+    const size_t nn = (size_t)p->n * p->n;
+    g->o_G = p->plan.take(g->cnt * nn * 8);
+    g->o_tau = p->plan.take(g->cnt * 8);
+    g->o_qidx = p->plan.take(g->cnt * 4);
+    g->o_info = p->plan.take(g->cnt * 8);
+    g->o_GT = p->lane ? p->plan.take(8)
+                      : p->plan.take((size_t)np * p->nops * p->NT * p->KP * 128 * 8);
+    return RT_OK;
+}
+
+// after post_begin: the tiled qidx / tau arrays and ONE launch of the route the model's own
+// transitions take (an ignored row: the resident length at every point)
+inline int post_grid_launch(post_pass *p, post_grid *g, const double *lengths,
+                            const unsigned char *use_row = nullptr)
+{
+    const rt_model *m = p->m;
+    const int64_t n = p->n, N = p->N;
+    const int np = g->np;
+    const size_t cnt = g->cnt, nn = (size_t)n * n;
+    hipStream_t st = p->st;
+    g->d_G = (double *)(p->base + g->o_G);
+    g->d_GT = (double *)(p->base + g->o_GT);
+    double *d_tau = (double *)(p->base + g->o_tau);
+    int32_t *d_qidx = (int32_t *)(p->base + g->o_qidx), *d_info = (int32_t *)(p->base + g->o_info);
+    g->tau.assign(cnt, 0.0);
+    g->qidx.assign(cnt, 0);
+    g->info.assign(2 * cnt, 0);
+    for (int k = 0; k < np; ++k)
+        for (int64_t v = 0; v < N; ++v) {
+            g->qidx[(size_t)k * N + v] = m->h_qidx[(size_t)v];   // (the root's: -1, a zero matrix)
+            if (v)
+                g->tau[(size_t)k * N + v] = !use_row || use_row[v] ? lengths[v * np + k] : m->h_t[(size_t)v];
+        }
+    RT_HIP(hipMemcpyAsync(d_tau, g->tau.data(), cnt * 8, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemcpyAsync(d_qidx, g->qidx.data(), cnt * 4, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemsetAsync(d_info, 0, cnt * 8, st));
+    if (m->spectral)
+        RT_TRY(rt_launch_spectral(p->ctx, n, (int64_t)cnt, m->d_spec, m->d_spec + 2 * nn,
+                                  m->d_spec + nn, m->spectral_has_D ? m->d_spec + 2 * nn + n : nullptr,
+                                  d_qidx, d_tau, g->d_G, d_info, nullptr, 0, nullptr));
+    else
+        RT_TRY(rt_launch_expm(p->ctx, n, (int64_t)cnt, m->d_Q, d_qidx, d_tau, g->d_G, d_info, nullptr,
+                              0, nullptr));
+    RT_HIP(hipMemcpyAsync(g->info.data(), d_info, cnt * 8, hipMemcpyDeviceToHost, st));
+    return RT_OK;
+}
+
+// n > 4, after post_up: P(tau)^T of every point as A fragments in step order
+inline int post_grid_pack(post_pass *p, post_grid *g)
+{
+    const size_t nn = (size_t)p->n * p->n, tab = (size_t)p->nops * p->NT * p->KP * 128;
+    for (int k = 0; k < g->np; ++k)
+        RT_TRY(rt_launch_pack_pt(p->ctx, (int)p->n, p->NT, p->KP, p->nops, p->d_ptab,
+                                 g->d_G + (size_t)k * p->N * nn, g->d_GT + (size_t)k * tab));
+    return RT_OK;
+}
+
+// after the synchronisation: an exponential the kernel gave up on (tau Q not finite) -- its
+// rows hold nothing usable
+inline int post_grid_result(const post_pass *p, const post_grid *g)
+{
+    for (size_t j = 0; j < g->cnt; ++j)
+        if (g->info[2 * j] < 0) {
+            rt_set_error("%s: expm failed for node %lld at length %g (a non-finite entry or norm "
+                         "of tau Q)", p->who, (long long)(j % (size_t)p->N), g->tau[j]);
+            return RT_ERR_SINGULAR;
+        }
+    return RT_OK;
+}
+
 // n <= 4: one lane per site.  The observation of stream position k from the batch's lane-family
 // image (dense pairs, or one byte per leaf: a state or an allowed-set mask; passes.hip
 // sets_from_lane_batch_kernel reads the same layouts).
@@ -435,6 +567,24 @@ __device__ __forceinline__ double4_t down_product(const double (&a)[2 * ((KS + 1
     for (int kk = 0; kk < KS; ++kk)
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], xb[kk * 64 + lane], acc, 0, 0, 0);
     return acc;
+}
+
+// [row][site] -> [site][row] for a caller's per-site array, 32 x 32 tiles through LDS (TILE = 32;
+// a template: only the translation units that launch it hold a copy)
+template <int TILE>
+__global__ void __launch_bounds__(256)
+post_transpose_kernel(long nrows, long nsites, const double *__restrict__ in,
+                      double *__restrict__ outT)
+{
+    static_assert(TILE == 32, "256 threads move 32 x 32 tiles");
+    __shared__ double tile[TILE][TILE + 1];
+    const long s0 = (long)blockIdx.x * 32, r0 = (long)blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int k = ty; k < 32; k += 8)
+        if (r0 + k < nrows && s0 + tx < nsites) tile[k][tx] = in[(size_t)(r0 + k) * nsites + s0 + tx];
+    __syncthreads();
+    for (int k = ty; k < 32; k += 8)
+        if (s0 + k < nsites && r0 + tx < nrows) outT[(size_t)(s0 + k) * nrows + r0 + tx] = tile[tx][k];
 }
 
 }  // namespace

@@ -304,6 +304,28 @@ def check_profile_lengths(lengths, nnodes, factors=None, resident=None, tree=Non
     return grid
 
 
+# TreeModel.nni_scores: moves int32[nmoves, 3] (TreeModel.nni_moves), lengths [nnodes, G] as
+# evaluated (the resident lengths [nnodes, 1] for the plain swap; None where the model has none),
+# sums [nmoves, G], values [nsites, nmoves, G] (or None) with values[i, mv, g] = log L_i(tree after
+# move mv, t_v -> lengths[v, g]) - log L_i; status as Posteriors
+NniScores = collections.namedtuple('NniScores', 'moves lengths sums values status')
+
+
+def tree_nni_moves(tree):
+    """rt_tree_nni_moves: the moves TreeModel.nni_moves lists, int32[nmoves, 3], from a
+    TreeArrays alone (host only: no context, no model)."""
+    idx = np.ascontiguousarray(tree.indices, dtype=np.int64)
+    ptr = np.ascontiguousarray(tree.indptr, dtype=np.int64)
+    count = c_int64(0)
+    _lib.check(_lib.lib().rt_tree_nni_moves(tree.nnodes, _ptr(idx, c_int64), _ptr(ptr, c_int64),
+                                            None, 0, byref(count)))
+    moves = np.zeros((count.value, 3), dtype=np.int32)
+    if count.value:
+        _lib.check(_lib.lib().rt_tree_nni_moves(tree.nnodes, _ptr(idx, c_int64), _ptr(ptr, c_int64),
+                                                _ptr(moves, c_int32), count.value, byref(count)))
+    return moves
+
+
 def check_draws(ndraws, seed, first_draw):
     """The draw arguments of sample_states / sample_mappings as ints; ValueError unless there is
     at least one draw and the seed and every draw number fit an unsigned 64-bit integer."""
@@ -1446,6 +1468,58 @@ class TreeModel(object):
             None if values is None else _ptr(values, c_double), _ptr(sums, c_double),
             _ptr(status, c_int32)))
         return BranchProfiles(list(ta.preorder_nodes), grid, sums, values, status)
+
+    def nni_moves(self):
+        """rt_model_nni_moves: the nearest-neighbour interchanges of the tree, int32[nmoves, 3]
+        of preorder indices (v, c, s) -- the subtrees of the child c of v and of the sibling s of
+        v exchanged -- ordered by v, then c, then s in child order (_tree.nni_apply makes the
+        moved tree).  Where parent(v) is a root with the two children v and s the move keeps
+        the unrooted topology."""
+        count = c_int64(0)
+        _lib.check(_lib.lib().rt_model_nni_moves(self._h, None, 0, byref(count)))
+        moves = np.zeros((count.value, 3), dtype=np.int32)
+        if count.value:
+            _lib.check(_lib.lib().rt_model_nni_moves(self._h, _ptr(moves, c_int32), count.value,
+                                                     byref(count)))
+        return moves
+
+    def nni_scores(self, batch, lengths=None, factors=None, per_site=False,
+                   recompute_transitions=False):
+        """rt_sites_nni_scores: the change of the log-likelihood for every move of nni_moves()
+        -- one upward and one downward pass for the whole neighbourhood instead of a model
+        build, an upload and a step per candidate.  With neither `lengths` nor `factors` the
+        edge above v keeps its transition matrix (the plain swap; no rates needed); else the
+        moves about v are scored at every trial length of that edge, given as for
+        branch_profiles (check_profile_lengths; rows of nodes without a move are ignored).
+        Returns an NniScores tuple: moves, lengths [nnodes, G] as evaluated, sums[mv, g] the
+        site-weighted sum (SiteBatch.set_weights) of values[i, mv, g] (None unless per_site),
+        status.  -inf where a live site has likelihood 0 on the moved tree."""
+        ta = self.tree
+        N, S = ta.nnodes, batch.nsites
+        moves = self.nni_moves()
+        if lengths is None and factors is None:
+            grid, G = None, 1
+        else:
+            resident = None
+            if factors is not None or isinstance(lengths, dict):
+                resident = self.branch_lengths()
+            grid = check_profile_lengths(lengths, N, factors=factors, resident=resident, tree=ta)
+            G = grid.shape[1]
+        M = len(moves)
+        values = np.zeros((S, M, G)) if per_site else None
+        sums = np.zeros((M, G))
+        status = np.zeros(S, dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_nni_scores(
+            self._h, batch._h, 1 if recompute_transitions else 0, G,
+            None if grid is None else _ptr(grid, c_double),
+            None if values is None else _ptr(values, c_double), _ptr(sums, c_double),
+            _ptr(status, c_int32)))
+        if grid is None:
+            try:                                 # (a model with transitions set directly: none)
+                grid = self.branch_lengths()[:, None].copy()
+            except (ValueError, _lib.RaotehHipError):
+                grid = None
+        return NniScores(moves, grid, sums, values, status)
 
     def branch_length_gradient(self, batch, recompute_transitions=False):
         """d (sum_i w_i log L_i) / d t_v for every branch, f64[nnodes] in preorder (0 at the
