@@ -563,6 +563,60 @@ int rt_tree_nni_moves(int64_t nnodes, const int64_t *tree_csr_indices, const int
 int rt_sites_nni_scores(rt_model *model, rt_sites *sites, int recompute_transitions,
             int64_t npoints, const double *lengths, double *values, double *sums,
             int32_t *status);
+/* Query sequences placed on every branch of the tree of a RESIDENT batch (evolutionary placement),
+ * without one model build, upload and rt_step per candidate.  Nodes are preorder indices.  v is a
+ * non-root node, p = parent(v), Q_v and t_v the rate matrix and the length of the edge above v.  A
+ * placement of query q is (v, rho, tau): a new unobserved node x cuts the edge p -> v into p -> x
+ * of length rho t_v and x -> v of length (1 - rho) t_v, and a new leaf that carries the query's
+ * observation o_q hangs below x on an edge of length tau; all three edges under Q_v.  The
+ * definition is ROOTED, as for NNI, because rate matrices need not be reversible; the root has no
+ * row.  For site i:
+ *   values[i][q][v][r][k] = log L_i(tree with q placed at (v, fractions[r], pendant[k])) - log L_i
+ *                           f64[nsites][nqueries][nnodes][nfractions][npendant]: the log of the
+ *                           conditional probability of the query's column given the reference
+ *                           column; -inf where it is 0; the root's row is 0
+ *   sums[q][v][r][k]      = sum_i w_i values[i][q][v][r][k]
+ *                           f64[nqueries][nnodes][nfractions][npendant]
+ *                           (w: rt_sites_set_weights, default 1; reduced on the device, fixed order;
+ *                           a site of weight 0 adds nothing, even where its value is -inf)
+ *   status[i]             : a site of zero likelihood has RT_SITE_ZERO_PROB, its values are 0 and it
+ *                           adds nothing to sums
+ * queries: query_kind RT_OBS_DENSE, f64[nqueries][nsites][n] likelihood vectors, or RT_OBS_STATE,
+ * uint8[nqueries][nsites] (a value >= n = unobserved, as for an upload); RT_OBS_MASK queries are
+ * not taken.  fractions f64[nfractions], each in [0, 1], 1..RT_MAX_PLACE_FRACTIONS of them;
+ * pendant f64[npendant], finite and >= 0, shared by all edges, 1..RT_MAX_PLACE_PENDANT of them;
+ * 2 nfractions + npendant <= 32: per node the lengths rho_r t_v, (1 - rho_r) t_v and tau_k are the
+ * grid of ONE launch of the model's exponential (fractions 0 and 1 go through it like any other
+ * length), from rt_model_set_rates (per-edge rate matrices included) or
+ * rt_model_set_rates_spectral (n <= 64).
+ * With L_w, M_w = P_w L_w of the stored upward pass and up_p the message into p from above,
+ * normalised once at the root by 1 / L_i:
+ *   A_v[a]       = up_p[a] obs_p[a] prod_{w child of p, w != v} M_w[a]
+ *   F_{v,r}[b]   = (P_v(rho_r t_v)^T A_v)[b] (P_v((1 - rho_r) t_v) L_v)[b]
+ *   h_{d,k,q}[b] = sum_c expm(Q_d tau_k)[b][c] o_q[c]         (d: a distinct rate-matrix index)
+ *   ratio        = sum_b F_{v,r}[b] h_{qidx(v),k,q}[b]
+ * Nothing is divided, so the result is exact where transition matrices or observations have
+ * zeros and at a resident t_v = 0.  h is made once per distinct rate matrix in use, never once
+ * per edge.  values, sums and status may each be NULL; only what is given crosses PCIe.  Every
+ * batch rt_sites_posteriors takes.  Where the per-site result of all queries would not fit the
+ * scratch the queries go through the device in chunks (RAOTEH_PLACE_CHUNK_BYTES of result per
+ * chunk, default 4 GB, or what the 96 GB cap leaves); the field F is made once, and chunked and
+ * unchunked calls give the same bits.
+ * RT_ERR_INVALID: nqueries < 1, counts out of range, a fraction outside [0, 1] or not finite, a
+ * negative or non-finite pendant length, NULL queries, fractions or pendant, a model without
+ * rates (or whose transitions were set directly after them, with recompute_transitions == 0), a
+ * batch of another model.  RT_ERR_SINGULAR: an exponential failed; nothing returned is usable
+ * then.  RT_ERR_UNSUPPORTED: RT_OBS_MASK queries, a partitioned batch, a "rescale" batch, a batch
+ * of the generic kernel, a tree deeper than the fast kernels take, nnodes < 2, more than 96 GB of
+ * scratch.  Synchronous; the model keeps its transitions and the batch its kernel,
+ * log-likelihoods, status and totals; two calls return the same bits.                          */
+#define RT_MAX_PLACE_FRACTIONS 8
+#define RT_MAX_PLACE_PENDANT   16
+int rt_sites_placements(rt_model *model, rt_sites *sites, int recompute_transitions,
+            int64_t nqueries, int query_kind, const void *queries,
+            int64_t nfractions, const double *fractions,
+            int64_t npendant, const double *pendant,
+            double *values, double *sums, int32_t *status);
 /* _sample_mcy_dense.resample_states (_sample_mcy_dense.py:23-69, through
  * _sample_mc0_dense.resample_states, _sample_mc0_dense.py:20-98) for every site of a RESIDENT
  * batch: ndraws joint draws of a state for every node from the posterior given the observations.

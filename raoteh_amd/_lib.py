@@ -33,6 +33,8 @@ RT_SITE_NEGATIVE = 4
 RT_MAX_POSTERIOR_SETS = 8
 RT_MAX_BRANCH_COEFS = 8
 RT_MAX_PROFILE_POINTS = 64
+RT_MAX_PLACE_FRACTIONS = 8
+RT_MAX_PLACE_PENDANT = 16
 RT_MAX_SAMPLE_NODES = 8192
 RT_MAX_MAPPING_EVENTS = 512
 RT_MAX_EXPECT_STATES = 64
@@ -143,6 +145,8 @@ SIGNATURES = {
     'rt_tree_nni_moves': (c_int, [c_int64, _p_i64, _p_i64, _p_i32, c_int64, _p_i64]),
     'rt_sites_nni_scores': (c_int, [c_void_p, c_void_p, c_int, c_int64, _p_f64, _p_f64, _p_f64,
                                     _p_i32]),
+    'rt_sites_placements': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_int64,
+                                    _p_f64, c_int64, _p_f64, _p_f64, _p_f64, _p_i32]),
     'rt_sites_sample_states': (c_int, [c_void_p, c_void_p, c_int, ctypes.c_uint64,
                                        ctypes.c_uint64, c_int64, POINTER(c_ubyte), _p_i32]),
     'rt_sample_states_draw_block': (c_int, [c_int64]),

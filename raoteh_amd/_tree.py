@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ['TreeArrays', 'marshal_tree', 'check_square_dense', 'nni_apply']
+__all__ = ['TreeArrays', 'marshal_tree', 'check_square_dense', 'nni_apply', 'place_apply']
 
 
 def check_square_dense(M):
@@ -155,5 +155,52 @@ def nni_apply(T, root, v, c, s):
         kids = [swap.get((a, int(b)), int(b)) for b in ta.indices[ta.indptr[a]:ta.indptr[a + 1]]]
         for b in kids:
             out.add_edge(ta.preorder_nodes[a], ta.preorder_nodes[b], **dict(ta.edge_data[b]))
+        stack.extend(reversed(kids))
+    return out
+
+
+def place_apply(T, root, v, fraction, pendant, label, cut_label=None):
+    """The tree with a query placed at (v, fraction, pendant) of rt_sites_placements, on node
+    LABELS of the networkx tree T rooted at `root`: a new node `cut_label` (default
+    ('cut', label)) cuts the edge p-v, p = parent(v), at `fraction` of its length from p, and
+    the new leaf `label` hangs below it on an edge of length `pendant`.  A new graph of T's
+    class with T's node and graph attributes; the cut node takes the place of v among the
+    children of p, v is its first child and the new leaf its second.  Every attribute of the
+    edge p-v is copied to the three edges (its rate matrix 'Q' among them), and 'weight', the
+    length TreeArrays.branch_lengths reads, is set to fraction * t, (1 - fraction) * t and
+    pendant.  ValueError for the root, an unknown node, a label already in the tree, or a
+    fraction outside [0, 1]."""
+    ta = TreeArrays(T, root)
+    idx = ta.node_to_index
+    if v not in idx:
+        raise ValueError('%r is not a node of the tree' % (v,))
+    iv = idx[v]
+    if iv == 0:
+        raise ValueError('%r is the root: no edge above it to place a query on' % (v,))
+    if cut_label is None:
+        cut_label = ('cut', label)
+    if label in idx or cut_label in idx or label == cut_label:
+        raise ValueError('the labels %r and %r must be new and distinct' % (label, cut_label))
+    fraction, pendant = float(fraction), float(pendant)
+    if not 0.0 <= fraction <= 1.0:
+        raise ValueError('the fraction %r is outside [0, 1]' % (fraction,))
+    if not (pendant >= 0.0 and pendant < float('inf')):
+        raise ValueError('the pendant length %r is negative or not finite' % (pendant,))
+    data = dict(ta.edge_data[iv])
+    t = data.get('weight', 0.0)
+    out = T.__class__()
+    out.graph.update(T.graph)
+    out.add_nodes_from((x, dict(T.nodes[x])) for x in ta.preorder_nodes)
+    stack = [0]
+    while stack:
+        a = stack.pop()
+        kids = [int(b) for b in ta.indices[ta.indptr[a]:ta.indptr[a + 1]]]
+        for b in kids:
+            if b != iv:
+                out.add_edge(ta.preorder_nodes[a], ta.preorder_nodes[b], **dict(ta.edge_data[b]))
+                continue
+            out.add_edge(ta.preorder_nodes[a], cut_label, **dict(data, weight=fraction * t))
+            out.add_edge(cut_label, v, **dict(data, weight=(1.0 - fraction) * t))
+            out.add_edge(cut_label, label, **dict(data, weight=pendant))
         stack.extend(reversed(kids))
     return out

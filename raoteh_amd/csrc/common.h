@@ -610,6 +610,9 @@ void rt_expect_lane_release(rt_model *m);
 // KP k-step pairs), asynchronous on the context's stream
 int rt_launch_pack_pt(rt_ctx *ctx, int n, int NT, int KP, int nops, const int *d_step_node,
                       const double *d_P, double *d_PT);
+// ... and P itself in the same form (the products P x of place.hip)
+int rt_launch_pack_p(rt_ctx *ctx, int n, int NT, int KP, int nops, const int *d_step_node,
+                     const double *d_P, double *d_PA);
 // a split-M interpreter batch over the resident observations of `src` (api.hip); of a
 // partitioned batch: over its slots, launched through a view with the batch's granule_set
 int rt_sites_twin_interpreter(rt_sites *src, rt_sites **out);

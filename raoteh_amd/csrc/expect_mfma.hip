@@ -59,6 +59,27 @@ pack_pt_kernel(int n, int NT, int KP, int nops, const int *__restrict__ step_nod
     }
 }
 
+// A fragments of P itself in step order: T[step][m][q][lane][e2] = P_v[16m + (lane&15)][4(2q+e2) + (lane>>4)]
+__global__ void __launch_bounds__(256)
+pack_p_kernel(int n, int NT, int KP, int nops, const int *__restrict__ step_node,
+              const double *__restrict__ P, double *__restrict__ out)
+{
+    const long total = (long)nops * NT * KP * 128;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        const int e2 = (int)(e & 1);
+        const int ln = (int)((e >> 1) & 63);
+        long rest = e >> 7;
+        const int q = (int)(rest % KP);
+        rest /= KP;
+        const int m = (int)(rest % NT);
+        const int step = (int)(rest / NT);
+        const int a = 16 * m + (ln & 15);                 // output state (row of P)
+        const int b = 4 * (2 * q + e2) + (ln >> 4);       // input state (k)
+        const int v = step_node[step];
+        out[e] = (a < n && b < n) ? P[((long)v * n + a) * n + b] : 0.0;
+    }
+}
+
 template <int NT, int KS>
 __global__ void __launch_bounds__(64 * NT)
 expect_down_kernel(const double *__restrict__ PfragT, int nops, const int *__restrict__ parent_step,
@@ -1096,6 +1117,16 @@ int rt_launch_pack_pt(rt_ctx *ctx, int n, int NT, int KP, int nops, const int *d
 {
     hipLaunchKernelGGL(pack_pt_kernel, dim3(512), dim3(256), 0, ctx->stream, n, NT, KP, nops, d_step_node,
                        d_P, d_PT);
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+// the same table of the untransposed matrices, for products P x (place.hip)
+int rt_launch_pack_p(rt_ctx *ctx, int n, int NT, int KP, int nops, const int *d_step_node,
+                     const double *d_P, double *d_PA)
+{
+    hipLaunchKernelGGL(pack_p_kernel, dim3(512), dim3(256), 0, ctx->stream, n, NT, KP, nops, d_step_node,
+                       d_P, d_PA);
     RT_HIP(hipGetLastError());
     return RT_OK;
 }

@@ -48,17 +48,8 @@ __device__ __forceinline__ double nni_value(double ratio, bool zero)
     return ratio > 0.0 ? log(ratio) : -__builtin_inf();
 }
 
-// The move tables, over slots j = 0 .. cnt - 1 (n > 4: schedule steps; n <= 4: preorder nodes):
-//   obs[j]          stream position of the slot's node, a leaf or an observed INTERNAL node (the
-//                   shared step table has the leaves' only), or -1
-//   cptr[j], cidx   the slots of its children in the CSR child order
-//   first[j]        the index of its first move: moves go by node ascending, then by child of the
-//                   node, then by sibling
-struct nni_tab {
-    const int *obs, *cptr, *first, *cidx;
-    __host__ __device__ nni_tab(const int *t, int cnt)
-        : obs(t), cptr(t + cnt), first(t + 2 * cnt + 1), cidx(t + 3 * cnt + 1) {}
-};
+// The move tables are a post_tab (post_common.h) whose first[j] is the index of the first move of
+// slot j: moves go by node ascending, then by child of the node, then by sibling.
 
 // n > 4.  steps[i] = {node, step of the parent, stream position of an observed leaf or -1, 1 if
 // the node has children}; the root is the last step.  PfragT: [step] A fragments of the resident
@@ -80,7 +71,7 @@ nni_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT,
     __shared__ double xb[NT * 4 * 64];
     __shared__ double red[NT][16];
     __shared__ double sums[2][NNI_CHUNK][NT][16];
-    const nni_tab tab(tabp, nops);
+    const post_tab tab(tabp, nops);
     const int lane = threadIdx.x & 63;
     const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long blk = blockIdx.x;
@@ -93,60 +84,12 @@ nni_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT,
     const size_t frag = ((size_t)m * KP * 64 + lane) * 2;
     constexpr size_t ASTRIDE = (size_t)NT * KP * 128;
     const double *og = obs + (size_t)blk * K * (KP * 128) + lane * 2;
-    // root: the site's likelihood sum_states(w L); up = w / it
-    bool zero;
-    {
-        const int i = nops - 1;
-        const size_t o = down_at<NT>(i, nblocks, blk, m, lane);
-        double w[4], s = 0.0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            w[r] = live[r] ? (root_w ? root_w[16 * m + 4 * r + (lane >> 4)] : 1.0) : 0.0;
-            s += w[r] * Larr[o + r * 64];
-        }
-        down_part(red, m, lane, s);
-        __syncthreads();
-        const double tot = down_total<NT>(red, lane & 15);
-        zero = !(tot > 0.0);
-        if (mv0 == 0) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Uarr[o + r * 64] = zero ? 0.0 : w[r] / tot;
-        }
-        if (writer && zero) atomicOr(&status[site], RT_SITE_ZERO_PROB);
-    }
+    // 1. root: the site's likelihood sum_states(w L), up = w / it; then the `up` vectors of the
+    // nodes with children, a parent before its children (shared with place.hip)
+    const bool zero = down_up_pass<NT, KS>(mv0 == 0, xb, red, tab, PfragT, nops, steps, Larr, Marr,
+                                           Uarr, og, root_w, live, m, lane, blk, nblocks, writer,
+                                           status, site);
     double a[2 * KP];
-    // 1. the `up` vectors of the nodes with children, a parent before its children
-    if (mv0 == 0)
-        for (int i = nops - 2; i >= 0; --i) {
-            const int4 st = steps[i];
-            if (!st.w) continue;
-            const size_t o = down_at<NT>(i, nblocks, blk, m, lane);
-            const size_t po = down_at<NT>(st.y, nblocks, blk, m, lane);
-            double x[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) x[r] = Uarr[po + r * 64];
-            const int kp = tab.obs[st.y];
-            if (kp >= 0) {
-                double ob[4];
-                down_L<KP>(kp, og, Larr, po, m, ob);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) x[r] *= ob[r];
-            }
-            for (int e = tab.cptr[st.y]; e < tab.cptr[st.y + 1]; ++e) {
-                const int w = tab.cidx[e];
-                if (w == i) continue;
-                const size_t wo = down_at<NT>(w, nblocks, blk, m, lane);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) x[r] *= Marr[wo + r * 64];
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) x[r] = live[r] ? x[r] : 0.0;     // (rows past the states)
-            down_stage(xb, m, lane, x);
-            down_frag<KP>(PfragT + (size_t)i * ASTRIDE + frag, a);
-            const double4_t acc = down_product<KS>(a, xb, lane);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Uarr[o + r * 64] = acc[r];
-        }
     // 2. the moves about every node v with children and siblings
     int par = 0;                                 // the half of `sums` the next chunk writes
     for (int i = nops - 2; i >= 0; --i) {
@@ -258,7 +201,7 @@ nni_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const dou
 {
     const long site = (long)blockIdx.x * 256 + threadIdx.x;
     if (site >= nsites) return;
-    const nni_tab tab(tabp, nnodes);
+    const post_tab tab(tabp, nnodes);
     auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
     auto node_obs = [&](int v, double (&x)[N]) {
         const int k = node_k[v];
@@ -270,38 +213,9 @@ nni_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const dou
     if (mv0 == 0)
         lane_up<N, true>(nnodes, nsites, site, P, parent, node_k, obs, compact, K, block_sites, Larr,
                          Marr);
-    double tot = 0.0;
-#pragma unroll
-    for (int s = 0; s < N; ++s) tot += (root_w ? root_w[s] : 1.0) * Larr[idx(0, s)];
-    const bool zero = !(tot > 0.0);
-    if (zero) status[site] |= RT_SITE_ZERO_PROB;
-    if (mv0 == 0) {
-        // the `up` vectors: the root, then every node with children after its parent
-#pragma unroll
-        for (int s = 0; s < N; ++s) Uarr[idx(0, s)] = zero ? 0.0 : (root_w ? root_w[s] : 1.0) / tot;
-        for (int v = 1; v < nnodes; ++v) {
-            if (tab.cptr[v + 1] == tab.cptr[v]) continue;
-            const int p = parent[v];
-            double x[N];
-            node_obs(p, x);
-#pragma unroll
-            for (int s = 0; s < N; ++s) x[s] *= Uarr[idx(p, s)];
-            for (int e = tab.cptr[p]; e < tab.cptr[p + 1]; ++e) {
-                const int w = tab.cidx[e];
-                if (w == v) continue;
-#pragma unroll
-                for (int s = 0; s < N; ++s) x[s] *= Marr[idx(w, s)];
-            }
-            const double *Pv = P + (size_t)v * N * N;
-#pragma unroll
-            for (int b = 0; b < N; ++b) {
-                double y = 0.0;
-#pragma unroll
-                for (int a = 0; a < N; ++a) y += Pv[a * N + b] * x[a];
-                Uarr[idx(v, b)] = y;
-            }
-        }
-    }
+    // the `up` vectors: the root, then every node with children after its parent
+    const bool zero = lane_up_pass<N>(mv0 == 0, nnodes, nsites, site, P, parent, node_k, tab, obs,
+                                      compact, K, block_sites, root_w, Larr, Marr, Uarr, status);
     for (int v = 1; v < nnodes; ++v) {
         const int p = parent[v];
         const int c0 = tab.cptr[v], c1 = tab.cptr[v + 1], s0 = tab.cptr[p], s1 = tab.cptr[p + 1];
@@ -498,27 +412,8 @@ extern "C" int rt_sites_nni_scores(rt_model *m, rt_sites *s, int recompute_trans
     if (lengths) RT_TRY(post_grid_launch(&p, &grid, lengths, has_move.data()));
     RT_TRY(post_up(&p, internal.data(), true));
     // the move tables, by step (n > 4) or by node
-    std::vector<int32_t> tab(tab_ints, 0), slot_of((size_t)N);
-    {
-        const rt_sites *x = p.lane ? s : p.x;
-        std::vector<int32_t> node_of((size_t)cnt), obs_of((size_t)N, -1);
-        for (int j = 0; j < cnt; ++j) node_of[(size_t)j] = p.lane ? j : x->ops[(size_t)j].node;
-        for (int j = 0; j < cnt; ++j) slot_of[(size_t)node_of[(size_t)j]] = j;
-        for (const rt_op &op : x->ops)
-            if (op.obs >= 0) obs_of[(size_t)op.node] = op.obs;
-        int32_t *t_obs = tab.data(), *t_cptr = t_obs + cnt, *t_first = t_cptr + cnt + 1;
-        int32_t *t_cidx = t_first + cnt;
-        int32_t e = 0;
-        for (int j = 0; j < cnt; ++j) {
-            const int64_t v = node_of[(size_t)j];
-            t_obs[j] = obs_of[(size_t)v];
-            t_first[j] = first[(size_t)v];
-            t_cptr[j] = e;
-            for (int64_t k = m->indptr[(size_t)v]; k < m->indptr[(size_t)v + 1]; ++k)
-                t_cidx[e++] = slot_of[(size_t)m->indices[(size_t)k]];
-        }
-        t_cptr[cnt] = e;
-    }
+    std::vector<int32_t> tab;
+    post_tab_build(&p, first.data(), &tab);
     RT_HIP(hipMemcpyAsync(d_tab, tab.data(), tab_ints * 4, hipMemcpyHostToDevice, st));
     if (!p.lane && lengths) RT_TRY(post_grid_pack(&p, &grid));
     for (int64_t mv0 = 0; mv0 == 0 || mv0 < nmoves; mv0 += CH) {

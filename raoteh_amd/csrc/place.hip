@@ -1,0 +1,614 @@
+// Query sequences placed on every branch of the model's tree on a RESIDENT batch
+// (rt_sites_placements): for every site i, query q, non-root node v, fraction rho_r and pendant
+// length tau_k,
+//     log L_i(tree with q placed at (v, rho_r, tau_k)) - log L_i,
+// the placement being a new node x that cuts the edge p -> v (p -> x of length rho t_v, x -> v of
+// length (1 - rho) t_v) with a new leaf below x on an edge of length tau that carries the query's
+// observation o_q; all three edges under the rate matrix Q_v of the cut edge.
+//
+// With L_w, M_w = P_w L_w of the stored upward pass and up_p the message into p = parent(v) from
+// above, normalised once at the root by 1 / L_i (the division-free `up` pass of nni.hip):
+//     A_v[a]       = up_p[a] obs_p[a] prod_{w child of p, w != v} M_w[a]
+//     F_{v,r}[b]   = (P_v(rho_r t_v)^T A_v)[b] (P_v((1 - rho_r) t_v) L_v)[b]     the field
+//     h_{d,k,q}[b] = sum_c expm(Q_d tau_k)[b][c] o_q[c]                        d = qidx(v)
+//     ratio        = sum_b F_{v,r}[b] h_{d,k,q}[b]
+// The field holds no query and the pendant vectors no edge: h is made once per DISTINCT rate
+// matrix in use, never once per edge.  Here:
+//
+//   1. P_v(rho_r t_v), P_v((1 - rho_r) t_v) and expm(Q_v tau_k) of every node in ONE launch of
+//      the model's own exponential (post_grid: 2 R + K points per node);
+//   2. n > 4: the upward pass with L and M of every step stored; place_field_kernel, one
+//      workgroup of NT row-tile waves per 16-site tile: the `up` pass, then per edge A_v and L_v
+//      staged and per fraction two matrix-pipe products, F to the scratch as [edge][fraction];
+//      per chunk of queries place_query_kernel (h per distinct matrix, pendant length and query:
+//      a matrix-pipe product for dense queries, a column or the row sums of the matrix for state
+//      queries) and place_score_kernel (PLACE_BLOCK vectors h in registers per walk of the
+//      field, the dot products on the vector ALU, the states summed in the fixed order of
+//      down_part / down_total, the logs by all lanes at the end);
+//      n <= 4: place_lane_kernel, one lane per site, the same three stages;
+//   3. place_sums_kernel: the site-weighted sums per (query, node, fraction, pendant length) in
+//      a fixed order; then, if the per-site array is asked for, its transpose.
+//
+// The field is made once; the queries go through 2 and 3 in chunks where the result of all of
+// them would not fit the scratch.  Nothing of the batch or the model is written; two calls give
+// the same bits, chunked or not.
+#include "common.h"
+#include "post_common.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <vector>
+
+namespace {
+
+constexpr int PLACE_BLOCK = 8;                   // (query, pendant) vectors held per walk of the field
+constexpr size_t PLACE_CHUNK_BYTES = (size_t)4 << 30;    // result bytes of one chunk of queries
+constexpr double PLACE_SCRATCH_CAP = 96e9;       // (post_begin's)
+constexpr int64_t PLACE_MAX_ROWS = (int64_t)1 << 21;     // rows of one transpose launch (grid y)
+
+// the stored value: 0 at a site of zero likelihood, else the log of the ratio (-inf where it is
+// not positive)
+__device__ __forceinline__ double place_value(double ratio, bool zero)
+{
+    if (zero) return 0.0;
+    return ratio > 0.0 ? log(ratio) : -__builtin_inf();
+}
+
+// n > 4.  steps as in nni_kernel (steps[i].w: the node has children); PfragT: [step] A fragments
+// of the resident P^T; GfragT: [fraction][step] those of P(rho t)^T; GfragA: [fraction][step]
+// those of P((1 - rho) t) itself; Uarr: the `up` vectors; Farr: the field,
+// [step * R + fraction] in the layout of L and M.
+template <int NT, int KS>
+__global__ void __launch_bounds__(64 * NT)
+place_field_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT,
+                   const double *__restrict__ GfragA, int R, int nops,
+                   const int4 *__restrict__ steps, const int *__restrict__ tabp,
+                   const double *__restrict__ Larr, const double *__restrict__ Marr,
+                   double *__restrict__ Uarr, const double *__restrict__ obs, int K,
+                   const double *__restrict__ root_w, int n, double *__restrict__ Farr,
+                   int *__restrict__ status, long nsites, long nblocks)
+{
+    constexpr int KP = (KS + 1) / 2;
+    __shared__ double xb[NT * 4 * 64];
+    __shared__ double lb[NT * 4 * 64];
+    __shared__ double red[NT][16];
+    const post_tab tab(tabp, nops);
+    const int lane = threadIdx.x & 63;
+    const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long blk = blockIdx.x;
+    const long site = blk * 16 + (lane & 15);
+    const bool writer = m == 0 && lane < 16 && site < nsites;
+    bool live[4];                                // own rows that are states
+#pragma unroll
+    for (int r = 0; r < 4; ++r) live[r] = 16 * m + 4 * r + (lane >> 4) < n;
+    const size_t frag = ((size_t)m * KP * 64 + lane) * 2;
+    constexpr size_t ASTRIDE = (size_t)NT * KP * 128;
+    const double *og = obs + (size_t)blk * K * (KP * 128) + lane * 2;
+    // 1. the `up` pass (nni_kernel's)
+    down_up_pass<NT, KS>(true, xb, red, tab, PfragT, nops, steps, Larr, Marr, Uarr, og, root_w, live,
+                         m, lane, blk, nblocks, writer, status, site);
+    // 2. the field of every edge: A_v and L_v staged once, two products per fraction
+    double a[2 * KP];
+    for (int i = nops - 2; i >= 0; --i) {
+        const int4 st = steps[i];
+        const int pi = st.y;
+        const size_t o = down_at<NT>(i, nblocks, blk, m, lane);
+        const size_t po = down_at<NT>(pi, nblocks, blk, m, lane);
+        double x[4], l[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) x[r] = Uarr[po + r * 64];
+        const int kp = tab.obs[pi];
+        if (kp >= 0) {
+            double ob[4];
+            down_L<KP>(kp, og, Larr, po, m, ob);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) x[r] *= ob[r];
+        }
+        for (int e = tab.cptr[pi]; e < tab.cptr[pi + 1]; ++e) {
+            const int w = tab.cidx[e];
+            if (w == i) continue;
+            const size_t wo = down_at<NT>(w, nblocks, blk, m, lane);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) x[r] *= Marr[wo + r * 64];
+        }
+        down_L<KP>(st.z, og, Larr, o, m, l);
+        __syncthreads();                         // (every wave is done with the previous operands)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {            // (rows past the states: 0)
+            xb[(4 * m + r) * 64 + lane] = live[r] ? x[r] : 0.0;
+            lb[(4 * m + r) * 64 + lane] = live[r] ? l[r] : 0.0;
+        }
+        __syncthreads();
+        for (int r = 0; r < R; ++r) {
+            down_frag<KP>(GfragT + ((size_t)r * nops + i) * ASTRIDE + frag, a);
+            const double4_t y = down_product<KS>(a, xb, lane);
+            down_frag<KP>(GfragA + ((size_t)r * nops + i) * ASTRIDE + frag, a);
+            const double4_t z = down_product<KS>(a, lb, lane);
+            const size_t fo = down_at<NT>(i * R + r, nblocks, blk, m, lane);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) Farr[fo + e * 64] = y[e] * z[e];
+        }
+    }
+}
+
+// n > 4, one workgroup per (tile, query of the chunk).  HfragA: [pendant][distinct] A fragments of
+// expm(Q_d tau_k); Gtau: the same matrices as the exponential left them, [pendant][node][n][n],
+// rep[d] the node that stands for distinct matrix d.  dense: queries f64[QC][nsites][n], staged
+// and multiplied on the matrix pipe; else uint8[QC][nsites]: column o of the matrix, or its row
+// sums where o >= n (unobserved).  Harr: [(d * K + k) * QC + q] in the layout of L and M.
+template <int NT, int KS>
+__global__ void __launch_bounds__(64 * NT)
+place_query_kernel(int dense, const void *__restrict__ queries, const double *__restrict__ HfragA,
+                   const double *__restrict__ Gtau, const int *__restrict__ rep, int nd, int K,
+                   int QC, int N, int n, double *__restrict__ Harr, long nsites, long nblocks)
+{
+    constexpr int KP = (KS + 1) / 2;
+    __shared__ double xb[NT * 4 * 64];
+    const int lane = threadIdx.x & 63;
+    const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long blk = blockIdx.x;
+    const int q = blockIdx.y;
+    const long site = blk * 16 + (lane & 15);
+    const bool site_ok = site < nsites;
+    const size_t frag = ((size_t)m * KP * 64 + lane) * 2;
+    constexpr size_t ASTRIDE = (size_t)NT * KP * 128;
+    if (dense) {
+        const double *qv = (const double *)queries + ((size_t)q * nsites + (site_ok ? site : 0)) * n;
+        double x[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * m + 4 * r + (lane >> 4);
+            x[r] = (site_ok && row < n) ? qv[row] : 0.0;
+        }
+        down_stage(xb, m, lane, x);
+        double a[2 * KP];
+        for (int d = 0; d < nd; ++d)
+            for (int k = 0; k < K; ++k) {
+                down_frag<KP>(HfragA + ((size_t)k * nd + d) * ASTRIDE + frag, a);
+                const double4_t y = down_product<KS>(a, xb, lane);
+                const size_t ho = down_at<NT>((d * K + k) * QC + q, nblocks, blk, m, lane);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) Harr[ho + e * 64] = y[e];
+            }
+    } else {
+        const int o = site_ok ? ((const unsigned char *)queries)[(size_t)q * nsites + site] : 255;
+        for (int d = 0; d < nd; ++d)
+            for (int k = 0; k < K; ++k) {
+                const double *G = Gtau + ((size_t)k * N + rep[d]) * n * n;
+                const size_t ho = down_at<NT>((d * K + k) * QC + q, nblocks, blk, m, lane);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = 16 * m + 4 * r + (lane >> 4);
+                    double y = 0.0;
+                    if (row < n) {
+                        if (o < n) y = G[(size_t)row * n + o];
+                        else
+                            for (int c = 0; c < n; ++c) y += G[(size_t)row * n + c];
+                    }
+                    Harr[ho + r * 64] = y;
+                }
+            }
+    }
+}
+
+// n > 4, one workgroup per (tile, block of PLACE_BLOCK (query, pendant) pairs of the chunk; pair
+// = q * K + k).  dslot[i]: the distinct matrix of step i's node.  Per distinct matrix the block's
+// vectors h are held in registers (four doubles per lane and vector) and the field of the edges
+// under that matrix is walked once: the dot products of own rows, the rows summed through the
+// halves of `sums` as in nni_kernel (wave 0 adds the waves in order and stores the ratio while
+// the next edge fills the other half).  out: [q][node][fraction][pendant][site]; the root's rows
+// are not written.  (PLACE_BLOCK = 8: 64 VGPRs of vectors; see profiles/placements_resource_usage.txt)
+template <int NT>
+__global__ void __launch_bounds__(64 * NT)
+place_score_kernel(int nops, int R, int K, int QC, int nd, const int4 *__restrict__ steps,
+                   const int *__restrict__ dslot, const double *__restrict__ Farr,
+                   const double *__restrict__ Harr, double *__restrict__ out,
+                   const int *__restrict__ status, int N, long nsites, long nblocks)
+{
+    __shared__ double sums[2][PLACE_BLOCK][NT][16];
+    const int lane = threadIdx.x & 63;
+    const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long blk = blockIdx.x;
+    const long site = blk * 16 + (lane & 15);
+    const bool site_ok = site < nsites;
+    const bool writer = m == 0 && lane < 16 && site_ok;
+    const int pairs = QC * K;
+    const int j0 = blockIdx.y * PLACE_BLOCK;
+    const int cnt = min(PLACE_BLOCK, pairs - j0);
+    const size_t NRK = (size_t)N * R * K;
+    int par = 0;                                 // the half of `sums` the next edge writes
+    for (int d = 0; d < nd; ++d) {
+        double h[PLACE_BLOCK][4];
+#pragma unroll
+        for (int j = 0; j < PLACE_BLOCK; ++j) {
+            const int pair = min(j0 + j, pairs - 1);
+            const int q = pair / K, k = pair - q * K;
+            const size_t ho = down_at<NT>((d * K + k) * QC + q, nblocks, blk, m, lane);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) h[j][e] = Harr[ho + e * 64];
+        }
+        for (int i = nops - 2; i >= 0; --i) {
+            if (dslot[i] != d) continue;
+            const int v = steps[i].x;
+            for (int r = 0; r < R; ++r) {
+                const size_t fo = down_at<NT>(i * R + r, nblocks, blk, m, lane);
+                double f[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) f[e] = Farr[fo + e * 64];
+#pragma unroll
+                for (int j = 0; j < PLACE_BLOCK; ++j) {
+                    double t = 0.0;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) t += f[e] * h[j][e];
+                    down_part(sums[par][j], m, lane, t);
+                }
+                __syncthreads();
+                if (writer)
+                    for (int j = 0; j < cnt; ++j) {
+                        const int pair = j0 + j;
+                        const int q = pair / K, k = pair - q * K;
+                        out[((size_t)q * NRK + ((size_t)v * R + r) * K + k) * nsites + site] =
+                            down_total<NT>(sums[par][j], lane);
+                    }
+                par ^= 1;
+            }
+        }
+    }
+    // the block's ratios -> values, by all waves: lane group g of the workgroup takes the rows
+    // g, g + 4 NT, ... of its site (the barrier: wave 0's stores are visible)
+    __syncthreads();
+    if (site_ok) {
+        const bool zero = status[site] & RT_SITE_ZERO_PROB;
+        const long per = (long)(N - 1) * R;
+        for (long t = 4 * m + (lane >> 4); t < (long)cnt * per; t += 4 * NT) {
+            const int j = (int)(t / per);
+            const long vr = t - (long)j * per + R;         // (v * R + r, v >= 1)
+            const int pair = j0 + j;
+            const int q = pair / K, k = pair - q * K;
+            double *x = out + ((size_t)q * NRK + (size_t)vr * K + k) * nsites + site;
+            *x = place_value(*x, zero);
+        }
+    }
+}
+
+// n <= 4: one lane per site; arrays [node][state][site], nodes in preorder; G [point][node][N][N]:
+// the points 0 .. R - 1 are P(rho t), R .. 2 R - 1 are P((1 - rho) t), 2 R .. 2 R + K - 1 are
+// expm(Q tau) (the same address in every lane: the scalar path); Farr [node * R + fraction][N][site];
+// dnode[v] the distinct matrix of node v, rep[d] the node that stands for it.  make: the first
+// chunk makes the upward pass, the `up` pass and the field, later ones find them.
+template <int N>
+__global__ void __launch_bounds__(256)
+place_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const double *__restrict__ G,
+                  int R, int K, const int *__restrict__ parent, const int *__restrict__ node_k,
+                  const int *__restrict__ tabp, const int *__restrict__ dnode,
+                  const int *__restrict__ rep, int nd, const void *__restrict__ obs, int compact,
+                  int Kobs, int block_sites, const double *__restrict__ root_w,
+                  double *__restrict__ Larr, double *__restrict__ Marr, double *__restrict__ Uarr,
+                  double *__restrict__ Farr, int dense, const void *__restrict__ queries, int QC,
+                  int make, double *__restrict__ out, int *__restrict__ status)
+{
+    const long site = (long)blockIdx.x * 256 + threadIdx.x;
+    if (site >= nsites) return;
+    const post_tab tab(tabp, nnodes);
+    auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
+    if (make)
+        lane_up<N, true>(nnodes, nsites, site, P, parent, node_k, obs, compact, Kobs, block_sites, Larr,
+                         Marr);
+    const bool zero = lane_up_pass<N>(make != 0, nnodes, nsites, site, P, parent, node_k, tab, obs,
+                                      compact, Kobs, block_sites, root_w, Larr, Marr, Uarr, status);
+    if (make)
+        for (int v = 1; v < nnodes; ++v) {
+            const int p = parent[v];
+            double x[N], l[N];
+            const int kp = node_k[p];
+            if (kp >= 0) lane_obs<N>(obs, compact, Kobs, block_sites, site, kp, x);
+            else
+#pragma unroll
+                for (int s = 0; s < N; ++s) x[s] = 1.0;
+#pragma unroll
+            for (int s = 0; s < N; ++s) {
+                x[s] *= Uarr[idx(p, s)];
+                l[s] = Larr[idx(v, s)];
+            }
+            for (int e = tab.cptr[p]; e < tab.cptr[p + 1]; ++e) {
+                const int w = tab.cidx[e];
+                if (w == v) continue;
+#pragma unroll
+                for (int s = 0; s < N; ++s) x[s] *= Marr[idx(w, s)];
+            }
+            for (int r = 0; r < R; ++r) {
+                const double *G1 = G + ((size_t)r * nnodes + v) * N * N;
+                const double *G2 = G + ((size_t)(R + r) * nnodes + v) * N * N;
+#pragma unroll
+                for (int b = 0; b < N; ++b) {
+                    double y = 0.0, z = 0.0;
+#pragma unroll
+                    for (int a = 0; a < N; ++a) {
+                        y += G1[a * N + b] * x[a];
+                        z += G2[b * N + a] * l[a];
+                    }
+                    Farr[idx(v * R + r, b)] = y * z;
+                }
+            }
+        }
+    const size_t NRK = (size_t)nnodes * R * K;
+    for (int q = 0; q < QC; ++q) {
+        double oq[N];
+        if (dense) {
+            const double *qv = (const double *)queries + ((size_t)q * nsites + site) * N;
+#pragma unroll
+            for (int s = 0; s < N; ++s) oq[s] = qv[s];
+        } else {
+            const unsigned o = ((const unsigned char *)queries)[(size_t)q * nsites + site];
+#pragma unroll
+            for (int s = 0; s < N; ++s) oq[s] = (o >= (unsigned)N || o == (unsigned)s) ? 1.0 : 0.0;
+        }
+        for (int d = 0; d < nd; ++d)
+            for (int k = 0; k < K; ++k) {
+                const double *Gh = G + ((size_t)(2 * R + k) * nnodes + rep[d]) * N * N;
+                double h[N];
+#pragma unroll
+                for (int b = 0; b < N; ++b) {
+                    double y = 0.0;
+#pragma unroll
+                    for (int c = 0; c < N; ++c) y += Gh[b * N + c] * oq[c];
+                    h[b] = y;
+                }
+                for (int v = 1; v < nnodes; ++v) {
+                    if (dnode[v] != d) continue;
+                    for (int r = 0; r < R; ++r) {
+                        double t = 0.0;
+#pragma unroll
+                        for (int b = 0; b < N; ++b) t += Farr[idx(v * R + r, b)] * h[b];
+                        out[((size_t)q * NRK + ((size_t)v * R + r) * K + k) * nsites + site] =
+                            place_value(t, zero);
+                    }
+                }
+            }
+    }
+}
+
+// one workgroup per (query, node, fraction, pendant length), the order of profile_sums_kernel:
+// thread j adds sites j, j + 256, ... in order, then the 256 partial sums by halves (fixed
+// rounding).  Sites of zero likelihood and of weight 0 are skipped.
+__global__ void __launch_bounds__(256)
+place_sums_kernel(long nsites, const double *__restrict__ values, const double *__restrict__ weights,
+                  const int *__restrict__ status, double *__restrict__ sums)
+{
+    __shared__ double part[256];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const double *x = values + (size_t)row * nsites;
+    double acc = 0.0;
+    for (long i = tid; i < nsites; i += 256) {
+        const double w = weights ? weights[i] : 1.0;       // (w = 0: not -inf * 0 = NaN)
+        if (w != 0.0 && !(status[i] & RT_SITE_ZERO_PROB)) acc += w * x[i];
+    }
+    part[tid] = acc;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) part[tid] += part[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) sums[row] = part[0];
+}
+
+}  // namespace
+
+extern "C" int rt_sites_placements(rt_model *m, rt_sites *s, int recompute_transitions,
+                                   int64_t nqueries, int query_kind, const void *queries,
+                                   int64_t nfractions, const double *fractions, int64_t npendant,
+                                   const double *pendant, double *values, double *sums,
+                                   int32_t *status)
+{
+    const char *who = "rt_sites_placements";
+    post_pass p;                                 // (alive until the synchronisation below)
+    RT_TRY(post_open(&p, who, m, s));
+    const int64_t n = p.n, N = p.N, nsites = p.nsites;
+    RT_REQUIRE(nqueries >= 1, "%s: at least one query (%lld here)", who, (long long)nqueries);
+    if (query_kind == RT_OBS_MASK) {
+        rt_set_error("%s: RT_OBS_MASK queries are not taken (RT_OBS_DENSE or RT_OBS_STATE)", who);
+        return RT_ERR_UNSUPPORTED;
+    }
+    RT_REQUIRE(query_kind == RT_OBS_DENSE || query_kind == RT_OBS_STATE, "%s: query_kind %d", who,
+               query_kind);
+    RT_REQUIRE(queries && fractions && pendant, "%s: queries, fractions or pendant is NULL", who);
+    RT_REQUIRE(nfractions >= 1 && nfractions <= RT_MAX_PLACE_FRACTIONS,
+               "%s: 1..%d fractions (%lld here)", who, RT_MAX_PLACE_FRACTIONS, (long long)nfractions);
+    RT_REQUIRE(npendant >= 1 && npendant <= RT_MAX_PLACE_PENDANT,
+               "%s: 1..%d pendant lengths (%lld here)", who, RT_MAX_PLACE_PENDANT, (long long)npendant);
+    RT_REQUIRE(2 * nfractions + npendant <= 32, "%s: 2 nfractions + npendant is at most 32 "
+               "(%lld here)", who, (long long)(2 * nfractions + npendant));
+    for (int64_t r = 0; r < nfractions; ++r)
+        RT_REQUIRE(std::isfinite(fractions[r]) && fractions[r] >= 0.0 && fractions[r] <= 1.0,
+                   "%s: fraction %d is outside [0, 1] or not finite", who, (int)r);
+    for (int64_t k = 0; k < npendant; ++k)
+        RT_REQUIRE(std::isfinite(pendant[k]) && pendant[k] >= 0.0,
+                   "%s: pendant length %d is negative or not finite", who, (int)k);
+    const int R = (int)nfractions, K = (int)npendant, np = 2 * R + K;
+    RT_TRY(post_layout(&p, true));
+    // the grid of every node: rho_r t_v, (1 - rho_r) t_v, tau_k
+    std::vector<double> lengths((size_t)N * np, 0.0);
+    if (post_model_has_rates(m))
+        for (int64_t v = 1; v < N; ++v) {
+            double *row = lengths.data() + (size_t)v * np;
+            const double t = m->h_t[(size_t)v];
+            for (int r = 0; r < R; ++r) {
+                row[r] = fractions[r] * t;
+                row[R + r] = (1.0 - fractions[r]) * t;
+            }
+            for (int k = 0; k < K; ++k) row[2 * R + k] = pendant[k];
+        }
+    RT_TRY(post_grid_check(&p, recompute_transitions, np, lengths.data()));
+    const int64_t NRK = N * R * K;
+    RT_REQUIRE(NRK < (int64_t)1 << 31, "%s: too many placements per query", who);
+    post_plan &plan = p.plan;
+    post_grid grid;                              // (alive until the synchronisation below)
+    RT_TRY(post_grid_take(&p, &grid, np));
+    // the distinct rate matrices in use: d of every node, the node that stands for d
+    std::vector<int32_t> dnode((size_t)N, -1), rep;
+    {
+        std::vector<int32_t> d_of_q;
+        for (int64_t v = 1; v < N; ++v) {
+            const int64_t qi = m->h_qidx[(size_t)v];
+            if (qi < 0) continue;
+            if ((int64_t)d_of_q.size() <= qi) d_of_q.resize((size_t)qi + 1, -1);
+            if (d_of_q[(size_t)qi] < 0) {
+                d_of_q[(size_t)qi] = (int32_t)rep.size();
+                rep.push_back((int32_t)v);
+            }
+            dnode[(size_t)v] = d_of_q[(size_t)qi];
+        }
+    }
+    const int nd = (int)rep.size();
+    RT_REQUIRE(nd >= 1 && (p.lane || (int64_t)nd <= (int64_t)p.nops), "%s: no rate matrix in use", who);
+    const int cnt = p.lane ? (int)N : p.nops;    // slots of the tables
+    const size_t o_tab = plan.take((size_t)4 * cnt * 4);
+    const size_t o_dtab = plan.take(((size_t)cnt + nd) * 4);
+    const size_t tile = p.lane ? 0 : (size_t)s->nblocks * p.NT * 256 * 8;    // one vector of every site
+    const size_t o_F = plan.take(p.lane ? (size_t)N * R * n * nsites * 8 : (size_t)p.nops * R * tile);
+    const size_t o_sum = plan.take((size_t)nqueries * NRK * 8);
+    // the queries of one chunk: their result (and its transpose) within the chunk size, and with
+    // their pendant vectors and their own image within the cap
+    const size_t per_result = (size_t)NRK * nsites * 8 * (values ? 2 : 1);
+    const size_t q_bytes = (size_t)nsites * (query_kind == RT_OBS_DENSE ? (size_t)n * 8 : 1);
+    const size_t per_query = per_result + q_bytes + 512 + (p.lane ? 0 : (size_t)nd * K * tile);
+    size_t chunk_bytes = PLACE_CHUNK_BYTES;
+    if (const char *e = getenv("RAOTEH_PLACE_CHUNK_BYTES")) {    // (tests: many chunks at small sizes)
+        const long long v = atoll(e);
+        if (v > 0) chunk_bytes = (size_t)v;
+    }
+    const double room = PLACE_SCRATCH_CAP - (double)plan.total - 4096.0;
+    int64_t CH = std::max<int64_t>(1, (int64_t)(chunk_bytes / per_result));
+    CH = std::min<int64_t>(CH, std::max<int64_t>(1, (int64_t)(room > 0.0 ? room / (double)per_query : 0.0)));
+    CH = std::min<int64_t>(CH, 32768);           // (the grids' y)
+    CH = std::min<int64_t>(CH, nqueries);
+    const size_t chunk_rows = (size_t)CH * NRK;
+    const size_t o_q = plan.take((size_t)CH * q_bytes);
+    const size_t o_H = plan.take(p.lane ? 8 : (size_t)nd * K * CH * tile);
+    const size_t o_val = plan.take(chunk_rows * nsites * 8);
+    const size_t o_valT = plan.take(values ? std::min<size_t>(chunk_rows, PLACE_MAX_ROWS) * nsites * 8 : 8);
+    RT_TRY(post_begin(&p, recompute_transitions));
+    hipStream_t st = p.st;
+    unsigned char *base = p.base;
+    double *d_val = (double *)(base + o_val), *d_valT = (double *)(base + o_valT);
+    double *d_sum = (double *)(base + o_sum), *d_F = (double *)(base + o_F), *d_H = (double *)(base + o_H);
+    int *d_tab = (int *)(base + o_tab), *d_dtab = (int *)(base + o_dtab);
+    void *d_q = (void *)(base + o_q);
+    int *d_status = p.d_status;
+    std::vector<int32_t> internal((size_t)N, 0);
+    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
+    RT_TRY(post_grid_launch(&p, &grid, lengths.data()));
+    RT_TRY(post_up(&p, internal.data(), true));
+    std::vector<int32_t> tab, dtab((size_t)cnt + nd, -1);
+    post_tab_build(&p, nullptr, &tab);
+    for (int j = 0; j < cnt; ++j) dtab[(size_t)j] = dnode[(size_t)(p.lane ? j : p.x->ops[(size_t)j].node)];
+    for (int d = 0; d < nd; ++d) dtab[(size_t)cnt + d] = rep[(size_t)d];
+    RT_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemcpyAsync(d_dtab, dtab.data(), dtab.size() * 4, hipMemcpyHostToDevice, st));
+    const size_t nn = (size_t)n * n;
+    // n > 4: the fragment tables in the grid's own piece, [point][step]: P(rho t)^T at the points
+    // 0 .. R - 1, P((1 - rho) t) at R .. 2 R - 1, and expm(Q_d tau_k) as [k][d] from point 2 R on
+    const size_t ftab = p.lane ? 0 : (size_t)p.nops * p.NT * p.KP * 128;
+    const double *d_HfragA = p.lane ? nullptr : grid.d_GT + (size_t)2 * R * ftab;
+    if (!p.lane) {
+        const size_t dfrag = (size_t)p.NT * p.KP * 128;
+        for (int r = 0; r < R; ++r) {
+            RT_TRY(rt_launch_pack_pt(p.ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab,
+                                     grid.d_G + (size_t)r * N * nn, grid.d_GT + (size_t)r * ftab));
+            RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab,
+                                    grid.d_G + (size_t)(R + r) * N * nn,
+                                    grid.d_GT + (size_t)(R + r) * ftab));
+        }
+        if (query_kind == RT_OBS_DENSE)
+            for (int k = 0; k < K; ++k)
+                RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, nd, d_dtab + cnt,
+                                        grid.d_G + (size_t)(2 * R + k) * N * nn,
+                                        grid.d_GT + (size_t)2 * R * ftab + (size_t)k * nd * dfrag));
+        // the field, once
+        const rt_sites *x = p.x;
+        RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
+            constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
+            hipLaunchKernelGGL((place_field_kernel<NT, KS>), dim3((unsigned)x->nblocks), dim3(64 * NT), 0,
+                               st, (const double *)p.d_PT, (const double *)grid.d_GT,
+                               (const double *)(grid.d_GT + (size_t)R * ftab), R, p.nops,
+                               (const int4 *)p.d_steps, (const int *)d_tab, (const double *)p.d_L,
+                               (const double *)p.d_M, p.d_D, (const double *)x->d_obs, (int)x->nobs,
+                               (const double *)m->d_root, (int)n, d_F, d_status, (long)x->nsites,
+                               (long)x->nblocks);
+            return RT_OK;
+        }));
+        RT_HIP(hipGetLastError());
+    }
+    const int dense = query_kind == RT_OBS_DENSE;
+    for (int64_t q0 = 0; q0 < nqueries; q0 += CH) {
+        const int QC = (int)std::min<int64_t>(CH, nqueries - q0);
+        const size_t rows = (size_t)QC * NRK;
+        RT_HIP(hipMemcpyAsync(d_q, (const unsigned char *)queries + (size_t)q0 * q_bytes,
+                              (size_t)QC * q_bytes, hipMemcpyHostToDevice, st));
+        RT_HIP(hipMemsetAsync(d_val, 0, rows * nsites * 8, st));       // (the root's rows)
+        if (p.lane) {
+            const int *d_ptab = p.d_ptab;
+            RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
+                hipLaunchKernelGGL((place_lane_kernel<decltype(nv)::value>),
+                                   dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)N,
+                                   (long)nsites, (const double *)m->d_P, (const double *)grid.d_G, R, K,
+                                   d_ptab, d_ptab + N, (const int *)d_tab, (const int *)d_dtab,
+                                   (const int *)(d_dtab + cnt), nd, (const void *)s->d_obs,
+                                   s->compact_states, (int)s->nobs, s->block_sites,
+                                   (const double *)m->d_root, p.d_L, p.d_M, p.d_D, d_F, dense,
+                                   (const void *)d_q, QC, q0 == 0 ? 1 : 0, d_val, d_status);
+                return RT_OK;
+            }));
+        } else {
+            const rt_sites *x = p.x;
+            RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
+                constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
+                hipLaunchKernelGGL((place_query_kernel<NT, KS>),
+                                   dim3((unsigned)x->nblocks, (unsigned)QC), dim3(64 * NT), 0, st, dense,
+                                   (const void *)d_q, d_HfragA,
+                                   (const double *)(grid.d_G + (size_t)2 * R * N * nn),
+                                   (const int *)(d_dtab + cnt), nd, K, QC, (int)N, (int)n, d_H,
+                                   (long)x->nsites, (long)x->nblocks);
+                return RT_OK;
+            }));
+            RT_HIP(hipGetLastError());
+            RT_TRY(post_dispatch<1, 8>(p.NT, [&](auto nt) {
+                constexpr int NT = decltype(nt)::value;
+                hipLaunchKernelGGL((place_score_kernel<NT>),
+                                   dim3((unsigned)x->nblocks,
+                                        (unsigned)(((size_t)QC * K + PLACE_BLOCK - 1) / PLACE_BLOCK)),
+                                   dim3(64 * NT), 0, st, p.nops, R, K, QC, nd, (const int4 *)p.d_steps,
+                                   (const int *)d_dtab, (const double *)d_F, (const double *)d_H, d_val,
+                                   (const int *)d_status, (int)N, (long)x->nsites, (long)x->nblocks);
+                return RT_OK;
+            }));
+        }
+        RT_HIP(hipGetLastError());
+        // 3. the weighted site sums; only what was asked for crosses PCIe
+        if (sums) {
+            hipLaunchKernelGGL(place_sums_kernel, dim3((unsigned)rows), dim3(256), 0, st, (long)nsites,
+                               (const double *)d_val, (const double *)s->d_weights,
+                               (const int *)d_status, d_sum + (size_t)q0 * NRK);
+            RT_HIP(hipGetLastError());
+        }
+        if (values)
+            for (size_t r0 = 0; r0 < rows; r0 += (size_t)PLACE_MAX_ROWS) {
+                const size_t nr = std::min<size_t>((size_t)PLACE_MAX_ROWS, rows - r0);
+                hipLaunchKernelGGL(post_transpose_kernel<32>,
+                                   dim3((unsigned)((nsites + 31) / 32), (unsigned)((nr + 31) / 32)),
+                                   dim3(256), 0, st, (long)nr, (long)nsites,
+                                   (const double *)(d_val + r0 * nsites), d_valT);
+                RT_HIP(hipGetLastError());
+                // [site][rows of the slab] into the caller's [site][nqueries][N][R][K]
+                RT_HIP(hipMemcpy2DAsync(values + (size_t)q0 * NRK + r0, (size_t)nqueries * NRK * 8,
+                                        d_valT, nr * 8, nr * 8, (size_t)nsites, hipMemcpyDeviceToHost,
+                                        st));
+            }
+    }
+    if (sums)
+        RT_HIP(hipMemcpyAsync(sums, d_sum, (size_t)nqueries * NRK * 8, hipMemcpyDeviceToHost, st));
+    if (status) RT_HIP(hipMemcpyAsync(status, d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipStreamSynchronize(st));
+    RT_TRY(post_grid_result(&p, &grid));
+    return RT_OK;
+}

@@ -1,5 +1,5 @@
 // What the reads of a RESIDENT batch share (posterior.hip, branch_expect.hip, branch_profile.hip,
-// nni.hip, sample.hip, mapping.hip).  Host: post_pass, one description of such a call -- its
+// nni.hip, place.hip, sample.hip, mapping.hip).  Host: post_pass, one description of such a call -- its
 // checks, the common pieces of its scratch, the upward pass with L (and M) of every step stored
 // (the plan of the scratch and the dispatch over the kernels' template arguments: common.h);
 // post_grid, the trial lengths of the edges through the model's own exponential.  Device: the
@@ -567,6 +567,169 @@ __device__ __forceinline__ double4_t down_product(const double (&a)[2 * ((KS + 1
     for (int kk = 0; kk < KS; ++kk)
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], xb[kk * 64 + lane], acc, 0, 0, 0);
     return acc;
+}
+
+// ---- the division-free `up` pass (nni.hip, place.hip) ----
+
+// The child tables of such a pass, over slots j = 0 .. cnt - 1 (n > 4: schedule steps; n <= 4:
+// preorder nodes):
+//   obs[j]          stream position of the slot's node, a leaf or an observed INTERNAL node (the
+//                   shared step table has the leaves' only), or -1
+//   cptr[j], cidx   the slots of its children in the CSR child order
+//   first[j]        a per-slot number of the caller's (nni.hip: the index of its first move)
+struct post_tab {
+    const int *obs, *cptr, *first, *cidx;
+    __host__ __device__ post_tab(const int *t, int cnt)
+        : obs(t), cptr(t + cnt), first(t + 2 * cnt + 1), cidx(t + 3 * cnt + 1) {}
+};
+
+// the host image of a post_tab (4 cnt ints), by step (n > 4, after post_begin) or by node;
+// first [nnodes] or null (zeros)
+inline void post_tab_build(const post_pass *p, const int32_t *first, std::vector<int32_t> *tab)
+{
+    const rt_model *m = p->m;
+    const int64_t N = p->N;
+    const int cnt = p->lane ? (int)N : p->nops;
+    const rt_sites *x = p->lane ? p->s : p->x;
+    tab->assign((size_t)4 * cnt, 0);
+    std::vector<int32_t> node_of((size_t)cnt), obs_of((size_t)N, -1), slot_of((size_t)N);
+    for (int j = 0; j < cnt; ++j) node_of[(size_t)j] = p->lane ? j : x->ops[(size_t)j].node;
+    for (int j = 0; j < cnt; ++j) slot_of[(size_t)node_of[(size_t)j]] = j;
+    for (const rt_op &op : x->ops)
+        if (op.obs >= 0) obs_of[(size_t)op.node] = op.obs;
+    int32_t *t_obs = tab->data(), *t_cptr = t_obs + cnt, *t_first = t_cptr + cnt + 1;
+    int32_t *t_cidx = t_first + cnt;
+    int32_t e = 0;
+    for (int j = 0; j < cnt; ++j) {
+        const int64_t v = node_of[(size_t)j];
+        t_obs[j] = obs_of[(size_t)v];
+        t_first[j] = first ? first[(size_t)v] : 0;
+        t_cptr[j] = e;
+        for (int64_t k = m->indptr[(size_t)v]; k < m->indptr[(size_t)v + 1]; ++k)
+            t_cidx[e++] = slot_of[(size_t)m->indices[(size_t)k]];
+    }
+    t_cptr[cnt] = e;
+}
+
+// n > 4.  The root: the site's likelihood sum_states(w L), true where it is not positive (the
+// status is set), and with `make` up_root = w / it; then the `up` vectors of the nodes with
+// children (steps[i].w), a parent before its children:
+//     up_v[b] = sum_a P_v[a][b] up_p[a] obs_p[a] prod_{w child of p, w != v} M_w[a].
+// make = false: a later launch that finds them in Uarr.  PfragT: [step] A fragments of the
+// resident P^T; live: own rows that are states.
+template <int NT, int KS>
+__device__ __forceinline__ bool down_up_pass(bool make, double *xb, double (*red)[16],
+                                             const post_tab &tab, const double *PfragT, int nops,
+                                             const int4 *steps, const double *Larr,
+                                             const double *Marr, double *Uarr, const double *og,
+                                             const double *root_w, const bool (&live)[4], int m,
+                                             int lane, long blk, long nblocks, bool writer,
+                                             int *status, long site)
+{
+    constexpr int KP = (KS + 1) / 2;
+    const size_t frag = ((size_t)m * KP * 64 + lane) * 2;
+    constexpr size_t ASTRIDE = (size_t)NT * KP * 128;
+    bool zero;
+    {
+        const int i = nops - 1;
+        const size_t o = down_at<NT>(i, nblocks, blk, m, lane);
+        double w[4], s = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            w[r] = live[r] ? (root_w ? root_w[16 * m + 4 * r + (lane >> 4)] : 1.0) : 0.0;
+            s += w[r] * Larr[o + r * 64];
+        }
+        down_part(red, m, lane, s);
+        __syncthreads();
+        const double tot = down_total<NT>(red, lane & 15);
+        zero = !(tot > 0.0);
+        if (make) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Uarr[o + r * 64] = zero ? 0.0 : w[r] / tot;
+        }
+        if (writer && zero) atomicOr(&status[site], RT_SITE_ZERO_PROB);
+    }
+    if (!make) return zero;
+    double a[2 * KP];
+    for (int i = nops - 2; i >= 0; --i) {
+        const int4 st = steps[i];
+        if (!st.w) continue;
+        const size_t o = down_at<NT>(i, nblocks, blk, m, lane);
+        const size_t po = down_at<NT>(st.y, nblocks, blk, m, lane);
+        double x[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) x[r] = Uarr[po + r * 64];
+        const int kp = tab.obs[st.y];
+        if (kp >= 0) {
+            double ob[4];
+            down_L<KP>(kp, og, Larr, po, m, ob);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) x[r] *= ob[r];
+        }
+        for (int e = tab.cptr[st.y]; e < tab.cptr[st.y + 1]; ++e) {
+            const int w = tab.cidx[e];
+            if (w == i) continue;
+            const size_t wo = down_at<NT>(w, nblocks, blk, m, lane);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) x[r] *= Marr[wo + r * 64];
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) x[r] = live[r] ? x[r] : 0.0;     // (rows past the states)
+        down_stage(xb, m, lane, x);
+        down_frag<KP>(PfragT + (size_t)i * ASTRIDE + frag, a);
+        const double4_t acc = down_product<KS>(a, xb, lane);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Uarr[o + r * 64] = acc[r];
+    }
+    return zero;
+}
+
+// n <= 4, after lane_up<N, true>: the site's likelihood (true where it is not positive; the status
+// is set), and with `make` the `up` vectors of the root and of every node with children
+template <int N>
+__device__ __forceinline__ bool lane_up_pass(bool make, int nnodes, long nsites, long site,
+                                             const double *P, const int *parent, const int *node_k,
+                                             const post_tab &tab, const void *obs, int compact, int K,
+                                             int block_sites, const double *root_w,
+                                             const double *Larr, const double *Marr, double *Uarr,
+                                             int *status)
+{
+    auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
+    double tot = 0.0;
+#pragma unroll
+    for (int s = 0; s < N; ++s) tot += (root_w ? root_w[s] : 1.0) * Larr[idx(0, s)];
+    const bool zero = !(tot > 0.0);
+    if (zero) status[site] |= RT_SITE_ZERO_PROB;
+    if (!make) return zero;
+#pragma unroll
+    for (int s = 0; s < N; ++s) Uarr[idx(0, s)] = zero ? 0.0 : (root_w ? root_w[s] : 1.0) / tot;
+    for (int v = 1; v < nnodes; ++v) {
+        if (tab.cptr[v + 1] == tab.cptr[v]) continue;
+        const int p = parent[v];
+        double x[N];
+        const int k = node_k[p];
+        if (k >= 0) lane_obs<N>(obs, compact, K, block_sites, site, k, x);
+        else
+#pragma unroll
+            for (int s = 0; s < N; ++s) x[s] = 1.0;
+#pragma unroll
+        for (int s = 0; s < N; ++s) x[s] *= Uarr[idx(p, s)];
+        for (int e = tab.cptr[p]; e < tab.cptr[p + 1]; ++e) {
+            const int w = tab.cidx[e];
+            if (w == v) continue;
+#pragma unroll
+            for (int s = 0; s < N; ++s) x[s] *= Marr[idx(w, s)];
+        }
+        const double *Pv = P + (size_t)v * N * N;
+#pragma unroll
+        for (int b = 0; b < N; ++b) {
+            double y = 0.0;
+#pragma unroll
+            for (int a = 0; a < N; ++a) y += Pv[a * N + b] * x[a];
+            Uarr[idx(v, b)] = y;
+        }
+    }
+    return zero;
 }
 
 // [row][site] -> [site][row] for a caller's per-site array, 32 x 32 tiles through LDS (TILE = 32;

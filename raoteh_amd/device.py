@@ -326,6 +326,46 @@ def tree_nni_moves(tree):
     return moves
 
 
+# TreeModel.place_queries: fractions [R] and pendant [K] as evaluated, sums [Q, nnodes, R, K],
+# values [nsites, Q, nnodes, R, K] (or None) with values[i, q, v, r, k] = log L_i(tree with query q
+# placed at (v, fractions[r], pendant[k])) - log L_i (the root's row: 0), status as Posteriors,
+# best int[Q, 3]: the arg-max (v, r, k) of sums per query, ties to the lowest index
+Placements = collections.namedtuple('Placements', 'fractions pendant sums values status best')
+
+
+def check_placement_grid(fractions, pendant):
+    """The attachment grid of TreeModel.place_queries -> (fractions f64[R], pendant f64[K]),
+    C-contiguous, for rt_sites_placements.  ValueError unless both are 1-D sequences of numbers,
+    1 <= R <= RT_MAX_PLACE_FRACTIONS, 1 <= K <= RT_MAX_PLACE_PENDANT, 2 R + K <= 32, every
+    fraction finite and in [0, 1], every pendant length finite and not negative."""
+    out = []
+    for name, seq in (('fractions', fractions), ('pendant', pendant)):
+        if seq is None:
+            raise ValueError('%s is None' % name)
+        try:
+            x = np.array(seq, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('%s must be a 1-D sequence of numbers' % name)
+        if x.ndim != 1:
+            raise ValueError('%s must be 1-D, not %s' % (name, x.shape))
+        out.append(np.ascontiguousarray(x))
+    f, t = out
+    if not 1 <= len(f) <= _lib.RT_MAX_PLACE_FRACTIONS:
+        raise ValueError('between 1 and %d fractions (%d here)'
+                         % (_lib.RT_MAX_PLACE_FRACTIONS, len(f)))
+    if not 1 <= len(t) <= _lib.RT_MAX_PLACE_PENDANT:
+        raise ValueError('between 1 and %d pendant lengths (%d here)'
+                         % (_lib.RT_MAX_PLACE_PENDANT, len(t)))
+    if 2 * len(f) + len(t) > 32:
+        raise ValueError('2 * fractions + pendant lengths is at most 32 (%d here)'
+                         % (2 * len(f) + len(t)))
+    if not (np.isfinite(f).all() and (f >= 0).all() and (f <= 1).all()):
+        raise ValueError('the fractions must be finite and in [0, 1]')
+    if not (np.isfinite(t).all() and (t >= 0).all()):
+        raise ValueError('the pendant lengths must be finite and not negative')
+    return f, t
+
+
 def check_draws(ndraws, seed, first_draw):
     """The draw arguments of sample_states / sample_mappings as ints; ValueError unless there is
     at least one draw and the seed and every draw number fit an unsigned 64-bit integer."""
@@ -1520,6 +1560,58 @@ class TreeModel(object):
             except (ValueError, _lib.RaotehHipError):
                 grid = None
         return NniScores(moves, grid, sums, values, status)
+
+    def place_queries(self, batch, queries, kind='dense', fractions=(0.5,), pendant=None,
+                      per_site=False, recompute_transitions=False):
+        """rt_sites_placements: every query placed on every branch -- for query q, non-root
+        node v, fraction r and pendant length k the change of the log-likelihood when a new
+        node cuts the edge above v at fractions[r] of its length (from the parent) and the
+        query hangs below it on an edge of length pendant[k], all under the rate matrix of the
+        cut edge -- in one call instead of a model build, an upload and a step per candidate.
+        queries: kind 'dense', f64 [Q, nsites, n] likelihood vectors, or 'state', uint8
+        [Q, nsites] (255 or -1: unobserved, as for upload_sites); fractions and pendant as check_placement_grid
+        takes them, pendant=None the one value mean(branch_lengths()[1:]).  Returns a Placements
+        tuple: fractions, pendant, sums [Q, nnodes, R, K] the site-weighted sums
+        (SiteBatch.set_weights), values [nsites, Q, nnodes, R, K] (None unless per_site),
+        status, best [Q, 3] the arg-max (v, r, k) of sums per query (ties to the lowest index;
+        _tree.place_apply adopts it).  The root's row is 0 and never the best; -inf where the
+        query's column is impossible given the reference column."""
+        ta = self.tree
+        N, S, n = ta.nnodes, batch.nsites, self.nstates
+        if pendant is None:
+            pendant = [float(np.mean(self.branch_lengths()[1:]))] if N > 1 else [0.0]
+        f, t = check_placement_grid(fractions, pendant)
+        if kind == 'dense':
+            q = np.ascontiguousarray(queries, dtype=np.float64)
+            if q.ndim != 3 or q.shape[1:] != (S, n):
+                raise ValueError('dense queries must be [Q, %d, %d], not %s' % (S, n, q.shape))
+            code = _lib.RT_OBS_DENSE
+        elif kind == 'state':
+            q = np.asarray(queries)
+            if q.ndim != 2 or q.shape[1] != S:
+                raise ValueError('state queries must be [Q, %d], not %s' % (S, q.shape))
+            q = _as_uint8_states(q, n)
+            code = _lib.RT_OBS_STATE
+        else:
+            raise ValueError("queries of kind 'dense' or 'state', not %r" % (kind,))
+        Q, R, K = q.shape[0], len(f), len(t)
+        if Q < 1:
+            raise ValueError('at least one query')
+        values = np.zeros((S, Q, N, R, K)) if per_site else None
+        sums = np.zeros((Q, N, R, K))
+        status = np.zeros(S, dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_placements(
+            self._h, batch._h, 1 if recompute_transitions else 0, Q, code,
+            q.ctypes.data_as(ctypes.c_void_p), R, _ptr(f, c_double), K, _ptr(t, c_double),
+            None if values is None else _ptr(values, c_double), _ptr(sums, c_double),
+            _ptr(status, c_int32)))
+        best = np.zeros((Q, 3), dtype=np.int64)
+        if N > 1:
+            flat = sums[:, 1:].reshape(Q, -1)
+            flat = np.where(np.isnan(flat), -np.inf, flat)
+            v, r, k = np.unravel_index(np.argmax(flat, axis=1), (N - 1, R, K))
+            best = np.stack([v + 1, r, k], axis=1).astype(np.int64)
+        return Placements(f, t, sums, values, status, best)
 
     def branch_length_gradient(self, batch, recompute_transitions=False):
         """d (sum_i w_i log L_i) / d t_v for every branch, f64[nnodes] in preorder (0 at the
