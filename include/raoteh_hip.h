@@ -617,6 +617,79 @@ int rt_sites_placements(rt_model *model, rt_sites *sites, int recompute_transiti
             int64_t nfractions, const double *fractions,
             int64_t npendant, const double *pendant,
             double *values, double *sums, int32_t *status);
+/* Subtree pruning and regrafting (SPR): every move of the tree within a radius scored on a
+ * RESIDENT batch, without one model build, upload and rt_step per candidate.  Nodes are preorder
+ * indices.  A move is (c, y) with a fraction rho: c is a non-root node, v = parent(c); y is a
+ * non-root node outside the subtree of c, q = parent(y).  The subtree of c leaves v and keeps its
+ * own edge (length, rate matrix and transition matrix go with the node below the edge, as in an
+ * NNI); a new unobserved node x cuts q -> y into q -> x of length rho t_y and x -> y of length
+ * (1 - rho) t_y, both under Q_y as in a placement, and c hangs below x.  v stays with one child
+ * fewer -- a single-child or childless node where that leaves one or none (an unobserved
+ * childless node contributes ones); no edges are merged: with per-edge rate matrices merging is
+ * not defined, and a single-child node has the same likelihood.  The definition is ROOTED, as
+ * for NNI and placements, because rate matrices need not be reversible.
+ * The radius of a move is d(c, y) = min(dist(v, y), dist(v, parent(y))) in edges of the tree:
+ * d = 0 for the edge above v and the edges above the siblings of c, d = 1 for the edge above
+ * parent(v), those above the siblings of v and those above the children of the siblings of c,
+ * and so on outward.  radius >= 0 lists every (c, y) with d <= radius; radius < 0 means no limit:
+ * nmoves = sum_{c != root} (nnodes - 1 - |subtree(c)|).  The list goes by c ascending, then by y
+ * ascending: a pure function of topology and radius.  Two families of moves leave the tree
+ * unchanged and stay in the list: y = v at rho = 1, and y a sibling of c at rho = 0 (x coincides
+ * with v across an identity matrix; their values are 0 to rounding).  Other moves onto those
+ * edges only slide c along an edge where v has two children; they are scored like any other.
+ * rt_model_spr_moves / rt_tree_spr_moves (from a CSR alone) are host only: moves
+ * int32[capacity][2] receives the pairs (c, y) and *nmoves their number; moves == NULL asks for
+ * the number alone; RT_ERR_INVALID, with *nmoves set, where capacity is short; RT_ERR_INVALID
+ * for a CSR that is no tree (a child before its parent, a child listed twice).                */
+int rt_model_spr_moves(const rt_model *model, int64_t radius, int32_t *moves, int64_t capacity,
+            int64_t *nmoves);
+int rt_tree_spr_moves(int64_t nnodes, const int64_t *tree_csr_indices, const int64_t *tree_csr_indptr,
+            int64_t radius, int32_t *moves, int64_t capacity, int64_t *nmoves);
+/* The moves of rt_model_spr_moves(model, radius) scored.  For site i:
+ *   values[i][mv][r] = log L_i(tree after move mv at fractions[r]) - log L_i
+ *                      f64[nsites][nmoves][nfractions]; -inf where a live site has likelihood 0
+ *                      after the move
+ *   sums[mv][r]      = sum_i w_i values[i][mv][r]          f64[nmoves][nfractions]
+ *                      (w: rt_sites_set_weights, default 1; reduced on the device, fixed order;
+ *                      sites of weight 0 and of zero likelihood add nothing)
+ *   status[i]        : as for rt_sites_nni_scores: a site of zero likelihood has
+ *                      RT_SITE_ZERO_PROB, its values are 0
+ * fractions f64[nfractions], each in [0, 1], 1..RT_MAX_PLACE_FRACTIONS of them.  Per node the
+ * lengths rho_r t and (1 - rho_r) t are the grid of ONE launch of the model's exponential
+ * (fractions 0 and 1 go through it like any other length), from rt_model_set_rates (per-edge rate
+ * matrices included) or rt_model_set_rates_spectral (n <= 64).
+ * With L_w, M_w = P_w L_w, obs_w of the stored upward pass, up_w the message into w from above,
+ * normalised once at the root by 1 / L_i, and a_0 = v, a_1 = parent(v), ... the path to the root:
+ *   L-_{a_0}[b]  = obs_v[b] prod_{w child of v, w != c} M_w[b]
+ *   M-_{a_j}     = P_{a_j} L-_{a_j}
+ *   L-_{a_j}[b]  = obs_{a_j}[b] M-_{a_{j-1}}[b] prod_{w child of a_j, w != a_{j-1}} M_w[b]
+ *   up-_{a_j}    = up_{a_j}             (an ancestor's message from above holds no c)
+ *   off the path: L-_x = L_x, M-_x = M_x,
+ *   A-_x[a]      = up-_q[a] obs_q[a] prod_{w child of q, w not in {x, c}} M-_w[a]   (q = parent(x))
+ *   up-_x        = P_x^T A-_x
+ *   F_{c,y,r}[b] = (P_y(rho_r t_y)^T A-_y)[b] (P_y((1 - rho_r) t_y) L-_y)[b]
+ *   ratio        = sum_b F_{c,y,r}[b] M_c[b]
+ * Nothing is divided, so the result is exact where transition matrices or observations have
+ * zeros and at resident lengths of 0.  Work per pruned node is bounded by the radius: only path
+ * nodes and off-path nodes within it are touched.  values, sums and status may each be NULL;
+ * only what is given crosses PCIe.  Every batch rt_sites_placements takes.  nmoves == 0 (two
+ * nodes) returns RT_OK with the status alone.  Where the per-site result of all moves would not
+ * fit the scratch the pruned nodes go through the device in chunks (RAOTEH_SPR_CHUNK_BYTES of
+ * result per chunk, default 4 GB, or what the 96 GB cap leaves); a chunk never splits the moves
+ * of one pruned node, and chunked and unchunked calls give the same bits.
+ * RT_ERR_INVALID: nfractions out of range, a fraction outside [0, 1] or not finite, NULL
+ * fractions, a model without rates (or whose transitions were set directly after them, with
+ * recompute_transitions == 0), a batch of another model, 2^31 or more (move, fraction) pairs.
+ * RT_ERR_SINGULAR: an exponential failed; nothing returned is usable then.  RT_ERR_UNSUPPORTED:
+ * a partitioned batch, a "rescale" batch, a batch of the generic kernel, a tree deeper than the
+ * fast kernels take, nnodes < 2, more than 96 GB of scratch.  Synchronous; the model keeps its
+ * transitions and the batch its kernel, log-likelihoods, status and totals; two calls return
+ * the same bits.  Not done here: trial lengths for the pruned edge or lengths optimised after
+ * the move (rt_sites_branch_profiles on the adopted tree), partitioned and mixture batches,
+ * unrooted de-duplication of moves.                                                           */
+int rt_sites_spr_scores(rt_model *model, rt_sites *sites, int recompute_transitions,
+            int64_t radius, int64_t nfractions, const double *fractions,
+            double *values, double *sums, int32_t *status);
 /* _sample_mcy_dense.resample_states (_sample_mcy_dense.py:23-69, through
  * _sample_mc0_dense.resample_states, _sample_mc0_dense.py:20-98) for every site of a RESIDENT
  * batch: ndraws joint draws of a state for every node from the posterior given the observations.

@@ -147,6 +147,10 @@ SIGNATURES = {
                                     _p_i32]),
     'rt_sites_placements': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_int64,
                                     _p_f64, c_int64, _p_f64, _p_f64, _p_f64, _p_i32]),
+    'rt_model_spr_moves': (c_int, [c_void_p, c_int64, _p_i32, c_int64, _p_i64]),
+    'rt_tree_spr_moves': (c_int, [c_int64, _p_i64, _p_i64, c_int64, _p_i32, c_int64, _p_i64]),
+    'rt_sites_spr_scores': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, _p_f64, _p_f64,
+                                    _p_f64, _p_i32]),
     'rt_sites_sample_states': (c_int, [c_void_p, c_void_p, c_int, ctypes.c_uint64,
                                        ctypes.c_uint64, c_int64, POINTER(c_ubyte), _p_i32]),
     'rt_sample_states_draw_block': (c_int, [c_int64]),

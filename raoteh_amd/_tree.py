@@ -10,7 +10,8 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ['TreeArrays', 'marshal_tree', 'check_square_dense', 'nni_apply', 'place_apply']
+__all__ = ['TreeArrays', 'marshal_tree', 'check_square_dense', 'nni_apply', 'place_apply',
+           'spr_apply']
 
 
 def check_square_dense(M):
@@ -202,5 +203,59 @@ def place_apply(T, root, v, fraction, pendant, label, cut_label=None):
             out.add_edge(ta.preorder_nodes[a], cut_label, **dict(data, weight=fraction * t))
             out.add_edge(cut_label, v, **dict(data, weight=(1.0 - fraction) * t))
             out.add_edge(cut_label, label, **dict(data, weight=pendant))
+        stack.extend(reversed(kids))
+    return out
+
+
+def spr_apply(T, root, c, y, fraction, cut_label=None):
+    """The tree after the move (c, y) of rt_sites_spr_scores at `fraction`, on node LABELS of the
+    networkx tree T rooted at `root`: the subtree of c leaves its parent and comes with every
+    attribute of its edge; a new node `cut_label` (default ('cut', c)) cuts the edge q-y,
+    q = parent(y), at `fraction` of its length from q, and c hangs below it.  A new graph of
+    T's class with T's node and graph attributes; the cut node stands in the place of y among
+    the children of q, y is its first child and c its second; the parent of c keeps its other
+    children.  Every attribute of the edge q-y is copied to its two halves (its rate matrix
+    'Q' among them), and 'weight', the length TreeArrays.branch_lengths reads, is set to
+    fraction * t and (1 - fraction) * t, as place_apply splits an edge.  ValueError for an
+    unknown node, the root as c or y, y inside the subtree of c, a label already in the tree,
+    or a fraction outside [0, 1]."""
+    ta = TreeArrays(T, root)
+    idx = ta.node_to_index
+    for x in (c, y):
+        if x not in idx:
+            raise ValueError('%r is not a node of the tree' % (x,))
+    ic, iy = idx[c], idx[y]
+    if ic == 0 or iy == 0:
+        raise ValueError('the root is neither pruned nor below an edge to regraft on')
+    a = iy
+    while a >= 0:
+        if a == ic:
+            raise ValueError('%r lies in the subtree of %r' % (y, c))
+        a = int(ta.parent[a])
+    if cut_label is None:
+        cut_label = ('cut', c)
+    if cut_label in idx:
+        raise ValueError('the label %r must be new' % (cut_label,))
+    fraction = float(fraction)
+    if not 0.0 <= fraction <= 1.0:
+        raise ValueError('the fraction %r is outside [0, 1]' % (fraction,))
+    data = dict(ta.edge_data[iy])
+    t = data.get('weight', 0.0)
+    out = T.__class__()
+    out.graph.update(T.graph)
+    out.add_nodes_from((x, dict(T.nodes[x])) for x in ta.preorder_nodes)
+    stack = [0]
+    while stack:
+        a = stack.pop()
+        kids = [int(b) for b in ta.indices[ta.indptr[a]:ta.indptr[a + 1]]]
+        for b in kids:
+            if b == ic:
+                continue
+            if b != iy:
+                out.add_edge(ta.preorder_nodes[a], ta.preorder_nodes[b], **dict(ta.edge_data[b]))
+                continue
+            out.add_edge(ta.preorder_nodes[a], cut_label, **dict(data, weight=fraction * t))
+            out.add_edge(cut_label, y, **dict(data, weight=(1.0 - fraction) * t))
+            out.add_edge(cut_label, c, **dict(ta.edge_data[ic]))
         stack.extend(reversed(kids))
     return out

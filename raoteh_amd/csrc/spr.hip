@@ -1,0 +1,846 @@
+// Every subtree pruning and regrafting (SPR) move of the model's tree scored on a RESIDENT batch
+// (rt_sites_spr_scores): for every site i, every move (c, y) within the radius and every
+// fraction rho_r,
+//     log L_i(tree after the move) - log L_i,
+// the move being: the subtree of the non-root node c leaves v = parent(c) with its own edge, a new
+// unobserved node x cuts the edge q -> y (y non-root, outside the subtree of c; q -> x of length
+// rho t_y, x -> y of length (1 - rho) t_y, both under Q_y) and c hangs below x.  v stays, with
+// one child fewer.
+//
+// A move is a placement (place.hip) whose "query" is the stored message M_c of the pruned
+// subtree; what is new is the field of the target edge on the tree WITHOUT the subtree.  With
+// L_w, M_w = P_w L_w, obs_w of the stored upward pass, up_w of the division-free `up` pass
+// (normalised once at the root by 1 / L_i) and a_0 = v, a_1 = parent(v), ... the path to the root:
+//     L-_{a_0}[b] = obs_v[b] prod_{w child of v, w != c} M_w[b]
+//     M-_{a_j}    = P_{a_j} L-_{a_j}
+//     L-_{a_j}[b] = obs_{a_j}[b] M-_{a_{j-1}}[b] prod_{w child of a_j, w != a_{j-1}} M_w[b]
+//     up-_{a_j}   = up_{a_j}                (an ancestor's message from above holds no c)
+//     off the path: L-_x = L_x, M-_x = M_x,
+//     A-_x[a]     = up-_q[a] obs_q[a] prod_{w child of q, w not in {x, c}} M-_w[a]    (q = parent(x))
+//     up-_x       = P_x^T A-_x
+//     F_{c,y,r}[b] = (P_y(rho_r t_y)^T A-_y)[b] (P_y((1 - rho_r) t_y) L-_y)[b]
+//     ratio       = sum_b F_{c,y,r}[b] M_c[b]
+// Nothing is divided.  The host plans the walk of every pruned node as a table of ops (spr_plan):
+// path steps up from v as far as the radius needs them, then in depth-first order one op per
+// target edge -- A-_y staged once, the `up-` product where targets lie below y, two products per
+// fraction where y is a target itself.  L- / M- of the path and up- per depth level live in a
+// scratch of the call in the layout of L and M: every lane reads back only what it wrote.  Here:
+//
+//   1. P_y(rho_r t_y) and P_y((1 - rho_r) t_y) of every node in ONE launch of the model's own
+//      exponential (post_grid: 2 R points per node);
+//   2. n > 4: the upward pass with L and M of every step stored; spr_up_kernel (the `up` pass,
+//      down_up_pass unchanged); per chunk of pruned nodes spr_kernel, one workgroup of NT row-tile
+//      waves per (16-site tile, group of pruned nodes): group g walks the ops of the pruned
+//      nodes c0 + g, c0 + g + G, ... of the chunk in its own piece of the scratch;
+//      n <= 4: spr_lane_up_kernel and spr_lane_kernel, one lane per site, the same walk;
+//   3. spr_sums_kernel: the site-weighted sums per (move, fraction) in a fixed order; then, if the
+//      per-site array is asked for, its transpose to [site][move][fraction].
+//
+// Steps 2 (the walk) and 3 run per chunk of pruned nodes where the result of all moves would not
+// fit the scratch; a chunk never splits the moves of one pruned node.  Nothing of the batch or the
+// model is written; two calls give the same bits, chunked or not, whatever the number of groups.
+#include "common.h"
+#include "post_common.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <vector>
+
+namespace {
+
+constexpr size_t SPR_CHUNK_BYTES = (size_t)4 << 30;      // result bytes of one chunk of pruned nodes
+constexpr double SPR_SCRATCH_CAP = 96e9;         // (post_begin's)
+constexpr int64_t SPR_MAX_ROWS = (int64_t)1 << 21;       // rows of one transpose launch (grid y)
+constexpr size_t SPR_LEVEL_BYTES = (size_t)2 << 30;      // the level vectors of all groups
+constexpr int SPR_R = RT_MAX_PLACE_FRACTIONS;
+
+// the stored value: 0 at a site of zero likelihood, else the log of the ratio (-inf where it is
+// not positive)
+__device__ __forceinline__ double spr_value(double ratio, bool zero)
+{
+    if (zero) return 0.0;
+    return ratio > 0.0 ? log(ratio) : -__builtin_inf();
+}
+
+// One op of the walk of a pruned node, three int4 on the device.  Slots are schedule steps (n > 4)
+// or preorder nodes (n <= 4); levels index the group's scratch.
+//   path step (kind 0): L- of the path node at slot i into level ldst, from the node's
+//       observation and the messages of its children but the pruned one -- the path child at slot
+//       pw (or -1) from level psrc instead of the stored pass; M- = P L- into level mdst (or -1)
+//   edge (kind 1): A- of the node y at slot i below the parent at slot pi -- up- of the parent
+//       from level usrc, or the stored `up` (usrc = -1: the parent is on the path); the parent's
+//       children but y and the pruned node, the path child pw from level psrc; up-_y = P_y^T A-
+//       into level udst (or -1); and the move itself (the planner makes an edge op for targets
+//       only, so mv >= 0): L-_y from level lsrc (y on the path) or the stored pass (lsrc = -1),
+//       the ratios of move mv at every fraction
+struct spr_op {
+    int32_t kind, i, pi, mv;
+    int32_t usrc, udst, pw, psrc;                // (path step: usrc is mdst, udst is ldst)
+    int32_t lsrc, pad0, pad1, pad2;
+};
+static_assert(sizeof(spr_op) == 48, "three int4 per op");
+
+// the pruned node c on the device: {slot of c, first op, one past the last op, first move}
+// (entry nnodes: the number of moves)
+
+// n > 4: the `up` pass alone, for every group of spr_kernel to find
+template <int NT, int KS>
+__global__ void __launch_bounds__(64 * NT)
+spr_up_kernel(const double *__restrict__ PfragT, int nops, const int4 *__restrict__ steps,
+              const int *__restrict__ tabp, const double *__restrict__ Larr,
+              const double *__restrict__ Marr, double *__restrict__ Uarr,
+              const double *__restrict__ obs, int K, const double *__restrict__ root_w, int n,
+              int *__restrict__ status, long nsites, long nblocks)
+{
+    constexpr int KP = (KS + 1) / 2;
+    __shared__ double xb[NT * 4 * 64];
+    __shared__ double red[NT][16];
+    const post_tab tab(tabp, nops);
+    const int lane = threadIdx.x & 63;
+    const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long blk = blockIdx.x;
+    const long site = blk * 16 + (lane & 15);
+    const bool writer = m == 0 && lane < 16 && site < nsites;
+    bool live[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) live[r] = 16 * m + 4 * r + (lane >> 4) < n;
+    const double *og = obs + (size_t)blk * K * (KP * 128) + lane * 2;
+    down_up_pass<NT, KS>(true, xb, red, tab, PfragT, nops, steps, Larr, Marr, Uarr, og, root_w, live,
+                         m, lane, blk, nblocks, writer, status, site);
+}
+
+// n > 4, one workgroup per (tile, group).  steps as in nni_kernel; PfragT / PfragA: [step] A
+// fragments of the resident P^T / P; GfragT: [fraction][step] those of P(rho t)^T; GfragA:
+// [fraction][step] those of P((1 - rho) t); Uarr: the `up` vectors of spr_up_kernel; S: the level
+// vectors, [group][level] in the layout of L and M; cut, ops: the plan; out
+// [move - mvA][fraction][site] for the moves of the pruned nodes cA .. cB - 1.
+template <int NT, int KS>
+__global__ void __launch_bounds__(64 * NT)
+spr_kernel(const double *__restrict__ PfragT, const double *__restrict__ PfragA,
+           const double *__restrict__ GfragT, const double *__restrict__ GfragA, int R, int nops,
+           const int4 *__restrict__ steps, const int *__restrict__ tabp,
+           const int4 *__restrict__ cut, const int4 *__restrict__ ops,
+           const double *__restrict__ Larr, const double *__restrict__ Marr,
+           const double *__restrict__ Uarr, double *S, int nlevels,
+           const double *__restrict__ obs, int K, const double *__restrict__ root_w, int n, int cA,
+           int cB, int mvA, double *__restrict__ out, int *__restrict__ status, long nsites,
+           long nblocks)
+{
+    constexpr int KP = (KS + 1) / 2;
+    __shared__ double xb[NT * 4 * 64];
+    __shared__ double lb[NT * 4 * 64];
+    __shared__ double red[NT][16];
+    __shared__ double sums[2][SPR_R][NT][16];
+    const post_tab tab(tabp, nops);
+    const int lane = threadIdx.x & 63;
+    const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long blk = blockIdx.x;
+    const long site = blk * 16 + (lane & 15);
+    const bool site_ok = site < nsites;
+    const bool writer = m == 0 && lane < 16 && site_ok;
+    bool live[4];                                // own rows that are states
+#pragma unroll
+    for (int r = 0; r < 4; ++r) live[r] = 16 * m + 4 * r + (lane >> 4) < n;
+    const size_t frag = ((size_t)m * KP * 64 + lane) * 2;
+    constexpr size_t ASTRIDE = (size_t)NT * KP * 128;
+    const double *og = obs + (size_t)blk * K * (KP * 128) + lane * 2;
+    // the site's likelihood (the `up` vectors are spr_up_kernel's)
+    const bool zero = down_up_pass<NT, KS>(false, xb, red, tab, PfragT, nops, steps, Larr, Marr,
+                                           nullptr, og, root_w, live, m, lane, blk, nblocks, writer,
+                                           status, site);
+    const int lv0 = blockIdx.y * nlevels;        // the group's levels
+    double a[2 * KP];
+    int par = 0;                                 // the half of `sums` the next move writes
+    for (int c = cA + blockIdx.y; c < cB; c += gridDim.y) {
+        const int4 ct = cut[c];
+        if (ct.y == ct.z) continue;
+        const int ci = ct.x;
+        double mc[4];                            // the pruned subtree's message
+        {
+            const size_t co = down_at<NT>(ci, nblocks, blk, m, lane);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) mc[r] = live[r] ? Marr[co + r * 64] : 0.0;
+        }
+        for (int o = ct.y; o < ct.z; ++o) {
+            const int4 oa = ops[3 * o], ob4 = ops[3 * o + 1];
+            const int kind = oa.x, i = oa.y, pi = oa.z, mv = oa.w;
+            const int usrc = ob4.x, udst = ob4.y, pw = ob4.z, psrc = ob4.w;
+            const size_t io = down_at<NT>(i, nblocks, blk, m, lane);
+            const size_t pso = down_at<NT>(lv0 + max(psrc, 0), nblocks, blk, m, lane);
+            double x[4];
+            if (kind == 0) {
+                // L- of a path node, then M- = P L-
+                const int k = tab.obs[i];
+                if (k >= 0) down_L<KP>(k, og, Larr, io, m, x);
+                else
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) x[r] = 1.0;
+                for (int e = tab.cptr[i]; e < tab.cptr[i + 1]; ++e) {
+                    const int w = tab.cidx[e];
+                    if (w == ci) continue;
+                    const double *src = w == pw ? S + pso
+                                                : Marr + down_at<NT>(w, nblocks, blk, m, lane);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) x[r] *= src[r * 64];
+                }
+                const size_t lo = down_at<NT>(lv0 + udst, nblocks, blk, m, lane);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    x[r] = live[r] ? x[r] : 0.0;     // (rows past the states)
+                    S[lo + r * 64] = x[r];
+                }
+                if (usrc >= 0) {
+                    down_stage(xb, m, lane, x);
+                    down_frag<KP>(PfragA + (size_t)i * ASTRIDE + frag, a);
+                    const double4_t y = down_product<KS>(a, xb, lane);
+                    const size_t mo = down_at<NT>(lv0 + usrc, nblocks, blk, m, lane);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) S[mo + r * 64] = y[r];
+                }
+                continue;
+            }
+            // A- of the edge above the node at slot i
+            const size_t po = down_at<NT>(pi, nblocks, blk, m, lane);
+            {
+                const double *us = usrc < 0 ? Uarr + po
+                                            : S + down_at<NT>(lv0 + usrc, nblocks, blk, m, lane);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) x[r] = us[r * 64];
+            }
+            const int kp = tab.obs[pi];
+            if (kp >= 0) {
+                double ob[4];
+                down_L<KP>(kp, og, Larr, po, m, ob);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) x[r] *= ob[r];
+            }
+            for (int e = tab.cptr[pi]; e < tab.cptr[pi + 1]; ++e) {
+                const int w = tab.cidx[e];
+                if (w == i || w == ci) continue;
+                const double *src = w == pw ? S + pso : Marr + down_at<NT>(w, nblocks, blk, m, lane);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) x[r] *= src[r * 64];
+            }
+            double l[4];
+            const int lsrc = ops[3 * o + 2].x;
+            if (lsrc >= 0) {
+                const size_t lo = down_at<NT>(lv0 + lsrc, nblocks, blk, m, lane);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) l[r] = S[lo + r * 64];
+            } else {
+                down_L<KP>(steps[i].z, og, Larr, io, m, l);
+            }
+            __syncthreads();                     // (every wave is done with the previous operands)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {        // (rows past the states: 0)
+                xb[(4 * m + r) * 64 + lane] = live[r] ? x[r] : 0.0;
+                lb[(4 * m + r) * 64 + lane] = live[r] ? l[r] : 0.0;
+            }
+            __syncthreads();
+            if (udst >= 0) {
+                down_frag<KP>(PfragT + (size_t)i * ASTRIDE + frag, a);
+                const double4_t y = down_product<KS>(a, xb, lane);
+                const size_t uo = down_at<NT>(lv0 + udst, nblocks, blk, m, lane);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) S[uo + r * 64] = y[r];
+            }
+            for (int r = 0; r < R; ++r) {
+                down_frag<KP>(GfragT + ((size_t)r * nops + i) * ASTRIDE + frag, a);
+                const double4_t y = down_product<KS>(a, xb, lane);
+                down_frag<KP>(GfragA + ((size_t)r * nops + i) * ASTRIDE + frag, a);
+                const double4_t z = down_product<KS>(a, lb, lane);
+                double t = 0.0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) t += y[e] * z[e] * mc[e];
+                down_part(sums[par][r], m, lane, t);
+            }
+            __syncthreads();
+            if (writer) {
+                double *row = out + (size_t)(mv - mvA) * R * nsites + site;
+                for (int r = 0; r < R; ++r) row[(size_t)r * nsites] = down_total<NT>(sums[par][r], lane);
+            }
+            par ^= 1;
+        }
+        // the pruned node's ratios -> values, by all waves: lane group g of the workgroup takes
+        // the rows g, g + 4 NT, ... of its site (the barrier: wave 0's stores are visible)
+        __syncthreads();
+        if (site_ok) {
+            const long r0 = (long)(ct.w - mvA) * R, r1 = (long)(cut[c + 1].w - mvA) * R;
+            for (long r = r0 + 4 * m + (lane >> 4); r < r1; r += 4 * NT) {
+                double *x = out + (size_t)r * nsites + site;
+                *x = spr_value(*x, zero);
+            }
+        }
+    }
+}
+
+// n <= 4: the upward pass and the `up` pass, one lane per site
+template <int N>
+__global__ void __launch_bounds__(256)
+spr_lane_up_kernel(int nnodes, long nsites, const double *__restrict__ P,
+                   const int *__restrict__ parent, const int *__restrict__ node_k,
+                   const int *__restrict__ tabp, const void *__restrict__ obs, int compact, int Kobs,
+                   int block_sites, const double *__restrict__ root_w, double *__restrict__ Larr,
+                   double *__restrict__ Marr, double *__restrict__ Uarr, int *__restrict__ status)
+{
+    const long site = (long)blockIdx.x * 256 + threadIdx.x;
+    if (site >= nsites) return;
+    const post_tab tab(tabp, nnodes);
+    lane_up<N, true>(nnodes, nsites, site, P, parent, node_k, obs, compact, Kobs, block_sites, Larr, Marr);
+    lane_up_pass<N>(true, nnodes, nsites, site, P, parent, node_k, tab, obs, compact, Kobs,
+                    block_sites, root_w, Larr, Marr, Uarr, status);
+}
+
+// n <= 4: one lane per (site, group); arrays [node][state][site], nodes in preorder; G
+// [point][node][N][N]: the points 0 .. R - 1 are P(rho t), R .. 2 R - 1 are P((1 - rho) t) (the
+// same address in every lane: the scalar path); S [group][level][state][site]
+template <int N>
+__global__ void __launch_bounds__(256)
+spr_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const double *__restrict__ G,
+                int R, const int *__restrict__ parent, const int *__restrict__ node_k,
+                const int *__restrict__ tabp, const int4 *__restrict__ cut,
+                const int4 *__restrict__ ops, const void *__restrict__ obs, int compact, int Kobs,
+                int block_sites, const double *__restrict__ root_w, const double *__restrict__ Larr,
+                const double *__restrict__ Marr, const double *__restrict__ Uarr, double *S,
+                int nlevels, int cA, int cB, int mvA, double *__restrict__ out,
+                int *__restrict__ status)
+{
+    const long site = (long)blockIdx.x * 256 + threadIdx.x;
+    if (site >= nsites) return;
+    const post_tab tab(tabp, nnodes);
+    auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
+    const int lv0 = blockIdx.y * nlevels;
+    auto lev = [&](int level, int s) { return ((size_t)(lv0 + level) * N + s) * nsites + site; };
+    auto node_obs = [&](int v, double (&x)[N]) {
+        const int k = node_k[v];
+        if (k >= 0) lane_obs<N>(obs, compact, Kobs, block_sites, site, k, x);
+        else
+#pragma unroll
+            for (int s = 0; s < N; ++s) x[s] = 1.0;
+    };
+    const bool zero = lane_up_pass<N>(false, nnodes, nsites, site, P, parent, node_k, tab, obs, compact,
+                                      Kobs, block_sites, root_w, Larr, Marr, nullptr, status);
+    for (int c = cA + blockIdx.y; c < cB; c += gridDim.y) {
+        const int4 ct = cut[c];
+        const int ci = ct.x;
+        double mc[N];
+#pragma unroll
+        for (int s = 0; s < N; ++s) mc[s] = Marr[idx(ci, s)];
+        for (int o = ct.y; o < ct.z; ++o) {
+            const int4 oa = ops[3 * o], ob4 = ops[3 * o + 1];
+            const int kind = oa.x, i = oa.y, pi = oa.z, mv = oa.w;
+            const int usrc = ob4.x, udst = ob4.y, pw = ob4.z, psrc = ob4.w;
+            double x[N];
+            if (kind == 0) {
+                node_obs(i, x);
+                for (int e = tab.cptr[i]; e < tab.cptr[i + 1]; ++e) {
+                    const int w = tab.cidx[e];
+                    if (w == ci) continue;
+#pragma unroll
+                    for (int s = 0; s < N; ++s) x[s] *= w == pw ? S[lev(psrc, s)] : Marr[idx(w, s)];
+                }
+#pragma unroll
+                for (int s = 0; s < N; ++s) S[lev(udst, s)] = x[s];
+                if (usrc >= 0) {
+                    const double *Pv = P + (size_t)i * N * N;
+#pragma unroll
+                    for (int a = 0; a < N; ++a) {
+                        double t = 0.0;
+#pragma unroll
+                        for (int b = 0; b < N; ++b) t += Pv[a * N + b] * x[b];
+                        S[lev(usrc, a)] = t;
+                    }
+                }
+                continue;
+            }
+            node_obs(pi, x);
+#pragma unroll
+            for (int s = 0; s < N; ++s) x[s] *= usrc < 0 ? Uarr[idx(pi, s)] : S[lev(usrc, s)];
+            for (int e = tab.cptr[pi]; e < tab.cptr[pi + 1]; ++e) {
+                const int w = tab.cidx[e];
+                if (w == i || w == ci) continue;
+#pragma unroll
+                for (int s = 0; s < N; ++s) x[s] *= w == pw ? S[lev(psrc, s)] : Marr[idx(w, s)];
+            }
+            if (udst >= 0) {
+                const double *Pv = P + (size_t)i * N * N;
+#pragma unroll
+                for (int b = 0; b < N; ++b) {
+                    double y = 0.0;
+#pragma unroll
+                    for (int a = 0; a < N; ++a) y += Pv[a * N + b] * x[a];
+                    S[lev(udst, b)] = y;
+                }
+            }
+            const int lsrc = ops[3 * o + 2].x;
+            double l[N];
+#pragma unroll
+            for (int s = 0; s < N; ++s) l[s] = lsrc >= 0 ? S[lev(lsrc, s)] : Larr[idx(i, s)];
+            for (int r = 0; r < R; ++r) {
+                const double *G1 = G + ((size_t)r * nnodes + i) * N * N;
+                const double *G2 = G + ((size_t)(R + r) * nnodes + i) * N * N;
+                double t = 0.0;
+#pragma unroll
+                for (int b = 0; b < N; ++b) {
+                    double y = 0.0, z = 0.0;
+#pragma unroll
+                    for (int a = 0; a < N; ++a) {
+                        y += G1[a * N + b] * x[a];
+                        z += G2[b * N + a] * l[a];
+                    }
+                    t += y * z * mc[b];
+                }
+                out[((size_t)(mv - mvA) * R + r) * nsites + site] = spr_value(t, zero);
+            }
+        }
+    }
+}
+
+// one workgroup per (move, fraction), the order of profile_sums_kernel: thread j adds sites j,
+// j + 256, ... in order, then the 256 partial sums by halves (fixed rounding).  Sites of zero
+// likelihood and of weight 0 are skipped.
+__global__ void __launch_bounds__(256)
+spr_sums_kernel(long nsites, const double *__restrict__ values, const double *__restrict__ weights,
+                const int *__restrict__ status, double *__restrict__ sums)
+{
+    __shared__ double part[256];
+    const size_t row = blockIdx.x;
+    const int tid = threadIdx.x;
+    const double *x = values + row * nsites;
+    double acc = 0.0;
+    for (long i = tid; i < nsites; i += 256) {
+        const double w = weights ? weights[i] : 1.0;       // (w = 0: not -inf * 0 = NaN)
+        if (w != 0.0 && !(status[i] & RT_SITE_ZERO_PROB)) acc += w * x[i];
+    }
+    part[tid] = acc;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) part[tid] += part[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) sums[row] = part[0];
+}
+
+// ---- the host's side: the moves and the plan of the walk ----
+
+// what the moves of one pruned node need of the tree (children after their parents, as every
+// CSR the library takes)
+struct spr_tree {
+    int64_t N = 0;
+    const int64_t *idx = nullptr, *ptr = nullptr;
+    const int32_t *parent = nullptr;
+    std::vector<int32_t> depth, size;            // edges from the root; nodes of the subtree
+    std::vector<int32_t> dist, path;             // per pruned node: edges from v; j on the path, else -1
+    std::vector<unsigned char> in, target;       // in the pruned subtree; a target of the pruned node
+
+    spr_tree(int64_t n, const int64_t *i, const int64_t *p, const int32_t *par)
+        : N(n), idx(i), ptr(p), parent(par), depth((size_t)n, 0), size((size_t)n, 1),
+          dist((size_t)n, 0), path((size_t)n, -1), in((size_t)n, 0), target((size_t)n, 0)
+    {
+        for (int64_t v = 1; v < N; ++v) depth[(size_t)v] = depth[(size_t)parent[v]] + 1;
+        for (int64_t v = N - 1; v >= 1; --v) size[(size_t)parent[v]] += size[(size_t)v];
+    }
+
+    // the path steps of the walk of the pruned node c: a_j, j = 0 .. J, the non-root ancestors
+    // of c within the radius
+    int64_t path_steps(int64_t c, int64_t radius) const
+    {
+        return std::min<int64_t>(radius < 0 ? N : radius, (int64_t)depth[(size_t)parent[c]] - 1) + 1;
+    }
+
+    // the targets y of the pruned node c within the radius (< 0: no limit), their number
+    int64_t cut(int64_t c, int64_t radius)
+    {
+        std::fill(path.begin(), path.end(), -1);
+        int32_t j = 0;
+        for (int64_t a = parent[c]; a >= 0; a = parent[a]) {
+            path[(size_t)a] = j;
+            dist[(size_t)a] = j++;
+        }
+        int64_t cnt = 0;
+        in[0] = target[0] = 0;
+        for (int64_t y = 1; y < N; ++y) {
+            const int64_t q = parent[y];
+            in[(size_t)y] = y == c || in[(size_t)q];
+            target[(size_t)y] = 0;
+            if (in[(size_t)y]) continue;
+            if (path[(size_t)y] < 0) dist[(size_t)y] = dist[(size_t)q] + 1;
+            const int64_t d = std::min(dist[(size_t)y], dist[(size_t)q]);
+            target[(size_t)y] = radius < 0 || d <= radius;
+            cnt += target[(size_t)y];
+        }
+        return cnt;
+    }
+};
+
+// the moves in their order: c ascending, then y ascending.  first (or null): [nnodes + 1] the
+// index of every pruned node's first move; moves (or null): the pairs
+int64_t spr_enumerate(spr_tree &t, int64_t radius, int32_t *first, int32_t *moves)
+{
+    int64_t k = 0;
+    if (first) first[0] = 0;
+    for (int64_t c = 1; c < t.N; ++c) {
+        if (first) first[c] = (int32_t)std::min<int64_t>(k, INT32_MAX);
+        // (without a limit and without the pairs the count needs no walk)
+        const int64_t cnt = radius < 0 && !moves ? t.N - 1 - t.size[(size_t)c] : t.cut(c, radius);
+        if (moves)
+            for (int64_t y = 1, j = k; y < t.N; ++y)
+                if (t.target[(size_t)y]) {
+                    moves[2 * j] = (int32_t)c;
+                    moves[2 * j + 1] = (int32_t)y;
+                    ++j;
+                }
+        k += cnt;
+    }
+    if (first) first[t.N] = (int32_t)std::min<int64_t>(k, INT32_MAX);
+    return k;
+}
+
+int spr_moves_out(int64_t cnt, int32_t *moves, int64_t capacity, int64_t *nmoves)
+{
+    *nmoves = cnt;
+    RT_REQUIRE(!moves || capacity >= cnt, "the tree has %lld moves within the radius, the array "
+               "holds %lld", (long long)cnt, (long long)capacity);
+    return RT_OK;
+}
+
+int spr_list(int64_t N, const int64_t *idx, const int64_t *ptr, const int32_t *parent, int64_t radius,
+             int32_t *moves, int64_t capacity, int64_t *nmoves)
+{
+    spr_tree t(N, idx, ptr, parent);
+    RT_TRY(spr_moves_out(spr_enumerate(t, radius, nullptr, nullptr), moves, capacity, nmoves));
+    if (moves) spr_enumerate(t, radius, nullptr, moves);
+    return RT_OK;
+}
+
+// The ops of every pruned node (after spr_tree::cut of it, in `t`).  Levels of a group's
+// scratch, D = 1 + the depth of the tree: L- of path node a_j at j, M- at D + j, up- of an
+// off-path node of depth d at 2 D + d.  slot_of: node -> slot of the kernels' tables.
+void spr_plan_one(const spr_tree &t, int64_t c, int64_t radius, int32_t mv0, int D,
+                  const int32_t *slot_of, std::vector<spr_op> *ops, std::vector<int32_t> *rank,
+                  std::vector<int32_t> *stack)
+{
+    const int64_t N = t.N;
+    const int32_t *parent = t.parent;
+    // the moves' indices: the rank of y among the targets, ascending
+    int32_t k = mv0;
+    for (int64_t y = 1; y < N; ++y) (*rank)[(size_t)y] = t.target[(size_t)y] ? k++ : -1;
+    if (k == mv0) return;
+    // the path: a_j, j = 0 .. J, the non-root ancestors whose L- a target or a later step needs
+    const int64_t v = parent[c];
+    const int64_t J = t.path_steps(c, radius) - 1;
+    int64_t a = v, below = -1;                   // a_j and a_{j-1}
+    for (int64_t j = 0; j <= J; ++j, below = a, a = parent[a]) {
+        const int64_t q = parent[a];
+        // M- of a_j: the next step's, or the A- of the siblings of a_j (d = j + 1)
+        const bool others = t.ptr[q + 1] - t.ptr[q] > 1;
+        const bool need_m = j < J || ((radius < 0 || j + 1 <= radius) && others);
+        spr_op op = {};
+        op.kind = 0;
+        op.i = slot_of[a];
+        op.pi = -1;
+        op.mv = -1;
+        op.usrc = need_m ? (int32_t)(D + j) : -1;
+        op.udst = (int32_t)j;
+        op.pw = j ? slot_of[below] : -1;
+        op.psrc = j ? (int32_t)(D + j - 1) : -1;
+        op.lsrc = -1;
+        ops->push_back(op);
+    }
+    // the edges, depth first from the root in CSR child order
+    size_t top = 0;
+    auto push_children = [&](int64_t q) {
+        for (int64_t e = t.ptr[q + 1] - 1; e >= t.ptr[q]; --e) (*stack)[top++] = (int32_t)t.idx[e];
+    };
+    push_children(0);
+    while (top) {
+        const int64_t y = (*stack)[--top];
+        if (t.in[(size_t)y] || !t.target[(size_t)y]) {
+            // not a target: below an off-path node nothing further down is one; a path node
+            // past the radius may still have targets below it (nearer v)
+            if (!t.in[(size_t)y] && t.path[(size_t)y] >= 0) push_children(y);
+            continue;
+        }
+        const int64_t q = parent[y];
+        const bool y_on = t.path[(size_t)y] >= 0, q_on = t.path[(size_t)q] >= 0;
+        const bool kids = t.ptr[y + 1] > t.ptr[y];
+        const bool up = !y_on && kids && (radius < 0 || t.dist[(size_t)y] <= radius);
+        spr_op op = {};
+        op.kind = 1;
+        op.i = slot_of[y];
+        op.pi = slot_of[q];
+        op.mv = (*rank)[(size_t)y];
+        op.usrc = q_on ? -1 : (int32_t)(2 * D + t.depth[(size_t)q]);
+        op.udst = up ? (int32_t)(2 * D + t.depth[(size_t)y]) : -1;
+        op.pw = -1;
+        op.psrc = -1;
+        op.lsrc = y_on ? t.path[(size_t)y] : -1;
+        if (q_on && !y_on && t.path[(size_t)q] >= 1) {
+            // q = a_j, j >= 1: its path child a_{j-1} comes without the pruned subtree
+            int64_t b = v;
+            while (parent[b] != q) b = parent[b];
+            op.pw = slot_of[b];
+            op.psrc = (int32_t)(D + t.path[(size_t)q] - 1);
+        }
+        ops->push_back(op);
+        if (y_on || up) push_children(y);
+    }
+}
+
+}  // namespace
+
+extern "C" int rt_model_spr_moves(const rt_model *m, int64_t radius, int32_t *moves,
+                                  int64_t capacity, int64_t *nmoves)
+{
+    RT_REQUIRE(m && nmoves, "null pointer");
+    return spr_list(m->nnodes, m->indices.data(), m->indptr.data(), m->parent.data(), radius, moves,
+                    capacity, nmoves);
+}
+
+extern "C" int rt_tree_spr_moves(int64_t nnodes, const int64_t *idx, const int64_t *ptr,
+                                 int64_t radius, int32_t *moves, int64_t capacity, int64_t *nmoves)
+{
+    RT_REQUIRE(nnodes >= 1 && ptr && (idx || nnodes == 1) && nmoves, "bad arguments");
+    RT_REQUIRE(ptr[0] == 0 && ptr[nnodes] == nnodes - 1, "tree_csr_indptr does not describe a tree");
+    // (the walk goes up through the parents: every node but the root has exactly one)
+    std::vector<int32_t> parent((size_t)nnodes, -1);
+    for (int64_t v = 0; v < nnodes; ++v) {
+        RT_REQUIRE(ptr[v + 1] >= ptr[v], "tree_csr_indptr not monotone");
+        for (int64_t e = ptr[v]; e < ptr[v + 1]; ++e) {
+            RT_REQUIRE(idx[e] > v && idx[e] < nnodes, "children not in preorder");
+            RT_REQUIRE(parent[(size_t)idx[e]] < 0, "node %lld is listed as a child twice",
+                       (long long)idx[e]);
+            parent[(size_t)idx[e]] = (int32_t)v;
+        }
+    }
+    return spr_list(nnodes, idx, ptr, parent.data(), radius, moves, capacity, nmoves);
+}
+
+extern "C" int rt_sites_spr_scores(rt_model *m, rt_sites *s, int recompute_transitions,
+                                   int64_t radius, int64_t nfractions, const double *fractions,
+                                   double *values, double *sums, int32_t *status)
+{
+    const char *who = "rt_sites_spr_scores";
+    post_pass p;                                 // (alive until the synchronisation below)
+    RT_TRY(post_open(&p, who, m, s));
+    const int64_t n = p.n, N = p.N, nsites = p.nsites;
+    RT_REQUIRE(fractions, "%s: fractions is NULL", who);
+    RT_REQUIRE(nfractions >= 1 && nfractions <= RT_MAX_PLACE_FRACTIONS,
+               "%s: 1..%d fractions (%lld here)", who, RT_MAX_PLACE_FRACTIONS, (long long)nfractions);
+    for (int64_t r = 0; r < nfractions; ++r)
+        RT_REQUIRE(std::isfinite(fractions[r]) && fractions[r] >= 0.0 && fractions[r] <= 1.0,
+                   "%s: fraction %d is outside [0, 1] or not finite", who, (int)r);
+    const int R = (int)nfractions, np = 2 * R;
+    // the moves
+    spr_tree tree(N, m->indices.data(), m->indptr.data(), m->parent.data());
+    std::vector<int32_t> first((size_t)N + 1, 0);
+    const int64_t nmoves = spr_enumerate(tree, radius, first.data(), nullptr);
+    RT_REQUIRE(nmoves * R < (int64_t)1 << 31, "%s: too many moves (%lld at %d fractions)", who,
+               (long long)nmoves, R);
+    // the ops of the plan: one per move, and the path steps of every pruned node that has moves
+    int64_t nplan = nmoves;
+    for (int64_t c = 1; c < N; ++c)
+        if (first[(size_t)c + 1] > first[(size_t)c]) nplan += tree.path_steps(c, radius);
+    RT_REQUIRE(nplan < INT32_MAX / 4, "%s: too many moves (a plan of %lld ops)", who, (long long)nplan);
+    RT_TRY(post_layout(&p, true));
+    // the grid of every node: rho_r t_v, (1 - rho_r) t_v
+    std::vector<double> lengths((size_t)N * np, 0.0);
+    if (post_model_has_rates(m))
+        for (int64_t v = 1; v < N; ++v) {
+            double *row = lengths.data() + (size_t)v * np;
+            const double t = m->h_t[(size_t)v];
+            for (int r = 0; r < R; ++r) {
+                row[r] = fractions[r] * t;
+                row[R + r] = (1.0 - fractions[r]) * t;
+            }
+        }
+    RT_TRY(post_grid_check(&p, recompute_transitions, np, lengths.data()));
+    post_plan &plan = p.plan;
+    post_grid grid;                              // (alive until the synchronisation below)
+    RT_TRY(post_grid_take(&p, &grid, np));
+    const int cnt = p.lane ? (int)N : p.nops;    // slots of the tables
+    const int D = 1 + *std::max_element(tree.depth.begin(), tree.depth.end()), nlevels = 3 * D;
+    const size_t o_tab = plan.take((size_t)4 * cnt * 4);
+    const size_t o_cut = plan.take(((size_t)N + 1) * 16);
+    const size_t ftab = p.lane ? 0 : (size_t)p.nops * p.NT * p.KP * 128;
+    const size_t o_PA = plan.take(p.lane ? 8 : ftab * 8);
+    const size_t o_sum = plan.take((size_t)std::max<int64_t>(nmoves, 1) * R * 8);
+    // the groups of pruned nodes that walk side by side: enough workgroups to fill the device at
+    // few sites, their level vectors within SPR_LEVEL_BYTES
+    const size_t vec = p.lane ? (size_t)n * nsites * 8 : (size_t)s->nblocks * p.NT * 256 * 8;
+    const int64_t wgs = p.lane ? (nsites + 255) / 256 : (int64_t)s->nblocks;
+    int64_t G = (2048 + wgs - 1) / std::max<int64_t>(wgs, 1);
+    G = std::min<int64_t>(G, (int64_t)(SPR_LEVEL_BYTES / std::max<size_t>((size_t)nlevels * vec, 1)));
+    G = std::max<int64_t>(1, std::min<int64_t>(G, N - 1));
+    const size_t o_S = plan.take((size_t)G * nlevels * vec);
+    const size_t o_ops = plan.take((size_t)std::max<int64_t>(nplan, 1) * sizeof(spr_op));
+    // the chunks of pruned nodes: their result (and its transpose) within the chunk size and the cap
+    const size_t per_move = (size_t)R * nsites * 8 * (values ? 2 : 1);
+    size_t chunk_bytes = SPR_CHUNK_BYTES;
+    if (const char *e = getenv("RAOTEH_SPR_CHUNK_BYTES")) {      // (tests: many chunks at small sizes)
+        const long long v = atoll(e);
+        if (v > 0) chunk_bytes = (size_t)v;
+    }
+    const double room = SPR_SCRATCH_CAP - (double)plan.total - 4096.0;
+    if (room < (double)chunk_bytes) chunk_bytes = room > 0.0 ? (size_t)room : 0;
+    const int64_t chunk_moves = std::max<int64_t>(1, (int64_t)(chunk_bytes / per_move));
+    std::vector<int32_t> chunks(1, 1);           // the first pruned node of every chunk, then nnodes
+    int64_t max_moves = 1;
+    for (int64_t c = 1, c0 = 1; c <= N; ++c)
+        if (c == N || (c > c0 && first[(size_t)c + 1] - first[(size_t)c0] > chunk_moves)) {
+            max_moves = std::max<int64_t>(max_moves, first[(size_t)c] - first[(size_t)c0]);
+            if (c < N) chunks.push_back((int32_t)c);
+            c0 = c;
+        }
+    chunks.push_back((int32_t)N);
+    const size_t chunk_rows = (size_t)max_moves * R;
+    const size_t o_val = plan.take(chunk_rows * nsites * 8);
+    const size_t o_valT = plan.take(values ? std::min<size_t>(chunk_rows, SPR_MAX_ROWS) * nsites * 8 : 8);
+    // (the cap is checked here, before the host makes the plan)
+    RT_TRY(post_begin(&p, recompute_transitions));
+    // the plan of the walk (slots: by node here; n > 4 renumbers by step below)
+    std::vector<spr_op> ops;
+    ops.reserve((size_t)nplan);
+    std::vector<int32_t> cut((size_t)(N + 1) * 4, 0);
+    {
+        std::vector<int32_t> ident((size_t)N), rank((size_t)N), stack((size_t)N + 1);
+        for (int64_t v = 0; v < N; ++v) ident[(size_t)v] = (int32_t)v;
+        for (int64_t c = 1; c < N; ++c) {
+            tree.cut(c, radius);
+            cut[(size_t)c * 4] = (int32_t)c;
+            cut[(size_t)c * 4 + 1] = (int32_t)ops.size();
+            spr_plan_one(tree, c, radius, first[(size_t)c], D, ident.data(), &ops, &rank, &stack);
+            cut[(size_t)c * 4 + 2] = (int32_t)ops.size();
+            cut[(size_t)c * 4 + 3] = first[(size_t)c];
+        }
+        cut[(size_t)N * 4 + 3] = (int32_t)nmoves;
+        RT_REQUIRE((int64_t)ops.size() == nplan, "%s: the plan has %lld ops, %lld were counted", who,
+                   (long long)ops.size(), (long long)nplan);
+    }
+    hipStream_t st = p.st;
+    unsigned char *base = p.base;
+    double *d_val = (double *)(base + o_val), *d_valT = (double *)(base + o_valT);
+    double *d_sum = (double *)(base + o_sum), *d_S = (double *)(base + o_S);
+    double *d_PA = (double *)(base + o_PA);
+    int *d_tab = (int *)(base + o_tab);
+    int4 *d_cut = (int4 *)(base + o_cut), *d_ops = (int4 *)(base + o_ops);
+    int *d_status = p.d_status;
+    std::vector<int32_t> internal((size_t)N, 0);
+    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
+    RT_TRY(post_grid_launch(&p, &grid, lengths.data()));
+    RT_TRY(post_up(&p, internal.data(), true));
+    std::vector<int32_t> tab;
+    post_tab_build(&p, nullptr, &tab);
+    if (!p.lane) {                               // node -> step in the plan
+        std::vector<int32_t> step_of((size_t)N, 0);
+        for (int j = 0; j < p.nops; ++j) step_of[(size_t)p.x->ops[(size_t)j].node] = j;
+        for (spr_op &op : ops) {
+            op.i = step_of[(size_t)op.i];
+            if (op.pi >= 0) op.pi = step_of[(size_t)op.pi];
+            if (op.pw >= 0) op.pw = step_of[(size_t)op.pw];
+        }
+        for (int64_t c = 1; c < N; ++c) cut[(size_t)c * 4] = step_of[(size_t)c];
+    }
+    RT_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemcpyAsync(d_cut, cut.data(), cut.size() * 4, hipMemcpyHostToDevice, st));
+    if (!ops.empty())
+        RT_HIP(hipMemcpyAsync(d_ops, ops.data(), ops.size() * sizeof(spr_op), hipMemcpyHostToDevice, st));
+    const size_t nn = (size_t)n * n;
+    if (p.lane) {
+        const int *d_ptab = p.d_ptab;
+        RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
+            hipLaunchKernelGGL((spr_lane_up_kernel<decltype(nv)::value>),
+                               dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)N,
+                               (long)nsites, (const double *)m->d_P, d_ptab, d_ptab + N,
+                               (const int *)d_tab, (const void *)s->d_obs, s->compact_states,
+                               (int)s->nobs, s->block_sites, (const double *)m->d_root, p.d_L, p.d_M,
+                               p.d_D, d_status);
+            return RT_OK;
+        }));
+    } else {
+        // the fragment tables: the resident P beside the resident P^T; in the grid's own piece,
+        // [point][step], P(rho t)^T at the points 0 .. R - 1 and P((1 - rho) t) at R .. 2 R - 1
+        RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab, m->d_P, d_PA));
+        for (int r = 0; r < R; ++r) {
+            RT_TRY(rt_launch_pack_pt(p.ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab,
+                                     grid.d_G + (size_t)r * N * nn, grid.d_GT + (size_t)r * ftab));
+            RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab,
+                                    grid.d_G + (size_t)(R + r) * N * nn,
+                                    grid.d_GT + (size_t)(R + r) * ftab));
+        }
+        const rt_sites *x = p.x;
+        RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
+            constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
+            hipLaunchKernelGGL((spr_up_kernel<NT, KS>), dim3((unsigned)x->nblocks), dim3(64 * NT), 0, st,
+                               (const double *)p.d_PT, p.nops, (const int4 *)p.d_steps,
+                               (const int *)d_tab, (const double *)p.d_L, (const double *)p.d_M, p.d_D,
+                               (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
+                               (int)n, d_status, (long)x->nsites, (long)x->nblocks);
+            return RT_OK;
+        }));
+    }
+    RT_HIP(hipGetLastError());
+    for (size_t ch = 0; ch + 1 < chunks.size() && nmoves; ++ch) {
+        const int cA = chunks[ch], cB = chunks[ch + 1];
+        const int mvA = first[(size_t)cA];
+        const size_t rows = (size_t)(first[(size_t)cB] - mvA) * R;
+        if (!rows) continue;
+        const unsigned groups = (unsigned)std::min<int64_t>(G, cB - cA);
+        if (p.lane) {
+            const int *d_ptab = p.d_ptab;
+            RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
+                hipLaunchKernelGGL((spr_lane_kernel<decltype(nv)::value>),
+                                   dim3((unsigned)((nsites + 255) / 256), groups), dim3(256), 0, st,
+                                   (int)N, (long)nsites, (const double *)m->d_P,
+                                   (const double *)grid.d_G, R, d_ptab, d_ptab + N, (const int *)d_tab,
+                                   (const int4 *)d_cut, (const int4 *)d_ops, (const void *)s->d_obs,
+                                   s->compact_states, (int)s->nobs, s->block_sites,
+                                   (const double *)m->d_root, (const double *)p.d_L,
+                                   (const double *)p.d_M, (const double *)p.d_D, d_S, nlevels, cA, cB,
+                                   mvA, d_val, d_status);
+                return RT_OK;
+            }));
+        } else {
+            const rt_sites *x = p.x;
+            RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
+                constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
+                hipLaunchKernelGGL((spr_kernel<NT, KS>), dim3((unsigned)x->nblocks, groups),
+                                   dim3(64 * NT), 0, st, (const double *)p.d_PT, (const double *)d_PA,
+                                   (const double *)grid.d_GT,
+                                   (const double *)(grid.d_GT + (size_t)R * ftab), R, p.nops,
+                                   (const int4 *)p.d_steps, (const int *)d_tab, (const int4 *)d_cut,
+                                   (const int4 *)d_ops, (const double *)p.d_L, (const double *)p.d_M,
+                                   (const double *)p.d_D, d_S, nlevels, (const double *)x->d_obs,
+                                   (int)x->nobs, (const double *)m->d_root, (int)n, cA, cB, mvA, d_val,
+                                   d_status, (long)x->nsites, (long)x->nblocks);
+                return RT_OK;
+            }));
+        }
+        RT_HIP(hipGetLastError());
+        // 3. the weighted site sums; only what was asked for crosses PCIe
+        if (sums) {
+            hipLaunchKernelGGL(spr_sums_kernel, dim3((unsigned)rows), dim3(256), 0, st, (long)nsites,
+                               (const double *)d_val, (const double *)s->d_weights,
+                               (const int *)d_status, d_sum + (size_t)mvA * R);
+            RT_HIP(hipGetLastError());
+        }
+        if (values)
+            for (size_t r0 = 0; r0 < rows; r0 += (size_t)SPR_MAX_ROWS) {
+                const size_t nr = std::min<size_t>((size_t)SPR_MAX_ROWS, rows - r0);
+                hipLaunchKernelGGL(post_transpose_kernel<32>,
+                                   dim3((unsigned)((nsites + 31) / 32), (unsigned)((nr + 31) / 32)),
+                                   dim3(256), 0, st, (long)nr, (long)nsites,
+                                   (const double *)(d_val + r0 * nsites), d_valT);
+                RT_HIP(hipGetLastError());
+                // [site][rows of the slab] into the caller's [site][nmoves][R]
+                RT_HIP(hipMemcpy2DAsync(values + (size_t)mvA * R + r0, (size_t)nmoves * R * 8, d_valT,
+                                        nr * 8, nr * 8, (size_t)nsites, hipMemcpyDeviceToHost, st));
+            }
+    }
+    if (sums && nmoves)
+        RT_HIP(hipMemcpyAsync(sums, d_sum, (size_t)nmoves * R * 8, hipMemcpyDeviceToHost, st));
+    if (status) RT_HIP(hipMemcpyAsync(status, d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipStreamSynchronize(st));
+    RT_TRY(post_grid_result(&p, &grid));
+    return RT_OK;
+}

@@ -326,6 +326,40 @@ def tree_nni_moves(tree):
     return moves
 
 
+# TreeModel.spr_scores: moves int32[nmoves, 2] (TreeModel.spr_moves: the pruned node c and the
+# node y below the target edge), fractions [R] as evaluated, sums [nmoves, R], values
+# [nsites, nmoves, R] (or None) with values[i, mv, r] = log L_i(tree after move mv at fractions[r])
+# - log L_i, status as Posteriors, best (move, r): the arg-max of sums, ties to the lowest index
+# (None without moves)
+SprScores = collections.namedtuple('SprScores', 'moves fractions sums values status best')
+
+
+def _spr_radius(radius):
+    """radius=None (no limit) or an int >= 0 -> the radius of the C ABI (-1: no limit)."""
+    if radius is None:
+        return -1
+    if isinstance(radius, bool) or int(radius) != radius or radius < 0:
+        raise ValueError('the radius is None (no limit) or an integer >= 0, not %r' % (radius,))
+    return int(radius)
+
+
+def tree_spr_moves(tree, radius=None):
+    """rt_tree_spr_moves: the moves TreeModel.spr_moves lists, int32[nmoves, 2], from a
+    TreeArrays alone (host only: no context, no model)."""
+    rad = _spr_radius(radius)
+    idx = np.ascontiguousarray(tree.indices, dtype=np.int64)
+    ptr = np.ascontiguousarray(tree.indptr, dtype=np.int64)
+    count = c_int64(0)
+    _lib.check(_lib.lib().rt_tree_spr_moves(tree.nnodes, _ptr(idx, c_int64), _ptr(ptr, c_int64),
+                                            rad, None, 0, byref(count)))
+    moves = np.zeros((count.value, 2), dtype=np.int32)
+    if count.value:
+        _lib.check(_lib.lib().rt_tree_spr_moves(tree.nnodes, _ptr(idx, c_int64), _ptr(ptr, c_int64),
+                                                rad, _ptr(moves, c_int32), count.value,
+                                                byref(count)))
+    return moves
+
+
 # TreeModel.place_queries: fractions [R] and pendant [K] as evaluated, sums [Q, nnodes, R, K],
 # values [nsites, Q, nnodes, R, K] (or None) with values[i, q, v, r, k] = log L_i(tree with query q
 # placed at (v, fractions[r], pendant[k])) - log L_i (the root's row: 0), status as Posteriors,
@@ -1560,6 +1594,52 @@ class TreeModel(object):
             except (ValueError, _lib.RaotehHipError):
                 grid = None
         return NniScores(moves, grid, sums, values, status)
+
+    def spr_moves(self, radius=None):
+        """rt_model_spr_moves: the subtree pruning and regrafting moves of the tree within
+        `radius` (None: no limit), int32[nmoves, 2] of preorder indices (c, y) -- the subtree of
+        the non-root node c cut off its parent v and hung on the edge above y, a non-root node
+        outside that subtree -- ordered by c, then y (_tree.spr_apply makes the moved tree).
+        The radius of a move is min(dist(v, y), dist(v, parent(y))) in edges: 0 for the edge
+        above v and those above the siblings of c.  (c, v) at fraction 1 and (c, sibling) at
+        fraction 0 leave the tree as it is; they are listed."""
+        rad = _spr_radius(radius)
+        count = c_int64(0)
+        _lib.check(_lib.lib().rt_model_spr_moves(self._h, rad, None, 0, byref(count)))
+        moves = np.zeros((count.value, 2), dtype=np.int32)
+        if count.value:
+            _lib.check(_lib.lib().rt_model_spr_moves(self._h, rad, _ptr(moves, c_int32),
+                                                     count.value, byref(count)))
+        return moves
+
+    def spr_scores(self, batch, radius=None, fractions=(0.5,), per_site=False,
+                   recompute_transitions=False):
+        """rt_sites_spr_scores: the change of the log-likelihood for every move of
+        spr_moves(radius) at every fraction -- the subtree of c, with its own edge, hung on a new
+        node that cuts the edge above y at fractions[r] of its length (from the parent), both
+        halves under the rate matrix of the cut edge -- in one call instead of a model build, an
+        upload and a step per candidate.  Returns an SprScores tuple: moves, fractions, sums
+        [nmoves, R] the site-weighted sums (SiteBatch.set_weights), values [nsites, nmoves, R]
+        (None unless per_site), status, best = (move, r) the arg-max of sums (ties to the lowest
+        index; None where the tree has no move).  -inf where a live site has likelihood 0 on the
+        moved tree."""
+        S = batch.nsites
+        rad = _spr_radius(radius)
+        f, _ = check_placement_grid(fractions, (0.0,))
+        moves = self.spr_moves(radius)
+        M, R = len(moves), len(f)
+        values = np.zeros((S, M, R)) if per_site else None
+        sums = np.zeros((M, R))
+        status = np.zeros(S, dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_spr_scores(
+            self._h, batch._h, 1 if recompute_transitions else 0, rad, R, _ptr(f, c_double),
+            None if values is None else _ptr(values, c_double), _ptr(sums, c_double),
+            _ptr(status, c_int32)))
+        best = None
+        if M:
+            flat = np.where(np.isnan(sums), -np.inf, sums).reshape(-1)
+            best = tuple(int(x) for x in np.unravel_index(int(np.argmax(flat)), (M, R)))
+        return SprScores(moves, f, sums, values, status, best)
 
     def place_queries(self, batch, queries, kind='dense', fractions=(0.5,), pendant=None,
                       per_site=False, recompute_transitions=False):
