@@ -1396,6 +1396,26 @@ int rt_jit_teams_env()
     return v && v[0] ? (atoi(v) != 0) : -1;
 }
 
+// The x image of the pipelined NT = 4 forms at three or more tiles per workgroup is three
+// buffers of T x 8 KB: more than the 64 KB an LDS instruction's immediate offset reaches.
+// RAOTEH_JIT_LDS_BASE (default 1; 0 gives the text without it): all traffic of the x buffers
+// goes through six lane-dependent base pointers per body, and every B operand is a named value
+// whose read stands a fixed number of k-steps ahead of its MFMA in the text
+// (rt_jit_mfma_split_pipelined_source).  For A/B runs: RAOTEH_JIT_LDS_AHEAD=<k-steps, 0..4>
+// (default 2; 0: the base pointers alone, operands read where they are used) and
+// RAOTEH_JIT_LDS_PIN=1 (the scheduling barriers also hold LDS reads in place; measured
+// slower, DESIGN.md 3.3(a'''')).  All of them are part of the text, so of the cache key.
+static bool rt_jit_lds_base_possible(int n, int T)
+{
+    return (n + 15) / 16 == 4 && T >= 3;
+}
+
+static int env_int(const char *name, int unset)
+{
+    const char *v = getenv(name);
+    return v && v[0] ? atoi(v) : unset;
+}
+
 // multi (rt_step_multi, one launch for all rate sets): the kernels take the rate set from
 // blockIdx.y and add that set's strides to the table and output pointers in their prologue
 // (wave-uniform scalar adds); without it the text is what it was.  The strides follow the
@@ -1426,6 +1446,12 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
     // three-chain body then fits the 256 registers of a wave that shares its SIMD)
     D = teams ? std::max(D - 1, 1) : std::max(D, 2);
     const int NT = (n + 15) / 16;
+    // (see rt_jit_lds_base_possible)  RA: k-steps a B operand's read stands ahead of its MFMA;
+    // at most four (twenty reads in flight at five chains: the counter of outstanding LDS
+    // operations has four bits, and the publishes share it)
+    const bool lds = rt_jit_lds_base_possible(n, T) && env_int("RAOTEH_JIT_LDS_BASE", 1) != 0;
+    const int RA = lds ? std::max(0, std::min(4, env_int("RAOTEH_JIT_LDS_AHEAD", 2))) : 0;
+    const bool pin = env_int("RAOTEH_JIT_LDS_PIN", 0) != 0;
     const int KS = (n + 3) / 4;
     const int KP = (KS + 1) / 2;
     const int XT = NT * 4 * 64;               // doubles of one tile's x image
@@ -1485,9 +1511,12 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
       << " steps (" << nlate << " serial), " << n << " states, " << K << " observed nodes, " << T
       << " tiles per workgroup of " << NT << " waves, " << nslots << " accumulator slots, prefetch "
       << D << " leaves"
-      << (teams ? ", two teams of four waves" : "") << "\n";
+      << (teams ? ", two teams of four waves" : "");
+    if (lds) o << ", x buffers through base pointers";
+    o << "\n";
     o << "typedef double rt_d2 __attribute__((ext_vector_type(2)));\n";
     o << "typedef double rt_d4 __attribute__((ext_vector_type(4)));\n";
+    if (lds) o << "typedef __attribute__((address_space(3))) double *rt_lds;\n";
     const trace_opt trace = trace_from_env();
     // [wave][step][t0 step start, t1 behind the barrier, t2 last MFMA issued]; teams: the waves
     // of team 1 follow team 0's, and a fourth stamp stands in front of the barrier (t1 - t3 is
@@ -1749,8 +1778,19 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
         emit_x(os, k);
         for (int t = TLO; t < THI; ++t)
             for (int r = 0; r < 4; ++r)
-                os << "    xb" << (k % 3) << "[" << t << "][(4 * m + " << r << ") * 64 + lane] = x" << k
-                   << "_" << t << "_" << r << ";\n";
+                if (lds)
+                    os << "    wb" << (k % 3) << "[" << t * XT + r * 64 << "] = x" << k << "_" << t << "_"
+                       << r << ";\n";
+                else
+                    os << "    xb" << (k % 3) << "[" << t << "][(4 * m + " << r << ") * 64 + lane] = x" << k
+                       << "_" << t << "_" << r << ";\n";
+    };
+    // operand kk of chain t from buffer b
+    auto xb_read = [&](int b, int t, int kk) {
+        std::ostringstream os;
+        if (lds) os << "rb" << b << "[" << t * XT + kk * 64 << "]";
+        else os << "xb" << b << "[" << t << "][" << kk * 64 << " + lane]";
+        return os.str();
     };
     auto emit_fold = [&](std::ostream &os, int k) {             // c(k) into the parent's accumulator
         const rt_op &op = st[(size_t)k].op;
@@ -1784,6 +1824,17 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
     }
     const int TT = THI - TLO;
     const size_t body_begin = (size_t)o.tellp();
+    if (lds) {
+        // one read and one write base per buffer, opaque to the compiler (or it folds the
+        // buffer's address back into them and keeps a register per distinct sum above 64 KB):
+        // every access is base + constant < 64 KB, the constant in the instruction's offset field
+        o << "    // x buffers: base + offset; B operands " << RA << " k-steps ahead"
+          << (pin ? ", held in place" : "") << "\n";
+        for (int b = 0; b < 3; ++b)
+            o << "    rt_lds rb" << b << " = (rt_lds)&xb" << b << "[0][0] + lane, wb" << b << " = rb" << b
+              << " + 4 * m * 64;\n";
+        o << "    asm volatile(\"\" : \"+v\"(rb0), \"+v\"(rb1), \"+v\"(rb2), \"+v\"(wb0), \"+v\"(wb1), \"+v\"(wb2));\n";
+    }
     // ---- prologue -----------------------------------------------------------------------
     for (int k = 0; k < GA; ++k) emit_gathers_of(o, k);
     for (int k = 0; k < std::min(D, (int)obs_order.size()); ++k) emit_obs_load(o, obs_order[(size_t)k]);
@@ -1890,6 +1941,25 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
         size_t next_sh = 0;
         int issued = 0;
         const bool early_barrier = have_next && !next_root && !next_late && KS >= 4;
+        // (RA > 0) operand kk of chain t is the value b<step>_<t>_<kk>, read RA k-steps ahead of
+        // its MFMA: those of the first RA k-steps behind the barrier that published the step's
+        // x -- in the chain of the step before, or at the top of this one where that barrier
+        // closed the step -- and every other one behind the MFMA of the same chain RA k-steps
+        // earlier.  That is where the text puts them; the scheduling barriers around them still
+        // let LDS reads move (0x124) unless `pin` asks for 0x24.  With the reads held in place
+        // the C3 kernel was 3 us slower at RA = 2.
+        const std::string sched =
+            "    __builtin_amdgcn_sched_barrier(" + std::string(RA > 0 && pin ? "0x24" : "0x124") + ");\n";
+        auto emit_b_read = [&](int step, int t, int kk) {
+            o << "    const double b" << step << "_" << t << "_" << kk << " = " << xb_read(step % 3, t, kk)
+              << ";\n";
+        };
+        const int npre = RA > 0 ? std::min(RA, KS) : 2;    // k-steps read behind the early barrier
+        if (RA > 0 && !prefetched) {
+            for (int k2 = 0; k2 < npre; ++k2)
+                for (int t2 = TLO; t2 < THI; ++t2) emit_b_read(i, t2, k2);
+            o << sched;
+        }
         for (int kk = 0; kk < KS; ++kk)
             for (int t = TLO; t < THI; ++t) {
                 if (early_barrier && issued == nmfma - TT) {
@@ -1898,28 +1968,35 @@ std::string rt_jit_mfma_split_pipelined_source(const std::vector<rt_op> &ops, in
                     stamp(i + 1, 3);
                     o << "    __syncthreads();      // x of step " << i + 1 << " is in LDS\n";
                     stamp(i + 1, 1);
-                    for (int k2 = 0; k2 < 2; ++k2)
+                    for (int k2 = 0; k2 < npre; ++k2)
                         for (int t2 = TLO; t2 < THI; ++t2)
-                            o << "    const double bp" << i + 1 << "_" << t2 << "_" << k2 << " = xb"
-                              << (i + 1) % 3 << "[" << t2 << "][" << k2 * 64 << " + lane];\n";
-                    o << "    __builtin_amdgcn_sched_barrier(0x124);\n";
+                            if (RA > 0)
+                                emit_b_read(i + 1, t2, k2);
+                            else
+                                o << "    const double bp" << i + 1 << "_" << t2 << "_" << k2 << " = "
+                                  << xb_read((i + 1) % 3, t2, k2) << ";\n";
+                    o << sched;
                 }
                 std::ostringstream bop;
-                if (prefetched && kk < 2) bop << "bp" << i << "_" << t << "_" << kk;
-                else bop << "xb" << b << "[" << t << "][" << kk * 64 << " + lane]";
+                if (RA > 0) bop << "b" << i << "_" << t << "_" << kk;
+                else if (prefetched && kk < 2) bop << "bp" << i << "_" << t << "_" << kk;
+                else bop << xb_read(b, t, kk);
                 o << "    c" << i << "_" << t << " = __builtin_amdgcn_mfma_f64_16x16x4f64(A" << i << "_"
                   << (kk >> 1) << ((kk & 1) ? ".y" : ".x") << ", " << bop.str() << ", c" << i << "_"
                   << t << ", 0, 0, 0);\n";
                 ++issued;
-                if (issued >= lead && next_sh < shadow.size()) {
+                const bool ahead = RA > 0 && kk + RA < KS;
+                const bool slice = issued >= lead && next_sh < shadow.size();
+                if (ahead || slice) o << sched;
+                if (ahead) emit_b_read(i, t, kk + RA);
+                if (slice) {
                     // spread what is left evenly over the MFMAs that are left
                     const int left = std::max(1, slots - (issued - lead));
                     size_t take = (shadow.size() - next_sh + (size_t)left - 1) / (size_t)left;
                     if (issued >= nmfma - 2 * TT) take = shadow.size() - next_sh;
-                    o << "    __builtin_amdgcn_sched_barrier(0x124);\n";
                     for (size_t q = 0; q < take && next_sh < shadow.size(); ++q) o << shadow[next_sh++];
-                    o << "    __builtin_amdgcn_sched_barrier(0x124);\n";
                 }
+                if (ahead || slice) o << sched;
             }
         while (next_sh < shadow.size()) o << shadow[next_sh++];
         stamp(i, 2);
