@@ -359,7 +359,9 @@ int rt_sites_create(rt_model *model, int64_t nsites, int kind, int64_t nobs,
  * the working set): the same observations, pruning kernel, per-site
  * log-likelihoods, statuses and totals (a pending batch sum is reduced first),
  * so that both read the same until either is pruned again.  A clone of a batch
- * that was never pruned is never pruned either.  (Site weights are not copied.) */
+ * that was never pruned is never pruned either.  (Site weights are not copied, and neither are
+ * the results of rt_step_multi: its getters return RT_ERR_INVALID on the clone until the clone
+ * has been stepped.)                                                            */
 int rt_sites_clone(rt_sites *sites, rt_sites **clone);
 /* Wait for the background compile of this batch's tree-specialised kernel, if one is
  * pending, and switch the batch to it (see "jit_async").                              */
@@ -397,8 +399,11 @@ int rt_step(rt_model *model, rt_sites *sites, int recompute_transitions);
  * the matrix-pipe layout: the 122-state switching model included), batches created by
  * rt_sites_create (n > 4: any observation kind; n <= 4: the fused lane kernel works on allowed sets, so a
  * dense batch counts a state as allowed where its likelihood is not zero), rates set by
- * rt_model_set_rates.  RT_ERR_UNSUPPORTED for a "rescale" batch (the passes work on
- * unscaled f64 messages), at every n.  Synchronous.                                     */
+ * rt_model_set_rates.  RT_ERR_INVALID for a model with spectral rates or with transitions set
+ * directly: on a model that never had rates, or after them with recompute_transitions == 0 (the
+ * resident rate matrices would no longer describe the transition matrices).
+ * RT_ERR_UNSUPPORTED for a "rescale" batch (the passes work on unscaled f64 messages), at every
+ * n.  Synchronous.                                                                       */
 int rt_expect_step(rt_model *model, rt_sites *sites, int recompute_transitions,
             double *dwell, double *root_posterior, double *trans, int32_t *status);
 /* _mcy_dense.kitchen_sink (_mcy_dense.py:57-230) for every site of a RESIDENT batch: the
@@ -452,7 +457,8 @@ int rt_sites_posteriors(rt_model *model, rt_sites *sites, int recompute_transiti
  * array is large: nsites * nnodes * n_coefs doubles).  Every batch rt_sites_create makes for
  * 2 <= n <= 128 (dense observations are used as values at every n), per-edge rate matrices, any
  * tree rt_sites_posteriors takes.  The rates must come from rt_model_set_rates (the derivative
- * needs Q): RT_ERR_INVALID for a model with spectral rates or with transitions set directly.
+ * needs Q): RT_ERR_INVALID for a model with spectral rates or with transitions set directly (on
+ * a model that never had rates, or after them with recompute_transitions == 0).
  * RT_ERR_UNSUPPORTED: a "rescale" batch, a tree deeper than the fast kernels take, nnodes < 2,
  * more than RT_MAX_BRANCH_COEFS matrices, more than 96 GB of scratch.  Synchronous; the batch
  * keeps its kernel, log-likelihoods, status and totals; two calls return the same bits.      */
@@ -813,8 +819,8 @@ int rt_sites_map_states(rt_model *model, rt_sites *sites, int recompute_transiti
  * with first_draw = f.  The mean over the draws converges to rt_sites_branch_expectations.
  * Batches and trees: those of rt_sites_sample_states (2..128 states, every observation kind,
  * per-edge rate matrices).  The rates must come from rt_model_set_rates: RT_ERR_INVALID for
- * spectral rates or transitions set directly, as for ndraws < 1, no coefficient matrix, a batch
- * of another model.  RT_ERR_UNSUPPORTED: what rt_sites_sample_states refuses, more than
+ * spectral rates or transitions set directly (on a model that never had rates, or after them with
+ * recompute_transitions == 0), as for ndraws < 1, no coefficient matrix, a batch of another model.  RT_ERR_UNSUPPORTED: what rt_sites_sample_states refuses, more than
  * RT_MAX_BRANCH_COEFS matrices, more than 96 GB of scratch, an edge with K_v >
  * RT_MAX_MAPPING_EVENTS (checked before anything is launched).  The per-draw outputs pass through
  * the device in chunks: scratch grows with ndraws by the node states only.  Synchronous; the
@@ -868,7 +874,7 @@ int rt_sites_get_totals(rt_sites *sites, double totals[3]);
  * rt_sites_multi_mixture: per site log sum_k c_k exp(loglik[k][i]) with the maximum taken out;
  *   sets with c_k = 0 or zero likelihood are skipped, a site where none remains gets -inf and
  *   RT_SITE_ZERO_PROB.  totals as rt_sites_get_totals, with the site weights applied to
- *   totals[0].  class_weights f64[K] finite, >= 0, not all zero.  loglik, status and totals may
+ *   totals[0] (the weights of the time of this call, not of the step).  class_weights f64[K] finite, >= 0, not all zero.  loglik, status and totals may
  *   each be NULL.  Synchronous; two calls return the same bits.
  * The getters and the mixture synchronise; they return RT_ERR_INVALID before any rt_step_multi
  * of the batch and after the number of rate sets changed (until the next rt_step_multi).

@@ -592,6 +592,10 @@ extern "C" int rt_sites_branch_expectations(rt_model *m, rt_sites *s, int recomp
                "rt_sites_branch_expectations: rt_model_set_rates has not been called (the "
                "derivative needs the rate matrices: a model with spectral rates or with "
                "transitions set directly has none)");
+    RT_REQUIRE(m->rates_current || recompute_transitions,
+               "%s: the transitions were set directly after the rates "
+               "(rt_model_set_transitions): the resident rate matrices no longer describe them; "
+               "set the rates again or pass recompute_transitions", "rt_sites_branch_expectations");
     if (n_coefs > RT_MAX_BRANCH_COEFS) {
         rt_set_error("rt_sites_branch_expectations: at most %d coefficient matrices (%lld here)",
                      RT_MAX_BRANCH_COEFS, (long long)n_coefs);

@@ -416,8 +416,12 @@ expect_wsum_kernel(int nops, const double *__restrict__ Uarr, const double *__re
         // ---- the same for an observed leaf: L from the observation image
         const int lk = leaf_k[step];                 // (uniform)
         const int par = (lo >> 2) & 1;               // which double of a pair this state is
+        // (KP == 1, 5 .. 8 states: the lanes of the padding states 8 .. 15 have no pair 1 -- they
+        // load pair 0 and select zeros below; pair 1 would be the next slot of the image and, for
+        // the last slot of the last tile, the kilobyte behind its end)
+        const int q0 = (lo >> 3) < KP ? (lo >> 3) : 0;
         const double *po = obs + ((size_t)first * K + (lk >= 0 ? lk : 0)) * KP * 128 +
-                           (size_t)(lo >> 3) * 128 + ((lo & 3) * 16 + 4 * hi) * 2;
+                           (size_t)q0 * 128 + ((lo & 3) * 16 + 4 * hi) * 2;
         const size_t obs_stride = (size_t)NT * K * KP * 128;
         auto fetch_leaf = [&](double4_t (&u)[NT], double4_t (&l0)[NT], double4_t (&l1)[NT], double4_t &w) {
 #pragma unroll
@@ -1146,6 +1150,10 @@ extern "C" int rt_expect_step(rt_model *m, rt_sites *s, int recompute_transition
     RT_TRY(post_open(&p, "rt_expect_step", m, s));
     RT_REQUIRE(m->d_Q && !m->spectral,
                "rt_model_set_rates has not been called (the statistics need the rate matrices)");
+    RT_REQUIRE(m->rates_current || recompute_transitions,
+               "%s: the transitions were set directly after the rates "
+               "(rt_model_set_transitions): the resident rate matrices no longer describe them; "
+               "set the rates again or pass recompute_transitions", "rt_expect_step");
     if (s->rescale) {
         // neither the lane kernel nor the split-M twin rescales its messages: on a tree whose
         // likelihood underflows f64 they would return zeros
