@@ -979,7 +979,8 @@ const char *rt_sites_multi_kernel_name(const rt_sites *sites);
  *   rt_prune, rt_step, rt_step_multi, rt_sites_clone, rt_expect_step, rt_sites_posteriors,
  *   rt_sites_branch_expectations, rt_sites_branch_profiles, rt_sites_sample_states,
  *   rt_sites_map_states, rt_sites_sample_mappings, rt_sites_branch_expectations_mixture,
- *   rt_allreduce_totals, rt_allreduce_totals_group.
+ *   rt_sites_branch_profiles_mixture, rt_sites_nni_scores_mixture, rt_allreduce_totals,
+ *   rt_allreduce_totals_group.
  *                                                               */
 int rt_partition_plan(const int32_t *site_set, int64_t nsites, int64_t nsets, int64_t granule,
             int64_t capacity, int64_t *order, int64_t *slot_of_site, uint8_t *is_pad,
@@ -1047,6 +1048,54 @@ int rt_sites_branch_expectations_mixture(rt_model *model, rt_sites *sites,
             int coefs_per_set, const double *coefs, double *values, double *edge_sums,
             double *set_edge_sums, double *class_post, double *class_sums, double *loglik,
             int32_t *status);
+/* The tree-search reads under the same mixture: rt_sites_branch_profiles and rt_sites_nni_scores
+ * of an ORDINARY resident batch with every site under every one of the model's K rate sets.
+ *     class_weights   f64[K], as above; a set with c_k = 0 is never run and never read
+ *     factors         f64[nnodes][npoints], 1 <= npoints <= RT_MAX_PROFILE_POINTS, finite, >= 0;
+ *                     row 0 is ignored.  Trial lengths are FACTORS of the resident ones: at point
+ *                     g, set k's edge above v takes the length factors[v][g] * t[k][v] -- the one
+ *                     parametrisation that means the same for every class, whether the classes
+ *                     differ in Q (Q_k = r_k Q, shared t) or in t (shared Q, t_k = r_k t)
+ *   L_ik is the likelihood of site i under set k, Lambda_i = sum_k c_k L_ik the mixture
+ *   likelihood, summed in set order.  A site whose Lambda_i is not positive gets
+ *   RT_SITE_ZERO_PROB; its values are 0 and it adds nothing to the sums.
+ * rt_sites_branch_profiles_mixture:
+ *     values          f64[nsites][nnodes][npoints]:
+ *                     log sum_k c_k L_ik(t[k][v] -> factors[v][g] t[k][v]) - log Lambda_i;
+ *                     the root's row is 0; -inf where the mixture likelihood is 0 at the point
+ *     sums            f64[nnodes][npoints]: sum_i w_i values[i][v][g], w from rt_sites_set_weights,
+ *                     in a fixed order; sites of weight 0 and of zero likelihood are skipped
+ *     loglik          f64[nsites]: log Lambda_i, -inf where dead (the loglik of
+ *                     rt_sites_branch_expectations_mixture)
+ *   As in rt_sites_branch_profiles, the row of edge v is NaN -- in values at live sites and in
+ *   sums -- when a set with c_k > 0 has resident t[k][v] == 0.
+ * rt_sites_nni_scores_mixture: moves and their order are those of rt_model_nni_moves;
+ *     values          f64[nsites][nmoves][npoints]: log sum_k c_k L_ik(tree after the move,
+ *                     t[k][v] -> factors[v][g] t[k][v]) - log Lambda_i
+ *     sums            f64[nmoves][npoints], loglik f64[nsites]: as above
+ *   factors == NULL: npoints must be 1, every set keeps its resident matrix on the edge above v
+ *   and no exponential runs; only the rows of nodes v with a move count.  The call is exact in
+ *   every term: a set with L_ik == 0 on the resident tree and L_ik > 0 on the moved one adds its
+ *   term (nothing is divided by L_ik), and a resident t[k][v] == 0 gives no NaN row.  Where the
+ *   result of all moves does not fit, the moves go in chunks as in rt_sites_nni_scores
+ *   (RAOTEH_NNI_CHUNK_BYTES), the sets' passes again per chunk.
+ * Both: each output may be NULL, only what is given crosses PCIe.  Synchronous; two calls return the
+ *   same bits.  Nothing resident changes: the batch's kernel, log-likelihoods, status and totals,
+ *   its rt_step_multi results, the model's own transitions and the rate sets keep what they had.
+ *   recompute_transitions != 0: the sets' exponentials again from the resident rate sets; no
+ *   earlier rt_step_multi is needed.  status: RT_SITE_ZERO_PROB where Lambda_i is not positive,
+ *   else the OR over the sets LIVE at the site of the 2 their passes report.
+ *   RT_ERR_INVALID: no rate sets; a batch of another model; bad class weights; npoints out of
+ *   range, or not 1 without factors; a negative or non-finite factor in a row that counts.
+ *   RT_ERR_SINGULAR: an exponential failed.  RT_ERR_UNSUPPORTED: a partitioned batch; what
+ *   rt_sites_branch_profiles / rt_sites_nni_scores refuse ("rescale", a generic-kernel batch, deep
+ *   trees, nnodes < 2); more than 96 GB of scratch.                          */
+int rt_sites_branch_profiles_mixture(rt_model *model, rt_sites *sites, int recompute_transitions,
+            const double *class_weights, int64_t npoints, const double *factors, double *values,
+            double *sums, double *loglik, int32_t *status);
+int rt_sites_nni_scores_mixture(rt_model *model, rt_sites *sites, int recompute_transitions,
+            const double *class_weights, int64_t npoints, const double *factors, double *values,
+            double *sums, double *loglik, int32_t *status);
 
 /* ---- 3. multi-GPU: one process per GPU, RCCL over xGMI ------------------- */
 

@@ -183,6 +183,10 @@ SIGNATURES = {
     'rt_sites_branch_expectations_mixture': (c_int, [c_void_p, c_void_p, c_int, _p_f64, c_int64, c_int,
                                                      _p_f64, _p_f64, _p_f64, _p_f64, _p_f64, _p_f64,
                                                      _p_f64, _p_i32]),
+    'rt_sites_branch_profiles_mixture': (c_int, [c_void_p, c_void_p, c_int, _p_f64, c_int64, _p_f64,
+                                                 _p_f64, _p_f64, _p_f64, _p_i32]),
+    'rt_sites_nni_scores_mixture': (c_int, [c_void_p, c_void_p, c_int, _p_f64, c_int64, _p_f64,
+                                            _p_f64, _p_f64, _p_f64, _p_i32]),
     'rt_comm_available': (c_int, []),
     'rt_comm_unique_id': (c_int, [POINTER(c_ubyte)]),
     'rt_comm_init': (c_int, [c_void_p, c_int, c_int, POINTER(c_ubyte)]),

@@ -28,8 +28,9 @@
 // rt_sites_branch_expectations_partitioned (at the end): the same read of a partitioned batch,
 // every site under its own rate set -- the kernels' PART forms and the part_* kernels.
 // rt_sites_branch_expectations_mixture (after it): an ordinary batch under a site-class mixture
-// over the rate sets -- the kernels' TOT forms once per set, the mix_* kernels; set_tables is what
-// the two share.
+// over the rate sets -- the kernels' TOT forms once per set, the mix_* kernels (mix_post_kernel:
+// post_common.h, shared with the mixture reads of branch_profile.hip and nni.hip); set_tables is
+// what the two share.
 #include "common.h"
 #include "post_common.h"
 
@@ -356,9 +357,10 @@ struct set_tables {
     bool per_set = false, wide = false;
     size_t ne = 0, tab = 0;                      // K (nnodes - 1) edges; bytes of one step table
     size_t o_E = 0, o_G = 0, o_W = 0, o_B = 0, o_X = 0, o_scale = 0, o_ones = 0, o_ident = 0, o_eq = 0,
-           o_et = 0, o_PTs = 0, o_GT = 0, o_tabP = 0, o_tabG = 0;
+           o_et = 0, o_GT = 0, o_tabG = 0;
     double *E = nullptr, *G = nullptr, *PTs = nullptr, *GT = nullptr;
-    std::vector<int32_t> tabP, tabG;
+    post_set_pt PT;                              // the sets' P^T fragments (post_common.h)
+    std::vector<int32_t> tabG;
 
     void take(post_pass *p, int64_t sets, int n_coefs, bool coefs_per_set)
     {
@@ -377,9 +379,8 @@ struct set_tables {
         o_X = wide ? plan.take(8) : plan.take(ne * 4 * nn * 8);
         o_scale = plan.take(ne * 8); o_ones = plan.take(ne * 8); o_ident = plan.take(ne * 4);
         o_eq = plan.take(ne * 4); o_et = plan.take(ne * 8);
-        o_PTs = p->lane ? plan.take(8) : plan.take((size_t)K * tab);
+        PT.take(p, K);
         o_GT = p->lane ? plan.take(8) : plan.take((size_t)K * nk * tab);
-        o_tabP = plan.take((size_t)K * p->nops * 4);
         o_tabG = plan.take((size_t)K * nk * p->nops * 4);
     }
 
@@ -397,7 +398,8 @@ struct set_tables {
         const size_t nn = (size_t)n * n;
         unsigned char *base = p->base;
         E = (double *)(base + o_E); G = (double *)(base + o_G);
-        PTs = (double *)(base + o_PTs); GT = (double *)(base + o_GT);
+        PT.place(p);
+        PTs = PT.d_PT; GT = (double *)(base + o_GT);
         double *d_W = (double *)(base + o_W), *d_B = (double *)(base + o_B), *d_X = (double *)(base + o_X);
         double *d_scale = (double *)(base + o_scale), *d_ones = (double *)(base + o_ones);
         double *d_et = (double *)(base + o_et);
@@ -428,26 +430,22 @@ struct set_tables {
 
     // n > 4, after post_up (the step -> node table): P^T and G^T of every set as A fragments by two
     // rt_launch_pack_pt launches over step tables that span the sets -- step -> matrix of the table
-    // it is packed from, P [set][node], G [coef][set][edge] (the root's step is never read: any
-    // matrix of the set)
+    // it is packed from, P [set][node] (post_set_pt), G [coef][set][edge] (the root's step is never
+    // read: any matrix of the set)
     int pack(post_pass *p)
     {
-        const rt_rate_sets &r = p->m->multi;
         const int64_t N = p->N, ne1 = N - 1;
-        int *d_tabP = (int *)(p->base + o_tabP), *d_tabG = (int *)(p->base + o_tabG);
-        tabP.resize((size_t)K * p->nops);
+        int *d_tabG = (int *)(p->base + o_tabG);
         tabG.resize((size_t)K * nk * p->nops);
         for (int64_t k = 0; k < K; ++k)
             for (int i = 0; i < p->nops; ++i) {
                 const int64_t v = p->step_node[(size_t)i];
-                tabP[(size_t)(k * p->nops + i)] = (int32_t)(k * N + v);
                 for (int c = 0; c < nk; ++c)
                     tabG[(size_t)((k * nk + c) * p->nops + i)] =
                         (int32_t)((c * K + k) * ne1 + (v ? v - 1 : 0));
             }
-        RT_HIP(hipMemcpyAsync(d_tabP, tabP.data(), tabP.size() * 4, hipMemcpyHostToDevice, p->st));
         RT_HIP(hipMemcpyAsync(d_tabG, tabG.data(), tabG.size() * 4, hipMemcpyHostToDevice, p->st));
-        RT_TRY(rt_launch_pack_pt(p->ctx, (int)p->n, p->NT, p->KP, (int)(K * p->nops), d_tabP, r.d_P, PTs));
+        RT_TRY(PT.pack(p));
         RT_TRY(rt_launch_pack_pt(p->ctx, (int)p->n, p->NT, p->KP, (int)(K * nk * p->nops), d_tabG, G, GT));
         return RT_OK;
     }
@@ -456,42 +454,6 @@ struct set_tables {
 // ---- a site-class mixture over the rate sets (rt_sites_branch_expectations_mixture) ----
 
 constexpr int MIX_POST_LDS = 2048;               // posteriors a combine workgroup stages (16 KB)
-
-// per site, over the K root totals tot [K][nsites] (L_ik; set k live: c_k > 0 and L_ik > 0): the
-// plain sum of c_k L_ik in set order, post [site][K] = c_k L_ik / sum (0 for a set that is not
-// live), loglik, and the status words of the LIVE sets OR-ed (set_status [K][nsites]); no live
-// set: a row of zeros, -inf, RT_SITE_ZERO_PROB
-__global__ void __launch_bounds__(256)
-mix_post_kernel(int K, long nsites, const double *__restrict__ cw, const double *__restrict__ tot,
-                const int *__restrict__ set_status, double *__restrict__ post,
-                double *__restrict__ loglik, int *__restrict__ status)
-{
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nsites) return;
-    double sum = 0.0;
-    for (int k = 0; k < K; ++k) {
-        const double c = cw[k];
-        if (!(c > 0.0)) continue;
-        const double L = tot[(size_t)k * nsites + i];
-        if (L > 0.0) sum = __dadd_rn(sum, __dmul_rn(c, L));
-    }
-    const bool none = !(sum > 0.0);
-    int st = none ? RT_SITE_ZERO_PROB : 0;
-    for (int k = 0; k < K; ++k) {
-        const double c = cw[k];
-        double pk = 0.0;
-        if (!none && c > 0.0) {
-            const double L = tot[(size_t)k * nsites + i];
-            if (L > 0.0) {
-                pk = __dmul_rn(c, L) / sum;
-                st |= set_status[(size_t)k * nsites + i];
-            }
-        }
-        post[(size_t)i * K + k] = pk;
-    }
-    loglik[i] = none ? -HUGE_VAL : log(sum);
-    status[i] = st;
-}
 
 // values[i][j] = sum_k post[i][k] x[k][i][j] in set order, j over the site's (node, coefficient)
 // row of `row` doubles; a set with post == 0 is skipped (nothing of a set that is not live is
@@ -852,18 +814,9 @@ extern "C" int rt_sites_branch_expectations_mixture(rt_model *m, rt_sites *s, in
     static const char who[] = "rt_sites_branch_expectations_mixture";
     post_pass p;                                 // (alive until the synchronisation below)
     RT_TRY(post_open(&p, who, m, s));
+    RT_TRY(post_class_weights(who, m, class_weights));
     const rt_rate_sets &r = m->multi;
     const int64_t K = r.K;
-    RT_REQUIRE(K >= 1, "%s: the model holds no rate sets (rt_model_set_rate_sets)", who);
-    RT_REQUIRE(class_weights, "%s: class_weights is NULL", who);
-    bool any = false;
-    for (int64_t k = 0; k < K; ++k) {
-        const double c = class_weights[k];
-        RT_REQUIRE(std::isfinite(c) && c >= 0.0, "class_weights[%lld] is not finite and >= 0",
-                   (long long)k);
-        any = any || c > 0.0;
-    }
-    RT_REQUIRE(any, "class_weights are all zero");
     RT_REQUIRE(n_coefs >= 1 && coefs, "at least one coefficient matrix is needed");
     if (n_coefs > RT_MAX_BRANCH_COEFS) {
         rt_set_error("%s: at most %d coefficient matrices (%lld here)", who, RT_MAX_BRANCH_COEFS,
@@ -952,7 +905,7 @@ extern "C" int rt_sites_branch_expectations_mixture(rt_model *m, rt_sites *s, in
         RT_HIP(hipGetLastError());
     }
     // 3. posteriors, values, sums
-    hipLaunchKernelGGL(mix_post_kernel, dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)K,
+    hipLaunchKernelGGL(mix_post_kernel<256>, dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)K,
                        (long)nsites, (const double *)d_cw, (const double *)d_tot, (const int *)d_stat,
                        d_post, d_ll, p.d_status);
     RT_HIP(hipGetLastError());

@@ -24,6 +24,9 @@
 //      the per-site array is asked for, its transpose to [site][node][point].
 //
 // Nothing of the batch or the model is written; two calls give the same bits.
+//
+// rt_sites_branch_profiles_mixture (at the end): the same read under a site-class mixture over the
+// model's rate sets -- the kernels' MIX forms once per set into one accumulator.
 #include "common.h"
 #include "post_common.h"
 
@@ -48,19 +51,26 @@ __device__ __forceinline__ double bp_value(double ratio, bool zero, double tv)
 // steps[i] = {node, step of the parent, stream position of an observed leaf or -1, 1 if the node
 // has children}; the root is the last step.  GfragT: [point][step] A fragments of P(tau)^T;
 // tlen: the resident lengths [node]; out [node][point][site].
-template <int NT, int KS>
+// MIX (rt_sites_branch_profiles_mixture, one launch per rate set k of weight ck > 0 against the
+// set's fragments, in set order on one stream): the root's sum L_ik goes to root_tot[site], the
+// status word is the set's own, and the RAW term ck L_ik * ratio = ck L_ik(tau) is written to `out`
+// by the first set and added to it by the later ones (the same lane, launches in order: a fixed
+// sum); the logs are mix_log_ratio_kernel's, once the sets are in.
+template <int NT, int KS, bool MIX = false>
 __global__ void __launch_bounds__(64 * NT)
 bp_down_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT, int np, int nops,
                const int4 *__restrict__ steps, const double *__restrict__ Larr,
                const double *__restrict__ Marr, double *__restrict__ Darr,
                const double *__restrict__ obs, int K, const double *__restrict__ root_w,
                const double *__restrict__ tlen, int n, double *__restrict__ out,
-               int *__restrict__ status, long nsites, long nblocks)
+               int *__restrict__ status, long nsites, long nblocks, double ck, int first,
+               double *__restrict__ root_tot)
 {
     constexpr int KP = (KS + 1) / 2;
     __shared__ double xb[NT * 4 * 64];
     __shared__ double red[NT][16];
     __shared__ double sums[2][BP_CHUNK][NT][16];
+    [[maybe_unused]] double scale = 0.0;         // MIX: ck L_ik of the lane's site
     const int lane = threadIdx.x & 63;
     const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long blk = blockIdx.x;
@@ -86,10 +96,13 @@ bp_down_kernel(const double *__restrict__ PfragT, const double *__restrict__ Gfr
         zero = !(tot > 0.0);
 #pragma unroll
         for (int r = 0; r < 4; ++r) Darr[o + r * 64] = zero ? 0.0 : wl[r] / tot;
+        if constexpr (MIX) scale = zero ? 0.0 : __dmul_rn(ck, tot);
         if (writer) {
             if (zero) atomicOr(&status[site], RT_SITE_ZERO_PROB);
+            if constexpr (MIX) root_tot[site] = tot;
             double *row = out + (size_t)steps[i].x * np * nsites + site;
-            for (int g = 0; g < np; ++g) row[(size_t)g * nsites] = 0.0;
+            if (!MIX || first)
+                for (int g = 0; g < np; ++g) row[(size_t)g * nsites] = 0.0;
         }
     }
     const size_t frag = ((size_t)m * KP * 64 + lane) * 2;
@@ -128,12 +141,17 @@ bp_down_kernel(const double *__restrict__ PfragT, const double *__restrict__ Gfr
             }
             __syncthreads();
             if (writer)
-                for (int j = 0; j < cnt; ++j)
-                    row[(size_t)(g0 + j) * nsites] = down_total<NT>(sums[par][j], lane);
+                for (int j = 0; j < cnt; ++j) {
+                    double *x = row + (size_t)(g0 + j) * nsites;
+                    const double t = down_total<NT>(sums[par][j], lane);
+                    if constexpr (MIX) *x = first ? __dmul_rn(scale, t) : __dadd_rn(*x, __dmul_rn(scale, t));
+                    else *x = t;
+                }
             par ^= 1;
         }
     }
     if (bad && site_ok) atomicOr(&status[site], 2);
+    if constexpr (MIX) return;
     // the tile's ratios -> values, by all waves: lane group q of the workgroup takes the rows
     // (node, point) q, q + 4 NT, ... of its site (the barrier: wave 0's stores are visible)
     __syncthreads();
@@ -148,15 +166,16 @@ bp_down_kernel(const double *__restrict__ PfragT, const double *__restrict__ Gfr
 }
 
 // n <= 4: one lane per site; arrays [node][state][site], nodes in preorder; G [point][node][N][N]
-// (the same address in every lane: the scalar path)
-template <int N>
+// (the same address in every lane: the scalar path).  MIX: as bp_down_kernel, P and G of the set.
+template <int N, bool MIX = false>
 __global__ void __launch_bounds__(256)
 bp_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const double *__restrict__ G,
                int np, const int *__restrict__ parent, const int *__restrict__ node_k,
                const void *__restrict__ obs, int compact, int K, int block_sites,
                const double *__restrict__ root_w, const double *__restrict__ tlen,
                double *__restrict__ Larr, double *__restrict__ Marr, double *__restrict__ Darr,
-               double *__restrict__ out, int *__restrict__ status)
+               double *__restrict__ out, int *__restrict__ status, double ck, int first,
+               double *__restrict__ root_tot)
 {
     const long site = (long)blockIdx.x * 256 + threadIdx.x;
     if (site >= nsites) return;
@@ -164,11 +183,17 @@ bp_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const doub
     lane_up<N, true>(nnodes, nsites, site, P, parent, node_k, obs, compact, K, block_sites, Larr, Marr);
     // down: the root, then every node after its parent
     bool zero;
+    [[maybe_unused]] double scale = 0.0;         // MIX: ck L_ik
     {
-        double d[N];
-        zero = lane_root<N>(nsites, site, root_w, Larr, Darr, d);
+        double d[N], tot = 0.0;
+        zero = lane_root<N>(nsites, site, root_w, Larr, Darr, d, MIX ? &tot : nullptr);
         if (zero) status[site] |= RT_SITE_ZERO_PROB;
-        for (int g = 0; g < np; ++g) out[(size_t)g * nsites + site] = 0.0;
+        if constexpr (MIX) {
+            root_tot[site] = tot;
+            scale = zero ? 0.0 : __dmul_rn(ck, tot);
+        }
+        if (!MIX || first)
+            for (int g = 0; g < np; ++g) out[(size_t)g * nsites + site] = 0.0;
     }
     bool bad = false;
     for (int v = 1; v < nnodes; ++v) {
@@ -184,7 +209,7 @@ bp_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const doub
             for (int a = 0; a < N; ++a) y += Pv[a * N + b] * u[a];
             Darr[idx(v, b)] = y * L[b];
         }
-        const double tv = tlen[v];
+        [[maybe_unused]] const double tv = MIX ? 1.0 : tlen[v];
         for (int g = 0; g < np; ++g) {
             const double *Gv = G + ((size_t)g * nnodes + v) * N * N;
             double t = 0.0;
@@ -195,7 +220,9 @@ bp_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const doub
                 for (int a = 0; a < N; ++a) y += Gv[a * N + b] * u[a];
                 t += y * L[b];
             }
-            out[((size_t)v * np + g) * nsites + site] = bp_value(t, zero, tv);
+            double *x = out + ((size_t)v * np + g) * nsites + site;
+            if constexpr (MIX) *x = first ? __dmul_rn(scale, t) : __dadd_rn(*x, __dmul_rn(scale, t));
+            else *x = bp_value(t, zero, tv);
         }
     }
     if (bad) status[site] |= 2;
@@ -277,7 +304,7 @@ extern "C" int rt_sites_branch_profiles(rt_model *m, rt_sites *s, int recompute_
                                (const double *)grid.d_G, np, d_tab, d_tab + N, (const void *)s->d_obs,
                                s->compact_states, (int)s->nobs, s->block_sites,
                                (const double *)m->d_root, (const double *)m->d_t, p.d_L, p.d_M, p.d_D,
-                               d_val, d_status);
+                               d_val, d_status, 1.0, 1, (double *)nullptr);
             return RT_OK;
         }));
     } else {
@@ -290,7 +317,7 @@ extern "C" int rt_sites_branch_profiles(rt_model *m, rt_sites *s, int recompute_
                                (const int4 *)p.d_steps, (const double *)p.d_L, (const double *)p.d_M,
                                p.d_D, (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
                                (const double *)m->d_t, (int)n, d_val, d_status, (long)x->nsites,
-                               (long)x->nblocks);
+                               (long)x->nblocks, 1.0, 1, (double *)nullptr);
             return RT_OK;
         }));
     }
@@ -313,5 +340,165 @@ extern "C" int rt_sites_branch_profiles(rt_model *m, rt_sites *s, int recompute_
     if (status) RT_HIP(hipMemcpyAsync(status, d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
     RT_HIP(hipStreamSynchronize(st));
     RT_TRY(post_grid_result(&p, &grid));
+    return RT_OK;
+}
+
+namespace {
+
+__global__ void __launch_bounds__(256)
+set_grid_args_kernel(int K, int np, int nnodes, const int *__restrict__ set_qidx,
+                     const double *__restrict__ set_t, const double *__restrict__ fac,
+                     const double *__restrict__ cw, int *__restrict__ qidx, double *__restrict__ tau)
+{
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= (long)K * np * nnodes) return;
+    const int v = (int)(j % nnodes), g = (int)(j / nnodes % np), k = (int)(j / nnodes / np);
+    const bool run = v > 0 && cw[k] > 0.0;
+    qidx[j] = run ? set_qidx[(size_t)k * nnodes + v] : -1;
+    tau[j] = run ? fac[(size_t)v * np + g] * set_t[(size_t)k * nnodes + v] : 0.0;
+}
+
+}  // namespace
+
+int rt_launch_set_grid_args(rt_ctx *ctx, int K, int np, int nnodes, const int32_t *d_set_qidx,
+                            const double *d_set_t, const double *d_fac, const double *d_cw,
+                            int32_t *d_qidx, double *d_tau)
+{
+    const long cnt = (long)K * np * nnodes;
+    hipLaunchKernelGGL(set_grid_args_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream,
+                       K, np, nnodes, (const int *)d_set_qidx, d_set_t, d_fac, d_cw, (int *)d_qidx, d_tau);
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+// The profiles of an ORDINARY batch under a site-class mixture over the model's K rate sets, trial
+// lengths as factors of every set's own resident lengths:
+//   1. P_kv(factor t_kv) of every set, point and edge in ONE launch of the sets' exponential
+//      (post_set_grid), their transposes and the sets' P^T as A fragments (post_set_pt);
+//   2. per set k with c_k > 0, on the one stream over one L, M, D scratch: the upward pass through
+//      a view of set k's tables (post_up_set), then the MIX instance of bp_down_kernel (n <= 4:
+//      bp_lane_kernel) against set k's fragments -- the term c_k L_ik(tau) into ONE accumulator
+//      [node][point][site], the sets added in set order, L_ik and a status word per set;
+//   3. mix_post_kernel (log Lambda_i, the status of the live sets), mix_log_ratio_kernel (the
+//      accumulator -> values), then profile_sums_kernel and the transpose as the single-set call.
+extern "C" int rt_sites_branch_profiles_mixture(rt_model *m, rt_sites *s, int recompute_transitions,
+                                                const double *class_weights, int64_t npoints,
+                                                const double *factors, double *values, double *sums,
+                                                double *loglik, int32_t *status)
+{
+    static const char who[] = "rt_sites_branch_profiles_mixture";
+    post_pass p;                                 // (alive until the synchronisation below)
+    RT_TRY(post_open(&p, who, m, s));
+    RT_TRY(post_class_weights(who, m, class_weights));
+    RT_TRY(post_set_grid::check(&p, npoints, factors));
+    const rt_rate_sets &r = m->multi;
+    const int64_t K = r.K, n = p.n, N = p.N, nsites = p.nsites;
+    const int np = (int)npoints;
+    p.per_set = true;
+    RT_TRY(post_layout(&p, true));
+    RT_REQUIRE(r.P_stride == N * n * n, "unexpected stride of the sets' transition matrices");
+    const size_t rows = (size_t)N * np;
+    post_plan &plan = p.plan;
+    post_set_grid grid;                          // (alive until the synchronisation below)
+    post_set_pt PT;
+    const size_t o_val = plan.take(rows * nsites * 8);
+    const size_t o_valT = plan.take(values ? rows * nsites * 8 : 8);
+    const size_t o_sum = plan.take(rows * 8);
+    const size_t o_tot = plan.take((size_t)K * nsites * 8), o_stat = plan.take((size_t)K * nsites * 4);
+    const size_t o_post = plan.take((size_t)nsites * K * 8), o_ll = plan.take((size_t)nsites * 8);
+    const size_t o_cw = plan.take((size_t)K * 8);
+    const size_t o_dead = plan.take((size_t)N * 4), o_tl = plan.take((size_t)N * 8);
+    RT_TRY(grid.take(&p, K, np));
+    PT.take(&p, K);
+    RT_TRY(post_begin(&p, recompute_transitions));
+    PT.place(&p);
+    hipStream_t st = p.st;
+    unsigned char *base = p.base;
+    double *d_val = (double *)(base + o_val), *d_valT = (double *)(base + o_valT);
+    double *d_sum = (double *)(base + o_sum), *d_tot = (double *)(base + o_tot);
+    double *d_post = (double *)(base + o_post), *d_ll = (double *)(base + o_ll);
+    double *d_cw = (double *)(base + o_cw), *d_tl = (double *)(base + o_tl);
+    int *d_stat = (int *)(base + o_stat), *d_dead = (int *)(base + o_dead);
+    std::vector<int32_t> internal((size_t)N, 0);
+    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
+    RT_HIP(hipMemcpyAsync(d_cw, class_weights, (size_t)K * 8, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemsetAsync(d_stat, 0, (size_t)K * nsites * 4, st));
+    RT_HIP(hipMemsetAsync(d_tot, 0, (size_t)K * nsites * 8, st));
+    hipLaunchKernelGGL(mix_dead_edge_kernel<256>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, (int)K,
+                       (int)N, (const double *)d_cw, (const double *)r.d_t, d_dead, d_tl);
+    RT_HIP(hipGetLastError());
+    // 1. the trial matrices of every set
+    RT_TRY(grid.launch(&p, d_cw, factors));
+    RT_TRY(post_up(&p, internal.data(), false));
+    if (!p.lane) {
+        RT_TRY(PT.pack(&p));
+        RT_TRY(grid.pack(&p));
+    }
+    // 2. the passes, set by set (a set of weight zero is never live: not run, never read)
+    int first = 1;
+    for (int64_t k = 0; k < K; ++k) {
+        const double ck = class_weights[k];
+        if (!(ck > 0.0)) continue;
+        double *totk = d_tot + (size_t)k * nsites;
+        int *statk = d_stat + (size_t)k * nsites;
+        if (p.lane) {
+            const int *d_tab = p.d_ptab;
+            RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
+                hipLaunchKernelGGL((bp_lane_kernel<decltype(nv)::value, true>),
+                                   dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)N,
+                                   (long)nsites, (const double *)(r.d_P + k * r.P_stride),
+                                   grid.G_of_set(&p, k), np, d_tab, d_tab + N, (const void *)s->d_obs,
+                                   s->compact_states, (int)s->nobs, s->block_sites,
+                                   (const double *)m->d_root, (const double *)nullptr, p.d_L, p.d_M, p.d_D,
+                                   d_val, statk, ck, first, totk);
+                return RT_OK;
+            }));
+        } else {
+            const rt_sites *x = p.x;
+            RT_TRY(post_up_set(&p, k, nullptr));
+            RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
+                constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
+                hipLaunchKernelGGL((bp_down_kernel<NT, KS, true>), dim3((unsigned)x->nblocks), dim3(64 * NT),
+                                   0, st, PT.of_set(k), grid.GT_of_set(k), np, p.nops,
+                                   (const int4 *)p.d_steps, (const double *)p.d_L, (const double *)p.d_M,
+                                   p.d_D, (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
+                                   (const double *)nullptr, (int)n, d_val, statk, (long)x->nsites,
+                                   (long)x->nblocks, ck, first, totk);
+                return RT_OK;
+            }));
+        }
+        RT_HIP(hipGetLastError());
+        first = 0;
+    }
+    // 3. log Lambda_i and the status, the values, the sums; only what was asked for crosses PCIe
+    hipLaunchKernelGGL(mix_post_kernel<256>, dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)K,
+                       (long)nsites, (const double *)d_cw, (const double *)d_tot, (const int *)d_stat,
+                       d_post, d_ll, p.d_status);
+    RT_HIP(hipGetLastError());
+    if (values || sums) {
+        hipLaunchKernelGGL(mix_log_ratio_kernel<256>,
+                           dim3((unsigned)((nsites + 255) / 256), (unsigned)std::min<size_t>(rows, 1024)),
+                           dim3(256), 0, st, (long)rows, np, (long)nsites, (const double *)d_ll,
+                           (const int *)p.d_status, (const int *)d_dead, d_val);
+        RT_HIP(hipGetLastError());
+    }
+    if (sums) {
+        hipLaunchKernelGGL(profile_sums_kernel, dim3((unsigned)rows), dim3(256), 0, st, np, (long)nsites,
+                           (const double *)d_val, (const double *)s->d_weights, (const int *)p.d_status,
+                           (const double *)d_tl, d_sum);
+        RT_HIP(hipGetLastError());
+        RT_HIP(hipMemcpyAsync(sums, d_sum, rows * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (values) {
+        hipLaunchKernelGGL(post_transpose_kernel<32>,
+                           dim3((unsigned)((nsites + 31) / 32), (unsigned)((rows + 31) / 32)), dim3(256),
+                           0, st, (long)rows, (long)nsites, (const double *)d_val, d_valT);
+        RT_HIP(hipGetLastError());
+        RT_HIP(hipMemcpyAsync(values, d_valT, rows * nsites * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (loglik) RT_HIP(hipMemcpyAsync(loglik, d_ll, (size_t)nsites * 8, hipMemcpyDeviceToHost, st));
+    if (status) RT_HIP(hipMemcpyAsync(status, p.d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipStreamSynchronize(st));
+    RT_TRY(grid.result(&p));
     return RT_OK;
 }

@@ -27,6 +27,10 @@
 //
 // Steps 2 and 3 run per chunk of moves where the result of all moves would not fit the scratch.
 // Nothing of the batch or the model is written; two calls give the same bits.
+//
+// rt_sites_nni_scores_mixture (at the end): the same scores under a site-class mixture over the
+// model's rate sets -- the kernels' MIX forms once per set into one accumulator, the root scaled by
+// the class weight instead of 1 / L_i.
 #include "common.h"
 #include "post_common.h"
 
@@ -58,14 +62,22 @@ __device__ __forceinline__ double nni_value(double ratio, bool zero)
 // mv0 .. mv1 - 1.  The first chunk (mv0 == 0) makes the `up` pass, later ones find it in Uarr.
 // (NT = 7: four waves per SIMD asked for, as bp_down_kernel has them -- left alone KS = 28 takes
 // 130 VGPRs.  NT = 8 takes 130 .. 136 and runs three: held to 128 it spills to scratch.)
-template <int NT, int KS>
+// MIX (rt_sites_nni_scores_mixture, one launch per rate set k of weight ck > 0 and chunk against the
+// set's fragments, in set order on one stream): the root is scaled by ck, not by 1 / L_ik -- a set
+// under which the resident tree is impossible may be live after a move -- so a move's sum is the
+// RAW term ck L_ik(moved tree, tau); it is written to `out` by the first set and added to it by the
+// later ones (the same lane, launches in order: a fixed sum).  Every launch makes the `up` pass
+// (the scratch is the current set's), L_ik goes to root_tot[site], the status word is the set's
+// own, and the logs are mix_log_ratio_kernel's once the sets are in.
+template <int NT, int KS, bool MIX = false>
 __global__ void __launch_bounds__(64 * NT, NT == 7 ? 4 : 1)
 nni_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT, int np, int nops,
            const int4 *__restrict__ steps, const int *__restrict__ tabp,
            const double *__restrict__ Larr, const double *__restrict__ Marr,
            double *__restrict__ Uarr, const double *__restrict__ obs, int K,
            const double *__restrict__ root_w, int n, int mv0, int mv1, double *__restrict__ out,
-           int *__restrict__ status, long nsites, long nblocks)
+           int *__restrict__ status, long nsites, long nblocks, double ck, int first,
+           double *__restrict__ root_tot)
 {
     constexpr int KP = (KS + 1) / 2;
     __shared__ double xb[NT * 4 * 64];
@@ -86,9 +98,10 @@ nni_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT,
     const double *og = obs + (size_t)blk * K * (KP * 128) + lane * 2;
     // 1. root: the site's likelihood sum_states(w L), up = w / it; then the `up` vectors of the
     // nodes with children, a parent before its children (shared with place.hip)
-    const bool zero = down_up_pass<NT, KS>(mv0 == 0, xb, red, tab, PfragT, nops, steps, Larr, Marr,
-                                           Uarr, og, root_w, live, m, lane, blk, nblocks, writer,
-                                           status, site);
+    [[maybe_unused]] const bool zero =
+        down_up_pass<NT, KS, MIX>(MIX || mv0 == 0, xb, red, tab, PfragT, nops, steps, Larr, Marr, Uarr,
+                                  og, root_w, live, m, lane, blk, nblocks, writer, status, site, ck,
+                                  root_tot);
     double a[2 * KP];
     // 2. the moves about every node v with children and siblings
     int par = 0;                                 // the half of `sums` the next chunk writes
@@ -170,12 +183,17 @@ nni_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT,
                     }
                     __syncthreads();
                     if (writer)
-                        for (int j = 0; j < cnt; ++j)
-                            row[(size_t)(g0 + j) * nsites] = down_total<NT>(sums[par][j], lane);
+                        for (int j = 0; j < cnt; ++j) {
+                            double *x = row + (size_t)(g0 + j) * nsites;
+                            const double t = down_total<NT>(sums[par][j], lane);
+                            if constexpr (MIX) *x = first ? t : __dadd_rn(*x, t);
+                            else *x = t;
+                        }
                     par ^= 1;
                 }
             }
     }
+    if constexpr (MIX) return;
     // the tile's ratios -> values, by all waves: lane group q of the workgroup takes the rows
     // (move, point) q, q + 4 NT, ... of its site (the barrier: wave 0's stores are visible)
     __syncthreads();
@@ -189,15 +207,17 @@ nni_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT,
 }
 
 // n <= 4: one lane per site; arrays [node][state][site], nodes in preorder; G [point][node][N][N]
-// or null for the resident P (the same address in every lane: the scalar path)
-template <int N>
+// or null for the resident P (the same address in every lane: the scalar path).  MIX: as
+// nni_kernel, P and G of the set.
+template <int N, bool MIX = false>
 __global__ void __launch_bounds__(256)
 nni_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const double *__restrict__ G,
                 int np, const int *__restrict__ parent, const int *__restrict__ node_k,
                 const int *__restrict__ tabp, const void *__restrict__ obs, int compact, int K,
                 int block_sites, const double *__restrict__ root_w, double *__restrict__ Larr,
                 double *__restrict__ Marr, double *__restrict__ Uarr, int mv0, int mv1,
-                double *__restrict__ out, int *__restrict__ status)
+                double *__restrict__ out, int *__restrict__ status, double ck, int first,
+                double *__restrict__ root_tot)
 {
     const long site = (long)blockIdx.x * 256 + threadIdx.x;
     if (site >= nsites) return;
@@ -210,12 +230,13 @@ nni_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const dou
 #pragma unroll
             for (int s = 0; s < N; ++s) x[s] = 1.0;
     };
-    if (mv0 == 0)
+    if (MIX || mv0 == 0)
         lane_up<N, true>(nnodes, nsites, site, P, parent, node_k, obs, compact, K, block_sites, Larr,
                          Marr);
     // the `up` vectors: the root, then every node with children after its parent
-    const bool zero = lane_up_pass<N>(mv0 == 0, nnodes, nsites, site, P, parent, node_k, tab, obs,
-                                      compact, K, block_sites, root_w, Larr, Marr, Uarr, status);
+    [[maybe_unused]] const bool zero =
+        lane_up_pass<N, MIX>(MIX || mv0 == 0, nnodes, nsites, site, P, parent, node_k, tab, obs, compact,
+                             K, block_sites, root_w, Larr, Marr, Uarr, status, ck, root_tot);
     for (int v = 1; v < nnodes; ++v) {
         const int p = parent[v];
         const int c0 = tab.cptr[v], c1 = tab.cptr[v + 1], s0 = tab.cptr[p], s1 = tab.cptr[p + 1];
@@ -260,7 +281,9 @@ nni_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const dou
                         for (int a = 0; a < N; ++a) y += Gv[a * N + b] * x[a];
                         t += y * lp[b];
                     }
-                    out[((size_t)(mv - mv0) * np + g) * nsites + site] = nni_value(t, zero);
+                    double *o = out + ((size_t)(mv - mv0) * np + g) * nsites + site;
+                    if constexpr (MIX) *o = first ? t : __dadd_rn(*o, t);
+                    else *o = nni_value(t, zero);
                 }
             }
     }
@@ -328,6 +351,22 @@ int nni_moves_out(int64_t cnt, int32_t *moves, int64_t capacity, int64_t *nmoves
     return RT_OK;
 }
 
+// the moves of one chunk: their result (and its transpose), per_move bytes a move, within the chunk
+// size and the cap of the scratch
+int64_t nni_chunk_moves(const post_plan &plan, size_t per_move, int np, int64_t nmoves)
+{
+    size_t chunk_bytes = NNI_CHUNK_BYTES;
+    if (const char *e = getenv("RAOTEH_NNI_CHUNK_BYTES")) {      // (tests: many chunks at small sizes)
+        const long long v = atoll(e);
+        if (v > 0) chunk_bytes = (size_t)v;
+    }
+    const double room = NNI_SCRATCH_CAP - (double)plan.total - 4096.0;
+    if (room < (double)chunk_bytes) chunk_bytes = room > 0.0 ? (size_t)room : 0;
+    int64_t CH = std::max<int64_t>(1, (int64_t)(chunk_bytes / per_move));
+    CH = std::min<int64_t>(CH, std::max<int64_t>(1, ((int64_t)1 << 21) / np));   // (the grids' y)
+    return std::min<int64_t>(CH, std::max<int64_t>(nmoves, 1));
+}
+
 }  // namespace
 
 extern "C" int rt_model_nni_moves(const rt_model *m, int32_t *moves, int64_t capacity, int64_t *nmoves)
@@ -385,18 +424,7 @@ extern "C" int rt_sites_nni_scores(rt_model *m, rt_sites *s, int recompute_trans
     const size_t tab_ints = (size_t)4 * cnt;
     const size_t o_tab = plan.take(tab_ints * 4);
     const size_t o_sum = plan.take((size_t)std::max<int64_t>(nmoves, 1) * np * 8);
-    // the moves of one chunk: their result (and its transpose) within the chunk size and the cap
-    const size_t per_move = (size_t)np * nsites * 8 * (values ? 2 : 1);
-    size_t chunk_bytes = NNI_CHUNK_BYTES;
-    if (const char *e = getenv("RAOTEH_NNI_CHUNK_BYTES")) {      // (tests: many chunks at small sizes)
-        const long long v = atoll(e);
-        if (v > 0) chunk_bytes = (size_t)v;
-    }
-    const double room = NNI_SCRATCH_CAP - (double)plan.total - 4096.0;
-    if (room < (double)chunk_bytes) chunk_bytes = room > 0.0 ? (size_t)room : 0;
-    int64_t CH = std::max<int64_t>(1, (int64_t)(chunk_bytes / per_move));
-    CH = std::min<int64_t>(CH, std::max<int64_t>(1, ((int64_t)1 << 21) / np));   // (the grids' y)
-    CH = std::min<int64_t>(CH, std::max<int64_t>(nmoves, 1));
+    const int64_t CH = nni_chunk_moves(plan, (size_t)np * nsites * 8 * (values ? 2 : 1), np, nmoves);
     const size_t chunk_rows = (size_t)CH * np;
     const size_t o_val = plan.take(chunk_rows * nsites * 8);
     const size_t o_valT = plan.take(values ? chunk_rows * nsites * 8 : 8);
@@ -428,7 +456,7 @@ extern "C" int rt_sites_nni_scores(rt_model *m, rt_sites *s, int recompute_trans
                                    (const double *)(lengths ? grid.d_G : nullptr), np, d_ptab, d_ptab + N,
                                    (const int *)d_tab, (const void *)s->d_obs, s->compact_states,
                                    (int)s->nobs, s->block_sites, (const double *)m->d_root, p.d_L, p.d_M,
-                                   p.d_D, (int)mv0, (int)mv1, d_val, d_status);
+                                   p.d_D, (int)mv0, (int)mv1, d_val, d_status, 1.0, 1, (double *)nullptr);
                 return RT_OK;
             }));
         } else {
@@ -441,7 +469,7 @@ extern "C" int rt_sites_nni_scores(rt_model *m, rt_sites *s, int recompute_trans
                                    (const double *)p.d_L, (const double *)p.d_M, p.d_D,
                                    (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
                                    (int)n, (int)mv0, (int)mv1, d_val, d_status, (long)x->nsites,
-                                   (long)x->nblocks);
+                                   (long)x->nblocks, 1.0, 1, (double *)nullptr);
                 return RT_OK;
             }));
         }
@@ -469,5 +497,164 @@ extern "C" int rt_sites_nni_scores(rt_model *m, rt_sites *s, int recompute_trans
     if (status) RT_HIP(hipMemcpyAsync(status, d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
     RT_HIP(hipStreamSynchronize(st));
     if (lengths) RT_TRY(post_grid_result(&p, &grid));
+    return RT_OK;
+}
+
+// The same scores of an ORDINARY batch under a site-class mixture over the model's K rate sets, trial
+// lengths as factors of every set's own resident length of the edge above v:
+//   1. factors given: P_kv(factor t_kv) of every set, point and edge in ONE launch of the sets'
+//      exponential (post_set_grid); the sets' P^T as A fragments (post_set_pt);
+//   2. per chunk of moves and per set k with c_k > 0, on the one stream over one L, M, U scratch: the
+//      upward pass through a view of set k's tables (post_up_set), then the MIX instance of
+//      nni_kernel (n <= 4: nni_lane_kernel) -- the term c_k L_ik(moved tree, tau) into ONE
+//      accumulator [move][point][site], the sets added in set order, L_ik and a status word per set;
+//   3. mix_post_kernel (log Lambda_i, the status), mix_log_ratio_kernel (the accumulator ->
+//      values), then nni_sums_kernel and the transpose as the single-set call.
+// Nothing is divided before the end: exact where L_ik == 0 on the resident tree.
+extern "C" int rt_sites_nni_scores_mixture(rt_model *m, rt_sites *s, int recompute_transitions,
+                                           const double *class_weights, int64_t npoints,
+                                           const double *factors, double *values, double *sums,
+                                           double *loglik, int32_t *status)
+{
+    static const char who[] = "rt_sites_nni_scores_mixture";
+    post_pass p;                                 // (alive until the synchronisation below)
+    RT_TRY(post_open(&p, who, m, s));
+    RT_TRY(post_class_weights(who, m, class_weights));
+    const rt_rate_sets &r = m->multi;
+    const int64_t K = r.K, n = p.n, N = p.N, nsites = p.nsites;
+    // the moves; the rows of `factors` that count are those of the nodes with one
+    std::vector<int32_t> first((size_t)N + 1, 0);
+    const int64_t nmoves = nni_enumerate(m, first.data(), nullptr);
+    first[(size_t)N] = (int32_t)nmoves;
+    std::vector<unsigned char> has_move((size_t)N, 0);
+    for (int64_t v = 1; v < N; ++v) has_move[(size_t)v] = first[(size_t)v + 1] > first[(size_t)v];
+    if (factors)
+        RT_TRY(post_set_grid::check(&p, npoints, factors, has_move.data()));
+    else
+        RT_REQUIRE(npoints == 1, "%s: without factors the edge above v keeps its matrices: 1 grid "
+                   "point (%lld here)", who, (long long)npoints);
+    RT_REQUIRE(nmoves * npoints < (int64_t)1 << 31, "%s: too many moves", who);
+    const int np = (int)npoints;
+    p.per_set = true;
+    RT_TRY(post_layout(&p, true));
+    RT_REQUIRE(r.P_stride == N * n * n, "unexpected stride of the sets' transition matrices");
+    post_plan &plan = p.plan;
+    post_set_grid grid;                          // (alive until the synchronisation below)
+    post_set_pt PT;
+    if (factors) RT_TRY(grid.take(&p, K, np));
+    PT.take(&p, K);
+    const int cnt = p.lane ? (int)N : p.nops;    // slots of the move tables
+    const size_t tab_ints = (size_t)4 * cnt;
+    const size_t o_tab = plan.take(tab_ints * 4);
+    const size_t o_sum = plan.take((size_t)std::max<int64_t>(nmoves, 1) * np * 8);
+    const size_t o_tot = plan.take((size_t)K * nsites * 8), o_stat = plan.take((size_t)K * nsites * 4);
+    const size_t o_post = plan.take((size_t)nsites * K * 8), o_ll = plan.take((size_t)nsites * 8);
+    const size_t o_cw = plan.take((size_t)K * 8);
+    const int64_t CH = nni_chunk_moves(plan, (size_t)np * nsites * 8 * (values ? 2 : 1), np, nmoves);
+    const size_t chunk_rows = (size_t)CH * np;
+    const size_t o_val = plan.take(chunk_rows * nsites * 8);
+    const size_t o_valT = plan.take(values ? chunk_rows * nsites * 8 : 8);
+    RT_TRY(post_begin(&p, recompute_transitions));
+    PT.place(&p);
+    hipStream_t st = p.st;
+    unsigned char *base = p.base;
+    double *d_val = (double *)(base + o_val), *d_valT = (double *)(base + o_valT);
+    double *d_sum = (double *)(base + o_sum), *d_tot = (double *)(base + o_tot);
+    double *d_post = (double *)(base + o_post), *d_ll = (double *)(base + o_ll);
+    double *d_cw = (double *)(base + o_cw);
+    int *d_tab = (int *)(base + o_tab), *d_stat = (int *)(base + o_stat);
+    std::vector<int32_t> internal((size_t)N, 0);
+    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
+    RT_HIP(hipMemcpyAsync(d_cw, class_weights, (size_t)K * 8, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemsetAsync(d_stat, 0, (size_t)K * nsites * 4, st));
+    RT_HIP(hipMemsetAsync(d_tot, 0, (size_t)K * nsites * 8, st));
+    if (factors) RT_TRY(grid.launch(&p, d_cw, factors, has_move.data()));
+    RT_TRY(post_up(&p, internal.data(), false));
+    // the move tables, by step (n > 4) or by node
+    std::vector<int32_t> tab;
+    post_tab_build(&p, first.data(), &tab);
+    RT_HIP(hipMemcpyAsync(d_tab, tab.data(), tab_ints * 4, hipMemcpyHostToDevice, st));
+    if (!p.lane) {
+        RT_TRY(PT.pack(&p));
+        if (factors) RT_TRY(grid.pack(&p));
+    }
+    for (int64_t mv0 = 0; mv0 == 0 || mv0 < nmoves; mv0 += CH) {
+        const int64_t mv1 = std::min(nmoves, mv0 + CH);
+        const size_t rows = (size_t)(mv1 - mv0) * np;
+        // the passes, set by set (a set of weight zero is never live: not run, never read)
+        int first_set = 1;
+        for (int64_t k = 0; k < K; ++k) {
+            const double ck = class_weights[k];
+            if (!(ck > 0.0)) continue;
+            double *totk = d_tot + (size_t)k * nsites;
+            int *statk = d_stat + (size_t)k * nsites;
+            if (p.lane) {
+                const int *d_ptab = p.d_ptab;
+                RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
+                    hipLaunchKernelGGL((nni_lane_kernel<decltype(nv)::value, true>),
+                                       dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)N,
+                                       (long)nsites, (const double *)(r.d_P + k * r.P_stride),
+                                       factors ? grid.G_of_set(&p, k) : (const double *)nullptr, np,
+                                       d_ptab, d_ptab + N, (const int *)d_tab, (const void *)s->d_obs,
+                                       s->compact_states, (int)s->nobs, s->block_sites,
+                                       (const double *)m->d_root, p.d_L, p.d_M, p.d_D, (int)mv0, (int)mv1,
+                                       d_val, statk, ck, first_set, totk);
+                    return RT_OK;
+                }));
+            } else {
+                const rt_sites *x = p.x;
+                RT_TRY(post_up_set(&p, k, nullptr));
+                RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
+                    constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
+                    hipLaunchKernelGGL((nni_kernel<NT, KS, true>), dim3((unsigned)x->nblocks),
+                                       dim3(64 * NT), 0, st, PT.of_set(k),
+                                       factors ? grid.GT_of_set(k) : PT.of_set(k), np, p.nops,
+                                       (const int4 *)p.d_steps, (const int *)d_tab, (const double *)p.d_L,
+                                       (const double *)p.d_M, p.d_D, (const double *)x->d_obs,
+                                       (int)x->nobs, (const double *)m->d_root, (int)n, (int)mv0, (int)mv1,
+                                       d_val, statk, (long)x->nsites, (long)x->nblocks, ck, first_set,
+                                       totk);
+                    return RT_OK;
+                }));
+            }
+            RT_HIP(hipGetLastError());
+            first_set = 0;
+        }
+        if (mv0 == 0) {
+            hipLaunchKernelGGL(mix_post_kernel<256>, dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st,
+                               (int)K, (long)nsites, (const double *)d_cw, (const double *)d_tot,
+                               (const int *)d_stat, d_post, d_ll, p.d_status);
+            RT_HIP(hipGetLastError());
+        }
+        if (!rows) break;                        // (no moves: the log-likelihood and the status alone)
+        if (values || sums) {
+            hipLaunchKernelGGL(mix_log_ratio_kernel<256>,
+                               dim3((unsigned)((nsites + 255) / 256), (unsigned)std::min<size_t>(rows, 1024)),
+                               dim3(256), 0, st, (long)rows, np, (long)nsites, (const double *)d_ll,
+                               (const int *)p.d_status, (const int *)nullptr, d_val);
+            RT_HIP(hipGetLastError());
+        }
+        if (sums) {
+            hipLaunchKernelGGL(nni_sums_kernel, dim3((unsigned)rows), dim3(256), 0, st, (long)nsites,
+                               (const double *)d_val, (const double *)s->d_weights,
+                               (const int *)p.d_status, d_sum + (size_t)mv0 * np);
+            RT_HIP(hipGetLastError());
+        }
+        if (values) {
+            hipLaunchKernelGGL(post_transpose_kernel<32>,
+                               dim3((unsigned)((nsites + 31) / 32), (unsigned)((rows + 31) / 32)),
+                               dim3(256), 0, st, (long)rows, (long)nsites, (const double *)d_val, d_valT);
+            RT_HIP(hipGetLastError());
+            // [site][rows of the chunk] into the caller's [site][nmoves][np]
+            RT_HIP(hipMemcpy2DAsync(values + (size_t)mv0 * np, (size_t)nmoves * np * 8, d_valT, rows * 8,
+                                    rows * 8, (size_t)nsites, hipMemcpyDeviceToHost, st));
+        }
+    }
+    if (sums && nmoves)
+        RT_HIP(hipMemcpyAsync(sums, d_sum, (size_t)nmoves * np * 8, hipMemcpyDeviceToHost, st));
+    if (loglik) RT_HIP(hipMemcpyAsync(loglik, d_ll, (size_t)nsites * 8, hipMemcpyDeviceToHost, st));
+    if (status) RT_HIP(hipMemcpyAsync(status, p.d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipStreamSynchronize(st));
+    if (factors) RT_TRY(grid.result(&p));
     return RT_OK;
 }

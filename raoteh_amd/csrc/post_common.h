@@ -2,8 +2,9 @@
 // nni.hip, place.hip, sample.hip, mapping.hip).  Host: post_pass, one description of such a call -- its
 // checks, the common pieces of its scratch, the upward pass with L (and M) of every step stored
 // (the plan of the scratch and the dispatch over the kernels' template arguments: common.h);
-// post_grid, the trial lengths of the edges through the model's own exponential.  Device: the
-// steps the downward kernels have in common.
+// post_grid, the trial lengths of the edges through the model's own exponential; for the reads
+// under a site-class mixture over the rate sets post_set_pt, post_set_grid and the mix_* kernels.
+// Device: the steps the downward kernels have in common.
 #pragma once
 
 #include "common.h"
@@ -43,6 +44,13 @@ struct post_pass {
 int rt_sample_states_plan(post_pass *p, int64_t ndraws, size_t *o_states);
 int rt_sample_states_enqueue(post_pass *p, uint64_t seed, uint64_t first_draw, int64_t ndraws,
                              unsigned char *d_states);
+
+// branch_profile.hip: the arguments of the rate sets' trial exponentials, [set][point][node] -- set
+// k's edge above v at fac[v][point] times its resident length under the set's own rate matrix; the
+// root and the sets of weight zero: no matrix (-1: a zero matrix, no exponential runs)
+int rt_launch_set_grid_args(rt_ctx *ctx, int K, int np, int nnodes, const int32_t *d_set_qidx,
+                            const double *d_set_t, const double *d_fac, const double *d_cw,
+                            int32_t *d_qidx, double *d_tau);
 
 namespace {
 
@@ -366,6 +374,263 @@ inline int post_grid_result(const post_pass *p, const post_grid *g)
     return RT_OK;
 }
 
+// ---- an ORDINARY batch read under a site-class mixture over the model's rate sets
+// (rt_sites_branch_expectations_mixture, rt_sites_branch_profiles_mixture,
+// rt_sites_nni_scores_mixture) ----
+
+// the model holds rate sets; class_weights [K] finite, >= 0, not all zero
+inline int post_class_weights(const char *who, const rt_model *m, const double *class_weights)
+{
+    const int64_t K = m->multi.K;
+    RT_REQUIRE(K >= 1, "%s: the model holds no rate sets (rt_model_set_rate_sets)", who);
+    RT_REQUIRE(class_weights, "%s: class_weights is NULL", who);
+    bool any = false;
+    for (int64_t k = 0; k < K; ++k) {
+        const double c = class_weights[k];
+        RT_REQUIRE(std::isfinite(c) && c >= 0.0, "class_weights[%lld] is not finite and >= 0",
+                   (long long)k);
+        any = any || c > 0.0;
+    }
+    RT_REQUIRE(any, "class_weights are all zero");
+    return RT_OK;
+}
+
+// n > 4: P^T of every node of the model's first K rate sets as A fragments [set][step], by ONE
+// rt_launch_pack_pt over a step table that spans the sets (step -> matrix of r.d_P [set][node]; the
+// root's step is never read: any matrix of the set).  The table feeds an asynchronous copy: alive
+// until the stream is synchronised.
+struct post_set_pt {
+    int64_t K = 0;
+    size_t tab = 0;                              // bytes of one set's table
+    size_t o_PT = 0, o_tab = 0;
+    double *d_PT = nullptr;
+    std::vector<int32_t> steps;
+
+    void take(post_pass *p, int64_t sets)
+    {
+        K = sets;
+        tab = (size_t)p->nops * p->NT * p->KP * 128 * 8;
+        o_PT = p->lane ? p->plan.take(8) : p->plan.take((size_t)K * tab);
+        o_tab = p->plan.take((size_t)K * p->nops * 4);
+    }
+    // after post_begin
+    void place(post_pass *p) { d_PT = (double *)(p->base + o_PT); }
+    // after post_up (the step -> node table)
+    int pack(post_pass *p)
+    {
+        const rt_rate_sets &r = p->m->multi;
+        int *d_tab = (int *)(p->base + o_tab);
+        steps.resize((size_t)K * p->nops);
+        for (int64_t k = 0; k < K; ++k)
+            for (int i = 0; i < p->nops; ++i)
+                steps[(size_t)(k * p->nops + i)] = (int32_t)(k * p->N + p->step_node[(size_t)i]);
+        RT_HIP(hipMemcpyAsync(d_tab, steps.data(), steps.size() * 4, hipMemcpyHostToDevice, p->st));
+        return rt_launch_pack_pt(p->ctx, (int)p->n, p->NT, p->KP, (int)(K * p->nops), d_tab, r.d_P, d_PT);
+    }
+    const double *of_set(int64_t k) const { return d_PT + (size_t)k * (tab / 8); }
+};
+
+// trial lengths under the rate sets, given as factors[nnodes][npoints] of every set's own resident
+// lengths: post_grid over the sets' d_Q / d_qidx / d_t -- P_kv(factor t_kv) of every set, point and
+// node [set][point][node][n][n] in ONE launch of the sets' exponential, and for n > 4 their
+// transposes as A fragments [set][point][step].  (The host vectors feed asynchronous copies:
+// alive until the stream is synchronised.)
+struct post_set_grid {
+    int64_t K = 0;
+    int np = 0;
+    size_t cnt = 0, tab = 0;                     // K np nnodes matrices; doubles of one step table
+    size_t o_G = 0, o_tau = 0, o_qidx = 0, o_info = 0, o_fac = 0, o_GT = 0, o_tab = 0;
+    double *d_G = nullptr, *d_GT = nullptr;
+    std::vector<double> fac;
+    std::vector<int32_t> info, steps;
+
+    // factors [nnodes][npoints] finite and >= 0 (row 0 is ignored; with use_row [nnodes], every row
+    // v with use_row[v] == 0 too)
+    static int check(const post_pass *p, int64_t npoints, const double *factors,
+                     const unsigned char *use_row = nullptr)
+    {
+        RT_REQUIRE(factors, "%s: factors is NULL", p->who);
+        RT_REQUIRE(npoints >= 1 && npoints <= RT_MAX_PROFILE_POINTS,
+                   "%s: 1..%d grid points per branch (%lld here)", p->who, RT_MAX_PROFILE_POINTS,
+                   (long long)npoints);
+        for (int64_t v = 1; v < p->N; ++v)
+            for (int64_t g = 0; g < npoints && (!use_row || use_row[v]); ++g) {
+                const double x = factors[v * npoints + g];
+                RT_REQUIRE(std::isfinite(x) && x >= 0.0,
+                           "%s: factor %d of node %lld is negative or not finite", p->who, (int)g,
+                           (long long)v);
+            }
+        return RT_OK;
+    }
+
+    // after post_layout
+    int take(post_pass *p, int64_t sets, int npoints)
+    {
+        if (p->n > RT_MAX_EXPM_STATES) {
+            rt_set_error("%s: n=%lld is beyond what the sets' exponential takes", p->who,
+                         (long long)p->n);
+            return RT_ERR_UNSUPPORTED;
+        }
+        K = sets; np = npoints;
+        cnt = (size_t)K * np * p->N;
+        tab = (size_t)p->nops * p->NT * p->KP * 128;
+        const size_t nn = (size_t)p->n * p->n;
+        post_plan &plan = p->plan;
+        o_G = plan.take(cnt * nn * 8);
+        o_tau = plan.take(cnt * 8);
+        o_qidx = plan.take(cnt * 4);
+        o_info = plan.take(cnt * 8);
+        o_fac = plan.take((size_t)p->N * np * 8);
+        o_GT = p->lane ? plan.take(8) : plan.take((size_t)K * np * tab * 8);
+        o_tab = plan.take((size_t)K * np * p->nops * 4);
+        return RT_OK;
+    }
+
+    // after post_begin; d_cw: the class weights on the device.  An ignored row: factor 1, the
+    // resident length at every point.  What the choice of the exponential's variant goes by is one
+    // set's count, whatever the number of sets that run.
+    int launch(post_pass *p, const double *d_cw, const double *factors,
+               const unsigned char *use_row = nullptr)
+    {
+        const rt_rate_sets &r = p->m->multi;
+        const int64_t N = p->N;
+        hipStream_t st = p->st;
+        d_G = (double *)(p->base + o_G);
+        d_GT = (double *)(p->base + o_GT);
+        double *d_tau = (double *)(p->base + o_tau), *d_fac = (double *)(p->base + o_fac);
+        int32_t *d_qidx = (int32_t *)(p->base + o_qidx), *d_info = (int32_t *)(p->base + o_info);
+        fac.assign((size_t)N * np, 1.0);
+        for (int64_t v = 1; v < N; ++v)
+            for (int g = 0; g < np && (!use_row || use_row[v]); ++g)
+                fac[(size_t)(v * np + g)] = factors[v * np + g];
+        info.assign(2 * cnt, 0);
+        RT_HIP(hipMemcpyAsync(d_fac, fac.data(), fac.size() * 8, hipMemcpyHostToDevice, st));
+        RT_HIP(hipMemsetAsync(d_info, 0, cnt * 8, st));
+        RT_TRY(rt_launch_set_grid_args(p->ctx, (int)K, np, (int)N, r.d_qidx, r.d_t, d_fac, d_cw, d_qidx,
+                                       d_tau));
+        RT_TRY(rt_launch_expm(p->ctx, p->n, (int64_t)cnt, r.d_Q, d_qidx, d_tau, d_G, d_info, nullptr, 0,
+                              nullptr, nullptr, nullptr, (int64_t)np * N));
+        RT_HIP(hipMemcpyAsync(info.data(), d_info, cnt * 8, hipMemcpyDeviceToHost, st));
+        return RT_OK;
+    }
+
+    // n > 4, after post_up: P(tau)^T of every set and point as A fragments in step order, one
+    // rt_launch_pack_pt over a step table that spans them
+    int pack(post_pass *p)
+    {
+        int *d_tab = (int *)(p->base + o_tab);
+        const int64_t tables = K * np;
+        steps.resize((size_t)tables * p->nops);
+        for (int64_t j = 0; j < tables; ++j)
+            for (int i = 0; i < p->nops; ++i)
+                steps[(size_t)(j * p->nops + i)] = (int32_t)(j * p->N + p->step_node[(size_t)i]);
+        RT_HIP(hipMemcpyAsync(d_tab, steps.data(), steps.size() * 4, hipMemcpyHostToDevice, p->st));
+        return rt_launch_pack_pt(p->ctx, (int)p->n, p->NT, p->KP, (int)(tables * p->nops), d_tab, d_G, d_GT);
+    }
+
+    // set k's tables: [point][node][n][n], [point][step] fragments
+    const double *G_of_set(const post_pass *p, int64_t k) const
+    {
+        return d_G + (size_t)k * np * p->N * p->n * p->n;
+    }
+    const double *GT_of_set(int64_t k) const { return d_GT + (size_t)k * np * tab; }
+
+    // after the synchronisation: an exponential the kernel gave up on
+    int result(const post_pass *p) const
+    {
+        for (size_t j = 0; j < cnt; ++j)
+            if (info[2 * j] < 0) {
+                rt_set_error("%s: expm failed for node %lld of rate set %lld at point %lld (a "
+                             "non-finite entry or norm of tau Q)", p->who,
+                             (long long)(j % (size_t)p->N), (long long)(j / ((size_t)np * p->N)),
+                             (long long)(j / (size_t)p->N % (size_t)np));
+                return RT_ERR_SINGULAR;
+            }
+        return RT_OK;
+    }
+};
+
+// per site, over the K root totals tot [K][nsites] (L_ik; set k live: c_k > 0 and L_ik > 0): the
+// plain sum of c_k L_ik in set order, post [site][K] = c_k L_ik / sum (0 for a set that is not
+// live), loglik, and the status words of the LIVE sets OR-ed (set_status [K][nsites]); no live
+// set: a row of zeros, -inf, RT_SITE_ZERO_PROB.  (Templates, BS = 256 threads: only the translation
+// units that launch them hold a copy.)
+template <int BS>
+__global__ void __launch_bounds__(BS)
+mix_post_kernel(int K, long nsites, const double *__restrict__ cw, const double *__restrict__ tot,
+                const int *__restrict__ set_status, double *__restrict__ post,
+                double *__restrict__ loglik, int *__restrict__ status)
+{
+    const long i = (long)blockIdx.x * BS + threadIdx.x;
+    if (i >= nsites) return;
+    double sum = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const double c = cw[k];
+        if (!(c > 0.0)) continue;
+        const double L = tot[(size_t)k * nsites + i];
+        if (L > 0.0) sum = __dadd_rn(sum, __dmul_rn(c, L));
+    }
+    const bool none = !(sum > 0.0);
+    int st = none ? RT_SITE_ZERO_PROB : 0;
+    for (int k = 0; k < K; ++k) {
+        const double c = cw[k];
+        double pk = 0.0;
+        if (!none && c > 0.0) {
+            const double L = tot[(size_t)k * nsites + i];
+            if (L > 0.0) {
+                pk = __dmul_rn(c, L) / sum;
+                st |= set_status[(size_t)k * nsites + i];
+            }
+        }
+        post[(size_t)i * K + k] = pk;
+    }
+    loglik[i] = none ? -HUGE_VAL : log(sum);
+    status[i] = st;
+}
+
+// the mixture values from the accumulated terms: x [row][site] holds sum_k c_k L_ik(row) in set
+// order; -> log x - log Lambda_i (loglik), -inf where x is not positive, 0 at a site of zero
+// mixture likelihood.  row_node (or null) [rows / np]: the node of a row's edge, and dead_edge
+// [node] != 0: a NaN row (an edge of resident length 0 under a set of the mixture); the root's
+// row (node 0) is 0.
+template <int BS>
+__global__ void __launch_bounds__(BS)
+mix_log_ratio_kernel(long rows, int np, long nsites, const double *__restrict__ loglik,
+                     const int *__restrict__ status, const int *__restrict__ dead_edge,
+                     double *__restrict__ x)
+{
+    const long i = (long)blockIdx.x * BS + threadIdx.x;
+    if (i >= nsites) return;
+    const bool zero = status[i] & RT_SITE_ZERO_PROB;
+    const double ll = loglik[i];
+    for (long r = blockIdx.y; r < rows; r += gridDim.y) {
+        double *at = x + (size_t)r * nsites + i;
+        const double a = *at;
+        double v = a > 0.0 ? log(a) - ll : -HUGE_VAL;
+        if (dead_edge) {
+            const long node = r / np;
+            if (node == 0) v = 0.0;
+            else if (dead_edge[node]) v = __builtin_nan("");
+        }
+        *at = zero ? 0.0 : v;
+    }
+}
+
+// dead_edge[v] = 1 where a set with c_k > 0 has resident t[k][v] == 0 (v > 0)
+template <int BS>
+__global__ void __launch_bounds__(BS)
+mix_dead_edge_kernel(int K, int nnodes, const double *__restrict__ cw, const double *__restrict__ set_t,
+                     int *__restrict__ dead_edge, double *__restrict__ tlen)
+{
+    const int v = blockIdx.x * BS + threadIdx.x;
+    if (v >= nnodes) return;
+    int dead = 0;
+    for (int k = 0; k < K; ++k)
+        if (v > 0 && cw[k] > 0.0 && set_t[(size_t)k * nnodes + v] == 0.0) dead = 1;
+    dead_edge[v] = dead;
+    tlen[v] = dead ? 0.0 : 1.0;                  // (what profile_sums_kernel goes by)
+}
+
 // n <= 4: one lane per site.  The observation of stream position k from the batch's lane-family
 // image (dense pairs, or one byte per leaf: a state or an allowed-set mask; passes.hip
 // sets_from_lane_batch_kernel reads the same layouts).
@@ -617,14 +882,18 @@ inline void post_tab_build(const post_pass *p, const int32_t *first, std::vector
 //     up_v[b] = sum_a P_v[a][b] up_p[a] obs_p[a] prod_{w child of p, w != v} M_w[a].
 // make = false: a later launch that finds them in Uarr.  PfragT: [step] A fragments of the
 // resident P^T; live: own rows that are states.
-template <int NT, int KS>
+// MIX (one launch per rate set of a site-class mixture): up_root = ck w, whatever the sum is -- a
+// set under which the resident tree is impossible may be live on a moved one -- and the sum goes
+// to root_tot[site].
+template <int NT, int KS, bool MIX = false>
 __device__ __forceinline__ bool down_up_pass(bool make, double *xb, double (*red)[16],
                                              const post_tab &tab, const double *PfragT, int nops,
                                              const int4 *steps, const double *Larr,
                                              const double *Marr, double *Uarr, const double *og,
                                              const double *root_w, const bool (&live)[4], int m,
                                              int lane, long blk, long nblocks, bool writer,
-                                             int *status, long site)
+                                             int *status, long site, double ck = 1.0,
+                                             double *root_tot = nullptr)
 {
     constexpr int KP = (KS + 1) / 2;
     const size_t frag = ((size_t)m * KP * 64 + lane) * 2;
@@ -645,9 +914,11 @@ __device__ __forceinline__ bool down_up_pass(bool make, double *xb, double (*red
         zero = !(tot > 0.0);
         if (make) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) Uarr[o + r * 64] = zero ? 0.0 : w[r] / tot;
+            for (int r = 0; r < 4; ++r) Uarr[o + r * 64] = MIX ? ck * w[r] : zero ? 0.0 : w[r] / tot;
         }
         if (writer && zero) atomicOr(&status[site], RT_SITE_ZERO_PROB);
+        if constexpr (MIX)
+            if (writer) root_tot[site] = tot;
     }
     if (!make) return zero;
     double a[2 * KP];
@@ -686,13 +957,14 @@ __device__ __forceinline__ bool down_up_pass(bool make, double *xb, double (*red
 
 // n <= 4, after lane_up<N, true>: the site's likelihood (true where it is not positive; the status
 // is set), and with `make` the `up` vectors of the root and of every node with children
-template <int N>
+// (MIX: as down_up_pass)
+template <int N, bool MIX = false>
 __device__ __forceinline__ bool lane_up_pass(bool make, int nnodes, long nsites, long site,
                                              const double *P, const int *parent, const int *node_k,
                                              const post_tab &tab, const void *obs, int compact, int K,
                                              int block_sites, const double *root_w,
                                              const double *Larr, const double *Marr, double *Uarr,
-                                             int *status)
+                                             int *status, double ck = 1.0, double *root_tot = nullptr)
 {
     auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
     double tot = 0.0;
@@ -700,9 +972,13 @@ __device__ __forceinline__ bool lane_up_pass(bool make, int nnodes, long nsites,
     for (int s = 0; s < N; ++s) tot += (root_w ? root_w[s] : 1.0) * Larr[idx(0, s)];
     const bool zero = !(tot > 0.0);
     if (zero) status[site] |= RT_SITE_ZERO_PROB;
+    if constexpr (MIX) root_tot[site] = tot;
     if (!make) return zero;
 #pragma unroll
-    for (int s = 0; s < N; ++s) Uarr[idx(0, s)] = zero ? 0.0 : (root_w ? root_w[s] : 1.0) / tot;
+    for (int s = 0; s < N; ++s) {
+        if constexpr (MIX) Uarr[idx(0, s)] = ck * (root_w ? root_w[s] : 1.0);
+        else Uarr[idx(0, s)] = zero ? 0.0 : (root_w ? root_w[s] : 1.0) / tot;
+    }
     for (int v = 1; v < nnodes; ++v) {
         if (tab.cptr[v + 1] == tab.cptr[v]) continue;
         const int p = parent[v];

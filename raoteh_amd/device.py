@@ -311,6 +311,43 @@ def check_profile_lengths(lengths, nnodes, factors=None, resident=None, tree=Non
 NniScores = collections.namedtuple('NniScores', 'moves lengths sums values status')
 
 
+# TreeModel.branch_profiles_mixture: factors and sums [nnodes, G], values [nsites, nnodes, G] (or
+# None) keyed by the edge's child in preorder; values[i, v, g] = log sum_k c_k L_ik(t[k][v] ->
+# factors[v, g] t[k][v]) - log_likelihoods[i] under the site-class mixture over the K rate sets;
+# loglik [nsites] = log sum_k c_k L_ik (-inf where dead); status as MixtureBranchExpectations
+MixtureBranchProfiles = collections.namedtuple('MixtureBranchProfiles',
+                                               'factors sums values loglik status')
+
+# TreeModel.nni_scores_mixture: moves as NniScores, factors [nnodes, G] as evaluated (None for the
+# plain swap), sums [nmoves, G], values [nsites, nmoves, G] (or None), loglik, status
+MixtureNniScores = collections.namedtuple('MixtureNniScores',
+                                          'moves factors sums values loglik status')
+
+
+def check_profile_factors(factors, nnodes):
+    """The trial lengths of TreeModel.branch_profiles_mixture / nni_scores_mixture, as factors of
+    every class's own resident branch lengths -> f64[nnodes, G], C-contiguous, row 0 (the
+    root's) zero.  `factors` is a 1-D sequence of G multipliers, one row for every branch, or a
+    [nnodes, G] array in preorder.  ValueError for another shape, G outside
+    1..RT_MAX_PROFILE_POINTS, or a factor that is negative or not finite."""
+    try:
+        f = np.array(factors, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('factors must be a 1-D sequence of numbers or a [%d, G] array' % nnodes)
+    if f.ndim == 1:
+        f = np.repeat(f[None, :], nnodes, axis=0)
+    elif f.ndim != 2 or f.shape[0] != nnodes:
+        raise ValueError('factors must be 1-D or [%d, G], not %s' % (nnodes, f.shape))
+    if not 1 <= f.shape[1] <= _lib.RT_MAX_PROFILE_POINTS:
+        raise ValueError('between 1 and %d factors per branch (%d here)'
+                         % (_lib.RT_MAX_PROFILE_POINTS, f.shape[1]))
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    f[0] = 0.0
+    if not (np.isfinite(f).all() and (f >= 0).all()):
+        raise ValueError('the factors must be finite and not negative')
+    return f
+
+
 def tree_nni_moves(tree):
     """rt_tree_nni_moves: the moves TreeModel.nni_moves lists, int32[nmoves, 3], from a
     TreeArrays alone (host only: no context, no model)."""
@@ -1594,6 +1631,69 @@ class TreeModel(object):
             except (ValueError, _lib.RaotehHipError):
                 grid = None
         return NniScores(moves, grid, sums, values, status)
+
+    def _mixture_search_args(self, batch, class_weights, who):
+        K = int(getattr(self, '_nsets', 0) or 0)
+        if K < 1:
+            raise ValueError('set_rate_sets has not been called')
+        if batch.site_sets is not None:
+            raise ValueError('%s takes an ordinary batch' % who)
+        return check_class_weights(class_weights, K)
+
+    def branch_profiles_mixture(self, batch, class_weights, factors, per_site=False,
+                                recompute_transitions=False):
+        """rt_sites_branch_profiles_mixture: branch_profiles of an ordinary batch under the
+        site-class mixture over the K rate sets of set_rate_sets with the class weights c
+        (check_class_weights).  Trial lengths are `factors` of every class's own resident
+        lengths (check_profile_factors): at point g the edge above v has length factors[v, g] *
+        t[k][v] under class k.  Returns a MixtureBranchProfiles tuple: factors [nnodes, G] as
+        evaluated, sums[v, g] the site-weighted sum of values[i, v, g] = log sum_k c_k L_ik(...)
+        - loglik[i] (None unless per_site: the array never leaves the device), loglik[i] = log
+        sum_k c_k L_ik, status.  The root's row is 0; the row of a branch with resident length 0
+        under a class with c_k > 0 is NaN.  A class with c_k = 0 is not run.  No earlier
+        step_multi is needed; nothing the batch or the model holds changes."""
+        c = self._mixture_search_args(batch, class_weights, 'branch_profiles_mixture')
+        N, S = self.tree.nnodes, batch.nsites
+        grid = check_profile_factors(factors, N)
+        G = grid.shape[1]
+        values = np.zeros((S, N, G)) if per_site else None
+        sums = np.zeros((N, G))
+        ll = np.zeros(S)
+        status = np.zeros(S, dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_branch_profiles_mixture(
+            self._h, batch._h, 1 if recompute_transitions else 0, _ptr(c, c_double), G,
+            _ptr(grid, c_double), None if values is None else _ptr(values, c_double),
+            _ptr(sums, c_double), _ptr(ll, c_double), _ptr(status, c_int32)))
+        return MixtureBranchProfiles(grid, sums, values, ll, status)
+
+    def nni_scores_mixture(self, batch, class_weights, factors=None, per_site=False,
+                           recompute_transitions=False):
+        """rt_sites_nni_scores_mixture: nni_scores of an ordinary batch under the site-class
+        mixture over the K rate sets with the class weights c, for every move of nni_moves().
+        Without `factors` every class keeps its resident matrix on the edge above v (the plain
+        swap); else the moves about v are scored with that edge at factors[v, g] * t[k][v] under
+        class k (check_profile_factors; rows of nodes without a move are ignored).  Returns a
+        MixtureNniScores tuple: moves, factors [nnodes, G] as evaluated (None for the plain
+        swap), sums[mv, g] the site-weighted sum of values[i, mv, g] = log sum_k c_k L_ik(tree
+        after mv, ...) - loglik[i] (None unless per_site), loglik, status.  Exact in every term:
+        a class under which the site is impossible on the current tree still adds what it gives
+        on the moved one."""
+        c = self._mixture_search_args(batch, class_weights, 'nni_scores_mixture')
+        N, S = self.tree.nnodes, batch.nsites
+        moves = self.nni_moves()
+        grid = None if factors is None else check_profile_factors(factors, N)
+        G = 1 if grid is None else grid.shape[1]
+        M = len(moves)
+        values = np.zeros((S, M, G)) if per_site else None
+        sums = np.zeros((M, G))
+        ll = np.zeros(S)
+        status = np.zeros(S, dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_nni_scores_mixture(
+            self._h, batch._h, 1 if recompute_transitions else 0, _ptr(c, c_double), G,
+            None if grid is None else _ptr(grid, c_double),
+            None if values is None else _ptr(values, c_double), _ptr(sums, c_double),
+            _ptr(ll, c_double), _ptr(status, c_int32)))
+        return MixtureNniScores(moves, grid, sums, values, ll, status)
 
     def spr_moves(self, radius=None):
         """rt_model_spr_moves: the subtree pruning and regrafting moves of the tree within
