@@ -596,9 +596,9 @@ extern "C" int rt_sites_branch_expectations(rt_model *m, rt_sites *s, int recomp
     int *d_ident = (int *)(base + o_ident), *d_status = p.d_status;
     // (host buffers of the asynchronous copies: alive until the synchronisation below)
     std::vector<double> ones(ne, 1.0);
-    std::vector<int32_t> ident(ne), internal((size_t)N, 0);
+    std::vector<int32_t> ident(ne);
+    const std::vector<int32_t> internal = post_internal_nodes(&p);
     for (size_t e = 0; e < ne; ++e) ident[e] = (int32_t)e;
-    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
     RT_HIP(hipMemcpyAsync(d_E, coefs, (size_t)nk * nn * 8, hipMemcpyHostToDevice, st));
     RT_HIP(hipMemcpyAsync(d_ones, ones.data(), ne * 8, hipMemcpyHostToDevice, st));
     RT_HIP(hipMemcpyAsync(d_ident, ident.data(), ne * 4, hipMemcpyHostToDevice, st));
@@ -727,8 +727,7 @@ extern "C" int rt_sites_branch_expectations_partitioned(rt_model *m, rt_sites *s
     double *d_part = (double *)(base + o_part);
     int *d_status = p.d_status, *d_statc = (int *)(base + o_statc);
     // (host buffer of an asynchronous copy: alive until the synchronisation below)
-    std::vector<int32_t> internal((size_t)N, 0);
-    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
+    const std::vector<int32_t> internal = post_internal_nodes(&p);
     // 1. the derivative tables
     RT_TRY(T.derivatives(&p, coefs));
     // 2. the passes
@@ -860,8 +859,7 @@ extern "C" int rt_sites_branch_expectations_mixture(rt_model *m, rt_sites *s, in
     double *d_cw = (double *)(base + o_cw);
     int *d_stat = (int *)(base + o_stat);
     // (host buffer of an asynchronous copy: alive until the synchronisation below)
-    std::vector<int32_t> internal((size_t)N, 0);
-    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
+    const std::vector<int32_t> internal = post_internal_nodes(&p);
     RT_HIP(hipMemcpyAsync(d_cw, class_weights, (size_t)K * 8, hipMemcpyHostToDevice, st));
     RT_HIP(hipMemsetAsync(d_stat, 0, (size_t)K * nsites * 4, st));
     // 1. the derivative tables

@@ -20,13 +20,21 @@
 //      is staged once, per point one n x n by n x 16 matrix-pipe product reduced over the states
 //      in a fixed order and stored (coalesced over the sites); the logs by all lanes at the end.
 //      n <= 4: bp_lane_kernel, one lane per site;
-//   3. profile_sums_kernel: the site-weighted sums per (node, point) in a fixed order; then, if
-//      the per-site array is asked for, its transpose to [site][node][point].
+//   3. post_result (post_common.h): the site-weighted sums per (node, point) in a fixed order;
+//      then, if the per-site array is asked for, its transpose to [site][node][point].
 //
 // Nothing of the batch or the model is written; two calls give the same bits.
 //
-// rt_sites_branch_profiles_mixture (at the end): the same read under a site-class mixture over the
-// model's rate sets -- the kernels' MIX forms once per set into one accumulator.
+// rt_sites_branch_profiles_mixture: the same read of an ORDINARY batch under a site-class mixture
+// over the model's K rate sets, trial lengths as factors of every set's own resident lengths.  One
+// host body (bp_read) serves both; under the mixture
+//   1. is P_kv(factor t_kv) of every set, point and edge in ONE launch of the sets' exponential
+//      (post_set_grid), their transposes and the sets' P^T as A fragments (post_set_pt);
+//   2. runs per set k with c_k > 0, on the one stream over one L, M, D scratch: the upward pass
+//      through a view of set k's tables (post_up_set), then the MIX instance of the kernel against
+//      set k's fragments -- the term c_k L_ik(tau) into ONE accumulator [node][point][site], the
+//      sets added in set order, L_ik and a status word per set; then mix_post_kernel (log
+//      Lambda_i, the status of the live sets) and mix_log_ratio_kernel (the accumulator -> values).
 #include "common.h"
 #include "post_common.h"
 
@@ -228,32 +236,6 @@ bp_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const doub
     if (bad) status[site] |= 2;
 }
 
-// one workgroup per (node, point), the order of edge_sums_kernel: thread j adds sites j, j + 256,
-// ... in order, then the 256 partial sums by halves (fixed rounding).  Sites of zero likelihood
-// and of weight 0 are skipped; the row of an edge of resident length 0 is NaN.
-__global__ void __launch_bounds__(256)
-profile_sums_kernel(int np, long nsites, const double *__restrict__ values,
-                    const double *__restrict__ weights, const int *__restrict__ status,
-                    const double *__restrict__ tlen, double *__restrict__ sums)
-{
-    __shared__ double part[256];
-    const int row = blockIdx.x, v = row / np, tid = threadIdx.x;
-    const double *x = values + (size_t)row * nsites;
-    double acc = 0.0;
-    for (long i = tid; i < nsites; i += 256)
-    {
-        const double w = weights ? weights[i] : 1.0;       // (w = 0: not -inf * 0 = NaN)
-        if (w != 0.0 && !(status[i] & RT_SITE_ZERO_PROB)) acc += w * x[i];
-    }
-    part[tid] = acc;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (tid < h) part[tid] += part[tid + h];
-        __syncthreads();
-    }
-    if (tid == 0) sums[row] = (v > 0 && tlen[v] == 0.0) ? __builtin_nan("") : part[0];
-}
-
 }  // namespace
 
 extern "C" int rt_model_get_branch_lengths(rt_model *m, double *t)
@@ -263,83 +245,6 @@ extern "C" int rt_model_get_branch_lengths(rt_model *m, double *t)
                "rt_model_get_branch_lengths: no rates have been set (rt_model_set_rates or "
                "rt_model_set_rates_spectral)");
     std::copy(m->h_t.begin(), m->h_t.end(), t);
-    return RT_OK;
-}
-
-extern "C" int rt_sites_branch_profiles(rt_model *m, rt_sites *s, int recompute_transitions,
-                                        int64_t npoints, const double *lengths, double *values,
-                                        double *sums, int32_t *status)
-{
-    post_pass p;                                 // (alive until the synchronisation below)
-    RT_TRY(post_open(&p, "rt_sites_branch_profiles", m, s));
-    RT_TRY(post_grid_check(&p, recompute_transitions, npoints, lengths));
-    const int64_t n = p.n, N = p.N, nsites = p.nsites;
-    const int np = (int)npoints;
-    RT_TRY(post_layout(&p, true));
-    const size_t rows = (size_t)N * np;
-    // scratch: L, M, D of every node and site (post_layout), the result, the grid matrices, their
-    // fragments and the tiled arguments of the exponential (post_grid)
-    post_plan &plan = p.plan;
-    post_grid grid;                              // (alive until the synchronisation below)
-    const size_t o_val = plan.take(rows * nsites * 8);
-    const size_t o_valT = plan.take(values ? rows * nsites * 8 : 8);
-    const size_t o_sum = plan.take(rows * 8);
-    RT_TRY(post_grid_take(&p, &grid, np));
-    RT_TRY(post_begin(&p, recompute_transitions));
-    hipStream_t st = p.st;
-    unsigned char *base = p.base;
-    double *d_val = (double *)(base + o_val), *d_valT = (double *)(base + o_valT);
-    double *d_sum = (double *)(base + o_sum);
-    int *d_status = p.d_status;
-    std::vector<int32_t> internal((size_t)N, 0);
-    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
-    // 1. the grid matrices: one launch of the route the model's own transitions take
-    RT_TRY(post_grid_launch(&p, &grid, lengths));
-    RT_TRY(post_up(&p, internal.data(), true));
-    if (p.lane) {
-        const int *d_tab = p.d_ptab;
-        RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
-            hipLaunchKernelGGL((bp_lane_kernel<decltype(nv)::value>), dim3((unsigned)((nsites + 255) / 256)),
-                               dim3(256), 0, st, (int)N, (long)nsites, (const double *)m->d_P,
-                               (const double *)grid.d_G, np, d_tab, d_tab + N, (const void *)s->d_obs,
-                               s->compact_states, (int)s->nobs, s->block_sites,
-                               (const double *)m->d_root, (const double *)m->d_t, p.d_L, p.d_M, p.d_D,
-                               d_val, d_status, 1.0, 1, (double *)nullptr);
-            return RT_OK;
-        }));
-    } else {
-        const rt_sites *x = p.x;
-        RT_TRY(post_grid_pack(&p, &grid));
-        RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
-            constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
-            hipLaunchKernelGGL((bp_down_kernel<NT, KS>), dim3((unsigned)x->nblocks), dim3(64 * NT), 0, st,
-                               (const double *)p.d_PT, (const double *)grid.d_GT, np, p.nops,
-                               (const int4 *)p.d_steps, (const double *)p.d_L, (const double *)p.d_M,
-                               p.d_D, (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
-                               (const double *)m->d_t, (int)n, d_val, d_status, (long)x->nsites,
-                               (long)x->nblocks, 1.0, 1, (double *)nullptr);
-            return RT_OK;
-        }));
-    }
-    RT_HIP(hipGetLastError());
-    // 3. the weighted site sums; only what was asked for crosses PCIe
-    if (sums) {
-        hipLaunchKernelGGL(profile_sums_kernel, dim3((unsigned)rows), dim3(256), 0, st, np, (long)nsites,
-                           (const double *)d_val, (const double *)s->d_weights, (const int *)d_status,
-                           (const double *)m->d_t, d_sum);
-        RT_HIP(hipGetLastError());
-        RT_HIP(hipMemcpyAsync(sums, d_sum, rows * 8, hipMemcpyDeviceToHost, st));
-    }
-    if (values) {
-        hipLaunchKernelGGL(post_transpose_kernel<32>,
-                           dim3((unsigned)((nsites + 31) / 32), (unsigned)((rows + 31) / 32)), dim3(256),
-                           0, st, (long)rows, (long)nsites, (const double *)d_val, d_valT);
-        RT_HIP(hipGetLastError());
-        RT_HIP(hipMemcpyAsync(values, d_valT, rows * nsites * 8, hipMemcpyDeviceToHost, st));
-    }
-    if (status) RT_HIP(hipMemcpyAsync(status, d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
-    RT_HIP(hipStreamSynchronize(st));
-    RT_TRY(post_grid_result(&p, &grid));
     return RT_OK;
 }
 
@@ -371,134 +276,131 @@ int rt_launch_set_grid_args(rt_ctx *ctx, int K, int np, int nnodes, const int32_
     return RT_OK;
 }
 
-// The profiles of an ORDINARY batch under a site-class mixture over the model's K rate sets, trial
-// lengths as factors of every set's own resident lengths:
-//   1. P_kv(factor t_kv) of every set, point and edge in ONE launch of the sets' exponential
-//      (post_set_grid), their transposes and the sets' P^T as A fragments (post_set_pt);
-//   2. per set k with c_k > 0, on the one stream over one L, M, D scratch: the upward pass through
-//      a view of set k's tables (post_up_set), then the MIX instance of bp_down_kernel (n <= 4:
-//      bp_lane_kernel) against set k's fragments -- the term c_k L_ik(tau) into ONE accumulator
-//      [node][point][site], the sets added in set order, L_ik and a status word per set;
-//   3. mix_post_kernel (log Lambda_i, the status of the live sets), mix_log_ratio_kernel (the
-//      accumulator -> values), then profile_sums_kernel and the transpose as the single-set call.
-extern "C" int rt_sites_branch_profiles_mixture(rt_model *m, rt_sites *s, int recompute_transitions,
-                                                const double *class_weights, int64_t npoints,
-                                                const double *factors, double *values, double *sums,
-                                                double *loglik, int32_t *status)
+namespace {
+
+// Both reads.  MIX = false: the pass runs once under the model's own matrices, `trial` are lengths
+// (post_grid), the plain kernel instance divides by L_i at the root.  MIX = true: once per rate set
+// of positive class weight, `trial` are factors (post_set_grid), the MIX instances accumulate and
+// post_mix turns the accumulator into the values.
+template <bool MIX>
+int bp_read(const char *who, rt_model *m, rt_sites *s, int recompute_transitions,
+            const double *class_weights, int64_t npoints, const double *trial, double *values,
+            double *sums, double *loglik, int32_t *status)
 {
-    static const char who[] = "rt_sites_branch_profiles_mixture";
+    using grid_t = std::conditional_t<MIX, post_set_grid, post_grid>;
     post_pass p;                                 // (alive until the synchronisation below)
     RT_TRY(post_open(&p, who, m, s));
-    RT_TRY(post_class_weights(who, m, class_weights));
-    RT_TRY(post_set_grid::check(&p, npoints, factors));
-    const rt_rate_sets &r = m->multi;
-    const int64_t K = r.K, n = p.n, N = p.N, nsites = p.nsites;
+    if (MIX) RT_TRY(post_class_weights(who, m, class_weights));
+    RT_TRY(grid_t::check(&p, recompute_transitions, npoints, trial));
+    const int64_t n = p.n, N = p.N, nsites = p.nsites;
     const int np = (int)npoints;
-    p.per_set = true;
+    p.per_set = MIX;
     RT_TRY(post_layout(&p, true));
-    RT_REQUIRE(r.P_stride == N * n * n, "unexpected stride of the sets' transition matrices");
     const size_t rows = (size_t)N * np;
-    post_plan &plan = p.plan;
-    post_set_grid grid;                          // (alive until the synchronisation below)
-    post_set_pt PT;
-    const size_t o_val = plan.take(rows * nsites * 8);
-    const size_t o_valT = plan.take(values ? rows * nsites * 8 : 8);
-    const size_t o_sum = plan.take(rows * 8);
-    const size_t o_tot = plan.take((size_t)K * nsites * 8), o_stat = plan.take((size_t)K * nsites * 4);
-    const size_t o_post = plan.take((size_t)nsites * K * 8), o_ll = plan.take((size_t)nsites * 8);
-    const size_t o_cw = plan.take((size_t)K * 8);
-    const size_t o_dead = plan.take((size_t)N * 4), o_tl = plan.take((size_t)N * 8);
-    RT_TRY(grid.take(&p, K, np));
-    PT.take(&p, K);
+    // scratch: L, M, D of every node and site (post_layout), the result, the grid matrices, their
+    // fragments and the tiled arguments of the exponential (the grid), the mixture's pieces
+    grid_t grid;                                 // (alive until the synchronisation below)
+    post_mix mix;
+    post_result res(values, sums);
+    res.take_sums(&p, rows);
+    res.take_chunk(&p, rows);
+    size_t o_dead = 0, o_tl = 0;
+    if (MIX) {
+        RT_TRY(mix.take(&p, class_weights));
+        o_dead = p.plan.take((size_t)N * 4);
+        o_tl = p.plan.take((size_t)N * 8);
+    }
+    RT_TRY(grid.take(&p, np));
     RT_TRY(post_begin(&p, recompute_transitions));
-    PT.place(&p);
+    res.place(&p);
     hipStream_t st = p.st;
-    unsigned char *base = p.base;
-    double *d_val = (double *)(base + o_val), *d_valT = (double *)(base + o_valT);
-    double *d_sum = (double *)(base + o_sum), *d_tot = (double *)(base + o_tot);
-    double *d_post = (double *)(base + o_post), *d_ll = (double *)(base + o_ll);
-    double *d_cw = (double *)(base + o_cw), *d_tl = (double *)(base + o_tl);
-    int *d_stat = (int *)(base + o_stat), *d_dead = (int *)(base + o_dead);
-    std::vector<int32_t> internal((size_t)N, 0);
-    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
-    RT_HIP(hipMemcpyAsync(d_cw, class_weights, (size_t)K * 8, hipMemcpyHostToDevice, st));
-    RT_HIP(hipMemsetAsync(d_stat, 0, (size_t)K * nsites * 4, st));
-    RT_HIP(hipMemsetAsync(d_tot, 0, (size_t)K * nsites * 8, st));
-    hipLaunchKernelGGL(mix_dead_edge_kernel<256>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, (int)K,
-                       (int)N, (const double *)d_cw, (const double *)r.d_t, d_dead, d_tl);
-    RT_HIP(hipGetLastError());
-    // 1. the trial matrices of every set
-    RT_TRY(grid.launch(&p, d_cw, factors));
-    RT_TRY(post_up(&p, internal.data(), false));
+    // what the sums go by: the resident lengths; MIX: 0 on an edge that is dead under a live set
+    const double *d_tlen = m->d_t;
+    int *d_dead = nullptr;
+    if (MIX) {
+        RT_TRY(mix.begin(&p));
+        d_dead = (int *)(p.base + o_dead);
+        double *d_tl = (double *)(p.base + o_tl);
+        hipLaunchKernelGGL(mix_dead_edge_kernel<256>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st,
+                           (int)mix.K, (int)N, p.d_cw, (const double *)m->multi.d_t, d_dead, d_tl);
+        RT_HIP(hipGetLastError());
+        d_tlen = d_tl;
+    }
+    const std::vector<int32_t> internal = post_internal_nodes(&p);
+    // 1. the trial matrices: one launch of the route the resident transitions take
+    RT_TRY(grid.launch(&p, trial));
+    RT_TRY(post_up(&p, internal.data(), !MIX));
     if (!p.lane) {
-        RT_TRY(PT.pack(&p));
+        if (MIX) RT_TRY(mix.PT.pack(&p));
         RT_TRY(grid.pack(&p));
     }
-    // 2. the passes, set by set (a set of weight zero is never live: not run, never read)
+    // 2. the pass; MIX: set by set (a set of weight zero is never live: not run, never read)
     int first = 1;
-    for (int64_t k = 0; k < K; ++k) {
-        const double ck = class_weights[k];
+    for (int64_t k = 0; k < (MIX ? mix.K : 1); ++k) {
+        const double ck = MIX ? class_weights[k] : 1.0;
         if (!(ck > 0.0)) continue;
-        double *totk = d_tot + (size_t)k * nsites;
-        int *statk = d_stat + (size_t)k * nsites;
+        const double *P = m->d_P, *G = grid.d_G, *PT = p.d_PT, *GT = grid.d_GT, *tlen = m->d_t;
+        int *stat = p.d_status;
+        double *tot = nullptr;
+        if constexpr (MIX) {
+            P = mix.P_of(&p, k); G = grid.G_of_set(&p, k);
+            PT = mix.PT.of_set(k); GT = grid.GT_of_set(k);
+            tlen = nullptr; stat = mix.status_of(&p, k); tot = mix.tot_of(&p, k);
+        }
         if (p.lane) {
             const int *d_tab = p.d_ptab;
             RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
-                hipLaunchKernelGGL((bp_lane_kernel<decltype(nv)::value, true>),
+                hipLaunchKernelGGL((bp_lane_kernel<decltype(nv)::value, MIX>),
                                    dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)N,
-                                   (long)nsites, (const double *)(r.d_P + k * r.P_stride),
-                                   grid.G_of_set(&p, k), np, d_tab, d_tab + N, (const void *)s->d_obs,
+                                   (long)nsites, P, G, np, d_tab, d_tab + N, (const void *)s->d_obs,
                                    s->compact_states, (int)s->nobs, s->block_sites,
-                                   (const double *)m->d_root, (const double *)nullptr, p.d_L, p.d_M, p.d_D,
-                                   d_val, statk, ck, first, totk);
+                                   (const double *)m->d_root, tlen, p.d_L, p.d_M, p.d_D, res.d_val, stat,
+                                   ck, first, tot);
                 return RT_OK;
             }));
         } else {
             const rt_sites *x = p.x;
-            RT_TRY(post_up_set(&p, k, nullptr));
+            if (MIX) RT_TRY(post_up_set(&p, k, nullptr));
             RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
                 constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
-                hipLaunchKernelGGL((bp_down_kernel<NT, KS, true>), dim3((unsigned)x->nblocks), dim3(64 * NT),
-                                   0, st, PT.of_set(k), grid.GT_of_set(k), np, p.nops,
-                                   (const int4 *)p.d_steps, (const double *)p.d_L, (const double *)p.d_M,
-                                   p.d_D, (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
-                                   (const double *)nullptr, (int)n, d_val, statk, (long)x->nsites,
-                                   (long)x->nblocks, ck, first, totk);
+                hipLaunchKernelGGL((bp_down_kernel<NT, KS, MIX>), dim3((unsigned)x->nblocks), dim3(64 * NT),
+                                   0, st, PT, GT, np, p.nops, (const int4 *)p.d_steps,
+                                   (const double *)p.d_L, (const double *)p.d_M, p.d_D,
+                                   (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root, tlen,
+                                   (int)n, res.d_val, stat, (long)x->nsites, (long)x->nblocks, ck, first,
+                                   tot);
                 return RT_OK;
             }));
         }
         RT_HIP(hipGetLastError());
         first = 0;
     }
-    // 3. log Lambda_i and the status, the values, the sums; only what was asked for crosses PCIe
-    hipLaunchKernelGGL(mix_post_kernel<256>, dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)K,
-                       (long)nsites, (const double *)d_cw, (const double *)d_tot, (const int *)d_stat,
-                       d_post, d_ll, p.d_status);
-    RT_HIP(hipGetLastError());
-    if (values || sums) {
-        hipLaunchKernelGGL(mix_log_ratio_kernel<256>,
-                           dim3((unsigned)((nsites + 255) / 256), (unsigned)std::min<size_t>(rows, 1024)),
-                           dim3(256), 0, st, (long)rows, np, (long)nsites, (const double *)d_ll,
-                           (const int *)p.d_status, (const int *)d_dead, d_val);
-        RT_HIP(hipGetLastError());
+    // MIX: log Lambda_i and the status, the accumulator -> values
+    if (MIX) {
+        RT_TRY(mix.post(&p));
+        if (values || sums) RT_TRY(mix.log_ratio(&p, rows, np, d_dead, res.d_val));
     }
-    if (sums) {
-        hipLaunchKernelGGL(profile_sums_kernel, dim3((unsigned)rows), dim3(256), 0, st, np, (long)nsites,
-                           (const double *)d_val, (const double *)s->d_weights, (const int *)p.d_status,
-                           (const double *)d_tl, d_sum);
-        RT_HIP(hipGetLastError());
-        RT_HIP(hipMemcpyAsync(sums, d_sum, rows * 8, hipMemcpyDeviceToHost, st));
-    }
-    if (values) {
-        hipLaunchKernelGGL(post_transpose_kernel<32>,
-                           dim3((unsigned)((nsites + 31) / 32), (unsigned)((rows + 31) / 32)), dim3(256),
-                           0, st, (long)rows, (long)nsites, (const double *)d_val, d_valT);
-        RT_HIP(hipGetLastError());
-        RT_HIP(hipMemcpyAsync(values, d_valT, rows * nsites * 8, hipMemcpyDeviceToHost, st));
-    }
-    if (loglik) RT_HIP(hipMemcpyAsync(loglik, d_ll, (size_t)nsites * 8, hipMemcpyDeviceToHost, st));
-    if (status) RT_HIP(hipMemcpyAsync(status, p.d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
-    RT_HIP(hipStreamSynchronize(st));
-    RT_TRY(grid.result(&p));
-    return RT_OK;
+    // 3. the weighted site sums and the per-site array
+    RT_TRY(res.chunk(&p, 0, rows, np, d_tlen));
+    RT_TRY(res.finish(&p, status, loglik, mix.d_ll));
+    return grid.result(&p);
+}
+
+}  // namespace
+
+extern "C" int rt_sites_branch_profiles(rt_model *m, rt_sites *s, int recompute_transitions,
+                                        int64_t npoints, const double *lengths, double *values,
+                                        double *sums, int32_t *status)
+{
+    return bp_read<false>("rt_sites_branch_profiles", m, s, recompute_transitions, nullptr, npoints,
+                          lengths, values, sums, nullptr, status);
+}
+
+extern "C" int rt_sites_branch_profiles_mixture(rt_model *m, rt_sites *s, int recompute_transitions,
+                                                const double *class_weights, int64_t npoints,
+                                                const double *factors, double *values, double *sums,
+                                                double *loglik, int32_t *status)
+{
+    return bp_read<true>("rt_sites_branch_profiles_mixture", m, s, recompute_transitions,
+                         class_weights, npoints, factors, values, sums, loglik, status);
 }

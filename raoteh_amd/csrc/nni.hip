@@ -22,27 +22,25 @@
 //      moves and per move the staged W o M_c, per grid point one n x n by n x 16 matrix-pipe
 //      product dotted with L'_v and reduced over the states in a fixed order; the logs by all
 //      lanes at the end.  n <= 4: nni_lane_kernel, one lane per site;
-//   3. nni_sums_kernel: the site-weighted sums per (move, point) in a fixed order; then, if the
-//      per-site array is asked for, its transpose to [site][move][point].
+//   3. post_result (post_common.h): the site-weighted sums per (move, point) in a fixed order;
+//      then, if the per-site array is asked for, its transpose to [site][move][point].
 //
-// Steps 2 and 3 run per chunk of moves where the result of all moves would not fit the scratch.
-// Nothing of the batch or the model is written; two calls give the same bits.
+// Steps 2 and 3 run per chunk of moves where the result of all moves would not fit the scratch
+// (post_chunk_units).  Nothing of the batch or the model is written; two calls give the same bits.
 //
-// rt_sites_nni_scores_mixture (at the end): the same scores under a site-class mixture over the
-// model's rate sets -- the kernels' MIX forms once per set into one accumulator, the root scaled by
-// the class weight instead of 1 / L_i.
+// rt_sites_nni_scores_mixture: the same scores of an ORDINARY batch under a site-class mixture over
+// the model's K rate sets, trial lengths as factors of every set's own resident length of the edge
+// above v -- the kernels' MIX forms once per set into one accumulator, the root scaled by the class
+// weight instead of 1 / L_i.  One host body (nni_read, at the end) serves both calls.
 #include "common.h"
 #include "post_common.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
 namespace {
 
 constexpr int NNI_CHUNK = 8;                     // grid points between two barriers of nni_kernel
-constexpr size_t NNI_CHUNK_BYTES = (size_t)4 << 30;      // result bytes of one chunk of moves
-constexpr double NNI_SCRATCH_CAP = 96e9;         // (post_begin's)
 
 // the stored value: 0 at a site of zero likelihood, else the log of the ratio (-inf where it is
 // not positive)
@@ -289,30 +287,6 @@ nni_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const dou
     }
 }
 
-// one workgroup per (move, point), the order of profile_sums_kernel: thread j adds sites j,
-// j + 256, ... in order, then the 256 partial sums by halves (fixed rounding).  Sites of zero
-// likelihood and of weight 0 are skipped.
-__global__ void __launch_bounds__(256)
-nni_sums_kernel(long nsites, const double *__restrict__ values, const double *__restrict__ weights,
-                const int *__restrict__ status, double *__restrict__ sums)
-{
-    __shared__ double part[256];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const double *x = values + (size_t)row * nsites;
-    double acc = 0.0;
-    for (long i = tid; i < nsites; i += 256) {
-        const double w = weights ? weights[i] : 1.0;       // (w = 0: not -inf * 0 = NaN)
-        if (w != 0.0 && !(status[i] & RT_SITE_ZERO_PROB)) acc += w * x[i];
-    }
-    part[tid] = acc;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (tid < h) part[tid] += part[tid + h];
-        __syncthreads();
-    }
-    if (tid == 0) sums[row] = part[0];
-}
-
 // the moves in their order: v ascending, then the children c of v, then the siblings s of v, both
 // in CSR order.  first (or null): [nnodes] the index of every node's first move; moves (or null):
 // the triples
@@ -351,22 +325,6 @@ int nni_moves_out(int64_t cnt, int32_t *moves, int64_t capacity, int64_t *nmoves
     return RT_OK;
 }
 
-// the moves of one chunk: their result (and its transpose), per_move bytes a move, within the chunk
-// size and the cap of the scratch
-int64_t nni_chunk_moves(const post_plan &plan, size_t per_move, int np, int64_t nmoves)
-{
-    size_t chunk_bytes = NNI_CHUNK_BYTES;
-    if (const char *e = getenv("RAOTEH_NNI_CHUNK_BYTES")) {      // (tests: many chunks at small sizes)
-        const long long v = atoll(e);
-        if (v > 0) chunk_bytes = (size_t)v;
-    }
-    const double room = NNI_SCRATCH_CAP - (double)plan.total - 4096.0;
-    if (room < (double)chunk_bytes) chunk_bytes = room > 0.0 ? (size_t)room : 0;
-    int64_t CH = std::max<int64_t>(1, (int64_t)(chunk_bytes / per_move));
-    CH = std::min<int64_t>(CH, std::max<int64_t>(1, ((int64_t)1 << 21) / np));   // (the grids' y)
-    return std::min<int64_t>(CH, std::max<int64_t>(nmoves, 1));
-}
-
 }  // namespace
 
 extern "C" int rt_model_nni_moves(const rt_model *m, int32_t *moves, int64_t capacity, int64_t *nmoves)
@@ -380,281 +338,152 @@ extern "C" int rt_model_nni_moves(const rt_model *m, int32_t *moves, int64_t cap
 extern "C" int rt_tree_nni_moves(int64_t nnodes, const int64_t *idx, const int64_t *ptr,
                                  int32_t *moves, int64_t capacity, int64_t *nmoves)
 {
-    RT_REQUIRE(nnodes >= 1 && ptr && (idx || nnodes == 1) && nmoves, "bad arguments");
-    RT_REQUIRE(ptr[0] == 0 && ptr[nnodes] == nnodes - 1, "tree_csr_indptr does not describe a tree");
-    std::vector<int32_t> parent((size_t)nnodes, -1);
-    for (int64_t v = 0; v < nnodes; ++v) {
-        RT_REQUIRE(ptr[v + 1] >= ptr[v], "tree_csr_indptr not monotone");
-        for (int64_t e = ptr[v]; e < ptr[v + 1]; ++e) {
-            RT_REQUIRE(idx[e] > v && idx[e] < nnodes, "children not in preorder");
-            parent[(size_t)idx[e]] = (int32_t)v;
-        }
-    }
+    RT_REQUIRE(nmoves, "bad arguments");
+    // (the moves of v go through the children of its parent: every node but the root has one)
+    std::vector<int32_t> parent;
+    RT_TRY(post_csr_parents(nnodes, idx, ptr, &parent));
     RT_TRY(nni_moves_out(nni_enumerate(nnodes, idx, ptr, parent.data(), nullptr, nullptr), moves,
                          capacity, nmoves));
     if (moves) nni_enumerate(nnodes, idx, ptr, parent.data(), nullptr, moves);
     return RT_OK;
 }
 
-extern "C" int rt_sites_nni_scores(rt_model *m, rt_sites *s, int recompute_transitions,
-                                   int64_t npoints, const double *lengths, double *values,
-                                   double *sums, int32_t *status)
-{
-    post_pass p;                                 // (alive until the synchronisation below)
-    RT_TRY(post_open(&p, "rt_sites_nni_scores", m, s));
-    const int64_t n = p.n, N = p.N, nsites = p.nsites;
-    // the moves; the rows of `lengths` that count are those of the nodes with one
-    std::vector<int32_t> first((size_t)N + 1, 0);
-    const int64_t nmoves = nni_enumerate(m, first.data(), nullptr);
-    first[(size_t)N] = (int32_t)nmoves;
-    std::vector<unsigned char> has_move((size_t)N, 0);
-    for (int64_t v = 1; v < N; ++v) has_move[(size_t)v] = first[(size_t)v + 1] > first[(size_t)v];
-    if (lengths)
-        RT_TRY(post_grid_check(&p, recompute_transitions, npoints, lengths, has_move.data()));
-    else
-        RT_REQUIRE(npoints == 1, "rt_sites_nni_scores: without lengths the edge above v keeps its "
-                   "matrix: 1 grid point (%lld here)", (long long)npoints);
-    RT_REQUIRE(nmoves * npoints < (int64_t)1 << 31, "rt_sites_nni_scores: too many moves");
-    const int np = (int)npoints;
-    RT_TRY(post_layout(&p, true));
-    post_plan &plan = p.plan;
-    post_grid grid;                              // (alive until the synchronisation below)
-    if (lengths) RT_TRY(post_grid_take(&p, &grid, np));
-    const int cnt = p.lane ? (int)N : p.nops;    // slots of the move tables
-    const size_t tab_ints = (size_t)4 * cnt;
-    const size_t o_tab = plan.take(tab_ints * 4);
-    const size_t o_sum = plan.take((size_t)std::max<int64_t>(nmoves, 1) * np * 8);
-    const int64_t CH = nni_chunk_moves(plan, (size_t)np * nsites * 8 * (values ? 2 : 1), np, nmoves);
-    const size_t chunk_rows = (size_t)CH * np;
-    const size_t o_val = plan.take(chunk_rows * nsites * 8);
-    const size_t o_valT = plan.take(values ? chunk_rows * nsites * 8 : 8);
-    RT_TRY(post_begin(&p, recompute_transitions));
-    hipStream_t st = p.st;
-    unsigned char *base = p.base;
-    double *d_val = (double *)(base + o_val), *d_valT = (double *)(base + o_valT);
-    double *d_sum = (double *)(base + o_sum);
-    int *d_tab = (int *)(base + o_tab);
-    int *d_status = p.d_status;
-    std::vector<int32_t> internal((size_t)N, 0);
-    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
-    if (lengths) RT_TRY(post_grid_launch(&p, &grid, lengths, has_move.data()));
-    RT_TRY(post_up(&p, internal.data(), true));
-    // the move tables, by step (n > 4) or by node
-    std::vector<int32_t> tab;
-    post_tab_build(&p, first.data(), &tab);
-    RT_HIP(hipMemcpyAsync(d_tab, tab.data(), tab_ints * 4, hipMemcpyHostToDevice, st));
-    if (!p.lane && lengths) RT_TRY(post_grid_pack(&p, &grid));
-    for (int64_t mv0 = 0; mv0 == 0 || mv0 < nmoves; mv0 += CH) {
-        const int64_t mv1 = std::min(nmoves, mv0 + CH);
-        const size_t rows = (size_t)(mv1 - mv0) * np;
-        if (p.lane) {
-            const int *d_ptab = p.d_ptab;
-            RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
-                hipLaunchKernelGGL((nni_lane_kernel<decltype(nv)::value>),
-                                   dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)N,
-                                   (long)nsites, (const double *)m->d_P,
-                                   (const double *)(lengths ? grid.d_G : nullptr), np, d_ptab, d_ptab + N,
-                                   (const int *)d_tab, (const void *)s->d_obs, s->compact_states,
-                                   (int)s->nobs, s->block_sites, (const double *)m->d_root, p.d_L, p.d_M,
-                                   p.d_D, (int)mv0, (int)mv1, d_val, d_status, 1.0, 1, (double *)nullptr);
-                return RT_OK;
-            }));
-        } else {
-            const rt_sites *x = p.x;
-            RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
-                constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
-                hipLaunchKernelGGL((nni_kernel<NT, KS>), dim3((unsigned)x->nblocks), dim3(64 * NT), 0, st,
-                                   (const double *)p.d_PT, (const double *)(lengths ? grid.d_GT : p.d_PT),
-                                   np, p.nops, (const int4 *)p.d_steps, (const int *)d_tab,
-                                   (const double *)p.d_L, (const double *)p.d_M, p.d_D,
-                                   (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
-                                   (int)n, (int)mv0, (int)mv1, d_val, d_status, (long)x->nsites,
-                                   (long)x->nblocks, 1.0, 1, (double *)nullptr);
-                return RT_OK;
-            }));
-        }
-        RT_HIP(hipGetLastError());
-        if (!rows) break;                        // (no moves: the status alone)
-        // 3. the weighted site sums; only what was asked for crosses PCIe
-        if (sums) {
-            hipLaunchKernelGGL(nni_sums_kernel, dim3((unsigned)rows), dim3(256), 0, st, (long)nsites,
-                               (const double *)d_val, (const double *)s->d_weights,
-                               (const int *)d_status, d_sum + (size_t)mv0 * np);
-            RT_HIP(hipGetLastError());
-        }
-        if (values) {
-            hipLaunchKernelGGL(post_transpose_kernel<32>,
-                               dim3((unsigned)((nsites + 31) / 32), (unsigned)((rows + 31) / 32)),
-                               dim3(256), 0, st, (long)rows, (long)nsites, (const double *)d_val, d_valT);
-            RT_HIP(hipGetLastError());
-            // [site][rows of the chunk] into the caller's [site][nmoves][np]
-            RT_HIP(hipMemcpy2DAsync(values + (size_t)mv0 * np, (size_t)nmoves * np * 8, d_valT, rows * 8,
-                                    rows * 8, (size_t)nsites, hipMemcpyDeviceToHost, st));
-        }
-    }
-    if (sums && nmoves)
-        RT_HIP(hipMemcpyAsync(sums, d_sum, (size_t)nmoves * np * 8, hipMemcpyDeviceToHost, st));
-    if (status) RT_HIP(hipMemcpyAsync(status, d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
-    RT_HIP(hipStreamSynchronize(st));
-    if (lengths) RT_TRY(post_grid_result(&p, &grid));
-    return RT_OK;
-}
+namespace {
 
-// The same scores of an ORDINARY batch under a site-class mixture over the model's K rate sets, trial
-// lengths as factors of every set's own resident length of the edge above v:
-//   1. factors given: P_kv(factor t_kv) of every set, point and edge in ONE launch of the sets'
-//      exponential (post_set_grid); the sets' P^T as A fragments (post_set_pt);
-//   2. per chunk of moves and per set k with c_k > 0, on the one stream over one L, M, U scratch: the
-//      upward pass through a view of set k's tables (post_up_set), then the MIX instance of
-//      nni_kernel (n <= 4: nni_lane_kernel) -- the term c_k L_ik(moved tree, tau) into ONE
-//      accumulator [move][point][site], the sets added in set order, L_ik and a status word per set;
-//   3. mix_post_kernel (log Lambda_i, the status), mix_log_ratio_kernel (the accumulator ->
-//      values), then nni_sums_kernel and the transpose as the single-set call.
-// Nothing is divided before the end: exact where L_ik == 0 on the resident tree.
-extern "C" int rt_sites_nni_scores_mixture(rt_model *m, rt_sites *s, int recompute_transitions,
-                                           const double *class_weights, int64_t npoints,
-                                           const double *factors, double *values, double *sums,
-                                           double *loglik, int32_t *status)
+// Both reads.  MIX = false: the pass runs once under the model's own matrices, `trial` are lengths
+// (post_grid), the plain kernel instance divides by L_i at the root and makes the `up` pass in the
+// first chunk only.  MIX = true: per chunk once per rate set of positive class weight over one L,
+// M, U scratch -- the upward pass through a view of set k's tables (post_up_set), then the MIX
+// instance, which makes the `up` pass every time and adds the term c_k L_ik(moved tree, tau) into
+// ONE accumulator [move][point][site] in set order; `trial` are factors (post_set_grid), post_mix
+// turns the accumulator into the values.  Nothing is divided before the end: exact where
+// L_ik == 0 on the resident tree.
+template <bool MIX>
+int nni_read(const char *who, rt_model *m, rt_sites *s, int recompute_transitions,
+             const double *class_weights, int64_t npoints, const double *trial, double *values,
+             double *sums, double *loglik, int32_t *status)
 {
-    static const char who[] = "rt_sites_nni_scores_mixture";
+    using grid_t = std::conditional_t<MIX, post_set_grid, post_grid>;
     post_pass p;                                 // (alive until the synchronisation below)
     RT_TRY(post_open(&p, who, m, s));
-    RT_TRY(post_class_weights(who, m, class_weights));
-    const rt_rate_sets &r = m->multi;
-    const int64_t K = r.K, n = p.n, N = p.N, nsites = p.nsites;
-    // the moves; the rows of `factors` that count are those of the nodes with one
+    if (MIX) RT_TRY(post_class_weights(who, m, class_weights));
+    const int64_t n = p.n, N = p.N, nsites = p.nsites;
+    // the moves; the rows of `trial` that count are those of the nodes with one
     std::vector<int32_t> first((size_t)N + 1, 0);
     const int64_t nmoves = nni_enumerate(m, first.data(), nullptr);
     first[(size_t)N] = (int32_t)nmoves;
     std::vector<unsigned char> has_move((size_t)N, 0);
     for (int64_t v = 1; v < N; ++v) has_move[(size_t)v] = first[(size_t)v + 1] > first[(size_t)v];
-    if (factors)
-        RT_TRY(post_set_grid::check(&p, npoints, factors, has_move.data()));
-    else
-        RT_REQUIRE(npoints == 1, "%s: without factors the edge above v keeps its matrices: 1 grid "
-                   "point (%lld here)", who, (long long)npoints);
+    if (trial) RT_TRY(grid_t::check(&p, recompute_transitions, npoints, trial, has_move.data()));
+    RT_REQUIRE(trial || npoints == 1, "%s: without %s the edge above v keeps its %s: 1 grid point "
+               "(%lld here)", who, MIX ? "factors" : "lengths", MIX ? "matrices" : "matrix",
+               (long long)npoints);
     RT_REQUIRE(nmoves * npoints < (int64_t)1 << 31, "%s: too many moves", who);
     const int np = (int)npoints;
-    p.per_set = true;
+    p.per_set = MIX;
     RT_TRY(post_layout(&p, true));
-    RT_REQUIRE(r.P_stride == N * n * n, "unexpected stride of the sets' transition matrices");
-    post_plan &plan = p.plan;
-    post_set_grid grid;                          // (alive until the synchronisation below)
-    post_set_pt PT;
-    if (factors) RT_TRY(grid.take(&p, K, np));
-    PT.take(&p, K);
+    grid_t grid;                                 // (alive until the synchronisation below)
+    post_mix mix;
+    post_result res(values, sums);
+    if (trial) RT_TRY(grid.take(&p, np));
+    if (MIX) RT_TRY(mix.take(&p, class_weights));
     const int cnt = p.lane ? (int)N : p.nops;    // slots of the move tables
     const size_t tab_ints = (size_t)4 * cnt;
-    const size_t o_tab = plan.take(tab_ints * 4);
-    const size_t o_sum = plan.take((size_t)std::max<int64_t>(nmoves, 1) * np * 8);
-    const size_t o_tot = plan.take((size_t)K * nsites * 8), o_stat = plan.take((size_t)K * nsites * 4);
-    const size_t o_post = plan.take((size_t)nsites * K * 8), o_ll = plan.take((size_t)nsites * 8);
-    const size_t o_cw = plan.take((size_t)K * 8);
-    const int64_t CH = nni_chunk_moves(plan, (size_t)np * nsites * 8 * (values ? 2 : 1), np, nmoves);
-    const size_t chunk_rows = (size_t)CH * np;
-    const size_t o_val = plan.take(chunk_rows * nsites * 8);
-    const size_t o_valT = plan.take(values ? chunk_rows * nsites * 8 : 8);
+    const size_t o_tab = p.plan.take(tab_ints * 4);
+    res.take_sums(&p, (size_t)nmoves * np);
+    // the chunks of moves: at most what the grids' y takes of (move, point) rows
+    const int64_t CH = post_chunk_units(p.plan, np * res.row_bytes(&p), 0, ((int64_t)1 << 21) / np, nmoves,
+                                        "RAOTEH_NNI_CHUNK_BYTES");
+    res.take_chunk(&p, (size_t)CH * np);
     RT_TRY(post_begin(&p, recompute_transitions));
-    PT.place(&p);
+    res.place(&p);
+    if (MIX) RT_TRY(mix.begin(&p));
     hipStream_t st = p.st;
-    unsigned char *base = p.base;
-    double *d_val = (double *)(base + o_val), *d_valT = (double *)(base + o_valT);
-    double *d_sum = (double *)(base + o_sum), *d_tot = (double *)(base + o_tot);
-    double *d_post = (double *)(base + o_post), *d_ll = (double *)(base + o_ll);
-    double *d_cw = (double *)(base + o_cw);
-    int *d_tab = (int *)(base + o_tab), *d_stat = (int *)(base + o_stat);
-    std::vector<int32_t> internal((size_t)N, 0);
-    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
-    RT_HIP(hipMemcpyAsync(d_cw, class_weights, (size_t)K * 8, hipMemcpyHostToDevice, st));
-    RT_HIP(hipMemsetAsync(d_stat, 0, (size_t)K * nsites * 4, st));
-    RT_HIP(hipMemsetAsync(d_tot, 0, (size_t)K * nsites * 8, st));
-    if (factors) RT_TRY(grid.launch(&p, d_cw, factors, has_move.data()));
-    RT_TRY(post_up(&p, internal.data(), false));
+    int *d_tab = (int *)(p.base + o_tab);
+    const std::vector<int32_t> internal = post_internal_nodes(&p);
+    if (trial) RT_TRY(grid.launch(&p, trial, has_move.data()));
+    RT_TRY(post_up(&p, internal.data(), !MIX));
     // the move tables, by step (n > 4) or by node
     std::vector<int32_t> tab;
     post_tab_build(&p, first.data(), &tab);
     RT_HIP(hipMemcpyAsync(d_tab, tab.data(), tab_ints * 4, hipMemcpyHostToDevice, st));
     if (!p.lane) {
-        RT_TRY(PT.pack(&p));
-        if (factors) RT_TRY(grid.pack(&p));
+        if (MIX) RT_TRY(mix.PT.pack(&p));
+        if (trial) RT_TRY(grid.pack(&p));
     }
     for (int64_t mv0 = 0; mv0 == 0 || mv0 < nmoves; mv0 += CH) {
         const int64_t mv1 = std::min(nmoves, mv0 + CH);
         const size_t rows = (size_t)(mv1 - mv0) * np;
-        // the passes, set by set (a set of weight zero is never live: not run, never read)
+        // the pass; MIX: set by set (a set of weight zero is never live: not run, never read)
         int first_set = 1;
-        for (int64_t k = 0; k < K; ++k) {
-            const double ck = class_weights[k];
+        for (int64_t k = 0; k < (MIX ? mix.K : 1); ++k) {
+            const double ck = MIX ? class_weights[k] : 1.0;
             if (!(ck > 0.0)) continue;
-            double *totk = d_tot + (size_t)k * nsites;
-            int *statk = d_stat + (size_t)k * nsites;
+            // without trial lengths: the resident matrices (n <= 4: no G; else their fragments)
+            const double *P = m->d_P, *G = trial ? grid.d_G : nullptr;
+            const double *PT = p.d_PT, *GT = trial ? grid.d_GT : p.d_PT;
+            int *stat = p.d_status;
+            double *tot = nullptr;
+            if constexpr (MIX) {
+                P = mix.P_of(&p, k); G = trial ? grid.G_of_set(&p, k) : nullptr;
+                PT = mix.PT.of_set(k); GT = trial ? grid.GT_of_set(k) : PT;
+                stat = mix.status_of(&p, k); tot = mix.tot_of(&p, k);
+            }
             if (p.lane) {
                 const int *d_ptab = p.d_ptab;
                 RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
-                    hipLaunchKernelGGL((nni_lane_kernel<decltype(nv)::value, true>),
+                    hipLaunchKernelGGL((nni_lane_kernel<decltype(nv)::value, MIX>),
                                        dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)N,
-                                       (long)nsites, (const double *)(r.d_P + k * r.P_stride),
-                                       factors ? grid.G_of_set(&p, k) : (const double *)nullptr, np,
-                                       d_ptab, d_ptab + N, (const int *)d_tab, (const void *)s->d_obs,
-                                       s->compact_states, (int)s->nobs, s->block_sites,
-                                       (const double *)m->d_root, p.d_L, p.d_M, p.d_D, (int)mv0, (int)mv1,
-                                       d_val, statk, ck, first_set, totk);
+                                       (long)nsites, P, G, np, d_ptab, d_ptab + N, (const int *)d_tab,
+                                       (const void *)s->d_obs, s->compact_states, (int)s->nobs,
+                                       s->block_sites, (const double *)m->d_root, p.d_L, p.d_M, p.d_D,
+                                       (int)mv0, (int)mv1, res.d_val, stat, ck, first_set, tot);
                     return RT_OK;
                 }));
             } else {
                 const rt_sites *x = p.x;
-                RT_TRY(post_up_set(&p, k, nullptr));
+                if (MIX) RT_TRY(post_up_set(&p, k, nullptr));
                 RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
                     constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
-                    hipLaunchKernelGGL((nni_kernel<NT, KS, true>), dim3((unsigned)x->nblocks),
-                                       dim3(64 * NT), 0, st, PT.of_set(k),
-                                       factors ? grid.GT_of_set(k) : PT.of_set(k), np, p.nops,
-                                       (const int4 *)p.d_steps, (const int *)d_tab, (const double *)p.d_L,
-                                       (const double *)p.d_M, p.d_D, (const double *)x->d_obs,
-                                       (int)x->nobs, (const double *)m->d_root, (int)n, (int)mv0, (int)mv1,
-                                       d_val, statk, (long)x->nsites, (long)x->nblocks, ck, first_set,
-                                       totk);
+                    hipLaunchKernelGGL((nni_kernel<NT, KS, MIX>), dim3((unsigned)x->nblocks),
+                                       dim3(64 * NT), 0, st, PT, GT, np, p.nops, (const int4 *)p.d_steps,
+                                       (const int *)d_tab, (const double *)p.d_L, (const double *)p.d_M,
+                                       p.d_D, (const double *)x->d_obs, (int)x->nobs,
+                                       (const double *)m->d_root, (int)n, (int)mv0, (int)mv1, res.d_val,
+                                       stat, (long)x->nsites, (long)x->nblocks, ck, first_set, tot);
                     return RT_OK;
                 }));
             }
             RT_HIP(hipGetLastError());
             first_set = 0;
         }
-        if (mv0 == 0) {
-            hipLaunchKernelGGL(mix_post_kernel<256>, dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st,
-                               (int)K, (long)nsites, (const double *)d_cw, (const double *)d_tot,
-                               (const int *)d_stat, d_post, d_ll, p.d_status);
-            RT_HIP(hipGetLastError());
-        }
-        if (!rows) break;                        // (no moves: the log-likelihood and the status alone)
-        if (values || sums) {
-            hipLaunchKernelGGL(mix_log_ratio_kernel<256>,
-                               dim3((unsigned)((nsites + 255) / 256), (unsigned)std::min<size_t>(rows, 1024)),
-                               dim3(256), 0, st, (long)rows, np, (long)nsites, (const double *)d_ll,
-                               (const int *)p.d_status, (const int *)nullptr, d_val);
-            RT_HIP(hipGetLastError());
-        }
-        if (sums) {
-            hipLaunchKernelGGL(nni_sums_kernel, dim3((unsigned)rows), dim3(256), 0, st, (long)nsites,
-                               (const double *)d_val, (const double *)s->d_weights,
-                               (const int *)p.d_status, d_sum + (size_t)mv0 * np);
-            RT_HIP(hipGetLastError());
-        }
-        if (values) {
-            hipLaunchKernelGGL(post_transpose_kernel<32>,
-                               dim3((unsigned)((nsites + 31) / 32), (unsigned)((rows + 31) / 32)),
-                               dim3(256), 0, st, (long)rows, (long)nsites, (const double *)d_val, d_valT);
-            RT_HIP(hipGetLastError());
-            // [site][rows of the chunk] into the caller's [site][nmoves][np]
-            RT_HIP(hipMemcpy2DAsync(values + (size_t)mv0 * np, (size_t)nmoves * np * 8, d_valT, rows * 8,
-                                    rows * 8, (size_t)nsites, hipMemcpyDeviceToHost, st));
-        }
+        if (MIX && mv0 == 0) RT_TRY(mix.post(&p));           // (log Lambda_i, the status)
+        if (!rows) break;                        // (no moves: the status, MIX: the log-likelihood)
+        if (MIX && (values || sums)) RT_TRY(mix.log_ratio(&p, rows, np, nullptr, res.d_val));
+        // the weighted site sums and the per-site array [site][nmoves][np]
+        RT_TRY(res.chunk(&p, (size_t)mv0 * np, rows));
     }
-    if (sums && nmoves)
-        RT_HIP(hipMemcpyAsync(sums, d_sum, (size_t)nmoves * np * 8, hipMemcpyDeviceToHost, st));
-    if (loglik) RT_HIP(hipMemcpyAsync(loglik, d_ll, (size_t)nsites * 8, hipMemcpyDeviceToHost, st));
-    if (status) RT_HIP(hipMemcpyAsync(status, p.d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
-    RT_HIP(hipStreamSynchronize(st));
-    if (factors) RT_TRY(grid.result(&p));
+    RT_TRY(res.finish(&p, status, loglik, mix.d_ll));
+    if (trial) RT_TRY(grid.result(&p));
     return RT_OK;
 }
+
+}  // namespace
+
+extern "C" int rt_sites_nni_scores(rt_model *m, rt_sites *s, int recompute_transitions,
+                                   int64_t npoints, const double *lengths, double *values,
+                                   double *sums, int32_t *status)
+{
+    return nni_read<false>("rt_sites_nni_scores", m, s, recompute_transitions, nullptr, npoints, lengths,
+                           values, sums, nullptr, status);
+}
+
+extern "C" int rt_sites_nni_scores_mixture(rt_model *m, rt_sites *s, int recompute_transitions,
+                                           const double *class_weights, int64_t npoints,
+                                           const double *factors, double *values, double *sums,
+                                           double *loglik, int32_t *status)
+{
+    return nni_read<true>("rt_sites_nni_scores_mixture", m, s, recompute_transitions, class_weights,
+                          npoints, factors, values, sums, loglik, status);
+}
+

@@ -26,24 +26,22 @@
 //      field, the dot products on the vector ALU, the states summed in the fixed order of
 //      down_part / down_total, the logs by all lanes at the end);
 //      n <= 4: place_lane_kernel, one lane per site, the same three stages;
-//   3. place_sums_kernel: the site-weighted sums per (query, node, fraction, pendant length) in
-//      a fixed order; then, if the per-site array is asked for, its transpose.
+//   3. post_result (post_common.h): the site-weighted sums per (query, node, fraction, pendant
+//      length) in a fixed order; then, if the per-site array is asked for, its transpose.
 //
 // The field is made once; the queries go through 2 and 3 in chunks where the result of all of
-// them would not fit the scratch.  Nothing of the batch or the model is written; two calls give
-// the same bits, chunked or not.
+// them would not fit the scratch (post_chunk_units).  The fraction grid (its checks, its lengths,
+// its fragment tables) is post_fraction_*, shared with spr.hip.  Nothing of the batch or the model
+// is written; two calls give the same bits, chunked or not.
 #include "common.h"
 #include "post_common.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
 namespace {
 
 constexpr int PLACE_BLOCK = 8;                   // (query, pendant) vectors held per walk of the field
-constexpr size_t PLACE_CHUNK_BYTES = (size_t)4 << 30;    // result bytes of one chunk of queries
-constexpr double PLACE_SCRATCH_CAP = 96e9;       // (post_begin's)
 constexpr int64_t PLACE_MAX_ROWS = (int64_t)1 << 21;     // rows of one transpose launch (grid y)
 
 // the stored value: 0 at a site of zero likelihood, else the log of the ratio (-inf where it is
@@ -368,30 +366,6 @@ place_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const d
     }
 }
 
-// one workgroup per (query, node, fraction, pendant length), the order of profile_sums_kernel:
-// thread j adds sites j, j + 256, ... in order, then the 256 partial sums by halves (fixed
-// rounding).  Sites of zero likelihood and of weight 0 are skipped.
-__global__ void __launch_bounds__(256)
-place_sums_kernel(long nsites, const double *__restrict__ values, const double *__restrict__ weights,
-                  const int *__restrict__ status, double *__restrict__ sums)
-{
-    __shared__ double part[256];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const double *x = values + (size_t)row * nsites;
-    double acc = 0.0;
-    for (long i = tid; i < nsites; i += 256) {
-        const double w = weights ? weights[i] : 1.0;       // (w = 0: not -inf * 0 = NaN)
-        if (w != 0.0 && !(status[i] & RT_SITE_ZERO_PROB)) acc += w * x[i];
-    }
-    part[tid] = acc;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (tid < h) part[tid] += part[tid + h];
-        __syncthreads();
-    }
-    if (tid == 0) sums[row] = part[0];
-}
-
 }  // namespace
 
 extern "C" int rt_sites_placements(rt_model *m, rt_sites *s, int recompute_transitions,
@@ -412,38 +386,26 @@ extern "C" int rt_sites_placements(rt_model *m, rt_sites *s, int recompute_trans
     RT_REQUIRE(query_kind == RT_OBS_DENSE || query_kind == RT_OBS_STATE, "%s: query_kind %d", who,
                query_kind);
     RT_REQUIRE(queries && fractions && pendant, "%s: queries, fractions or pendant is NULL", who);
-    RT_REQUIRE(nfractions >= 1 && nfractions <= RT_MAX_PLACE_FRACTIONS,
-               "%s: 1..%d fractions (%lld here)", who, RT_MAX_PLACE_FRACTIONS, (long long)nfractions);
+    RT_TRY(post_fraction_count(who, nfractions));
     RT_REQUIRE(npendant >= 1 && npendant <= RT_MAX_PLACE_PENDANT,
                "%s: 1..%d pendant lengths (%lld here)", who, RT_MAX_PLACE_PENDANT, (long long)npendant);
     RT_REQUIRE(2 * nfractions + npendant <= 32, "%s: 2 nfractions + npendant is at most 32 "
                "(%lld here)", who, (long long)(2 * nfractions + npendant));
-    for (int64_t r = 0; r < nfractions; ++r)
-        RT_REQUIRE(std::isfinite(fractions[r]) && fractions[r] >= 0.0 && fractions[r] <= 1.0,
-                   "%s: fraction %d is outside [0, 1] or not finite", who, (int)r);
+    RT_TRY(post_fraction_values(who, nfractions, fractions));
     for (int64_t k = 0; k < npendant; ++k)
         RT_REQUIRE(std::isfinite(pendant[k]) && pendant[k] >= 0.0,
                    "%s: pendant length %d is negative or not finite", who, (int)k);
     const int R = (int)nfractions, K = (int)npendant, np = 2 * R + K;
     RT_TRY(post_layout(&p, true));
     // the grid of every node: rho_r t_v, (1 - rho_r) t_v, tau_k
-    std::vector<double> lengths((size_t)N * np, 0.0);
-    if (post_model_has_rates(m))
-        for (int64_t v = 1; v < N; ++v) {
-            double *row = lengths.data() + (size_t)v * np;
-            const double t = m->h_t[(size_t)v];
-            for (int r = 0; r < R; ++r) {
-                row[r] = fractions[r] * t;
-                row[R + r] = (1.0 - fractions[r]) * t;
-            }
-            for (int k = 0; k < K; ++k) row[2 * R + k] = pendant[k];
-        }
-    RT_TRY(post_grid_check(&p, recompute_transitions, np, lengths.data()));
+    const std::vector<double> lengths = post_fraction_lengths(&p, R, fractions, K, pendant);
+    RT_TRY(post_grid::check(&p, recompute_transitions, np, lengths.data()));
     const int64_t NRK = N * R * K;
     RT_REQUIRE(NRK < (int64_t)1 << 31, "%s: too many placements per query", who);
     post_plan &plan = p.plan;
     post_grid grid;                              // (alive until the synchronisation below)
-    RT_TRY(post_grid_take(&p, &grid, np));
+    post_result res(values, sums);
+    RT_TRY(grid.take(&p, np));
     // the distinct rate matrices in use: d of every node, the node that stands for d
     std::vector<int32_t> dnode((size_t)N, -1), rep;
     {
@@ -466,38 +428,26 @@ extern "C" int rt_sites_placements(rt_model *m, rt_sites *s, int recompute_trans
     const size_t o_dtab = plan.take(((size_t)cnt + nd) * 4);
     const size_t tile = p.lane ? 0 : (size_t)s->nblocks * p.NT * 256 * 8;    // one vector of every site
     const size_t o_F = plan.take(p.lane ? (size_t)N * R * n * nsites * 8 : (size_t)p.nops * R * tile);
-    const size_t o_sum = plan.take((size_t)nqueries * NRK * 8);
-    // the queries of one chunk: their result (and its transpose) within the chunk size, and with
-    // their pendant vectors and their own image within the cap
-    const size_t per_result = (size_t)NRK * nsites * 8 * (values ? 2 : 1);
+    res.take_sums(&p, (size_t)nqueries * NRK);
+    // the queries of one chunk (post_chunk_units): beside their result, their pendant vectors and
+    // their own image; at most what the grids' y takes
     const size_t q_bytes = (size_t)nsites * (query_kind == RT_OBS_DENSE ? (size_t)n * 8 : 1);
-    const size_t per_query = per_result + q_bytes + 512 + (p.lane ? 0 : (size_t)nd * K * tile);
-    size_t chunk_bytes = PLACE_CHUNK_BYTES;
-    if (const char *e = getenv("RAOTEH_PLACE_CHUNK_BYTES")) {    // (tests: many chunks at small sizes)
-        const long long v = atoll(e);
-        if (v > 0) chunk_bytes = (size_t)v;
-    }
-    const double room = PLACE_SCRATCH_CAP - (double)plan.total - 4096.0;
-    int64_t CH = std::max<int64_t>(1, (int64_t)(chunk_bytes / per_result));
-    CH = std::min<int64_t>(CH, std::max<int64_t>(1, (int64_t)(room > 0.0 ? room / (double)per_query : 0.0)));
-    CH = std::min<int64_t>(CH, 32768);           // (the grids' y)
-    CH = std::min<int64_t>(CH, nqueries);
-    const size_t chunk_rows = (size_t)CH * NRK;
+    const int64_t CH = post_chunk_units(plan, NRK * res.row_bytes(&p),
+                                        q_bytes + 512 + (p.lane ? 0 : (size_t)nd * K * tile), 32768,
+                                        nqueries, "RAOTEH_PLACE_CHUNK_BYTES");
     const size_t o_q = plan.take((size_t)CH * q_bytes);
     const size_t o_H = plan.take(p.lane ? 8 : (size_t)nd * K * CH * tile);
-    const size_t o_val = plan.take(chunk_rows * nsites * 8);
-    const size_t o_valT = plan.take(values ? std::min<size_t>(chunk_rows, PLACE_MAX_ROWS) * nsites * 8 : 8);
+    res.take_chunk(&p, (size_t)CH * NRK, (size_t)PLACE_MAX_ROWS);
     RT_TRY(post_begin(&p, recompute_transitions));
+    res.place(&p);
     hipStream_t st = p.st;
     unsigned char *base = p.base;
-    double *d_val = (double *)(base + o_val), *d_valT = (double *)(base + o_valT);
-    double *d_sum = (double *)(base + o_sum), *d_F = (double *)(base + o_F), *d_H = (double *)(base + o_H);
+    double *d_val = res.d_val, *d_F = (double *)(base + o_F), *d_H = (double *)(base + o_H);
     int *d_tab = (int *)(base + o_tab), *d_dtab = (int *)(base + o_dtab);
     void *d_q = (void *)(base + o_q);
     int *d_status = p.d_status;
-    std::vector<int32_t> internal((size_t)N, 0);
-    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
-    RT_TRY(post_grid_launch(&p, &grid, lengths.data()));
+    const std::vector<int32_t> internal = post_internal_nodes(&p);
+    RT_TRY(grid.launch(&p, lengths.data()));
     RT_TRY(post_up(&p, internal.data(), true));
     std::vector<int32_t> tab, dtab((size_t)cnt + nd, -1);
     post_tab_build(&p, nullptr, &tab);
@@ -512,13 +462,7 @@ extern "C" int rt_sites_placements(rt_model *m, rt_sites *s, int recompute_trans
     const double *d_HfragA = p.lane ? nullptr : grid.d_GT + (size_t)2 * R * ftab;
     if (!p.lane) {
         const size_t dfrag = (size_t)p.NT * p.KP * 128;
-        for (int r = 0; r < R; ++r) {
-            RT_TRY(rt_launch_pack_pt(p.ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab,
-                                     grid.d_G + (size_t)r * N * nn, grid.d_GT + (size_t)r * ftab));
-            RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab,
-                                    grid.d_G + (size_t)(R + r) * N * nn,
-                                    grid.d_GT + (size_t)(R + r) * ftab));
-        }
+        RT_TRY(post_fraction_pack(&p, &grid, R));
         if (query_kind == RT_OBS_DENSE)
             for (int k = 0; k < K; ++k)
                 RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, nd, d_dtab + cnt,
@@ -584,31 +528,9 @@ extern "C" int rt_sites_placements(rt_model *m, rt_sites *s, int recompute_trans
             }));
         }
         RT_HIP(hipGetLastError());
-        // 3. the weighted site sums; only what was asked for crosses PCIe
-        if (sums) {
-            hipLaunchKernelGGL(place_sums_kernel, dim3((unsigned)rows), dim3(256), 0, st, (long)nsites,
-                               (const double *)d_val, (const double *)s->d_weights,
-                               (const int *)d_status, d_sum + (size_t)q0 * NRK);
-            RT_HIP(hipGetLastError());
-        }
-        if (values)
-            for (size_t r0 = 0; r0 < rows; r0 += (size_t)PLACE_MAX_ROWS) {
-                const size_t nr = std::min<size_t>((size_t)PLACE_MAX_ROWS, rows - r0);
-                hipLaunchKernelGGL(post_transpose_kernel<32>,
-                                   dim3((unsigned)((nsites + 31) / 32), (unsigned)((nr + 31) / 32)),
-                                   dim3(256), 0, st, (long)nr, (long)nsites,
-                                   (const double *)(d_val + r0 * nsites), d_valT);
-                RT_HIP(hipGetLastError());
-                // [site][rows of the slab] into the caller's [site][nqueries][N][R][K]
-                RT_HIP(hipMemcpy2DAsync(values + (size_t)q0 * NRK + r0, (size_t)nqueries * NRK * 8,
-                                        d_valT, nr * 8, nr * 8, (size_t)nsites, hipMemcpyDeviceToHost,
-                                        st));
-            }
+        // 3. the weighted site sums and the per-site array [site][nqueries][N][R][K]
+        RT_TRY(res.chunk(&p, (size_t)q0 * NRK, rows));
     }
-    if (sums)
-        RT_HIP(hipMemcpyAsync(sums, d_sum, (size_t)nqueries * NRK * 8, hipMemcpyDeviceToHost, st));
-    if (status) RT_HIP(hipMemcpyAsync(status, d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
-    RT_HIP(hipStreamSynchronize(st));
-    RT_TRY(post_grid_result(&p, &grid));
-    return RT_OK;
+    RT_TRY(res.finish(&p, status));
+    return grid.result(&p);
 }

@@ -1,16 +1,30 @@
-// What the reads of a RESIDENT batch share (posterior.hip, branch_expect.hip, branch_profile.hip,
-// nni.hip, place.hip, sample.hip, mapping.hip).  Host: post_pass, one description of such a call -- its
-// checks, the common pieces of its scratch, the upward pass with L (and M) of every step stored
-// (the plan of the scratch and the dispatch over the kernels' template arguments: common.h);
-// post_grid, the trial lengths of the edges through the model's own exponential; for the reads
-// under a site-class mixture over the rate sets post_set_pt, post_set_grid and the mix_* kernels.
-// Device: the steps the downward kernels have in common.
+// What the reads of a RESIDENT batch share.  Host:
+//   post_pass (post_open .. post_up), one description of such a call -- its checks, the common
+//       pieces of its scratch, the upward pass with L (and M) of every step stored (the plan of the
+//       scratch and the dispatch over the kernels' template arguments: common.h): posterior.hip,
+//       branch_expect.hip, sample.hip, mapping.hip, map_states.hip and the tree-search reads
+//       branch_profile.hip, nni.hip, place.hip, spr.hip; post_internal_nodes, the mark post_up's
+//       table carries (branch_expect.hip and the four tree-search reads);
+//   post_grid, the trial lengths of the edges through the model's own exponential (the four
+//       tree-search reads), and post_fraction_*, the grid of an edge cut at fractions of its length
+//       (place.hip, spr.hip);
+//   post_set_pt, post_set_grid, post_mix and the mix_* kernels: the reads under a site-class mixture
+//       over the rate sets (branch_expect.hip; branch_profile.hip, nni.hip);
+//   post_chunk_units and post_result: the chunks a result that does not fit the scratch is made
+//       in, the weighted site sums (post_sums_kernel) and the way of the result to the caller (the
+//       four tree-search reads);
+//   post_csr_parents: the parents of a caller's CSR tree (nni.hip, spr.hip).
+// Device: the steps the downward kernels have in common; the division-free `up` pass (nni.hip,
+// place.hip, spr.hip).
 #pragma once
 
 #include "common.h"
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
+
+constexpr double POST_SCRATCH_CAP = 96e9;        // bytes of scratch one call may plan
 
 // One read of a resident batch.  post_open .. post_layout make the checks every such call makes
 // and take the common pieces from `plan`; the caller takes its own from the same plan, then
@@ -26,6 +40,7 @@ struct post_pass {
     bool lane = false, with_D = false;
     bool per_set = false;                       // an ordinary batch read under the model's rate sets:
                                                 // the caller runs the upward pass set by set (post_up_set)
+    const double *d_cw = nullptr;               // (post_mix: the class weights [K] on the device)
     int NT = 0, KS = 0, KP = 0, nops = 0;       // row tiles, k-steps, k-step pairs; schedule steps
     post_plan plan;
     size_t o_L = 0, o_M = 0, o_D = 0, o_status = 0, o_steps = 0, o_ptab = 0, o_PT = 0;
@@ -94,6 +109,14 @@ inline void post_lane_table(const rt_model *m, const rt_sites *s, const int *w_o
         if (op.obs >= 0) (*table)[(size_t)N + op.node] = op.obs;
 }
 
+// [nnodes]: 1 for a node with children, what the downward passes take as post_up's w_of_node
+inline std::vector<int32_t> post_internal_nodes(const post_pass *p)
+{
+    std::vector<int32_t> internal((size_t)p->N, 0);
+    for (int64_t v = 1; v < p->N; ++v) internal[(size_t)p->m->parent[(size_t)v]] = 1;
+    return internal;
+}
+
 // the handles and the sizes every later check and layout goes by
 // (partitioned: the call is one of those that take a partitioned batch, and nothing else --
 // nsites counts its slots, the tables are those of the model's rate sets)
@@ -153,7 +176,7 @@ inline int post_layout(post_pass *p, bool with_D, bool with_M = true)
 // (status cleared).  `draws`: the call's scratch grows with a number of draws too.
 inline int post_begin(post_pass *p, int recompute_transitions, bool draws = false)
 {
-    if ((double)p->plan.total > 96e9) {
+    if ((double)p->plan.total > POST_SCRATCH_CAP) {
         rt_set_error("%s: this %s needs %.0f GB of scratch; split the batch%s", p->who,
                      draws ? "call" : "batch", (double)p->plan.total / 1e9,
                      draws ? " or the draws" : "");
@@ -263,114 +286,165 @@ struct post_grid {
     double *d_G = nullptr, *d_GT = nullptr;
     std::vector<double> tau;
     std::vector<int32_t> qidx, info;
+
+    // what such a call asks of the model and of lengths[nnodes][npoints] (row 0 is ignored; with
+    // use_row [nnodes], every row v with use_row[v] == 0 too)
+    static int check(const post_pass *p, int recompute_transitions, int64_t npoints,
+                     const double *lengths, const unsigned char *use_row = nullptr)
+    {
+        const rt_model *m = p->m;
+        RT_REQUIRE(post_model_has_rates(m),
+                   "%s: no rates have been set (rt_model_set_rates or "
+                   "rt_model_set_rates_spectral; a model with transitions set directly has no rate "
+                   "matrix to exponentiate at another length)", p->who);
+        RT_REQUIRE(m->rates_current || recompute_transitions,
+                   "%s: the transitions were set directly after the rates "
+                   "(rt_model_set_transitions): the resident rates and lengths no longer describe them; "
+                   "set the rates again or pass recompute_transitions", p->who);
+        RT_REQUIRE(lengths, "%s: lengths is NULL", p->who);
+        RT_REQUIRE(npoints >= 1 && npoints <= RT_MAX_PROFILE_POINTS,
+                   "%s: 1..%d grid points per branch (%lld here)", p->who,
+                   RT_MAX_PROFILE_POINTS, (long long)npoints);
+        for (int64_t v = 1; v < p->N; ++v)
+            for (int64_t g = 0; g < npoints && (!use_row || use_row[v]); ++g) {
+                const double x = lengths[v * npoints + g];
+                RT_REQUIRE(std::isfinite(x) && x >= 0.0,
+                           "%s: length %d of node %lld is negative or not finite", p->who, (int)g,
+                           (long long)v);
+            }
+        return RT_OK;
+    }
+
+    // after post_layout: the orders the model's exponential takes, the grid's pieces of the scratch
+    int take(post_pass *p, int npoints)
+    {
+        const rt_model *m = p->m;
+        if (m->spectral ? p->n > 64 : p->n > RT_MAX_EXPM_STATES) {
+            rt_set_error("%s: n=%lld is beyond what the model's exponential takes", p->who,
+                         (long long)p->n);
+            return RT_ERR_UNSUPPORTED;
+        }
+        np = npoints;
+        cnt = (size_t)np * p->N;
+        const size_t nn = (size_t)p->n * p->n;
+        o_G = p->plan.take(cnt * nn * 8);
+        o_tau = p->plan.take(cnt * 8);
+        o_qidx = p->plan.take(cnt * 4);
+        o_info = p->plan.take(cnt * 8);
+        o_GT = p->lane ? p->plan.take(8) : p->plan.take((size_t)np * p->nops * p->NT * p->KP * 128 * 8);
+        return RT_OK;
+    }
+
+    // after post_begin: the tiled qidx / tau arrays and ONE launch of the route the model's own
+    // transitions take (an ignored row: the resident length at every point)
+    int launch(post_pass *p, const double *lengths, const unsigned char *use_row = nullptr)
+    {
+        const rt_model *m = p->m;
+        const int64_t n = p->n, N = p->N;
+        const size_t nn = (size_t)n * n;
+        hipStream_t st = p->st;
+        d_G = (double *)(p->base + o_G);
+        d_GT = (double *)(p->base + o_GT);
+        double *d_tau = (double *)(p->base + o_tau);
+        int32_t *d_qidx = (int32_t *)(p->base + o_qidx), *d_info = (int32_t *)(p->base + o_info);
+        tau.assign(cnt, 0.0);
+        qidx.assign(cnt, 0);
+        info.assign(2 * cnt, 0);
+        for (int k = 0; k < np; ++k)
+            for (int64_t v = 0; v < N; ++v) {
+                qidx[(size_t)k * N + v] = m->h_qidx[(size_t)v];  // (the root's: -1, a zero matrix)
+                if (v)
+                    tau[(size_t)k * N + v] = !use_row || use_row[v] ? lengths[v * np + k] : m->h_t[(size_t)v];
+            }
+        RT_HIP(hipMemcpyAsync(d_tau, tau.data(), cnt * 8, hipMemcpyHostToDevice, st));
+        RT_HIP(hipMemcpyAsync(d_qidx, qidx.data(), cnt * 4, hipMemcpyHostToDevice, st));
+        RT_HIP(hipMemsetAsync(d_info, 0, cnt * 8, st));
+        if (m->spectral)
+            RT_TRY(rt_launch_spectral(p->ctx, n, (int64_t)cnt, m->d_spec, m->d_spec + 2 * nn,
+                                      m->d_spec + nn, m->spectral_has_D ? m->d_spec + 2 * nn + n : nullptr,
+                                      d_qidx, d_tau, d_G, d_info, nullptr, 0, nullptr));
+        else
+            RT_TRY(rt_launch_expm(p->ctx, n, (int64_t)cnt, m->d_Q, d_qidx, d_tau, d_G, d_info, nullptr,
+                                  0, nullptr));
+        RT_HIP(hipMemcpyAsync(info.data(), d_info, cnt * 8, hipMemcpyDeviceToHost, st));
+        return RT_OK;
+    }
+
+    // n > 4, after post_up: P(tau)^T of every point as A fragments in step order
+    int pack(post_pass *p)
+    {
+        const size_t nn = (size_t)p->n * p->n, tab = (size_t)p->nops * p->NT * p->KP * 128;
+        for (int k = 0; k < np; ++k)
+            RT_TRY(rt_launch_pack_pt(p->ctx, (int)p->n, p->NT, p->KP, p->nops, p->d_ptab,
+                                     d_G + (size_t)k * p->N * nn, d_GT + (size_t)k * tab));
+        return RT_OK;
+    }
+
+    // after the synchronisation: an exponential the kernel gave up on (tau Q not finite) -- its
+    // rows hold nothing usable
+    int result(const post_pass *p) const
+    {
+        for (size_t j = 0; j < cnt; ++j)
+            if (info[2 * j] < 0) {
+                rt_set_error("%s: expm failed for node %lld at length %g (a non-finite entry or norm "
+                             "of tau Q)", p->who, (long long)(j % (size_t)p->N), tau[j]);
+                return RT_ERR_SINGULAR;
+            }
+        return RT_OK;
+    }
 };
 
-// what such a call asks of the model and of lengths[nnodes][npoints] (row 0 is ignored; with
-// use_row [nnodes], every row v with use_row[v] == 0 too)
-inline int post_grid_check(const post_pass *p, int recompute_transitions, int64_t npoints,
-                           const double *lengths, const unsigned char *use_row = nullptr)
+// ---- an edge cut at fractions of its length (rt_sites_placements, rt_sites_spr_scores): the grid
+// of every node v is rho_r t_v at the points 0 .. R - 1 and (1 - rho_r) t_v at R .. 2 R - 1 ----
+
+// (two checks: rt_sites_placements checks its other counts between them)
+inline int post_fraction_count(const char *who, int64_t nfractions)
+{
+    RT_REQUIRE(nfractions >= 1 && nfractions <= RT_MAX_PLACE_FRACTIONS,
+               "%s: 1..%d fractions (%lld here)", who, RT_MAX_PLACE_FRACTIONS, (long long)nfractions);
+    return RT_OK;
+}
+
+inline int post_fraction_values(const char *who, int64_t nfractions, const double *fractions)
+{
+    for (int64_t r = 0; r < nfractions; ++r)
+        RT_REQUIRE(std::isfinite(fractions[r]) && fractions[r] >= 0.0 && fractions[r] <= 1.0,
+                   "%s: fraction %d is outside [0, 1] or not finite", who, (int)r);
+    return RT_OK;
+}
+
+// lengths [nnodes][2 R + nmore] for post_grid, the further points `more` the same at every node
+// (zeros while the model has no rates: post_grid::check refuses it)
+inline std::vector<double> post_fraction_lengths(const post_pass *p, int R, const double *fractions,
+                                                 int nmore = 0, const double *more = nullptr)
 {
     const rt_model *m = p->m;
-    RT_REQUIRE(post_model_has_rates(m),
-               "%s: no rates have been set (rt_model_set_rates or "
-               "rt_model_set_rates_spectral; a model with transitions set directly has no rate "
-               "matrix to exponentiate at another length)", p->who);
-    RT_REQUIRE(m->rates_current || recompute_transitions,
-               "%s: the transitions were set directly after the rates "
-               "(rt_model_set_transitions): the resident rates and lengths no longer describe them; "
-               "set the rates again or pass recompute_transitions", p->who);
-    RT_REQUIRE(lengths, "%s: lengths is NULL", p->who);
-    RT_REQUIRE(npoints >= 1 && npoints <= RT_MAX_PROFILE_POINTS,
-               "%s: 1..%d grid points per branch (%lld here)", p->who,
-               RT_MAX_PROFILE_POINTS, (long long)npoints);
-    for (int64_t v = 1; v < p->N; ++v)
-        for (int64_t g = 0; g < npoints && (!use_row || use_row[v]); ++g) {
-            const double x = lengths[v * npoints + g];
-            RT_REQUIRE(std::isfinite(x) && x >= 0.0,
-                       "%s: length %d of node %lld is negative or not finite", p->who, (int)g,
-                       (long long)v);
+    const int np = 2 * R + nmore;
+    std::vector<double> lengths((size_t)p->N * np, 0.0);
+    if (post_model_has_rates(m))
+        for (int64_t v = 1; v < p->N; ++v) {
+            double *row = lengths.data() + (size_t)v * np;
+            const double t = m->h_t[(size_t)v];
+            for (int r = 0; r < R; ++r) {
+                row[r] = fractions[r] * t;
+                row[R + r] = (1.0 - fractions[r]) * t;
+            }
+            for (int k = 0; k < nmore; ++k) row[2 * R + k] = more[k];
         }
-    return RT_OK;
+    return lengths;
 }
 
-// after post_layout: the orders the model's exponential takes, the grid's pieces of the scratch
-inline int post_grid_take(post_pass *p, post_grid *g, int np)
-{
-    const rt_model *m = p->m;
-    if (m->spectral ? p->n > 64 : p->n > RT_MAX_EXPM_STATES) {
-        rt_set_error("%s: n=%lld is beyond what the model's exponential takes", p->who,
-                     (long long)p->n);
-        return RT_ERR_UNSUPPORTED;
-    }
-    g->np = np;
-    g->cnt = (size_t)np * p->N;
-    const size_t nn = (size_t)p->n * p->n;
-    g->o_G = p->plan.take(g->cnt * nn * 8);
-    g->o_tau = p->plan.take(g->cnt * 8);
-    g->o_qidx = p->plan.take(g->cnt * 4);
-    g->o_info = p->plan.take(g->cnt * 8);
-    g->o_GT = p->lane ? p->plan.take(8)
-                      : p->plan.take((size_t)np * p->nops * p->NT * p->KP * 128 * 8);
-    return RT_OK;
-}
-
-// after post_begin: the tiled qidx / tau arrays and ONE launch of the route the model's own
-// transitions take (an ignored row: the resident length at every point)
-inline int post_grid_launch(post_pass *p, post_grid *g, const double *lengths,
-                            const unsigned char *use_row = nullptr)
-{
-    const rt_model *m = p->m;
-    const int64_t n = p->n, N = p->N;
-    const int np = g->np;
-    const size_t cnt = g->cnt, nn = (size_t)n * n;
-    hipStream_t st = p->st;
-    g->d_G = (double *)(p->base + g->o_G);
-    g->d_GT = (double *)(p->base + g->o_GT);
-    double *d_tau = (double *)(p->base + g->o_tau);
-    int32_t *d_qidx = (int32_t *)(p->base + g->o_qidx), *d_info = (int32_t *)(p->base + g->o_info);
-    g->tau.assign(cnt, 0.0);
-    g->qidx.assign(cnt, 0);
-    g->info.assign(2 * cnt, 0);
-    for (int k = 0; k < np; ++k)
-        for (int64_t v = 0; v < N; ++v) {
-            g->qidx[(size_t)k * N + v] = m->h_qidx[(size_t)v];   // (the root's: -1, a zero matrix)
-            if (v)
-                g->tau[(size_t)k * N + v] = !use_row || use_row[v] ? lengths[v * np + k] : m->h_t[(size_t)v];
-        }
-    RT_HIP(hipMemcpyAsync(d_tau, g->tau.data(), cnt * 8, hipMemcpyHostToDevice, st));
-    RT_HIP(hipMemcpyAsync(d_qidx, g->qidx.data(), cnt * 4, hipMemcpyHostToDevice, st));
-    RT_HIP(hipMemsetAsync(d_info, 0, cnt * 8, st));
-    if (m->spectral)
-        RT_TRY(rt_launch_spectral(p->ctx, n, (int64_t)cnt, m->d_spec, m->d_spec + 2 * nn,
-                                  m->d_spec + nn, m->spectral_has_D ? m->d_spec + 2 * nn + n : nullptr,
-                                  d_qidx, d_tau, g->d_G, d_info, nullptr, 0, nullptr));
-    else
-        RT_TRY(rt_launch_expm(p->ctx, n, (int64_t)cnt, m->d_Q, d_qidx, d_tau, g->d_G, d_info, nullptr,
-                              0, nullptr));
-    RT_HIP(hipMemcpyAsync(g->info.data(), d_info, cnt * 8, hipMemcpyDeviceToHost, st));
-    return RT_OK;
-}
-
-// n > 4, after post_up: P(tau)^T of every point as A fragments in step order
-inline int post_grid_pack(post_pass *p, post_grid *g)
+// n > 4, after post_up(.., true): in the grid's own fragment piece, [point][step], P(rho t)^T at
+// the points 0 .. R - 1 and P((1 - rho) t) itself at R .. 2 R - 1
+inline int post_fraction_pack(post_pass *p, post_grid *g, int R)
 {
     const size_t nn = (size_t)p->n * p->n, tab = (size_t)p->nops * p->NT * p->KP * 128;
-    for (int k = 0; k < g->np; ++k)
+    for (int r = 0; r < R; ++r) {
         RT_TRY(rt_launch_pack_pt(p->ctx, (int)p->n, p->NT, p->KP, p->nops, p->d_ptab,
-                                 g->d_G + (size_t)k * p->N * nn, g->d_GT + (size_t)k * tab));
-    return RT_OK;
-}
-
-// after the synchronisation: an exponential the kernel gave up on (tau Q not finite) -- its
-// rows hold nothing usable
-inline int post_grid_result(const post_pass *p, const post_grid *g)
-{
-    for (size_t j = 0; j < g->cnt; ++j)
-        if (g->info[2 * j] < 0) {
-            rt_set_error("%s: expm failed for node %lld at length %g (a non-finite entry or norm "
-                         "of tau Q)", p->who, (long long)(j % (size_t)p->N), g->tau[j]);
-            return RT_ERR_SINGULAR;
-        }
+                                 g->d_G + (size_t)r * p->N * nn, g->d_GT + (size_t)r * tab));
+        RT_TRY(rt_launch_pack_p(p->ctx, (int)p->n, p->NT, p->KP, p->nops, p->d_ptab,
+                                g->d_G + (size_t)(R + r) * p->N * nn, g->d_GT + (size_t)(R + r) * tab));
+    }
     return RT_OK;
 }
 
@@ -445,9 +519,10 @@ struct post_set_grid {
     std::vector<int32_t> info, steps;
 
     // factors [nnodes][npoints] finite and >= 0 (row 0 is ignored; with use_row [nnodes], every row
-    // v with use_row[v] == 0 too)
-    static int check(const post_pass *p, int64_t npoints, const double *factors,
-                     const unsigned char *use_row = nullptr)
+    // v with use_row[v] == 0 too).  (The arguments of post_grid::check: the sets' tables follow
+    // rt_model_set_rate_sets, there is nothing to ask of recompute_transitions.)
+    static int check(const post_pass *p, int /*recompute_transitions*/, int64_t npoints,
+                     const double *factors, const unsigned char *use_row = nullptr)
     {
         RT_REQUIRE(factors, "%s: factors is NULL", p->who);
         RT_REQUIRE(npoints >= 1 && npoints <= RT_MAX_PROFILE_POINTS,
@@ -463,15 +538,15 @@ struct post_set_grid {
         return RT_OK;
     }
 
-    // after post_layout
-    int take(post_pass *p, int64_t sets, int npoints)
+    // after post_layout: every rate set the model holds
+    int take(post_pass *p, int npoints)
     {
         if (p->n > RT_MAX_EXPM_STATES) {
             rt_set_error("%s: n=%lld is beyond what the sets' exponential takes", p->who,
                          (long long)p->n);
             return RT_ERR_UNSUPPORTED;
         }
-        K = sets; np = npoints;
+        K = p->m->multi.K; np = npoints;
         cnt = (size_t)K * np * p->N;
         tab = (size_t)p->nops * p->NT * p->KP * 128;
         const size_t nn = (size_t)p->n * p->n;
@@ -486,12 +561,12 @@ struct post_set_grid {
         return RT_OK;
     }
 
-    // after post_begin; d_cw: the class weights on the device.  An ignored row: factor 1, the
-    // resident length at every point.  What the choice of the exponential's variant goes by is one
-    // set's count, whatever the number of sets that run.
-    int launch(post_pass *p, const double *d_cw, const double *factors,
-               const unsigned char *use_row = nullptr)
+    // after post_begin and post_mix::begin (p->d_cw: the class weights on the device).  An ignored
+    // row: factor 1, the resident length at every point.  What the choice of the exponential's
+    // variant goes by is one set's count, whatever the number of sets that run.
+    int launch(post_pass *p, const double *factors, const unsigned char *use_row = nullptr)
     {
+        RT_REQUIRE(p->d_cw, "%s: the class weights are not on the device yet (post_mix::begin)", p->who);
         const rt_rate_sets &r = p->m->multi;
         const int64_t N = p->N;
         hipStream_t st = p->st;
@@ -506,8 +581,8 @@ struct post_set_grid {
         info.assign(2 * cnt, 0);
         RT_HIP(hipMemcpyAsync(d_fac, fac.data(), fac.size() * 8, hipMemcpyHostToDevice, st));
         RT_HIP(hipMemsetAsync(d_info, 0, cnt * 8, st));
-        RT_TRY(rt_launch_set_grid_args(p->ctx, (int)K, np, (int)N, r.d_qidx, r.d_t, d_fac, d_cw, d_qidx,
-                                       d_tau));
+        RT_TRY(rt_launch_set_grid_args(p->ctx, (int)K, np, (int)N, r.d_qidx, r.d_t, d_fac, p->d_cw,
+                                       d_qidx, d_tau));
         RT_TRY(rt_launch_expm(p->ctx, p->n, (int64_t)cnt, r.d_Q, d_qidx, d_tau, d_G, d_info, nullptr, 0,
                               nullptr, nullptr, nullptr, (int64_t)np * N));
         RT_HIP(hipMemcpyAsync(info.data(), d_info, cnt * 8, hipMemcpyDeviceToHost, st));
@@ -628,8 +703,73 @@ mix_dead_edge_kernel(int K, int nnodes, const double *__restrict__ cw, const dou
     for (int k = 0; k < K; ++k)
         if (v > 0 && cw[k] > 0.0 && set_t[(size_t)k * nnodes + v] == 0.0) dead = 1;
     dead_edge[v] = dead;
-    tlen[v] = dead ? 0.0 : 1.0;                  // (what profile_sums_kernel goes by)
+    tlen[v] = dead ? 0.0 : 1.0;                  // (what post_sums_kernel goes by)
 }
+
+// What a tree-search read under the mixture (rt_sites_branch_profiles_mixture,
+// rt_sites_nni_scores_mixture) holds beside the single-set one: the class weights on the device,
+// the sets' P^T fragments, per set the root totals L_ik and a status word (tot_of / status_of: what
+// the MIX kernel instance of set k writes), the class posteriors and log Lambda_i.
+struct post_mix {
+    int64_t K = 0;
+    const double *cw = nullptr;                  // the caller's class weights
+    post_set_pt PT;
+    size_t o_tot = 0, o_stat = 0, o_post = 0, o_ll = 0, o_cw = 0;
+    double *d_tot = nullptr, *d_post = nullptr, *d_ll = nullptr;
+    int *d_stat = nullptr;
+
+    // after post_layout
+    int take(post_pass *p, const double *class_weights)
+    {
+        const rt_rate_sets &r = p->m->multi;
+        RT_REQUIRE(r.P_stride == p->N * p->n * p->n, "unexpected stride of the sets' transition matrices");
+        K = r.K; cw = class_weights;
+        PT.take(p, K);
+        o_tot = p->plan.take((size_t)K * p->nsites * 8);
+        o_stat = p->plan.take((size_t)K * p->nsites * 4);
+        o_post = p->plan.take((size_t)p->nsites * K * 8);
+        o_ll = p->plan.take((size_t)p->nsites * 8);
+        o_cw = p->plan.take((size_t)K * 8);
+        return RT_OK;
+    }
+    // after post_begin: the weights go up, the sets' totals and status words are cleared
+    int begin(post_pass *p)
+    {
+        PT.place(p);
+        d_tot = (double *)(p->base + o_tot); d_post = (double *)(p->base + o_post);
+        d_ll = (double *)(p->base + o_ll); d_stat = (int *)(p->base + o_stat);
+        p->d_cw = (double *)(p->base + o_cw);
+        RT_HIP(hipMemcpyAsync(p->base + o_cw, cw, (size_t)K * 8, hipMemcpyHostToDevice, p->st));
+        RT_HIP(hipMemsetAsync(d_stat, 0, (size_t)K * p->nsites * 4, p->st));
+        RT_HIP(hipMemsetAsync(d_tot, 0, (size_t)K * p->nsites * 8, p->st));
+        return RT_OK;
+    }
+    const double *P_of(const post_pass *p, int64_t k) const { return p->m->multi.d_P + k * p->m->multi.P_stride; }
+    double *tot_of(const post_pass *p, int64_t k) const { return d_tot + (size_t)k * p->nsites; }
+    int *status_of(const post_pass *p, int64_t k) const { return d_stat + (size_t)k * p->nsites; }
+    // once every set's launch is in: log Lambda_i and the status of the live sets.  (Templates,
+    // as the kernels: only a translation unit that calls them holds a copy.)
+    template <int BS = 256>
+    int post(post_pass *p)
+    {
+        hipLaunchKernelGGL(mix_post_kernel<BS>, dim3((unsigned)((p->nsites + BS - 1) / BS)), dim3(BS), 0,
+                           p->st, (int)K, (long)p->nsites, p->d_cw, (const double *)d_tot,
+                           (const int *)d_stat, d_post, d_ll, p->d_status);
+        RT_HIP(hipGetLastError());
+        return RT_OK;
+    }
+    // after post: the accumulator x [rows][site] -> values
+    template <int BS = 256>
+    int log_ratio(post_pass *p, size_t rows, int np, const int *d_dead_edge, double *x)
+    {
+        hipLaunchKernelGGL(mix_log_ratio_kernel<BS>,
+                           dim3((unsigned)((p->nsites + BS - 1) / BS), (unsigned)std::min<size_t>(rows, 1024)),
+                           dim3(BS), 0, p->st, (long)rows, np, (long)p->nsites, (const double *)d_ll,
+                           (const int *)p->d_status, d_dead_edge, x);
+        RT_HIP(hipGetLastError());
+        return RT_OK;
+    }
+};
 
 // n <= 4: one lane per site.  The observation of stream position k from the batch's lane-family
 // image (dense pairs, or one byte per leaf: a state or an allowed-set mask; passes.hip
@@ -1024,6 +1164,149 @@ post_transpose_kernel(long nrows, long nsites, const double *__restrict__ in,
     __syncthreads();
     for (int k = ty; k < 32; k += 8)
         if (s0 + k < nsites && r0 + tx < nrows) outT[(size_t)(s0 + k) * nrows + r0 + tx] = tile[tx][k];
+}
+
+// ---- the result of a tree-search read (branch_profile.hip, nni.hip, place.hip, spr.hip): the
+// kernels leave values [row][site] in the scratch, a chunk of rows at a time where all of them
+// would not fit; the caller gets sums [row] and / or values [site][row] ----
+
+// the site-weighted sum of every row, one workgroup per row: thread j adds sites j, j + BS, ... in
+// order, then the BS partial sums by halves (fixed rounding).  Sites of zero likelihood and of
+// weight 0 are skipped.  tlen (or null; rt_sites_branch_profiles: rows [node][np]): the row of an
+// edge of resident length 0 is NaN.  (A template, BS = 256, as the mix_* kernels.)
+template <int BS>
+__global__ void __launch_bounds__(BS)
+post_sums_kernel(long nsites, const double *__restrict__ values, const double *__restrict__ weights,
+                 const int *__restrict__ status, int np, const double *__restrict__ tlen,
+                 double *__restrict__ sums)
+{
+    __shared__ double part[BS];
+    const size_t row = blockIdx.x;
+    const int tid = threadIdx.x;
+    const double *x = values + row * nsites;
+    double acc = 0.0;
+    for (long i = tid; i < nsites; i += BS) {
+        const double w = weights ? weights[i] : 1.0;       // (w = 0: not -inf * 0 = NaN)
+        if (w != 0.0 && !(status[i] & RT_SITE_ZERO_PROB)) acc += w * x[i];
+    }
+    part[tid] = acc;
+    __syncthreads();
+    for (int h = BS / 2; h > 0; h >>= 1) {
+        if (tid < h) part[tid] += part[tid + h];
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    const size_t v = tlen ? row / np : 0;
+    sums[row] = (v > 0 && tlen[v] == 0.0) ? __builtin_nan("") : part[0];
+}
+
+constexpr size_t POST_CHUNK_BYTES = (size_t)4 << 30;     // result bytes of one chunk
+
+// The units (moves, queries) of one chunk of `units`: their result within POST_CHUNK_BYTES at
+// per_unit bytes each, and with `further` bytes a unit that are no result within what the plan so
+// far leaves of the scratch's cap; at most max_units (a grid's y dimension), at least one.
+// env: the variable that overrides the chunk's bytes (the tests: many chunks at small sizes).
+inline int64_t post_chunk_units(const post_plan &plan, size_t per_unit, size_t further,
+                                int64_t max_units, int64_t units, const char *env)
+{
+    size_t chunk_bytes = POST_CHUNK_BYTES;
+    if (const char *e = getenv(env)) {
+        const long long v = atoll(e);
+        if (v > 0) chunk_bytes = (size_t)v;
+    }
+    const double room = POST_SCRATCH_CAP - (double)plan.total - 4096.0;
+    const size_t fit = room > 0.0 ? (size_t)room / (per_unit + further) : 0;
+    const int64_t CH = (int64_t)std::max<size_t>(1, std::min(chunk_bytes / per_unit, fit));
+    return std::min(CH, std::max<int64_t>(1, std::min(max_units, units)));
+}
+
+struct post_result {
+    double *values, *sums;                       // the caller's [site][rows] and [rows], or null
+    size_t rows = 0, slab = 0;                   // rows of the whole result, of one transpose launch
+    size_t o_sum = 0, o_val = 0, o_valT = 0;
+    double *d_sum = nullptr, *d_val = nullptr, *d_valT = nullptr;
+
+    post_result(double *v, double *s) : values(v), sums(s) {}
+    // scratch bytes of one row: the values, and their transpose where the caller takes them
+    size_t row_bytes(const post_pass *p) const { return (size_t)p->nsites * 8 * (values ? 2 : 1); }
+    // after post_layout: the sums of all rows; then (the chunk planned with the sums in the plan)
+    // the values of one chunk and the transpose of at most max_rows of them (a grid's y dimension)
+    void take_sums(post_pass *p, size_t total_rows)
+    {
+        rows = total_rows;
+        o_sum = p->plan.take(std::max<size_t>(rows, 1) * 8);
+    }
+    void take_chunk(post_pass *p, size_t chunk_rows, size_t max_rows = ~(size_t)0)
+    {
+        slab = std::min(chunk_rows, max_rows);
+        o_val = p->plan.take(chunk_rows * p->nsites * 8);
+        o_valT = p->plan.take(values ? slab * p->nsites * 8 : 8);
+    }
+    // after post_begin
+    void place(const post_pass *p)
+    {
+        d_sum = (double *)(p->base + o_sum);
+        d_val = (double *)(p->base + o_val);
+        d_valT = (double *)(p->base + o_valT);
+    }
+    // the chunk's nrows rows at d_val are rows row0 .. of the result: their sums, and slab by slab
+    // their transpose into the caller's array; only what was asked for crosses PCIe.
+    // np, d_tlen: post_sums_kernel's.  (A template, as the kernels: only a translation unit that
+    // calls it holds a copy of them.)
+    template <int BS = 256>
+    int chunk(post_pass *p, size_t row0, size_t nrows, int np = 1, const double *d_tlen = nullptr)
+    {
+        const long nsites = (long)p->nsites;
+        if (sums) {
+            hipLaunchKernelGGL(post_sums_kernel<BS>, dim3((unsigned)nrows), dim3(BS), 0, p->st, nsites,
+                               (const double *)d_val, (const double *)p->s->d_weights,
+                               (const int *)p->d_status, np, d_tlen, d_sum + row0);
+            RT_HIP(hipGetLastError());
+        }
+        for (size_t r0 = 0; values && r0 < nrows; r0 += slab) {
+            const size_t nr = std::min(slab, nrows - r0);
+            hipLaunchKernelGGL(post_transpose_kernel<32>,
+                               dim3((unsigned)((nsites + 31) / 32), (unsigned)((nr + 31) / 32)), dim3(256),
+                               0, p->st, (long)nr, nsites, (const double *)(d_val + r0 * nsites), d_valT);
+            RT_HIP(hipGetLastError());
+            // [site][rows of the slab] into the caller's [site][rows]
+            RT_HIP(hipMemcpy2DAsync(values + row0 + r0, rows * 8, d_valT, nr * 8, nr * 8, (size_t)nsites,
+                                    hipMemcpyDeviceToHost, p->st));
+        }
+        return RT_OK;
+    }
+    // after the last chunk: the sums, the status (and log Lambda_i of a mixture) to the caller; the
+    // stream is synchronised
+    int finish(post_pass *p, int32_t *status, double *loglik = nullptr, const double *d_loglik = nullptr)
+    {
+        if (sums && rows) RT_HIP(hipMemcpyAsync(sums, d_sum, rows * 8, hipMemcpyDeviceToHost, p->st));
+        if (loglik)
+            RT_HIP(hipMemcpyAsync(loglik, d_loglik, (size_t)p->nsites * 8, hipMemcpyDeviceToHost, p->st));
+        if (status)
+            RT_HIP(hipMemcpyAsync(status, p->d_status, (size_t)p->nsites * 4, hipMemcpyDeviceToHost, p->st));
+        RT_HIP(hipStreamSynchronize(p->st));
+        return RT_OK;
+    }
+};
+
+// parent [nnodes] of a caller's tree in CSR form (the root's: -1), or what is wrong with it: every
+// node but the root is the child of exactly one node before it
+inline int post_csr_parents(int64_t nnodes, const int64_t *idx, const int64_t *ptr,
+                            std::vector<int32_t> *parent)
+{
+    RT_REQUIRE(nnodes >= 1 && ptr && (idx || nnodes == 1), "bad arguments");
+    RT_REQUIRE(ptr[0] == 0 && ptr[nnodes] == nnodes - 1, "tree_csr_indptr does not describe a tree");
+    parent->assign((size_t)nnodes, -1);
+    for (int64_t v = 0; v < nnodes; ++v) {
+        RT_REQUIRE(ptr[v + 1] >= ptr[v], "tree_csr_indptr not monotone");
+        for (int64_t e = ptr[v]; e < ptr[v + 1]; ++e) {
+            RT_REQUIRE(idx[e] > v && idx[e] < nnodes, "children not in preorder");
+            RT_REQUIRE((*parent)[(size_t)idx[e]] < 0, "node %lld is listed as a child twice",
+                       (long long)idx[e]);
+            (*parent)[(size_t)idx[e]] = (int32_t)v;
+        }
+    }
+    return RT_OK;
 }
 
 }  // namespace

@@ -33,23 +33,22 @@
 //      waves per (16-site tile, group of pruned nodes): group g walks the ops of the pruned
 //      nodes c0 + g, c0 + g + G, ... of the chunk in its own piece of the scratch;
 //      n <= 4: spr_lane_up_kernel and spr_lane_kernel, one lane per site, the same walk;
-//   3. spr_sums_kernel: the site-weighted sums per (move, fraction) in a fixed order; then, if the
-//      per-site array is asked for, its transpose to [site][move][fraction].
+//   3. post_result (post_common.h): the site-weighted sums per (move, fraction) in a fixed order;
+//      then, if the per-site array is asked for, its transpose to [site][move][fraction].
 //
 // Steps 2 (the walk) and 3 run per chunk of pruned nodes where the result of all moves would not
-// fit the scratch; a chunk never splits the moves of one pruned node.  Nothing of the batch or the
-// model is written; two calls give the same bits, chunked or not, whatever the number of groups.
+// fit the scratch (post_chunk_units); a chunk never splits the moves of one pruned node.  The
+// fraction grid (its checks, its lengths, its fragment tables) is post_fraction_*, shared with
+// place.hip.  Nothing of the batch or the model is written; two calls give the same bits, chunked
+// or not, whatever the number of groups.
 #include "common.h"
 #include "post_common.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
 namespace {
 
-constexpr size_t SPR_CHUNK_BYTES = (size_t)4 << 30;      // result bytes of one chunk of pruned nodes
-constexpr double SPR_SCRATCH_CAP = 96e9;         // (post_begin's)
 constexpr int64_t SPR_MAX_ROWS = (int64_t)1 << 21;       // rows of one transpose launch (grid y)
 constexpr size_t SPR_LEVEL_BYTES = (size_t)2 << 30;      // the level vectors of all groups
 constexpr int SPR_R = RT_MAX_PLACE_FRACTIONS;
@@ -396,31 +395,6 @@ spr_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const dou
     }
 }
 
-// one workgroup per (move, fraction), the order of profile_sums_kernel: thread j adds sites j,
-// j + 256, ... in order, then the 256 partial sums by halves (fixed rounding).  Sites of zero
-// likelihood and of weight 0 are skipped.
-__global__ void __launch_bounds__(256)
-spr_sums_kernel(long nsites, const double *__restrict__ values, const double *__restrict__ weights,
-                const int *__restrict__ status, double *__restrict__ sums)
-{
-    __shared__ double part[256];
-    const size_t row = blockIdx.x;
-    const int tid = threadIdx.x;
-    const double *x = values + row * nsites;
-    double acc = 0.0;
-    for (long i = tid; i < nsites; i += 256) {
-        const double w = weights ? weights[i] : 1.0;       // (w = 0: not -inf * 0 = NaN)
-        if (w != 0.0 && !(status[i] & RT_SITE_ZERO_PROB)) acc += w * x[i];
-    }
-    part[tid] = acc;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (tid < h) part[tid] += part[tid + h];
-        __syncthreads();
-    }
-    if (tid == 0) sums[row] = part[0];
-}
-
 // ---- the host's side: the moves and the plan of the walk ----
 
 // what the moves of one pruned node need of the tree (children after their parents, as every
@@ -600,19 +574,10 @@ extern "C" int rt_model_spr_moves(const rt_model *m, int64_t radius, int32_t *mo
 extern "C" int rt_tree_spr_moves(int64_t nnodes, const int64_t *idx, const int64_t *ptr,
                                  int64_t radius, int32_t *moves, int64_t capacity, int64_t *nmoves)
 {
-    RT_REQUIRE(nnodes >= 1 && ptr && (idx || nnodes == 1) && nmoves, "bad arguments");
-    RT_REQUIRE(ptr[0] == 0 && ptr[nnodes] == nnodes - 1, "tree_csr_indptr does not describe a tree");
+    RT_REQUIRE(nmoves, "bad arguments");
     // (the walk goes up through the parents: every node but the root has exactly one)
-    std::vector<int32_t> parent((size_t)nnodes, -1);
-    for (int64_t v = 0; v < nnodes; ++v) {
-        RT_REQUIRE(ptr[v + 1] >= ptr[v], "tree_csr_indptr not monotone");
-        for (int64_t e = ptr[v]; e < ptr[v + 1]; ++e) {
-            RT_REQUIRE(idx[e] > v && idx[e] < nnodes, "children not in preorder");
-            RT_REQUIRE(parent[(size_t)idx[e]] < 0, "node %lld is listed as a child twice",
-                       (long long)idx[e]);
-            parent[(size_t)idx[e]] = (int32_t)v;
-        }
-    }
+    std::vector<int32_t> parent;
+    RT_TRY(post_csr_parents(nnodes, idx, ptr, &parent));
     return spr_list(nnodes, idx, ptr, parent.data(), radius, moves, capacity, nmoves);
 }
 
@@ -625,11 +590,8 @@ extern "C" int rt_sites_spr_scores(rt_model *m, rt_sites *s, int recompute_trans
     RT_TRY(post_open(&p, who, m, s));
     const int64_t n = p.n, N = p.N, nsites = p.nsites;
     RT_REQUIRE(fractions, "%s: fractions is NULL", who);
-    RT_REQUIRE(nfractions >= 1 && nfractions <= RT_MAX_PLACE_FRACTIONS,
-               "%s: 1..%d fractions (%lld here)", who, RT_MAX_PLACE_FRACTIONS, (long long)nfractions);
-    for (int64_t r = 0; r < nfractions; ++r)
-        RT_REQUIRE(std::isfinite(fractions[r]) && fractions[r] >= 0.0 && fractions[r] <= 1.0,
-                   "%s: fraction %d is outside [0, 1] or not finite", who, (int)r);
+    RT_TRY(post_fraction_count(who, nfractions));
+    RT_TRY(post_fraction_values(who, nfractions, fractions));
     const int R = (int)nfractions, np = 2 * R;
     // the moves
     spr_tree tree(N, m->indices.data(), m->indptr.data(), m->parent.data());
@@ -644,27 +606,19 @@ extern "C" int rt_sites_spr_scores(rt_model *m, rt_sites *s, int recompute_trans
     RT_REQUIRE(nplan < INT32_MAX / 4, "%s: too many moves (a plan of %lld ops)", who, (long long)nplan);
     RT_TRY(post_layout(&p, true));
     // the grid of every node: rho_r t_v, (1 - rho_r) t_v
-    std::vector<double> lengths((size_t)N * np, 0.0);
-    if (post_model_has_rates(m))
-        for (int64_t v = 1; v < N; ++v) {
-            double *row = lengths.data() + (size_t)v * np;
-            const double t = m->h_t[(size_t)v];
-            for (int r = 0; r < R; ++r) {
-                row[r] = fractions[r] * t;
-                row[R + r] = (1.0 - fractions[r]) * t;
-            }
-        }
-    RT_TRY(post_grid_check(&p, recompute_transitions, np, lengths.data()));
+    const std::vector<double> lengths = post_fraction_lengths(&p, R, fractions);
+    RT_TRY(post_grid::check(&p, recompute_transitions, np, lengths.data()));
     post_plan &plan = p.plan;
     post_grid grid;                              // (alive until the synchronisation below)
-    RT_TRY(post_grid_take(&p, &grid, np));
+    post_result res(values, sums);
+    RT_TRY(grid.take(&p, np));
     const int cnt = p.lane ? (int)N : p.nops;    // slots of the tables
     const int D = 1 + *std::max_element(tree.depth.begin(), tree.depth.end()), nlevels = 3 * D;
     const size_t o_tab = plan.take((size_t)4 * cnt * 4);
     const size_t o_cut = plan.take(((size_t)N + 1) * 16);
     const size_t ftab = p.lane ? 0 : (size_t)p.nops * p.NT * p.KP * 128;
     const size_t o_PA = plan.take(p.lane ? 8 : ftab * 8);
-    const size_t o_sum = plan.take((size_t)std::max<int64_t>(nmoves, 1) * R * 8);
+    res.take_sums(&p, (size_t)nmoves * R);
     // the groups of pruned nodes that walk side by side: enough workgroups to fill the device at
     // few sites, their level vectors within SPR_LEVEL_BYTES
     const size_t vec = p.lane ? (size_t)n * nsites * 8 : (size_t)s->nblocks * p.NT * 256 * 8;
@@ -674,17 +628,11 @@ extern "C" int rt_sites_spr_scores(rt_model *m, rt_sites *s, int recompute_trans
     G = std::max<int64_t>(1, std::min<int64_t>(G, N - 1));
     const size_t o_S = plan.take((size_t)G * nlevels * vec);
     const size_t o_ops = plan.take((size_t)std::max<int64_t>(nplan, 1) * sizeof(spr_op));
-    // the chunks of pruned nodes: their result (and its transpose) within the chunk size and the cap
-    const size_t per_move = (size_t)R * nsites * 8 * (values ? 2 : 1);
-    size_t chunk_bytes = SPR_CHUNK_BYTES;
-    if (const char *e = getenv("RAOTEH_SPR_CHUNK_BYTES")) {      // (tests: many chunks at small sizes)
-        const long long v = atoll(e);
-        if (v > 0) chunk_bytes = (size_t)v;
-    }
-    const double room = SPR_SCRATCH_CAP - (double)plan.total - 4096.0;
-    if (room < (double)chunk_bytes) chunk_bytes = room > 0.0 ? (size_t)room : 0;
-    const int64_t chunk_moves = std::max<int64_t>(1, (int64_t)(chunk_bytes / per_move));
-    std::vector<int32_t> chunks(1, 1);           // the first pruned node of every chunk, then nnodes
+    // the chunks of pruned nodes: the moves of a chunk by post_chunk_units (the rows go through the
+    // transpose in slabs: no bound from a grid), a chunk never splits the moves of one pruned node
+    const int64_t chunk_moves = post_chunk_units(plan, R * res.row_bytes(&p), 0, INT64_MAX, nmoves,
+                                                 "RAOTEH_SPR_CHUNK_BYTES");
+    std::vector<int32_t> chunks(1, 1);          // the first pruned node of every chunk, then nnodes
     int64_t max_moves = 1;
     for (int64_t c = 1, c0 = 1; c <= N; ++c)
         if (c == N || (c > c0 && first[(size_t)c + 1] - first[(size_t)c0] > chunk_moves)) {
@@ -693,9 +641,7 @@ extern "C" int rt_sites_spr_scores(rt_model *m, rt_sites *s, int recompute_trans
             c0 = c;
         }
     chunks.push_back((int32_t)N);
-    const size_t chunk_rows = (size_t)max_moves * R;
-    const size_t o_val = plan.take(chunk_rows * nsites * 8);
-    const size_t o_valT = plan.take(values ? std::min<size_t>(chunk_rows, SPR_MAX_ROWS) * nsites * 8 : 8);
+    res.take_chunk(&p, (size_t)max_moves * R, (size_t)SPR_MAX_ROWS);
     // (the cap is checked here, before the host makes the plan)
     RT_TRY(post_begin(&p, recompute_transitions));
     // the plan of the walk (slots: by node here; n > 4 renumbers by step below)
@@ -719,15 +665,14 @@ extern "C" int rt_sites_spr_scores(rt_model *m, rt_sites *s, int recompute_trans
     }
     hipStream_t st = p.st;
     unsigned char *base = p.base;
-    double *d_val = (double *)(base + o_val), *d_valT = (double *)(base + o_valT);
-    double *d_sum = (double *)(base + o_sum), *d_S = (double *)(base + o_S);
+    res.place(&p);
+    double *d_val = res.d_val, *d_S = (double *)(base + o_S);
     double *d_PA = (double *)(base + o_PA);
     int *d_tab = (int *)(base + o_tab);
     int4 *d_cut = (int4 *)(base + o_cut), *d_ops = (int4 *)(base + o_ops);
     int *d_status = p.d_status;
-    std::vector<int32_t> internal((size_t)N, 0);
-    for (int64_t v = 1; v < N; ++v) internal[(size_t)m->parent[(size_t)v]] = 1;
-    RT_TRY(post_grid_launch(&p, &grid, lengths.data()));
+    const std::vector<int32_t> internal = post_internal_nodes(&p);
+    RT_TRY(grid.launch(&p, lengths.data()));
     RT_TRY(post_up(&p, internal.data(), true));
     std::vector<int32_t> tab;
     post_tab_build(&p, nullptr, &tab);
@@ -745,7 +690,6 @@ extern "C" int rt_sites_spr_scores(rt_model *m, rt_sites *s, int recompute_trans
     RT_HIP(hipMemcpyAsync(d_cut, cut.data(), cut.size() * 4, hipMemcpyHostToDevice, st));
     if (!ops.empty())
         RT_HIP(hipMemcpyAsync(d_ops, ops.data(), ops.size() * sizeof(spr_op), hipMemcpyHostToDevice, st));
-    const size_t nn = (size_t)n * n;
     if (p.lane) {
         const int *d_ptab = p.d_ptab;
         RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
@@ -758,16 +702,9 @@ extern "C" int rt_sites_spr_scores(rt_model *m, rt_sites *s, int recompute_trans
             return RT_OK;
         }));
     } else {
-        // the fragment tables: the resident P beside the resident P^T; in the grid's own piece,
-        // [point][step], P(rho t)^T at the points 0 .. R - 1 and P((1 - rho) t) at R .. 2 R - 1
+        // the fragment tables: the resident P beside the resident P^T; the grid's
         RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab, m->d_P, d_PA));
-        for (int r = 0; r < R; ++r) {
-            RT_TRY(rt_launch_pack_pt(p.ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab,
-                                     grid.d_G + (size_t)r * N * nn, grid.d_GT + (size_t)r * ftab));
-            RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab,
-                                    grid.d_G + (size_t)(R + r) * N * nn,
-                                    grid.d_GT + (size_t)(R + r) * ftab));
-        }
+        RT_TRY(post_fraction_pack(&p, &grid, R));
         const rt_sites *x = p.x;
         RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
             constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
@@ -817,30 +754,9 @@ extern "C" int rt_sites_spr_scores(rt_model *m, rt_sites *s, int recompute_trans
             }));
         }
         RT_HIP(hipGetLastError());
-        // 3. the weighted site sums; only what was asked for crosses PCIe
-        if (sums) {
-            hipLaunchKernelGGL(spr_sums_kernel, dim3((unsigned)rows), dim3(256), 0, st, (long)nsites,
-                               (const double *)d_val, (const double *)s->d_weights,
-                               (const int *)d_status, d_sum + (size_t)mvA * R);
-            RT_HIP(hipGetLastError());
-        }
-        if (values)
-            for (size_t r0 = 0; r0 < rows; r0 += (size_t)SPR_MAX_ROWS) {
-                const size_t nr = std::min<size_t>((size_t)SPR_MAX_ROWS, rows - r0);
-                hipLaunchKernelGGL(post_transpose_kernel<32>,
-                                   dim3((unsigned)((nsites + 31) / 32), (unsigned)((nr + 31) / 32)),
-                                   dim3(256), 0, st, (long)nr, (long)nsites,
-                                   (const double *)(d_val + r0 * nsites), d_valT);
-                RT_HIP(hipGetLastError());
-                // [site][rows of the slab] into the caller's [site][nmoves][R]
-                RT_HIP(hipMemcpy2DAsync(values + (size_t)mvA * R + r0, (size_t)nmoves * R * 8, d_valT,
-                                        nr * 8, nr * 8, (size_t)nsites, hipMemcpyDeviceToHost, st));
-            }
+        // 3. the weighted site sums and the per-site array [site][nmoves][R]
+        RT_TRY(res.chunk(&p, (size_t)mvA * R, rows));
     }
-    if (sums && nmoves)
-        RT_HIP(hipMemcpyAsync(sums, d_sum, (size_t)nmoves * R * 8, hipMemcpyDeviceToHost, st));
-    if (status) RT_HIP(hipMemcpyAsync(status, d_status, (size_t)nsites * 4, hipMemcpyDeviceToHost, st));
-    RT_HIP(hipStreamSynchronize(st));
-    RT_TRY(post_grid_result(&p, &grid));
-    return RT_OK;
+    RT_TRY(res.finish(&p, status));
+    return grid.result(&p);
 }

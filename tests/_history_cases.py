@@ -488,7 +488,7 @@ def flagged_reads(row):
 
 def read_outcome(s, name, recompute=False):
     """'ok' or the error code the header documents for this read in state s.  Every refusal below
-    is decided on the host before anything is launched (post_open, post_grid_check, the RT_REQUIRE
+    is decided on the host before anything is launched (post_open, post_grid::check, the RT_REQUIRE
     lines at the head of each entry point, sites_multi_ready, the wrapper's own ValueErrors)."""
     row, c = s.row, s.cur
     r = READ[name]

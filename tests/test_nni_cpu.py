@@ -99,6 +99,13 @@ def test_moves_capacity_and_bad_trees():
     bad[0] = 0                                   # a child that is not after its parent
     assert call(ta.nnodes, bad.ctypes.data_as(p64), ptr, None, 0,
                 ctypes.byref(count)) == _lib.RT_ERR_INVALID
+    # a child listed twice leaves another node without a parent: refused before the moves are
+    # counted through the parents
+    twice = ta.indices.copy()
+    twice[1] = twice[0]
+    assert call(ta.nnodes, twice.ctypes.data_as(p64), ptr, None, 0,
+                ctypes.byref(count)) == _lib.RT_ERR_INVALID
+    assert 'twice' in _lib.last_error()
 
 
 # ---- nni_apply ------------------------------------------------------------------------------
