@@ -1096,6 +1096,70 @@ int rt_sites_branch_profiles_mixture(rt_model *model, rt_sites *sites, int recom
 int rt_sites_nni_scores_mixture(rt_model *model, rt_sites *sites, int recompute_transitions,
             const double *class_weights, int64_t npoints, const double *factors, double *values,
             double *sums, double *loglik, int32_t *status);
+/* rt_sites_spr_scores_mixture: rt_sites_spr_scores of an ORDINARY resident batch under the same
+ * mixture.  Moves, their order, radius, fractions and the output shapes are those of
+ * rt_sites_spr_scores and rt_model_spr_moves; class_weights as above (a set with c_k = 0 is never
+ * run and never read).
+ *     values          f64[nsites][nmoves][nfractions]:
+ *                     log sum_k c_k L_ik(tree after the move at fractions[r]) - log Lambda_i, the
+ *                     sum in set order; 0 at a site whose Lambda_i is not positive
+ *                     (RT_SITE_ZERO_PROB; it adds nothing to the sums); -inf where the mixture
+ *                     likelihood after the move is 0 at a live site
+ *     sums            f64[nmoves][nfractions], loglik f64[nsites], status: exactly those of
+ *                     rt_sites_nni_scores_mixture
+ *   Under set k the cut edge above y has the lengths fractions[r] t[k][y] and
+ *   (1 - fractions[r]) t[k][y] under Q[k][node_q[y]]: the fractions are factors of the resident
+ *   length already, nothing new is parametrised.  The pruned subtree keeps set k's resident
+ *   matrix on its own edge.  The call is exact in every term and nothing is divided by L_ik: a set
+ *   dead on the resident tree and alive after a move adds its term; a resident t[k][y] == 0 gives
+ *   no NaN row, as in rt_sites_spr_scores.
+ *   Each output may be NULL.  Synchronous; two calls return the same bits, chunked or not, whatever
+ *   the number of groups of pruned nodes.  Nothing resident changes.  recompute_transitions as in
+ *   the other mixture reads.  Where the result of all moves does not fit, the pruned nodes go in
+ *   chunks as in rt_sites_spr_scores (RAOTEH_SPR_CHUNK_BYTES), the sets' passes again per chunk.
+ *   RT_ERR_INVALID: no rate sets; a batch of another model; bad class weights; fractions NULL,
+ *   nfractions outside 1..RT_MAX_PLACE_FRACTIONS, a fraction outside [0, 1] or not finite; too
+ *   many moves.  RT_ERR_SINGULAR: an exponential failed.  RT_ERR_UNSUPPORTED: a partitioned batch;
+ *   what rt_sites_spr_scores refuses ("rescale", a generic-kernel batch, deep trees, nnodes < 2);
+ *   more than 96 GB of scratch.                                              */
+int rt_sites_spr_scores_mixture(rt_model *model, rt_sites *sites, int recompute_transitions,
+            const double *class_weights, int64_t radius, int64_t nfractions,
+            const double *fractions, double *values, double *sums, double *loglik,
+            int32_t *status);
+/* rt_sites_placements_mixture: rt_sites_placements of an ORDINARY resident batch under the same
+ * mixture.  Queries, their kinds (RT_OBS_DENSE, RT_OBS_STATE; RT_OBS_MASK is not taken), the grid
+ * limits (RT_MAX_PLACE_FRACTIONS, RT_MAX_PLACE_PENDANT, 2 nfractions + npendant <= 32) and the
+ * output shapes are those of rt_sites_placements; class_weights as above.
+ *     pendant_scale   f64[K], finite and >= 0, or NULL for ones: under set k the query at pendant
+ *                     point tau_j hangs on an edge of length pendant_scale[k] * tau_j under the
+ *                     cut edge's rate matrix of set k, Q[k][node_q[v]].  Where the classes differ
+ *                     in Q (Q_k = r_k Q over a shared t) ones is right; where they share Q and
+ *                     differ in t (t_k = r_k t) pass r_k, so that the new edge is stretched as
+ *                     the resident ones are.  The entry of a set with c_k = 0 is not read.
+ *     values          f64[nsites][nqueries][nnodes][nfractions][npendant]:
+ *                     log sum_k c_k L_ik(tree with the query placed) - log Lambda_i, the sum in set
+ *                     order; the root's rows are 0; 0 at a site whose Lambda_i is not positive;
+ *                     -inf where the mixture likelihood with the query placed is 0 at a live site
+ *     sums            f64[nqueries][nnodes][nfractions][npendant], loglik f64[nsites], status:
+ *                     exactly those of rt_sites_nni_scores_mixture
+ *   Under set k the cut edge above v has the lengths fractions[r] t[k][v] and
+ *   (1 - fractions[r]) t[k][v] under Q[k][node_q[v]].  Exact in every term, nothing is divided by
+ *   L_ik; a resident t[k][v] == 0 gives no NaN row.  Each output may be NULL.  Synchronous; two
+ *   calls return the same bits, chunked or not.  Nothing resident changes.  recompute_transitions
+ *   as in the other mixture reads.  Where the result of all queries does not fit, the queries go
+ *   in chunks as in rt_sites_placements (RAOTEH_PLACE_CHUNK_BYTES); every chunk runs the sets'
+ *   passes and fields again (the scratch holds one set's field at a time).
+ *   RT_ERR_INVALID: no rate sets; a batch of another model; bad class weights; nqueries < 1; a
+ *   query_kind that is none of the three; queries, fractions or pendant NULL; a count out of
+ *   range; a fraction outside [0, 1], a pendant length or a pendant_scale entry that is negative
+ *   or not finite.  RT_ERR_SINGULAR: an exponential failed.  RT_ERR_UNSUPPORTED: RT_OBS_MASK
+ *   queries; a partitioned batch; what rt_sites_placements refuses ("rescale", a generic-kernel
+ *   batch, deep trees, nnodes < 2); more than 96 GB of scratch.               */
+int rt_sites_placements_mixture(rt_model *model, rt_sites *sites, int recompute_transitions,
+            const double *class_weights, int64_t nqueries, int query_kind, const void *queries,
+            int64_t nfractions, const double *fractions, int64_t npendant, const double *pendant,
+            const double *pendant_scale, double *values, double *sums, double *loglik,
+            int32_t *status);
 
 /* ---- 3. multi-GPU: one process per GPU, RCCL over xGMI ------------------- */
 

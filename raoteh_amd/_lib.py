@@ -187,6 +187,11 @@ SIGNATURES = {
                                                  _p_f64, _p_f64, _p_f64, _p_i32]),
     'rt_sites_nni_scores_mixture': (c_int, [c_void_p, c_void_p, c_int, _p_f64, c_int64, _p_f64,
                                             _p_f64, _p_f64, _p_f64, _p_i32]),
+    'rt_sites_spr_scores_mixture': (c_int, [c_void_p, c_void_p, c_int, _p_f64, c_int64, c_int64,
+                                            _p_f64, _p_f64, _p_f64, _p_f64, _p_i32]),
+    'rt_sites_placements_mixture': (c_int, [c_void_p, c_void_p, c_int, _p_f64, c_int64, c_int,
+                                            c_void_p, c_int64, _p_f64, c_int64, _p_f64, _p_f64,
+                                            _p_f64, _p_f64, _p_f64, _p_i32]),
     'rt_comm_available': (c_int, []),
     'rt_comm_unique_id': (c_int, [POINTER(c_ubyte)]),
     'rt_comm_init': (c_int, [c_void_p, c_int, c_int, POINTER(c_ubyte)]),

@@ -815,6 +815,8 @@ extern "C" int rt_model_set_rate_sets(rt_model *m, int64_t K, const double *Q, i
     if (K != r.K) r.epoch += 1;
     r.K = K;
     r.nq = nq;
+    r.h_node_q.assign((size_t)N, -1);
+    for (int64_t v = 1; v < N; ++v) r.h_node_q[(size_t)v] = node_q ? (int32_t)node_q[v] : 0;
     return rate_sets_run_expm(m);
 }
 

@@ -253,25 +253,35 @@ namespace {
 __global__ void __launch_bounds__(256)
 set_grid_args_kernel(int K, int np, int nnodes, const int *__restrict__ set_qidx,
                      const double *__restrict__ set_t, const double *__restrict__ fac,
-                     const double *__restrict__ cw, int *__restrict__ qidx, double *__restrict__ tau)
+                     const double *__restrict__ cw, int nabs, const double *__restrict__ abs_tau,
+                     const double *__restrict__ abs_scale, int *__restrict__ qidx,
+                     double *__restrict__ tau)
 {
     const long j = (long)blockIdx.x * 256 + threadIdx.x;
     if (j >= (long)K * np * nnodes) return;
     const int v = (int)(j % nnodes), g = (int)(j / nnodes % np), k = (int)(j / nnodes / np);
     const bool run = v > 0 && cw[k] > 0.0;
     qidx[j] = run ? set_qidx[(size_t)k * nnodes + v] : -1;
-    tau[j] = run ? fac[(size_t)v * np + g] * set_t[(size_t)k * nnodes + v] : 0.0;
+    double x = 0.0;
+    if (run) {
+        // (the last nabs points: an absolute length, the set's scale times the point's)
+        if (g >= np - nabs) x = abs_scale[k] * abs_tau[g - (np - nabs)];
+        else x = fac[(size_t)v * np + g] * set_t[(size_t)k * nnodes + v];
+    }
+    tau[j] = x;
 }
 
 }  // namespace
 
 int rt_launch_set_grid_args(rt_ctx *ctx, int K, int np, int nnodes, const int32_t *d_set_qidx,
                             const double *d_set_t, const double *d_fac, const double *d_cw,
+                            int nabs, const double *d_abs_tau, const double *d_abs_scale,
                             int32_t *d_qidx, double *d_tau)
 {
     const long cnt = (long)K * np * nnodes;
     hipLaunchKernelGGL(set_grid_args_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream,
-                       K, np, nnodes, (const int *)d_set_qidx, d_set_t, d_fac, d_cw, (int *)d_qidx, d_tau);
+                       K, np, nnodes, (const int *)d_set_qidx, d_set_t, d_fac, d_cw, nabs, d_abs_tau,
+                       d_abs_scale, (int *)d_qidx, d_tau);
     RT_HIP(hipGetLastError());
     return RT_OK;
 }

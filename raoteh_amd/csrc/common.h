@@ -181,6 +181,8 @@ struct rt_rate_sets {
     double *d_Q = nullptr;          // [K][nq][n][n]
     int32_t *d_qidx = nullptr;      // [K][nnodes], set k's entries + k * nq (root: -1)
     double *d_t = nullptr;          // [K][nnodes]
+    std::vector<int32_t> h_node_q;  // [nnodes] the rate matrix of every node within a set, shared by
+                                    // the sets (root: -1); the host's copy of what d_qidx holds
     int32_t *d_info = nullptr;      // [K][nnodes][2]
     int32_t *d_step_of_node = nullptr;  // [K][nnodes], set k's entries + k * steps per set
     double *d_P = nullptr;          // [K][nnodes][n][n]

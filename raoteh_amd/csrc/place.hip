@@ -33,6 +33,13 @@
 // them would not fit the scratch (post_chunk_units).  The fraction grid (its checks, its lengths,
 // its fragment tables) is post_fraction_*, shared with spr.hip.  Nothing of the batch or the model
 // is written; two calls give the same bits, chunked or not.
+//
+// rt_sites_placements_mixture: the same placements of an ORDINARY batch under a site-class mixture
+// over the model's K rate sets -- the cut edge at fractions of every set's own resident length, the
+// pendant edge at pendant_scale[k] tau under the set's rate matrix; the kernels' MIX forms once per
+// set and chunk of queries into one accumulator, the root scaled by the class weight instead of
+// 1 / L_i; the field holds one set at a time.  One host body (place_read, at the end) serves both
+// calls.
 #include "common.h"
 #include "post_common.h"
 
@@ -52,11 +59,28 @@ __device__ __forceinline__ double place_value(double ratio, bool zero)
     return ratio > 0.0 ? log(ratio) : -__builtin_inf();
 }
 
+// What the MIX kernel instances (rt_sites_placements_mixture: one launch per rate set k of weight
+// ck > 0 and chunk of queries, in set order on one stream) take beside the plain ones' arguments:
+// the class weight the root is scaled by instead of 1 / L_ik, where L_ik goes (post_mix::tot_of),
+// and whether the set is the first to run (it stores its terms, the later ones add to them).  It is
+// an argument of the MIX instances ALONE (a parameter pack that is empty otherwise): the plain
+// instances keep their argument lists and with them the parent's instruction streams.
+struct place_mix {
+    double ck;
+    double *root_tot;
+    int first;
+};
+struct place_plain {};
+__device__ __forceinline__ place_plain place_args() { return {}; }
+__device__ __forceinline__ place_mix place_args(place_mix a) { return a; }
+
 // n > 4.  steps as in nni_kernel (steps[i].w: the node has children); PfragT: [step] A fragments
 // of the resident P^T; GfragT: [fraction][step] those of P(rho t)^T; GfragA: [fraction][step]
 // those of P((1 - rho) t) itself; Uarr: the `up` vectors; Farr: the field,
 // [step * R + fraction] in the layout of L and M.
-template <int NT, int KS>
+// MIX: the set's fragments; down_up_pass's MIX form (the root scaled by ck, L_ik to root_tot, the
+// status word the set's own), so the field is c_k times the unnormalised one.
+template <int NT, int KS, bool MIX = false, class... MX>
 __global__ void __launch_bounds__(64 * NT)
 place_field_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT,
                    const double *__restrict__ GfragA, int R, int nops,
@@ -64,8 +88,10 @@ place_field_kernel(const double *__restrict__ PfragT, const double *__restrict__
                    const double *__restrict__ Larr, const double *__restrict__ Marr,
                    double *__restrict__ Uarr, const double *__restrict__ obs, int K,
                    const double *__restrict__ root_w, int n, double *__restrict__ Farr,
-                   int *__restrict__ status, long nsites, long nblocks)
+                   int *__restrict__ status, long nsites, long nblocks, MX... mix)
 {
+    static_assert(sizeof...(MX) == (MIX ? 1 : 0), "place_mix: the MIX instance's alone");
+    [[maybe_unused]] const auto mx = place_args(mix...);
     constexpr int KP = (KS + 1) / 2;
     __shared__ double xb[NT * 4 * 64];
     __shared__ double lb[NT * 4 * 64];
@@ -83,8 +109,13 @@ place_field_kernel(const double *__restrict__ PfragT, const double *__restrict__
     constexpr size_t ASTRIDE = (size_t)NT * KP * 128;
     const double *og = obs + (size_t)blk * K * (KP * 128) + lane * 2;
     // 1. the `up` pass (nni_kernel's)
-    down_up_pass<NT, KS>(true, xb, red, tab, PfragT, nops, steps, Larr, Marr, Uarr, og, root_w, live,
-                         m, lane, blk, nblocks, writer, status, site);
+    if constexpr (MIX)
+        down_up_pass<NT, KS, true>(true, xb, red, tab, PfragT, nops, steps, Larr, Marr, Uarr, og, root_w,
+                                   live, m, lane, blk, nblocks, writer, status, site, mx.ck,
+                                   mx.root_tot);
+    else
+        down_up_pass<NT, KS>(true, xb, red, tab, PfragT, nops, steps, Larr, Marr, Uarr, og, root_w, live,
+                             m, lane, blk, nblocks, writer, status, site);
     // 2. the field of every edge: A_v and L_v staged once, two products per fraction
     double a[2 * KP];
     for (int i = nops - 2; i >= 0; --i) {
@@ -196,13 +227,19 @@ place_query_kernel(int dense, const void *__restrict__ queries, const double *__
 // halves of `sums` as in nni_kernel (wave 0 adds the waves in order and stores the ratio while
 // the next edge fills the other half).  out: [q][node][fraction][pendant][site]; the root's rows
 // are not written.  (PLACE_BLOCK = 8: 64 VGPRs of vectors; see profiles/placements_resource_usage.txt)
-template <int NT>
+// MIX: the field and the pendant vectors are the set's; the dot product is the RAW term
+// c_k L_ik(tree with the query placed), stored by the first running set and added to by the later
+// ones (the same lane of the same workgroup, launches in order: a fixed sum); no logs here and no
+// look at the status -- mix_log_ratio_kernel's once the sets are in.
+template <int NT, bool MIX = false, class... MX>
 __global__ void __launch_bounds__(64 * NT)
 place_score_kernel(int nops, int R, int K, int QC, int nd, const int4 *__restrict__ steps,
                    const int *__restrict__ dslot, const double *__restrict__ Farr,
                    const double *__restrict__ Harr, double *__restrict__ out,
-                   const int *__restrict__ status, int N, long nsites, long nblocks)
+                   const int *__restrict__ status, int N, long nsites, long nblocks, MX... mix)
 {
+    static_assert(sizeof...(MX) == (MIX ? 1 : 0), "place_mix: the MIX instance's alone");
+    [[maybe_unused]] const auto mx = place_args(mix...);
     __shared__ double sums[2][PLACE_BLOCK][NT][16];
     const int lane = threadIdx.x & 63;
     const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -245,13 +282,16 @@ place_score_kernel(int nops, int R, int K, int QC, int nd, const int4 *__restric
                     for (int j = 0; j < cnt; ++j) {
                         const int pair = j0 + j;
                         const int q = pair / K, k = pair - q * K;
-                        out[((size_t)q * NRK + ((size_t)v * R + r) * K + k) * nsites + site] =
-                            down_total<NT>(sums[par][j], lane);
+                        double *x = out + ((size_t)q * NRK + ((size_t)v * R + r) * K + k) * nsites + site;
+                        const double t = down_total<NT>(sums[par][j], lane);
+                        if constexpr (MIX) *x = mx.first ? t : __dadd_rn(*x, t);
+                        else *x = t;
                     }
                 par ^= 1;
             }
         }
     }
+    if constexpr (MIX) return;
     // the block's ratios -> values, by all waves: lane group g of the workgroup takes the rows
     // g, g + 4 NT, ... of its site (the barrier: wave 0's stores are visible)
     __syncthreads();
@@ -274,7 +314,9 @@ place_score_kernel(int nops, int R, int K, int QC, int nd, const int4 *__restric
 // expm(Q tau) (the same address in every lane: the scalar path); Farr [node * R + fraction][N][site];
 // dnode[v] the distinct matrix of node v, rep[d] the node that stands for it.  make: the first
 // chunk makes the upward pass, the `up` pass and the field, later ones find them.
-template <int N>
+// MIX: P and G of the set, make != 0 in every launch (the scratch is the current set's); the terms
+// as in place_score_kernel.
+template <int N, bool MIX = false, class... MX>
 __global__ void __launch_bounds__(256)
 place_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const double *__restrict__ G,
                   int R, int K, const int *__restrict__ parent, const int *__restrict__ node_k,
@@ -283,8 +325,10 @@ place_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const d
                   int Kobs, int block_sites, const double *__restrict__ root_w,
                   double *__restrict__ Larr, double *__restrict__ Marr, double *__restrict__ Uarr,
                   double *__restrict__ Farr, int dense, const void *__restrict__ queries, int QC,
-                  int make, double *__restrict__ out, int *__restrict__ status)
+                  int make, double *__restrict__ out, int *__restrict__ status, MX... mix)
 {
+    static_assert(sizeof...(MX) == (MIX ? 1 : 0), "place_mix: the MIX instance's alone");
+    [[maybe_unused]] const auto mx = place_args(mix...);
     const long site = (long)blockIdx.x * 256 + threadIdx.x;
     if (site >= nsites) return;
     const post_tab tab(tabp, nnodes);
@@ -292,8 +336,14 @@ place_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const d
     if (make)
         lane_up<N, true>(nnodes, nsites, site, P, parent, node_k, obs, compact, Kobs, block_sites, Larr,
                          Marr);
-    const bool zero = lane_up_pass<N>(make != 0, nnodes, nsites, site, P, parent, node_k, tab, obs,
-                                      compact, Kobs, block_sites, root_w, Larr, Marr, Uarr, status);
+    [[maybe_unused]] bool zero;
+    if constexpr (MIX)
+        zero = lane_up_pass<N, true>(make != 0, nnodes, nsites, site, P, parent, node_k, tab, obs,
+                                     compact, Kobs, block_sites, root_w, Larr, Marr, Uarr, status,
+                                     mx.ck, mx.root_tot);
+    else
+        zero = lane_up_pass<N>(make != 0, nnodes, nsites, site, P, parent, node_k, tab, obs, compact,
+                               Kobs, block_sites, root_w, Larr, Marr, Uarr, status);
     if (make)
         for (int v = 1; v < nnodes; ++v) {
             const int p = parent[v];
@@ -358,25 +408,35 @@ place_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const d
                         double t = 0.0;
 #pragma unroll
                         for (int b = 0; b < N; ++b) t += Farr[idx(v * R + r, b)] * h[b];
-                        out[((size_t)q * NRK + ((size_t)v * R + r) * K + k) * nsites + site] =
-                            place_value(t, zero);
+                        double *o = out + ((size_t)q * NRK + ((size_t)v * R + r) * K + k) * nsites + site;
+                        if constexpr (MIX) *o = mx.first ? t : __dadd_rn(*o, t);
+                        else *o = place_value(t, zero);
                     }
                 }
             }
     }
 }
 
-}  // namespace
-
-extern "C" int rt_sites_placements(rt_model *m, rt_sites *s, int recompute_transitions,
-                                   int64_t nqueries, int query_kind, const void *queries,
-                                   int64_t nfractions, const double *fractions, int64_t npendant,
-                                   const double *pendant, double *values, double *sums,
-                                   int32_t *status)
+// Both reads.  MIX = false: the grid of the model's own exponential (post_grid: 2 R + K points per
+// node), the upward pass, the `up` pass and the field once, then the queries in chunks.  MIX = true:
+// the sets' grid (post_set_grid: the factors rho_r, 1 - rho_r of every set's own length and K
+// ABSOLUTE points pendant_scale[k] tau_j per set) and the sets' fragment tables once; then per chunk
+// of queries, once per rate set of positive class weight over the one L / M / U / field / h scratch,
+// the set's upward pass (post_up_set), the MIX field (the root scaled by c_k), the set's pendant
+// vectors and the MIX scores, which add c_k L_ik(query placed) into ONE accumulator in set order;
+// post_mix turns it into the values, the root's rows are cleared afterwards.  node_q is shared by
+// the sets: the distinct matrices in use (dnode, rep) are found once.
+template <bool MIX>
+int place_read(const char *who, rt_model *m, rt_sites *s, int recompute_transitions,
+               const double *class_weights, int64_t nqueries, int query_kind, const void *queries,
+               int64_t nfractions, const double *fractions, int64_t npendant, const double *pendant,
+               const double *pendant_scale, double *values, double *sums, double *loglik,
+               int32_t *status)
 {
-    const char *who = "rt_sites_placements";
+    using grid_t = std::conditional_t<MIX, post_set_grid, post_grid>;
     post_pass p;                                 // (alive until the synchronisation below)
     RT_TRY(post_open(&p, who, m, s));
+    if (MIX) RT_TRY(post_class_weights(who, m, class_weights));
     const int64_t n = p.n, N = p.N, nsites = p.nsites;
     RT_REQUIRE(nqueries >= 1, "%s: at least one query (%lld here)", who, (long long)nqueries);
     if (query_kind == RT_OBS_MASK) {
@@ -395,23 +455,36 @@ extern "C" int rt_sites_placements(rt_model *m, rt_sites *s, int recompute_trans
     for (int64_t k = 0; k < npendant; ++k)
         RT_REQUIRE(std::isfinite(pendant[k]) && pendant[k] >= 0.0,
                    "%s: pendant length %d is negative or not finite", who, (int)k);
+    for (int64_t k = 0; MIX && pendant_scale && k < m->multi.K; ++k)
+        RT_REQUIRE(std::isfinite(pendant_scale[k]) && pendant_scale[k] >= 0.0,
+                   "%s: pendant_scale[%lld] is negative or not finite", who, (long long)k);
     const int R = (int)nfractions, K = (int)npendant, np = 2 * R + K;
+    p.per_set = MIX;
     RT_TRY(post_layout(&p, true));
-    // the grid of every node: rho_r t_v, (1 - rho_r) t_v, tau_k
-    const std::vector<double> lengths = post_fraction_lengths(&p, R, fractions, K, pendant);
-    RT_TRY(post_grid::check(&p, recompute_transitions, np, lengths.data()));
+    // the grid of every node: rho_r t_v, (1 - rho_r) t_v, tau_k (MIX: factors, the pendant points
+    // absolute)
+    const std::vector<double> lengths = MIX ? post_set_fraction_factors(&p, R, fractions, K)
+                                            : post_fraction_lengths(&p, R, fractions, K, pendant);
+    RT_TRY(grid_t::check(&p, recompute_transitions, np, lengths.data()));
     const int64_t NRK = N * R * K;
     RT_REQUIRE(NRK < (int64_t)1 << 31, "%s: too many placements per query", who);
     post_plan &plan = p.plan;
-    post_grid grid;                              // (alive until the synchronisation below)
+    grid_t grid;                                 // (alive until the synchronisation below)
+    post_mix mix;
+    post_set_fractions setfrac;
     post_result res(values, sums);
-    RT_TRY(grid.take(&p, np));
+    if constexpr (MIX) RT_TRY(grid.take(&p, np, K));
+    else RT_TRY(grid.take(&p, np));
+    if (MIX) RT_TRY(mix.take(&p, class_weights));
+    const int64_t nsets = MIX ? mix.K : 1;
     // the distinct rate matrices in use: d of every node, the node that stands for d
     std::vector<int32_t> dnode((size_t)N, -1), rep;
     {
+        const std::vector<int32_t> &node_q = MIX ? m->multi.h_node_q : m->h_qidx;
+        RT_REQUIRE((int64_t)node_q.size() == N, "%s: the model's rate matrix indices are missing", who);
         std::vector<int32_t> d_of_q;
         for (int64_t v = 1; v < N; ++v) {
-            const int64_t qi = m->h_qidx[(size_t)v];
+            const int64_t qi = node_q[(size_t)v];
             if (qi < 0) continue;
             if ((int64_t)d_of_q.size() <= qi) d_of_q.resize((size_t)qi + 1, -1);
             if (d_of_q[(size_t)qi] < 0) {
@@ -440,15 +513,16 @@ extern "C" int rt_sites_placements(rt_model *m, rt_sites *s, int recompute_trans
     res.take_chunk(&p, (size_t)CH * NRK, (size_t)PLACE_MAX_ROWS);
     RT_TRY(post_begin(&p, recompute_transitions));
     res.place(&p);
+    if (MIX) RT_TRY(mix.begin(&p));
     hipStream_t st = p.st;
     unsigned char *base = p.base;
     double *d_val = res.d_val, *d_F = (double *)(base + o_F), *d_H = (double *)(base + o_H);
     int *d_tab = (int *)(base + o_tab), *d_dtab = (int *)(base + o_dtab);
     void *d_q = (void *)(base + o_q);
-    int *d_status = p.d_status;
     const std::vector<int32_t> internal = post_internal_nodes(&p);
-    RT_TRY(grid.launch(&p, lengths.data()));
-    RT_TRY(post_up(&p, internal.data(), true));
+    if constexpr (MIX) RT_TRY(grid.launch(&p, lengths.data(), nullptr, pendant, pendant_scale));
+    else RT_TRY(grid.launch(&p, lengths.data()));
+    RT_TRY(post_up(&p, internal.data(), !MIX));
     std::vector<int32_t> tab, dtab((size_t)cnt + nd, -1);
     post_tab_build(&p, nullptr, &tab);
     for (int j = 0; j < cnt; ++j) dtab[(size_t)j] = dnode[(size_t)(p.lane ? j : p.x->ops[(size_t)j].node)];
@@ -456,51 +530,98 @@ extern "C" int rt_sites_placements(rt_model *m, rt_sites *s, int recompute_trans
     RT_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
     RT_HIP(hipMemcpyAsync(d_dtab, dtab.data(), dtab.size() * 4, hipMemcpyHostToDevice, st));
     const size_t nn = (size_t)n * n;
-    // n > 4: the fragment tables in the grid's own piece, [point][step]: P(rho t)^T at the points
-    // 0 .. R - 1, P((1 - rho) t) at R .. 2 R - 1, and expm(Q_d tau_k) as [k][d] from point 2 R on
+    const int dense = query_kind == RT_OBS_DENSE;
+    // n > 4: the fragment tables in the grid's own piece.  Plain, [point][step]: P(rho t)^T at the
+    // points 0 .. R - 1, P((1 - rho) t) at R .. 2 R - 1, and expm(Q_d tau_k) as [k][d] from point
+    // 2 R on.  MIX: the fraction tables of every set (post_set_fractions: [half][set][fraction][step])
+    // and behind them expm(Q[set][d] s_set tau_k) as [set][k][d], each by one launch over a table
+    // that spans the sets.
     const size_t ftab = p.lane ? 0 : (size_t)p.nops * p.NT * p.KP * 128;
-    const double *d_HfragA = p.lane ? nullptr : grid.d_GT + (size_t)2 * R * ftab;
+    const size_t dfrag = p.lane ? 0 : (size_t)p.NT * p.KP * 128;
+    std::vector<int32_t> htab;                   // (feeds an asynchronous copy)
     if (!p.lane) {
-        const size_t dfrag = (size_t)p.NT * p.KP * 128;
-        RT_TRY(post_fraction_pack(&p, &grid, R));
-        if (query_kind == RT_OBS_DENSE)
-            for (int k = 0; k < K; ++k)
-                RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, nd, d_dtab + cnt,
-                                        grid.d_G + (size_t)(2 * R + k) * N * nn,
-                                        grid.d_GT + (size_t)2 * R * ftab + (size_t)k * nd * dfrag));
-        // the field, once
+        if constexpr (MIX) {
+            RT_TRY(mix.PT.pack(&p));
+            RT_TRY(setfrac.pack(&p, &grid, R));
+            if (dense) {
+                int *d_htab = (int *)(base + grid.o_tab) + (size_t)2 * nsets * R * p.nops;
+                htab.resize((size_t)nsets * K * nd);
+                for (int64_t k = 0; k < nsets; ++k)
+                    for (int j = 0; j < K; ++j)
+                        for (int d = 0; d < nd; ++d)
+                            htab[(size_t)((k * K + j) * nd + d)] =
+                                (int32_t)((k * np + 2 * R + j) * N + rep[(size_t)d]);
+                RT_HIP(hipMemcpyAsync(d_htab, htab.data(), htab.size() * 4, hipMemcpyHostToDevice, st));
+                RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, (int)htab.size(), d_htab, grid.d_G,
+                                        grid.d_GT + (size_t)2 * nsets * R * ftab));
+            }
+        } else {
+            RT_TRY(post_fraction_pack(&p, &grid, R));
+            if (dense)
+                for (int k = 0; k < K; ++k)
+                    RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, nd, d_dtab + cnt,
+                                            grid.d_G + (size_t)(2 * R + k) * N * nn,
+                                            grid.d_GT + (size_t)2 * R * ftab + (size_t)k * nd * dfrag));
+        }
+    }
+    // what set k's launches read and write (plain: the model's own, the batch's status)
+    struct set_view {
+        const double *P, *G, *PT, *GT, *GA, *HA;
+        int *stat;
+        place_mix mx;
+    };
+    auto view_of = [&](int64_t k, int first_set) {
+        set_view v = {m->d_P, grid.d_G, p.d_PT, grid.d_GT, grid.d_GT + (size_t)R * ftab,
+                      p.lane ? nullptr : grid.d_GT + (size_t)2 * R * ftab, p.d_status,
+                      {1.0, nullptr, first_set}};
+        if constexpr (MIX) {
+            v.P = mix.P_of(&p, k); v.G = grid.G_of_set(&p, k); v.PT = mix.PT.of_set(k);
+            v.GT = p.lane ? nullptr : setfrac.T_of_set(k);
+            v.GA = p.lane ? nullptr : setfrac.A_of_set(k);
+            v.HA = p.lane ? nullptr : grid.d_GT + (size_t)2 * nsets * R * ftab + (size_t)k * K * nd * dfrag;
+            v.stat = mix.status_of(&p, k);
+            v.mx = {class_weights[k], mix.tot_of(&p, k), first_set};
+        }
+        return v;
+    };
+    // n > 4: the upward pass (MIX: under set k), the `up` pass and the field
+    auto field = [&](int64_t k) -> int {
+        const set_view v = view_of(k, 0);
         const rt_sites *x = p.x;
+        if (MIX) RT_TRY(post_up_set(&p, k, nullptr));
         RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
             constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
-            hipLaunchKernelGGL((place_field_kernel<NT, KS>), dim3((unsigned)x->nblocks), dim3(64 * NT), 0,
-                               st, (const double *)p.d_PT, (const double *)grid.d_GT,
-                               (const double *)(grid.d_GT + (size_t)R * ftab), R, p.nops,
-                               (const int4 *)p.d_steps, (const int *)d_tab, (const double *)p.d_L,
-                               (const double *)p.d_M, p.d_D, (const double *)x->d_obs, (int)x->nobs,
-                               (const double *)m->d_root, (int)n, d_F, d_status, (long)x->nsites,
-                               (long)x->nblocks);
+            auto launch = [&](auto kernel, auto... mx) {
+                hipLaunchKernelGGL(kernel, dim3((unsigned)x->nblocks), dim3(64 * NT), 0, st, v.PT, v.GT,
+                                   v.GA, R, p.nops, (const int4 *)p.d_steps, (const int *)d_tab,
+                                   (const double *)p.d_L, (const double *)p.d_M, p.d_D,
+                                   (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
+                                   (int)n, d_F, v.stat, (long)x->nsites, (long)x->nblocks, mx...);
+            };
+            if constexpr (MIX) launch(place_field_kernel<NT, KS, true, place_mix>, v.mx);
+            else launch(place_field_kernel<NT, KS>);
             return RT_OK;
         }));
         RT_HIP(hipGetLastError());
-    }
-    const int dense = query_kind == RT_OBS_DENSE;
-    for (int64_t q0 = 0; q0 < nqueries; q0 += CH) {
-        const int QC = (int)std::min<int64_t>(CH, nqueries - q0);
-        const size_t rows = (size_t)QC * NRK;
-        RT_HIP(hipMemcpyAsync(d_q, (const unsigned char *)queries + (size_t)q0 * q_bytes,
-                              (size_t)QC * q_bytes, hipMemcpyHostToDevice, st));
-        RT_HIP(hipMemsetAsync(d_val, 0, rows * nsites * 8, st));       // (the root's rows)
+        return RT_OK;
+    };
+    // the QC queries at d_q against the field (n <= 4: `make` first makes the passes and the field)
+    auto score = [&](int64_t k, int QC, int make, int first_set) -> int {
+        const set_view v = view_of(k, first_set);
         if (p.lane) {
             const int *d_ptab = p.d_ptab;
             RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
-                hipLaunchKernelGGL((place_lane_kernel<decltype(nv)::value>),
-                                   dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)N,
-                                   (long)nsites, (const double *)m->d_P, (const double *)grid.d_G, R, K,
-                                   d_ptab, d_ptab + N, (const int *)d_tab, (const int *)d_dtab,
-                                   (const int *)(d_dtab + cnt), nd, (const void *)s->d_obs,
-                                   s->compact_states, (int)s->nobs, s->block_sites,
-                                   (const double *)m->d_root, p.d_L, p.d_M, p.d_D, d_F, dense,
-                                   (const void *)d_q, QC, q0 == 0 ? 1 : 0, d_val, d_status);
+                auto launch = [&](auto kernel, auto... mx) {
+                    hipLaunchKernelGGL(kernel, dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st,
+                                       (int)N, (long)nsites, v.P, v.G, R, K, d_ptab, d_ptab + N,
+                                       (const int *)d_tab, (const int *)d_dtab,
+                                       (const int *)(d_dtab + cnt), nd, (const void *)s->d_obs,
+                                       s->compact_states, (int)s->nobs, s->block_sites,
+                                       (const double *)m->d_root, p.d_L, p.d_M, p.d_D, d_F, dense,
+                                       (const void *)d_q, QC, make, d_val, v.stat, mx...);
+                };
+                if constexpr (MIX) launch(place_lane_kernel<decltype(nv)::value, true, place_mix>, v.mx);
+                else launch(place_lane_kernel<decltype(nv)::value>);
                 return RT_OK;
             }));
         } else {
@@ -509,8 +630,7 @@ extern "C" int rt_sites_placements(rt_model *m, rt_sites *s, int recompute_trans
                 constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
                 hipLaunchKernelGGL((place_query_kernel<NT, KS>),
                                    dim3((unsigned)x->nblocks, (unsigned)QC), dim3(64 * NT), 0, st, dense,
-                                   (const void *)d_q, d_HfragA,
-                                   (const double *)(grid.d_G + (size_t)2 * R * N * nn),
+                                   (const void *)d_q, v.HA, v.G + (size_t)2 * R * N * nn,
                                    (const int *)(d_dtab + cnt), nd, K, QC, (int)N, (int)n, d_H,
                                    (long)x->nsites, (long)x->nblocks);
                 return RT_OK;
@@ -518,19 +638,77 @@ extern "C" int rt_sites_placements(rt_model *m, rt_sites *s, int recompute_trans
             RT_HIP(hipGetLastError());
             RT_TRY(post_dispatch<1, 8>(p.NT, [&](auto nt) {
                 constexpr int NT = decltype(nt)::value;
-                hipLaunchKernelGGL((place_score_kernel<NT>),
-                                   dim3((unsigned)x->nblocks,
-                                        (unsigned)(((size_t)QC * K + PLACE_BLOCK - 1) / PLACE_BLOCK)),
-                                   dim3(64 * NT), 0, st, p.nops, R, K, QC, nd, (const int4 *)p.d_steps,
-                                   (const int *)d_dtab, (const double *)d_F, (const double *)d_H, d_val,
-                                   (const int *)d_status, (int)N, (long)x->nsites, (long)x->nblocks);
+                auto launch = [&](auto kernel, auto... mx) {
+                    hipLaunchKernelGGL(kernel,
+                                       dim3((unsigned)x->nblocks,
+                                            (unsigned)(((size_t)QC * K + PLACE_BLOCK - 1) / PLACE_BLOCK)),
+                                       dim3(64 * NT), 0, st, p.nops, R, K, QC, nd,
+                                       (const int4 *)p.d_steps, (const int *)d_dtab, (const double *)d_F,
+                                       (const double *)d_H, d_val, (const int *)v.stat, (int)N,
+                                       (long)x->nsites, (long)x->nblocks, mx...);
+                };
+                if constexpr (MIX) launch(place_score_kernel<NT, true, place_mix>, v.mx);
+                else launch(place_score_kernel<NT>);
                 return RT_OK;
             }));
         }
         RT_HIP(hipGetLastError());
+        return RT_OK;
+    };
+    if (!MIX && !p.lane) RT_TRY(field(0));       // the field, once
+    for (int64_t q0 = 0; q0 < nqueries; q0 += CH) {
+        const int QC = (int)std::min<int64_t>(CH, nqueries - q0);
+        const size_t rows = (size_t)QC * NRK;
+        RT_HIP(hipMemcpyAsync(d_q, (const unsigned char *)queries + (size_t)q0 * q_bytes,
+                              (size_t)QC * q_bytes, hipMemcpyHostToDevice, st));
+        RT_HIP(hipMemsetAsync(d_val, 0, rows * nsites * 8, st));       // (the root's rows)
+        // the pass; MIX: set by set, the field holds one set at a time (a set of weight zero is
+        // never live: not run, never read)
+        int first_set = 1;
+        for (int64_t k = 0; k < nsets; ++k) {
+            if (MIX && !(class_weights[k] > 0.0)) continue;
+            if (MIX && !p.lane) RT_TRY(field(k));
+            RT_TRY(score(k, QC, MIX || q0 == 0 ? 1 : 0, first_set));
+            first_set = 0;
+        }
+        if constexpr (MIX) {
+            if (q0 == 0) RT_TRY(mix.post(&p));   // (log Lambda_i, the status)
+            if (values || sums) {
+                RT_TRY(mix.log_ratio(&p, rows, K, nullptr, d_val));
+                // the root's rows: log(0) there, 0 by the definition
+                RT_HIP(hipMemset2DAsync(d_val, (size_t)NRK * nsites * 8, 0, (size_t)R * K * nsites * 8,
+                                        (size_t)QC, st));
+            }
+        }
         // 3. the weighted site sums and the per-site array [site][nqueries][N][R][K]
         RT_TRY(res.chunk(&p, (size_t)q0 * NRK, rows));
     }
-    RT_TRY(res.finish(&p, status));
+    RT_TRY(res.finish(&p, status, loglik, mix.d_ll));
     return grid.result(&p);
+}
+
+}  // namespace
+
+extern "C" int rt_sites_placements(rt_model *m, rt_sites *s, int recompute_transitions,
+                                   int64_t nqueries, int query_kind, const void *queries,
+                                   int64_t nfractions, const double *fractions, int64_t npendant,
+                                   const double *pendant, double *values, double *sums,
+                                   int32_t *status)
+{
+    return place_read<false>("rt_sites_placements", m, s, recompute_transitions, nullptr, nqueries,
+                             query_kind, queries, nfractions, fractions, npendant, pendant, nullptr,
+                             values, sums, nullptr, status);
+}
+
+extern "C" int rt_sites_placements_mixture(rt_model *m, rt_sites *s, int recompute_transitions,
+                                           const double *class_weights, int64_t nqueries,
+                                           int query_kind, const void *queries, int64_t nfractions,
+                                           const double *fractions, int64_t npendant,
+                                           const double *pendant, const double *pendant_scale,
+                                           double *values, double *sums, double *loglik,
+                                           int32_t *status)
+{
+    return place_read<true>("rt_sites_placements_mixture", m, s, recompute_transitions, class_weights,
+                            nqueries, query_kind, queries, nfractions, fractions, npendant, pendant,
+                            pendant_scale, values, sums, loglik, status);
 }

@@ -9,7 +9,8 @@
 //       tree-search reads), and post_fraction_*, the grid of an edge cut at fractions of its length
 //       (place.hip, spr.hip);
 //   post_set_pt, post_set_grid, post_mix and the mix_* kernels: the reads under a site-class mixture
-//       over the rate sets (branch_expect.hip; branch_profile.hip, nni.hip);
+//       over the rate sets (branch_expect.hip; branch_profile.hip, nni.hip, place.hip, spr.hip), and
+//       post_set_fractions, the fraction grid of every set (place.hip, spr.hip);
 //   post_chunk_units and post_result: the chunks a result that does not fit the scratch is made
 //       in, the weighted site sums (post_sums_kernel) and the way of the result to the caller (the
 //       four tree-search reads);
@@ -62,9 +63,13 @@ int rt_sample_states_enqueue(post_pass *p, uint64_t seed, uint64_t first_draw, i
 
 // branch_profile.hip: the arguments of the rate sets' trial exponentials, [set][point][node] -- set
 // k's edge above v at fac[v][point] times its resident length under the set's own rate matrix; the
-// root and the sets of weight zero: no matrix (-1: a zero matrix, no exponential runs)
+// root and the sets of weight zero: no matrix (-1: a zero matrix, no exponential runs).  The last
+// nabs of the np points are ABSOLUTE: set k's argument at point np - nabs + j is
+// abs_scale[k] * abs_tau[j] at every node, not a multiple of the resident length
+// (rt_sites_placements_mixture: the pendant edge); nabs = 0: the two tables are not read.
 int rt_launch_set_grid_args(rt_ctx *ctx, int K, int np, int nnodes, const int32_t *d_set_qidx,
                             const double *d_set_t, const double *d_fac, const double *d_cw,
+                            int nabs, const double *d_abs_tau, const double *d_abs_scale,
                             int32_t *d_qidx, double *d_tau);
 
 namespace {
@@ -507,11 +512,14 @@ struct post_set_pt {
 // trial lengths under the rate sets, given as factors[nnodes][npoints] of every set's own resident
 // lengths: post_grid over the sets' d_Q / d_qidx / d_t -- P_kv(factor t_kv) of every set, point and
 // node [set][point][node][n][n] in ONE launch of the sets' exponential, and for n > 4 their
-// transposes as A fragments [set][point][step].  (The host vectors feed asynchronous copies:
-// alive until the stream is synchronised.)
+// transposes as A fragments [set][point][step].  With nabs > 0 the last nabs points are absolute
+// lengths abs_scale[k] * abs_tau[j], the same at every node (rt_launch_set_grid_args).  (The host
+// vectors feed asynchronous copies: alive until the stream is synchronised.)
 struct post_set_grid {
     int64_t K = 0;
-    int np = 0;
+    int np = 0, nabs = 0;
+    size_t o_abs = 0;
+    std::vector<double> abs;                     // abs_tau [nabs], then abs_scale [K]
     size_t cnt = 0, tab = 0;                     // K np nnodes matrices; doubles of one step table
     size_t o_G = 0, o_tau = 0, o_qidx = 0, o_info = 0, o_fac = 0, o_GT = 0, o_tab = 0;
     double *d_G = nullptr, *d_GT = nullptr;
@@ -538,15 +546,15 @@ struct post_set_grid {
         return RT_OK;
     }
 
-    // after post_layout: every rate set the model holds
-    int take(post_pass *p, int npoints)
+    // after post_layout: every rate set the model holds (npoints counts the absolute points)
+    int take(post_pass *p, int npoints, int nabsolute = 0)
     {
         if (p->n > RT_MAX_EXPM_STATES) {
             rt_set_error("%s: n=%lld is beyond what the sets' exponential takes", p->who,
                          (long long)p->n);
             return RT_ERR_UNSUPPORTED;
         }
-        K = p->m->multi.K; np = npoints;
+        K = p->m->multi.K; np = npoints; nabs = nabsolute;
         cnt = (size_t)K * np * p->N;
         tab = (size_t)p->nops * p->NT * p->KP * 128;
         const size_t nn = (size_t)p->n * p->n;
@@ -558,13 +566,15 @@ struct post_set_grid {
         o_fac = plan.take((size_t)p->N * np * 8);
         o_GT = p->lane ? plan.take(8) : plan.take((size_t)K * np * tab * 8);
         o_tab = plan.take((size_t)K * np * p->nops * 4);
+        if (nabs) o_abs = plan.take((size_t)(nabs + K) * 8);
         return RT_OK;
     }
 
     // after post_begin and post_mix::begin (p->d_cw: the class weights on the device).  An ignored
     // row: factor 1, the resident length at every point.  What the choice of the exponential's
     // variant goes by is one set's count, whatever the number of sets that run.
-    int launch(post_pass *p, const double *factors, const unsigned char *use_row = nullptr)
+    int launch(post_pass *p, const double *factors, const unsigned char *use_row = nullptr,
+               const double *abs_tau = nullptr, const double *abs_scale = nullptr)
     {
         RT_REQUIRE(p->d_cw, "%s: the class weights are not on the device yet (post_mix::begin)", p->who);
         const rt_rate_sets &r = p->m->multi;
@@ -581,8 +591,15 @@ struct post_set_grid {
         info.assign(2 * cnt, 0);
         RT_HIP(hipMemcpyAsync(d_fac, fac.data(), fac.size() * 8, hipMemcpyHostToDevice, st));
         RT_HIP(hipMemsetAsync(d_info, 0, cnt * 8, st));
+        const double *d_abs = nullptr;
+        if (nabs) {                              // (abs_scale null: ones)
+            abs.assign(abs_tau, abs_tau + nabs);
+            for (int64_t k = 0; k < K; ++k) abs.push_back(abs_scale ? abs_scale[k] : 1.0);
+            d_abs = (const double *)(p->base + o_abs);
+            RT_HIP(hipMemcpyAsync(p->base + o_abs, abs.data(), abs.size() * 8, hipMemcpyHostToDevice, st));
+        }
         RT_TRY(rt_launch_set_grid_args(p->ctx, (int)K, np, (int)N, r.d_qidx, r.d_t, d_fac, p->d_cw,
-                                       d_qidx, d_tau));
+                                       nabs, d_abs, d_abs ? d_abs + nabs : nullptr, d_qidx, d_tau));
         RT_TRY(rt_launch_expm(p->ctx, p->n, (int64_t)cnt, r.d_Q, d_qidx, d_tau, d_G, d_info, nullptr, 0,
                               nullptr, nullptr, nullptr, (int64_t)np * N));
         RT_HIP(hipMemcpyAsync(info.data(), d_info, cnt * 8, hipMemcpyDeviceToHost, st));
@@ -623,6 +640,56 @@ struct post_set_grid {
             }
         return RT_OK;
     }
+};
+
+// An edge cut at fractions under the rate sets (rt_sites_spr_scores_mixture,
+// rt_sites_placements_mixture): the set grid of 2 R + nmore points per node, the factors rho_r at
+// 0 .. R - 1 and 1 - rho_r at R .. 2 R - 1 of every set's own resident length; the nmore further
+// points are the grid's absolute ones (factor 1, not read).  factors: [nnodes][2 R + nmore] for
+// post_set_grid::launch.
+inline std::vector<double> post_set_fraction_factors(const post_pass *p, int R, const double *fractions,
+                                                     int nmore = 0)
+{
+    const int np = 2 * R + nmore;
+    std::vector<double> fac((size_t)p->N * np, 1.0);
+    for (int64_t v = 0; v < p->N; ++v)
+        for (int r = 0; r < R; ++r) {
+            fac[(size_t)(v * np + r)] = v ? fractions[r] : 0.0;
+            fac[(size_t)(v * np + R + r)] = v ? 1.0 - fractions[r] : 0.0;
+        }
+    return fac;
+}
+
+// n > 4, after post_up: the fraction fragment tables of EVERY set in the set grid's own fragment
+// piece by one rt_launch_pack_pt and one rt_launch_pack_p over step tables that span the sets
+// (post_fraction_pack is the single-set form): [half][set][fraction][step], P(rho t)^T in the first
+// half, P((1 - rho) t) itself in the second.
+struct post_set_fractions {
+    int R = 0;
+    const post_set_grid *g = nullptr;
+
+    int pack(post_pass *p, post_set_grid *grid, int nfractions)
+    {
+        g = grid; R = nfractions;
+        RT_REQUIRE(g->np >= 2 * R, "%s: the set grid holds %d points, fewer than 2 x %d", p->who, g->np, R);
+        int *d_tab = (int *)(p->base + g->o_tab);
+        const int64_t K = g->K, half = K * R * p->nops;
+        std::vector<int32_t> &steps = grid->steps;
+        steps.resize((size_t)(2 * half));
+        for (int h = 0; h < 2; ++h)
+            for (int64_t k = 0; k < K; ++k)
+                for (int r = 0; r < R; ++r)
+                    for (int i = 0; i < p->nops; ++i)
+                        steps[(size_t)(h * half + (k * R + r) * p->nops + i)] =
+                            (int32_t)((k * g->np + h * R + r) * p->N + p->step_node[(size_t)i]);
+        RT_HIP(hipMemcpyAsync(d_tab, steps.data(), steps.size() * 4, hipMemcpyHostToDevice, p->st));
+        RT_TRY(rt_launch_pack_pt(p->ctx, (int)p->n, p->NT, p->KP, (int)half, d_tab, g->d_G, g->d_GT));
+        return rt_launch_pack_p(p->ctx, (int)p->n, p->NT, p->KP, (int)half, d_tab + half, g->d_G,
+                                g->d_GT + (size_t)K * R * g->tab);
+    }
+    // set k's [fraction][step] tables of P(rho t)^T and of P((1 - rho) t)
+    const double *T_of_set(int64_t k) const { return g->d_GT + (size_t)k * R * g->tab; }
+    const double *A_of_set(int64_t k) const { return g->d_GT + (size_t)(g->K + k) * R * g->tab; }
 };
 
 // per site, over the K root totals tot [K][nsites] (L_ik; set k live: c_k > 0 and L_ik > 0): the

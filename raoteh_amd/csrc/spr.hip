@@ -41,6 +41,12 @@
 // fraction grid (its checks, its lengths, its fragment tables) is post_fraction_*, shared with
 // place.hip.  Nothing of the batch or the model is written; two calls give the same bits, chunked
 // or not, whatever the number of groups.
+//
+// rt_sites_spr_scores_mixture: the same scores of an ORDINARY batch under a site-class mixture over
+// the model's K rate sets, the cut edge at fractions of every set's own resident length -- the
+// kernels' MIX forms once per set and chunk into one accumulator, the root scaled by the class
+// weight instead of 1 / L_i; the plan of the walk is the same for every set.  One host body
+// (spr_read, at the end) serves both calls.
 #include "common.h"
 #include "post_common.h"
 
@@ -82,14 +88,18 @@ static_assert(sizeof(spr_op) == 48, "three int4 per op");
 // the pruned node c on the device: {slot of c, first op, one past the last op, first move}
 // (entry nnodes: the number of moves)
 
-// n > 4: the `up` pass alone, for every group of spr_kernel to find
-template <int NT, int KS>
+// n > 4: the `up` pass alone, for every group of spr_kernel to find.  MIX
+// (rt_sites_spr_scores_mixture, one launch per rate set k of weight ck > 0 and chunk, after the
+// set's upward pass): down_up_pass's MIX form -- the root scaled by ck, L_ik to root_tot[site], the
+// status word the set's own.
+template <int NT, int KS, bool MIX = false>
 __global__ void __launch_bounds__(64 * NT)
 spr_up_kernel(const double *__restrict__ PfragT, int nops, const int4 *__restrict__ steps,
               const int *__restrict__ tabp, const double *__restrict__ Larr,
               const double *__restrict__ Marr, double *__restrict__ Uarr,
               const double *__restrict__ obs, int K, const double *__restrict__ root_w, int n,
-              int *__restrict__ status, long nsites, long nblocks)
+              int *__restrict__ status, long nsites, long nblocks, double ck,
+              double *__restrict__ root_tot)
 {
     constexpr int KP = (KS + 1) / 2;
     __shared__ double xb[NT * 4 * 64];
@@ -104,8 +114,8 @@ spr_up_kernel(const double *__restrict__ PfragT, int nops, const int4 *__restric
 #pragma unroll
     for (int r = 0; r < 4; ++r) live[r] = 16 * m + 4 * r + (lane >> 4) < n;
     const double *og = obs + (size_t)blk * K * (KP * 128) + lane * 2;
-    down_up_pass<NT, KS>(true, xb, red, tab, PfragT, nops, steps, Larr, Marr, Uarr, og, root_w, live,
-                         m, lane, blk, nblocks, writer, status, site);
+    down_up_pass<NT, KS, MIX>(true, xb, red, tab, PfragT, nops, steps, Larr, Marr, Uarr, og, root_w,
+                              live, m, lane, blk, nblocks, writer, status, site, ck, root_tot);
 }
 
 // n > 4, one workgroup per (tile, group).  steps as in nni_kernel; PfragT / PfragA: [step] A
@@ -113,7 +123,15 @@ spr_up_kernel(const double *__restrict__ PfragT, int nops, const int4 *__restric
 // [fraction][step] those of P((1 - rho) t); Uarr: the `up` vectors of spr_up_kernel; S: the level
 // vectors, [group][level] in the layout of L and M; cut, ops: the plan; out
 // [move - mvA][fraction][site] for the moves of the pruned nodes cA .. cB - 1.
-template <int NT, int KS>
+// MIX (one launch per rate set of weight > 0 and chunk, against the set's P, P^T and fraction
+// fragments; Uarr from the MIX spr_up_kernel, scaled by the class weight): a move's sum is the RAW
+// term c_k L_ik(moved tree) -- no log, no look at the site's likelihood under the set, which may be
+// 0 on the resident tree and positive on the moved one.  The first running set stores it, the
+// later ones add to it (first == 0): the same lane of the same workgroup, launches in order on
+// one stream -- a fixed sum.  The logs are mix_log_ratio_kernel's once the sets are in.
+// (`first` is an argument of the MIX instance alone, FIRST = int: the plain instance keeps its
+// argument list, and with it the offsets of the hidden arguments behind it -- gridDim.y.)
+template <int NT, int KS, bool MIX = false, class... FIRST>
 __global__ void __launch_bounds__(64 * NT)
 spr_kernel(const double *__restrict__ PfragT, const double *__restrict__ PfragA,
            const double *__restrict__ GfragT, const double *__restrict__ GfragA, int R, int nops,
@@ -123,8 +141,10 @@ spr_kernel(const double *__restrict__ PfragT, const double *__restrict__ PfragA,
            const double *__restrict__ Uarr, double *S, int nlevels,
            const double *__restrict__ obs, int K, const double *__restrict__ root_w, int n, int cA,
            int cB, int mvA, double *__restrict__ out, int *__restrict__ status, long nsites,
-           long nblocks)
+           long nblocks, FIRST... first_set)
 {
+    static_assert(sizeof...(FIRST) == (MIX ? 1 : 0), "first: the MIX instance's alone");
+    [[maybe_unused]] const int first = (0 + ... + first_set);
     constexpr int KP = (KS + 1) / 2;
     __shared__ double xb[NT * 4 * 64];
     __shared__ double lb[NT * 4 * 64];
@@ -144,9 +164,10 @@ spr_kernel(const double *__restrict__ PfragT, const double *__restrict__ PfragA,
     constexpr size_t ASTRIDE = (size_t)NT * KP * 128;
     const double *og = obs + (size_t)blk * K * (KP * 128) + lane * 2;
     // the site's likelihood (the `up` vectors are spr_up_kernel's)
-    const bool zero = down_up_pass<NT, KS>(false, xb, red, tab, PfragT, nops, steps, Larr, Marr,
-                                           nullptr, og, root_w, live, m, lane, blk, nblocks, writer,
-                                           status, site);
+    [[maybe_unused]] bool zero = false;
+    if constexpr (!MIX)
+        zero = down_up_pass<NT, KS>(false, xb, red, tab, PfragT, nops, steps, Larr, Marr, nullptr, og,
+                                    root_w, live, m, lane, blk, nblocks, writer, status, site);
     const int lv0 = blockIdx.y * nlevels;        // the group's levels
     double a[2 * KP];
     int par = 0;                                 // the half of `sums` the next move writes
@@ -256,12 +277,18 @@ spr_kernel(const double *__restrict__ PfragT, const double *__restrict__ PfragA,
             __syncthreads();
             if (writer) {
                 double *row = out + (size_t)(mv - mvA) * R * nsites + site;
-                for (int r = 0; r < R; ++r) row[(size_t)r * nsites] = down_total<NT>(sums[par][r], lane);
+                for (int r = 0; r < R; ++r) {
+                    const double t = down_total<NT>(sums[par][r], lane);
+                    double *x = row + (size_t)r * nsites;
+                    if constexpr (MIX) *x = first ? t : __dadd_rn(*x, t);
+                    else *x = t;
+                }
             }
             par ^= 1;
         }
         // the pruned node's ratios -> values, by all waves: lane group g of the workgroup takes
         // the rows g, g + 4 NT, ... of its site (the barrier: wave 0's stores are visible)
+        if constexpr (MIX) continue;
         __syncthreads();
         if (site_ok) {
             const long r0 = (long)(ct.w - mvA) * R, r1 = (long)(cut[c + 1].w - mvA) * R;
@@ -273,27 +300,29 @@ spr_kernel(const double *__restrict__ PfragT, const double *__restrict__ PfragA,
     }
 }
 
-// n <= 4: the upward pass and the `up` pass, one lane per site
-template <int N>
+// n <= 4: the upward pass and the `up` pass, one lane per site (MIX: as spr_up_kernel, P of the set)
+template <int N, bool MIX = false>
 __global__ void __launch_bounds__(256)
 spr_lane_up_kernel(int nnodes, long nsites, const double *__restrict__ P,
                    const int *__restrict__ parent, const int *__restrict__ node_k,
                    const int *__restrict__ tabp, const void *__restrict__ obs, int compact, int Kobs,
                    int block_sites, const double *__restrict__ root_w, double *__restrict__ Larr,
-                   double *__restrict__ Marr, double *__restrict__ Uarr, int *__restrict__ status)
+                   double *__restrict__ Marr, double *__restrict__ Uarr, int *__restrict__ status,
+                   double ck, double *__restrict__ root_tot)
 {
     const long site = (long)blockIdx.x * 256 + threadIdx.x;
     if (site >= nsites) return;
     const post_tab tab(tabp, nnodes);
     lane_up<N, true>(nnodes, nsites, site, P, parent, node_k, obs, compact, Kobs, block_sites, Larr, Marr);
-    lane_up_pass<N>(true, nnodes, nsites, site, P, parent, node_k, tab, obs, compact, Kobs,
-                    block_sites, root_w, Larr, Marr, Uarr, status);
+    lane_up_pass<N, MIX>(true, nnodes, nsites, site, P, parent, node_k, tab, obs, compact, Kobs,
+                         block_sites, root_w, Larr, Marr, Uarr, status, ck, root_tot);
 }
 
 // n <= 4: one lane per (site, group); arrays [node][state][site], nodes in preorder; G
 // [point][node][N][N]: the points 0 .. R - 1 are P(rho t), R .. 2 R - 1 are P((1 - rho) t) (the
-// same address in every lane: the scalar path); S [group][level][state][site]
-template <int N>
+// same address in every lane: the scalar path); S [group][level][state][site].  MIX: as spr_kernel,
+// P and G of the set, `first` its argument alone.
+template <int N, bool MIX = false, class... FIRST>
 __global__ void __launch_bounds__(256)
 spr_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const double *__restrict__ G,
                 int R, const int *__restrict__ parent, const int *__restrict__ node_k,
@@ -302,8 +331,10 @@ spr_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const dou
                 int block_sites, const double *__restrict__ root_w, const double *__restrict__ Larr,
                 const double *__restrict__ Marr, const double *__restrict__ Uarr, double *S,
                 int nlevels, int cA, int cB, int mvA, double *__restrict__ out,
-                int *__restrict__ status)
+                int *__restrict__ status, FIRST... first_set)
 {
+    static_assert(sizeof...(FIRST) == (MIX ? 1 : 0), "first: the MIX instance's alone");
+    [[maybe_unused]] const int first = (0 + ... + first_set);
     const long site = (long)blockIdx.x * 256 + threadIdx.x;
     if (site >= nsites) return;
     const post_tab tab(tabp, nnodes);
@@ -317,8 +348,10 @@ spr_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const dou
 #pragma unroll
             for (int s = 0; s < N; ++s) x[s] = 1.0;
     };
-    const bool zero = lane_up_pass<N>(false, nnodes, nsites, site, P, parent, node_k, tab, obs, compact,
-                                      Kobs, block_sites, root_w, Larr, Marr, nullptr, status);
+    [[maybe_unused]] bool zero = false;
+    if constexpr (!MIX)
+        zero = lane_up_pass<N>(false, nnodes, nsites, site, P, parent, node_k, tab, obs, compact, Kobs,
+                               block_sites, root_w, Larr, Marr, nullptr, status);
     for (int c = cA + blockIdx.y; c < cB; c += gridDim.y) {
         const int4 ct = cut[c];
         const int ci = ct.x;
@@ -389,7 +422,9 @@ spr_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const dou
                     }
                     t += y * z * mc[b];
                 }
-                out[((size_t)(mv - mvA) * R + r) * nsites + site] = spr_value(t, zero);
+                double *o = out + ((size_t)(mv - mvA) * R + r) * nsites + site;
+                if constexpr (MIX) *o = first ? t : __dadd_rn(*o, t);
+                else *o = spr_value(t, zero);
             }
         }
     }
@@ -581,13 +616,25 @@ extern "C" int rt_tree_spr_moves(int64_t nnodes, const int64_t *idx, const int64
     return spr_list(nnodes, idx, ptr, parent.data(), radius, moves, capacity, nmoves);
 }
 
-extern "C" int rt_sites_spr_scores(rt_model *m, rt_sites *s, int recompute_transitions,
-                                   int64_t radius, int64_t nfractions, const double *fractions,
-                                   double *values, double *sums, int32_t *status)
+namespace {
+
+// Both reads.  MIX = false: the grid of the model's own exponential (post_grid), the upward pass
+// and the `up` pass once, then per chunk of pruned nodes the walk, whose plain instance takes the
+// logs.  MIX = true: the sets' grid (post_set_grid at the factors rho_r, 1 - rho_r) and the sets'
+// P, P^T and fraction fragments packed once; then per chunk, once per rate set of positive class
+// weight over the one L / M / U / level scratch, the set's upward pass (post_up_set), the MIX `up`
+// pass and the MIX walk, which adds c_k L_ik(moved tree) into ONE accumulator [move][fraction][site]
+// in set order; post_mix turns it into the values.  The plan of the walk holds no matrix: it is
+// made once per call.
+template <bool MIX>
+int spr_read(const char *who, rt_model *m, rt_sites *s, int recompute_transitions,
+             const double *class_weights, int64_t radius, int64_t nfractions, const double *fractions,
+             double *values, double *sums, double *loglik, int32_t *status)
 {
-    const char *who = "rt_sites_spr_scores";
+    using grid_t = std::conditional_t<MIX, post_set_grid, post_grid>;
     post_pass p;                                 // (alive until the synchronisation below)
     RT_TRY(post_open(&p, who, m, s));
+    if (MIX) RT_TRY(post_class_weights(who, m, class_weights));
     const int64_t n = p.n, N = p.N, nsites = p.nsites;
     RT_REQUIRE(fractions, "%s: fractions is NULL", who);
     RT_TRY(post_fraction_count(who, nfractions));
@@ -604,20 +651,26 @@ extern "C" int rt_sites_spr_scores(rt_model *m, rt_sites *s, int recompute_trans
     for (int64_t c = 1; c < N; ++c)
         if (first[(size_t)c + 1] > first[(size_t)c]) nplan += tree.path_steps(c, radius);
     RT_REQUIRE(nplan < INT32_MAX / 4, "%s: too many moves (a plan of %lld ops)", who, (long long)nplan);
+    p.per_set = MIX;
     RT_TRY(post_layout(&p, true));
-    // the grid of every node: rho_r t_v, (1 - rho_r) t_v
-    const std::vector<double> lengths = post_fraction_lengths(&p, R, fractions);
-    RT_TRY(post_grid::check(&p, recompute_transitions, np, lengths.data()));
+    // the grid of every node: rho_r t_v, (1 - rho_r) t_v (MIX: the factors of every set's own t)
+    const std::vector<double> lengths = MIX ? post_set_fraction_factors(&p, R, fractions)
+                                            : post_fraction_lengths(&p, R, fractions);
+    RT_TRY(grid_t::check(&p, recompute_transitions, np, lengths.data()));
     post_plan &plan = p.plan;
-    post_grid grid;                              // (alive until the synchronisation below)
+    grid_t grid;                                 // (alive until the synchronisation below)
+    post_mix mix;
+    post_set_fractions setfrac;
     post_result res(values, sums);
     RT_TRY(grid.take(&p, np));
+    if (MIX) RT_TRY(mix.take(&p, class_weights));
+    const int64_t nsets = MIX ? mix.K : 1;
     const int cnt = p.lane ? (int)N : p.nops;    // slots of the tables
     const int D = 1 + *std::max_element(tree.depth.begin(), tree.depth.end()), nlevels = 3 * D;
     const size_t o_tab = plan.take((size_t)4 * cnt * 4);
     const size_t o_cut = plan.take(((size_t)N + 1) * 16);
     const size_t ftab = p.lane ? 0 : (size_t)p.nops * p.NT * p.KP * 128;
-    const size_t o_PA = plan.take(p.lane ? 8 : ftab * 8);
+    const size_t o_PA = plan.take(p.lane ? 8 : (size_t)nsets * ftab * 8);
     res.take_sums(&p, (size_t)nmoves * R);
     // the groups of pruned nodes that walk side by side: enough workgroups to fill the device at
     // few sites, their level vectors within SPR_LEVEL_BYTES
@@ -666,14 +719,14 @@ extern "C" int rt_sites_spr_scores(rt_model *m, rt_sites *s, int recompute_trans
     hipStream_t st = p.st;
     unsigned char *base = p.base;
     res.place(&p);
+    if (MIX) RT_TRY(mix.begin(&p));
     double *d_val = res.d_val, *d_S = (double *)(base + o_S);
     double *d_PA = (double *)(base + o_PA);
     int *d_tab = (int *)(base + o_tab);
     int4 *d_cut = (int4 *)(base + o_cut), *d_ops = (int4 *)(base + o_ops);
-    int *d_status = p.d_status;
     const std::vector<int32_t> internal = post_internal_nodes(&p);
     RT_TRY(grid.launch(&p, lengths.data()));
-    RT_TRY(post_up(&p, internal.data(), true));
+    RT_TRY(post_up(&p, internal.data(), !MIX));
     std::vector<int32_t> tab;
     post_tab_build(&p, nullptr, &tab);
     if (!p.lane) {                               // node -> step in the plan
@@ -690,73 +743,152 @@ extern "C" int rt_sites_spr_scores(rt_model *m, rt_sites *s, int recompute_trans
     RT_HIP(hipMemcpyAsync(d_cut, cut.data(), cut.size() * 4, hipMemcpyHostToDevice, st));
     if (!ops.empty())
         RT_HIP(hipMemcpyAsync(d_ops, ops.data(), ops.size() * sizeof(spr_op), hipMemcpyHostToDevice, st));
-    if (p.lane) {
-        const int *d_ptab = p.d_ptab;
-        RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
-            hipLaunchKernelGGL((spr_lane_up_kernel<decltype(nv)::value>),
-                               dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)N,
-                               (long)nsites, (const double *)m->d_P, d_ptab, d_ptab + N,
-                               (const int *)d_tab, (const void *)s->d_obs, s->compact_states,
-                               (int)s->nobs, s->block_sites, (const double *)m->d_root, p.d_L, p.d_M,
-                               p.d_D, d_status);
-            return RT_OK;
-        }));
-    } else {
-        // the fragment tables: the resident P beside the resident P^T; the grid's
-        RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab, m->d_P, d_PA));
-        RT_TRY(post_fraction_pack(&p, &grid, R));
-        const rt_sites *x = p.x;
-        RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
-            constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
-            hipLaunchKernelGGL((spr_up_kernel<NT, KS>), dim3((unsigned)x->nblocks), dim3(64 * NT), 0, st,
-                               (const double *)p.d_PT, p.nops, (const int4 *)p.d_steps,
-                               (const int *)d_tab, (const double *)p.d_L, (const double *)p.d_M, p.d_D,
-                               (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
-                               (int)n, d_status, (long)x->nsites, (long)x->nblocks);
-            return RT_OK;
-        }));
+    if (!p.lane) {
+        // the fragment tables: the resident P beside the resident P^T; the grid's (MIX: of every
+        // set, each by one launch over the step table that spans the sets)
+        if constexpr (MIX) {
+            RT_TRY(mix.PT.pack(&p));
+            RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, (int)(mix.K * p.nops),
+                                    (const int *)(base + mix.PT.o_tab), m->multi.d_P, d_PA));
+            RT_TRY(setfrac.pack(&p, &grid, R));
+        } else {
+            RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab, m->d_P, d_PA));
+            RT_TRY(post_fraction_pack(&p, &grid, R));
+        }
     }
-    RT_HIP(hipGetLastError());
-    for (size_t ch = 0; ch + 1 < chunks.size() && nmoves; ++ch) {
-        const int cA = chunks[ch], cB = chunks[ch + 1];
-        const int mvA = first[(size_t)cA];
-        const size_t rows = (size_t)(first[(size_t)cB] - mvA) * R;
-        if (!rows) continue;
-        const unsigned groups = (unsigned)std::min<int64_t>(G, cB - cA);
+    // what set k's launches read and write (plain: the model's own, the batch's status)
+    struct set_view {
+        const double *P, *G, *PT, *PA, *GT, *GA;
+        int *stat;
+        double *tot, ck;
+    };
+    auto view_of = [&](int64_t k) {
+        set_view v = {m->d_P, grid.d_G, p.d_PT, d_PA, grid.d_GT, grid.d_GT + (size_t)R * ftab,
+                      p.d_status, nullptr, 1.0};
+        if constexpr (MIX) {
+            v.P = mix.P_of(&p, k); v.G = grid.G_of_set(&p, k);
+            v.PT = mix.PT.of_set(k); v.PA = d_PA + (size_t)k * ftab;
+            v.GT = p.lane ? nullptr : setfrac.T_of_set(k); v.GA = p.lane ? nullptr : setfrac.A_of_set(k);
+            v.stat = mix.status_of(&p, k); v.tot = mix.tot_of(&p, k); v.ck = class_weights[k];
+        }
+        return v;
+    };
+    // the upward pass (MIX: under set k) and the `up` pass
+    auto up_stage = [&](int64_t k) -> int {
+        const set_view v = view_of(k);
         if (p.lane) {
             const int *d_ptab = p.d_ptab;
             RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
-                hipLaunchKernelGGL((spr_lane_kernel<decltype(nv)::value>),
-                                   dim3((unsigned)((nsites + 255) / 256), groups), dim3(256), 0, st,
-                                   (int)N, (long)nsites, (const double *)m->d_P,
-                                   (const double *)grid.d_G, R, d_ptab, d_ptab + N, (const int *)d_tab,
-                                   (const int4 *)d_cut, (const int4 *)d_ops, (const void *)s->d_obs,
-                                   s->compact_states, (int)s->nobs, s->block_sites,
-                                   (const double *)m->d_root, (const double *)p.d_L,
-                                   (const double *)p.d_M, (const double *)p.d_D, d_S, nlevels, cA, cB,
-                                   mvA, d_val, d_status);
+                hipLaunchKernelGGL((spr_lane_up_kernel<decltype(nv)::value, MIX>),
+                                   dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)N,
+                                   (long)nsites, v.P, d_ptab, d_ptab + N, (const int *)d_tab,
+                                   (const void *)s->d_obs, s->compact_states, (int)s->nobs,
+                                   s->block_sites, (const double *)m->d_root, p.d_L, p.d_M, p.d_D, v.stat,
+                                   v.ck, v.tot);
+                return RT_OK;
+            }));
+        } else {
+            const rt_sites *x = p.x;
+            if (MIX) RT_TRY(post_up_set(&p, k, nullptr));
+            RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
+                constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
+                hipLaunchKernelGGL((spr_up_kernel<NT, KS, MIX>), dim3((unsigned)x->nblocks),
+                                   dim3(64 * NT), 0, st, v.PT, p.nops, (const int4 *)p.d_steps,
+                                   (const int *)d_tab, (const double *)p.d_L, (const double *)p.d_M, p.d_D,
+                                   (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
+                                   (int)n, v.stat, (long)x->nsites, (long)x->nblocks, v.ck, v.tot);
+                return RT_OK;
+            }));
+        }
+        RT_HIP(hipGetLastError());
+        return RT_OK;
+    };
+    // the walk of the pruned nodes cA .. cB - 1
+    auto walk = [&](int64_t k, int cA, int cB, int mvA, unsigned groups, int first_set) -> int {
+        const set_view v = view_of(k);
+        if (p.lane) {
+            const int *d_ptab = p.d_ptab;
+            RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
+                auto launch = [&](auto kernel, auto... first) {
+                    hipLaunchKernelGGL(kernel, dim3((unsigned)((nsites + 255) / 256), groups), dim3(256),
+                                       0, st, (int)N, (long)nsites, v.P, v.G, R, d_ptab, d_ptab + N,
+                                       (const int *)d_tab, (const int4 *)d_cut, (const int4 *)d_ops,
+                                       (const void *)s->d_obs, s->compact_states, (int)s->nobs,
+                                       s->block_sites, (const double *)m->d_root, (const double *)p.d_L,
+                                       (const double *)p.d_M, (const double *)p.d_D, d_S, nlevels, cA,
+                                       cB, mvA, d_val, v.stat, first...);
+                };
+                if constexpr (MIX) launch(spr_lane_kernel<decltype(nv)::value, true, int>, first_set);
+                else launch(spr_lane_kernel<decltype(nv)::value>);
                 return RT_OK;
             }));
         } else {
             const rt_sites *x = p.x;
             RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
                 constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
-                hipLaunchKernelGGL((spr_kernel<NT, KS>), dim3((unsigned)x->nblocks, groups),
-                                   dim3(64 * NT), 0, st, (const double *)p.d_PT, (const double *)d_PA,
-                                   (const double *)grid.d_GT,
-                                   (const double *)(grid.d_GT + (size_t)R * ftab), R, p.nops,
-                                   (const int4 *)p.d_steps, (const int *)d_tab, (const int4 *)d_cut,
-                                   (const int4 *)d_ops, (const double *)p.d_L, (const double *)p.d_M,
-                                   (const double *)p.d_D, d_S, nlevels, (const double *)x->d_obs,
-                                   (int)x->nobs, (const double *)m->d_root, (int)n, cA, cB, mvA, d_val,
-                                   d_status, (long)x->nsites, (long)x->nblocks);
+                auto launch = [&](auto kernel, auto... first) {
+                    hipLaunchKernelGGL(kernel, dim3((unsigned)x->nblocks, groups), dim3(64 * NT), 0, st,
+                                       v.PT, v.PA, v.GT, v.GA, R, p.nops, (const int4 *)p.d_steps,
+                                       (const int *)d_tab, (const int4 *)d_cut, (const int4 *)d_ops,
+                                       (const double *)p.d_L, (const double *)p.d_M,
+                                       (const double *)p.d_D, d_S, nlevels, (const double *)x->d_obs,
+                                       (int)x->nobs, (const double *)m->d_root, (int)n, cA, cB, mvA,
+                                       d_val, v.stat, (long)x->nsites, (long)x->nblocks, first...);
+                };
+                if constexpr (MIX) launch(spr_kernel<NT, KS, true, int>, first_set);
+                else launch(spr_kernel<NT, KS>);
                 return RT_OK;
             }));
         }
         RT_HIP(hipGetLastError());
+        return RT_OK;
+    };
+    if (!MIX) RT_TRY(up_stage(0));
+    bool have_ll = false;                        // (MIX: log Lambda_i and the status are in)
+    for (size_t ch = 0; ch + 1 < chunks.size(); ++ch) {
+        const int cA = chunks[ch], cB = chunks[ch + 1];
+        const int mvA = first[(size_t)cA];
+        const size_t rows = (size_t)(first[(size_t)cB] - mvA) * R;
+        // (a chunk without moves: nothing, but the first one brings the mixture's likelihood)
+        if (!rows && (!MIX || have_ll)) continue;
+        const unsigned groups = (unsigned)std::min<int64_t>(G, cB - cA);
+        // the pass; MIX: set by set (a set of weight zero is never live: not run, never read)
+        int first_set = 1;
+        for (int64_t k = 0; k < nsets; ++k) {
+            if (MIX && !(class_weights[k] > 0.0)) continue;
+            if (MIX) RT_TRY(up_stage(k));
+            if (rows) RT_TRY(walk(k, cA, cB, mvA, groups, first_set));
+            first_set = 0;
+        }
+        if (MIX && !have_ll) {
+            RT_TRY(mix.post(&p));                // (log Lambda_i, the status)
+            have_ll = true;
+        }
+        if (!rows) continue;
+        if (MIX && (values || sums)) RT_TRY(mix.log_ratio(&p, rows, R, nullptr, d_val));
         // 3. the weighted site sums and the per-site array [site][nmoves][R]
         RT_TRY(res.chunk(&p, (size_t)mvA * R, rows));
     }
-    RT_TRY(res.finish(&p, status));
+    RT_TRY(res.finish(&p, status, loglik, mix.d_ll));
     return grid.result(&p);
 }
+
+}  // namespace
+
+extern "C" int rt_sites_spr_scores(rt_model *m, rt_sites *s, int recompute_transitions,
+                                   int64_t radius, int64_t nfractions, const double *fractions,
+                                   double *values, double *sums, int32_t *status)
+{
+    return spr_read<false>("rt_sites_spr_scores", m, s, recompute_transitions, nullptr, radius,
+                           nfractions, fractions, values, sums, nullptr, status);
+}
+
+extern "C" int rt_sites_spr_scores_mixture(rt_model *m, rt_sites *s, int recompute_transitions,
+                                           const double *class_weights, int64_t radius,
+                                           int64_t nfractions, const double *fractions, double *values,
+                                           double *sums, double *loglik, int32_t *status)
+{
+    return spr_read<true>("rt_sites_spr_scores_mixture", m, s, recompute_transitions, class_weights,
+                          radius, nfractions, fractions, values, sums, loglik, status);
+}
+

@@ -371,6 +371,13 @@ def tree_nni_moves(tree):
 SprScores = collections.namedtuple('SprScores', 'moves fractions sums values status best')
 
 
+# TreeModel.spr_scores_mixture: as SprScores under the site-class mixture over the K rate sets,
+# values[i, mv, r] = log sum_k c_k L_ik(tree after move mv at fractions[r]) - loglik[i]; loglik and
+# status as MixtureNniScores
+MixtureSprScores = collections.namedtuple('MixtureSprScores',
+                                          'moves fractions sums values loglik status best')
+
+
 def _spr_radius(radius):
     """radius=None (no limit) or an int >= 0 -> the radius of the C ABI (-1: no limit)."""
     if radius is None:
@@ -402,6 +409,14 @@ def tree_spr_moves(tree, radius=None):
 # placed at (v, fractions[r], pendant[k])) - log L_i (the root's row: 0), status as Posteriors,
 # best int[Q, 3]: the arg-max (v, r, k) of sums per query, ties to the lowest index
 Placements = collections.namedtuple('Placements', 'fractions pendant sums values status best')
+
+
+# TreeModel.place_queries_mixture: as Placements under the site-class mixture over the K rate sets,
+# pendant_scale [K] as evaluated, values[i, q, v, r, j] = log sum_k c_k L_ik(tree with query q placed
+# at (v, fractions[r], pendant_scale[k] pendant[j])) - loglik[i]; loglik and status as
+# MixtureNniScores
+MixturePlacements = collections.namedtuple(
+    'MixturePlacements', 'fractions pendant pendant_scale sums values loglik status best')
 
 
 def check_placement_grid(fractions, pendant):
@@ -510,6 +525,25 @@ def check_class_weights(class_weights, nsets):
     if not np.isfinite(c).all() or (c < 0).any() or not (c > 0).any():
         raise ValueError('the class weights must be finite, >= 0 and not all zero')
     return c
+
+
+def check_pendant_scale(pendant_scale, nsets):
+    """The per-class scale of the pendant lengths of TreeModel.place_queries_mixture -> f64[K]:
+    under class k the query hangs on an edge of length pendant_scale[k] * pendant[j].  None gives
+    ones (right where the classes differ in Q, Q_k = r_k Q, over shared lengths; with a shared Q
+    and t_k = r_k t pass r_k).  ValueError for another shape or an entry that is negative or not
+    finite."""
+    if pendant_scale is None:
+        return np.ones(nsets)
+    try:
+        s = np.ascontiguousarray(pendant_scale, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('pendant_scale must be a sequence of %d numbers' % nsets)
+    if s.shape != (nsets,):
+        raise ValueError('one pendant scale per rate set expected (%d), not %s' % (nsets, s.shape))
+    if not (np.isfinite(s).all() and (s >= 0).all()):
+        raise ValueError('the pendant scales must be finite and not negative')
+    return s
 
 
 def _mask_states(mask, nstates):
@@ -1741,6 +1775,38 @@ class TreeModel(object):
             best = tuple(int(x) for x in np.unravel_index(int(np.argmax(flat)), (M, R)))
         return SprScores(moves, f, sums, values, status, best)
 
+    def spr_scores_mixture(self, batch, class_weights, radius=None, fractions=(0.5,),
+                           per_site=False, recompute_transitions=False):
+        """rt_sites_spr_scores_mixture: spr_scores of an ordinary batch under the site-class
+        mixture over the K rate sets of set_rate_sets with the class weights c
+        (check_class_weights), for every move of spr_moves(radius) at every fraction: under class
+        k the edge above y is cut at fractions[r] of its own resident length t[k][y], the pruned
+        subtree keeps its edge.  Returns a MixtureSprScores tuple: moves, fractions, sums[mv, r]
+        the site-weighted sum of values[i, mv, r] = log sum_k c_k L_ik(tree after mv at
+        fractions[r]) - loglik[i] (None unless per_site), loglik, status, best as spr_scores.
+        Exact in every term: a class under which the site is impossible on the current tree
+        still adds what it gives on the moved one.  Nothing the batch or the model holds
+        changes."""
+        c = self._mixture_search_args(batch, class_weights, 'spr_scores_mixture')
+        S = batch.nsites
+        rad = _spr_radius(radius)
+        f, _ = check_placement_grid(fractions, (0.0,))
+        moves = self.spr_moves(radius)
+        M, R = len(moves), len(f)
+        values = np.zeros((S, M, R)) if per_site else None
+        sums = np.zeros((M, R))
+        ll = np.zeros(S)
+        status = np.zeros(S, dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_spr_scores_mixture(
+            self._h, batch._h, 1 if recompute_transitions else 0, _ptr(c, c_double), rad, R,
+            _ptr(f, c_double), None if values is None else _ptr(values, c_double),
+            _ptr(sums, c_double), _ptr(ll, c_double), _ptr(status, c_int32)))
+        best = None
+        if M:
+            flat = np.where(np.isnan(sums), -np.inf, sums).reshape(-1)
+            best = tuple(int(x) for x in np.unravel_index(int(np.argmax(flat)), (M, R)))
+        return MixtureSprScores(moves, f, sums, values, ll, status, best)
+
     def place_queries(self, batch, queries, kind='dense', fractions=(0.5,), pendant=None,
                       per_site=False, recompute_transitions=False):
         """rt_sites_placements: every query placed on every branch -- for query q, non-root
@@ -1792,6 +1858,63 @@ class TreeModel(object):
             v, r, k = np.unravel_index(np.argmax(flat, axis=1), (N - 1, R, K))
             best = np.stack([v + 1, r, k], axis=1).astype(np.int64)
         return Placements(f, t, sums, values, status, best)
+
+    def place_queries_mixture(self, batch, class_weights, queries, kind='dense', fractions=(0.5,),
+                              pendant=None, pendant_scale=None, per_site=False,
+                              recompute_transitions=False):
+        """rt_sites_placements_mixture: place_queries of an ordinary batch under the site-class
+        mixture over the K rate sets of set_rate_sets with the class weights c
+        (check_class_weights).  Under class k the edge above v is cut at fractions[r] of its own
+        resident length t[k][v] and the query hangs on an edge of length pendant_scale[k] *
+        pendant[j] (check_pendant_scale: None gives ones, right for classes Q_k = r_k Q over
+        shared lengths; for a shared Q with t_k = r_k t pass r_k).  queries, kind, fractions and
+        pendant as for place_queries (pendant=None: the one value mean(rate_set_lengths)).
+        Returns a MixturePlacements tuple: fractions, pendant, pendant_scale, sums
+        [Q, nnodes, R, K] the site-weighted sums of values[i, q, v, r, j] = log sum_k c_k
+        L_ik(tree with q placed) - loglik[i] (None unless per_site), loglik, status, best as
+        place_queries.  The root's row is 0.  Exact in every term; nothing the batch or the
+        model holds changes."""
+        c = self._mixture_search_args(batch, class_weights, 'place_queries_mixture')
+        ta = self.tree
+        N, S, n = ta.nnodes, batch.nsites, self.nstates
+        scale = check_pendant_scale(pendant_scale, len(c))
+        if pendant is None:
+            sets = getattr(self, '_rate_sets', None)
+            t = None if sets is None else np.asarray(sets[1])
+            pendant = [float(np.mean(t[:, 1:]))] if t is not None and N > 1 else [0.0]
+        f, t = check_placement_grid(fractions, pendant)
+        if kind == 'dense':
+            q = np.ascontiguousarray(queries, dtype=np.float64)
+            if q.ndim != 3 or q.shape[1:] != (S, n):
+                raise ValueError('dense queries must be [Q, %d, %d], not %s' % (S, n, q.shape))
+            code = _lib.RT_OBS_DENSE
+        elif kind == 'state':
+            q = np.asarray(queries)
+            if q.ndim != 2 or q.shape[1] != S:
+                raise ValueError('state queries must be [Q, %d], not %s' % (S, q.shape))
+            q = _as_uint8_states(q, n)
+            code = _lib.RT_OBS_STATE
+        else:
+            raise ValueError("queries of kind 'dense' or 'state', not %r" % (kind,))
+        Q, R, K = q.shape[0], len(f), len(t)
+        if Q < 1:
+            raise ValueError('at least one query')
+        values = np.zeros((S, Q, N, R, K)) if per_site else None
+        sums = np.zeros((Q, N, R, K))
+        ll = np.zeros(S)
+        status = np.zeros(S, dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_placements_mixture(
+            self._h, batch._h, 1 if recompute_transitions else 0, _ptr(c, c_double), Q, code,
+            q.ctypes.data_as(ctypes.c_void_p), R, _ptr(f, c_double), K, _ptr(t, c_double),
+            _ptr(scale, c_double), None if values is None else _ptr(values, c_double),
+            _ptr(sums, c_double), _ptr(ll, c_double), _ptr(status, c_int32)))
+        best = np.zeros((Q, 3), dtype=np.int64)
+        if N > 1:
+            flat = sums[:, 1:].reshape(Q, -1)
+            flat = np.where(np.isnan(flat), -np.inf, flat)
+            v, r, k = np.unravel_index(np.argmax(flat, axis=1), (N - 1, R, K))
+            best = np.stack([v + 1, r, k], axis=1).astype(np.int64)
+        return MixturePlacements(f, t, scale, sums, values, ll, status, best)
 
     def branch_length_gradient(self, batch, recompute_transitions=False):
         """d (sum_i w_i log L_i) / d t_v for every branch, f64[nnodes] in preorder (0 at the
