@@ -975,11 +975,48 @@ const char *rt_sites_multi_kernel_name(const rt_sites *sites);
  *   rate sets resident in the model than the batch's nsets; a batch of another model; n_coefs < 1
  *   or coefs NULL; a coefficient that is not finite.  RT_ERR_UNSUPPORTED: more than
  *   RT_MAX_BRANCH_COEFS matrices; more than 96 GB of scratch.
+ * rt_sites_branch_profiles_partitioned, rt_sites_nni_scores_partitioned: rt_sites_branch_profiles
+ *   and rt_sites_nni_scores (above) for a partitioned batch.  Site i with k = site_set[i] uses
+ *   Q[k][node_q[v]], t[k][v] and P of its own set on every edge; under set k the moved tree of an
+ *   NNI keeps every moved subtree's own edge of set k.  Trial lengths are FACTORS, as in section 2d:
+ *   at point g the edge above v has length factors[v][g] * t[k][v] under set k -- the same meaning
+ *   whether the sets differ in Q or in t, and what a shared tree with one multiplier per partition
+ *   needs.
+ *     factors         f64[nnodes][npoints], 1 <= npoints <= RT_MAX_PROFILE_POINTS, finite, >= 0
+ *                     (row 0, and for the NNI scores the rows of nodes without a move, are ignored);
+ *                     rt_sites_nni_scores_partitioned: NULL with npoints == 1 is the plain swap
+ *     values          f64[nsites][nnodes][npoints] / f64[nsites][nmoves][npoints] in CALLER order,
+ *                     real sites only: log L_i(trial) - log L_i.  -inf where a live site has
+ *                     likelihood 0 at the trial; a site of zero likelihood under its set: zeros
+ *                     (RT_SITE_ZERO_PROB).  Profiles: the root's row is 0, and where the resident
+ *                     t[k][v] == 0 (v != root) row v is NaN for the live sites of set k.  NNI: the
+ *                     moves of rt_model_nni_moves, division-free and exact as
+ *                     rt_sites_nni_scores, no NaN rows
+ *     set_sums        f64[nsets][rows][npoints]: the sum of w_i values over the real sites of set k
+ *                     (rt_sites_set_weights, caller order; pads skipped; a site of weight 0 adds
+ *                     nothing even at -inf); zeros for an empty set; profiles: NaN in row v where
+ *                     t[k][v] == 0 and set k has a site
+ *     sums            f64[rows][npoints]: the per-set rows added in set order
+ *     status          int32[nsites] in caller order, as the single-set calls
+ *   Each output may be NULL; only what is given crosses PCIe.  The trial matrices of all sets with
+ *   a site come from ONE launch of the sets' exponential (its variant chosen by one set's count: a
+ *   matrix does not depend on K), the pass runs once with every 16-site tile (n <= 4: every wave)
+ *   under the tables of its granule's set, and the sums are reduced on the device in two stages
+ *   whose shape depends on the plan alone: two calls return the same bits.  The NNI scores are
+ *   made in chunks of moves as rt_sites_nni_scores makes them.  nmoves == 0: RT_OK, only status is
+ *   written.  Synchronous; the batch's log-likelihoods, status and totals, the model's transitions
+ *   and rate sets keep what they had.  RT_ERR_INVALID: fewer rate sets resident in the model than
+ *   the batch's nsets; a batch of another model; npoints outside 1..RT_MAX_PROFILE_POINTS; factors
+ *   NULL (NNI: with npoints != 1); a factor that is negative or not finite.
+ *   RT_ERR_UNSUPPORTED: an ordinary batch, a "rescale" or generic-kernel batch, a tree deeper than the
+ *   fast kernels take, more than 96 GB of scratch.  RT_ERR_SINGULAR: a failed exponential.  SPR
+ *   scores and placements of a partitioned batch are not offered yet.
  * Everything else refuses a partitioned batch with RT_ERR_UNSUPPORTED and leaves it untouched:
  *   rt_prune, rt_step, rt_step_multi, rt_sites_clone, rt_expect_step, rt_sites_posteriors,
  *   rt_sites_branch_expectations, rt_sites_branch_profiles, rt_sites_sample_states,
  *   rt_sites_map_states, rt_sites_sample_mappings, rt_sites_branch_expectations_mixture,
- *   rt_sites_branch_profiles_mixture, rt_sites_nni_scores_mixture, rt_allreduce_totals,
+ *   rt_sites_branch_profiles_mixture, rt_sites_nni_scores_mixture, rt_sites_nni_scores,
+ *   rt_sites_spr_scores, rt_sites_placements and their _mixture forms, rt_allreduce_totals,
  *   rt_allreduce_totals_group.
  *                                                               */
 int rt_partition_plan(const int32_t *site_set, int64_t nsites, int64_t nsets, int64_t granule,
@@ -993,6 +1030,12 @@ int rt_sites_get_partition_totals(rt_sites *sites, double *totals, double *weigh
 int rt_sites_branch_expectations_partitioned(rt_model *model, rt_sites *sites,
             int recompute_transitions, int64_t n_coefs, int coefs_per_set, const double *coefs,
             double *values, double *edge_sums, double *set_edge_sums, int32_t *status);
+int rt_sites_branch_profiles_partitioned(rt_model *model, rt_sites *sites, int recompute_transitions,
+            int64_t npoints, const double *factors, double *values, double *sums,
+            double *set_sums, int32_t *status);
+int rt_sites_nni_scores_partitioned(rt_model *model, rt_sites *sites, int recompute_transitions,
+            int64_t npoints, const double *factors, double *values, double *sums,
+            double *set_sums, int32_t *status);
 /* what the batch was laid out with: any pointer may be NULL; an ordinary batch gives zeros */
 int rt_sites_partition_info(const rt_sites *sites, int64_t *nsets, int64_t *granule,
             int64_t *padded);

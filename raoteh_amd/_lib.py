@@ -180,6 +180,10 @@ SIGNATURES = {
     'rt_sites_partition_info': (c_int, [c_void_p, _p_i64, _p_i64, _p_i64]),
     'rt_sites_branch_expectations_partitioned': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int,
                                                          _p_f64, _p_f64, _p_f64, _p_f64, _p_i32]),
+    'rt_sites_branch_profiles_partitioned': (c_int, [c_void_p, c_void_p, c_int, c_int64, _p_f64, _p_f64,
+                                                     _p_f64, _p_f64, _p_i32]),
+    'rt_sites_nni_scores_partitioned': (c_int, [c_void_p, c_void_p, c_int, c_int64, _p_f64, _p_f64,
+                                                _p_f64, _p_f64, _p_i32]),
     'rt_sites_branch_expectations_mixture': (c_int, [c_void_p, c_void_p, c_int, _p_f64, c_int64, c_int,
                                                      _p_f64, _p_f64, _p_f64, _p_f64, _p_f64, _p_f64,
                                                      _p_f64, _p_i32]),

@@ -2961,6 +2961,7 @@ extern "C" int rt_sites_create_partitioned(rt_model *m, int64_t nsites, int kind
     p->nsets = nsets;
     p->G = G;
     p->padded = plan.padded;
+    p->run_begin = plan.run_begin;
     int64_t longest = 0;
     for (int64_t k = 0; k < nsets; ++k)
         longest = std::max(longest, plan.run_begin[(size_t)k + 1] - plan.run_begin[(size_t)k]);

@@ -35,6 +35,16 @@
 //      set k's fragments -- the term c_k L_ik(tau) into ONE accumulator [node][point][site], the
 //      sets added in set order, L_ik and a status word per set; then mix_post_kernel (log
 //      Lambda_i, the status of the live sets) and mix_log_ratio_kernel (the accumulator -> values).
+//
+// rt_sites_branch_profiles_partitioned: the same read of a PARTITIONED batch, every site under its
+// own rate set, trial lengths as factors of that set's resident lengths; bp_read again:
+//   1. as under the mixture, for the sets that have a site (post_part: weight 1, an empty set 0);
+//   2. ONE pass: the stored upward pass of the twin through the batch's granule_set (post_up), then
+//      the PART instance of the kernel, every tile (n <= 4: every wave) against the fragments,
+//      trial fragments and resident lengths of its granule's set;
+//   3. post_part_result (post_common.h): per (set, node, point) the fixed-order two-stage sum over
+//      the set's run with the pads skipped, the per-set rows added in set order, and the gather of
+//      the values and the status into caller order.
 #include "common.h"
 #include "post_common.h"
 
@@ -64,7 +74,11 @@ __device__ __forceinline__ double bp_value(double ratio, bool zero, double tv)
 // status word is the set's own, and the RAW term ck L_ik * ratio = ck L_ik(tau) is written to `out`
 // by the first set and added to it by the later ones (the same lane, launches in order: a fixed
 // sum); the logs are mix_log_ratio_kernel's, once the sets are in.
-template <int NT, int KS, bool MIX = false>
+// PART (rt_sites_branch_profiles_partitioned: sites are the batch's slots, the output is in slot
+// order): the workgroup's tile is one granule; the tables of its rate set are gset[tile] * (gs_pt,
+// gs_gt, gs_t) doubles further on -- PfragT [set][step], GfragT [set][point][step], tlen
+// [set][node] -- wave-uniform, a scalar load and three scalar adds before the first fragment load.
+template <int NT, int KS, bool MIX = false, bool PART = false>
 __global__ void __launch_bounds__(64 * NT)
 bp_down_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT, int np, int nops,
                const int4 *__restrict__ steps, const double *__restrict__ Larr,
@@ -72,7 +86,8 @@ bp_down_kernel(const double *__restrict__ PfragT, const double *__restrict__ Gfr
                const double *__restrict__ obs, int K, const double *__restrict__ root_w,
                const double *__restrict__ tlen, int n, double *__restrict__ out,
                int *__restrict__ status, long nsites, long nblocks, double ck, int first,
-               double *__restrict__ root_tot)
+               double *__restrict__ root_tot, const int *__restrict__ gset, long gs_pt, long gs_gt,
+               long gs_t)
 {
     constexpr int KP = (KS + 1) / 2;
     __shared__ double xb[NT * 4 * 64];
@@ -82,6 +97,12 @@ bp_down_kernel(const double *__restrict__ PfragT, const double *__restrict__ Gfr
     const int lane = threadIdx.x & 63;
     const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long blk = blockIdx.x;
+    if constexpr (PART) {
+        const long gs = __builtin_amdgcn_readfirstlane(gset[blk]);
+        PfragT += gs * gs_pt;
+        GfragT += gs * gs_gt;
+        tlen += gs * gs_t;
+    }
     const long site = blk * 16 + (lane & 15);
     const bool site_ok = site < nsites;
     const bool writer = m == 0 && lane < 16 && site_ok;
@@ -175,7 +196,10 @@ bp_down_kernel(const double *__restrict__ PfragT, const double *__restrict__ Gfr
 
 // n <= 4: one lane per site; arrays [node][state][site], nodes in preorder; G [point][node][N][N]
 // (the same address in every lane: the scalar path).  MIX: as bp_down_kernel, P and G of the set.
-template <int N, bool MIX = false>
+// PART (sites are the batch's slots): a wave's 64 slots lie in one granule of 1 << gshift slots (256
+// or 64); P, G and tlen of its rate set are gset[site >> gshift] * (gs_p, gs_g, nnodes) doubles further on
+// ([set][node], [set][point][node], [set][node]) -- wave-uniform, so they stay scalar loads.
+template <int N, bool MIX = false, bool PART = false>
 __global__ void __launch_bounds__(256)
 bp_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const double *__restrict__ G,
                int np, const int *__restrict__ parent, const int *__restrict__ node_k,
@@ -183,10 +207,17 @@ bp_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const doub
                const double *__restrict__ root_w, const double *__restrict__ tlen,
                double *__restrict__ Larr, double *__restrict__ Marr, double *__restrict__ Darr,
                double *__restrict__ out, int *__restrict__ status, double ck, int first,
-               double *__restrict__ root_tot)
+               double *__restrict__ root_tot, const int *__restrict__ gset, int gshift, long gs_p,
+               long gs_g)
 {
     const long site = (long)blockIdx.x * 256 + threadIdx.x;
     if (site >= nsites) return;
+    if constexpr (PART) {
+        const long gs = __builtin_amdgcn_readfirstlane(gset[site >> gshift]);
+        P += gs * gs_p;
+        G += gs * gs_g;
+        tlen += gs * nnodes;
+    }
     auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
     lane_up<N, true>(nnodes, nsites, site, P, parent, node_k, obs, compact, K, block_sites, Larr, Marr);
     // down: the root, then every node after its parent
@@ -288,18 +319,24 @@ int rt_launch_set_grid_args(rt_ctx *ctx, int K, int np, int nnodes, const int32_
 
 namespace {
 
-// Both reads.  MIX = false: the pass runs once under the model's own matrices, `trial` are lengths
-// (post_grid), the plain kernel instance divides by L_i at the root.  MIX = true: once per rate set
-// of positive class weight, `trial` are factors (post_set_grid), the MIX instances accumulate and
-// post_mix turns the accumulator into the values.
-template <bool MIX>
+// The three reads.  MIX = false: the pass runs once under the model's own matrices, `trial` are
+// lengths (post_grid), the plain kernel instance divides by L_i at the root.  MIX = true: once per
+// rate set of positive class weight, `trial` are factors (post_set_grid), the MIX instances
+// accumulate and post_mix turns the accumulator into the values.  PART (a partitioned batch): the
+// pass runs once, every tile under the tables of its own set -- `trial` are factors, the set grid
+// makes matrices for the sets that have a site, the PART instance picks its tile's; the sums go per
+// set over the runs of the plan and the result leaves in caller order (post_part_result).
+template <bool MIX, bool PART = false>
 int bp_read(const char *who, rt_model *m, rt_sites *s, int recompute_transitions,
             const double *class_weights, int64_t npoints, const double *trial, double *values,
-            double *sums, double *loglik, int32_t *status)
+            double *sums, double *set_sums, double *loglik, int32_t *status)
 {
-    using grid_t = std::conditional_t<MIX, post_set_grid, post_grid>;
+    static_assert(!(MIX && PART), "a mixture is read on an ordinary batch");
+    using grid_t = std::conditional_t<MIX || PART, post_set_grid, post_grid>;
+    using result_t = std::conditional_t<PART, post_part_result, post_result>;
     post_pass p;                                 // (alive until the synchronisation below)
-    RT_TRY(post_open(&p, who, m, s));
+    if (PART) RT_TRY(post_partitioned_only(who, s));
+    RT_TRY(post_open(&p, who, m, s, PART));
     if (MIX) RT_TRY(post_class_weights(who, m, class_weights));
     RT_TRY(grid_t::check(&p, recompute_transitions, npoints, trial));
     const int64_t n = p.n, N = p.N, nsites = p.nsites;
@@ -311,7 +348,11 @@ int bp_read(const char *who, rt_model *m, rt_sites *s, int recompute_transitions
     // fragments and the tiled arguments of the exponential (the grid), the mixture's pieces
     grid_t grid;                                 // (alive until the synchronisation below)
     post_mix mix;
-    post_result res(values, sums);
+    post_part part;
+    result_t res = [&] {
+        if constexpr (PART) return post_part_result(values, sums, set_sums);
+        else return post_result(values, sums);
+    }();
     res.take_sums(&p, rows);
     res.take_chunk(&p, rows);
     size_t o_dead = 0, o_tl = 0;
@@ -320,12 +361,14 @@ int bp_read(const char *who, rt_model *m, rt_sites *s, int recompute_transitions
         o_dead = p.plan.take((size_t)N * 4);
         o_tl = p.plan.take((size_t)N * 8);
     }
+    if (PART) RT_TRY(part.take(&p));
     RT_TRY(grid.take(&p, np));
     RT_TRY(post_begin(&p, recompute_transitions));
     res.place(&p);
     hipStream_t st = p.st;
-    // what the sums go by: the resident lengths; MIX: 0 on an edge that is dead under a live set
-    const double *d_tlen = m->d_t;
+    // what the sums go by: the resident lengths; MIX: 0 on an edge that is dead under a live set;
+    // PART: those of every set
+    const double *d_tlen = PART ? m->multi.d_t : m->d_t;
     int *d_dead = nullptr;
     if (MIX) {
         RT_TRY(mix.begin(&p));
@@ -336,12 +379,14 @@ int bp_read(const char *who, rt_model *m, rt_sites *s, int recompute_transitions
         RT_HIP(hipGetLastError());
         d_tlen = d_tl;
     }
+    if (PART) RT_TRY(part.begin(&p));
     const std::vector<int32_t> internal = post_internal_nodes(&p);
     // 1. the trial matrices: one launch of the route the resident transitions take
     RT_TRY(grid.launch(&p, trial));
-    RT_TRY(post_up(&p, internal.data(), !MIX));
+    RT_TRY(post_up(&p, internal.data(), !MIX && !PART));
     if (!p.lane) {
         if (MIX) RT_TRY(mix.PT.pack(&p));
+        if (PART) RT_TRY(part.PT.pack(&p));
         RT_TRY(grid.pack(&p));
     }
     // 2. the pass; MIX: set by set (a set of weight zero is never live: not run, never read)
@@ -352,20 +397,29 @@ int bp_read(const char *who, rt_model *m, rt_sites *s, int recompute_transitions
         const double *P = m->d_P, *G = grid.d_G, *PT = p.d_PT, *GT = grid.d_GT, *tlen = m->d_t;
         int *stat = p.d_status;
         double *tot = nullptr;
+        const int *gset = nullptr;
+        int gshift = 0;
+        long gs_p = 0, gs_g = 0, gs_pt = 0, gs_gt = 0;
         if constexpr (MIX) {
             P = mix.P_of(&p, k); G = grid.G_of_set(&p, k);
             PT = mix.PT.of_set(k); GT = grid.GT_of_set(k);
             tlen = nullptr; stat = mix.status_of(&p, k); tot = mix.tot_of(&p, k);
         }
+        if constexpr (PART) {
+            P = m->multi.d_P; PT = part.PT.d_PT; tlen = m->multi.d_t;
+            gset = part.pt->d_granule_set; gshift = part.gshift();
+            gs_p = (long)m->multi.P_stride; gs_g = (long)((size_t)np * N * n * n);
+            gs_pt = part.pt_stride(); gs_gt = (long)((size_t)np * grid.tab);
+        }
         if (p.lane) {
             const int *d_tab = p.d_ptab;
             RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
-                hipLaunchKernelGGL((bp_lane_kernel<decltype(nv)::value, MIX>),
+                hipLaunchKernelGGL((bp_lane_kernel<decltype(nv)::value, MIX, PART>),
                                    dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)N,
                                    (long)nsites, P, G, np, d_tab, d_tab + N, (const void *)s->d_obs,
                                    s->compact_states, (int)s->nobs, s->block_sites,
                                    (const double *)m->d_root, tlen, p.d_L, p.d_M, p.d_D, res.d_val, stat,
-                                   ck, first, tot);
+                                   ck, first, tot, gset, gshift, gs_p, gs_g);
                 return RT_OK;
             }));
         } else {
@@ -373,12 +427,12 @@ int bp_read(const char *who, rt_model *m, rt_sites *s, int recompute_transitions
             if (MIX) RT_TRY(post_up_set(&p, k, nullptr));
             RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
                 constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
-                hipLaunchKernelGGL((bp_down_kernel<NT, KS, MIX>), dim3((unsigned)x->nblocks), dim3(64 * NT),
-                                   0, st, PT, GT, np, p.nops, (const int4 *)p.d_steps,
+                hipLaunchKernelGGL((bp_down_kernel<NT, KS, MIX, PART>), dim3((unsigned)x->nblocks),
+                                   dim3(64 * NT), 0, st, PT, GT, np, p.nops, (const int4 *)p.d_steps,
                                    (const double *)p.d_L, (const double *)p.d_M, p.d_D,
                                    (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root, tlen,
                                    (int)n, res.d_val, stat, (long)x->nsites, (long)x->nblocks, ck, first,
-                                   tot);
+                                   tot, gset, gs_pt, gs_gt, (long)N);
                 return RT_OK;
             }));
         }
@@ -392,7 +446,8 @@ int bp_read(const char *who, rt_model *m, rt_sites *s, int recompute_transitions
     }
     // 3. the weighted site sums and the per-site array
     RT_TRY(res.chunk(&p, 0, rows, np, d_tlen));
-    RT_TRY(res.finish(&p, status, loglik, mix.d_ll));
+    if constexpr (PART) RT_TRY(res.finish(&p, status));
+    else RT_TRY(res.finish(&p, status, loglik, mix.d_ll));
     return grid.result(&p);
 }
 
@@ -403,7 +458,7 @@ extern "C" int rt_sites_branch_profiles(rt_model *m, rt_sites *s, int recompute_
                                         double *sums, int32_t *status)
 {
     return bp_read<false>("rt_sites_branch_profiles", m, s, recompute_transitions, nullptr, npoints,
-                          lengths, values, sums, nullptr, status);
+                          lengths, values, sums, nullptr, nullptr, status);
 }
 
 extern "C" int rt_sites_branch_profiles_mixture(rt_model *m, rt_sites *s, int recompute_transitions,
@@ -412,5 +467,14 @@ extern "C" int rt_sites_branch_profiles_mixture(rt_model *m, rt_sites *s, int re
                                                 double *loglik, int32_t *status)
 {
     return bp_read<true>("rt_sites_branch_profiles_mixture", m, s, recompute_transitions,
-                         class_weights, npoints, factors, values, sums, loglik, status);
+                         class_weights, npoints, factors, values, sums, nullptr, loglik, status);
+}
+
+extern "C" int rt_sites_branch_profiles_partitioned(rt_model *m, rt_sites *s, int recompute_transitions,
+                                                    int64_t npoints, const double *factors,
+                                                    double *values, double *sums, double *set_sums,
+                                                    int32_t *status)
+{
+    return bp_read<false, true>("rt_sites_branch_profiles_partitioned", m, s, recompute_transitions,
+                                nullptr, npoints, factors, values, sums, set_sums, nullptr, status);
 }

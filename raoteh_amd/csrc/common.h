@@ -262,6 +262,7 @@ struct rt_partition {
     uint8_t *d_is_pad = nullptr;        // [padded]
     int32_t *d_granule_set = nullptr;   // [granules the kernel's grid covers]
     int64_t *d_run_begin = nullptr;     // [nsets + 1]
+    std::vector<int64_t> run_begin;     // (its host copy: an empty run is a set without a site)
     double *d_loglik = nullptr;         // [nsites] caller order (gathered after every step)
     int32_t *d_status = nullptr;
     int nblocks = 1;                    // stage-1 workgroups per set (from the plan alone)

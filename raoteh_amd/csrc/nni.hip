@@ -31,7 +31,11 @@
 // rt_sites_nni_scores_mixture: the same scores of an ORDINARY batch under a site-class mixture over
 // the model's K rate sets, trial lengths as factors of every set's own resident length of the edge
 // above v -- the kernels' MIX forms once per set into one accumulator, the root scaled by the class
-// weight instead of 1 / L_i.  One host body (nni_read, at the end) serves both calls.
+// weight instead of 1 / L_i.  One host body (nni_read, at the end) serves both calls, and
+// rt_sites_nni_scores_partitioned: the same scores of a PARTITIONED batch, every site under its own
+// rate set (under set k a moved subtree keeps its own edge of set k), trial lengths as factors -- one
+// pass with the kernels' PART forms, every tile under the tables of its granule's set, then the
+// per-set sums and the gather to caller order (post_part_result).
 #include "common.h"
 #include "post_common.h"
 
@@ -67,7 +71,12 @@ __device__ __forceinline__ double nni_value(double ratio, bool zero)
 // later ones (the same lane, launches in order: a fixed sum).  Every launch makes the `up` pass
 // (the scratch is the current set's), L_ik goes to root_tot[site], the status word is the set's
 // own, and the logs are mix_log_ratio_kernel's once the sets are in.
-template <int NT, int KS, bool MIX = false>
+// PART (rt_sites_nni_scores_partitioned: sites are the batch's slots, the output is in slot order):
+// the workgroup's tile is one granule; the fragment tables of its rate set are gset[tile] * (gs_pt,
+// gs_gt) doubles further on (PfragT [set][step], GfragT [set][point][step]; the plain swap: both
+// PfragT) -- wave-uniform, a scalar load and two scalar adds before the `up` pass, which takes the
+// set's PfragT as it is.
+template <int NT, int KS, bool MIX = false, bool PART = false>
 __global__ void __launch_bounds__(64 * NT, NT == 7 ? 4 : 1)
 nni_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT, int np, int nops,
            const int4 *__restrict__ steps, const int *__restrict__ tabp,
@@ -75,7 +84,7 @@ nni_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT,
            double *__restrict__ Uarr, const double *__restrict__ obs, int K,
            const double *__restrict__ root_w, int n, int mv0, int mv1, double *__restrict__ out,
            int *__restrict__ status, long nsites, long nblocks, double ck, int first,
-           double *__restrict__ root_tot)
+           double *__restrict__ root_tot, const int *__restrict__ gset, long gs_pt, long gs_gt)
 {
     constexpr int KP = (KS + 1) / 2;
     __shared__ double xb[NT * 4 * 64];
@@ -85,6 +94,11 @@ nni_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT,
     const int lane = threadIdx.x & 63;
     const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long blk = blockIdx.x;
+    if constexpr (PART) {
+        const long gs = __builtin_amdgcn_readfirstlane(gset[blk]);
+        PfragT += gs * gs_pt;
+        GfragT += gs * gs_gt;
+    }
     const long site = blk * 16 + (lane & 15);
     const bool site_ok = site < nsites;
     const bool writer = m == 0 && lane < 16 && site_ok;
@@ -207,7 +221,10 @@ nni_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT,
 // n <= 4: one lane per site; arrays [node][state][site], nodes in preorder; G [point][node][N][N]
 // or null for the resident P (the same address in every lane: the scalar path).  MIX: as
 // nni_kernel, P and G of the set.
-template <int N, bool MIX = false>
+// PART (sites are the batch's slots): a wave's 64 slots lie in one granule of 1 << gshift slots (256
+// or 64); P and G of its rate set are gset[site >> gshift] * (gs_p, gs_g) doubles further on ([set][node],
+// [set][point][node]) -- wave-uniform, so they stay scalar loads, in the `up` pass too.
+template <int N, bool MIX = false, bool PART = false>
 __global__ void __launch_bounds__(256)
 nni_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const double *__restrict__ G,
                 int np, const int *__restrict__ parent, const int *__restrict__ node_k,
@@ -215,10 +232,16 @@ nni_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const dou
                 int block_sites, const double *__restrict__ root_w, double *__restrict__ Larr,
                 double *__restrict__ Marr, double *__restrict__ Uarr, int mv0, int mv1,
                 double *__restrict__ out, int *__restrict__ status, double ck, int first,
-                double *__restrict__ root_tot)
+                double *__restrict__ root_tot, const int *__restrict__ gset, int gshift, long gs_p,
+                long gs_g)
 {
     const long site = (long)blockIdx.x * 256 + threadIdx.x;
     if (site >= nsites) return;
+    if constexpr (PART) {
+        const long gs = __builtin_amdgcn_readfirstlane(gset[site >> gshift]);
+        P += gs * gs_p;
+        G += gs * gs_g;                          // (the plain swap: the host gives P as G)
+    }
     const post_tab tab(tabp, nnodes);
     auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
     auto node_obs = [&](int v, double (&x)[N]) {
@@ -357,15 +380,21 @@ namespace {
 // instance, which makes the `up` pass every time and adds the term c_k L_ik(moved tree, tau) into
 // ONE accumulator [move][point][site] in set order; `trial` are factors (post_set_grid), post_mix
 // turns the accumulator into the values.  Nothing is divided before the end: exact where
-// L_ik == 0 on the resident tree.
-template <bool MIX>
+// L_ik == 0 on the resident tree.  PART (a partitioned batch): as MIX = false, every tile under the
+// tables of its own set -- `trial` are factors, the set grid makes matrices for the sets that have
+// a site, the PART instance picks its tile's; the sums go per set over the runs of the plan and the
+// result leaves in caller order (post_part_result).
+template <bool MIX, bool PART = false>
 int nni_read(const char *who, rt_model *m, rt_sites *s, int recompute_transitions,
              const double *class_weights, int64_t npoints, const double *trial, double *values,
-             double *sums, double *loglik, int32_t *status)
+             double *sums, double *set_sums, double *loglik, int32_t *status)
 {
-    using grid_t = std::conditional_t<MIX, post_set_grid, post_grid>;
+    static_assert(!(MIX && PART), "a mixture is read on an ordinary batch");
+    using grid_t = std::conditional_t<MIX || PART, post_set_grid, post_grid>;
+    using result_t = std::conditional_t<PART, post_part_result, post_result>;
     post_pass p;                                 // (alive until the synchronisation below)
-    RT_TRY(post_open(&p, who, m, s));
+    if (PART) RT_TRY(post_partitioned_only(who, s));
+    RT_TRY(post_open(&p, who, m, s, PART));
     if (MIX) RT_TRY(post_class_weights(who, m, class_weights));
     const int64_t n = p.n, N = p.N, nsites = p.nsites;
     // the moves; the rows of `trial` that count are those of the nodes with one
@@ -376,7 +405,7 @@ int nni_read(const char *who, rt_model *m, rt_sites *s, int recompute_transition
     for (int64_t v = 1; v < N; ++v) has_move[(size_t)v] = first[(size_t)v + 1] > first[(size_t)v];
     if (trial) RT_TRY(grid_t::check(&p, recompute_transitions, npoints, trial, has_move.data()));
     RT_REQUIRE(trial || npoints == 1, "%s: without %s the edge above v keeps its %s: 1 grid point "
-               "(%lld here)", who, MIX ? "factors" : "lengths", MIX ? "matrices" : "matrix",
+               "(%lld here)", who, MIX || PART ? "factors" : "lengths", MIX || PART ? "matrices" : "matrix",
                (long long)npoints);
     RT_REQUIRE(nmoves * npoints < (int64_t)1 << 31, "%s: too many moves", who);
     const int np = (int)npoints;
@@ -384,9 +413,14 @@ int nni_read(const char *who, rt_model *m, rt_sites *s, int recompute_transition
     RT_TRY(post_layout(&p, true));
     grid_t grid;                                 // (alive until the synchronisation below)
     post_mix mix;
-    post_result res(values, sums);
+    post_part part;
+    result_t res = [&] {
+        if constexpr (PART) return post_part_result(values, sums, set_sums);
+        else return post_result(values, sums);
+    }();
     if (trial) RT_TRY(grid.take(&p, np));
     if (MIX) RT_TRY(mix.take(&p, class_weights));
+    if (PART) RT_TRY(part.take(&p));
     const int cnt = p.lane ? (int)N : p.nops;    // slots of the move tables
     const size_t tab_ints = (size_t)4 * cnt;
     const size_t o_tab = p.plan.take(tab_ints * 4);
@@ -398,17 +432,19 @@ int nni_read(const char *who, rt_model *m, rt_sites *s, int recompute_transition
     RT_TRY(post_begin(&p, recompute_transitions));
     res.place(&p);
     if (MIX) RT_TRY(mix.begin(&p));
+    if (PART) RT_TRY(part.begin(&p));
     hipStream_t st = p.st;
     int *d_tab = (int *)(p.base + o_tab);
     const std::vector<int32_t> internal = post_internal_nodes(&p);
     if (trial) RT_TRY(grid.launch(&p, trial, has_move.data()));
-    RT_TRY(post_up(&p, internal.data(), !MIX));
+    RT_TRY(post_up(&p, internal.data(), !MIX && !PART));
     // the move tables, by step (n > 4) or by node
     std::vector<int32_t> tab;
     post_tab_build(&p, first.data(), &tab);
     RT_HIP(hipMemcpyAsync(d_tab, tab.data(), tab_ints * 4, hipMemcpyHostToDevice, st));
     if (!p.lane) {
         if (MIX) RT_TRY(mix.PT.pack(&p));
+        if (PART) RT_TRY(part.PT.pack(&p));
         if (trial) RT_TRY(grid.pack(&p));
     }
     for (int64_t mv0 = 0; mv0 == 0 || mv0 < nmoves; mv0 += CH) {
@@ -429,15 +465,27 @@ int nni_read(const char *who, rt_model *m, rt_sites *s, int recompute_transition
                 PT = mix.PT.of_set(k); GT = trial ? grid.GT_of_set(k) : PT;
                 stat = mix.status_of(&p, k); tot = mix.tot_of(&p, k);
             }
+            const int *gset = nullptr;
+            int gshift = 0;
+            long gs_p = 0, gs_g = 0, gs_pt = 0, gs_gt = 0;
+            if constexpr (PART) {
+                P = m->multi.d_P; PT = part.PT.d_PT; GT = trial ? grid.d_GT : PT;
+                gset = part.pt->d_granule_set; gshift = part.gshift();
+                // (n <= 4, the plain swap: the sets' P as the one-point grid [set][node])
+                if (!trial) G = P;
+                gs_p = (long)m->multi.P_stride; gs_g = trial ? (long)((size_t)np * N * n * n) : gs_p;
+                gs_pt = part.pt_stride(); gs_gt = trial ? (long)((size_t)np * grid.tab) : gs_pt;
+            }
             if (p.lane) {
                 const int *d_ptab = p.d_ptab;
                 RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
-                    hipLaunchKernelGGL((nni_lane_kernel<decltype(nv)::value, MIX>),
+                    hipLaunchKernelGGL((nni_lane_kernel<decltype(nv)::value, MIX, PART>),
                                        dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)N,
                                        (long)nsites, P, G, np, d_ptab, d_ptab + N, (const int *)d_tab,
                                        (const void *)s->d_obs, s->compact_states, (int)s->nobs,
                                        s->block_sites, (const double *)m->d_root, p.d_L, p.d_M, p.d_D,
-                                       (int)mv0, (int)mv1, res.d_val, stat, ck, first_set, tot);
+                                       (int)mv0, (int)mv1, res.d_val, stat, ck, first_set, tot, gset,
+                                       gshift, gs_p, gs_g);
                     return RT_OK;
                 }));
             } else {
@@ -445,12 +493,13 @@ int nni_read(const char *who, rt_model *m, rt_sites *s, int recompute_transition
                 if (MIX) RT_TRY(post_up_set(&p, k, nullptr));
                 RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
                     constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
-                    hipLaunchKernelGGL((nni_kernel<NT, KS, MIX>), dim3((unsigned)x->nblocks),
+                    hipLaunchKernelGGL((nni_kernel<NT, KS, MIX, PART>), dim3((unsigned)x->nblocks),
                                        dim3(64 * NT), 0, st, PT, GT, np, p.nops, (const int4 *)p.d_steps,
                                        (const int *)d_tab, (const double *)p.d_L, (const double *)p.d_M,
                                        p.d_D, (const double *)x->d_obs, (int)x->nobs,
                                        (const double *)m->d_root, (int)n, (int)mv0, (int)mv1, res.d_val,
-                                       stat, (long)x->nsites, (long)x->nblocks, ck, first_set, tot);
+                                       stat, (long)x->nsites, (long)x->nblocks, ck, first_set, tot,
+                                       gset, gs_pt, gs_gt);
                     return RT_OK;
                 }));
             }
@@ -463,7 +512,8 @@ int nni_read(const char *who, rt_model *m, rt_sites *s, int recompute_transition
         // the weighted site sums and the per-site array [site][nmoves][np]
         RT_TRY(res.chunk(&p, (size_t)mv0 * np, rows));
     }
-    RT_TRY(res.finish(&p, status, loglik, mix.d_ll));
+    if constexpr (PART) RT_TRY(res.finish(&p, status));
+    else RT_TRY(res.finish(&p, status, loglik, mix.d_ll));
     if (trial) RT_TRY(grid.result(&p));
     return RT_OK;
 }
@@ -475,7 +525,7 @@ extern "C" int rt_sites_nni_scores(rt_model *m, rt_sites *s, int recompute_trans
                                    double *sums, int32_t *status)
 {
     return nni_read<false>("rt_sites_nni_scores", m, s, recompute_transitions, nullptr, npoints, lengths,
-                           values, sums, nullptr, status);
+                           values, sums, nullptr, nullptr, status);
 }
 
 extern "C" int rt_sites_nni_scores_mixture(rt_model *m, rt_sites *s, int recompute_transitions,
@@ -484,6 +534,14 @@ extern "C" int rt_sites_nni_scores_mixture(rt_model *m, rt_sites *s, int recompu
                                            double *loglik, int32_t *status)
 {
     return nni_read<true>("rt_sites_nni_scores_mixture", m, s, recompute_transitions, class_weights,
-                          npoints, factors, values, sums, loglik, status);
+                          npoints, factors, values, sums, nullptr, loglik, status);
+}
+
+extern "C" int rt_sites_nni_scores_partitioned(rt_model *m, rt_sites *s, int recompute_transitions,
+                                               int64_t npoints, const double *factors, double *values,
+                                               double *sums, double *set_sums, int32_t *status)
+{
+    return nni_read<false, true>("rt_sites_nni_scores_partitioned", m, s, recompute_transitions, nullptr,
+                                 npoints, factors, values, sums, set_sums, nullptr, status);
 }
 

@@ -13,7 +13,9 @@
 //       post_set_fractions, the fraction grid of every set (place.hip, spr.hip);
 //   post_chunk_units and post_result: the chunks a result that does not fit the scratch is made
 //       in, the weighted site sums (post_sums_kernel) and the way of the result to the caller (the
-//       four tree-search reads);
+//       four tree-search reads); post_part and post_part_result: the same for a PARTITIONED batch
+//       (branch_profile.hip, nni.hip) -- the sets' fragments and which of them have a site, the
+//       per-set sums over the runs of the plan (post_part_sums_*) and the gather to caller order;
 //   post_csr_parents: the parents of a caller's CSR tree (nni.hip, spr.hip).
 // Device: the steps the downward kernels have in common; the division-free `up` pass (nni.hip,
 // place.hip, spr.hip).
@@ -130,7 +132,8 @@ inline int post_open(post_pass *p, const char *who, rt_model *m, rt_sites *s, bo
     RT_REQUIRE(m && s, "null pointer");
     if (s->part && !partitioned) {
         rt_set_error("%s: a partitioned batch is evaluated by rt_step_partitioned and read by "
-                     "rt_sites_branch_expectations_partitioned only", who);
+                     "rt_sites_branch_expectations_partitioned, rt_sites_branch_profiles_partitioned "
+                     "and rt_sites_nni_scores_partitioned only", who);
         return RT_ERR_UNSUPPORTED;
     }
     RT_REQUIRE(!partitioned || s->part, "%s: an ordinary batch (rt_sites_create_partitioned makes "
@@ -143,6 +146,19 @@ inline int post_open(post_pass *p, const char *who, rt_model *m, rt_sites *s, bo
     p->n = m->n; p->N = m->nnodes; p->nsites = s->nsites; p->nops = (int)s->ops.size();
     p->lane = s->layout == RT_LAYOUT_LANE;
     p->NT = (int)((p->n + 15) / 16); p->KS = (int)((p->n + 3) / 4); p->KP = (p->KS + 1) / 2;
+    return RT_OK;
+}
+
+// the tree-search reads of a partitioned batch refuse an ordinary one as every other read refuses
+// a batch it does not take (before post_open, whose own check stays that of
+// rt_sites_branch_expectations_partitioned)
+inline int post_partitioned_only(const char *who, const rt_sites *s)
+{
+    if (s && !s->part) {
+        rt_set_error("%s: an ordinary batch (rt_sites_create_partitioned makes the batches this "
+                     "call takes)", who);
+        return RT_ERR_UNSUPPORTED;
+    }
     return RT_OK;
 }
 
@@ -1351,6 +1367,249 @@ struct post_result {
             RT_HIP(hipMemcpyAsync(loglik, d_loglik, (size_t)p->nsites * 8, hipMemcpyDeviceToHost, p->st));
         if (status)
             RT_HIP(hipMemcpyAsync(status, p->d_status, (size_t)p->nsites * 4, hipMemcpyDeviceToHost, p->st));
+        RT_HIP(hipStreamSynchronize(p->st));
+        return RT_OK;
+    }
+};
+
+// ---- the same of a PARTITIONED batch (rt_sites_branch_profiles_partitioned,
+// rt_sites_nni_scores_partitioned): the kernels' PART forms leave values [row][slot]; the caller
+// gets set_sums [set][row], sums [row] and / or values [site][row] in caller order ----
+
+// stage 1 of the per-set sums (the shape of branch_expect.hip's part_sums_stage1_kernel, over rows
+// [row][slot]): workgroup (row, b, k) adds a contiguous piece of set k's run, thread t every BS-th
+// slot of it, then the BS partial sums by halves.  Pads, slots of zero likelihood and sites of
+// weight 0 (not -inf * 0 = NaN) are skipped; the weights are in caller order, through `order`.  The
+// shape comes from the plan alone: the same bits every call.
+template <int BS>
+__global__ void __launch_bounds__(BS)
+post_part_sums_stage1_kernel(long nslots, const double *__restrict__ values,
+                             const unsigned char *__restrict__ is_pad, const long *__restrict__ order,
+                             const long *__restrict__ run_begin, const double *__restrict__ weights,
+                             const int *__restrict__ status, double *__restrict__ part)
+{
+    __shared__ double sh[BS];
+    const size_t row = blockIdx.x, nrows = gridDim.x;
+    const int b = blockIdx.y, nblocks = gridDim.y, k = blockIdx.z, tid = threadIdx.x;
+    const long r0 = run_begin[k], r1 = run_begin[k + 1];
+    const long per = (r1 - r0 + nblocks - 1) / nblocks;
+    const long lo = r0 + (long)b * per, hi = lo + per < r1 ? lo + per : r1;
+    const double *x = values + row * nslots;
+    double acc = 0.0;
+    for (long slot = lo + tid; slot < hi; slot += BS) {
+        if (is_pad[slot] || (status[slot] & RT_SITE_ZERO_PROB)) continue;
+        const double w = weights ? weights[order[slot]] : 1.0;
+        if (w != 0.0) acc += w * x[slot];
+    }
+    sh[tid] = acc;
+    __syncthreads();
+    for (int h = BS / 2; h > 0; h >>= 1) {
+        if (tid < h) sh[tid] += sh[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) part[((size_t)k * nblocks + b) * nrows + row] = sh[0];
+}
+
+// stage 2: workgroup (row, k) adds set k's stage-1 sums of the row -> set_sums[k][row0 + row].
+// set_t (or null; rt_sites_branch_profiles_partitioned: rows [node][np], set_t [set][nnodes]): the
+// row of an edge of resident length 0 under a set with a site is NaN.
+template <int BS>
+__global__ void __launch_bounds__(BS)
+post_part_sums_stage2_kernel(const double *__restrict__ part, int nblocks, size_t total_rows,
+                             size_t row0, int np, int nnodes, const double *__restrict__ set_t,
+                             const long *__restrict__ run_begin, double *__restrict__ set_sums)
+{
+    __shared__ double sh[BS];
+    const size_t row = blockIdx.x, nrows = gridDim.x;
+    const int k = blockIdx.y, tid = threadIdx.x;
+    double acc = 0.0;
+    for (int b = tid; b < nblocks; b += BS) acc += part[((size_t)k * nblocks + b) * nrows + row];
+    sh[tid] = acc;
+    __syncthreads();
+    for (int h = BS / 2; h > 0; h >>= 1) {
+        if (tid < h) sh[tid] += sh[tid + h];
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    const size_t v = set_t ? (row0 + row) / np : 0;
+    const bool dead = v > 0 && run_begin[k + 1] > run_begin[k] && set_t[(size_t)k * nnodes + v] == 0.0;
+    set_sums[(size_t)k * total_rows + row0 + row] = dead ? __builtin_nan("") : sh[0];
+}
+
+// sums[row]: the per-set rows added in set order (one thread per row)
+template <int BS>
+__global__ void __launch_bounds__(BS)
+post_part_sums_total_kernel(int K, size_t total_rows, size_t row0, size_t nrows,
+                            const double *__restrict__ set_sums, double *__restrict__ sums)
+{
+    const size_t j = (size_t)blockIdx.x * BS + threadIdx.x;
+    if (j >= nrows) return;
+    double t = 0.0;
+    for (int k = 0; k < K; ++k) t += set_sums[(size_t)k * total_rows + row0 + j];
+    sums[row0 + j] = t;
+}
+
+// slot order -> caller order: rows [row][slot] -> [row][site]; status (or null) with row 0
+template <int BS>
+__global__ void __launch_bounds__(BS)
+post_part_gather_kernel(long nrows, long nslots, long nsites, const long *__restrict__ slot_of_site,
+                        const double *__restrict__ val_slot, double *__restrict__ val,
+                        const int *__restrict__ status_slot, int *__restrict__ status)
+{
+    const long i = (long)blockIdx.x * BS + threadIdx.x;
+    if (i >= nsites) return;
+    const long slot = slot_of_site[i];
+    if (status && blockIdx.y == 0) status[i] = status_slot[slot];
+    for (long r = blockIdx.y; r < nrows; r += gridDim.y)
+        val[(size_t)r * nsites + i] = val_slot[(size_t)r * nslots + slot];
+}
+
+// What a tree-search read of a partitioned batch holds beside the single-set one: the sets of the
+// batch, a "class weight" per set of the model for post_set_grid (1 for a set with a site, 0 for an
+// empty one and for the model's sets past the batch's: no matrices are made for them) and the
+// sets' P^T fragments.  The strides are what the kernels' PART forms add per set.
+struct post_part {
+    const rt_partition *pt = nullptr;
+    int64_t K = 0;                               // the batch's sets
+    post_set_pt PT;
+    std::vector<double> live;                    // [the model's sets]
+    size_t o_live = 0;
+
+    // after post_layout
+    int take(post_pass *p)
+    {
+        const rt_rate_sets &r = p->m->multi;
+        RT_REQUIRE(r.P_stride == p->N * p->n * p->n, "unexpected stride of the sets' transition matrices");
+        pt = p->s->part; K = pt->nsets;
+        RT_REQUIRE((int64_t)pt->run_begin.size() == K + 1, "%s: the batch has no plan", p->who);
+        RT_REQUIRE(pt->G >= 16 && (pt->G & (pt->G - 1)) == 0, "%s: unexpected granule %lld", p->who,
+                   (long long)pt->G);
+        live.assign((size_t)r.K, 0.0);
+        for (int64_t k = 0; k < K; ++k)
+            live[(size_t)k] = pt->run_begin[(size_t)k + 1] > pt->run_begin[(size_t)k] ? 1.0 : 0.0;
+        PT.take(p, K);
+        o_live = p->plan.take(live.size() * 8);
+        return RT_OK;
+    }
+    // after post_begin
+    int begin(post_pass *p)
+    {
+        PT.place(p);
+        p->d_cw = (double *)(p->base + o_live);
+        RT_HIP(hipMemcpyAsync(p->base + o_live, live.data(), live.size() * 8, hipMemcpyHostToDevice, p->st));
+        return RT_OK;
+    }
+    long pt_stride() const { return (long)(PT.tab / 8); }
+    // n <= 4: the granule (256 or 64 slots) as the shift that takes a slot to its granule
+    int gshift() const
+    {
+        int sh = 0;
+        while (((int64_t)1 << sh) < pt->G) ++sh;
+        return sh;
+    }
+};
+
+// post_result's interface for a partitioned batch: p->nsites counts the slots, the caller's arrays
+// hold the pt->nsites real sites.
+struct post_part_result {
+    double *values, *sums, *set_sums;            // [site][rows], [rows], [set][rows], or null
+    size_t rows = 0, slab = 0, chunk_rows = 0;
+    size_t o_sum = 0, o_setsum = 0, o_part = 0, o_val = 0, o_valc = 0, o_valT = 0, o_statc = 0;
+    double *d_sum = nullptr, *d_setsum = nullptr, *d_part = nullptr, *d_val = nullptr;
+    double *d_valc = nullptr, *d_valT = nullptr;
+    int *d_statc = nullptr;
+
+    post_part_result(double *v, double *s, double *ss) : values(v), sums(s), set_sums(ss) {}
+    // scratch bytes of one row: the values in slot order, the stage-1 sums, and where the caller
+    // takes the values, those in caller order and their transpose
+    size_t row_bytes(const post_pass *p) const
+    {
+        const rt_partition *pt = p->s->part;
+        return (size_t)p->nsites * 8 + (size_t)pt->nsets * pt->nblocks * 8 +
+               (values ? (size_t)pt->nsites * 16 : 0);
+    }
+    void take_sums(post_pass *p, size_t total_rows)
+    {
+        const rt_partition *pt = p->s->part;
+        rows = total_rows;
+        o_sum = p->plan.take(std::max<size_t>(rows, 1) * 8);
+        o_setsum = p->plan.take(std::max<size_t>(rows, 1) * pt->nsets * 8);
+        o_statc = p->plan.take((size_t)pt->nsites * 4);
+    }
+    void take_chunk(post_pass *p, size_t nrows, size_t max_rows = ~(size_t)0)
+    {
+        const rt_partition *pt = p->s->part;
+        chunk_rows = nrows;
+        slab = std::min(chunk_rows, max_rows);
+        o_val = p->plan.take(chunk_rows * p->nsites * 8);
+        o_part = p->plan.take(std::max<size_t>(chunk_rows, 1) * pt->nsets * pt->nblocks * 8);
+        o_valc = p->plan.take(values ? chunk_rows * pt->nsites * 8 : 8);
+        o_valT = p->plan.take(values ? slab * pt->nsites * 8 : 8);
+    }
+    // after post_begin
+    void place(const post_pass *p)
+    {
+        d_sum = (double *)(p->base + o_sum); d_setsum = (double *)(p->base + o_setsum);
+        d_part = (double *)(p->base + o_part); d_val = (double *)(p->base + o_val);
+        d_valc = (double *)(p->base + o_valc); d_valT = (double *)(p->base + o_valT);
+        d_statc = (int *)(p->base + o_statc);
+    }
+    // the chunk's nrows rows at d_val are rows row0 .. of the result.  np, d_set_t: the NaN rule of
+    // post_part_sums_stage2_kernel.
+    template <int BS = 256>
+    int chunk(post_pass *p, size_t row0, size_t nrows, int np = 1, const double *d_set_t = nullptr)
+    {
+        const rt_partition *pt = p->s->part;
+        const long nslots = (long)p->nsites, nreal = (long)pt->nsites;
+        const int K = (int)pt->nsets, nb = pt->nblocks;
+        if (sums || set_sums) {
+            hipLaunchKernelGGL(post_part_sums_stage1_kernel<BS>, dim3((unsigned)nrows, (unsigned)nb, (unsigned)K),
+                               dim3(BS), 0, p->st, nslots, (const double *)d_val,
+                               (const unsigned char *)pt->d_is_pad, (const long *)pt->d_order,
+                               (const long *)pt->d_run_begin, (const double *)p->s->d_weights,
+                               (const int *)p->d_status, d_part);
+            hipLaunchKernelGGL(post_part_sums_stage2_kernel<BS>, dim3((unsigned)nrows, (unsigned)K), dim3(BS),
+                               0, p->st, (const double *)d_part, nb, rows, row0, np, (int)p->N, d_set_t,
+                               (const long *)pt->d_run_begin, d_setsum);
+            hipLaunchKernelGGL(post_part_sums_total_kernel<BS>, dim3((unsigned)((nrows + BS - 1) / BS)),
+                               dim3(BS), 0, p->st, K, rows, row0, nrows, (const double *)d_setsum, d_sum);
+            RT_HIP(hipGetLastError());
+        }
+        if (!values) return RT_OK;
+        hipLaunchKernelGGL(post_part_gather_kernel<BS>,
+                           dim3((unsigned)((nreal + BS - 1) / BS), (unsigned)std::min<size_t>(nrows, 1024)),
+                           dim3(BS), 0, p->st, (long)nrows, nslots, nreal, (const long *)pt->d_slot_of_site,
+                           (const double *)d_val, d_valc, (const int *)nullptr, (int *)nullptr);
+        RT_HIP(hipGetLastError());
+        for (size_t r0 = 0; r0 < nrows; r0 += slab) {
+            const size_t nr = std::min(slab, nrows - r0);
+            hipLaunchKernelGGL(post_transpose_kernel<32>,
+                               dim3((unsigned)((nreal + 31) / 32), (unsigned)((nr + 31) / 32)), dim3(256),
+                               0, p->st, (long)nr, nreal, (const double *)(d_valc + r0 * nreal), d_valT);
+            RT_HIP(hipGetLastError());
+            RT_HIP(hipMemcpy2DAsync(values + row0 + r0, rows * 8, d_valT, nr * 8, nr * 8, (size_t)nreal,
+                                    hipMemcpyDeviceToHost, p->st));
+        }
+        return RT_OK;
+    }
+    // after the last chunk: the sums and the status (caller order) to the caller; the stream is
+    // synchronised
+    template <int BS = 256>
+    int finish(post_pass *p, int32_t *status)
+    {
+        const rt_partition *pt = p->s->part;
+        const long nreal = (long)pt->nsites;
+        if (sums && rows) RT_HIP(hipMemcpyAsync(sums, d_sum, rows * 8, hipMemcpyDeviceToHost, p->st));
+        if (set_sums && rows)
+            RT_HIP(hipMemcpyAsync(set_sums, d_setsum, rows * pt->nsets * 8, hipMemcpyDeviceToHost, p->st));
+        if (status) {
+            hipLaunchKernelGGL(post_part_gather_kernel<BS>, dim3((unsigned)((nreal + BS - 1) / BS), 1u),
+                               dim3(BS), 0, p->st, 0L, (long)p->nsites, nreal,
+                               (const long *)pt->d_slot_of_site, (const double *)nullptr, (double *)nullptr,
+                               (const int *)p->d_status, d_statc);
+            RT_HIP(hipGetLastError());
+            RT_HIP(hipMemcpyAsync(status, d_statc, (size_t)nreal * 4, hipMemcpyDeviceToHost, p->st));
+        }
         RT_HIP(hipStreamSynchronize(p->st));
         return RT_OK;
     }

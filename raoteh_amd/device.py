@@ -324,6 +324,19 @@ MixtureNniScores = collections.namedtuple('MixtureNniScores',
                                           'moves factors sums values loglik status')
 
 
+# TreeModel.branch_profiles_partitioned: factors [nnodes, G] as evaluated, values [nsites, nnodes,
+# G] in caller order (or None), sums [nnodes, G], set_sums [nsets, nnodes, G] the weighted sums over
+# each rate set's sites (zeros for an empty set; sums is their sum in set order), status, nodes
+PartitionedBranchProfiles = collections.namedtuple(
+    'PartitionedBranchProfiles', 'factors values sums set_sums status nodes')
+
+# TreeModel.nni_scores_partitioned: moves as NniScores, factors [nnodes, G] as evaluated (None for
+# the plain swap), values [nsites, nmoves, G] in caller order (or None), sums [nmoves, G], set_sums
+# [nsets, nmoves, G], status
+PartitionedNniScores = collections.namedtuple(
+    'PartitionedNniScores', 'moves factors values sums set_sums status')
+
+
 def check_profile_factors(factors, nnodes):
     """The trial lengths of TreeModel.branch_profiles_mixture / nni_scores_mixture, as factors of
     every class's own resident branch lengths -> f64[nnodes, G], C-contiguous, row 0 (the
@@ -1728,6 +1741,76 @@ class TreeModel(object):
             None if values is None else _ptr(values, c_double), _ptr(sums, c_double),
             _ptr(ll, c_double), _ptr(status, c_int32)))
         return MixtureNniScores(moves, grid, sums, values, ll, status)
+
+    def _partitioned_search_args(self, batch, who):
+        nsets = int(getattr(batch, 'nsets', 0) or 0)
+        if batch.site_sets is None or nsets < 1:
+            raise ValueError('%s takes a batch uploaded with site_sets (an ordinary batch: %s)'
+                             % (who, who[:-len('_partitioned')]))
+        K = int(getattr(self, '_nsets', 0) or 0)
+        if K < 1:
+            raise ValueError('set_rate_sets has not been called')
+        if K < nsets:
+            raise ValueError('the batch uses nsets=%d rate sets, set_rate_sets gave %d'
+                             % (nsets, K))
+        return nsets
+
+    def branch_profiles_partitioned(self, batch, factors, per_site=False,
+                                    recompute_transitions=False):
+        """rt_sites_branch_profiles_partitioned: branch_profiles for a batch uploaded with
+        site_sets -- site i reads every edge under its own rate set of set_rate_sets.  Trial
+        lengths are `factors` of every set's own resident lengths (check_profile_factors): at
+        point g the edge above v has length factors[v, g] * t[k][v] under set k.  Returns a
+        PartitionedBranchProfiles tuple: factors [nnodes, G] as evaluated, values[i, v, g] =
+        log L_i(t[k][v] -> factors[v, g] t[k][v]) - log L_i in caller order (None unless
+        per_site: the array never leaves the device), sums[v, g] the site-weighted sum over the
+        batch, set_sums[k, v, g] the same over set k's sites (zeros for an empty set), status,
+        nodes.  The root's row is 0; where t[k][v] == 0 row v is NaN for the live sites of set
+        k, in set_sums[k] and in sums.  No earlier step_partitioned is needed; nothing the
+        batch or the model holds changes."""
+        nsets = self._partitioned_search_args(batch, 'branch_profiles_partitioned')
+        ta = self.tree
+        N, S = ta.nnodes, batch.nsites
+        grid = check_profile_factors(factors, N)
+        G = grid.shape[1]
+        values = np.zeros((S, N, G)) if per_site else None
+        sums = np.zeros((N, G))
+        set_sums = np.zeros((nsets, N, G))
+        status = np.zeros(S, dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_branch_profiles_partitioned(
+            self._h, batch._h, 1 if recompute_transitions else 0, G, _ptr(grid, c_double),
+            None if values is None else _ptr(values, c_double), _ptr(sums, c_double),
+            _ptr(set_sums, c_double), _ptr(status, c_int32)))
+        return PartitionedBranchProfiles(grid, values, sums, set_sums, status,
+                                         list(ta.preorder_nodes))
+
+    def nni_scores_partitioned(self, batch, factors=None, per_site=False,
+                               recompute_transitions=False):
+        """rt_sites_nni_scores_partitioned: nni_scores for a batch uploaded with site_sets, for
+        every move of nni_moves() -- under set k the moved tree keeps every moved subtree's own
+        edge of set k.  Without `factors` every set keeps its resident matrix on the edge above
+        v (the plain swap); else the moves about v are scored with that edge at factors[v, g] *
+        t[k][v] under set k (check_profile_factors; rows of nodes without a move are ignored).
+        Returns a PartitionedNniScores tuple: moves, factors [nnodes, G] as evaluated (None for
+        the plain swap), values[i, mv, g] in caller order (None unless per_site), sums[mv, g],
+        set_sums[k, mv, g] over set k's sites (zeros for an empty set), status.  -inf where a
+        live site has likelihood 0 on the moved tree."""
+        nsets = self._partitioned_search_args(batch, 'nni_scores_partitioned')
+        N, S = self.tree.nnodes, batch.nsites
+        moves = self.nni_moves()
+        grid = None if factors is None else check_profile_factors(factors, N)
+        G = 1 if grid is None else grid.shape[1]
+        M = len(moves)
+        values = np.zeros((S, M, G)) if per_site else None
+        sums = np.zeros((M, G))
+        set_sums = np.zeros((nsets, M, G))
+        status = np.zeros(S, dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_nni_scores_partitioned(
+            self._h, batch._h, 1 if recompute_transitions else 0, G,
+            None if grid is None else _ptr(grid, c_double),
+            None if values is None else _ptr(values, c_double), _ptr(sums, c_double),
+            _ptr(set_sums, c_double), _ptr(status, c_int32)))
+        return PartitionedNniScores(moves, grid, values, sums, set_sums, status)
 
     def spr_moves(self, radius=None):
         """rt_model_spr_moves: the subtree pruning and regrafting moves of the tree within
