@@ -1009,8 +1009,42 @@ const char *rt_sites_multi_kernel_name(const rt_sites *sites);
  *   the batch's nsets; a batch of another model; npoints outside 1..RT_MAX_PROFILE_POINTS; factors
  *   NULL (NNI: with npoints != 1); a factor that is negative or not finite.
  *   RT_ERR_UNSUPPORTED: an ordinary batch, a "rescale" or generic-kernel batch, a tree deeper than the
- *   fast kernels take, more than 96 GB of scratch.  RT_ERR_SINGULAR: a failed exponential.  SPR
- *   scores and placements of a partitioned batch are not offered yet.
+ *   fast kernels take, more than 96 GB of scratch.  RT_ERR_SINGULAR: a failed exponential.
+ * rt_sites_spr_scores_partitioned, rt_sites_placements_partitioned: rt_sites_spr_scores and
+ *   rt_sites_placements (above) for a partitioned batch, every site under its own set as for the
+ *   two reads before.  SPR: the moves of rt_model_spr_moves(model, radius); under set k the edge
+ *   above y is cut at fractions[r] of the set's own resident length t[k][y] and the pruned subtree
+ *   keeps its own edge of set k.  Placements: the cut edge likewise; the pendant edge has length
+ *   pendant_scale[k] * pendant[j] under Q[k][node_q[v]].
+ *     fractions       f64[nfractions], 1 <= nfractions <= RT_MAX_PLACE_FRACTIONS, in [0, 1]
+ *     pendant         f64[npendant], 1 <= npendant <= RT_MAX_PLACE_PENDANT, finite, >= 0;
+ *                     2 nfractions + npendant <= 32
+ *     pendant_scale   f64[the model's sets], finite, >= 0; NULL: ones (as
+ *                     rt_sites_placements_mixture)
+ *     queries         RT_OBS_DENSE f64[nqueries][nsites][n] or RT_OBS_STATE uint8[nqueries][nsites]
+ *                     in CALLER order over the real sites (the caller never sees slots or pads:
+ *                     the library brings a chunk's queries to slot order on the device)
+ *     values          f64[nsites][nmoves][nfractions] /
+ *                     f64[nsites][nqueries][nnodes][nfractions][npendant] in CALLER order, real
+ *                     sites only (the root's rows are 0): -inf where a live site has likelihood 0
+ *                     after the change; a site of zero likelihood under its set: zeros
+ *                     (RT_SITE_ZERO_PROB).  Division-free and exact at t[k][v] == 0: no NaN rule
+ *     set_sums        f64[nsets][rows]: as above (a site of weight 0 adds nothing even at -inf;
+ *                     zeros for an empty set);  sums f64[rows]: the per-set rows added in set order
+ *     status          int32[nsites] in caller order
+ *   Each output may be NULL; only what is given crosses PCIe.  The matrices of all sets with a
+ *   site (both halves of every cut edge, the pendant edges) come from ONE launch of the sets'
+ *   exponential, their fragments are packed once, and per chunk ONE launch of every kernel runs with
+ *   every 16-site tile (n <= 4: every wave) under the tables of its granule's set.  Grid limits,
+ *   chunks (RAOTEH_SPR_CHUNK_BYTES over pruned nodes, RAOTEH_PLACE_CHUNK_BYTES over queries), the
+ *   96 GB cap and nmoves == 0 (RT_OK, only status is written) are those of the single-set calls.
+ *   Synchronous; two calls return the same bits, chunked or not; the batch's log-likelihoods, status
+ *   and totals, the model's transitions and rate sets keep what they had.  RT_ERR_INVALID: fewer
+ *   rate sets resident in the model than the batch's nsets; a batch of another model; counts,
+ *   fractions, pendant lengths or scales out of range; NULL fractions, pendant or queries; a
+ *   query_kind that is no observation kind.  RT_ERR_UNSUPPORTED: an ordinary batch, a "rescale" or
+ *   generic-kernel batch, RT_OBS_MASK queries, more than 96 GB of scratch.  RT_ERR_SINGULAR: a
+ *   failed exponential.
  * Everything else refuses a partitioned batch with RT_ERR_UNSUPPORTED and leaves it untouched:
  *   rt_prune, rt_step, rt_step_multi, rt_sites_clone, rt_expect_step, rt_sites_posteriors,
  *   rt_sites_branch_expectations, rt_sites_branch_profiles, rt_sites_sample_states,
@@ -1036,6 +1070,14 @@ int rt_sites_branch_profiles_partitioned(rt_model *model, rt_sites *sites, int r
 int rt_sites_nni_scores_partitioned(rt_model *model, rt_sites *sites, int recompute_transitions,
             int64_t npoints, const double *factors, double *values, double *sums,
             double *set_sums, int32_t *status);
+int rt_sites_spr_scores_partitioned(rt_model *model, rt_sites *sites, int recompute_transitions,
+            int64_t radius, int64_t nfractions, const double *fractions,
+            double *values, double *sums, double *set_sums, int32_t *status);
+int rt_sites_placements_partitioned(rt_model *model, rt_sites *sites, int recompute_transitions,
+            int64_t nqueries, int query_kind, const void *queries,
+            int64_t nfractions, const double *fractions, int64_t npendant, const double *pendant,
+            const double *pendant_scale, double *values, double *sums, double *set_sums,
+            int32_t *status);
 /* what the batch was laid out with: any pointer may be NULL; an ordinary batch gives zeros */
 int rt_sites_partition_info(const rt_sites *sites, int64_t *nsets, int64_t *granule,
             int64_t *padded);

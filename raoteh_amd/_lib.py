@@ -184,6 +184,11 @@ SIGNATURES = {
                                                      _p_f64, _p_f64, _p_i32]),
     'rt_sites_nni_scores_partitioned': (c_int, [c_void_p, c_void_p, c_int, c_int64, _p_f64, _p_f64,
                                                 _p_f64, _p_f64, _p_i32]),
+    'rt_sites_spr_scores_partitioned': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, _p_f64,
+                                                _p_f64, _p_f64, _p_f64, _p_i32]),
+    'rt_sites_placements_partitioned': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p,
+                                                c_int64, _p_f64, c_int64, _p_f64, _p_f64, _p_f64,
+                                                _p_f64, _p_f64, _p_i32]),
     'rt_sites_branch_expectations_mixture': (c_int, [c_void_p, c_void_p, c_int, _p_f64, c_int64, c_int,
                                                      _p_f64, _p_f64, _p_f64, _p_f64, _p_f64, _p_f64,
                                                      _p_f64, _p_i32]),

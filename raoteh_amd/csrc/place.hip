@@ -38,8 +38,12 @@
 // over the model's K rate sets -- the cut edge at fractions of every set's own resident length, the
 // pendant edge at pendant_scale[k] tau under the set's rate matrix; the kernels' MIX forms once per
 // set and chunk of queries into one accumulator, the root scaled by the class weight instead of
-// 1 / L_i; the field holds one set at a time.  One host body (place_read, at the end) serves both
-// calls.
+// 1 / L_i; the field holds one set at a time.
+// rt_sites_placements_partitioned: the same placements of a PARTITIONED batch, every site under its
+// own rate set, the queries in the caller's site order -- the kernels' PART forms, every tile under
+// the tables of its granule's set, one field and per chunk of queries one launch of each; the
+// per-set sums and the gather to caller order are post_part_result's.  One host body (place_read,
+// at the end) serves the three calls.
 #include "common.h"
 #include "post_common.h"
 
@@ -73,6 +77,8 @@ struct place_mix {
 struct place_plain {};
 __device__ __forceinline__ place_plain place_args() { return {}; }
 __device__ __forceinline__ place_mix place_args(place_mix a) { return a; }
+// (a PART instance's pack holds the post_part_arg instead: post_common.h)
+__device__ __forceinline__ post_part_arg place_args(post_part_arg a) { return a; }
 
 // n > 4.  steps as in nni_kernel (steps[i].w: the node has children); PfragT: [step] A fragments
 // of the resident P^T; GfragT: [fraction][step] those of P(rho t)^T; GfragA: [fraction][step]
@@ -80,7 +86,10 @@ __device__ __forceinline__ place_mix place_args(place_mix a) { return a; }
 // [step * R + fraction] in the layout of L and M.
 // MIX: the set's fragments; down_up_pass's MIX form (the root scaled by ck, L_ik to root_tot, the
 // status word the set's own), so the field is c_k times the unnormalised one.
-template <int NT, int KS, bool MIX = false, class... MX>
+// PART (rt_sites_placements_partitioned: sites are the batch's slots): the plain field, the tile
+// under the tables of its granule's set -- PfragT [set][step], GfragT / GfragA [set][fraction][step]
+// moved on by set * (s_p, s_g) doubles before anything else.
+template <int NT, int KS, bool MIX = false, bool PART = false, class... MX>
 __global__ void __launch_bounds__(64 * NT)
 place_field_kernel(const double *__restrict__ PfragT, const double *__restrict__ GfragT,
                    const double *__restrict__ GfragA, int R, int nops,
@@ -90,7 +99,8 @@ place_field_kernel(const double *__restrict__ PfragT, const double *__restrict__
                    const double *__restrict__ root_w, int n, double *__restrict__ Farr,
                    int *__restrict__ status, long nsites, long nblocks, MX... mix)
 {
-    static_assert(sizeof...(MX) == (MIX ? 1 : 0), "place_mix: the MIX instance's alone");
+    static_assert(sizeof...(MX) == (MIX || PART ? 1 : 0) && !(MIX && PART),
+                  "place_mix: the MIX instance's alone; post_part_arg: the PART instance's");
     [[maybe_unused]] const auto mx = place_args(mix...);
     constexpr int KP = (KS + 1) / 2;
     __shared__ double xb[NT * 4 * 64];
@@ -100,6 +110,12 @@ place_field_kernel(const double *__restrict__ PfragT, const double *__restrict__
     const int lane = threadIdx.x & 63;
     const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long blk = blockIdx.x;
+    if constexpr (PART) {
+        const long gs = post_part_set(mx, blk);
+        PfragT += gs * mx.s_p;
+        GfragT += gs * mx.s_g;
+        GfragA += gs * mx.s_g;
+    }
     const long site = blk * 16 + (lane & 15);
     const bool writer = m == 0 && lane < 16 && site < nsites;
     bool live[4];                                // own rows that are states
@@ -165,17 +181,27 @@ place_field_kernel(const double *__restrict__ PfragT, const double *__restrict__
 // rep[d] the node that stands for distinct matrix d.  dense: queries f64[QC][nsites][n], staged
 // and multiplied on the matrix pipe; else uint8[QC][nsites]: column o of the matrix, or its row
 // sums where o >= n (unobserved).  Harr: [(d * K + k) * QC + q] in the layout of L and M.
-template <int NT, int KS>
+// PART (queries in slot order: place_query_gather_kernel): HfragA [set][pendant][distinct] and Gtau
+// [set][point][node] of the tile's set, moved on by set * (s_p, s_g) doubles.
+template <int NT, int KS, bool PART = false, class... PX>
 __global__ void __launch_bounds__(64 * NT)
 place_query_kernel(int dense, const void *__restrict__ queries, const double *__restrict__ HfragA,
                    const double *__restrict__ Gtau, const int *__restrict__ rep, int nd, int K,
-                   int QC, int N, int n, double *__restrict__ Harr, long nsites, long nblocks)
+                   int QC, int N, int n, double *__restrict__ Harr, long nsites, long nblocks,
+                   PX... part)
 {
+    static_assert(sizeof...(PX) == (PART ? 1 : 0), "post_part_arg: the PART instance's alone");
     constexpr int KP = (KS + 1) / 2;
     __shared__ double xb[NT * 4 * 64];
     const int lane = threadIdx.x & 63;
     const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long blk = blockIdx.x;
+    if constexpr (PART) {
+        const post_part_arg px = post_pack_one(part...);
+        const long gs = post_part_set(px, blk);
+        HfragA += gs * px.s_p;
+        Gtau += gs * px.s_g;
+    }
     const int q = blockIdx.y;
     const long site = blk * 16 + (lane & 15);
     const bool site_ok = site < nsites;
@@ -315,8 +341,9 @@ place_score_kernel(int nops, int R, int K, int QC, int nd, const int4 *__restric
 // dnode[v] the distinct matrix of node v, rep[d] the node that stands for it.  make: the first
 // chunk makes the upward pass, the `up` pass and the field, later ones find them.
 // MIX: P and G of the set, make != 0 in every launch (the scratch is the current set's); the terms
-// as in place_score_kernel.
-template <int N, bool MIX = false, class... MX>
+// as in place_score_kernel.  PART (sites are the batch's slots, the queries in slot order): P
+// [set][node] and G [set][point][node] of the set of the wave's granule, wave-uniform.
+template <int N, bool MIX = false, bool PART = false, class... MX>
 __global__ void __launch_bounds__(256)
 place_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const double *__restrict__ G,
                   int R, int K, const int *__restrict__ parent, const int *__restrict__ node_k,
@@ -327,10 +354,16 @@ place_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const d
                   double *__restrict__ Farr, int dense, const void *__restrict__ queries, int QC,
                   int make, double *__restrict__ out, int *__restrict__ status, MX... mix)
 {
-    static_assert(sizeof...(MX) == (MIX ? 1 : 0), "place_mix: the MIX instance's alone");
+    static_assert(sizeof...(MX) == (MIX || PART ? 1 : 0) && !(MIX && PART),
+                  "place_mix: the MIX instance's alone; post_part_arg: the PART instance's");
     [[maybe_unused]] const auto mx = place_args(mix...);
     const long site = (long)blockIdx.x * 256 + threadIdx.x;
     if (site >= nsites) return;
+    if constexpr (PART) {
+        const long gs = post_part_set(mx, site >> mx.gshift);
+        P += gs * mx.s_p;
+        G += gs * mx.s_g;
+    }
     const post_tab tab(tabp, nnodes);
     auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
     if (make)
@@ -417,6 +450,22 @@ place_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const d
     }
 }
 
+// rt_sites_placements_partitioned: a chunk's queries from caller order [QC][nsites][width] to slot
+// order [QC][nslots][width] (width: n doubles, or one byte) -- slot j takes the query of its source
+// site order[j], a pad that of the site it repeats.
+template <class T, int BS>
+__global__ void __launch_bounds__(BS)
+place_query_gather_kernel(long nslots, long nsites, int width, const long *__restrict__ order,
+                          const T *__restrict__ in, T *__restrict__ out)
+{
+    const long j = (long)blockIdx.x * BS + threadIdx.x;
+    if (j >= nslots * width) return;
+    const long slot = j / width;
+    const int e = (int)(j - slot * width);
+    const size_t q = blockIdx.y;
+    out[(q * nslots + slot) * width + e] = in[(q * nsites + order[slot]) * width + e];
+}
+
 // Both reads.  MIX = false: the grid of the model's own exponential (post_grid: 2 R + K points per
 // node), the upward pass, the `up` pass and the field once, then the queries in chunks.  MIX = true:
 // the sets' grid (post_set_grid: the factors rho_r, 1 - rho_r of every set's own length and K
@@ -425,17 +474,26 @@ place_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const d
 // the set's upward pass (post_up_set), the MIX field (the root scaled by c_k), the set's pendant
 // vectors and the MIX scores, which add c_k L_ik(query placed) into ONE accumulator in set order;
 // post_mix turns it into the values, the root's rows are cleared afterwards.  node_q is shared by
-// the sets: the distinct matrices in use (dnode, rep) are found once.
-template <bool MIX>
+// the sets: the distinct matrices in use (dnode, rep) are found once.  PART (a partitioned batch):
+// as MIX = false -- the sets' grid and fragment tables as for MIX, made for the sets that have a
+// site; the field once and per chunk one launch of the PART instances, every tile under the tables
+// of its own set; a chunk's queries arrive in caller order and are brought to slot order on the
+// device (place_query_gather_kernel: the chunk's scratch holds both images); the sums go per set
+// and the result leaves in caller order (post_part_result).
+template <bool MIX, bool PART = false>
 int place_read(const char *who, rt_model *m, rt_sites *s, int recompute_transitions,
                const double *class_weights, int64_t nqueries, int query_kind, const void *queries,
                int64_t nfractions, const double *fractions, int64_t npendant, const double *pendant,
-               const double *pendant_scale, double *values, double *sums, double *loglik,
-               int32_t *status)
+               const double *pendant_scale, double *values, double *sums, double *set_sums,
+               double *loglik, int32_t *status)
 {
-    using grid_t = std::conditional_t<MIX, post_set_grid, post_grid>;
+    static_assert(!(MIX && PART), "a mixture is read on an ordinary batch");
+    constexpr bool SETS = MIX || PART;           // the tables are those of the model's rate sets
+    using grid_t = std::conditional_t<SETS, post_set_grid, post_grid>;
+    using result_t = std::conditional_t<PART, post_part_result, post_result>;
     post_pass p;                                 // (alive until the synchronisation below)
-    RT_TRY(post_open(&p, who, m, s));
+    if (PART) RT_TRY(post_partitioned_only(who, s));
+    RT_TRY(post_open(&p, who, m, s, PART));
     if (MIX) RT_TRY(post_class_weights(who, m, class_weights));
     const int64_t n = p.n, N = p.N, nsites = p.nsites;
     RT_REQUIRE(nqueries >= 1, "%s: at least one query (%lld here)", who, (long long)nqueries);
@@ -455,7 +513,7 @@ int place_read(const char *who, rt_model *m, rt_sites *s, int recompute_transiti
     for (int64_t k = 0; k < npendant; ++k)
         RT_REQUIRE(std::isfinite(pendant[k]) && pendant[k] >= 0.0,
                    "%s: pendant length %d is negative or not finite", who, (int)k);
-    for (int64_t k = 0; MIX && pendant_scale && k < m->multi.K; ++k)
+    for (int64_t k = 0; SETS && pendant_scale && k < m->multi.K; ++k)
         RT_REQUIRE(std::isfinite(pendant_scale[k]) && pendant_scale[k] >= 0.0,
                    "%s: pendant_scale[%lld] is negative or not finite", who, (long long)k);
     const int R = (int)nfractions, K = (int)npendant, np = 2 * R + K;
@@ -463,24 +521,31 @@ int place_read(const char *who, rt_model *m, rt_sites *s, int recompute_transiti
     RT_TRY(post_layout(&p, true));
     // the grid of every node: rho_r t_v, (1 - rho_r) t_v, tau_k (MIX: factors, the pendant points
     // absolute)
-    const std::vector<double> lengths = MIX ? post_set_fraction_factors(&p, R, fractions, K)
-                                            : post_fraction_lengths(&p, R, fractions, K, pendant);
+    const std::vector<double> lengths = SETS ? post_set_fraction_factors(&p, R, fractions, K)
+                                             : post_fraction_lengths(&p, R, fractions, K, pendant);
     RT_TRY(grid_t::check(&p, recompute_transitions, np, lengths.data()));
     const int64_t NRK = N * R * K;
     RT_REQUIRE(NRK < (int64_t)1 << 31, "%s: too many placements per query", who);
     post_plan &plan = p.plan;
     grid_t grid;                                 // (alive until the synchronisation below)
     post_mix mix;
+    post_part part;
     post_set_fractions setfrac;
-    post_result res(values, sums);
-    if constexpr (MIX) RT_TRY(grid.take(&p, np, K));
+    result_t res = [&] {
+        if constexpr (PART) return post_part_result(values, sums, set_sums);
+        else return post_result(values, sums);
+    }();
+    if constexpr (SETS) RT_TRY(grid.take(&p, np, K));
     else RT_TRY(grid.take(&p, np));
     if (MIX) RT_TRY(mix.take(&p, class_weights));
-    const int64_t nsets = MIX ? mix.K : 1;
+    if (PART) RT_TRY(part.take(&p));
+    // the sets the grid's tables span: every set the MODEL holds, also for a partitioned batch that
+    // uses fewer (spr_read's batch_sets counts the batch's: its PfragA follows the PT table)
+    const int64_t grid_sets = SETS ? m->multi.K : 1;
     // the distinct rate matrices in use: d of every node, the node that stands for d
     std::vector<int32_t> dnode((size_t)N, -1), rep;
     {
-        const std::vector<int32_t> &node_q = MIX ? m->multi.h_node_q : m->h_qidx;
+        const std::vector<int32_t> &node_q = SETS ? m->multi.h_node_q : m->h_qidx;
         RT_REQUIRE((int64_t)node_q.size() == N, "%s: the model's rate matrix indices are missing", who);
         std::vector<int32_t> d_of_q;
         for (int64_t v = 1; v < N; ++v) {
@@ -503,26 +568,33 @@ int place_read(const char *who, rt_model *m, rt_sites *s, int recompute_transiti
     const size_t o_F = plan.take(p.lane ? (size_t)N * R * n * nsites * 8 : (size_t)p.nops * R * tile);
     res.take_sums(&p, (size_t)nqueries * NRK);
     // the queries of one chunk (post_chunk_units): beside their result, their pendant vectors and
-    // their own image; at most what the grids' y takes
-    const size_t q_bytes = (size_t)nsites * (query_kind == RT_OBS_DENSE ? (size_t)n * 8 : 1);
+    // their own image (PART: in slot order, and beside it the caller's); at most what the grids' y
+    // takes
+    const size_t q_unit = query_kind == RT_OBS_DENSE ? (size_t)n * 8 : 1;
+    const size_t q_bytes = (size_t)nsites * q_unit;
+    const size_t qc_bytes = PART ? (size_t)s->part->nsites * q_unit : 0;     // a query as the caller has it
     const int64_t CH = post_chunk_units(plan, NRK * res.row_bytes(&p),
-                                        q_bytes + 512 + (p.lane ? 0 : (size_t)nd * K * tile), 32768,
-                                        nqueries, "RAOTEH_PLACE_CHUNK_BYTES");
+                                        q_bytes + qc_bytes + (PART ? 1024 : 512) +
+                                            (p.lane ? 0 : (size_t)nd * K * tile),
+                                        32768, nqueries, "RAOTEH_PLACE_CHUNK_BYTES");
     const size_t o_q = plan.take((size_t)CH * q_bytes);
+    // (the other calls take nothing here: their scratch lies as it did)
+    const size_t o_qc = PART ? plan.take((size_t)CH * qc_bytes) : 0;
     const size_t o_H = plan.take(p.lane ? 8 : (size_t)nd * K * CH * tile);
     res.take_chunk(&p, (size_t)CH * NRK, (size_t)PLACE_MAX_ROWS);
     RT_TRY(post_begin(&p, recompute_transitions));
     res.place(&p);
     if (MIX) RT_TRY(mix.begin(&p));
+    if (PART) RT_TRY(part.begin(&p));
     hipStream_t st = p.st;
     unsigned char *base = p.base;
     double *d_val = res.d_val, *d_F = (double *)(base + o_F), *d_H = (double *)(base + o_H);
     int *d_tab = (int *)(base + o_tab), *d_dtab = (int *)(base + o_dtab);
-    void *d_q = (void *)(base + o_q);
+    void *d_q = (void *)(base + o_q), *d_qc = (void *)(base + o_qc);
     const std::vector<int32_t> internal = post_internal_nodes(&p);
-    if constexpr (MIX) RT_TRY(grid.launch(&p, lengths.data(), nullptr, pendant, pendant_scale));
+    if constexpr (SETS) RT_TRY(grid.launch(&p, lengths.data(), nullptr, pendant, pendant_scale));
     else RT_TRY(grid.launch(&p, lengths.data()));
-    RT_TRY(post_up(&p, internal.data(), !MIX));
+    RT_TRY(post_up(&p, internal.data(), !SETS));
     std::vector<int32_t> tab, dtab((size_t)cnt + nd, -1);
     post_tab_build(&p, nullptr, &tab);
     for (int j = 0; j < cnt; ++j) dtab[(size_t)j] = dnode[(size_t)(p.lane ? j : p.x->ops[(size_t)j].node)];
@@ -540,20 +612,21 @@ int place_read(const char *who, rt_model *m, rt_sites *s, int recompute_transiti
     const size_t dfrag = p.lane ? 0 : (size_t)p.NT * p.KP * 128;
     std::vector<int32_t> htab;                   // (feeds an asynchronous copy)
     if (!p.lane) {
-        if constexpr (MIX) {
-            RT_TRY(mix.PT.pack(&p));
+        if constexpr (SETS) {
+            if constexpr (MIX) RT_TRY(mix.PT.pack(&p));
+            else RT_TRY(part.PT.pack(&p));
             RT_TRY(setfrac.pack(&p, &grid, R));
             if (dense) {
-                int *d_htab = (int *)(base + grid.o_tab) + (size_t)2 * nsets * R * p.nops;
-                htab.resize((size_t)nsets * K * nd);
-                for (int64_t k = 0; k < nsets; ++k)
+                int *d_htab = (int *)(base + grid.o_tab) + (size_t)2 * grid_sets * R * p.nops;
+                htab.resize((size_t)grid_sets * K * nd);
+                for (int64_t k = 0; k < grid_sets; ++k)
                     for (int j = 0; j < K; ++j)
                         for (int d = 0; d < nd; ++d)
                             htab[(size_t)((k * K + j) * nd + d)] =
                                 (int32_t)((k * np + 2 * R + j) * N + rep[(size_t)d]);
                 RT_HIP(hipMemcpyAsync(d_htab, htab.data(), htab.size() * 4, hipMemcpyHostToDevice, st));
                 RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, (int)htab.size(), d_htab, grid.d_G,
-                                        grid.d_GT + (size_t)2 * nsets * R * ftab));
+                                        grid.d_GT + (size_t)2 * grid_sets * R * ftab));
             }
         } else {
             RT_TRY(post_fraction_pack(&p, &grid, R));
@@ -578,12 +651,28 @@ int place_read(const char *who, rt_model *m, rt_sites *s, int recompute_transiti
             v.P = mix.P_of(&p, k); v.G = grid.G_of_set(&p, k); v.PT = mix.PT.of_set(k);
             v.GT = p.lane ? nullptr : setfrac.T_of_set(k);
             v.GA = p.lane ? nullptr : setfrac.A_of_set(k);
-            v.HA = p.lane ? nullptr : grid.d_GT + (size_t)2 * nsets * R * ftab + (size_t)k * K * nd * dfrag;
+            v.HA = p.lane ? nullptr : grid.d_GT + (size_t)2 * grid_sets * R * ftab + (size_t)k * K * nd * dfrag;
             v.stat = mix.status_of(&p, k);
             v.mx = {class_weights[k], mix.tot_of(&p, k), first_set};
         }
+        if constexpr (PART) {                    // (the tables of set 0: the kernels move on)
+            v.P = m->multi.d_P; v.PT = part.PT.d_PT;
+            v.GT = p.lane ? nullptr : setfrac.T_of_set(0);
+            v.GA = p.lane ? nullptr : setfrac.A_of_set(0);
+            v.HA = p.lane ? nullptr : grid.d_GT + (size_t)2 * grid_sets * R * ftab;
+        }
         return v;
     };
+    // what the PART instances add per set: n <= 4 to P [set][node] and G [set][point][node]; else
+    // the field's to the fragments [set][step] and [set][fraction][step], the queries' to the
+    // pendant fragments [set][pendant][distinct] and to G
+    [[maybe_unused]] post_part_arg px = {}, pxq = {};
+    if constexpr (PART) {
+        const long s_G = (long)((size_t)np * N * nn);
+        px = p.lane ? part.arg((long)m->multi.P_stride, s_G)
+                    : part.arg(part.pt_stride(), (long)((size_t)R * grid.tab));
+        pxq = part.arg((long)((size_t)K * nd * dfrag), s_G);
+    }
     // n > 4: the upward pass (MIX: under set k), the `up` pass and the field
     auto field = [&](int64_t k) -> int {
         const set_view v = view_of(k, 0);
@@ -598,7 +687,8 @@ int place_read(const char *who, rt_model *m, rt_sites *s, int recompute_transiti
                                    (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
                                    (int)n, d_F, v.stat, (long)x->nsites, (long)x->nblocks, mx...);
             };
-            if constexpr (MIX) launch(place_field_kernel<NT, KS, true, place_mix>, v.mx);
+            if constexpr (MIX) launch(place_field_kernel<NT, KS, true, false, place_mix>, v.mx);
+            else if constexpr (PART) launch(place_field_kernel<NT, KS, false, true, post_part_arg>, px);
             else launch(place_field_kernel<NT, KS>);
             return RT_OK;
         }));
@@ -620,7 +710,10 @@ int place_read(const char *who, rt_model *m, rt_sites *s, int recompute_transiti
                                        (const double *)m->d_root, p.d_L, p.d_M, p.d_D, d_F, dense,
                                        (const void *)d_q, QC, make, d_val, v.stat, mx...);
                 };
-                if constexpr (MIX) launch(place_lane_kernel<decltype(nv)::value, true, place_mix>, v.mx);
+                if constexpr (MIX)
+                    launch(place_lane_kernel<decltype(nv)::value, true, false, place_mix>, v.mx);
+                else if constexpr (PART)
+                    launch(place_lane_kernel<decltype(nv)::value, false, true, post_part_arg>, px);
                 else launch(place_lane_kernel<decltype(nv)::value>);
                 return RT_OK;
             }));
@@ -628,11 +721,14 @@ int place_read(const char *who, rt_model *m, rt_sites *s, int recompute_transiti
             const rt_sites *x = p.x;
             RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
                 constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
-                hipLaunchKernelGGL((place_query_kernel<NT, KS>),
-                                   dim3((unsigned)x->nblocks, (unsigned)QC), dim3(64 * NT), 0, st, dense,
-                                   (const void *)d_q, v.HA, v.G + (size_t)2 * R * N * nn,
-                                   (const int *)(d_dtab + cnt), nd, K, QC, (int)N, (int)n, d_H,
-                                   (long)x->nsites, (long)x->nblocks);
+                auto launch = [&](auto kernel, auto... part_arg) {
+                    hipLaunchKernelGGL(kernel, dim3((unsigned)x->nblocks, (unsigned)QC), dim3(64 * NT), 0,
+                                       st, dense, (const void *)d_q, v.HA, v.G + (size_t)2 * R * N * nn,
+                                       (const int *)(d_dtab + cnt), nd, K, QC, (int)N, (int)n, d_H,
+                                       (long)x->nsites, (long)x->nblocks, part_arg...);
+                };
+                if constexpr (PART) launch(place_query_kernel<NT, KS, true, post_part_arg>, pxq);
+                else launch(place_query_kernel<NT, KS>);
                 return RT_OK;
             }));
             RT_HIP(hipGetLastError());
@@ -655,17 +751,40 @@ int place_read(const char *who, rt_model *m, rt_sites *s, int recompute_transiti
         RT_HIP(hipGetLastError());
         return RT_OK;
     };
+    // PART: the chunk's queries at d_qc, caller order -> d_q, slot order
+    auto gather = [&](int QC) -> int {
+        const rt_partition *pt = s->part;
+        const int width = dense ? (int)n : 1;
+        const dim3 grid_dim((unsigned)(((size_t)nsites * width + 255) / 256), (unsigned)QC);
+        if (dense)
+            hipLaunchKernelGGL((place_query_gather_kernel<double, 256>), grid_dim, dim3(256), 0, st,
+                               (long)nsites, (long)pt->nsites, width, (const long *)pt->d_order,
+                               (const double *)d_qc, (double *)d_q);
+        else
+            hipLaunchKernelGGL((place_query_gather_kernel<unsigned char, 256>), grid_dim, dim3(256), 0,
+                               st, (long)nsites, (long)pt->nsites, width, (const long *)pt->d_order,
+                               (const unsigned char *)d_qc, (unsigned char *)d_q);
+        RT_HIP(hipGetLastError());
+        return RT_OK;
+    };
     if (!MIX && !p.lane) RT_TRY(field(0));       // the field, once
     for (int64_t q0 = 0; q0 < nqueries; q0 += CH) {
         const int QC = (int)std::min<int64_t>(CH, nqueries - q0);
         const size_t rows = (size_t)QC * NRK;
-        RT_HIP(hipMemcpyAsync(d_q, (const unsigned char *)queries + (size_t)q0 * q_bytes,
-                              (size_t)QC * q_bytes, hipMemcpyHostToDevice, st));
+        if constexpr (PART) {
+            RT_HIP(hipMemcpyAsync(d_qc, (const unsigned char *)queries + (size_t)q0 * qc_bytes,
+                                  (size_t)QC * qc_bytes, hipMemcpyHostToDevice, st));
+            RT_TRY(gather(QC));
+        } else {
+            RT_HIP(hipMemcpyAsync(d_q, (const unsigned char *)queries + (size_t)q0 * q_bytes,
+                                  (size_t)QC * q_bytes, hipMemcpyHostToDevice, st));
+        }
         RT_HIP(hipMemsetAsync(d_val, 0, rows * nsites * 8, st));       // (the root's rows)
         // the pass; MIX: set by set, the field holds one set at a time (a set of weight zero is
         // never live: not run, never read)
         int first_set = 1;
-        for (int64_t k = 0; k < nsets; ++k) {
+        // (PART: one launch, every tile under its own set)
+        for (int64_t k = 0; k < (MIX ? grid_sets : 1); ++k) {
             if (MIX && !(class_weights[k] > 0.0)) continue;
             if (MIX && !p.lane) RT_TRY(field(k));
             RT_TRY(score(k, QC, MIX || q0 == 0 ? 1 : 0, first_set));
@@ -683,7 +802,8 @@ int place_read(const char *who, rt_model *m, rt_sites *s, int recompute_transiti
         // 3. the weighted site sums and the per-site array [site][nqueries][N][R][K]
         RT_TRY(res.chunk(&p, (size_t)q0 * NRK, rows));
     }
-    RT_TRY(res.finish(&p, status, loglik, mix.d_ll));
+    if constexpr (PART) RT_TRY(res.finish(&p, status));
+    else RT_TRY(res.finish(&p, status, loglik, mix.d_ll));
     return grid.result(&p);
 }
 
@@ -697,7 +817,7 @@ extern "C" int rt_sites_placements(rt_model *m, rt_sites *s, int recompute_trans
 {
     return place_read<false>("rt_sites_placements", m, s, recompute_transitions, nullptr, nqueries,
                              query_kind, queries, nfractions, fractions, npendant, pendant, nullptr,
-                             values, sums, nullptr, status);
+                             values, sums, nullptr, nullptr, status);
 }
 
 extern "C" int rt_sites_placements_mixture(rt_model *m, rt_sites *s, int recompute_transitions,
@@ -710,5 +830,18 @@ extern "C" int rt_sites_placements_mixture(rt_model *m, rt_sites *s, int recompu
 {
     return place_read<true>("rt_sites_placements_mixture", m, s, recompute_transitions, class_weights,
                             nqueries, query_kind, queries, nfractions, fractions, npendant, pendant,
-                            pendant_scale, values, sums, loglik, status);
+                            pendant_scale, values, sums, nullptr, loglik, status);
+}
+
+extern "C" int rt_sites_placements_partitioned(rt_model *m, rt_sites *s, int recompute_transitions,
+                                               int64_t nqueries, int query_kind, const void *queries,
+                                               int64_t nfractions, const double *fractions,
+                                               int64_t npendant, const double *pendant,
+                                               const double *pendant_scale, double *values,
+                                               double *sums, double *set_sums, int32_t *status)
+{
+    return place_read<false, true>("rt_sites_placements_partitioned", m, s, recompute_transitions,
+                                   nullptr, nqueries, query_kind, queries, nfractions, fractions,
+                                   npendant, pendant, pendant_scale, values, sums, set_sums, nullptr,
+                                   status);
 }

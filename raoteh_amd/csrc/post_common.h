@@ -14,8 +14,9 @@
 //   post_chunk_units and post_result: the chunks a result that does not fit the scratch is made
 //       in, the weighted site sums (post_sums_kernel) and the way of the result to the caller (the
 //       four tree-search reads); post_part and post_part_result: the same for a PARTITIONED batch
-//       (branch_profile.hip, nni.hip) -- the sets' fragments and which of them have a site, the
+//       (the four tree-search reads) -- the sets' fragments and which of them have a site, the
 //       per-set sums over the runs of the plan (post_part_sums_*) and the gather to caller order;
+//       post_part_arg, what the PART forms of spr.hip's and place.hip's kernels take;
 //   post_csr_parents: the parents of a caller's CSR tree (nni.hip, spr.hip).
 // Device: the steps the downward kernels have in common; the division-free `up` pass (nni.hip,
 // place.hip, spr.hip).
@@ -132,8 +133,9 @@ inline int post_open(post_pass *p, const char *who, rt_model *m, rt_sites *s, bo
     RT_REQUIRE(m && s, "null pointer");
     if (s->part && !partitioned) {
         rt_set_error("%s: a partitioned batch is evaluated by rt_step_partitioned and read by "
-                     "rt_sites_branch_expectations_partitioned, rt_sites_branch_profiles_partitioned "
-                     "and rt_sites_nni_scores_partitioned only", who);
+                     "rt_sites_branch_expectations_partitioned, rt_sites_branch_profiles_partitioned, "
+                     "rt_sites_nni_scores_partitioned, rt_sites_spr_scores_partitioned and "
+                     "rt_sites_placements_partitioned only", who);
         return RT_ERR_UNSUPPORTED;
     }
     RT_REQUIRE(!partitioned || s->part, "%s: an ordinary batch (rt_sites_create_partitioned makes "
@@ -1373,7 +1375,8 @@ struct post_result {
 };
 
 // ---- the same of a PARTITIONED batch (rt_sites_branch_profiles_partitioned,
-// rt_sites_nni_scores_partitioned): the kernels' PART forms leave values [row][slot]; the caller
+// rt_sites_nni_scores_partitioned, rt_sites_spr_scores_partitioned,
+// rt_sites_placements_partitioned): the kernels' PART forms leave values [row][slot]; the caller
 // gets set_sums [set][row], sums [row] and / or values [site][row] in caller order ----
 
 // stage 1 of the per-set sums (the shape of branch_expect.hip's part_sums_stage1_kernel, over rows
@@ -1464,6 +1467,25 @@ post_part_gather_kernel(long nrows, long nslots, long nsites, const long *__rest
         val[(size_t)r * nsites + i] = val_slot[(size_t)r * nslots + slot];
 }
 
+// What the PART instances of spr.hip's and place.hip's kernels take beside the plain ones'
+// arguments, as ONE trailing argument that the other instances do not have (a parameter pack that
+// is empty there: they keep their argument lists and their instruction streams).  A tile (n <= 4: a
+// wave, whose 64 slots lie in one granule of 1 << gshift slots) reads its rate set once,
+// wave-uniform, and moves its table bases on by set * s_p (the resident tables) and set * s_g (the
+// grid's) doubles before anything else; read-only.
+struct post_part_arg {
+    const int *gset;                             // the set of every granule
+    int gshift;
+    long s_p, s_g;
+};
+// (the one argument of a pack that holds one)
+template <class T>
+__host__ __device__ __forceinline__ T post_pack_one(T x) { return x; }
+__device__ __forceinline__ long post_part_set(const post_part_arg &a, long granule)
+{
+    return __builtin_amdgcn_readfirstlane(a.gset[granule]);
+}
+
 // What a tree-search read of a partitioned batch holds beside the single-set one: the sets of the
 // batch, a "class weight" per set of the model for post_set_grid (1 for a set with a site, 0 for an
 // empty one and for the model's sets past the batch's: no matrices are made for them) and the
@@ -1500,6 +1522,7 @@ struct post_part {
         return RT_OK;
     }
     long pt_stride() const { return (long)(PT.tab / 8); }
+    post_part_arg arg(long s_p, long s_g) const { return {pt->d_granule_set, gshift(), s_p, s_g}; }
     // n <= 4: the granule (256 or 64 slots) as the shift that takes a slot to its granule
     int gshift() const
     {

@@ -45,8 +45,12 @@
 // rt_sites_spr_scores_mixture: the same scores of an ORDINARY batch under a site-class mixture over
 // the model's K rate sets, the cut edge at fractions of every set's own resident length -- the
 // kernels' MIX forms once per set and chunk into one accumulator, the root scaled by the class
-// weight instead of 1 / L_i; the plan of the walk is the same for every set.  One host body
-// (spr_read, at the end) serves both calls.
+// weight instead of 1 / L_i; the plan of the walk is the same for every set.
+// rt_sites_spr_scores_partitioned: the same scores of a PARTITIONED batch, every site under its own
+// rate set (the cut edge at fractions of the set's own length, the pruned subtree with its own edge
+// of the set) -- one pass with the kernels' PART forms, every tile under the tables of its granule's
+// set, then the per-set sums and the gather to caller order (post_part_result).  One host body
+// (spr_read, at the end) serves the three calls.
 #include "common.h"
 #include "post_common.h"
 
@@ -91,16 +95,19 @@ static_assert(sizeof(spr_op) == 48, "three int4 per op");
 // n > 4: the `up` pass alone, for every group of spr_kernel to find.  MIX
 // (rt_sites_spr_scores_mixture, one launch per rate set k of weight ck > 0 and chunk, after the
 // set's upward pass): down_up_pass's MIX form -- the root scaled by ck, L_ik to root_tot[site], the
-// status word the set's own.
-template <int NT, int KS, bool MIX = false>
+// status word the set's own.  PART (rt_sites_spr_scores_partitioned: sites are the batch's slots):
+// the tile is one granule; PfragT [set][step] is moved on to the tile's set (post_part_arg, the PART
+// instance's one further argument) and down_up_pass takes it as it is.
+template <int NT, int KS, bool MIX = false, bool PART = false, class... PX>
 __global__ void __launch_bounds__(64 * NT)
 spr_up_kernel(const double *__restrict__ PfragT, int nops, const int4 *__restrict__ steps,
               const int *__restrict__ tabp, const double *__restrict__ Larr,
               const double *__restrict__ Marr, double *__restrict__ Uarr,
               const double *__restrict__ obs, int K, const double *__restrict__ root_w, int n,
               int *__restrict__ status, long nsites, long nblocks, double ck,
-              double *__restrict__ root_tot)
+              double *__restrict__ root_tot, PX... part)
 {
+    static_assert(sizeof...(PX) == (PART ? 1 : 0) && !(MIX && PART), "post_part_arg: the PART instance's alone");
     constexpr int KP = (KS + 1) / 2;
     __shared__ double xb[NT * 4 * 64];
     __shared__ double red[NT][16];
@@ -108,6 +115,10 @@ spr_up_kernel(const double *__restrict__ PfragT, int nops, const int4 *__restric
     const int lane = threadIdx.x & 63;
     const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long blk = blockIdx.x;
+    if constexpr (PART) {
+        const post_part_arg px = post_pack_one(part...);
+        PfragT += post_part_set(px, blk) * px.s_p;
+    }
     const long site = blk * 16 + (lane & 15);
     const bool writer = m == 0 && lane < 16 && site < nsites;
     bool live[4];
@@ -131,7 +142,10 @@ spr_up_kernel(const double *__restrict__ PfragT, int nops, const int4 *__restric
 // one stream -- a fixed sum.  The logs are mix_log_ratio_kernel's once the sets are in.
 // (`first` is an argument of the MIX instance alone, FIRST = int: the plain instance keeps its
 // argument list, and with it the offsets of the hidden arguments behind it -- gridDim.y.)
-template <int NT, int KS, bool MIX = false, class... FIRST>
+// PART (one launch per chunk; out in slot order): the plain walk, every tile under the tables of
+// its granule's set -- PfragT / PfragA [set][step], GfragT / GfragA [set][fraction][step] are moved
+// on by set * (s_p, s_g) doubles before anything else; the pack holds the post_part_arg instead.
+template <int NT, int KS, bool MIX = false, bool PART = false, class... FIRST>
 __global__ void __launch_bounds__(64 * NT)
 spr_kernel(const double *__restrict__ PfragT, const double *__restrict__ PfragA,
            const double *__restrict__ GfragT, const double *__restrict__ GfragA, int R, int nops,
@@ -143,8 +157,10 @@ spr_kernel(const double *__restrict__ PfragT, const double *__restrict__ PfragA,
            int cB, int mvA, double *__restrict__ out, int *__restrict__ status, long nsites,
            long nblocks, FIRST... first_set)
 {
-    static_assert(sizeof...(FIRST) == (MIX ? 1 : 0), "first: the MIX instance's alone");
-    [[maybe_unused]] const int first = (0 + ... + first_set);
+    static_assert(sizeof...(FIRST) == (MIX || PART ? 1 : 0) && !(MIX && PART),
+                  "first: the MIX instance's alone; post_part_arg: the PART instance's");
+    [[maybe_unused]] int first = 0;
+    if constexpr (MIX) first = post_pack_one(first_set...);
     constexpr int KP = (KS + 1) / 2;
     __shared__ double xb[NT * 4 * 64];
     __shared__ double lb[NT * 4 * 64];
@@ -154,6 +170,14 @@ spr_kernel(const double *__restrict__ PfragT, const double *__restrict__ PfragA,
     const int lane = threadIdx.x & 63;
     const int m = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long blk = blockIdx.x;
+    if constexpr (PART) {
+        const post_part_arg px = post_pack_one(first_set...);
+        const long gs = post_part_set(px, blk);
+        PfragT += gs * px.s_p;
+        PfragA += gs * px.s_p;
+        GfragT += gs * px.s_g;
+        GfragA += gs * px.s_g;
+    }
     const long site = blk * 16 + (lane & 15);
     const bool site_ok = site < nsites;
     const bool writer = m == 0 && lane < 16 && site_ok;
@@ -300,18 +324,25 @@ spr_kernel(const double *__restrict__ PfragT, const double *__restrict__ PfragA,
     }
 }
 
-// n <= 4: the upward pass and the `up` pass, one lane per site (MIX: as spr_up_kernel, P of the set)
-template <int N, bool MIX = false>
+// n <= 4: the upward pass and the `up` pass, one lane per site (MIX: as spr_up_kernel, P of the set;
+// PART: P [set][node] moved on to the set of the wave's granule -- wave-uniform, so the matrices stay
+// scalar loads)
+template <int N, bool MIX = false, bool PART = false, class... PX>
 __global__ void __launch_bounds__(256)
 spr_lane_up_kernel(int nnodes, long nsites, const double *__restrict__ P,
                    const int *__restrict__ parent, const int *__restrict__ node_k,
                    const int *__restrict__ tabp, const void *__restrict__ obs, int compact, int Kobs,
                    int block_sites, const double *__restrict__ root_w, double *__restrict__ Larr,
                    double *__restrict__ Marr, double *__restrict__ Uarr, int *__restrict__ status,
-                   double ck, double *__restrict__ root_tot)
+                   double ck, double *__restrict__ root_tot, PX... part)
 {
+    static_assert(sizeof...(PX) == (PART ? 1 : 0) && !(MIX && PART), "post_part_arg: the PART instance's alone");
     const long site = (long)blockIdx.x * 256 + threadIdx.x;
     if (site >= nsites) return;
+    if constexpr (PART) {
+        const post_part_arg px = post_pack_one(part...);
+        P += post_part_set(px, site >> px.gshift) * px.s_p;
+    }
     const post_tab tab(tabp, nnodes);
     lane_up<N, true>(nnodes, nsites, site, P, parent, node_k, obs, compact, Kobs, block_sites, Larr, Marr);
     lane_up_pass<N, MIX>(true, nnodes, nsites, site, P, parent, node_k, tab, obs, compact, Kobs,
@@ -321,8 +352,9 @@ spr_lane_up_kernel(int nnodes, long nsites, const double *__restrict__ P,
 // n <= 4: one lane per (site, group); arrays [node][state][site], nodes in preorder; G
 // [point][node][N][N]: the points 0 .. R - 1 are P(rho t), R .. 2 R - 1 are P((1 - rho) t) (the
 // same address in every lane: the scalar path); S [group][level][state][site].  MIX: as spr_kernel,
-// P and G of the set, `first` its argument alone.
-template <int N, bool MIX = false, class... FIRST>
+// P and G of the set, `first` its argument alone.  PART: as spr_lane_up_kernel, P [set][node] and G
+// [set][point][node] of the set of the wave's granule.
+template <int N, bool MIX = false, bool PART = false, class... FIRST>
 __global__ void __launch_bounds__(256)
 spr_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const double *__restrict__ G,
                 int R, const int *__restrict__ parent, const int *__restrict__ node_k,
@@ -333,10 +365,18 @@ spr_lane_kernel(int nnodes, long nsites, const double *__restrict__ P, const dou
                 int nlevels, int cA, int cB, int mvA, double *__restrict__ out,
                 int *__restrict__ status, FIRST... first_set)
 {
-    static_assert(sizeof...(FIRST) == (MIX ? 1 : 0), "first: the MIX instance's alone");
-    [[maybe_unused]] const int first = (0 + ... + first_set);
+    static_assert(sizeof...(FIRST) == (MIX || PART ? 1 : 0) && !(MIX && PART),
+                  "first: the MIX instance's alone; post_part_arg: the PART instance's");
+    [[maybe_unused]] int first = 0;
+    if constexpr (MIX) first = post_pack_one(first_set...);
     const long site = (long)blockIdx.x * 256 + threadIdx.x;
     if (site >= nsites) return;
+    if constexpr (PART) {
+        const post_part_arg px = post_pack_one(first_set...);
+        const long gs = post_part_set(px, site >> px.gshift);
+        P += gs * px.s_p;
+        G += gs * px.s_g;
+    }
     const post_tab tab(tabp, nnodes);
     auto idx = [&](int v, int s) { return ((size_t)v * N + s) * nsites + site; };
     const int lv0 = blockIdx.y * nlevels;
@@ -624,16 +664,23 @@ namespace {
 // P, P^T and fraction fragments packed once; then per chunk, once per rate set of positive class
 // weight over the one L / M / U / level scratch, the set's upward pass (post_up_set), the MIX `up`
 // pass and the MIX walk, which adds c_k L_ik(moved tree) into ONE accumulator [move][fraction][site]
-// in set order; post_mix turns it into the values.  The plan of the walk holds no matrix: it is
-// made once per call.
-template <bool MIX>
+// in set order; post_mix turns it into the values.  PART (a partitioned batch): as MIX = false, one
+// launch of the PART instances per chunk, every tile under the tables of its own set -- the sets'
+// grid makes matrices for the sets that have a site, their fragments are packed once; the sums go
+// per set over the runs of the plan and the result leaves in caller order (post_part_result).  The
+// plan of the walk holds no matrix: it is made once per call.
+template <bool MIX, bool PART = false>
 int spr_read(const char *who, rt_model *m, rt_sites *s, int recompute_transitions,
              const double *class_weights, int64_t radius, int64_t nfractions, const double *fractions,
-             double *values, double *sums, double *loglik, int32_t *status)
+             double *values, double *sums, double *set_sums, double *loglik, int32_t *status)
 {
-    using grid_t = std::conditional_t<MIX, post_set_grid, post_grid>;
+    static_assert(!(MIX && PART), "a mixture is read on an ordinary batch");
+    constexpr bool SETS = MIX || PART;           // the tables are those of the model's rate sets
+    using grid_t = std::conditional_t<SETS, post_set_grid, post_grid>;
+    using result_t = std::conditional_t<PART, post_part_result, post_result>;
     post_pass p;                                 // (alive until the synchronisation below)
-    RT_TRY(post_open(&p, who, m, s));
+    if (PART) RT_TRY(post_partitioned_only(who, s));
+    RT_TRY(post_open(&p, who, m, s, PART));
     if (MIX) RT_TRY(post_class_weights(who, m, class_weights));
     const int64_t n = p.n, N = p.N, nsites = p.nsites;
     RT_REQUIRE(fractions, "%s: fractions is NULL", who);
@@ -654,23 +701,30 @@ int spr_read(const char *who, rt_model *m, rt_sites *s, int recompute_transition
     p.per_set = MIX;
     RT_TRY(post_layout(&p, true));
     // the grid of every node: rho_r t_v, (1 - rho_r) t_v (MIX: the factors of every set's own t)
-    const std::vector<double> lengths = MIX ? post_set_fraction_factors(&p, R, fractions)
-                                            : post_fraction_lengths(&p, R, fractions);
+    const std::vector<double> lengths = SETS ? post_set_fraction_factors(&p, R, fractions)
+                                             : post_fraction_lengths(&p, R, fractions);
     RT_TRY(grid_t::check(&p, recompute_transitions, np, lengths.data()));
     post_plan &plan = p.plan;
     grid_t grid;                                 // (alive until the synchronisation below)
     post_mix mix;
+    post_part part;
     post_set_fractions setfrac;
-    post_result res(values, sums);
+    result_t res = [&] {
+        if constexpr (PART) return post_part_result(values, sums, set_sums);
+        else return post_result(values, sums);
+    }();
     RT_TRY(grid.take(&p, np));
     if (MIX) RT_TRY(mix.take(&p, class_weights));
-    const int64_t nsets = MIX ? mix.K : 1;
+    if (PART) RT_TRY(part.take(&p));
+    // the sets whose PfragA is packed, beside the PT table: the model's sets for a mixture, the
+    // BATCH's sets for a partitioned batch (place_read's grid_sets counts the model's either way)
+    const int64_t batch_sets = MIX ? mix.K : PART ? part.K : 1;
     const int cnt = p.lane ? (int)N : p.nops;    // slots of the tables
     const int D = 1 + *std::max_element(tree.depth.begin(), tree.depth.end()), nlevels = 3 * D;
     const size_t o_tab = plan.take((size_t)4 * cnt * 4);
     const size_t o_cut = plan.take(((size_t)N + 1) * 16);
     const size_t ftab = p.lane ? 0 : (size_t)p.nops * p.NT * p.KP * 128;
-    const size_t o_PA = plan.take(p.lane ? 8 : (size_t)nsets * ftab * 8);
+    const size_t o_PA = plan.take(p.lane ? 8 : (size_t)batch_sets * ftab * 8);
     res.take_sums(&p, (size_t)nmoves * R);
     // the groups of pruned nodes that walk side by side: enough workgroups to fill the device at
     // few sites, their level vectors within SPR_LEVEL_BYTES
@@ -720,13 +774,14 @@ int spr_read(const char *who, rt_model *m, rt_sites *s, int recompute_transition
     unsigned char *base = p.base;
     res.place(&p);
     if (MIX) RT_TRY(mix.begin(&p));
+    if (PART) RT_TRY(part.begin(&p));
     double *d_val = res.d_val, *d_S = (double *)(base + o_S);
     double *d_PA = (double *)(base + o_PA);
     int *d_tab = (int *)(base + o_tab);
     int4 *d_cut = (int4 *)(base + o_cut), *d_ops = (int4 *)(base + o_ops);
     const std::vector<int32_t> internal = post_internal_nodes(&p);
     RT_TRY(grid.launch(&p, lengths.data()));
-    RT_TRY(post_up(&p, internal.data(), !MIX));
+    RT_TRY(post_up(&p, internal.data(), !SETS));
     std::vector<int32_t> tab;
     post_tab_build(&p, nullptr, &tab);
     if (!p.lane) {                               // node -> step in the plan
@@ -746,10 +801,14 @@ int spr_read(const char *who, rt_model *m, rt_sites *s, int recompute_transition
     if (!p.lane) {
         // the fragment tables: the resident P beside the resident P^T; the grid's (MIX: of every
         // set, each by one launch over the step table that spans the sets)
-        if constexpr (MIX) {
-            RT_TRY(mix.PT.pack(&p));
-            RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, (int)(mix.K * p.nops),
-                                    (const int *)(base + mix.PT.o_tab), m->multi.d_P, d_PA));
+        if constexpr (SETS) {
+            post_set_pt &PT = [&]() -> post_set_pt & {
+                if constexpr (MIX) return mix.PT;
+                else return part.PT;
+            }();
+            RT_TRY(PT.pack(&p));
+            RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, (int)(batch_sets * p.nops),
+                                    (const int *)(base + PT.o_tab), m->multi.d_P, d_PA));
             RT_TRY(setfrac.pack(&p, &grid, R));
         } else {
             RT_TRY(rt_launch_pack_p(p.ctx, (int)n, p.NT, p.KP, p.nops, p.d_ptab, m->d_P, d_PA));
@@ -771,20 +830,34 @@ int spr_read(const char *who, rt_model *m, rt_sites *s, int recompute_transition
             v.GT = p.lane ? nullptr : setfrac.T_of_set(k); v.GA = p.lane ? nullptr : setfrac.A_of_set(k);
             v.stat = mix.status_of(&p, k); v.tot = mix.tot_of(&p, k); v.ck = class_weights[k];
         }
+        if constexpr (PART) {                    // (the tables of set 0: the kernels move on)
+            v.P = m->multi.d_P; v.PT = part.PT.d_PT;
+            v.GT = p.lane ? nullptr : setfrac.T_of_set(0); v.GA = p.lane ? nullptr : setfrac.A_of_set(0);
+        }
         return v;
     };
+    // what a PART instance adds per set: n <= 4 to P [set][node] and G [set][point][node], else to
+    // the fragments [set][step] and [set][fraction][step]
+    [[maybe_unused]] post_part_arg px = {};
+    if constexpr (PART)
+        px = p.lane ? part.arg((long)m->multi.P_stride, (long)((size_t)np * N * n * n))
+                    : part.arg(part.pt_stride(), (long)((size_t)R * grid.tab));
     // the upward pass (MIX: under set k) and the `up` pass
     auto up_stage = [&](int64_t k) -> int {
         const set_view v = view_of(k);
         if (p.lane) {
             const int *d_ptab = p.d_ptab;
             RT_TRY(post_dispatch<2, 4>((int)n, [&](auto nv) {
-                hipLaunchKernelGGL((spr_lane_up_kernel<decltype(nv)::value, MIX>),
-                                   dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st, (int)N,
-                                   (long)nsites, v.P, d_ptab, d_ptab + N, (const int *)d_tab,
-                                   (const void *)s->d_obs, s->compact_states, (int)s->nobs,
-                                   s->block_sites, (const double *)m->d_root, p.d_L, p.d_M, p.d_D, v.stat,
-                                   v.ck, v.tot);
+                auto launch = [&](auto kernel, auto... part_arg) {
+                    hipLaunchKernelGGL(kernel, dim3((unsigned)((nsites + 255) / 256)), dim3(256), 0, st,
+                                       (int)N, (long)nsites, v.P, d_ptab, d_ptab + N, (const int *)d_tab,
+                                       (const void *)s->d_obs, s->compact_states, (int)s->nobs,
+                                       s->block_sites, (const double *)m->d_root, p.d_L, p.d_M, p.d_D,
+                                       v.stat, v.ck, v.tot, part_arg...);
+                };
+                if constexpr (PART)
+                    launch(spr_lane_up_kernel<decltype(nv)::value, false, true, post_part_arg>, px);
+                else launch(spr_lane_up_kernel<decltype(nv)::value, MIX>);
                 return RT_OK;
             }));
         } else {
@@ -792,11 +865,16 @@ int spr_read(const char *who, rt_model *m, rt_sites *s, int recompute_transition
             if (MIX) RT_TRY(post_up_set(&p, k, nullptr));
             RT_TRY(post_dispatch<2, 32>(p.KS, [&](auto ks) {
                 constexpr int KS = decltype(ks)::value, NT = (KS + 3) / 4;
-                hipLaunchKernelGGL((spr_up_kernel<NT, KS, MIX>), dim3((unsigned)x->nblocks),
-                                   dim3(64 * NT), 0, st, v.PT, p.nops, (const int4 *)p.d_steps,
-                                   (const int *)d_tab, (const double *)p.d_L, (const double *)p.d_M, p.d_D,
-                                   (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
-                                   (int)n, v.stat, (long)x->nsites, (long)x->nblocks, v.ck, v.tot);
+                auto launch = [&](auto kernel, auto... part_arg) {
+                    hipLaunchKernelGGL(kernel, dim3((unsigned)x->nblocks), dim3(64 * NT), 0, st, v.PT,
+                                       p.nops, (const int4 *)p.d_steps, (const int *)d_tab,
+                                       (const double *)p.d_L, (const double *)p.d_M, p.d_D,
+                                       (const double *)x->d_obs, (int)x->nobs, (const double *)m->d_root,
+                                       (int)n, v.stat, (long)x->nsites, (long)x->nblocks, v.ck, v.tot,
+                                       part_arg...);
+                };
+                if constexpr (PART) launch(spr_up_kernel<NT, KS, false, true, post_part_arg>, px);
+                else launch(spr_up_kernel<NT, KS, MIX>);
                 return RT_OK;
             }));
         }
@@ -818,7 +896,9 @@ int spr_read(const char *who, rt_model *m, rt_sites *s, int recompute_transition
                                        (const double *)p.d_M, (const double *)p.d_D, d_S, nlevels, cA,
                                        cB, mvA, d_val, v.stat, first...);
                 };
-                if constexpr (MIX) launch(spr_lane_kernel<decltype(nv)::value, true, int>, first_set);
+                if constexpr (MIX) launch(spr_lane_kernel<decltype(nv)::value, true, false, int>, first_set);
+                else if constexpr (PART)
+                    launch(spr_lane_kernel<decltype(nv)::value, false, true, post_part_arg>, px);
                 else launch(spr_lane_kernel<decltype(nv)::value>);
                 return RT_OK;
             }));
@@ -835,7 +915,8 @@ int spr_read(const char *who, rt_model *m, rt_sites *s, int recompute_transition
                                        (int)x->nobs, (const double *)m->d_root, (int)n, cA, cB, mvA,
                                        d_val, v.stat, (long)x->nsites, (long)x->nblocks, first...);
                 };
-                if constexpr (MIX) launch(spr_kernel<NT, KS, true, int>, first_set);
+                if constexpr (MIX) launch(spr_kernel<NT, KS, true, false, int>, first_set);
+                else if constexpr (PART) launch(spr_kernel<NT, KS, false, true, post_part_arg>, px);
                 else launch(spr_kernel<NT, KS>);
                 return RT_OK;
             }));
@@ -854,7 +935,8 @@ int spr_read(const char *who, rt_model *m, rt_sites *s, int recompute_transition
         const unsigned groups = (unsigned)std::min<int64_t>(G, cB - cA);
         // the pass; MIX: set by set (a set of weight zero is never live: not run, never read)
         int first_set = 1;
-        for (int64_t k = 0; k < nsets; ++k) {
+        // (PART: one launch, every tile under its own set)
+        for (int64_t k = 0; k < (MIX ? batch_sets : 1); ++k) {
             if (MIX && !(class_weights[k] > 0.0)) continue;
             if (MIX) RT_TRY(up_stage(k));
             if (rows) RT_TRY(walk(k, cA, cB, mvA, groups, first_set));
@@ -869,7 +951,8 @@ int spr_read(const char *who, rt_model *m, rt_sites *s, int recompute_transition
         // 3. the weighted site sums and the per-site array [site][nmoves][R]
         RT_TRY(res.chunk(&p, (size_t)mvA * R, rows));
     }
-    RT_TRY(res.finish(&p, status, loglik, mix.d_ll));
+    if constexpr (PART) RT_TRY(res.finish(&p, status));
+    else RT_TRY(res.finish(&p, status, loglik, mix.d_ll));
     return grid.result(&p);
 }
 
@@ -880,7 +963,7 @@ extern "C" int rt_sites_spr_scores(rt_model *m, rt_sites *s, int recompute_trans
                                    double *values, double *sums, int32_t *status)
 {
     return spr_read<false>("rt_sites_spr_scores", m, s, recompute_transitions, nullptr, radius,
-                           nfractions, fractions, values, sums, nullptr, status);
+                           nfractions, fractions, values, sums, nullptr, nullptr, status);
 }
 
 extern "C" int rt_sites_spr_scores_mixture(rt_model *m, rt_sites *s, int recompute_transitions,
@@ -889,6 +972,15 @@ extern "C" int rt_sites_spr_scores_mixture(rt_model *m, rt_sites *s, int recompu
                                            double *sums, double *loglik, int32_t *status)
 {
     return spr_read<true>("rt_sites_spr_scores_mixture", m, s, recompute_transitions, class_weights,
-                          radius, nfractions, fractions, values, sums, loglik, status);
+                          radius, nfractions, fractions, values, sums, nullptr, loglik, status);
+}
+
+extern "C" int rt_sites_spr_scores_partitioned(rt_model *m, rt_sites *s, int recompute_transitions,
+                                               int64_t radius, int64_t nfractions,
+                                               const double *fractions, double *values, double *sums,
+                                               double *set_sums, int32_t *status)
+{
+    return spr_read<false, true>("rt_sites_spr_scores_partitioned", m, s, recompute_transitions, nullptr,
+                                 radius, nfractions, fractions, values, sums, set_sums, nullptr, status);
 }
 

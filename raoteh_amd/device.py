@@ -336,6 +336,17 @@ PartitionedBranchProfiles = collections.namedtuple(
 PartitionedNniScores = collections.namedtuple(
     'PartitionedNniScores', 'moves factors values sums set_sums status')
 
+# TreeModel.spr_scores_partitioned: moves, fractions and best as SprScores, values [nsites, nmoves,
+# R] in caller order (or None), sums [nmoves, R], set_sums [nsets, nmoves, R], status
+PartitionedSprScores = collections.namedtuple(
+    'PartitionedSprScores', 'moves fractions values sums set_sums status best')
+
+# TreeModel.place_queries_partitioned: fractions, pendant and best as Placements, pendant_scale
+# [the model's sets] as evaluated, values [nsites, Q, nnodes, R, K] in caller order (or None), sums
+# [Q, nnodes, R, K], set_sums [nsets, Q, nnodes, R, K], status
+PartitionedPlacements = collections.namedtuple(
+    'PartitionedPlacements', 'fractions pendant pendant_scale values sums set_sums status best')
+
 
 def check_profile_factors(factors, nnodes):
     """The trial lengths of TreeModel.branch_profiles_mixture / nni_scores_mixture, as factors of
@@ -557,6 +568,29 @@ def check_pendant_scale(pendant_scale, nsets):
     if not (np.isfinite(s).all() and (s >= 0).all()):
         raise ValueError('the pendant scales must be finite and not negative')
     return s
+
+
+def _placement_queries(queries, kind, nsites, nstates):
+    """The queries of TreeModel.place_queries and its _mixture and _partitioned forms as the C ABI
+    takes them, (array, observation kind): 'dense' f64 [Q, nsites, n] or 'state' uint8 [Q, nsites]
+    (255 or -1: unobserved), Q >= 1; ValueError otherwise ('mask' queries are not taken)."""
+    S, n = nsites, nstates
+    if kind == 'dense':
+        q = np.ascontiguousarray(queries, dtype=np.float64)
+        if q.ndim != 3 or q.shape[1:] != (S, n):
+            raise ValueError('dense queries must be [Q, %d, %d], not %s' % (S, n, q.shape))
+        code = _lib.RT_OBS_DENSE
+    elif kind == 'state':
+        q = np.asarray(queries)
+        if q.ndim != 2 or q.shape[1] != S:
+            raise ValueError('state queries must be [Q, %d], not %s' % (S, q.shape))
+        q = _as_uint8_states(q, n)
+        code = _lib.RT_OBS_STATE
+    else:
+        raise ValueError("queries of kind 'dense' or 'state', not %r" % (kind,))
+    if q.shape[0] < 1:
+        raise ValueError('at least one query')
+    return q, code
 
 
 def _mask_states(mask, nstates):
@@ -1910,22 +1944,8 @@ class TreeModel(object):
         if pendant is None:
             pendant = [float(np.mean(self.branch_lengths()[1:]))] if N > 1 else [0.0]
         f, t = check_placement_grid(fractions, pendant)
-        if kind == 'dense':
-            q = np.ascontiguousarray(queries, dtype=np.float64)
-            if q.ndim != 3 or q.shape[1:] != (S, n):
-                raise ValueError('dense queries must be [Q, %d, %d], not %s' % (S, n, q.shape))
-            code = _lib.RT_OBS_DENSE
-        elif kind == 'state':
-            q = np.asarray(queries)
-            if q.ndim != 2 or q.shape[1] != S:
-                raise ValueError('state queries must be [Q, %d], not %s' % (S, q.shape))
-            q = _as_uint8_states(q, n)
-            code = _lib.RT_OBS_STATE
-        else:
-            raise ValueError("queries of kind 'dense' or 'state', not %r" % (kind,))
+        q, code = _placement_queries(queries, kind, S, n)
         Q, R, K = q.shape[0], len(f), len(t)
-        if Q < 1:
-            raise ValueError('at least one query')
         values = np.zeros((S, Q, N, R, K)) if per_site else None
         sums = np.zeros((Q, N, R, K))
         status = np.zeros(S, dtype=np.int32)
@@ -1966,22 +1986,8 @@ class TreeModel(object):
             t = None if sets is None else np.asarray(sets[1])
             pendant = [float(np.mean(t[:, 1:]))] if t is not None and N > 1 else [0.0]
         f, t = check_placement_grid(fractions, pendant)
-        if kind == 'dense':
-            q = np.ascontiguousarray(queries, dtype=np.float64)
-            if q.ndim != 3 or q.shape[1:] != (S, n):
-                raise ValueError('dense queries must be [Q, %d, %d], not %s' % (S, n, q.shape))
-            code = _lib.RT_OBS_DENSE
-        elif kind == 'state':
-            q = np.asarray(queries)
-            if q.ndim != 2 or q.shape[1] != S:
-                raise ValueError('state queries must be [Q, %d], not %s' % (S, q.shape))
-            q = _as_uint8_states(q, n)
-            code = _lib.RT_OBS_STATE
-        else:
-            raise ValueError("queries of kind 'dense' or 'state', not %r" % (kind,))
+        q, code = _placement_queries(queries, kind, S, n)
         Q, R, K = q.shape[0], len(f), len(t)
-        if Q < 1:
-            raise ValueError('at least one query')
         values = np.zeros((S, Q, N, R, K)) if per_site else None
         sums = np.zeros((Q, N, R, K))
         ll = np.zeros(S)
@@ -1998,6 +2004,79 @@ class TreeModel(object):
             v, r, k = np.unravel_index(np.argmax(flat, axis=1), (N - 1, R, K))
             best = np.stack([v + 1, r, k], axis=1).astype(np.int64)
         return MixturePlacements(f, t, scale, sums, values, ll, status, best)
+
+    def spr_scores_partitioned(self, batch, radius=None, fractions=(0.5,), per_site=False,
+                               recompute_transitions=False):
+        """rt_sites_spr_scores_partitioned: spr_scores for a batch uploaded with site_sets, for
+        every move of spr_moves(radius) at every fraction -- site i reads every edge under its own
+        rate set k of set_rate_sets: the edge above y is cut at fractions[r] of the set's own
+        resident length t[k][y], the pruned subtree keeps its own edge of set k.  Returns a
+        PartitionedSprScores tuple: moves, fractions, values[i, mv, r] in caller order (None
+        unless per_site), sums[mv, r], set_sums[k, mv, r] over set k's sites (zeros for an empty
+        set), status, best as spr_scores.  -inf where a live site has likelihood 0 on the moved
+        tree.  No earlier step_partitioned is needed; nothing the batch or the model holds
+        changes."""
+        nsets = self._partitioned_search_args(batch, 'spr_scores_partitioned')
+        S = batch.nsites
+        rad = _spr_radius(radius)
+        f, _ = check_placement_grid(fractions, (0.0,))
+        moves = self.spr_moves(radius)
+        M, R = len(moves), len(f)
+        values = np.zeros((S, M, R)) if per_site else None
+        sums = np.zeros((M, R))
+        set_sums = np.zeros((nsets, M, R))
+        status = np.zeros(S, dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_spr_scores_partitioned(
+            self._h, batch._h, 1 if recompute_transitions else 0, rad, R, _ptr(f, c_double),
+            None if values is None else _ptr(values, c_double), _ptr(sums, c_double),
+            _ptr(set_sums, c_double), _ptr(status, c_int32)))
+        best = None
+        if M:
+            flat = np.where(np.isnan(sums), -np.inf, sums).reshape(-1)
+            best = tuple(int(x) for x in np.unravel_index(int(np.argmax(flat)), (M, R)))
+        return PartitionedSprScores(moves, f, values, sums, set_sums, status, best)
+
+    def place_queries_partitioned(self, batch, queries, kind='dense', fractions=(0.5,),
+                                  pendant=None, pendant_scale=None, per_site=False,
+                                  recompute_transitions=False):
+        """rt_sites_placements_partitioned: place_queries for a batch uploaded with site_sets --
+        site i under its own rate set k of set_rate_sets: the edge above v is cut at fractions[r]
+        of the set's own resident length t[k][v] and the query hangs on an edge of length
+        pendant_scale[k] * pendant[j] under the set's rate matrix of the cut edge
+        (check_pendant_scale over the model's sets: None gives ones).  queries, kind and
+        fractions as for place_queries, the queries in the caller's site order; pendant=None:
+        the one value mean(t[:nsets, 1:]) of the resident rate sets.  Returns a
+        PartitionedPlacements tuple: fractions, pendant, pendant_scale, values[i, q, v, r, j] in
+        caller order (None unless per_site), sums [Q, nnodes, R, K], set_sums [nsets, Q, nnodes,
+        R, K] over each set's sites (zeros for an empty set), status, best as place_queries.
+        The root's row is 0.  Nothing the batch or the model holds changes."""
+        nsets = self._partitioned_search_args(batch, 'place_queries_partitioned')
+        ta = self.tree
+        N, S, n = ta.nnodes, batch.nsites, self.nstates
+        scale = check_pendant_scale(pendant_scale, int(self._nsets))
+        if pendant is None:
+            sets = getattr(self, '_rate_sets', None)
+            t = None if sets is None else np.asarray(sets[1])
+            pendant = [float(np.mean(t[:nsets, 1:]))] if t is not None and N > 1 else [0.0]
+        f, t = check_placement_grid(fractions, pendant)
+        q, code = _placement_queries(queries, kind, S, n)
+        Q, R, K = q.shape[0], len(f), len(t)
+        values = np.zeros((S, Q, N, R, K)) if per_site else None
+        sums = np.zeros((Q, N, R, K))
+        set_sums = np.zeros((nsets, Q, N, R, K))
+        status = np.zeros(S, dtype=np.int32)
+        _lib.check(_lib.lib().rt_sites_placements_partitioned(
+            self._h, batch._h, 1 if recompute_transitions else 0, Q, code,
+            q.ctypes.data_as(ctypes.c_void_p), R, _ptr(f, c_double), K, _ptr(t, c_double),
+            _ptr(scale, c_double), None if values is None else _ptr(values, c_double),
+            _ptr(sums, c_double), _ptr(set_sums, c_double), _ptr(status, c_int32)))
+        best = np.zeros((Q, 3), dtype=np.int64)
+        if N > 1:
+            flat = sums[:, 1:].reshape(Q, -1)
+            flat = np.where(np.isnan(flat), -np.inf, flat)
+            v, r, k = np.unravel_index(np.argmax(flat, axis=1), (N - 1, R, K))
+            best = np.stack([v + 1, r, k], axis=1).astype(np.int64)
+        return PartitionedPlacements(f, t, scale, values, sums, set_sums, status, best)
 
     def branch_length_gradient(self, batch, recompute_transitions=False):
         """d (sum_i w_i log L_i) / d t_v for every branch, f64[nnodes] in preorder (0 at the

@@ -11,7 +11,7 @@ vectors, by
 
 each the median of nine windows with the window minimum and maximum, the two forms alternating
 window by window.  The sub-batch loop uses nothing this call added, so `--baseline-only` runs on
-a checkout without it (copy this file and time_nni_scores_partitioned.py into its tools/).
+a checkout without it (copy this file and the time_*_partitioned.py that calls it into its tools/).
 `--single` times the single-set call alone on the whole alignment as one ordinary batch (set_rates
 + the call), for a comparison of two builds.
 
@@ -20,7 +20,10 @@ a checkout without it (copy this file and time_nni_scores_partitioned.py into it
 
 `--once K`: warm up, then ten partitioned evaluations (the program to put behind
 `rocprofv3 --kernel-trace --stats --`).  time_nni_scores_partitioned.py is the same program for
-nni_scores_partitioned, at eight factors and for the plain swap.
+nni_scores_partitioned, at eight factors and for the plain swap; time_spr_scores_partitioned.py for
+spr_scores_partitioned at radius 1 and 3 and one fraction; time_placements_partitioned.py for
+place_queries_partitioned with 16 state queries on every edge at one fraction and one pendant
+length.
 """
 import argparse
 import json
@@ -60,16 +63,40 @@ def rate_sets(cfg, K, model):
     return Q, t
 
 
-def calls(call, model, factors):
-    """(the single-set call on a batch -> sums, the partitioned call on a batch -> set_sums)."""
+PLACE_QUERIES = 16
+PLACE_PENDANT = (0.1,)
+
+
+def calls(call, model, factors, nsites=0):
+    """(the single-set call on a batch -> sums, the partitioned call on a batch -> set_sums); both
+    take the batch and the sites it holds (an index array; None: all of them).  `factors`: the
+    variant -- factors or None (profiles, nni), the radius (spr), nothing (place: PLACE_QUERIES
+    state queries on every edge at one fraction and one pendant length)."""
     if call == 'profiles':
-        return (lambda b: model.branch_profiles(b, factors=factors).sums,
-                lambda b: model.branch_profiles_partitioned(b, factors).set_sums)
+        return (lambda b, sites: model.branch_profiles(b, factors=factors).sums,
+                lambda b, sites: model.branch_profiles_partitioned(b, factors).set_sums)
+    if call == 'spr':
+        return (lambda b, sites: model.spr_scores(b, radius=factors).sums,
+                lambda b, sites: model.spr_scores_partitioned(b, radius=factors).set_sums)
+    if call == 'place':
+        q = np.random.RandomState(5).randint(0, model.nstates, size=(PLACE_QUERIES, nsites)).astype(np.uint8)
+        cut = {}
+
+        def mine(sites):                         # (the set's queries, sliced once per index array:
+            if sites is None:                    # the entry keeps the array, so its id stays its own)
+                return q
+            if id(sites) not in cut:
+                cut[id(sites)] = (sites, np.ascontiguousarray(q[:, sites]))
+            return cut[id(sites)][1]
+        return (lambda b, sites: model.place_queries(b, mine(sites), kind='state',
+                                                     pendant=PLACE_PENDANT).sums,
+                lambda b, sites: model.place_queries_partitioned(b, q, kind='state',
+                                                                 pendant=PLACE_PENDANT).set_sums)
     if factors is None:
-        return (lambda b: model.nni_scores(b).sums,
-                lambda b: model.nni_scores_partitioned(b).set_sums)
-    return (lambda b: model.nni_scores(b, factors=factors).sums,
-            lambda b: model.nni_scores_partitioned(b, factors).set_sums)
+        return (lambda b, sites: model.nni_scores(b).sums,
+                lambda b, sites: model.nni_scores_partitioned(b).set_sums)
+    return (lambda b, sites: model.nni_scores(b, factors=factors).sums,
+            lambda b, sites: model.nni_scores_partitioned(b, factors).set_sums)
 
 
 def main(call='profiles', variants=(('8 factors', FACTORS),)):
@@ -93,11 +120,11 @@ def main(call='profiles', variants=(('8 factors', FACTORS),)):
         Q, t = rate_sets(cfg, 1, model)
         batch = model.upload_sites(cfg['leaves'], dense, kind='dense')
         for label, factors in variants:
-            single, _ = calls(call, model, factors)
+            single, _ = calls(call, model, factors, nsites)
 
             def fn():
                 model.set_rates(Q=Q[0], t=t[0])
-                return single(batch)
+                return single(batch, None)
             for _ in range(2):
                 fn()
             row = dict(single=True, points=label, reps_per_window=args.reps or 6)
@@ -108,6 +135,7 @@ def main(call='profiles', variants=(('8 factors', FACTORS),)):
     for K in Ks:
         reps = args.reps or 12 // K + 3
         site_sets = np.arange(nsites) % K
+        members = [np.flatnonzero(site_sets == k) for k in range(K)]
         ctx, model = new_model(cfg, 0)
         Q, t = rate_sets(cfg, K, model)
         subs = [model.upload_sites(cfg['leaves'], np.ascontiguousarray(dense[site_sets == k]),
@@ -116,19 +144,19 @@ def main(call='profiles', variants=(('8 factors', FACTORS),)):
         if not args.baseline_only:
             part = model.upload_sites(cfg['leaves'], dense, kind='dense', site_sets=site_sets, nsets=K)
         for label, factors in variants:
-            single, partitioned_call = calls(call, model, factors)
+            single, partitioned_call = calls(call, model, factors, nsites)
             row = dict(K=K, points=label, reps_per_window=reps)
 
             def subbatch():
                 out = []
                 for k in range(K):
                     model.set_rates(Q=Q[k], t=t[k])
-                    out.append(single(subs[k]))
+                    out.append(single(subs[k], members[k]))
                 return np.array(out)
 
             def partitioned():
                 model.set_rate_sets(Q, t=t)
-                return partitioned_call(part)
+                return partitioned_call(part, None)
             forms = [('subbatch', subbatch)]
             if part is not None:
                 forms.insert(0, ('partitioned', partitioned))
