@@ -5,13 +5,13 @@ set is two uint64 words.  Against the reference's un-accelerated passes and exac
 against a closed-form stationary law and against the expectation path at 122 states.  The
 tolerances are those of the sampler tests for up to 64 states in test_gpu_parity.py."""
 import ctypes
-from math import exp, factorial
 
 import networkx as nx
 import numpy as np
 import pytest
 
-from _forest_wide_cases import forest_wide_cases, lumped_cycle, rows
+from _forest_wide_cases import (check_lumped_cycle_law, check_resident_histories, forest_wide_cases,
+                                rows, sparse_uniformized)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,17 +27,6 @@ def ra():
     ns.pkg, ns.device, ns.lib, ns.synth, ns.pyf = raoteh_amd, device, _lib, synth, pyfelscore_compat
     ns.ctx = device.get_context()
     return ns
-
-
-def sparse_uniformized(rng, n, extras=3.0):
-    """P = I + Q / omega of a sparse random rate matrix whose support holds a cycle."""
-    Q = np.zeros((n, n))
-    for i in range(n):
-        Q[i, (i + 1) % n] = rng.exponential() + 0.1
-    Q += (rng.uniform(size=(n, n)) < extras / n) * rng.exponential(size=(n, n))
-    np.fill_diagonal(Q, 0.0)
-    Q -= np.diag(Q.sum(axis=1))
-    return Q, np.identity(n) + Q / (2.0 * (-np.diag(Q)).max())
 
 
 # ---------------------------------------------------------------------------
@@ -225,38 +214,6 @@ def test_embedded_64_state_problem_gets_the_draws_of_the_one_word_kernels(ra):
 # 8: exact stationary law
 # ---------------------------------------------------------------------------
 
-def _cycle_law(ta, tb, kmax=40):
-    law = {}
-    for s in range(4):
-        for ka in range((-s) % 4, kmax, 4):
-            for kb in range((-s) % 4, kmax, 4):
-                w = 0.25 * exp(-ta) * ta ** ka / factorial(ka) * exp(-tb) * tb ** kb / factorial(kb)
-                law[(s, ka + kb)] = law.get((s, ka + kb), 0.0) + w
-    z = sum(law.values())
-    return dict((k, v / z) for k, v in law.items())
-
-
-def _chi_square(root, total, law, C):
-    cells = sorted(law, key=lambda k: -law[k])
-    stat, dof, rest_e, rest_o = 0.0, -1, 0.0, 0
-    seen = 0
-    for key in cells:
-        e = law[key] * C
-        o = int(((root == key[0]) & (total == key[1])).sum())
-        seen += o
-        if e >= 8.0:
-            stat += (o - e) ** 2 / e
-            dof += 1
-        else:
-            rest_e += e
-            rest_o += o
-    rest_o += C - seen
-    if rest_e >= 8.0:
-        stat += (rest_o - rest_e) ** 2 / rest_e
-        dof += 1
-    return stat, dof
-
-
 LUMPED_SETTINGS = [
     ('device', 128, (3.0, 2.0), 2.0, 400),
     ('device', 128, (0.9, 0.7), 2.0, 3000),
@@ -275,56 +232,7 @@ def test_wide_stationary_law_on_a_lumped_cycle_is_exact(ra, where, n, lengths, f
     uniform root, the law of (root class, total number of transitions) is that test's closed
     form; same chains, settings and criteria.  The number of transitions of a chain is its
     rows minus its two edges (the int64[C][n][n] count array would be 2.6 GB)."""
-    from raoteh_amd import _sampler
-    Q = lumped_cycle(n)
-    device = where == 'device'
-    cls = _sampler.DeviceHistoryBatch if device else _sampler.HistoryBatch
-    C = 20000 if device else 3000
-    ta, tb = lengths
-    T = nx.Graph()
-    T.add_edge(0, 1, weight=ta)
-    T.add_edge(0, 2, weight=tb)
-    law = _cycle_law(ta, tb)
-    base = lambda st: 2 * ((-st) % 4)
-    turned = sum(p for (st, k), p in law.items() if k >= base(st) + 4)
-    zero_class = set(s for s in range(n) if s % 4 == 0)
-    b = cls(T, 0, Q, node_to_allowed_states={1: zero_class, 2: zero_class}, nchains=C,
-            root_distn=np.full(n, 1.0 / n), uniformization_factor=factor, seed=11, ctx=ra.ctx)
-
-    def run(k):
-        if device:
-            b.sweep(k)
-        else:
-            for _ in range(k):
-                b.sweep()
-
-    def observed():
-        chain = b.rows()[0] if device else b.chain
-        states = b.node_states
-        assert (states[:, 1:] % 4 == 0).all()
-        return states[:, 0] % 4, np.bincount(chain, minlength=C) - 2
-
-    if (ta, factor) == (0.9, 2.0):
-        run(3)
-        root, total = observed()
-        early = float((total >= 2 * ((-root) % 4) + 4).mean())
-        assert early <= turned + 4.0 * np.sqrt(turned / C), (early, turned)
-        run(sweeps - 3)
-    else:
-        run(sweeps)
-    root, total = observed()
-    assert ((total + 2 * root) % 4 == 0).all()
-    stat, dof = _chi_square(root, total, law, C)
-    print('lumped cycle %s n=%d t=%s factor=%g: chi-square %.1f, dof %d' % (
-        where, n, lengths, factor, stat, dof))
-    assert stat < dof + 6.0 * np.sqrt(2.0 * dof) + 10.0, (ta, tb, factor, stat, dof)
-    late = float((total >= 2 * ((-root) % 4) + 4).mean())
-    assert abs(late - turned) < 6.0 * np.sqrt(turned * (1 - turned) / C) + 1e-3, \
-        (ta, tb, factor, late, turned)
-    # the replicas of a class are exchangeable: the root's replica is uniform
-    replica = np.bincount(b.node_states[:, 0] // 4, minlength=n // 4)
-    e = C / float(n // 4)
-    assert ((replica - e) ** 2 / e).sum() < (n // 4 - 1) + 6.0 * np.sqrt(2.0 * (n // 4 - 1)) + 10.0
+    check_lumped_cycle_law(ra.ctx, where, n, lengths, factor, sweeps)
 
 
 # ---------------------------------------------------------------------------
@@ -467,75 +375,9 @@ def test_wide_device_resident_histories_are_consistent_and_reproducible(ra):
     cols = [index[v] for v in cfg['leaves']]
     masks[:, cols] = table[cfg['leaf_states']]
     masks[:, :, 1] |= np.uint64(1) << np.uint64(63)          # bits at or above n are ignored
-    batches = [_sampler.DeviceHistoryBatch(T, root, Q, node_masks=masks,
-                                           root_distn=cfg['root_distn'], seed=21, ctx=ra.ctx)
-               for _ in range(2)]
-    for b in batches:
-        b.sweep(5)
-    a, b = batches
-    rows_a, rows_b = a.rows(), b.rows()
-    for x, y in zip(rows_a, rows_b):
-        np.testing.assert_array_equal(x, y)
-
-    def consistent(batch, rows_):
-        chain, edge, length, state = rows_
-        key = chain * N + edge
-        assert (np.diff(key) >= 0).all()
-        per_edge = np.bincount(key, weights=length, minlength=C * N).reshape(C, N)
-        np.testing.assert_allclose(per_edge[:, 1:], np.broadcast_to(batch.branch[1:], (C, N - 1)),
-                                   rtol=1e-12)
-        assert (length > 0).all() and ((state >= 0) & (state < n)).all()
-        same_edge = key[1:] == key[:-1]
-        assert (state[1:][same_edge] != state[:-1][same_edge]).all()
-        assert (Q[state[:-1][same_edge], state[1:][same_edge]] > 0).all()
-        ns = batch.node_states
-        last = np.ones(chain.shape[0], dtype=bool)
-        last[:-1] = ~same_edge
-        first = np.ones(chain.shape[0], dtype=bool)
-        first[1:] = ~same_edge
-        np.testing.assert_array_equal(ns[chain[last], edge[last]], state[last])
-        np.testing.assert_array_equal(ns[chain[first], batch.parent[edge[first]]], state[first])
-        word = np.take_along_axis(masks, (ns // 64)[:, :, None], axis=2)[:, :, 0]
-        assert ((word >> (ns % 64).astype(np.uint64)) & np.uint64(1)).all()
-        return same_edge
-
-    same_edge = consistent(a, rows_a)
-    chain, edge, length, state = rows_a
-    assert a.sizes()[0] == chain.shape[0] and a.sizes()[1] >= C
+    rows_a = check_resident_histories(ra.ctx, T, root, Q, cfg['root_distn'], masks)
+    state = rows_a[3]
     assert (state >= 64).any() and (state < 64).any()
-    dwell = np.bincount(chain * n + state, weights=length, minlength=C * n).reshape(C, n)
-    np.testing.assert_allclose(a.dwell_times(), dwell, rtol=1e-13)
-    at = np.nonzero(same_edge)[0] + 1
-    trans = np.bincount((chain[at] * n + state[at - 1]) * n + state[at],
-                        minlength=C * n * n).reshape(C, n, n)
-    np.testing.assert_array_equal(a.transition_counts(), trans)
-    # another seed: other histories
-    c = _sampler.DeviceHistoryBatch(T, root, Q, node_masks=masks, root_distn=cfg['root_distn'],
-                                    seed=22, ctx=ra.ctx)
-    c.sweep(5)
-    assert c.rows()[2].shape != length.shape or not np.array_equal(c.rows()[2], length)
-
-    # snapshot / restore: the rejected chains are back at their snapshot, the others moved on
-    def per_chain(rows_):
-        ch = rows_[0]
-        cut = np.searchsorted(ch, np.arange(C + 1))
-        return [tuple(x[cut[k]:cut[k + 1]].tolist() for x in rows_[1:]) for k in range(C)]
-
-    before, ns_before = per_chain(rows_a), a.node_states
-    a.snapshot()
-    a.sweep(1)
-    after, ns_after = per_chain(a.rows()), a.node_states
-    reject = np.arange(C) % 3 == 0
-    a.restore(reject)
-    rows_r = a.rows()
-    consistent(a, rows_r)
-    now, ns_now = per_chain(rows_r), a.node_states
-    moved = 0
-    for k in range(C):
-        assert now[k] == (before[k] if reject[k] else after[k]), k
-        np.testing.assert_array_equal(ns_now[k], ns_before[k] if reject[k] else ns_after[k])
-        moved += before[k] != after[k]
-    assert moved >= C // 2
     # the shapes the constructor takes at 122 states
     with pytest.raises(ValueError):
         _sampler.DeviceHistoryBatch(T, root, Q, node_masks=masks[:, :, 0], ctx=ra.ctx)
