@@ -386,6 +386,23 @@ int rt_prune(rt_model *model, rt_sites *sites);
  * one call: rt_model_recompute_transitions (if recompute_transitions != 0) +
  * rt_prune.                                                                   */
 int rt_step(rt_model *model, rt_sites *sites, int recompute_transitions);
+/* When the results of rt_step exist.  rt_step queues work and returns; two pieces of a step
+ * may still be pending after it: the batch sum (it rides in the next expm launch of the
+ * context) and, for a 49..64-state batch that runs its tree as two root halves, the root
+ * combine that writes the per-site log-likelihoods, the status and the partial sums (it runs
+ * in the idle waves of the next expm launch, the batch sum one launch later).  Nothing changes
+ * for callers: every call that reads or replaces a batch's results, its observations or the
+ * model's root distribution -- the getters, rt_sites_clone, rt_prune, the multi and
+ * partitioned steps, the resident reads, the all-reduce entries, rt_ctx_sync, the destroy
+ * calls -- runs what is pending first, with the stand-alone kernels, and the numbers are the
+ * same bit for bit.  RAOTEH_CARRY_COMBINE=0 (read per call) keeps the combine a launch of
+ * its own right after the pruning kernel; RAOTEH_NO_DEFER_REDUCE keeps both.              */
+/* The rule of the carried combine on the host (no device needed; tests): may an expm launch
+ * of G matrix workgroups carry the root combine of a batch of nt row tiles per site tile and
+ * nblocks16 site tiles?  1 / 0.  With tile_of (int64[4 G]) non-NULL and the answer 1,
+ * tile_of[4 g + k] = the tile that idle wave k of workgroup g finishes, or -1.            */
+int rt_carry_combine_deal(int64_t nt, int64_t nblocks16, int64_t G, int root_halves,
+            int rescale, int partitioned, int multi, int64_t *tile_of);
 /* _mjp_dense.get_expected_history_statistics (_mjp_dense.py:410-539) summed over a RESIDENT
  * batch: (optionally) the per-edge expm from the resident rates, the upward pass, the downward
  * pass (mc0_esd_get_node_to_distn), the per-edge site sums of J / P and one Frechet block

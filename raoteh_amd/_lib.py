@@ -121,6 +121,7 @@ SIGNATURES = {
     'rt_model_schedule_depth': (c_int, [c_void_p]),
     'rt_model_get_schedule': (c_int, [c_void_p, _p_i32, c_int64, _p_i64]),
     'rt_build_schedule': (c_int, [c_int64, _p_i64, _p_i64, _p_i32, _p_i32]),
+    'rt_carry_combine_deal': (c_int, [c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, _p_i64]),
     'rt_set_option': (c_int, [c_char_p, c_int64]),
     'rt_ctx_set_option': (c_int, [c_void_p, c_char_p, c_int64]),
     'rt_sites_jit_compile_seconds': (c_double, [c_void_p]),

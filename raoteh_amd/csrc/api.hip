@@ -85,7 +85,7 @@ extern "C" int rt_ctx_sync(rt_ctx *ctx)
 {
     RT_REQUIRE(ctx, "null context");
     RT_HIP(hipSetDevice(ctx->device));
-    RT_TRY(rt_flush_reduce(ctx));
+    RT_TRY(rt_flush_pending(ctx));
     RT_HIP(hipStreamSynchronize(ctx->stream));
     if (ctx->comm_stream) RT_HIP(hipStreamSynchronize(ctx->comm_stream));
     return RT_OK;
@@ -124,6 +124,7 @@ extern "C" int rt_ctx_destroy(rt_ctx *ctx)
         return RT_ERR_INVALID;
     }
     ctx->pending_reduce = nullptr;
+    ctx->pending_combine = nullptr;
     hipStreamSynchronize(ctx->stream);
     rt_comm_destroy(ctx);
     rt_jit_join_all(ctx);                // no compile thread of this context outlives it
@@ -532,6 +533,7 @@ static int model_run_expm(rt_model *m)
     rt_reduce_args red;
     const bool carry = rt_take_pending_reduce(m->ctx, &red);
     if (m->spectral) {
+        RT_TRY(rt_flush_combine(m->ctx));
         const size_t nn = (size_t)m->n * m->n;
         RT_TRY(rt_launch_spectral(m->ctx, m->n, m->nnodes, m->d_spec, m->d_spec + 2 * nn,
                                   m->d_spec + nn, m->spectral_has_D ? m->d_spec + 2 * nn + m->n
@@ -544,9 +546,21 @@ static int model_run_expm(rt_model *m)
         m->frag_dirty = false;
         return rt_model_pack_pcol(m);
     }
-    RT_TRY(rt_launch_expm(m->ctx, m->n, m->nnodes, m->d_Q, m->d_qidx, m->d_t, m->d_P,
-                          m->d_info, m->d_step_of_node, m->n <= 4 ? 0 : 1, m->d_Pfrag,
-                          carry ? &red : nullptr, m->d_Pquad));
+    // ... and so does the root combine the previous rt_step left pending, in the idle waves of
+    // the eight-wave 49..64-state kernel (any other launch: the stand-alone kernel, now)
+    rt_combine_args comb;
+    rt_sites *carried = nullptr;      // the batch whose combine this launch carries
+    RT_TRY(rt_take_pending_combine(m->ctx, rt_expm_carry_groups(m->ctx, m->n, m->nnodes, carry,
+                                                                m->d_Pquad != nullptr),
+                                   carry ? &red : nullptr, &comb, &carried));
+    // (a combine that ran on its own just now left its batch's reduction pending, after the one
+    // taken above: it stays pending)
+    const int erc = rt_launch_expm(m->ctx, m->n, m->nnodes, m->d_Q, m->d_qidx, m->d_t, m->d_P,
+                                   m->d_info, m->d_step_of_node, m->n <= 4 ? 0 : 1, m->d_Pfrag,
+                                   carry ? &red : nullptr, m->d_Pquad, 0, carried ? &comb : nullptr);
+    // in the stream: the batch's partial sums await their reduction; not launched: pending again
+    if (carried) RT_TRY(rt_carried_combine_done(m->ctx, carried, erc == RT_OK));
+    RT_TRY(erc);
     m->have_P = true;
     m->rates_current = true;
     m->frag_dirty = false;
@@ -874,6 +888,9 @@ extern "C" int rt_model_set_root_distn(rt_model *m, const double *root_distn)
     RT_HIP(hipSetDevice(m->ctx->device));
     std::vector<double> w((size_t)m->n, 1.0);
     if (root_distn) w.assign(root_distn, root_distn + m->n);
+    // a pending root combine reads the weights it was stepped with: it runs now, and the copy
+    // (null stream; the context's stream is non-blocking) waits for it and all before it
+    RT_TRY(rt_flush_pending(m->ctx));
     RT_HIP(hipStreamSynchronize(m->ctx->stream));
     RT_HIP(hipMemcpy(m->d_root, w.data(), m->n * 8, hipMemcpyHostToDevice));
     return RT_OK;
@@ -988,7 +1005,9 @@ extern "C" int rt_sites_destroy(rt_sites *s)
     if (!s) return RT_OK;
     if (s->counted) s->model->live_batches -= 1;
     hipSetDevice(s->model->ctx->device);
+    // (results nobody can read any more: what is pending for this batch is dropped)
     if (s->model->ctx->pending_reduce == s) s->model->ctx->pending_reduce = nullptr;
+    if (s->model->ctx->pending_combine == s) s->model->ctx->pending_combine = nullptr;
     hipStreamSynchronize(s->model->ctx->stream);
     // an all-reduce of this batch's totals may still be in flight on the comm stream
     rt_jit_ref(s->model->ctx, s->jit_fn, -1);
@@ -2183,7 +2202,7 @@ static int sites_lane_switch(rt_sites *s, const std::string &src)
         rc = verify_jit_kernel(s, s->jit_kind);
         rt_jit_set_verified(ctx, fn, rc == RT_OK);
     }
-    if (rc == RT_OK && ctx->pending_reduce == s) rc = rt_flush_reduce(ctx);
+    if (rc == RT_OK) rc = rt_flush_pending_of(ctx, s);
     if (rc == RT_OK) rc = hipStreamSynchronize(ctx->stream) == hipSuccess ? RT_OK : RT_ERR_HIP;
     double *n_obs = nullptr, *n_ll = nullptr, *n_part = nullptr, *n_alt = nullptr;
     int32_t *n_st = nullptr;
@@ -2319,6 +2338,8 @@ int rt_sites_jit_poll(rt_sites *s, bool wait)
     rt_model *m = s->model;
     RT_HIP(hipSetDevice(m->ctx->device));
     if (s->layout == RT_LAYOUT_LANE) return sites_lane_switch(s, srcs[(size_t)chosen]);
+    // what is pending for this batch belongs to the kernel it is about to leave
+    RT_TRY(rt_flush_pending_of(m->ctx, s));
     // (a two-team kernel the probe rejects: on to the one-team form that follows it in the list)
     for (;; ++chosen) {
         const rt_sites::jit_cand &c = cands[(size_t)chosen];
@@ -2327,8 +2348,10 @@ int rt_sites_jit_poll(rt_sites *s, bool wait)
     }
     // the interpreter kernel and the specialised one leave their per-wave partial sums in
     // different places of d_partial: what the other one wrote must read as zero
-    if (m->ctx->pending_reduce == s) RT_TRY(rt_flush_reduce(m->ctx));
+    RT_TRY(rt_flush_pending_of(m->ctx, s));
     RT_HIP(hipMemsetAsync(s->d_partial, 0, (size_t)s->npartials * 16, m->ctx->stream));
+    if (s->d_partial_alt)
+        RT_HIP(hipMemsetAsync(s->d_partial_alt, 0, (size_t)s->npartials * 16, m->ctx->stream));
     return RT_OK;
 }
 
@@ -2355,7 +2378,7 @@ extern "C" int rt_sites_clone(rt_sites *src, rt_sites **out)
     if (src->jit_job && src->layout == RT_LAYOUT_LANE) RT_TRY(rt_sites_jit_poll(src, true));
     // the clone carries the source's results: its batch sum must be reduced first
     rt_ctx *ctx = src->model->ctx;
-    if (ctx->pending_reduce == src) RT_TRY(rt_flush_reduce(ctx));
+    RT_TRY(rt_flush_pending_of(ctx, src));
     rt_sites *s = new (std::nothrow) rt_sites();
     if (!s) return RT_ERR_NOMEM;
     s->model = src->model;
@@ -2552,6 +2575,13 @@ extern "C" int rt_step(rt_model *m, rt_sites *s, int recompute_transitions)
     return rt_launch_prune(m, s, true, fuse);
 }
 
+extern "C" int rt_carry_combine_deal(int64_t nt, int64_t nblocks16, int64_t G, int root_halves,
+                                     int rescale, int partitioned, int multi, int64_t *tile_of)
+{
+    return rt_carry_combine_plan(nt, nblocks16, G, root_halves != 0, rescale != 0, partitioned != 0,
+                                 multi != 0, tile_of) ? 1 : 0;
+}
+
 extern "C" int rt_sites_get_logliks(rt_sites *s, double *loglik, int32_t *status)
 {
     RT_REQUIRE(s, "null pointer");
@@ -2568,6 +2598,8 @@ extern "C" int rt_sites_get_logliks(rt_sites *s, double *loglik, int32_t *status
     RT_REQUIRE(s->pruned, "rt_sites_get_logliks: no pruning kernel has written this batch yet "
                "(rt_prune / rt_step first)");
     RT_HIP(hipSetDevice(s->model->ctx->device));
+    // (a root combine left to the next expm launch writes them: it runs now)
+    RT_TRY(rt_flush_pending_of(s->model->ctx, s));
     RT_HIP(hipStreamSynchronize(s->model->ctx->stream));
     if (loglik)
         RT_HIP(hipMemcpy(loglik, s->d_loglik, s->nsites * 8, hipMemcpyDeviceToHost));
@@ -2581,7 +2613,7 @@ extern "C" int rt_sites_get_totals(rt_sites *s, double totals[3])
     RT_REQUIRE(s && totals, "null pointer");
     if (s->part && s->part->stepped) RT_TRY(partition_ready(s, "rt_sites_get_totals"));
     RT_HIP(hipSetDevice(s->model->ctx->device));
-    RT_TRY(rt_flush_reduce(s->model->ctx));
+    RT_TRY(rt_flush_pending(s->model->ctx));
     RT_HIP(hipStreamSynchronize(s->model->ctx->stream));
     if (s->model->ctx->comm_stream)
         RT_HIP(hipStreamSynchronize(s->model->ctx->comm_stream));
@@ -2749,7 +2781,7 @@ extern "C" int rt_step_multi(rt_model *m, rt_sites *s, int recompute_transitions
     RT_HIP(hipSetDevice(ctx->device));
     if (s->jit_job) RT_TRY(rt_sites_jit_poll(s, false));
     // nothing of this call is deferred, and what was is reduced now
-    RT_TRY(rt_flush_reduce(ctx));
+    RT_TRY(rt_flush_pending(ctx));
     if (recompute_transitions) RT_TRY(rate_sets_run_expm(m));
     else RT_TRY(rate_sets_pack_pcol(m, false));      // (a leaf-state batch created since)
     const int64_t K = r.K;
@@ -3011,7 +3043,7 @@ extern "C" int rt_step_partitioned(rt_model *m, rt_sites *s, int recompute_trans
     rt_ctx *ctx = m->ctx;
     RT_HIP(hipSetDevice(ctx->device));
     // nothing of this call is deferred, and what was is reduced now
-    RT_TRY(rt_flush_reduce(ctx));
+    RT_TRY(rt_flush_pending(ctx));
     if (recompute_transitions) RT_TRY(rate_sets_run_expm(m));
     else RT_TRY(rate_sets_pack_pcol(m, false));      // (a leaf-state batch created since)
     p->stepped = false;

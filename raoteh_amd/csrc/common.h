@@ -139,6 +139,11 @@ struct rt_ctx {
     // launch-latency-sized kernels were a quarter of the step); every reader of the
     // totals, rt_prune, rt_ctx_sync and the destructors flush it (rt_flush_reduce).
     struct rt_sites *pending_reduce = nullptr;
+    // The root-halves batch whose combine has not run yet: rt_step leaves it to the next expm
+    // launch of this context, whose waves 4..7 idle until the first barrier (expm.hip).  Its
+    // per-site results and partial sums exist after that launch, so its reduction rides one
+    // launch later still.  rt_flush_pending runs both now.
+    struct rt_sites *pending_combine = nullptr;
     size_t expm_attr_lds = 0;      // dynamic-LDS attribute already granted to expm_kernel
     size_t expm_ts_attr_lds[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ... to the Taylor kernels (per NT)
     size_t expm_split_attr_lds = 0;                           // ... to the two-workgroup form
@@ -421,6 +426,47 @@ struct rt_reduce_args {
     double *totals = nullptr;          // [3]
     double nsites = 0.0;
 };
+// The root combine of a root-halves batch that the eight-wave 49..64-state expm launch may carry
+// in its waves 4..7, which idle until the first barrier (halfbuf == nullptr: none).  The
+// arguments of prune_mfma_combine_kernel / rt_jit_combine, plus the batch's layout of partial
+// sums: wave_slots entries per tile (4: the interpreter's, 1: the tree-specialised kernels').
+struct rt_combine_args {
+    const double *halfbuf = nullptr;   // [tile][half][k-step][lane]
+    const double *obs = nullptr;       // [tile][K][KP][64][2]
+    int K = 0, KP = 0, kroot = -1;     // kroot: stream position of the root's observation, or -1
+    const double *root_w = nullptr;
+    int n = 0;
+    double *loglik = nullptr;
+    int *status = nullptr;
+    double *partial = nullptr;
+    long nsites = 0, nblocks16 = 0;
+    int wave_slots = 1;
+};
+// How a carrying launch of G matrix workgroups deals the tiles: idle wave k (0..3) of workgroup
+// wg finishes tile wg + k G -- one round, so a batch of more than 4 G tiles is not carried.
+// -> the tile, or -1 (no tile for this wave)
+__host__ __device__ inline long rt_carry_tile(long wg, int k, long G, long nblocks16)
+{
+    const long t = wg + (long)k * G;
+    return t < nblocks16 ? t : -1;
+}
+// The whole rule, for the host (and exported as rt_carry_combine_deal for the tests): may a
+// launch of G matrix workgroups carry the combine of a batch of nt row tiles per site tile and
+// nblocks16 site tiles?  Only NT = 4 root halves, plain (no rescaling, no partition, no rate-set
+// axis), all tiles in one round.  With tile_of (4 G entries) non-null: tile_of[4 wg + k].
+inline bool rt_carry_combine_plan(int64_t nt, int64_t nblocks16, int64_t G, bool halves, bool rescale,
+                                  bool partitioned, bool multi, int64_t *tile_of = nullptr)
+{
+    const bool ok = nt == 4 && halves && !rescale && !partitioned && !multi && G >= 1 &&
+                    nblocks16 >= 1 && nblocks16 <= 4 * G;
+    if (ok && tile_of)
+        for (int64_t wg = 0; wg < G; ++wg)
+            for (int k = 0; k < 4; ++k) tile_of[4 * wg + k] = rt_carry_tile((long)wg, k, (long)G, (long)nblocks16);
+    return ok;
+}
+// expm.hip: the number of matrix workgroups G of the launch rt_launch_expm would make for these
+// arguments if that launch is of the carrying kernel (eight waves, 49..64 states), else 0
+int64_t rt_expm_carry_groups(rt_ctx *ctx, int64_t n, int64_t count, bool with_reduce, bool quad);
 // expm_wide.hip: the LDS-resident Taylor kernel for 64 < n <= 128 (scratch: ctx->d_expm_scratch)
 int rt_expm_wide_launch(rt_ctx *ctx, int nt, bool split2, size_t grid, int64_t n, const double *d_Q,
                         const int *d_qidx, const double *d_t, double *d_P, int *d_info,
@@ -433,7 +479,8 @@ int rt_launch_expm(rt_ctx *ctx, int64_t n, int64_t count, const double *d_Q,
                    const int32_t *d_qidx, const double *d_t, double *d_P,
                    int32_t *d_info, const int32_t *d_step_of_node, int frag_kind,
                    double *d_Pfrag, const rt_reduce_args *fused_reduce = nullptr,
-                   double *d_Pquad = nullptr, int64_t variant_count = 0);
+                   double *d_Pquad = nullptr, int64_t variant_count = 0,
+                   const rt_combine_args *carried_combine = nullptr);
 // spectral.hip: P_e = A diag(exp(lam t_e)) B per edge, outputs as rt_launch_expm's
 int rt_launch_spectral(rt_ctx *ctx, int64_t n, int64_t count, const double *d_A,
                        const double *d_lam, const double *d_B, const double *d_D,
@@ -444,6 +491,21 @@ int rt_launch_spectral(rt_ctx *ctx, int64_t n, int64_t count, const double *d_A,
 bool rt_take_pending_reduce(rt_ctx *ctx, rt_reduce_args *out);
 // ... or launched on its own now (no-op when nothing is pending)
 int rt_flush_reduce(rt_ctx *ctx);
+// The pending combine, handed to an expm launch of G matrix workgroups that also carries the
+// reduction *red (partial == nullptr: none) -> true; false: not this launch (nothing pending,
+// too many tiles for G, RAOTEH_CARRY_COMBINE=0), and then it has been launched on its own.
+// *taken: the batch (the caller launches, then calls rt_carried_combine_done with it), or null.
+int rt_take_pending_combine(rt_ctx *ctx, int64_t G, const rt_reduce_args *red, rt_combine_args *out,
+                            struct rt_sites **taken);
+int rt_carried_combine_done(rt_ctx *ctx, struct rt_sites *s, bool launched);
+// the pending combine launched on its own now; its batch's reduction becomes the pending one
+int rt_flush_combine(rt_ctx *ctx);
+// Everything pending, with the stand-alone kernels: the combine, then the reduction.  Whoever
+// reads or replaces the per-site results, the partial sums, the totals or the half buffer of a
+// batch, or what a pending combine reads (root distribution, observations), calls this first.
+int rt_flush_pending(rt_ctx *ctx);
+// ... if any of it belongs to batch s
+int rt_flush_pending_of(rt_ctx *ctx, const struct rt_sites *s);
 // A timed launch: the runtime stamps the two events with the kernel's own begin and
 // end (what rocprofv3's kernel trace reports), not with the stream position of an
 // event record, which adds 2-3 us per pair.  Null events: a plain launch.
@@ -473,6 +535,9 @@ struct rt_prune_view {
     // batch reads those of set granule_set[g], the per-set strides (doubles) further on
     const int32_t *granule_set = nullptr;
     int64_t frag_stride = 0, pcol_stride = 0;
+    // rt_step on a root-halves batch whose combine the next expm launch can carry: the launcher
+    // records the batch as rt_ctx::pending_combine instead of launching the combine kernel
+    bool defer_combine = false;
 };
 // prune.hip: sites per granule of the lane family's VGPR-ring kernel on this model's tree (the
 // workgroup's span: 256 with the transition table staged in LDS, else 64)

@@ -2642,6 +2642,9 @@ int rt_launch_prune_jit(rt_model *m, rt_sites *s, const rt_fuse_args *fuse, cons
             return RT_OK;
         }
         void *cargs[] = {&chalf, &obs, &root_w, &loglik, &status, &partial, &nsites, &nblocks};
+        // rt_step: the combine is left to the next expm launch of the context (prune.hip)
+        const bool defer = v.defer_combine;
+        if (defer) m->ctx->pending_combine = s;
         // (teams: eight waves per pruning workgroup; the combine kernel keeps its four)
         const unsigned ctpb = 64u * (unsigned)s->jit_waves;
         const unsigned tpb = ctpb * (s->jit_teams ? 2u : 1u);
@@ -2649,18 +2652,20 @@ int rt_launch_prune_jit(rt_model *m, rt_sites *s, const rt_fuse_args *fuse, cons
         const unsigned groups = (unsigned)((s->nblocks + s->jit_tiles - 1) / s->jit_tiles);
         if (m->ctx->ev_start) {
             hipEvent_t ca = nullptr, cb = nullptr;
-            rt_time_extra_begin(m->ctx, RT_K_COMBINE, "rt_jit_combine", &ca, &cb);
+            if (!defer) rt_time_extra_begin(m->ctx, RT_K_COMBINE, "rt_jit_combine", &ca, &cb);
             RT_HIP(hipExtModuleLaunchKernel((hipFunction_t)s->jit_fn, 2u * groups * tpb, 1, 1, tpb, 1, 1,
                                             0, m->ctx->stream, hargs, nullptr, m->ctx->ev_start,
                                             m->ctx->ev_stop, 0));
-            RT_HIP(hipExtModuleLaunchKernel((hipFunction_t)s->jit_combine, tiles * ctpb, 1, 1, ctpb, 1, 1,
-                                            0, m->ctx->stream, cargs, nullptr, ca, cb, 0));
+            if (!defer)
+                RT_HIP(hipExtModuleLaunchKernel((hipFunction_t)s->jit_combine, tiles * ctpb, 1, 1, ctpb, 1,
+                                                1, 0, m->ctx->stream, cargs, nullptr, ca, cb, 0));
             rt_time_extra_end(m->ctx, RT_K_COMBINE, ca, cb);
         } else {
             RT_HIP(hipModuleLaunchKernel((hipFunction_t)s->jit_fn, 2u * groups, 1, 1, tpb, 1, 1, 0,
                                          m->ctx->stream, hargs, nullptr));
-            RT_HIP(hipModuleLaunchKernel((hipFunction_t)s->jit_combine, tiles, 1, 1, ctpb, 1, 1, 0,
-                                         m->ctx->stream, cargs, nullptr));
+            if (!defer)
+                RT_HIP(hipModuleLaunchKernel((hipFunction_t)s->jit_combine, tiles, 1, 1, ctpb, 1, 1, 0,
+                                             m->ctx->stream, cargs, nullptr));
         }
         return RT_OK;
     }

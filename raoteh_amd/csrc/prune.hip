@@ -50,40 +50,8 @@ __device__ __forceinline__ rt_op load_op(const RT_CONST_AS int4_t *ops, int i)
     return op;
 }
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// escale: the site's messages were multiplied by 2^-escale on the way up (opt-in rescaling:
-// exact powers of two, so the mantissa of the likelihood is what it would have been)
-__device__ __forceinline__ void finish_site(double lik, bool negative,
-                                            bool valid, double *loglik,
-                                            int *status, long site,
-                                            double &sum, double &nzero, int escale = 0)
-{
-    const bool ok = lik > 0.0;
-    if (valid) {
-        double ll = ok ? log(lik) : -INFINITY;
-        if (ok && escale != 0) {
-            // in range: undo the scaling exactly and take the logarithm of the true value;
-            // out of range: log(m 2^e) = log(m) + e ln 2
-            const double back = ldexp(lik, escale);
-            ll = (back > 0x1p-1000 && back < 0x1p1000) ? log(back)
-                                                       : log(lik) + (double)escale * 0.6931471805599453094;
-        }
-        loglik[site] = ll;
-        status[site] = (ok ? RT_SITE_OK : RT_SITE_ZERO_PROB) |
-                       (negative ? RT_SITE_NEGATIVE : 0);
-        sum = ok ? ll : 0.0;
-        nzero = ok ? 0.0 : 1.0;
-    } else {
-        sum = 0.0;
-        nzero = 0.0;
-    }
-}
+// (wave_sum, finish_site: site_epilogue.h, shared with the carried combine of expm.hip)
+#include "site_epilogue.h"
 
 // Opt-in rescaling ("rescale", interpreter kernels): when the largest entry of a site's
 // message drops below 2^-256 the message is multiplied by the power of two that brings it
@@ -1471,6 +1439,10 @@ static int launch_mfma_inst(rt_model *m, rt_sites *s, const rt_prune_view &v)
                            s->d_obs, (int)s->nobs, m->d_root, (int)m->n, lds_slots,
                            v.loglik, v.status, v.partial, (long)s->nsites,
                            (long)s->nblocks, s->d_Lout, s->d_Mout, hv, 0, ilw, ipc, ism);
+        if (v.defer_combine) {               // (rt_step: the next expm launch carries it)
+            m->ctx->pending_combine = s;
+            return RT_OK;
+        }
         hipEvent_t ca = nullptr, cb = nullptr;
         rt_time_extra_begin(m->ctx, RT_K_COMBINE, "prune_mfma_combine", &ca, &cb);
         auto ckern = prune_mfma_combine_kernel<NT>;
@@ -1619,6 +1591,139 @@ int rt_flush_reduce(rt_ctx *ctx)
     return RT_OK;
 }
 
+// ---- the pending root combine (common.h: rt_ctx::pending_combine) ----------------------------
+
+static bool carry_combine_enabled()
+{
+    const char *v = getenv("RAOTEH_CARRY_COMBINE");
+    return !(v && v[0] && atoi(v) == 0);
+}
+
+// a tree-specialised halves kernel with its second kernel, or the interpreter's root halves
+static bool batch_runs_halves(const rt_sites *s)
+{
+    if (s->layout != RT_LAYOUT_MFMA || s->d_scratch || s->mfma_solo) return false;
+    if (s->jit_fn) return s->jit_halves && !s->jit_fold && s->jit_combine;
+    return s->interp_halves && !s->d_Lout;
+}
+
+// May this rt_step launch of batch s leave its combine to the model's next expm launch?  (That
+// launch, as far as it can be told now: if another model's launch comes first and cannot carry
+// the batch, rt_take_pending_combine runs the stand-alone kernel then.)
+static bool want_deferred_combine(rt_model *m, const rt_sites *s)
+{
+    if (!carry_combine_enabled() || getenv("RAOTEH_NO_DEFER_REDUCE") || m->spectral || !m->d_Q) return false;
+    const int64_t G = rt_expm_carry_groups(m->ctx, m->n, m->nnodes, true, m->d_Pquad != nullptr);
+    return rt_carry_combine_plan(nt_of(m->n), s->nblocks, G, batch_runs_halves(s), s->rescale, s->part != nullptr,
+                                 false);
+}
+
+static void combine_args_of(const rt_sites *s, rt_combine_args *c)
+{
+    const rt_model *m = s->model;
+    const bool jit = s->jit_fn != nullptr;
+    c->halfbuf = s->d_half;
+    c->obs = (const double *)s->d_obs;
+    c->K = (int)s->nobs;
+    c->KP = (ks_of(m->n) + 1) / 2;
+    c->kroot = jit ? s->ops.back().obs : s->half_kroot;
+    c->root_w = m->d_root;
+    c->n = (int)m->n;
+    c->loglik = s->d_loglik;
+    c->status = s->d_status;
+    c->partial = s->d_partial;
+    c->nsites = (long)s->nsites;
+    c->nblocks16 = (long)s->nblocks;
+    c->wave_slots = jit ? 1 : 4;
+}
+
+int rt_flush_combine(rt_ctx *ctx)
+{
+    rt_sites *s = ctx->pending_combine;
+    if (!s) return RT_OK;
+    ctx->pending_combine = nullptr;
+    // the kernel rewrites the batch's partial sums: a reduction of the SAME batch still pending
+    // (the step before) is superseded; another batch's runs now (there is one slot)
+    if (ctx->pending_reduce == s) ctx->pending_reduce = nullptr;
+    else RT_TRY(rt_flush_reduce(ctx));
+    rt_combine_args c;
+    combine_args_of(s, &c);
+    hipEvent_t ev = nullptr;
+    if (s->jit_fn) {
+        rt_time_begin(ctx, RT_K_COMBINE, "rt_jit_combine", &ev);
+        void *cargs[] = {&c.halfbuf, &c.obs, &c.root_w, &c.loglik, &c.status, &c.partial, &c.nsites,
+                         &c.nblocks16};
+        const unsigned ctpb = 64u * (unsigned)s->jit_waves, tiles = (unsigned)s->nblocks;
+        if (ctx->ev_start)
+            RT_HIP(hipExtModuleLaunchKernel((hipFunction_t)s->jit_combine, tiles * ctpb, 1, 1, ctpb, 1, 1, 0,
+                                            ctx->stream, cargs, nullptr, ctx->ev_start, ctx->ev_stop, 0));
+        else
+            RT_HIP(hipModuleLaunchKernel((hipFunction_t)s->jit_combine, tiles, 1, 1, ctpb, 1, 1, 0,
+                                         ctx->stream, cargs, nullptr));
+    } else {
+        rt_time_begin(ctx, RT_K_COMBINE, "prune_mfma_combine", &ev);
+        RT_LAUNCH_TIMED(ctx, prune_mfma_combine_kernel<4>, dim3((unsigned)s->nblocks), dim3(256), 0,
+                        c.halfbuf, c.obs, c.K, c.KP, c.kroot, c.root_w, c.n, c.loglik, c.status, c.partial,
+                        c.nsites, c.nblocks16);
+    }
+    RT_HIP(hipGetLastError());
+    rt_time_end(ctx, RT_K_COMBINE, ev);
+    ctx->pending_reduce = s;
+    return RT_OK;
+}
+
+int rt_flush_pending(rt_ctx *ctx)
+{
+    RT_TRY(rt_flush_combine(ctx));
+    return rt_flush_reduce(ctx);
+}
+
+int rt_take_pending_combine(rt_ctx *ctx, int64_t G, const rt_reduce_args *red, rt_combine_args *out,
+                            rt_sites **taken)
+{
+    *taken = nullptr;
+    rt_sites *s = ctx->pending_combine;
+    if (!s) return RT_OK;
+    if (!carry_combine_enabled() ||
+        !rt_carry_combine_plan(nt_of(s->model->n), s->nblocks, G, batch_runs_halves(s), s->rescale,
+                               s->part != nullptr, false))
+        return rt_flush_combine(ctx);
+    // The launch may also carry the reduction of this batch's previous step (one batch stepped
+    // again and again): that workgroup reads the partial sums this launch's waves rewrite, so
+    // the combine writes the batch's other buffer and the two change places.
+    if (red && red->partial && red->partial == s->d_partial) {
+        if (!s->d_partial_alt) {
+            RT_HIP(hipMalloc((void **)&s->d_partial_alt, s->npartials * 16));
+            RT_HIP(hipMemsetAsync(s->d_partial_alt, 0, s->npartials * 16, ctx->stream));
+        }
+        std::swap(s->d_partial, s->d_partial_alt);
+    }
+    combine_args_of(s, out);
+    ctx->pending_combine = nullptr;
+    *taken = s;
+    return RT_OK;
+}
+
+// launched: the carrying launch is in the stream and the batch's partial sums await their
+// reduction; else the combine is pending as before
+int rt_carried_combine_done(rt_ctx *ctx, rt_sites *s, bool launched)
+{
+    if (!launched) {
+        ctx->pending_combine = s;
+        return RT_OK;
+    }
+    // (a reduction the launch could not take is still pending: there is one slot)
+    if (ctx->pending_reduce && ctx->pending_reduce != s) RT_TRY(rt_flush_reduce(ctx));
+    ctx->pending_reduce = s;
+    return RT_OK;
+}
+
+int rt_flush_pending_of(rt_ctx *ctx, const rt_sites *s)
+{
+    if (ctx->pending_combine == s || ctx->pending_reduce == s) return rt_flush_pending(ctx);
+    return RT_OK;
+}
+
 int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm,
                     const rt_prune_view *view)
 {
@@ -1626,6 +1731,7 @@ int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm,
     const char *name = "";
     hipEvent_t ev = nullptr;
     rt_fuse_args fuse;
+    bool defer_combine = false;
     // the model's tables and the batch's outputs unless the caller brought others
     rt_prune_view v;
     if (view) {
@@ -1645,6 +1751,7 @@ int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm,
         // partial sums of ITS batch while this launch writes its own: if it is this batch,
         // the two must be different buffers
         fuse.expm = true;
+        RT_TRY(rt_flush_combine(ctx));
         if (!rt_take_pending_reduce(ctx, &fuse.red) && ctx->pending_reduce) RT_TRY(rt_flush_reduce(ctx));
         std::swap(s->d_partial, s->d_partial_alt);
         m->have_P = true;
@@ -1654,7 +1761,11 @@ int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm,
         fuse_expm = false;
         // a reduction still pending reads d_partial of ITS batch: if that is this batch, it
         // must run before the pruning kernel overwrites the partial sums
-        if (ctx->pending_reduce) RT_TRY(rt_flush_reduce(ctx));
+        // (a root-halves launch of rt_step that leaves its combine pending writes no partial
+        // sums itself: a pending reduction stays pending -- the next expm launch carries it)
+        defer_combine = defer_reduce && !view && want_deferred_combine(m, s);
+        RT_TRY(rt_flush_combine(ctx));       // (it reads the half buffer this launch may rewrite)
+        if (!defer_combine) RT_TRY(rt_flush_reduce(ctx));
     }
     // which family this batch was packed for
     const bool generic = s->d_scratch != nullptr;
@@ -1665,6 +1776,7 @@ int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm,
     char *jit_name = s->kernel_name;
     RT_REQUIRE(!v.granule_set || (!generic && !s->jit_fn && !s->lane_dma),
                "a partitioned batch runs the interpreter kernels with the per-granule lookup only");
+    v.defer_combine = defer_combine;
     if (generic) rc = launch_generic(m, s, v, &name);
     else if (s->jit_fn) {
         rc = rt_launch_prune_jit(m, s, s->jit_fused ? &fuse : nullptr, &v);
@@ -1704,6 +1816,9 @@ int rt_launch_prune(rt_model *m, rt_sites *s, bool defer_reduce, bool fuse_expm,
     rt_time_end(ctx, RT_K_PRUNE, ev);
     if (view) return RT_OK;          // (the caller reduces its own partial sums)
 
+    // the combine left to the next expm launch: the partial sums do not exist yet
+    if (ctx->pending_combine == s) return RT_OK;
+    if (ctx->pending_reduce && ctx->pending_reduce != s) RT_TRY(rt_flush_reduce(ctx));   // (one slot)
     ctx->pending_reduce = s;
     // deferred (rt_step): the reduction rides on the next expm launch of this context
     if (defer_reduce && !getenv("RAOTEH_NO_DEFER_REDUCE")) return RT_OK;
